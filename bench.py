@@ -2,6 +2,7 @@
 """Headline benchmark: edges aggregated per second (+ achieved HBM GB/s) of a 2-layer GCN forward.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload s100m|s100m-rmat|reddit|cora]
+                    [--full] [--dump-outputs DIR]
 
 A "step" is one 2-layer forward over one synthetic graph already resident in HBM:
     layer 1:  D1 = relu(A . (X . W1))    X sparse CSR (gemm_mode 0), F_in -> hidden
@@ -20,6 +21,12 @@ the other partitions, the rest stay inside it -- the shape a graph partitioner l
 is exactly the single-GPU graph).  Per layer the rows of H = X.W that other partitions reference are exchanged
 over xGMI (RCCL all-to-all of halo rows; --exchange allgather / --cut 1.0 = every row) and
 aggregated locally (sgracex1_amd/dist.py).
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, and the roofline of the
+aggregation launches, timed by events inside the steps).  --full adds what takes runs of its own: the device's
+stream-copy rate, the R-MAT leg (`roofline_rmat`), the CPU baselines (`cpu_baseline`) and, for N > 1, the exchanges
+timed alone (`exchange`, `exchange_allgather`).  --dump-outputs DIR writes what the last timed step computed (a fixed,
+seeded row sample of both layers' outputs) as DIR/<name>.npy; the inputs are seeded, so two builds compare row for row.
 """
 import argparse
 import json
@@ -47,7 +54,13 @@ def parse():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="s100m", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need: the device's stream-copy rate, the R-MAT "
+                         "leg, the CPU baselines and, for N > 1, the exchanges timed alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write a fixed, seeded row sample of the last step's layer outputs "
+                         "as DIR/<name>.npy (float32, under 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
     ap.add_argument("--exact", action="store_true",
                     help="N = 1: run both layers in SGX_ACC_REF_HALF with SPMM_BLOCK 4 -- the reference's half arithmetic, "
                          "bit for bit (the setting that reproduces its csim log)")
@@ -62,14 +75,17 @@ def parse():
                     help="N > 1: rows of H exchanged per layer (default: halo-overlap = halo rows travel while the "
                          "own-partition edges are aggregated; allgather when --cut >= 0.5)")
     ap.add_argument("--no-rmat-leg", action="store_true",
-                    help="N = 1, workload s100m: skip the power-law (R-MAT) variant of the aggregation launch that is timed "
+                    help="--full, N = 1, workload s100m: skip the power-law (R-MAT) variant of the aggregation launch that is timed "
                          "after the step and reported as roofline_rmat (outside `value`)")
     ap.add_argument("--rank-timeout", type=float, default=1500.0,
                     help="--gpus N > 1 started without torch.distributed.run: seconds the ranks get before the parent ends "
                          "them and prints an error line")
     ap.add_argument("--traffic-file", default=os.path.join(ROOT, "profiles", "traffic_latest.json"),
                     help="rocprofv3 --pmc result for the dominant kernel (HBM bytes per launch)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    return args
 
 
 def make_inputs(torch, graphs, ops, wl, rank, world, device, cut=1.0, boundary=1.0):
@@ -307,6 +323,25 @@ def device_identity(torch, device):
         if v is not None:
             parts.append(f"{attr}={v}")
     return " ".join(str(x) for x in parts)
+
+
+DUMP_BYTES = 48 << 20          # --dump-outputs: all ranks' files together, rows.npy aside (the limit is 64 MB)
+
+
+def dump_outputs(torch, outdir, outputs, rank, world):
+    """--dump-outputs: the same rows of every output of the last timed step as float32 DIR/<name>.npy, plus the row ids
+    as DIR/rows.npy (float64).  The rows are drawn with a fixed seed (without replacement, ascending), so two runs or two
+    builds compare row for row.  N > 1: every rank writes its own partition's rows, its names suffixed with the rank."""
+    import numpy as np
+    n, width = next(iter(outputs.values())).shape
+    n_rows = min(n, DUMP_BYTES // (world * len(outputs) * width * 4))
+    rows = np.sort(np.random.default_rng(20241015).choice(n, size=n_rows, replace=False))
+    idx = torch.as_tensor(rows, device=next(iter(outputs.values())).device)
+    suffix = f"_rank{rank}" if world > 1 else ""
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, f"rows{suffix}.npy"), rows.astype(np.float64))
+    for name, t in outputs.items():
+        np.save(os.path.join(outdir, f"{name}{suffix}.npy"), t.index_select(0, idx).float().cpu().numpy())
 
 
 _WHERE = ["start"]
@@ -593,6 +628,8 @@ def run(args):
     barrier()
     elapsed = time.perf_counter() - t0
     note(f"timed steps done: {elapsed:.3f} s")
+    if args.dump_outputs:
+        dump_outputs(torch, args.dump_outputs, {"layer1_out": D1, "layer2_out": D2}, rank, world)
     if world > 1:
         red_dev = device if dist.get_backend() == "nccl" else "cpu"
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=red_dev)
@@ -608,7 +645,7 @@ def run(args):
     # same collective on the same row lists, 5 rounds between barriers, slowest rank
     exchange_stats = None
     allgather_stats = None
-    if world > 1:
+    if world > 1 and args.full:
         row_bytes = hidden * 2
 
         def time_alone(fn, rounds=5):
@@ -689,7 +726,7 @@ def run(args):
 
     # the roof a plain copy reaches on this very device (SURVEY 8d asks for it next to the nominal 8 TB/s)
     copy_gbps = None
-    if rank == 0:
+    if rank == 0 and args.full:
         src = torch.empty(1 << 29, dtype=torch.float16, device=device)     # 1 GiB read + 1 GiB written
         dst = torch.empty_like(src)
         from sgracex1_amd._lib import check, lib
@@ -740,10 +777,10 @@ def run(args):
     if exchange_stats is not None:
         line["exchange"] = exchange_stats
         line["exchange_allgather"] = allgather_stats
-    if world == 1 and args.workload == "s100m" and not args.no_rmat_leg and not args.exact:
+    if args.full and world == 1 and args.workload == "s100m" and not args.no_rmat_leg and not args.exact:
         note("power-law leg")
         line["roofline_rmat"] = rmat_leg(torch, graphs, ops, Event, wl, device, stream, max(5, min(args.steps, 20)), 3)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(torch, ops, A, X, W1t, W2t, args.cpu_sample_frac)
         line["cpu_baseline"]["reference_formulation"] = cpu_reference_formulation(torch, ops, A, X, W1t, W2t,
                                                                                   min(args.cpu_sample_frac, 0.125))

@@ -107,7 +107,7 @@ def test_bench_multi_rank_path_rehearsal(extra, expect):
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                           "--master-addr", "127.0.0.1", "--master-port", str(29900 + os.getpid() % 80 + len(expect) % 17),
                           os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                          "--workload", "small"] + extra, env=env, capture_output=True, text=True, timeout=600)
+                          "--workload", "small", "--full"] + extra, env=env, capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     import json
     line = [ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1]
@@ -141,7 +141,7 @@ def test_bench_starts_its_own_ranks():
     with tempfile.TemporaryDirectory() as tmp:
         env["SGX_BENCH_PARENT_REPORT"] = os.path.join(tmp, "parent.json")
         out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                              "--workload", "small"], env=env, capture_output=True, text=True, timeout=900)
+                              "--workload", "small", "--full"], env=env, capture_output=True, text=True, timeout=900)
         rep = json.load(open(env["SGX_BENCH_PARENT_REPORT"]))
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.strip()]
@@ -167,12 +167,52 @@ def test_bench_falls_back_to_the_one_pass_halo_exchange():
     assert rec["exchange_fallback"] is True                     # in the line, not only on stderr
 
 
+def test_bench_plain_run_line_and_dumped_outputs(tmp_path):
+    """`python bench.py --dump-outputs DIR` (N = 1, no --full) on the small workload: the headline line without the
+    measurements that take runs of their own, and the last step's layer outputs on disk.  The small graph fits the
+    sample, so every row is written; the inputs, regenerated here from the same seeds in this process, give both
+    layers back on the host."""
+    import json
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    rec = json.loads(lines[0])
+    assert rec["steps"] == 3 and rec["unit"] == "edges/s" and rec["higher_is_better"] is True
+    assert rec["dtype"] == "f16 (f32 accumulate)" and rec["metric"] == "edges aggregated/sec, 2-layer GCN forward"
+    assert abs(rec["value"] - 2.0 * rec["config"]["edges_per_gpu"] / (rec["ms_per_step"] * 1e-3)) < 1e-6 * rec["value"]
+    assert rec["roofline"]["launches_timed"] == 6 and rec["roofline"]["stream_copy_GBps_this_device"] is None
+    assert rec["cpu_baseline"] is None and "roofline_rmat" not in rec
+
+    import bench
+    from sgracex1_amd import graphs, ops
+    files = sorted(os.listdir(tmp_path))
+    assert files == ["layer1_out.npy", "layer2_out.npy", "rows.npy"]
+    assert sum(os.path.getsize(tmp_path / f) for f in files) <= 64 << 20
+    n, hidden = bench.WORKLOADS["small"]["n"], bench.WORKLOADS["small"]["hidden"]
+    rows = np.load(tmp_path / "rows.npy")
+    d1, d2 = np.load(tmp_path / "layer1_out.npy"), np.load(tmp_path / "layer2_out.npy")
+    assert rows.dtype == np.float64 and np.array_equal(rows, np.arange(n))
+    assert d1.dtype == d2.dtype == np.float32 and d1.shape == d2.shape == (n, hidden)
+    A, X, W1t, W2t = bench.make_inputs(torch, graphs, ops, bench.WORKLOADS["small"], 0, 1, torch.device("cuda:0"))
+
+    def host(m):
+        return torch.sparse_csr_tensor(m.rowptr.cpu().long(), m.col[:m.nnz].cpu().long(), m.val[:m.nnz].cpu().double(),
+                                       size=(m.n_rows, m.n_cols))
+    A_h, X_h = host(A), host(X)
+    want1 = torch.relu(A_h @ (X_h @ W1t.cpu().double().t())).numpy()
+    want2 = (A_h @ (torch.from_numpy(d1).double() @ W2t.cpu().double().t())).numpy()
+    np.testing.assert_allclose(d1, want1, rtol=1e-2, atol=2e-3)
+    np.testing.assert_allclose(d2, want2, rtol=1e-2, atol=2e-3)
+
+
 def test_bench_single_gpu_line_has_the_contract_fields():
-    """`python bench.py` (N = 1) on the small workload: one JSON line with the driver's fields, the
+    """`python bench.py --full` (N = 1) on the small workload: one JSON line with the driver's fields, the
     roofline object timed on the launch stream, and the CPU baseline from the oracle port."""
     import json
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--workload", "small", "--steps", "4",
-                          "--warmup", "1"], capture_output=True, text=True, timeout=600)
+                          "--warmup", "1", "--full"], capture_output=True, text=True, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     lines = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1

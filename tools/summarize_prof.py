@@ -34,8 +34,8 @@ def counter(rows, kernel_sub, name):
 
 def agg_kernels(wl):
     """the A.H launch of a workload in a trace: the plain kernel on the uniform graph; under a degree-ordered plan
-    (power-law graphs) the kernel with the one-step tail.  (The default bench line also times the R-MAT leg, so a
-    trace of the s100m workload holds both; each summary takes its own.)"""
+    (power-law graphs) the kernel with the one-step tail.  (A --full bench line also times the R-MAT leg, so a
+    trace of it on the s100m workload holds both; each summary takes its own.)"""
     return ("spmm_short_tail_kernel",) if "rmat" in wl else ("11spmm_kernelI",)
 
 
