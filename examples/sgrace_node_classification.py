@@ -5,6 +5,7 @@ synthetic planted-partition graph because the demo's datasets (Planetoid Cora, A
 downloaded by torch_geometric and are not available offline.
 
     python examples/sgrace_node_classification.py [--attention] [--qbits 8] [--epochs 60] [--acc 0]
+                                                  [--batch-size 128 --num-neighbors 10,10]
 
 --attention  GAT edge softmax instead of the GCN aggregate (config.compute_attention)
 --qbits B    run the layers with the quantised arithmetic of the SGRACE bitstream (config.fake_quantization and
@@ -12,6 +13,10 @@ downloaded by torch_geometric and are not available offline.
              cores for the dense-feature layer when it is wider than 128 columns -- --hidden 256 makes layer 2 such a layer)
 --emulate    with --qbits: config.fake_quantization only (the fp32 emulation of the grid everywhere)
 --acc 0      the reference's dense torch emulation instead of the kernels (small graphs only)
+--batch-size B --num-neighbors K1[,K2..]
+             the demo's mini-batch mode (demo_sgrace.py:112-125, full_graph = 0): every epoch trains on
+             pyg_lite.NeighborLoader batches of B training nodes with K1 sampled neighbours per node at hop 1, K2 at
+             hop 2 ..., sampled on the GPU; evaluation stays on the full graph
 """
 import argparse
 import os
@@ -40,7 +45,8 @@ def planted_partition(n, classes, f_in, p_in, p_out, seed, device):
     return x.to(device), edge_index.to(device), y.to(device)
 
 
-def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, verbose=True, emulate=False):
+def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, verbose=True, emulate=False,
+        batch_size=None, num_neighbors=None):
     from sgracex1_amd import config, sgrace
     config.acc = acc
     config.compute_attention = int(attention)
@@ -58,13 +64,31 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
     model = sgrace.GAT_PYNQ(x.shape[1], hidden, 1, 5).to(device)
     opt = torch.optim.Adam(model.parameters(), lr=0.01, weight_decay=5e-4)
     crit = torch.nn.CrossEntropyLoss()
+    loader = None
+    if batch_size:
+        from sgracex1_amd import pyg_lite
+        train_mask = torch.zeros(n, dtype=torch.bool, device=device)
+        train_mask[train] = True
+        data = pyg_lite.NodeData(x, edge_index, y, train_mask=train_mask)
+        loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
+                                         shuffle=True, seed=seed)
     t0 = time.time()
     for epoch in range(epochs):
         model.train()
-        opt.zero_grad()
-        loss = crit(model(x, edge_index)[train], y[train])
-        loss.backward()
-        opt.step()
+        if loader is None:
+            opt.zero_grad()
+            loss = crit(model(x, edge_index)[train], y[train])
+            loss.backward()
+            opt.step()
+        else:
+            for batch in loader:                            # demo_sgrace.py train(), :476-507
+                opt.zero_grad()
+                # the layers aggregate at edge_index[0]; PyG's batches put the seed in row 1, so flipped, each seed row
+                # holds its sampled neighbours (taken literally, it would hold its self loop and little else)
+                out = model(batch.x, batch.edge_index.flip(0))
+                loss = crit(out[batch.train_mask], batch.y[batch.train_mask])
+                loss.backward()
+                opt.step()
         if verbose and (epoch + 1) % 20 == 0:
             print(f"epoch {epoch + 1:3d}  loss {float(loss):.4f}", flush=True)
     if device.type == "cuda":
@@ -76,6 +100,8 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
     result = {"train_acc": float((pred[train] == y[train]).float().mean()),
               "test_acc": float((pred[test] == y[test]).float().mean()),
               "edges": int(edge_index.shape[1]), "ms_per_epoch": 1000 * elapsed / epochs}
+    if loader is not None:
+        result["batches_per_epoch"] = len(loader)
     if verbose:
         print(result)
     return result, model, (x, edge_index, y)
@@ -90,5 +116,10 @@ if __name__ == "__main__":
     ap.add_argument("--hidden", type=int, default=16)
     ap.add_argument("--nodes", type=int, default=3000)
     ap.add_argument("--emulate", action="store_true")
+    ap.add_argument("--batch-size", type=int, default=None)
+    ap.add_argument("--num-neighbors", type=lambda s: [int(k) for k in s.split(",")], default=None)
     a = ap.parse_args()
-    run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate)
+    if (a.batch_size is None) != (a.num_neighbors is None) or (a.batch_size is not None and a.acc != 1):
+        ap.error("--batch-size and --num-neighbors go together, on the kernels (--acc 1)")
+    run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
+        num_neighbors=a.num_neighbors)

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SGX_VERSION 107
+#define SGX_VERSION 108
 
 typedef enum sgx_status {
     SGX_OK = 0,
@@ -45,7 +45,8 @@ typedef enum sgx_status {
     SGX_ERR_WORKSPACE = -4,    /* workspace missing or too small                     */
     SGX_ERR_HIP = -5,          /* a HIP call or launch failed                        */
     SGX_ERR_CSR = -6,          /* sgx_csr_validate: rowPtr not monotone / index out of range */
-    SGX_ERR_ALIGN = -7         /* pointer or leading dimension not aligned as required */
+    SGX_ERR_ALIGN = -7,        /* pointer or leading dimension not aligned as required */
+    SGX_ERR_SEEDS = -8         /* sgx_sample_neighbors: a seed repeats or lies outside [0, n_nodes) */
 } sgx_status;
 
 /* Element type of B, D, values_fea, values_adj (MM.h:76-148 selects ONE type for all:
@@ -392,6 +393,58 @@ int sgx_relu_mask_backward(int dtype_out, const void *out, int dtype_grad, void 
  * block select of dsp_kernel_float_adj_4, K.cpp:217-264, done on the sending side).  ld_* in elements. */
 int sgx_pack_rows(int dtype, int64_t n_rows, int n_feat, const void *src, int64_t ld_src, const int32_t *row_index,
                   void *dst, int64_t ld_dst, void *stream);
+
+/* ---- neighbour sampling for mini-batch training ---------------------------------------
+ * The NeighborLoader batches of the reference's demo (demo/emulation/demo_sgrace.py:112-125, `full_graph = 0`:
+ * num_neighbors=[10], batch_size=128, input_nodes=train_mask), sampled on the device (csrc/sample.hip).
+ *
+ * Graph: the CSR (rowPtr [n_nodes+1], columnIndex [nnz]) built on the TARGET of every edge, so row v holds the
+ * in-edges j -> v (PyG's flow="source_to_target").  Self loops and repeated edges are positions like any other.
+ *
+ * Sampling rule, for seed / frontier node v of degree deg = rowPtr[v+1] - rowPtr[v] at hop h with fan-out k:
+ *   - k == -1 or deg <= k: every position 0 .. deg-1;
+ *   - otherwise a uniform k-subset of the positions without replacement, by Floyd's algorithm:
+ *       S = {};  for j = deg-k .. deg-1:  t = draw(j);  S += (t in S) ? j : t;
+ *   - the positions of S in ascending order.
+ * The draw is a counter-based hash; mix64 is the splitmix64 finaliser
+ *     z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9;  z = (z ^ (z >> 27)) * 0x94d049bb133111eb;  z ^ (z >> 31)
+ * on uint64 with wrap-around, and
+ *     key_h   = mix64(mix64(mix64(seed) ^ step) ^ (uint64)h)          h = hop index, 0 = the hop that samples the seeds
+ *     w       = ((uint64)(uint32)v << 32) | (uint32)j                 node id in bits 63..32, Floyd index in 31..0
+ *     draw(j) = (mix64(key_h ^ mix64(w)) * (j + 1)) >> 64              128-bit product, high word: t in [0, j]
+ * The multiply-high map is biased by at most (j+1) / 2^64 <= deg / 2^64 per draw.  The cost is O(k) per node whatever
+ * its degree; the sample is a pure function of (graph, seeds, fanouts, seed, step).
+ *
+ * Relabel: local ids 0 .. B-1 are the seeds in the order given (they must be unique: SGX_ERR_SEEDS otherwise, checked on
+ * the device).  Hop h samples every node of its frontier (hop 0: the seeds; hop h+1: the nodes that were new at hop h);
+ * a sampled node without a local id gets the next one in order of first appearance -- frontier order, then position order
+ * within the node's sample.  Outputs:
+ *   n_id [nodes]            global id of every local node, seeds first;
+ *   out_rowPtr [nodes+1], out_col [edges]
+ *                           CSR over local rows: row i holds the sampled neighbours of local node i as local ids, in
+ *                           sampled order; rows of the nodes new at the last hop are empty;
+ *   edge_pos [edges]        the position in columnIndex (of the input CSR) of every sampled edge, to gather edge values;
+ *   hop_nodes [n_hops+1]    HOST: node count before hop 0 (B) and after each hop; hop_edges [n_hops+1] HOST: edge count
+ *                           likewise (hop_edges[0] = 0).  nodes = hop_nodes[n_hops], edges = hop_edges[n_hops].
+ * node_map [n_nodes] is caller-owned int32 scratch that holds 0x7fffffff (the sentinel) in every entry before the call and
+ * again after it (also after SGX_ERR_SEEDS; after any other device-side error the caller refills it).  The relabel uses it
+ * instead of a sort: each sampled slot atomicMin's its ordinal into the entry of its node, the slot that finds its own
+ * ordinal there is the first appearance, an exclusive scan of those flags gives the new ids, the edges are relabelled
+ * through the map and the touched entries reset -- each step its own launch.  One stream synchronisation and one
+ * device->host read-back of (2 n_hops + 3) int32 per call; not capturable.
+ *
+ * Capacity: sgx_sample_workspace_bytes returns the workspace size (0 for bad arguments) and the bounds the outputs are
+ * sized from: per hop, edges <= frontier * k (nnz for k == -1), new nodes (the next frontier) <= those edges and <=
+ * n_nodes - B; max_edges <= nnz, max_nodes <= n_nodes.  Arguments: n_nodes >= 0, 0 <= nnz < 2^31 - 1, 0 <= batch <= n_nodes, 1 <= n_hops <= 64, fanouts[h] >= -1
+ * (fan-outs up to 64 keep the subset in registers; larger ones are correct and slow).  max_nodes / max_edges below the
+ * bounds: SGX_ERR_SHAPE. */
+size_t sgx_sample_workspace_bytes(int n_nodes, int64_t nnz, int batch, int n_hops, const int *fanouts,
+                                  int64_t *max_nodes, int64_t *max_edges);
+int sgx_sample_neighbors(const int32_t *rowPtr, const int32_t *columnIndex, int n_nodes, int64_t nnz,
+                         const int32_t *seeds, int batch, int n_hops, const int *fanouts, uint64_t seed, uint64_t step,
+                         int32_t *node_map, int32_t *n_id, int32_t *out_rowPtr, int32_t *out_col, int32_t *edge_pos,
+                         int64_t max_nodes, int64_t max_edges, int64_t *hop_nodes, int64_t *hop_edges,
+                         void *workspace, size_t workspace_bytes, void *stream);
 
 /* A plain streaming copy (16 bytes per lane, non-temporal, each workgroup on a contiguous chunk), the kernel the attainable HBM rate of a device is
  * measured with next to the nominal 8 TB/s (bench.py reports it as roofline.stream_copy_GBps_this_device).

@@ -20,6 +20,7 @@ SGX_ACC_F32, SGX_ACC_REF_HALF = 0, 1
 SGX_ORDER_REFERENCE, SGX_ORDER_AGGREGATE_FIRST = 0, 1      # sgx_layer_order
 SGX_QUANT_INT8 = 2                                          # sgx_quant.flags: integer operands on the int8 matrix cores
 SGX_QUANT_INT8_AUTO = 4                                     # ... where they are the faster form (M_fea > 128)
+SGX_ERR_SEEDS = -8                                          # sgx_sample_neighbors: a repeated or out-of-range seed
 
 # every symbol include/sgx.h declares (tests/test_abi.py checks header and library against this)
 SYMBOLS = [
@@ -33,6 +34,7 @@ SYMBOLS = [
     "sgx_stream_copy", "sgx_xw_dense_act", "sgx_event_create", "sgx_event_destroy", "sgx_event_record", "sgx_event_elapsed_ms",
     "sgx_gat_aggregate_fill", "sgx_col_sums", "sgx_col_sums_scratch_bytes", "sgx_pack_rows",
     "sgx_code_bias", "sgx_quantize_codes_i8", "sgx_xw_dense_i8", "sgx_xw_dense_i8_workspace_bytes",
+    "sgx_sample_workspace_bytes", "sgx_sample_neighbors",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -177,6 +179,12 @@ def _load():
     lib.sgx_event_record.restype = c_int
     lib.sgx_event_elapsed_ms.argtypes = [vp, vp, ctypes.POINTER(ctypes.c_float)]
     lib.sgx_event_elapsed_ms.restype = c_int
+    i64p, i32p = ctypes.POINTER(c_i64), ctypes.POINTER(ctypes.c_int32)
+    lib.sgx_sample_workspace_bytes.argtypes = [c_int, c_i64, c_int, c_int, i32p, i64p, i64p]
+    lib.sgx_sample_workspace_bytes.restype = sz
+    lib.sgx_sample_neighbors.argtypes = [vp, vp, c_int, c_i64, vp, c_int, c_int, i32p, ctypes.c_uint64, ctypes.c_uint64,
+                                         vp, vp, vp, vp, vp, c_i64, c_i64, i64p, i64p, vp, sz, vp]
+    lib.sgx_sample_neighbors.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

@@ -326,6 +326,7 @@ extern "C" const char *sgx_status_string(int status)
     case SGX_ERR_HIP: return "HIP call or kernel launch failed";
     case SGX_ERR_CSR: return "CSR structure invalid";
     case SGX_ERR_ALIGN: return "pointer or leading dimension misaligned";
+    case SGX_ERR_SEEDS: return "seed list holds a repeated or out-of-range node";
     default: return "unknown status";
     }
 }

@@ -721,3 +721,74 @@ def relu_mask_backward_(out, grad):
     check(lib.sgx_relu_mask_backward(dtype_code(out.dtype), _ptr(out), dtype_code(grad.dtype), _ptr(grad),
                                      out.numel(), _stream()), "sgx_relu_mask_backward")
     return grad
+
+
+# ---- neighbour sampling (sgx_sample_neighbors): the NeighborLoader batches of demo_sgrace.py:112-125 ----------------
+SAMPLE_SENTINEL = 0x7FFFFFFF
+_node_maps = {}
+
+
+def _node_map(device, n_nodes):
+    """The sampler's node -> local id map, one per (device, stream), kept at the sentinel between calls."""
+    key = (device.index, torch.cuda.current_stream(device).cuda_stream)
+    m = _node_maps.get(key)
+    if m is None or m.numel() < n_nodes:
+        m = torch.full((max(int(n_nodes), 1),), SAMPLE_SENTINEL, dtype=torch.int32, device=device)
+        _node_maps[key] = m
+    return m
+
+
+class Sample:
+    """One sampled mini-batch (include/sgx.h, "neighbour sampling"): n_id (global ids, seeds first), adj (Csr over the
+    local nodes: row i = the sampled in-neighbours of local node i), edge_pos (position of every sampled edge in the
+    input CSR), batch_size, and the node / edge counts after each hop (num_sampled_* as PyG counts them: per hop)."""
+
+    def __init__(self, n_id, adj, edge_pos, batch_size, hop_nodes, hop_edges):
+        self.n_id, self.adj, self.edge_pos, self.batch_size = n_id, adj, edge_pos, batch_size
+        self.hop_nodes, self.hop_edges = list(hop_nodes), list(hop_edges)
+
+    @property
+    def num_sampled_nodes(self):
+        h = self.hop_nodes
+        return [h[0]] + [h[i + 1] - h[i] for i in range(len(h) - 1)]
+
+    @property
+    def num_sampled_edges(self):
+        h = self.hop_edges
+        return [h[i + 1] - h[i] for i in range(len(h) - 1)]
+
+
+def sample_neighbors(csr, seeds, fanouts, seed=0, step=0, gather_values=False):
+    """Neighbour sample of `seeds` (int32 or int64 global ids on the device, unique) over `csr` (row v = the in-edges
+    of v), one fan-out per hop (-1 = every neighbour), by the rule of include/sgx.h: the same bits for the same
+    (graph, seeds, fanouts, seed, step).  adj holds fp32 ones, or the sampled entries of csr.val with gather_values.
+    One stream synchronisation per call."""
+    _dev(seeds, "seeds")
+    fan = [int(k) for k in fanouts]
+    dev = csr.rowptr.device
+    seeds = seeds.to(torch.int32).contiguous()
+    B, H, n = seeds.numel(), len(fan), csr.n_rows
+    fan_c = (ctypes.c_int32 * max(H, 1))(*fan)
+    max_nodes, max_edges = ctypes.c_int64(0), ctypes.c_int64(0)
+    nbytes = lib.sgx_sample_workspace_bytes(n, csr.nnz, B, H, fan_c, ctypes.byref(max_nodes), ctypes.byref(max_edges))
+    if nbytes == 0:
+        raise ValueError(f"sample_neighbors: bad arguments (n_nodes {n}, nnz {csr.nnz}, batch {B}, fanouts {fan}): "
+                         "fan-outs must be >= -1, 1 to 64 hops, batch <= n_nodes")
+    n_id = torch.empty(max(max_nodes.value, 1), dtype=torch.int32, device=dev)
+    rowptr = torch.empty(max_nodes.value + 1, dtype=torch.int32, device=dev)
+    col = torch.empty(max(max_edges.value, 1), dtype=torch.int32, device=dev)
+    pos = torch.empty(max(max_edges.value, 1), dtype=torch.int32, device=dev)
+    hop_nodes, hop_edges = (ctypes.c_int64 * (H + 1))(), (ctypes.c_int64 * (H + 1))()
+    node_map = _node_map(dev, n)
+    ws = _workspace(dev, nbytes)
+    status = lib.sgx_sample_neighbors(_ptr(csr.rowptr), _ptr(csr.col), n, csr.nnz, _ptr(seeds) if B else None, B, H, fan_c,
+                                      int(seed) & (2**64 - 1), int(step) & (2**64 - 1), _ptr(node_map), _ptr(n_id),
+                                      _ptr(rowptr), _ptr(col), _ptr(pos), max_nodes.value, max_edges.value, hop_nodes,
+                                      hop_edges, _ptr(ws), ws.numel(), _stream())
+    if status not in (0, _lib.SGX_ERR_SEEDS):
+        node_map.fill_(SAMPLE_SENTINEL)                 # (sgx.h: the map is restored on success and on SGX_ERR_SEEDS only)
+    check(status, "sgx_sample_neighbors")
+    N, E = hop_nodes[H], hop_edges[H]
+    val = csr.val[pos[:E].long()] if gather_values else torch.ones(E, dtype=torch.float32, device=dev)
+    adj = Csr(rowptr[:N + 1], col[:E], val, N)
+    return Sample(n_id[:N], adj, pos[:E], B, hop_nodes[:], hop_edges[:])

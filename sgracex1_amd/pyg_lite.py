@@ -1,7 +1,8 @@
 """The few torch_geometric pieces the reference's notebooks use around the hot path, restated
 with plain torch so the end-to-end runs do not need PyG (it is not installed here): the TU
 dataset reader for MUTAG (raw files -> graphs), DataLoader-style batching into one block-
-diagonal graph, `to_dense_adj`, `global_mean_pool` (MOL cells 4-10, 18).
+diagonal graph, `to_dense_adj`, `global_mean_pool` (MOL cells 4-10, 18), and the NeighborLoader
+of the node-classification demo's mini-batch mode (demo_sgrace.py:112-125), sampled on the GPU.
 """
 from dataclasses import dataclass
 from typing import List
@@ -120,3 +121,93 @@ def sort_edge_index(edge_index, edge_weight, num_nodes):
     key = edge_index[0] * num_nodes + edge_index[1]
     perm = torch.argsort(key, stable=True)
     return edge_index[:, perm], edge_weight[perm]
+
+
+class NodeData:
+    """A node-classification graph as the demo's Planetoid / Amazon datasets carry it: x, y, edge_index and optional
+    train / val / test masks."""
+
+    def __init__(self, x, edge_index, y=None, train_mask=None, val_mask=None, test_mask=None):
+        self.x, self.edge_index, self.y = x, edge_index, y
+        self.train_mask, self.val_mask, self.test_mask = train_mask, val_mask, test_mask
+
+    @property
+    def num_nodes(self):
+        return self.x.shape[0]
+
+
+class NodeBatch:
+    """One NeighborLoader batch, PyG's surface: x / y / masks / n_id of the sampled nodes (seeds first), edge_index in
+    local ids oriented as PyG does (row 0 = sampled neighbour, row 1 = the node it was sampled for), batch_size,
+    input_id (positions of the seeds in input_nodes), num_sampled_nodes / num_sampled_edges per hop; plus adj, the same
+    edges as a Csr whose row i holds the neighbours sampled for local node i (aggregation at the seed rows)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    @property
+    def num_nodes(self):
+        return self.n_id.numel()
+
+
+_MASKS = ("train_mask", "val_mask", "test_mask")
+
+
+class NeighborLoader:
+    """torch_geometric.loader.NeighborLoader(data, num_neighbors, batch_size, input_nodes, shuffle) on the HIP sampler
+    (ops.sample_neighbors, rule in include/sgx.h).  The CSR on the targets of edge_index (row v = the edges j -> v,
+    flow="source_to_target", repeated edges kept) is built once per loader.  An epoch visits every input node once, in
+    order or in a permutation drawn from `seed` and the epoch number; batch b of epoch e samples with step
+    e * len(loader) + b, so every batch is reproducible."""
+
+    def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0):
+        from . import ops
+        self.data, self.num_neighbors = data, [int(k) for k in num_neighbors]
+        self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
+        x, ei = data.x, data.edge_index
+        n = x.shape[0]
+        dev = x.device
+        if input_nodes is None:
+            input_nodes = torch.arange(n, device=dev)
+        elif input_nodes.dtype == torch.bool:
+            input_nodes = torch.nonzero(input_nodes.to(dev)).reshape(-1)
+        self.input_nodes = input_nodes.to(dev, torch.int64)
+        dst, src = ei[1].to(dev, torch.int64), ei[0].to(dev, torch.int64)
+        order = torch.argsort(dst * n + src, stable=True)
+        self.csr = ops.Csr.from_coo(dst[order].to(torch.int32), src[order].to(torch.int32),
+                                    torch.ones(order.numel(), dtype=torch.float32, device=dev), n, n)
+        self.epoch = 0
+
+    def __len__(self):
+        return (self.input_nodes.numel() + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        m = self.input_nodes.numel()
+        if self.shuffle:
+            g = torch.Generator().manual_seed(self.seed * 1000003 + self.epoch)
+            perm = torch.randperm(m, generator=g).to(self.input_nodes.device)
+        else:
+            perm = torch.arange(m, device=self.input_nodes.device)
+        first_step, self.epoch = self.epoch * len(self), self.epoch + 1
+        for b, i in enumerate(range(0, m, self.batch_size)):
+            input_id = perm[i:i + self.batch_size]
+            yield self._batch(self.input_nodes[input_id], input_id, first_step + b)
+
+    def _batch(self, seeds, input_id, step):
+        from . import ops
+        d = self.data
+        s = ops.sample_neighbors(self.csr, seeds, self.num_neighbors, seed=self.seed, step=step)
+        A = s.adj
+        n_idx = s.n_id.long()
+        target = torch.repeat_interleave(torch.arange(A.n_rows, device=n_idx.device),
+                                         (A.rowptr[1:] - A.rowptr[:-1]).long(), output_size=A.nnz)
+        fields = dict(x=ops.pack_rows(d.x, s.n_id), edge_index=torch.stack([A.col[:A.nnz].long(), target]),
+                      n_id=n_idx, adj=A, batch_size=s.batch_size, input_id=input_id,
+                      num_sampled_nodes=s.num_sampled_nodes, num_sampled_edges=s.num_sampled_edges)
+        if getattr(d, "y", None) is not None:
+            fields["y"] = d.y[n_idx]
+        for name in _MASKS:
+            mask = getattr(d, name, None)
+            if mask is not None:
+                fields[name] = mask[n_idx]
+        return NodeBatch(**fields)

@@ -1,0 +1,81 @@
+"""Restatement of the neighbour-sampling rule of include/sgx.h in numpy / Python integers, for the sampler tests.
+
+Reads only the rows it samples, so a host copy of a full-size CSR (rowptr, col as numpy arrays) is enough."""
+import numpy as np
+
+M64 = (1 << 64) - 1
+SENTINEL = 0x7FFFFFFF
+
+
+def mix64(z):
+    """splitmix64 finaliser on Python ints."""
+    z &= M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+def hop_key(seed, step, hop):
+    return mix64(mix64(mix64(seed) ^ (step & M64)) ^ hop)
+
+
+def _mix64_np(z):
+    with np.errstate(over="ignore"):
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return z ^ (z >> np.uint64(31))
+
+
+def draws(key, v, deg, k):
+    """t_j for j = deg-k .. deg-1 (vectorised): high word of mix64(key ^ mix64(v << 32 | j)) * (j + 1)."""
+    j = np.arange(deg - k, deg, dtype=np.uint64)
+    w = (np.uint64(v) << np.uint64(32)) | j
+    r = _mix64_np(np.uint64(key) ^ _mix64_np(w))
+    m = j + np.uint64(1)                                   # < 2^32: the 128-bit product's high word from 32-bit halves
+    rh, rl = r >> np.uint64(32), r & np.uint64(0xFFFFFFFF)
+    with np.errstate(over="ignore"):
+        hi = (rh * m + ((rl * m) >> np.uint64(32))) >> np.uint64(32)
+    return hi.astype(np.int64)
+
+
+def floyd(key, v, deg, k):
+    """Positions (ascending) sampled from a row of `deg` entries with fan-out k."""
+    if k < 0 or deg <= k:
+        return list(range(deg))
+    chosen = set()
+    for j, t in zip(range(deg - k, deg), draws(key, v, deg, k).tolist()):
+        chosen.add(j if t in chosen else t)
+    return sorted(chosen)
+
+
+def sample(rowptr, col, seeds, fanouts, seed=0, step=0):
+    """-> n_id, out_rowptr, out_col, edge_pos, hop_nodes, hop_edges (numpy int64 / lists), or raises ValueError for
+    repeated seeds."""
+    seeds = [int(s) for s in seeds]
+    if len(set(seeds)) != len(seeds):
+        raise ValueError("repeated seed")
+    local = {v: i for i, v in enumerate(seeds)}
+    n_id = list(seeds)
+    row_start = {}
+    out_col, edge_pos = [], []
+    hop_nodes, hop_edges = [len(seeds)], [0]
+    f0, f1 = 0, len(seeds)
+    for h, k in enumerate(fanouts):
+        key = hop_key(seed, step, h)
+        for i in range(f0, f1):
+            v = n_id[i]
+            p0, p1 = int(rowptr[v]), int(rowptr[v + 1])
+            row_start[i] = len(out_col)
+            for p in floyd(key, v, p1 - p0, k):
+                c = int(col[p0 + p])
+                if c not in local:
+                    local[c] = len(n_id)
+                    n_id.append(c)
+                out_col.append(local[c])
+                edge_pos.append(p0 + p)
+        f0, f1 = f1, len(n_id)
+        hop_nodes.append(len(n_id))
+        hop_edges.append(len(out_col))
+    out_rowptr = [row_start.get(i, len(out_col)) for i in range(len(n_id))] + [len(out_col)]
+    return (np.asarray(n_id, np.int64), np.asarray(out_rowptr, np.int64), np.asarray(out_col, np.int64),
+            np.asarray(edge_pos, np.int64), hop_nodes, hop_edges)
