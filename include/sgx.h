@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SGX_VERSION 108
+#define SGX_VERSION 109
 
 typedef enum sgx_status {
     SGX_OK = 0,
@@ -364,11 +364,14 @@ int sgx_xt_g(int dtype_x, int n_rows, int M, int P, const void *X, int64_t ldx, 
  *   d_e = G[row e] . Wh[col e];  dx_e = S_e d_e;  sg_e = dx_e - S_e sum_row(dx);
  *   sg_e = 0 where values[e] <= 0;  sg_e *= (E_e > 0 ? 1 : alpha)
  * writes sg [nnz] and g1[r] = sum_row(sg).  The attention gradient is then [Wh^T g1 ; Wh^T g2] with
- * g2 = the column sums of sg (row sums over A^T: sgx_spmm_csr) through sgx_xt_g. */
+ * g2 = the column sums of sg (row sums over A^T: sgx_spmm_csr) through sgx_xt_g.
+ * dead, dead_row_sum (both NULL, or both [n_rows]): rows with dead[r] != 0 are the rows the forward found
+ * without a positive entry, whose softmax is uniform over ALL n_cols columns (SG.py:638-641); for them
+ * sum_row(dx) is dead_row_sum[r] = G[r] . colsum(Wh) / n_cols instead of the sum over the stored entries. */
 int sgx_gat_backward_edges(int dtype_values, int n_rows, int n_cols, int n_feat, float alpha,
                            const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
                            const float *E, const float *S, const float *G, int64_t ldg, const float *Wh, int64_t ldw,
-                           float *sg, float *g1, void *stream);
+                           const uint8_t *dead, const float *dead_row_sum, float *sg, float *g1, void *stream);
 
 /* Readout + classifier head of the graph-classification model (MOL cell 18 tail) in one launch:
  * pooled[g][:] = mean of X rows [graph_ptr[g], graph_ptr[g+1])  (global_mean_pool over a sorted

@@ -157,7 +157,7 @@ def _load():
     lib.sgx_relu_mask_backward.argtypes = [c_int, vp, c_int, vp, c_i64, vp]
     lib.sgx_relu_mask_backward.restype = c_int
     lib.sgx_gat_backward_edges.argtypes = [c_int, c_int, c_int, c_int, ctypes.c_float, vp, vp, vp, vp, vp, vp, c_i64, vp,
-                                           c_i64, vp, vp, vp]
+                                           c_i64, vp, vp, vp, vp, vp]
     lib.sgx_gat_backward_edges.restype = c_int
     lib.sgx_readout_mean_linear.argtypes = [c_int, c_int, c_int, c_int, vp, c_i64, vp, vp, vp, vp, vp, vp]
     lib.sgx_readout_mean_linear.restype = c_int

@@ -93,7 +93,8 @@ __global__ __launch_bounds__(kDotBlock) void gat_bwd_dots_kernel(
 template <typename TV>
 __global__ __launch_bounds__(kBlock) void gat_bwd_rows_kernel(
     int n_rows, const int32_t *__restrict__ rowptr, const TV *__restrict__ val, const float *__restrict__ E,
-    const float *__restrict__ S, float alpha, float *__restrict__ sg, float *__restrict__ g1)
+    const float *__restrict__ S, float alpha, const uint8_t *__restrict__ dead, const float *__restrict__ dead_row_sum,
+    float *__restrict__ sg, float *__restrict__ g1)
 {
     constexpr int RPW = 64 / kRowLanes;
     const int lane = threadIdx.x & 63, sub = lane % kRowLanes, grp = lane / kRowLanes;
@@ -114,6 +115,7 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_rows_kernel(
         for (int idx = e0 + sub; idx < e1; idx += kRowLanes) rs += sg[idx];
 #pragma unroll
         for (int off = 1; off < kRowLanes; off <<= 1) rs += __shfl_xor(rs, off);
+        if (dead != nullptr && live && dead[r]) rs = dead_row_sum[r];       // softmax over all N columns, not the stored ones
         float acc = 0.0f;
         for (int idx = e0 + sub; idx < e1; idx += kRowLanes) acc += finish(idx, rs);
 #pragma unroll
@@ -128,7 +130,8 @@ constexpr int kLongThreads = 1024;
 template <typename TV>
 __global__ __launch_bounds__(kLongThreads) void gat_bwd_long_rows_kernel(
     int n_rows, const int32_t *__restrict__ rowptr, const TV *__restrict__ val, const float *__restrict__ E,
-    const float *__restrict__ S, float alpha, float *__restrict__ sg, float *__restrict__ g1)
+    const float *__restrict__ S, float alpha, const uint8_t *__restrict__ dead, const float *__restrict__ dead_row_sum,
+    float *__restrict__ sg, float *__restrict__ g1)
 {
     __shared__ float part[kLongThreads / 64];
     __shared__ float total;
@@ -165,6 +168,7 @@ __global__ __launch_bounds__(kLongThreads) void gat_bwd_long_rows_kernel(
         float rs = 0.0f;
         for (int idx = e0 + (int)threadIdx.x; idx < e1; idx += kLongThreads) rs += sg[idx];
         rs = block_sum(rs);
+        if (dead != nullptr && dead[r]) rs = dead_row_sum[r];
         float acc = 0.0f;
         for (int idx = e0 + (int)threadIdx.x; idx < e1; idx += kLongThreads) {
             float v = sg[idx] - S[idx] * rs;
@@ -203,11 +207,13 @@ int dots_launch(const BwdArgs &a)
 extern "C" int sgx_gat_backward_edges(int dtype_values, int n_rows, int n_cols, int n_feat, float alpha,
                                       const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
                                       const float *E, const float *S, const float *G, int64_t ldg, const float *Wh,
-                                      int64_t ldw, float *sg, float *g1, void *stream)
+                                      int64_t ldw, const uint8_t *dead, const float *dead_row_sum, float *sg, float *g1,
+                                      void *stream)
 {
     if (n_rows < 0 || n_cols < 0 || n_feat < 1 || ldg < n_feat || ldw < n_feat) return SGX_ERR_SHAPE;
     if (n_rows == 0) return SGX_OK;
     if (!rowPtr || !columnIndex || !values || !E || !S || !G || !Wh || !sg || !g1) return SGX_ERR_NULL;
+    if ((dead == nullptr) != (dead_row_sum == nullptr)) return SGX_ERR_NULL;
     if (dtype_values != SGX_F16 && dtype_values != SGX_F32) return SGX_ERR_UNSUPPORTED;
     if ((uintptr_t)Wh % 16 != 0 || (ldw * 4) % 16 != 0) return SGX_ERR_ALIGN;          // 16-byte gathers of fp32 rows
     const unsigned long long w_bytes = (unsigned long long)n_cols * (unsigned long long)ldw * 4ull;
@@ -243,15 +249,15 @@ extern "C" int sgx_gat_backward_edges(int dtype_values, int n_rows, int n_cols, 
     const int rows_per_block = (64 / kRowLanes) * (kBlock / 64);
     const unsigned grid = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
     if (dtype_values == SGX_F16)
-        hipLaunchKernelGGL(gat_bwd_rows_kernel<f16>, dim3(grid), dim3(kBlock), 0, s, n_rows, rowPtr, (const f16 *)values, E, S, alpha, sg, g1);
+        hipLaunchKernelGGL(gat_bwd_rows_kernel<f16>, dim3(grid), dim3(kBlock), 0, s, n_rows, rowPtr, (const f16 *)values, E, S, alpha, dead, dead_row_sum, sg, g1);
     else
-        hipLaunchKernelGGL(gat_bwd_rows_kernel<float>, dim3(grid), dim3(kBlock), 0, s, n_rows, rowPtr, (const float *)values, E, S, alpha, sg, g1);
+        hipLaunchKernelGGL(gat_bwd_rows_kernel<float>, dim3(grid), dim3(kBlock), 0, s, n_rows, rowPtr, (const float *)values, E, S, alpha, dead, dead_row_sum, sg, g1);
     SGX_LAUNCH_CHECK();
     const unsigned grid_long = (unsigned)((n_rows + 63) / 64);
     if (dtype_values == SGX_F16)
-        hipLaunchKernelGGL(gat_bwd_long_rows_kernel<f16>, dim3(grid_long), dim3(kLongThreads), 0, s, n_rows, rowPtr, (const f16 *)values, E, S, alpha, sg, g1);
+        hipLaunchKernelGGL(gat_bwd_long_rows_kernel<f16>, dim3(grid_long), dim3(kLongThreads), 0, s, n_rows, rowPtr, (const f16 *)values, E, S, alpha, dead, dead_row_sum, sg, g1);
     else
-        hipLaunchKernelGGL(gat_bwd_long_rows_kernel<float>, dim3(grid_long), dim3(kLongThreads), 0, s, n_rows, rowPtr, (const float *)values, E, S, alpha, sg, g1);
+        hipLaunchKernelGGL(gat_bwd_long_rows_kernel<float>, dim3(grid_long), dim3(kLongThreads), 0, s, n_rows, rowPtr, (const float *)values, E, S, alpha, dead, dead_row_sum, sg, g1);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }

@@ -231,14 +231,15 @@ class GCN_PYNQ(torch.nn.Module):
         x = x.relu() if acc == 0 else self.reluh(x)
         dense, relu = 1, 0
         x = self.conv2(acc, dense, relu, x, adj, *bufs)
-        if acc == 1 and not self.training and not torch.is_grad_enabled():
-            # inference: pooling and the Linear head in one launch (dropout is the identity in eval);
-            # `batch` is sorted (graphs are contiguous), so a graph is a row segment
-            return ops.readout_mean_linear(x.contiguous(), ops.graph_ptr_of(batch), self.lin.weight, self.lin.bias)
-        if acc == 1:
+        # a sorted `batch` (PyG's collation: graphs are contiguous) makes a graph a row segment; an unsorted one does not
+        ptr = ops.graph_ptr_of(batch) if acc == 1 else None
+        if ptr is not None and not self.training and not torch.is_grad_enabled():
+            # inference: pooling and the Linear head in one launch (dropout is the identity in eval)
+            return ops.readout_mean_linear(x.contiguous(), ptr, self.lin.weight, self.lin.bias)
+        if ptr is not None:
             # training: the pooling as one launch each way (the same fp32 means as the inference kernel); dropout and
             # the 64 x 2 head stay torch's
-            x = ops.ReadoutMean.apply(x, ops.graph_ptr_of(batch), batch.numel() == x.shape[0])
+            x = ops.ReadoutMean.apply(x, ptr, batch.numel() == x.shape[0])
         else:
             x = global_mean_pool(x.float(), batch)
         x = F.dropout(x, p=0.5, training=self.training)

@@ -158,18 +158,26 @@ class Csr:
             self.val = torch.zeros(1, dtype=val.dtype, device=self.rowptr.device)
         self._plan = plan
         self._dead_rows = None
+        self._dead_row_mask = None
         self._quantized = {}
 
     @property
-    def has_dead_rows(self):
-        """True when some row holds no positive value -- the rows the GAT mask `adj > 0` (SG.py:640)
-        leaves without a neighbour.  One device->host sync, once per matrix."""
-        if self._dead_rows is None:
+    def dead_rows(self):
+        """bool [n_rows] on the device: the rows that hold no positive value, which the GAT mask `adj > 0` (SG.py:640)
+        leaves without a neighbour.  Built once per matrix, without a sync."""
+        if self._dead_row_mask is None:
             deg = (self.rowptr[1:] - self.rowptr[:-1]).long()
-            row = torch.repeat_interleave(torch.arange(self.n_rows, device=self.val.device), deg)
+            row = torch.repeat_interleave(torch.arange(self.n_rows, device=self.val.device), deg, output_size=self.nnz)
             live = torch.zeros(self.n_rows, dtype=torch.int32, device=self.val.device)
             live.index_add_(0, row, (self.val[:self.nnz] > 0).to(torch.int32))
-            self._dead_rows = bool((live == 0).any().item())
+            self._dead_row_mask = live == 0
+        return self._dead_row_mask
+
+    @property
+    def has_dead_rows(self):
+        """True when some row is one of dead_rows.  One device->host sync, once per matrix."""
+        if self._dead_rows is None:
+            self._dead_rows = bool(self.dead_rows.any().item())
         return self._dead_rows
 
     def quantized(self, qc):
@@ -634,14 +642,23 @@ def csr_transpose(A, return_order=False):
     return (T, order) if return_order else T
 
 
-def gat_backward_edges(adj, E, S, G, Wh, alpha=0.2):
-    """Edge pass of FPYNQ_GAT.backward (sgx_gat_backward_edges): returns (sg [nnz], g1 [n_rows]) fp32."""
+def gat_backward_edges(adj, E, S, G, Wh, alpha=0.2, dead=None):
+    """Edge pass of FPYNQ_GAT.backward (sgx_gat_backward_edges): returns (sg [nnz], g1 [n_rows]) fp32.
+    dead: None, or bool [n_rows] -- the rows the forward gave a uniform softmax over all n_cols columns (the dead rows
+    of the adjacency it masked with, quantised or not); their softmax row sum is G[r] . mean(Wh) (SG.py:884-1126)."""
     _dev2d(G, "G")
     _dev2d(Wh, "Wh")
     if G.dtype != torch.float32 or Wh.dtype != torch.float32 or E.dtype != torch.float32 or S.dtype != torch.float32:
         raise TypeError("gat_backward_edges works on float32 E, S, G, Wh (the reference's backward is fp32)")
     if Wh.shape[0] != adj.n_cols or G.shape != (adj.n_rows, Wh.shape[1]):
         raise ValueError("G must be [adj.n_rows, F] and Wh [adj.n_cols, F]")
+    dead_rs = None
+    if dead is not None:
+        _dev(dead, "dead")
+        if dead.dtype != torch.bool or dead.shape != (adj.n_rows,):
+            raise ValueError("dead must be a bool [adj.n_rows] tensor")
+        wh_mean = (col_sums(Wh) / adj.n_cols).unsqueeze(0)                   # [1, F]
+        dead_rs = xw_dense(G if G.stride(0) == G.shape[1] else G.contiguous(), wh_mean)[:, 0].contiguous()
     if Wh.stride(0) % 4 or Wh.data_ptr() % 16:           # rows are gathered 16 bytes at a time: pad them
         padded = torch.zeros((Wh.shape[0], (Wh.shape[1] + 3) // 4 * 4), dtype=torch.float32, device=Wh.device)
         padded[:, :Wh.shape[1]] = Wh
@@ -650,7 +667,8 @@ def gat_backward_edges(adj, E, S, G, Wh, alpha=0.2):
     g1 = torch.empty(adj.n_rows, dtype=torch.float32, device=G.device)
     check(lib.sgx_gat_backward_edges(dtype_code(adj.val.dtype), adj.n_rows, adj.n_cols, Wh.shape[1], float(alpha),
                                      _ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(E.contiguous()), _ptr(S.contiguous()),
-                                     _ptr(G), G.stride(0), _ptr(Wh), Wh.stride(0), _ptr(sg), _ptr(g1), _stream()),
+                                     _ptr(G), G.stride(0), _ptr(Wh), Wh.stride(0), _ptr(dead), _ptr(dead_rs), _ptr(sg),
+                                     _ptr(g1), _stream()),
           "sgx_gat_backward_edges")
     return sg, g1
 
@@ -705,8 +723,11 @@ class ReadoutMean(torch.autograd.Function):
 
 def graph_ptr_of(batch):
     """graph_ptr [n_graphs + 1] int32 of a sorted PyG `batch` vector, kept on the tensor (an epoch loop passes the same
-    batch every step)."""
+    batch every step); None when `batch` is not sorted, so that its graphs are not row segments (checked once per
+    tensor, one device->host sync)."""
     def build():
+        if batch.numel() > 1 and not bool((batch[1:] >= batch[:-1]).all().item()):
+            return None
         counts = torch.bincount(batch)
         ptr = torch.zeros(counts.numel() + 1, dtype=torch.int32, device=batch.device)
         ptr[1:] = torch.cumsum(counts, 0)

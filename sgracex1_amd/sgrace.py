@@ -24,7 +24,8 @@ emulation for `acc == 0`.  The backward pass uses the unquantised operands, as i
 Backward mirrors SG.py:884-1126 (the `accb == 0` branch) on the edge list instead of dense
 N x N matrices: grad_input = P @ (g @ W^T), grad_weights = X^T @ (P @ g) with P = the attention
 matrix (GAT) or adj (GCN) -- like the reference, P and not P^T -- and for GAT the attention-vector
-gradient through softmax and LeakyReLU.
+gradient through softmax and LeakyReLU.  A GAT row without a positive entry in the adjacency the forward masked
+with (the quantised one in quantised mode) has P = 1/N on all N columns, not only on its stored entries.
 """
 import torch
 import torch.nn.functional as F
@@ -145,6 +146,12 @@ class FPYNQ_GAT(torch.autograd.Function):
             else:
                 out, E, S = my_ip.run_layer(A, fea, Wt, quant=qc, quant_int8=int8), None, None
             ctx.csr = A
+            # the rows the forward gave a uniform softmax over all N columns: decided on the adjacency it masked with,
+            # the quantised one when qc is set (ops.layer_forward); the mask is built once per graph
+            ctx.dead = None
+            if ctx.gat:
+                masked = A.quantized(qc) if qc is not None else A
+                ctx.dead = masked.dead_rows if masked.has_dead_rows else None
             ctx.save_for_backward(input, weights, out, *([E, S] if ctx.gat else []))
             return out.float()                                            # SG.py:543 `.float()`
 
@@ -176,7 +183,9 @@ class FPYNQ_GAT(torch.autograd.Function):
         if qc is not None:
             output_cpu = output_cpu * qc.deq_o                            # SG.py:666-667
         ctx.csr = None
-        ctx.save_for_backward(input, weights, output_cpu, e, attentions if ctx.gat else adj_d, adj_d)
+        # SG.py:678-680 keep the UNquantised adjacency for the backward: P of the GCN form and the mask `adj > 0`
+        adj_u = adj.to_dense().float()
+        ctx.save_for_backward(input, weights, output_cpu, e, attentions if ctx.gat else adj_u, adj_u)
         return output_cpu
 
     @staticmethod
@@ -208,7 +217,7 @@ class FPYNQ_GAT(torch.autograd.Function):
             E, S = saved[3], saved[4]
             P = ops.Csr(A.rowptr, A.col, S.contiguous(), A.n_cols, A.plan if A.wants_plan else None)   # attention matrix, fp32 values; A's schedule
             Wh = ops.xw_dense(input.contiguous(), weights.t().contiguous())       # X . W, fp32 (SG.py:601); rows padded to 16 B
-            sg, g1 = ops.gat_backward_edges(A, E, S, g.contiguous(), Wh, ctx.alpha)
+            sg, g1 = ops.gat_backward_edges(A, E, S, g.contiguous(), Wh, ctx.alpha, dead=ctx.dead)
             # column sums of sg = row sums over A^T; the transposed pattern is built once per graph
             if getattr(A, "_transpose_pattern", None) is None:
                 A._transpose_pattern = ops.csr_transpose(A, return_order=True)
@@ -221,6 +230,8 @@ class FPYNQ_GAT(torch.autograd.Function):
             P = A.to(torch.float32)
             grad_attention = torch.zeros((2 * weights.shape[1], 1), device=g.device)
         pg = ops.spmm(P, g.contiguous())                                       # P @ g
+        if ctx.gat and ctx.dead is not None:                                   # a dead row of P is 1/N on every column
+            pg = torch.where(ctx.dead.unsqueeze(1), (ops.col_sums(g.contiguous()) / A.n_cols).unsqueeze(0), pg)
         grad_input = ops.xw_dense(pg, weights.contiguous())                    # (P @ g) @ W^T == P @ (g @ W^T)
         if grad_input.stride(0) != grad_input.shape[1]:
             grad_input = grad_input.contiguous()

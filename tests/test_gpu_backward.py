@@ -67,6 +67,42 @@ def test_training_step_gradients_match_torch_twin():
         assert err < 2e-2, (k, float(err))                        # fp16 forward vs fp32 twin
 
 
+def test_training_step_with_an_unsorted_batch():
+    """GCN_PYNQ on MUTAG with its nodes permuted, so that `batch` is not sorted and a graph is no row segment: the
+    logits and every parameter gradient equal those of the same graphs in collation order (the pooling falls back
+    to pooling by index), in training mode under autograd and in inference."""
+    import os
+    from _fixtures import GOLD
+    from sgracex1_amd import molecule_gcn as M, ops, pyg_lite as G, pynq_shim
+    dev = torch.device("cuda")
+    raw = np.load(os.path.join(GOLD, "mutag_raw.npz"))
+    b = G.collate(G.load_tu_raw(raw["A"], raw["graph_indicator"], raw["graph_labels"], raw["node_labels"])).to(dev)
+    n = b.x.shape[0]
+    perm = torch.randperm(n, generator=torch.Generator().manual_seed(3)).to(dev)
+    inv = torch.empty_like(perm)
+    inv[perm] = torch.arange(n, device=dev)
+    x_p, batch_p, ei_p = b.x[perm].contiguous(), b.batch[perm].contiguous(), inv[b.edge_index]
+    assert ops.graph_ptr_of(batch_p) is None and ops.graph_ptr_of(b.batch) is not None
+    ip = pynq_shim.Overlay("gnn_all.bit").mmult_top_0
+    model = M.GCN_PYNQ(64, 7, 2, ip).to(dev).eval()              # eval: no dropout
+    crit = torch.nn.CrossEntropyLoss()
+    runs = {}
+    for name, (x, ei, batch) in dict(sorted=(b.x, b.edge_index, b.batch), permuted=(x_p, ei_p, batch_p)).items():
+        model.zero_grad()
+        logits = model(1, x, ei, batch)
+        crit(logits, b.y).backward()
+        with torch.no_grad():
+            infer = model(1, x, ei, batch)
+        runs[name] = (logits.detach(), infer, {k: p.grad.clone() for k, p in model.named_parameters() if p.grad is not None})
+    (l0, i0, g0), (l1, i1, g1) = runs["sorted"], runs["permuted"]
+    torch.testing.assert_close(l1, l0, rtol=1e-3, atol=1e-4)
+    torch.testing.assert_close(i1, i0, rtol=1e-3, atol=1e-4)
+    assert set(g0) == set(g1) and "conv1.weight" in g0
+    for k in g0:
+        err = (g1[k] - g0[k]).abs().max() / (g0[k].abs().max() + 1e-12)
+        assert err < 1e-2, (k, float(err))                        # fp16 layers, sums in another order
+
+
 @pytest.mark.parametrize("dtype", [torch.float16, torch.float32])
 def test_readout_mean_linear_matches_torch(dtype):
     """Fused global_mean_pool + Linear head ("next" row f3) against the two torch ops, with an empty

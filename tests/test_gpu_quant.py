@@ -167,6 +167,12 @@ def test_sgrace_layers_quantised_on_the_gpu_match_the_dense_twin(bits, gat):
         close = torch.isclose(outs[1][0], outs[0][0], rtol=1e-4, atol=1e-5)
         assert close.float().mean() > 0.99, float((outs[1][0] - outs[0][0]).abs().max())
         assert bits == 1 or outs[0][0].abs().max() > 0     # one bit: layer-2 inputs below 0.5 quantise to 0
+        # the layer-1 weight gradient through both layers' backward: the twin keeps the unquantised adjacency for P and
+        # the mask, as the device path and the reference (SG.py:678-680)
+        gw1, gw0 = outs[1][1], outs[0][1]
+        assert gw0.abs().max() > 0
+        err = float((gw1 - gw0).abs().max() / gw0.abs().max())
+        assert err < 2e-2, err
     finally:
         config.restore(old)
         sgrace.init_SGRACE()

@@ -186,3 +186,15 @@ def test_quantiser_registers_round_trip_through_the_register_map():
     with pytest.raises(ValueError):
         ip.quant_from_registers()
     assert ip.register_map.max_fea == 0
+
+
+def test_graph_ptr_of_refuses_an_unsorted_batch():
+    """graph_ptr_of: the row segments of a sorted `batch` (empty graphs included), kept on the tensor; None for a batch
+    whose graphs are not contiguous, so that the model pools it by index instead of by segment."""
+    from sgracex1_amd import ops
+    batch = torch.tensor([0, 0, 0, 2, 2, 3])
+    ptr = ops.graph_ptr_of(batch)
+    assert ptr.dtype == torch.int32 and ptr.tolist() == [0, 3, 3, 5, 6] and ops.graph_ptr_of(batch) is ptr
+    assert ops.graph_ptr_of(torch.tensor([0, 1, 0, 1])) is None
+    assert ops.graph_ptr_of(torch.tensor([1, 0])) is None
+    assert ops.graph_ptr_of(torch.tensor([0])).tolist() == [0, 1]
