@@ -5,7 +5,9 @@ train on all 188 graphs in one batch, test on graphs [50:100], hidden 64, Adam l
 entropy, fp16 layer kernels in forward, device kernels in backward.  The notebook's recorded run
 reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epoch 36").
 
-    python examples/molecule_gcn_train.py [--epochs 60] [--acc 0]     # --acc 0 = the torch twin
+    python examples/molecule_gcn_train.py [--epochs 60] [--acc 0] [--layer-count 2]
+        --acc 0 = the torch twin; --layer-count 2 = the accuracy passes (eval) run the whole model in one call
+        (register layer_count, sgx_stack_forward); training steps run layer by layer either way
 """
 import argparse
 import json
@@ -26,6 +28,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=60)
     ap.add_argument("--acc", type=int, default=1)
+    ap.add_argument("--layer-count", type=int, default=1)
     args = ap.parse_args()
     dev = torch.device("cuda")
     raw = np.load(os.path.join(ROOT, "tests", "golden", "mutag_raw.npz"))
@@ -34,6 +37,7 @@ def main():
     graphs = [graphs[i] for i in torch.randperm(len(graphs)).tolist()]
     train, test = G.collate(graphs[:2000]).to(dev), G.collate(graphs[50:100]).to(dev)
     my_ip = pynq_shim.Overlay("gnn_all.bit").mmult_top_0      # MOL cell 11
+    my_ip.register_map.layer_count = args.layer_count          # layers per call (SG.py:1862): eval passes only
     model = M.GCN_PYNQ(64, 7, 2, my_ip).to(dev)               # MOL cell 18 (seed 12345 inside)
     opt = torch.optim.Adam(model.parameters(), lr=0.01)       # MOL cell 20
     crit = torch.nn.CrossEntropyLoss()
@@ -61,7 +65,7 @@ def main():
         print(f"Epoch: {epoch:03d}, Train Acc: {tr:.4f}, Test Acc: {te:.4f}, loss {float(loss.detach()):.4f}, "
               f"step {dt * 1e3:.2f} ms", flush=True)
     print(json.dumps({"best_test_acc": best, "final_test_acc": log[-1]["test_acc"], "epochs": args.epochs,
-                      "acc": args.acc, "reference": "0.76 at epoch 34 (notebook cell 20 output)"}))
+                      "acc": args.acc, "layer_count": args.layer_count, "reference": "0.76 at epoch 34 (notebook cell 20 output)"}))
 
 
 if __name__ == "__main__":

@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define SGX_VERSION 109
+#define SGX_VERSION 110
 
 typedef enum sgx_status {
     SGX_OK = 0,
@@ -46,7 +46,8 @@ typedef enum sgx_status {
     SGX_ERR_HIP = -5,          /* a HIP call or launch failed                        */
     SGX_ERR_CSR = -6,          /* sgx_csr_validate: rowPtr not monotone / index out of range */
     SGX_ERR_ALIGN = -7,        /* pointer or leading dimension not aligned as required */
-    SGX_ERR_SEEDS = -8         /* sgx_sample_neighbors: a seed repeats or lies outside [0, n_nodes) */
+    SGX_ERR_SEEDS = -8,        /* sgx_sample_neighbors: a seed repeats or lies outside [0, n_nodes) */
+    SGX_ERR_BLOCKS = -9        /* sgx_batch_plan_create: graph_ptr does not cut the adjacency into diagonal blocks */
 } sgx_status;
 
 /* Element type of B, D, values_fea, values_adj (MM.h:76-148 selects ONE type for all:
@@ -448,6 +449,81 @@ int sgx_sample_neighbors(const int32_t *rowPtr, const int32_t *columnIndex, int 
                          int32_t *node_map, int32_t *n_id, int32_t *out_rowPtr, int32_t *out_col, int32_t *edge_pos,
                          int64_t max_nodes, int64_t max_edges, int64_t *hop_nodes, int64_t *hop_edges,
                          void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- a batch of small graphs through the whole GCN stack in one launch -----------------------
+ * The reference's `layer_count` register: how many layers one hardware call processes (demo/<board>/config.py:5,
+ * SG.py:1862).  A PyG batch of graphs is sorted: graph g is the row segment [graph_ptr[g], graph_ptr[g+1]) and no edge
+ * leaves its graph, so the adjacency is block-diagonal.  One 256-thread workgroup then owns a run of whole graphs and
+ * forms every stage for them in LDS -- X.W, aggregation, activation, the next layer, the per-graph mean and the head --
+ * without exchanging anything with another workgroup (no flags, no grid barrier; the grid is the plan's group count).
+ *
+ * Semantics: exactly the chain
+ *     sgx_layer_forward(layer 0) -> ... -> sgx_layer_forward(layer n_layers-1) -> sgx_readout_mean_linear
+ * (GCN aggregate, SGX_ACC_F32, no plans), with the same rounding points:
+ *     H_l = dtype(X_l . W_l)            summed in fp32;  X_0 = the features, X_l = D_{l-1}
+ *     D_l = dtype(act_l(A . H_l))       act_l = ReLU where layer[l].relu, else identity
+ *     pooled[g][:] = fp32 mean of the rows of graph g of D_{n_layers-1};  logits = bias + W_head . pooled (fp32)
+ * and the same summation orders, so every output is bit-equal to that chain:
+ *   - aggregation: per row and column an fp32 fma chain over the row's stored entries in CSR order, starting from 0
+ *     (the sblock path of sgx_spmm_csr; a row is never split);
+ *   - sparse X.W (layer 0, gemm_mode 0): the same fma chain over the feature row's entries (sgx_xw_sparse without a plan,
+ *     or with one for every row it does not cut);
+ *   - dense X.W: the MFMA shape and K order of sgx_xw_dense (fp16: v_mfma_f32_16x16x32_f16, lane quad q holding k = 32 s
+ *     + 8 q .. + 7 of k-step s; fp32: v_mfma_f32_16x16x4_f32, step j of k-block s taking k = 16 s + 4 q + j), k-steps
+ *     in ascending order from 0: bit-equal, not merely within an ulp;
+ *   - readout: the order of sgx_readout_mean_linear (rows added in order, times 1 / n; the head's lane-strided fmas
+ *     over 64 lanes and an xor butterfly, then the bias).
+ * Where the plan fits (no graph over its row budget) and every width is within the fused kernel's limits
+ * (M_fea, P_w <= the plan's max_width <= 256; a sparse layer 0 may have any M_fea), one launch computes it all.
+ * Otherwise sgx_stack_forward runs the chained kernels through the workspace -- same results, so a call always
+ * works (single large graphs such as Cora take this path).  Quantised and GAT layers are not offered here. */
+typedef struct sgx_batch_plan sgx_batch_plan;
+
+typedef struct sgx_stack_layer {
+    int32_t gemm_mode;    /* layer 0: 0 = CSR features (rowPtr_fea ...), 1 = dense [n_rows][M_fea] in values_fea;
+                             layers >= 1 must be 1 (their input is the previous layer's D) */
+    int32_t relu;         /* 1: D = max(D, 0) on the rounded value, as sgx_layer_desc.relu */
+    int32_t M_fea, P_w;   /* columns of X_l and of D_l; layer l+1 has M_fea = layer l's P_w */
+    const void *B;        /* W^T [P_w][M_fea] in dtype, as sgx_layer_desc.B */
+    void *D;              /* optional: this layer's output [n_rows][ldd] in dtype (NULL = not written) */
+    int64_t ldd;          /* leading dimension of D in elements (0 = P_w) */
+} sgx_stack_layer;
+
+typedef struct sgx_stack_desc {
+    int32_t dtype, n_layers;                   /* SGX_F16 / SGX_F32; 1 .. 4 */
+    int32_t n_rows, n_graphs;                  /* must equal the plan's */
+    const int32_t *graph_ptr;                  /* [n_graphs + 1] device, the array the plan was built on */
+    const int32_t *rowPtr_adj, *columnIndex_adj; const void *values_adj;   /* [n_rows] x [n_rows] CSR, the plan's */
+    const int32_t *rowPtr_fea, *columnIndex_fea; const void *values_fea;   /* layer 0's input */
+    sgx_stack_layer layer[4];
+    int32_t C;                                 /* head width; 0 = no head (logits not written) */
+    const float *W_head, *bias;                /* [C][P_last] fp32, [C] fp32 (bias may be NULL) */
+    float *pooled, *logits;                    /* [n_graphs][P_last], [n_graphs][C] fp32; either may be NULL */
+    const sgx_batch_plan *plan;                /* from sgx_batch_plan_create */
+    void *workspace; size_t workspace_bytes;   /* sgx_stack_workspace_bytes(d), 256-byte aligned (0 on the fused path) */
+} sgx_stack_desc;
+
+/* Builds the plan on the device and reads back 16 bytes once (the stream is synchronised; not capturable):
+ *   - graph_ptr[0] == 0, monotone, graph_ptr[n_graphs] == n_rows;
+ *   - rowPtr_adj monotone, and every stored entry of a row of graph g has its column in graph g;
+ * SGX_ERR_BLOCKS when either fails.  Groups are contiguous runs of graphs of at most R rows, R = the LDS row budget for
+ * rows of max_width elements of `dtype`, at most 128 (sgx_batch_plan_rows); graph g joins group floor(graph_ptr[g] / S) with
+ * S = min(ceil(n_rows / 256), R - largest graph + 1) -- about one group per CU for a small batch, full groups for a large
+ * one.  A graph larger than R is recorded (sgx_batch_plan_fits = 0) and the batch then takes the chained path. */
+int sgx_batch_plan_create(int dtype, int n_rows, int n_graphs, const int32_t *graph_ptr, const int32_t *rowPtr_adj,
+                          const int32_t *columnIndex_adj, int max_width, sgx_batch_plan **plan, void *stream);
+int sgx_batch_plan_destroy(sgx_batch_plan *plan);
+/* the row budget R, the number of groups, the largest graph's rows, and whether every graph fits (1) or not (0) */
+int sgx_batch_plan_rows(const sgx_batch_plan *plan);
+int sgx_batch_plan_groups(const sgx_batch_plan *plan);
+int sgx_batch_plan_max_graph(const sgx_batch_plan *plan);
+int sgx_batch_plan_fits(const sgx_batch_plan *plan);
+/* 0 for the fused path, the chained path's scratch otherwise (and for a bad descriptor) */
+size_t sgx_stack_workspace_bytes(const sgx_stack_desc *d);
+/* Argument errors, returned before anything reaches the device: d, the plan, graph_ptr, the adjacency, layer 0's input,
+ * every B, W_head when C > 0: SGX_ERR_NULL; n_layers outside 1..4, n_rows / n_graphs not the plan's, widths that do not
+ * chain: SGX_ERR_SHAPE; a dtype other than SGX_F16 / SGX_F32, gemm_mode 0 past layer 0: SGX_ERR_UNSUPPORTED. */
+int sgx_stack_forward(const sgx_stack_desc *d, void *stream);
 
 /* A plain streaming copy (16 bytes per lane, non-temporal, each workgroup on a contiguous chunk), the kernel the attainable HBM rate of a device is
  * measured with next to the nominal 8 TB/s (bench.py reports it as roofline.stream_copy_GBps_this_device).

@@ -21,6 +21,7 @@ SGX_ORDER_REFERENCE, SGX_ORDER_AGGREGATE_FIRST = 0, 1      # sgx_layer_order
 SGX_QUANT_INT8 = 2                                          # sgx_quant.flags: integer operands on the int8 matrix cores
 SGX_QUANT_INT8_AUTO = 4                                     # ... where they are the faster form (M_fea > 128)
 SGX_ERR_SEEDS = -8                                          # sgx_sample_neighbors: a repeated or out-of-range seed
+SGX_ERR_BLOCKS = -9                                         # sgx_batch_plan_create: an edge leaves its graph / bad graph_ptr
 
 # every symbol include/sgx.h declares (tests/test_abi.py checks header and library against this)
 SYMBOLS = [
@@ -35,6 +36,8 @@ SYMBOLS = [
     "sgx_gat_aggregate_fill", "sgx_col_sums", "sgx_col_sums_scratch_bytes", "sgx_pack_rows",
     "sgx_code_bias", "sgx_quantize_codes_i8", "sgx_xw_dense_i8", "sgx_xw_dense_i8_workspace_bytes",
     "sgx_sample_workspace_bytes", "sgx_sample_neighbors",
+    "sgx_batch_plan_create", "sgx_batch_plan_destroy", "sgx_batch_plan_rows", "sgx_batch_plan_groups",
+    "sgx_batch_plan_max_graph", "sgx_batch_plan_fits", "sgx_stack_workspace_bytes", "sgx_stack_forward",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -79,6 +82,30 @@ class LayerDesc(ctypes.Structure):
         ("ev_agg_begin", ctypes.c_void_p), ("ev_agg_end", ctypes.c_void_p),
         ("quant", ctypes.POINTER(Quant)),
         ("order", ctypes.c_int32),
+    ]
+
+
+class StackLayer(ctypes.Structure):
+    """struct sgx_stack_layer -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("gemm_mode", ctypes.c_int32), ("relu", ctypes.c_int32), ("M_fea", ctypes.c_int32), ("P_w", ctypes.c_int32),
+        ("B", ctypes.c_void_p), ("D", ctypes.c_void_p), ("ldd", ctypes.c_int64),
+    ]
+
+
+class StackDesc(ctypes.Structure):
+    """struct sgx_stack_desc -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("dtype", ctypes.c_int32), ("n_layers", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_graphs", ctypes.c_int32),
+        ("graph_ptr", ctypes.c_void_p),
+        ("rowPtr_adj", ctypes.c_void_p), ("columnIndex_adj", ctypes.c_void_p), ("values_adj", ctypes.c_void_p),
+        ("rowPtr_fea", ctypes.c_void_p), ("columnIndex_fea", ctypes.c_void_p), ("values_fea", ctypes.c_void_p),
+        ("layer", StackLayer * 4),
+        ("C", ctypes.c_int32),
+        ("W_head", ctypes.c_void_p), ("bias", ctypes.c_void_p),
+        ("pooled", ctypes.c_void_p), ("logits", ctypes.c_void_p),
+        ("plan", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
 
 
@@ -185,6 +212,17 @@ def _load():
     lib.sgx_sample_neighbors.argtypes = [vp, vp, c_int, c_i64, vp, c_int, c_int, i32p, ctypes.c_uint64, ctypes.c_uint64,
                                          vp, vp, vp, vp, vp, c_i64, c_i64, i64p, i64p, vp, sz, vp]
     lib.sgx_sample_neighbors.restype = c_int
+    lib.sgx_batch_plan_create.argtypes = [c_int, c_int, c_int, vp, vp, vp, c_int, ctypes.POINTER(vp), vp]
+    lib.sgx_batch_plan_create.restype = c_int
+    lib.sgx_batch_plan_destroy.argtypes = [vp]
+    lib.sgx_batch_plan_destroy.restype = c_int
+    for name in ("sgx_batch_plan_rows", "sgx_batch_plan_groups", "sgx_batch_plan_max_graph", "sgx_batch_plan_fits"):
+        getattr(lib, name).argtypes = [vp]
+        getattr(lib, name).restype = c_int
+    lib.sgx_stack_workspace_bytes.argtypes = [ctypes.POINTER(StackDesc)]
+    lib.sgx_stack_workspace_bytes.restype = sz
+    lib.sgx_stack_forward.argtypes = [ctypes.POINTER(StackDesc), vp]
+    lib.sgx_stack_forward.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

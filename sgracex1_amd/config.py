@@ -27,8 +27,11 @@ _FLAGS = {
                                  "other association (sgx_layer_desc.order); no flag of this name in the reference"),
     "hidden_channels": (16, "default hidden width of the demo models"),
     "head_count": (1, "accepted, unused (the reference marks it 'not in use' as well)"),
+    "layer_count": (1, "layers per hardware call (SG.py:1862).  Live for the graph-classification model: with "
+                       "my_ip.register_map.layer_count >= 2, GCN_PYNQ's eval forward over a sorted batch of graphs runs "
+                       "both layers, the mean pool and the head in one call (sgx_stack_forward, bit-equal to the "
+                       "layer-by-layer path); training and every other model run one launch per stage"),
     # -- accepted, no effect on this path --------------------------------------------------------
-    "layer_count": (1, "layers per hardware call on the FPGA"),
     "load_weights": (1, "FPGA weight preload switch"),
     "stream_mode": (0, "FPGA streaming I/O switch"),
     "profiling": (0, "print per-layer host timings"),

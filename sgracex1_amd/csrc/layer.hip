@@ -327,6 +327,7 @@ extern "C" const char *sgx_status_string(int status)
     case SGX_ERR_CSR: return "CSR structure invalid";
     case SGX_ERR_ALIGN: return "pointer or leading dimension misaligned";
     case SGX_ERR_SEEDS: return "seed list holds a repeated or out-of-range node";
+    case SGX_ERR_BLOCKS: return "graph_ptr does not cut the adjacency into diagonal blocks";
     default: return "unknown status";
     }
 }

@@ -1,0 +1,591 @@
+// A batch of small graphs through the whole GCN stack in one launch (sgx_stack_forward; the reference's
+// `layer_count` register, SG.py:1862).
+//
+// A sorted PyG batch makes graph g the row segment [graph_ptr[g], graph_ptr[g+1]) of a block-diagonal adjacency.
+// The plan (sgx_batch_plan_create) checks that, and cuts the graphs into contiguous groups of at most R rows, R being
+// what two [R][pitch] tiles of LDS hold.  One 256-thread workgroup per group then runs every stage in LDS:
+//   X.W      layer 0: CSR feature rows against W^T in global (L2), or dense rows staged into LDS; layers >= 1 from the
+//            previous D in LDS.  Dense products on the matrix cores, with the operand layout and K order of
+//            xw_dense.hip, so H is bit-equal to sgx_xw_dense's.
+//   A.H      one fp32 fma chain per (row, column) over the row's stored entries in CSR order (the sblock order of
+//            spmm_csr.hip), columns rebased to the group's first row, gathers from LDS; D rounded and activated as
+//            finish_value does, written back into LDS (and to the caller's D when asked).
+//   readout  one wavefront per graph: the column means in row order, then the head's lane-strided fmas and the xor
+//            butterfly of readout.hip -- the same bits as sgx_readout_mean_linear.
+// Nothing crosses workgroups: no flags, no barriers beyond __syncthreads, no residency assumption.
+//
+// Where the plan does not fit (a graph over R rows) or a width is over the plan's, the same chain runs as separate
+// launches through the workspace, with the same kernels as the layer path.
+#include "sgx_device.h"
+
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef f16x8 f16x8_u __attribute__((aligned(2)));
+typedef f32x4 f32x4_u __attribute__((aligned(4)));
+
+struct sgx_batch_plan {
+    int dtype, n_rows, n_graphs, max_width;
+    int rows;            // row budget R
+    int n_groups;        // 0 when a graph is over R (or max_width over the fused kernel's limit)
+    int max_graph;
+    int fits;
+    int32_t *group_graph;   // [n_groups + 1] device: first graph of every group, then n_graphs
+};
+
+#ifndef SGX_STACK_ROWS_CAP
+// rows per group at most: smaller groups leave LDS for more workgroups per CU to hide the global reads' latency (a
+// million MUTAG graphs, fp16, 64 wide: 224 rows / 2 workgroups per CU 11.9 ms, 128 / 4: 7.6 ms, 64: 7.8 ms)
+#define SGX_STACK_ROWS_CAP 128
+#endif
+
+namespace {
+
+constexpr int kStackLds = 64 * 1024;   // bytes of LDS per workgroup: two workgroups per CU (160 KiB)
+constexpr int kStackMaxWidth = 256;
+constexpr int kMaxLayers = 4;
+constexpr int kTargetGroups = 256;     // one group per CU of an MI355X when the batch is small
+
+// LDS row pitch in elements: 16-byte fragments, plus 16 bytes so that consecutive rows start on different banks
+int lds_pitch(int dtype, int width)
+{
+    const int per16 = (int)(16 / sgx_elem_size(dtype));
+    return (width + per16 - 1) / per16 * per16 + per16;
+}
+
+int rows_budget(int dtype, int max_width)
+{
+    if (max_width < 1 || max_width > kStackMaxWidth) return 0;
+    const int row_bytes = 2 * lds_pitch(dtype, max_width) * (int)sgx_elem_size(dtype);     // X/D tile + H tile
+    const int rows = kStackLds / row_bytes / 16 * 16;                                         // whole 16-row MFMA tiles
+    return rows < SGX_STACK_ROWS_CAP ? rows : SGX_STACK_ROWS_CAP;
+}
+
+// ---- plan build ---------------------------------------------------------------------------------------------------
+struct PlanStatus {
+    int bad;          // graph_ptr does not cover [0, n_rows) monotonically, or an edge leaves its graph
+    int max_graph;
+    int pad[2];
+};
+
+__global__ void check_graph_ptr_kernel(int n_rows, int n_graphs, const int32_t *__restrict__ ptr, PlanStatus *st)
+{
+    const int g = blockIdx.x * blockDim.x + threadIdx.x;
+    if (g > n_graphs) return;
+    const int v = ptr[g];
+    if ((g == 0 && v != 0) || (g == n_graphs && v != n_rows)) atomicOr(&st->bad, 1);
+    if (g < n_graphs) {
+        const int size = ptr[g + 1] - v;
+        if (size < 0) atomicOr(&st->bad, 1);
+        else atomicMax(&st->max_graph, size);
+    }
+}
+
+// the graph of row r: the last g with ptr[g] <= r (binary search over ptr[0 .. n_graphs-1])
+__device__ __forceinline__ int graph_of(int r, int n_graphs, const int32_t *__restrict__ ptr)
+{
+    int lo = 0, hi = n_graphs - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (ptr[mid] <= r) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+__global__ void check_blocks_kernel(int n_rows, int n_graphs, const int32_t *__restrict__ ptr, const int32_t *__restrict__ rowptr,
+                                    const int32_t *__restrict__ col, PlanStatus *st)
+{
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= n_rows) return;
+    const int e0 = rowptr[r], e1 = rowptr[r + 1];
+    if (e1 < e0) {
+        atomicOr(&st->bad, 1);
+        return;
+    }
+    const int g = graph_of(r, n_graphs, ptr);
+    const int lo = ptr[g], hi = ptr[g + 1];
+    bool ok = true;
+    for (int e = e0; e < e1; ++e) {
+        const int c = col[e];
+        ok = ok && c >= lo && c < hi;
+    }
+    if (!ok) atomicOr(&st->bad, 1);
+}
+
+// group k = the graphs whose first row lies in [k S, (k+1) S); the last group also takes the empty graphs at n_rows
+__global__ void group_graphs_kernel(int n_groups, int n_graphs, int S, const int32_t *__restrict__ ptr, int32_t *__restrict__ first)
+{
+    const int k = blockIdx.x * blockDim.x + threadIdx.x;
+    if (k > n_groups) return;
+    if (k == n_groups) {
+        first[k] = n_graphs;
+        return;
+    }
+    const long long start = (long long)k * S;
+    int lo = 0, hi = n_graphs;                 // first g with ptr[g] >= start
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if ((long long)ptr[mid] < start) lo = mid + 1;
+        else hi = mid;
+    }
+    first[k] = k == 0 ? 0 : lo;
+}
+
+// ---- the fused kernel ---------------------------------------------------------------------------------------------
+struct StackArgs {
+    int n_layers, gemm0, C, pitch;
+    int relu[kMaxLayers], K[kMaxLayers], P[kMaxLayers];
+    const void *B[kMaxLayers];
+    void *D[kMaxLayers];
+    int64_t ldd[kMaxLayers];
+    const int32_t *graph_ptr, *group_graph;
+    const int32_t *rowptr, *col;
+    const void *val;
+    const int32_t *rowptr_f, *col_f;
+    const void *val_f;
+    const float *W_head, *bias;
+    float *pooled, *logits;
+    int rows;
+};
+
+template <typename T> struct Mfma;
+
+// fp16: a k-step of 32; lane quad lq holds k = k0 + 8 lq .. + 7 of its row (xw_dense_f16_kernel's layout)
+template <> struct Mfma<f16> {
+    static constexpr int kStep = 32;
+    typedef f16x8 frag;
+    static __device__ __forceinline__ frag load(const f16 *row, int k, int k_end, bool ok)
+    {
+        frag v = {0, 0, 0, 0, 0, 0, 0, 0};
+        if (!ok) return v;
+        if (k + 8 <= k_end) return *reinterpret_cast<const f16x8_u *>(row + k);
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (k + j < k_end) v[j] = row[k + j];
+        return v;
+    }
+    static __device__ __forceinline__ int lane_k(int k0, int lq) { return k0 + 8 * lq; }
+    static __device__ __forceinline__ f32x4 step(frag a, frag b, f32x4 acc)
+    {
+        return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, acc, 0, 0, 0);
+    }
+};
+
+// fp32: a k-block of 16; lane quad lq holds k = k0 + 4 lq .. + 3, step j of the block consumes element j
+// (xw_dense_f32_kernel's layout and step order)
+template <> struct Mfma<float> {
+    static constexpr int kStep = 16;
+    typedef f32x4 frag;
+    static __device__ __forceinline__ frag load(const float *row, int k, int k_end, bool ok)
+    {
+        frag v = {0, 0, 0, 0};
+        if (!ok) return v;
+        if (k + 4 <= k_end) return *reinterpret_cast<const f32x4_u *>(row + k);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (k + j < k_end) v[j] = row[k + j];
+        return v;
+    }
+    static __device__ __forceinline__ int lane_k(int k0, int lq) { return k0 + 4 * lq; }
+    static __device__ __forceinline__ f32x4 step(frag a, frag b, f32x4 acc)
+    {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[j], b[j], acc, 0, 0, 0);
+        return acc;
+    }
+};
+
+// H[0:nr][0:P] = X[0:nr][0:K] . Wt^T, X in LDS, Wt [P][K] in global.  A wavefront takes (16-row tile, 64-column
+// group) items: the MFMA forms the transposed tile H^T = Wt . X^T as in xw_dense.hip, so a lane ends with four
+// consecutive columns of one row.
+template <typename T>
+__device__ __forceinline__ void xw_dense_lds(const T *__restrict__ X, T *__restrict__ H, int pitch, int nr, int K, int P,
+                                             const T *__restrict__ Wt)
+{
+    typedef Mfma<T> M;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int l15 = lane & 15, lq = lane >> 4;
+    const int n_rt = (nr + 15) / 16, n_cg = (P + 63) / 64;
+    for (int item = wave; item < n_rt * n_cg; item += kBlock / 64) {
+        const int rt = item % n_rt, cg = item / n_rt;
+        const int m = rt * 16 + l15;
+        f32x4 acc[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) acc[nt] = (f32x4){0, 0, 0, 0};
+        for (int k0 = 0; k0 < K; k0 += M::kStep) {
+            const int k = M::lane_k(k0, lq);
+            const typename M::frag b = M::load(X + (size_t)m * pitch, k, K, m < nr);
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                if (cg * 64 + nt * 16 >= P) break;                       // (wave-uniform)
+                const int n = cg * 64 + nt * 16 + l15;
+                const typename M::frag a = M::load(Wt + (size_t)n * K, k, K, n < P);
+                acc[nt] = M::step(a, b, acc[nt]);
+            }
+        }
+        if (m >= nr) continue;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            const int n = cg * 64 + nt * 16 + 4 * lq;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (n + j < P) H[(size_t)m * pitch + n + j] = Elem<T>::from_f32(acc[nt][j]);
+        }
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void gcn_stack_kernel(StackArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char stack_lds[];
+    T *const XD = reinterpret_cast<T *>(stack_lds);                 // X_l, then D_l      [rows][pitch]
+    T *const Hs = XD + (size_t)a.rows * a.pitch;                    // H_l                [rows][pitch]
+    const int gf = a.group_graph[blockIdx.x], gl = a.group_graph[blockIdx.x + 1];
+    if (gf >= gl) return;
+    const int r0 = a.graph_ptr[gf], r1 = a.graph_ptr[gl];
+    const int nr = r1 - r0;
+    if (nr > a.rows) return;                                        // (the plan never makes such a group)
+    const int pitch = a.pitch;
+    const sgx_epilogue no_ep{0.0f, 0.0f, 0.0f, 0.0f};
+
+    for (int l = 0; l < a.n_layers; ++l) {
+        const int K = a.K[l], P = a.P[l];
+        const T *__restrict__ Wt = static_cast<const T *>(a.B[l]);
+        const int nch = (P + 3) / 4;                                // four columns per thread in the row-wise stages
+        if (l == 0 && a.gemm0 == 0) {
+            // H = X.W for a CSR X: per (row, column) an fp32 fma chain over the row's entries in CSR order
+            const T *__restrict__ vf = static_cast<const T *>(a.val_f);
+            for (int it = threadIdx.x; it < nr * nch; it += kBlock) {
+                const int i = it / nch, c0 = (it - i * nch) * 4;
+                float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                const int e0 = a.rowptr_f[r0 + i], e1 = a.rowptr_f[r0 + i + 1];
+                for (int e = e0; e < e1; ++e) {
+                    const int k = a.col_f[e];
+                    if ((unsigned)k >= (unsigned)K) continue;          // (the chained gather reads 0 there)
+                    const float x = Elem<T>::to_f32(vf[e]);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (c0 + u < P) acc[u] = __builtin_fmaf(x, Elem<T>::to_f32(Wt[(size_t)(c0 + u) * K + k]), acc[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u)
+                    if (c0 + u < P) Hs[(size_t)i * pitch + c0 + u] = Elem<T>::from_f32(acc[u]);
+            }
+        } else {
+            if (l == 0) {
+                // dense layer-0 rows of the group into LDS
+                const T *__restrict__ X = static_cast<const T *>(a.val_f) + (size_t)r0 * K;
+                for (int it = threadIdx.x; it < nr * K; it += kBlock) {
+                    const int i = it / K, k = it - i * K;
+                    XD[(size_t)i * pitch + k] = X[it];
+                }
+                __syncthreads();
+            }
+            xw_dense_lds<T>(XD, Hs, pitch, nr, K, P, Wt);
+        }
+        __syncthreads();
+
+        // D = act(A.H): rows of A from global, columns rebased to the group's first row, H gathered from LDS
+        {
+            const T *__restrict__ val = static_cast<const T *>(a.val);
+            T *__restrict__ Dg = static_cast<T *>(a.D[l]);
+            const int64_t ldd = a.ldd[l];
+            const int relu = a.relu[l];
+            for (int it = threadIdx.x; it < nr * nch; it += kBlock) {
+                const int i = it / nch, c0 = (it - i * nch) * 4;
+                float acc[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                const int e0 = a.rowptr[r0 + i], e1 = a.rowptr[r0 + i + 1];
+                for (int e = e0; e < e1; ++e) {
+                    const int c = a.col[e] - r0;
+                    if ((unsigned)c >= (unsigned)nr) continue;         // (the plan admits no such edge)
+                    const float w = Elem<T>::to_f32(val[e]);
+                    const T *h = Hs + (size_t)c * pitch + c0;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) acc[u] = __builtin_fmaf(w, Elem<T>::to_f32(h[u]), acc[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < 4; ++u) {
+                    if (c0 + u >= P) break;
+                    const T v = finish_value<T>(acc[u], relu, no_ep);
+                    XD[(size_t)i * pitch + c0 + u] = v;
+                    if (Dg) Dg[(int64_t)(r0 + i) * ldd + c0 + u] = v;
+                }
+            }
+        }
+        __syncthreads();
+    }
+
+    // readout: one wavefront per graph; lane j of the row sums holds columns j, j + 64, ... -- the columns its head
+    // fmas read, so the means stay in registers
+    if (!a.pooled && !a.logits) return;
+    const int F = a.P[a.n_layers - 1];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    for (int g = gf + wave; g < gl; g += kBlock / 64) {
+        const int s0 = a.graph_ptr[g] - r0, s1 = a.graph_ptr[g + 1] - r0;
+        const float inv = s1 > s0 ? 1.0f / (float)(s1 - s0) : 0.0f;
+        float mean[kStackMaxWidth / 64];
+#pragma unroll
+        for (int q = 0; q < kStackMaxWidth / 64; ++q) {
+            const int j = lane + 64 * q;
+            mean[q] = 0.0f;
+            if (j < F) {
+                float s = 0.0f;
+                for (int r = s0; r < s1; ++r) s += Elem<T>::to_f32(XD[(size_t)r * pitch + j]);
+                s *= inv;
+                mean[q] = s;
+                if (a.pooled) a.pooled[(int64_t)g * F + j] = s;
+            }
+        }
+        if (!a.logits) continue;
+        for (int c = 0; c < a.C; ++c) {
+            float s = 0.0f;
+#pragma unroll
+            for (int q = 0; q < kStackMaxWidth / 64; ++q) {
+                const int j = lane + 64 * q;
+                if (j < F) s = __builtin_fmaf(a.W_head[(int64_t)c * F + j], mean[q], s);
+            }
+#pragma unroll
+            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            if (lane == 0) a.logits[(int64_t)g * a.C + c] = s + (a.bias ? a.bias[c] : 0.0f);
+        }
+    }
+}
+
+// ---- descriptor checks and the two paths ----------------------------------------------------------------------------
+int64_t layer_ldd(const sgx_stack_layer &L) { return L.ldd == 0 ? L.P_w : L.ldd; }
+
+int check_stack(const sgx_stack_desc *d)
+{
+    if (!d) return SGX_ERR_NULL;
+    if (d->n_layers < 1 || d->n_layers > kMaxLayers) return SGX_ERR_SHAPE;
+    if (d->dtype != SGX_F16 && d->dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;
+    if (!d->plan) return SGX_ERR_NULL;
+    if (d->n_rows != d->plan->n_rows || d->n_graphs != d->plan->n_graphs) return SGX_ERR_SHAPE;
+    if (d->C < 0) return SGX_ERR_SHAPE;
+    for (int l = 0; l < d->n_layers; ++l) {
+        const sgx_stack_layer &L = d->layer[l];
+        if (L.gemm_mode != 0 && L.gemm_mode != 1) return SGX_ERR_UNSUPPORTED;
+        if (l > 0 && L.gemm_mode != 1) return SGX_ERR_UNSUPPORTED;
+        if (L.M_fea < 1 || L.P_w < 1 || L.ldd < 0 || (L.ldd != 0 && L.ldd < L.P_w)) return SGX_ERR_SHAPE;
+        if (l > 0 && L.M_fea != d->layer[l - 1].P_w) return SGX_ERR_SHAPE;
+        if (!L.B) return SGX_ERR_NULL;
+    }
+    if (d->C > 0 && !d->W_head) return SGX_ERR_NULL;
+    if (d->n_graphs > 0 && !d->graph_ptr) return SGX_ERR_NULL;
+    if (d->n_rows > 0) {
+        if (!d->rowPtr_adj || !d->columnIndex_adj || !d->values_adj || !d->values_fea) return SGX_ERR_NULL;
+        if (d->layer[0].gemm_mode == 0 && (!d->rowPtr_fea || !d->columnIndex_fea)) return SGX_ERR_NULL;
+    }
+    return SGX_OK;
+}
+
+bool fused_applies(const sgx_stack_desc *d)
+{
+    const sgx_batch_plan *p = d->plan;
+    if (!p->fits || p->n_groups < 1 || p->dtype != d->dtype || p->max_width > kStackMaxWidth) return false;
+    for (int l = 0; l < d->n_layers; ++l) {
+        const sgx_stack_layer &L = d->layer[l];
+        if (L.P_w > p->max_width) return false;
+        if ((l > 0 || L.gemm_mode == 1) && L.M_fea > p->max_width) return false;
+    }
+    return true;
+}
+
+struct ChainCarve {
+    size_t h_off, d_off, w_off, total;
+    int64_t ld;          // pitch of H and of the intermediate D
+};
+
+ChainCarve chain_carve(const sgx_stack_desc *d)
+{
+    ChainCarve c;
+    const size_t es = sgx_elem_size(d->dtype);
+    int pmax = 1;
+    for (int l = 0; l < d->n_layers; ++l) pmax = d->layer[l].P_w > pmax ? d->layer[l].P_w : pmax;
+    c.ld = sgx_ldh(d->dtype, pmax);
+    size_t off = 0;
+    c.h_off = off; off += sgx_align_up((size_t)d->n_rows * c.ld * es, 256);
+    c.d_off = off; off += sgx_align_up((size_t)d->n_rows * c.ld * es, 256);
+    c.w_off = off;
+    if (d->layer[0].gemm_mode == 0) off += sgx_align_up((size_t)d->layer[0].M_fea * sgx_ldh(d->dtype, d->layer[0].P_w) * es, 256);
+    c.total = off;
+    return c;
+}
+
+// the chain sgx_layer_forward x n_layers -> sgx_readout_mean_linear with the same kernels, no plans
+int run_chain(const sgx_stack_desc *d, hipStream_t s)
+{
+    const ChainCarve c = chain_carve(d);
+    if (!d->workspace || d->workspace_bytes < c.total) return SGX_ERR_WORKSPACE;
+    if ((uintptr_t)d->workspace % 256 != 0) return SGX_ERR_ALIGN;
+    char *ws = static_cast<char *>(d->workspace);
+    void *H = ws + c.h_off;
+    const void *X = d->values_fea;
+    int64_t ldx = d->layer[0].M_fea;
+    int rc;
+    for (int l = 0; l < d->n_layers; ++l) {
+        const sgx_stack_layer &L = d->layer[l];
+        if (l == 0 && L.gemm_mode == 0) {
+            const int64_t ldw = sgx_ldh(d->dtype, L.P_w);
+            void *W = ws + c.w_off;
+            rc = sgx_transpose(d->dtype, L.P_w, L.M_fea, L.B, L.M_fea, W, ldw, s);              // B [P][M] -> W [M][ldw]
+            if (rc != SGX_OK) return rc;
+            rc = sgx_spmm_launch(d->dtype, SGX_ACC_F32, 1, /*relu*/0, d->n_rows, L.M_fea, L.P_w, d->rowPtr_fea,
+                                 d->columnIndex_fea, d->values_fea, W, ldw, H, c.ld, nullptr, nullptr, 0, s, nullptr, nullptr,
+                                 0, /*fea_stage*/true);
+        } else {
+            rc = sgx_xw_dense_ep(d->dtype, SGX_ACC_F32, 1, d->n_rows, L.M_fea, L.P_w, X, ldx, L.B, L.M_fea, H, c.ld, s,
+                                 sgx_no_epilogue());
+        }
+        if (rc != SGX_OK) return rc;
+        void *D = L.D ? L.D : ws + c.d_off;
+        const int64_t ldd = L.D ? layer_ldd(L) : c.ld;
+        rc = sgx_spmm_launch(d->dtype, SGX_ACC_F32, 1, L.relu ? 1 : 0, d->n_rows, d->n_rows, L.P_w, d->rowPtr_adj,
+                             d->columnIndex_adj, d->values_adj, H, c.ld, D, ldd, nullptr, nullptr, 0, s);
+        if (rc != SGX_OK) return rc;
+        X = D;
+        ldx = ldd;
+    }
+    float *logits = d->C > 0 ? d->logits : nullptr;
+    if (!d->pooled && !logits) return SGX_OK;
+    return sgx_readout_mean_linear(d->dtype, d->n_graphs, d->layer[d->n_layers - 1].P_w, logits ? d->C : 0, X, ldx,
+                                   d->graph_ptr, d->W_head, d->bias, d->pooled, logits, s);
+}
+
+int run_fused(const sgx_stack_desc *d, hipStream_t s)
+{
+    const sgx_batch_plan *p = d->plan;
+    StackArgs a;
+    a.n_layers = d->n_layers;
+    a.gemm0 = d->layer[0].gemm_mode;
+    a.C = d->logits ? d->C : 0;
+    a.pitch = lds_pitch(d->dtype, p->max_width);
+    a.rows = p->rows;
+    for (int l = 0; l < kMaxLayers; ++l) {
+        const bool live = l < d->n_layers;
+        a.relu[l] = live ? (d->layer[l].relu ? 1 : 0) : 0;
+        a.K[l] = live ? d->layer[l].M_fea : 0;
+        a.P[l] = live ? d->layer[l].P_w : 0;
+        a.B[l] = live ? d->layer[l].B : nullptr;
+        a.D[l] = live ? d->layer[l].D : nullptr;
+        a.ldd[l] = live ? layer_ldd(d->layer[l]) : 0;
+    }
+    a.graph_ptr = d->graph_ptr;
+    a.group_graph = p->group_graph;
+    a.rowptr = d->rowPtr_adj;
+    a.col = d->columnIndex_adj;
+    a.val = d->values_adj;
+    a.rowptr_f = d->rowPtr_fea;
+    a.col_f = d->columnIndex_fea;
+    a.val_f = d->values_fea;
+    a.W_head = d->W_head;
+    a.bias = d->bias;
+    a.pooled = d->pooled;
+    a.logits = a.C > 0 ? d->logits : nullptr;
+    const size_t lds = (size_t)2 * p->rows * a.pitch * sgx_elem_size(d->dtype);
+    if (d->dtype == SGX_F16)
+        hipLaunchKernelGGL(gcn_stack_kernel<f16>, dim3(p->n_groups), dim3(kBlock), lds, s, a);
+    else
+        hipLaunchKernelGGL(gcn_stack_kernel<float>, dim3(p->n_groups), dim3(kBlock), lds, s, a);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}
+
+}  // namespace
+
+extern "C" int sgx_batch_plan_create(int dtype, int n_rows, int n_graphs, const int32_t *graph_ptr, const int32_t *rowPtr_adj,
+                                     const int32_t *columnIndex_adj, int max_width, sgx_batch_plan **plan, void *stream)
+{
+    if (!plan) return SGX_ERR_NULL;
+    *plan = nullptr;
+    if (n_rows < 0 || n_graphs < 0 || max_width < 1) return SGX_ERR_SHAPE;
+    if (dtype != SGX_F16 && dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;
+    if ((n_rows > 0 || n_graphs > 0) && !graph_ptr) return SGX_ERR_NULL;
+    if (n_rows > 0 && (!rowPtr_adj || !columnIndex_adj)) return SGX_ERR_NULL;
+    sgx_batch_plan *p = new sgx_batch_plan;
+    p->dtype = dtype;
+    p->n_rows = n_rows;
+    p->n_graphs = n_graphs;
+    p->max_width = max_width;
+    p->rows = rows_budget(dtype, max_width);
+    p->n_groups = 0;
+    p->max_graph = 0;
+    p->fits = 1;
+    p->group_graph = nullptr;
+    if (n_rows == 0 && n_graphs == 0) {             // nothing to check or to run
+        *plan = p;
+        return SGX_OK;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    PlanStatus *st = nullptr;
+    auto fail = [&](int rc) {
+        if (st) (void)hipFreeAsync(st, s);
+        delete p;
+        return rc;
+    };
+    if (hipMallocAsync((void **)&st, sizeof(PlanStatus), s) != hipSuccess) return fail(SGX_ERR_HIP);
+    if (hipMemsetAsync(st, 0, sizeof(PlanStatus), s) != hipSuccess) return fail(SGX_ERR_HIP);
+    hipLaunchKernelGGL(check_graph_ptr_kernel, dim3((unsigned)((n_graphs + 1 + 255) / 256)), dim3(256), 0, s, n_rows, n_graphs,
+                       graph_ptr, st);
+    if (hipGetLastError() != hipSuccess) return fail(SGX_ERR_HIP);
+    if (n_rows > 0 && n_graphs > 0) {
+        hipLaunchKernelGGL(check_blocks_kernel, dim3((unsigned)((n_rows + 255) / 256)), dim3(256), 0, s, n_rows, n_graphs, graph_ptr,
+                           rowPtr_adj, columnIndex_adj, st);
+        if (hipGetLastError() != hipSuccess) return fail(SGX_ERR_HIP);
+    }
+    PlanStatus host;
+    if (hipMemcpyAsync(&host, st, sizeof(PlanStatus), hipMemcpyDeviceToHost, s) != hipSuccess) return fail(SGX_ERR_HIP);
+    if (hipStreamSynchronize(s) != hipSuccess) return fail(SGX_ERR_HIP);      // the one read-back (16 bytes)
+    (void)hipFreeAsync(st, s);
+    st = nullptr;
+    if (host.bad) return fail(SGX_ERR_BLOCKS);
+    p->max_graph = host.max_graph;
+    p->fits = (p->rows > 0 && host.max_graph <= p->rows) ? 1 : 0;
+    if (p->fits && n_graphs > 0) {
+        // S = the window of first rows a group takes: its rows are at most S - 1 + the largest graph <= R
+        const int target = (n_rows + kTargetGroups - 1) / kTargetGroups;
+        int S = p->rows - host.max_graph + 1;
+        if (target < S) S = target;
+        if (S < 1) S = 1;
+        p->n_groups = n_rows > 0 ? (n_rows + S - 1) / S : 1;
+        if (hipMalloc((void **)&p->group_graph, sizeof(int32_t) * ((size_t)p->n_groups + 1)) != hipSuccess) return fail(SGX_ERR_HIP);
+        hipLaunchKernelGGL(group_graphs_kernel, dim3((unsigned)((p->n_groups + 1 + 255) / 256)), dim3(256), 0, s, p->n_groups, n_graphs,
+                           S, graph_ptr, p->group_graph);
+        if (hipGetLastError() != hipSuccess) {
+            (void)hipFree(p->group_graph);
+            return fail(SGX_ERR_HIP);
+        }
+    }
+    *plan = p;
+    return SGX_OK;
+}
+
+extern "C" int sgx_batch_plan_destroy(sgx_batch_plan *plan)
+{
+    if (!plan) return SGX_OK;
+    if (plan->group_graph) SGX_HIP_CHECK(hipFree(plan->group_graph));
+    delete plan;
+    return SGX_OK;
+}
+
+extern "C" int sgx_batch_plan_rows(const sgx_batch_plan *plan) { return plan ? plan->rows : SGX_ERR_NULL; }
+extern "C" int sgx_batch_plan_groups(const sgx_batch_plan *plan) { return plan ? plan->n_groups : SGX_ERR_NULL; }
+extern "C" int sgx_batch_plan_max_graph(const sgx_batch_plan *plan) { return plan ? plan->max_graph : SGX_ERR_NULL; }
+extern "C" int sgx_batch_plan_fits(const sgx_batch_plan *plan) { return plan ? plan->fits : SGX_ERR_NULL; }
+
+extern "C" size_t sgx_stack_workspace_bytes(const sgx_stack_desc *d)
+{
+    if (check_stack(d) != SGX_OK) return 0;
+    if (fused_applies(d)) return 0;
+    return chain_carve(d).total;
+}
+
+extern "C" int sgx_stack_forward(const sgx_stack_desc *d, void *stream)
+{
+    const int rc = check_stack(d);
+    if (rc != SGX_OK) return rc;
+    if (d->n_rows == 0 && d->n_graphs == 0) return SGX_OK;
+    hipStream_t s = (hipStream_t)stream;
+    return fused_applies(d) ? run_fused(d, s) : run_chain(d, s);
+}

@@ -813,3 +813,154 @@ def sample_neighbors(csr, seeds, fanouts, seed=0, step=0, gather_values=False):
     val = csr.val[pos[:E].long()] if gather_values else torch.ones(E, dtype=torch.float32, device=dev)
     adj = Csr(rowptr[:N + 1], col[:E], val, N)
     return Sample(n_id[:N], adj, pos[:E], B, hop_nodes[:], hop_edges[:])
+
+
+# ---- a batch of small graphs through the whole GCN stack in one launch (sgx_stack_forward) ----------------------------
+class BatchPlan:
+    """Groups of whole graphs for sgx_stack_forward (sgx_batch_plan): graph_ptr and the adjacency are checked on the
+    device to be block-diagonal (SgxError SGX_ERR_BLOCKS otherwise) and the graphs are cut into runs of at most `rows`
+    rows, what the fused kernel keeps in LDS for layers up to max_width columns.  `fits` is False when a graph is larger
+    than that; the stack then takes the chained kernels.  One stream synchronisation per plan."""
+
+    def __init__(self, adj, graph_ptr, max_width):
+        _dev(graph_ptr, "graph_ptr")
+        if graph_ptr.dtype != torch.int32:
+            raise TypeError("graph_ptr must be int32")
+        self.dtype = adj.val.dtype
+        self.n_rows, self.n_graphs, self.max_width = adj.n_rows, graph_ptr.numel() - 1, int(max_width)
+        h = ctypes.c_void_p()
+        check(lib.sgx_batch_plan_create(dtype_code(self.dtype), self.n_rows, self.n_graphs, _ptr(graph_ptr), _ptr(adj.rowptr),
+                                        _ptr(adj.col), self.max_width, ctypes.byref(h), _stream()), "sgx_batch_plan_create")
+        self._h = h
+
+    @staticmethod
+    def cached(adj, graph_ptr, max_width):
+        """The plan of (adj, graph_ptr, max_width), kept on the adjacency's column array while both stay unchanged; None
+        when the batch is not block-diagonal under graph_ptr (remembered too, so that a caller falls back without a
+        device sync per call)."""
+        hit = cached_on(adj.col, ("batch_plan", adj.val.dtype, int(max_width)), lambda: [None, -1, None])
+        if hit[0] is not graph_ptr or hit[1] != graph_ptr._version:
+            try:
+                plan = BatchPlan(adj, graph_ptr, max_width)
+            except _lib.SgxError as e:
+                if e.status != _lib.SGX_ERR_BLOCKS:
+                    raise
+                plan = None
+            hit[:] = [graph_ptr, graph_ptr._version, plan]
+        return hit[2]
+
+    @property
+    def handle(self):
+        return self._h
+
+    @property
+    def rows(self):
+        return lib.sgx_batch_plan_rows(self._h)
+
+    @property
+    def groups(self):
+        return lib.sgx_batch_plan_groups(self._h)
+
+    @property
+    def max_graph(self):
+        return lib.sgx_batch_plan_max_graph(self._h)
+
+    @property
+    def fits(self):
+        return bool(lib.sgx_batch_plan_fits(self._h))
+
+    def __del__(self, _destroy=lib.sgx_batch_plan_destroy):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _destroy(h)
+
+
+def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, head_bias=None, want_layer_outputs=False,
+                      want_pooled=False, plan=None):
+    """n GCN layers, the per-graph mean and a Linear head in one call (sgx_stack_forward) -- exactly the chain
+    layer_forward x n -> readout_mean_linear, bit for bit (include/sgx.h), in one launch where the batch's graphs fit
+    the plan, through the chained kernels otherwise.
+
+    adj: Csr [N, N] whose graphs are the row segments of graph_ptr (int32 [G+1]; None = one graph of all N rows);
+    x: Csr features (layer 0 sparse) or a dense [N, M] tensor; weights_t: 1 to 4 tensors W_l^T [P_l, M_l] in adj's
+    dtype; relus: one flag per layer.  Returns logits [G, C] fp32 with a head ((logits, pooled) with want_pooled), the
+    pooled means [G, P_last] fp32 without one, or with graph_ptr None the last layer's output [N, P_last]; with
+    want_layer_outputs also the list of every layer's output D_l [N, P_l]."""
+    n = len(weights_t)
+    if not 1 <= n <= 4 or len(relus) != n:
+        raise ValueError("gcn_stack_forward takes 1 to 4 layers and one relu flag per layer")
+    dtype = adj.val.dtype
+    code = dtype_code(dtype)
+    N, dev = adj.n_rows, adj.val.device
+    if adj.n_cols != N:
+        raise ValueError("the adjacency must be square")
+    readout = graph_ptr is not None
+    if graph_ptr is None:
+        graph_ptr = cached_on(adj.rowptr, ("one_graph_ptr",),
+                              lambda: torch.tensor([0, N], dtype=torch.int32, device=dev))
+    _dev(graph_ptr, "graph_ptr")
+    d = _lib.StackDesc()
+    d.dtype, d.n_layers, d.n_rows, d.n_graphs = code, n, N, graph_ptr.numel() - 1
+    d.graph_ptr = graph_ptr.data_ptr()
+    d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
+    sparse = isinstance(x, Csr)
+    if sparse:
+        if x.val.dtype != dtype or x.n_rows != N:
+            raise ValueError("feature CSR does not match the adjacency")
+        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = x.rowptr.data_ptr(), x.col.data_ptr(), x.val.data_ptr()
+        k_in = x.n_cols
+    else:
+        _dev(x, "x")
+        if x.dtype != dtype or x.dim() != 2 or x.shape[0] != N:
+            raise ValueError(f"dense features must be [{N}, M] {dtype}")
+        d.values_fea = x.data_ptr()
+        k_in = x.shape[1]
+    outs = []
+    widths = []
+    for l, (Wt, relu) in enumerate(zip(weights_t, relus)):
+        _dev(Wt, f"weights_t[{l}]")
+        P, M = Wt.shape
+        if Wt.dtype != dtype or M != k_in:
+            raise ValueError(f"weights_t[{l}] must be [P, {k_in}] {dtype}, got {tuple(Wt.shape)} {Wt.dtype}")
+        L = d.layer[l]
+        L.gemm_mode = 0 if (l == 0 and sparse) else 1
+        L.relu, L.M_fea, L.P_w, L.B = int(bool(relu)), M, P, Wt.data_ptr()
+        if want_layer_outputs or (not readout and l == n - 1):
+            D = torch.empty((N, P), dtype=dtype, device=dev)
+            L.D, L.ldd = D.data_ptr(), P
+            outs.append(D)
+        widths += [P] if (l == 0 and sparse) else [P, M]
+        k_in = P
+    G = d.n_graphs
+    pooled = logits = None
+    if readout:
+        if head_weight is not None:
+            w = _dev(head_weight.detach().float().contiguous(), "head_weight")
+            if w.dim() != 2 or w.shape[1] != k_in:
+                raise ValueError(f"head_weight must be [C, {k_in}]")
+            d.C, d.W_head = w.shape[0], w.data_ptr()
+            if head_bias is not None:
+                b = _dev(head_bias.detach().float().contiguous(), "head_bias")
+                d.bias = b.data_ptr()
+            logits = torch.empty((G, d.C), dtype=torch.float32, device=dev)
+            d.logits = logits.data_ptr()
+        if head_weight is None or want_pooled:
+            pooled = torch.empty((G, k_in), dtype=torch.float32, device=dev)
+            d.pooled = pooled.data_ptr()
+    if plan is None:
+        plan = BatchPlan.cached(adj, graph_ptr, max(widths))
+        if plan is None:
+            check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create")
+    d.plan = plan.handle
+    nbytes = lib.sgx_stack_workspace_bytes(ctypes.byref(d))
+    if nbytes:
+        ws = _workspace(dev, nbytes)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(lib.sgx_stack_forward(ctypes.byref(d), _stream()), "sgx_stack_forward")
+    if not readout:
+        out = outs[-1]
+    elif logits is not None:
+        out = (logits, pooled) if want_pooled else logits
+    else:
+        out = pooled
+    return (out, outs) if want_layer_outputs else out

@@ -1,0 +1,106 @@
+#!/usr/bin/env python3
+"""What one call for the whole GCN stack (sgx_stack_forward, csrc/stack.hip) saves against one launch per stage.
+
+Two workloads, eval forward of MOL cell 18's model (7 -> 64 ReLU -> 64, mean pool, 64 -> 2 head), fp16:
+  mutag    the 188-graph MUTAG batch;
+  big      MUTAG's graphs repeated to --graphs graphs (default 1,000,160: 5,320 copies, 17.9 M nodes, 39.6 M edges).
+Each is timed chained (ops.layer_forward x 2 + ops.readout_mean_linear, plans as the layer path builds them) and fused
+(ops.gcn_stack_forward), eagerly and replayed from a hipGraph, with hipEvents around --reps calls after warm-up (median
+of --trials); the outputs of the two are checked bit-equal first.  One JSON line per measurement.
+
+    python tools/stack_probe.py > stack.jsonl
+    python tools/stack_probe.py --only big --form fused --reps 5 --trials 1    # one form only, for a counter run
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from sgracex1_amd import graphed, molecule_gcn as M, ops, pyg_lite as G  # noqa: E402
+
+DT = torch.float16
+
+
+def mutag_batch(copies, dev):
+    raw = np.load(os.path.join(ROOT, "tests", "golden", "mutag_raw.npz"))
+    b = G.collate(G.load_tu_raw(raw["A"], raw["graph_indicator"], raw["graph_labels"], raw["node_labels"]))
+    n, e = b.num_nodes, b.edge_index.shape[1]
+    k = torch.arange(copies).repeat_interleave(e)
+    ei = b.edge_index.repeat(1, copies) + (k * n).unsqueeze(0)
+    batch = b.batch.repeat(copies) + torch.arange(copies).repeat_interleave(n) * b.num_graphs
+    return b.x.repeat(copies, 1).to(dev), ei.to(dev), batch.to(dev), b.num_graphs * copies
+
+
+def setup(copies, dev):
+    x, ei, batch, n_graphs = mutag_batch(copies, dev)
+    adj = ops.csr_from_edge_index(ei, x.shape[0], dtype=DT)
+    fea = M.as_csr(x, DT)
+    ptr = ops.graph_ptr_of(batch)
+    torch.manual_seed(12345)
+    w1, w2 = (torch.randn(64, 7, device=dev) * 0.4).to(DT), (torch.randn(64, 64, device=dev) * 0.15).to(DT)
+    hw, hb = torch.randn(2, 64, device=dev), torch.randn(2, device=dev)
+
+    def chained():
+        d1 = ops.layer_forward(adj, fea, w1, relu=True)
+        d2 = ops.layer_forward(adj, d1, w2, relu=False)
+        return ops.readout_mean_linear(d2, ptr, hw, hb)
+
+    def fused():
+        return ops.gcn_stack_forward(adj, fea, [w1, w2], [True, False], ptr, hw, hb)
+
+    return dict(chained=chained, fused=fused, n_graphs=n_graphs, nodes=x.shape[0], edges=adj.nnz, adj=adj, ptr=ptr)
+
+
+def time_ms(fn, reps, trials):
+    out = []
+    for _ in range(trials):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        for _ in range(reps):
+            fn()
+        b.record()
+        b.synchronize()
+        out.append(a.elapsed_time(b) / reps)
+    return float(np.median(out))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=["mutag", "big"], default=None)
+    ap.add_argument("--form", choices=["chained", "fused"], default=None)
+    ap.add_argument("--graphs", type=int, default=1_000_160)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--trials", type=int, default=5)
+    args = ap.parse_args()
+    dev = torch.device("cuda")
+    work = [("mutag", 1), ("big", max(1, args.graphs // 188))]
+    for name, copies in work:
+        if args.only and name != args.only:
+            continue
+        s = setup(copies, dev)
+        plan = ops.BatchPlan.cached(s["adj"], s["ptr"], 64)
+        assert torch.equal(s["chained"]().view(torch.int32), s["fused"]().view(torch.int32)), "fused != chained"
+        reps = args.reps if name == "mutag" else max(1, args.reps // 10)
+        for form in ("chained", "fused"):
+            if args.form and form != args.form:
+                continue
+            fn = s[form]
+            for _ in range(3):
+                fn()
+            rec = {"workload": name, "form": form, "graphs": s["n_graphs"], "nodes": s["nodes"], "edges": s["edges"],
+                   "plan_groups": plan.groups, "plan_rows": plan.rows, "dtype": "f16"}
+            rec["eager_ms"] = time_ms(fn, reps, args.trials)
+            g = graphed.Graphed(fn)
+            rec["graph_ms"] = time_ms(g, reps, args.trials)
+            rec["graphs_per_s_eager"] = s["n_graphs"] / (rec["eager_ms"] * 1e-3)
+            print(json.dumps(rec), flush=True)
+            del g
+
+
+if __name__ == "__main__":
+    main()
