@@ -5,9 +5,11 @@ train on all 188 graphs in one batch, test on graphs [50:100], hidden 64, Adam l
 entropy, fp16 layer kernels in forward, device kernels in backward.  The notebook's recorded run
 reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epoch 36").
 
-    python examples/molecule_gcn_train.py [--epochs 60] [--acc 0] [--layer-count 2]
+    python examples/molecule_gcn_train.py [--epochs 60] [--acc 0] [--layer-count 2 [--train-stack]]
         --acc 0 = the torch twin; --layer-count 2 = the accuracy passes (eval) run the whole model in one call
-        (register layer_count, sgx_stack_forward); training steps run layer by layer either way
+        (register layer_count, sgx_stack_forward); training steps run layer by layer unless --train-stack, which
+        (with --layer-count >= 2) runs each step's two layers and the pooling as one forward call (sgx_stack_forward)
+        and one backward call (sgx_stack_backward) -- GCN_PYNQ(train_stack=True)
 """
 import argparse
 import json
@@ -29,7 +31,10 @@ def main():
     ap.add_argument("--epochs", type=int, default=60)
     ap.add_argument("--acc", type=int, default=1)
     ap.add_argument("--layer-count", type=int, default=1)
+    ap.add_argument("--train-stack", action="store_true")
     args = ap.parse_args()
+    if args.train_stack and args.layer_count < 2:
+        ap.error("--train-stack needs --layer-count >= 2")
     dev = torch.device("cuda")
     raw = np.load(os.path.join(ROOT, "tests", "golden", "mutag_raw.npz"))
     graphs = G.load_tu_raw(raw["A"], raw["graph_indicator"], raw["graph_labels"], raw["node_labels"])
@@ -37,8 +42,8 @@ def main():
     graphs = [graphs[i] for i in torch.randperm(len(graphs)).tolist()]
     train, test = G.collate(graphs[:2000]).to(dev), G.collate(graphs[50:100]).to(dev)
     my_ip = pynq_shim.Overlay("gnn_all.bit").mmult_top_0      # MOL cell 11
-    my_ip.register_map.layer_count = args.layer_count          # layers per call (SG.py:1862): eval passes only
-    model = M.GCN_PYNQ(64, 7, 2, my_ip).to(dev)               # MOL cell 18 (seed 12345 inside)
+    my_ip.register_map.layer_count = args.layer_count          # layers per call (SG.py:1862)
+    model = M.GCN_PYNQ(64, 7, 2, my_ip, train_stack=args.train_stack).to(dev)   # MOL cell 18 (seed 12345 inside)
     opt = torch.optim.Adam(model.parameters(), lr=0.01)       # MOL cell 20
     crit = torch.nn.CrossEntropyLoss()
 
@@ -65,7 +70,7 @@ def main():
         print(f"Epoch: {epoch:03d}, Train Acc: {tr:.4f}, Test Acc: {te:.4f}, loss {float(loss.detach()):.4f}, "
               f"step {dt * 1e3:.2f} ms", flush=True)
     print(json.dumps({"best_test_acc": best, "final_test_acc": log[-1]["test_acc"], "epochs": args.epochs,
-                      "acc": args.acc, "layer_count": args.layer_count, "reference": "0.76 at epoch 34 (notebook cell 20 output)"}))
+                      "acc": args.acc, "layer_count": args.layer_count, "train_stack": args.train_stack, "reference": "0.76 at epoch 34 (notebook cell 20 output)"}))
 
 
 if __name__ == "__main__":

@@ -525,6 +525,79 @@ size_t sgx_stack_workspace_bytes(const sgx_stack_desc *d);
  * chain: SGX_ERR_SHAPE; a dtype other than SGX_F16 / SGX_F32, gemm_mode 0 past layer 0: SGX_ERR_UNSUPPORTED. */
 int sgx_stack_forward(const sgx_stack_desc *d, void *stream);
 
+/* ---- training: the backward of that stack in one launch plus one reduction ---------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * Plan kinds: the backward keeps three tiles per row in LDS (X_l / D in dtype, g and G in fp32) where the forward keeps
+ * two of dtype, so it needs its own row budget.  sgx_batch_plan_create_ex(..., kind, ...) builds a plan for either
+ * kernel; sgx_batch_plan_create is exactly sgx_batch_plan_create_ex(..., SGX_BATCH_FORWARD, ...).  sgx_stack_forward
+ * accepts a plan of either kind (its results do not depend on how graphs are grouped), so one SGX_BATCH_BACKWARD plan
+ * serves both launches of a training step; sgx_stack_backward takes only SGX_BATCH_BACKWARD plans.
+ *
+ * Semantics: the backward the layer-by-layer model runs (FPYNQ / RPYNQ / ReadoutMean of sgracex1_amd/molecule_gcn.py:
+ * sgx_readout_mean_backward -> per layer sgx_relu_mask_backward, sgx_spmm_csr over the fp32 adjacency, the weight
+ * gradient, and sgx_xw_dense(G, W) for the layer below), for the forward of sgx_stack_forward with the same layers:
+ *     g_{L-1}[r] = dtype(grad_pooled[graph(r)] * (1 / n_graph))      (sgx_readout_mean_backward's expression)
+ *     for l = L-1 .. 0:
+ *         g_l[r][c] = 0 where layer[l].relu and D_l[r][c] == 0       (RPYNQ: the mask on the dtype gradient)
+ *         G_l    = A . g_l          fp32, per (row, column) an fma chain over the row's stored entries in CSR order from 0
+ *                                   (A, not A^T, as the model and the reference multiply)
+ *         dW_l   = X_l^T . G_l      fp32 [M_fea][P_w], the layout of the weight parameter; X_0 = the features (CSR or
+ *                                   dense), X_l = D_{l-1}
+ *         g_{l-1} = dtype(G_l . W_l^T)     (l > 0) W_l the fp32 parameter; the MFMA layout and K order of sgx_xw_dense's
+ *                                   fp32 kernel, then one rounding to dtype (autograd's cast to the layer output's type)
+ * G_l and every g_l are bit-equal to that chain.  dW_l sums over the batch's rows in another order than the chain's
+ * kernels: every workgroup of the launch walks the plan's groups blockIdx.x, blockIdx.x + grid, ... and adds each group's
+ * X_l^T . G_l into its own fp32 slice of the workspace (row order within a group, the slice's previous value first;
+ * plain loads and stores, no atomics), and a second launch adds the slices in slice order.  The grid is
+ * min(max(groups, 1), 512) whatever the device, so a plan gives the same bits on every run and every device; the result
+ * stays within the fp32 reordering bound of the chain's X^T . G.
+ *
+ * Limits: 1 to 4 layers, SGX_F16 / SGX_F32, every P_w and the M_fea of dense layers <= the plan's max_width <= 256 (a
+ * sparse layer 0 may have any M_fea; above 16 columns its weight gradient takes a slow path), and a plan that fits.
+ * Otherwise SGX_ERR_UNSUPPORTED before anything reaches the device: there is no chained form inside this call (the
+ * layer-by-layer autograd path of the model is that form).  Capturable: no allocation and no host synchronisation.
+ *
+ * Argument errors, returned before anything reaches the device: d, the plan, graph_ptr, the adjacency, layer 0's input,
+ * grad_pooled, every W and grad_W, a D the backward reads (D_0 .. D_{L-2}, and D_{L-1} when the last layer has ReLU):
+ * SGX_ERR_NULL; n_layers outside 1..4, n_rows / n_graphs not the plan's, widths that do not chain, ldd < P_w:
+ * SGX_ERR_SHAPE; a dtype other than SGX_F16 / SGX_F32, gemm_mode 0 past layer 0, a plan of the wrong kind or that does
+ * not fit, a width over the limits: SGX_ERR_UNSUPPORTED; workspace missing or smaller than
+ * sgx_stack_backward_workspace_bytes: SGX_ERR_WORKSPACE; workspace not 256-byte aligned: SGX_ERR_ALIGN. */
+typedef enum sgx_batch_kind {
+    SGX_BATCH_FORWARD = 0,          /* row budget of sgx_stack_forward's tiles                   */
+    SGX_BATCH_BACKWARD = 1          /* row budget of sgx_stack_backward's (fits both kernels)    */
+} sgx_batch_kind;
+
+typedef struct sgx_stack_grad_layer {
+    int32_t gemm_mode;    /* as sgx_stack_layer: layer 0 may be 0 (CSR features), layers >= 1 must be 1 */
+    int32_t relu;         /* the forward's flag: the gradient is masked where D == 0 */
+    int32_t M_fea, P_w;   /* columns of X_l and of D_l */
+    const float *W;       /* the fp32 weight parameter [M_fea][P_w] (not transposed) */
+    const void *D;        /* the forward's output of this layer [n_rows][ldd] in dtype */
+    int64_t ldd;          /* leading dimension of D in elements (0 = P_w) */
+    float *grad_W;        /* out: [M_fea][P_w] fp32 */
+    float *G;             /* optional out: A . g_l [n_rows][P_w] fp32 (NULL = not written) */
+} sgx_stack_grad_layer;
+
+typedef struct sgx_stack_grad_desc {
+    int32_t dtype, n_layers;                   /* SGX_F16 / SGX_F32; 1 .. 4 */
+    int32_t n_rows, n_graphs;                  /* must equal the plan's */
+    const int32_t *graph_ptr;                  /* [n_graphs + 1] device, the array the plan was built on */
+    const int32_t *rowPtr_adj, *columnIndex_adj; const void *values_adj;   /* the forward's adjacency (dtype values) */
+    const int32_t *rowPtr_fea, *columnIndex_fea; const void *values_fea;   /* layer 0's input, as the forward's */
+    sgx_stack_grad_layer layer[4];
+    const float *grad_pooled;                  /* [n_graphs][P_last] fp32: the gradient of the pooled means */
+    const sgx_batch_plan *plan;                /* from sgx_batch_plan_create_ex(..., SGX_BATCH_BACKWARD, ...) */
+    void *workspace; size_t workspace_bytes;   /* sgx_stack_backward_workspace_bytes(d), 256-byte aligned */
+} sgx_stack_grad_desc;
+
+int sgx_batch_plan_create_ex(int dtype, int n_rows, int n_graphs, const int32_t *graph_ptr, const int32_t *rowPtr_adj,
+                             const int32_t *columnIndex_adj, int max_width, int kind, sgx_batch_plan **plan, void *stream);
+/* the weight-gradient slices: min(max(groups, 1), 512) x sum_l M_fea P_w floats; 0 for a descriptor the call refuses */
+size_t sgx_stack_backward_workspace_bytes(const sgx_stack_grad_desc *d);
+int sgx_stack_backward(const sgx_stack_grad_desc *d, void *stream);
+
 /* A plain streaming copy (16 bytes per lane, non-temporal, each workgroup on a contiguous chunk), the kernel the attainable HBM rate of a device is
  * measured with next to the nominal 8 TB/s (bench.py reports it as roofline.stream_copy_GBps_this_device).
  * bytes must be a multiple of 16, both pointers 16-byte aligned. */

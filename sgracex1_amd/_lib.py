@@ -22,6 +22,7 @@ SGX_QUANT_INT8 = 2                                          # sgx_quant.flags: i
 SGX_QUANT_INT8_AUTO = 4                                     # ... where they are the faster form (M_fea > 128)
 SGX_ERR_SEEDS = -8                                          # sgx_sample_neighbors: a repeated or out-of-range seed
 SGX_ERR_BLOCKS = -9                                         # sgx_batch_plan_create: an edge leaves its graph / bad graph_ptr
+SGX_BATCH_FORWARD, SGX_BATCH_BACKWARD = 0, 1                # sgx_batch_kind: whose LDS tiles set a batch plan's row budget
 
 # every symbol include/sgx.h declares (tests/test_abi.py checks header and library against this)
 SYMBOLS = [
@@ -38,6 +39,7 @@ SYMBOLS = [
     "sgx_sample_workspace_bytes", "sgx_sample_neighbors",
     "sgx_batch_plan_create", "sgx_batch_plan_destroy", "sgx_batch_plan_rows", "sgx_batch_plan_groups",
     "sgx_batch_plan_max_graph", "sgx_batch_plan_fits", "sgx_stack_workspace_bytes", "sgx_stack_forward",
+    "sgx_batch_plan_create_ex", "sgx_stack_backward_workspace_bytes", "sgx_stack_backward",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -104,6 +106,29 @@ class StackDesc(ctypes.Structure):
         ("C", ctypes.c_int32),
         ("W_head", ctypes.c_void_p), ("bias", ctypes.c_void_p),
         ("pooled", ctypes.c_void_p), ("logits", ctypes.c_void_p),
+        ("plan", ctypes.c_void_p),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class StackGradLayer(ctypes.Structure):
+    """struct sgx_stack_grad_layer -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("gemm_mode", ctypes.c_int32), ("relu", ctypes.c_int32), ("M_fea", ctypes.c_int32), ("P_w", ctypes.c_int32),
+        ("W", ctypes.c_void_p), ("D", ctypes.c_void_p), ("ldd", ctypes.c_int64),
+        ("grad_W", ctypes.c_void_p), ("G", ctypes.c_void_p),
+    ]
+
+
+class StackGradDesc(ctypes.Structure):
+    """struct sgx_stack_grad_desc -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("dtype", ctypes.c_int32), ("n_layers", ctypes.c_int32), ("n_rows", ctypes.c_int32), ("n_graphs", ctypes.c_int32),
+        ("graph_ptr", ctypes.c_void_p),
+        ("rowPtr_adj", ctypes.c_void_p), ("columnIndex_adj", ctypes.c_void_p), ("values_adj", ctypes.c_void_p),
+        ("rowPtr_fea", ctypes.c_void_p), ("columnIndex_fea", ctypes.c_void_p), ("values_fea", ctypes.c_void_p),
+        ("layer", StackGradLayer * 4),
+        ("grad_pooled", ctypes.c_void_p),
         ("plan", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
@@ -223,6 +248,12 @@ def _load():
     lib.sgx_stack_workspace_bytes.restype = sz
     lib.sgx_stack_forward.argtypes = [ctypes.POINTER(StackDesc), vp]
     lib.sgx_stack_forward.restype = c_int
+    lib.sgx_batch_plan_create_ex.argtypes = [c_int, c_int, c_int, vp, vp, vp, c_int, c_int, ctypes.POINTER(vp), vp]
+    lib.sgx_batch_plan_create_ex.restype = c_int
+    lib.sgx_stack_backward_workspace_bytes.argtypes = [ctypes.POINTER(StackGradDesc)]
+    lib.sgx_stack_backward_workspace_bytes.restype = sz
+    lib.sgx_stack_backward.argtypes = [ctypes.POINTER(StackGradDesc), vp]
+    lib.sgx_stack_backward.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

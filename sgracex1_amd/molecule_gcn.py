@@ -203,10 +203,15 @@ class GraphConvolution_pynq(Module):
 
 class GCN_PYNQ(torch.nn.Module):
     """MOL cell 18: conv1 (sparse X, ReLU in the kernel) -> Relu_pynq -> conv2 (dense X) ->
-    global_mean_pool -> dropout(0.5) -> Linear."""
+    global_mean_pool -> dropout(0.5) -> Linear.
 
-    def __init__(self, hidden_channels, num_node_features, num_classes, my_ip):
+    train_stack (opt-in, also settable as an attribute): with register layer_count >= 2, a training step's two layers
+    and the pooling run as one forward and one backward call (ops.GcnStack) on a sorted, block-diagonal batch whose
+    graphs fit the backward plan; every other case runs the layers one by one as before."""
+
+    def __init__(self, hidden_channels, num_node_features, num_classes, my_ip, train_stack=False):
         super(GCN_PYNQ, self).__init__()
+        self.train_stack = bool(train_stack)
         torch.manual_seed(12345)
         self.conv1 = GraphConvolution_pynq(num_node_features, hidden_channels, my_ip)
         self.conv2 = GraphConvolution_pynq(hidden_channels, hidden_channels, my_ip)
@@ -224,6 +229,13 @@ class GCN_PYNQ(torch.nn.Module):
             out = self._forward_stack(x, edge_index, batch)
             if out is not None:
                 return out
+        if acc == 1 and getattr(self, "train_stack", False) and torch.is_grad_enabled() and \
+                getattr(self.conv1.my_ip.register_map, "layer_count", 1) >= 2:
+            # the training step's GCN part as one forward and one backward call
+            pooled = self._train_stack(x, edge_index, batch)
+            if pooled is not None:
+                x = F.dropout(pooled, p=0.5, training=self.training)
+                return self.lin(x)
         if acc == 1:
             # pynq_adj = to_dense_adj(edge_index)._to_sparse_csr() of the notebook, built from the
             # edge list directly (same CSR, no dense N x N intermediate); the batch of an epoch loop is
@@ -267,3 +279,24 @@ class GCN_PYNQ(torch.nn.Module):
             return None
         return ops.gcn_stack_forward(adj, feature_csr(x, ACC_DTYPE), weights, [True, False], ptr, self.lin.weight,
                                      self.lin.bias, plan=plan)
+
+    def _train_stack(self, x, edge_index, batch):
+        """Both layers and the mean pool through ops.GcnStack (one sgx_stack_forward, one sgx_stack_backward): the pooled
+        means [G, hidden] fp32, bit-equal to the layer-by-layer forward.  None (the caller then runs the layers one by
+        one) when x needs a gradient, `batch` is not sorted, an edge joins two of its graphs, a graph is over the
+        backward plan's row budget or a width is over its limit."""
+        if x.requires_grad:
+            return None
+        ptr = ops.graph_ptr_of(batch)
+        if ptr is None:
+            return None
+        adj = ops.cached_on(edge_index, ("adj_csr", x.shape[0], ACC_DTYPE),
+                            lambda: ops.csr_from_edge_index(edge_index, x.shape[0], dtype=ACC_DTYPE))
+        width = max(self.conv1.out_features, self.conv2.in_features, self.conv2.out_features)
+        if width > 256:
+            return None
+        plan = ops.BatchPlan.cached(adj, ptr, width, ops._lib.SGX_BATCH_BACKWARD)
+        if plan is None or not plan.fits:
+            return None
+        return ops.GcnStack.apply(adj, feature_csr(x, ACC_DTYPE), ptr, plan, (True, False), self.conv1.weight,
+                                  self.conv2.weight)

@@ -820,28 +820,38 @@ class BatchPlan:
     """Groups of whole graphs for sgx_stack_forward (sgx_batch_plan): graph_ptr and the adjacency are checked on the
     device to be block-diagonal (SgxError SGX_ERR_BLOCKS otherwise) and the graphs are cut into runs of at most `rows`
     rows, what the fused kernel keeps in LDS for layers up to max_width columns.  `fits` is False when a graph is larger
-    than that; the stack then takes the chained kernels.  One stream synchronisation per plan."""
+    than that; the stack then takes the chained kernels.  One stream synchronisation per plan.
+    kind: _lib.SGX_BATCH_FORWARD, or SGX_BATCH_BACKWARD for the smaller row budget of sgx_stack_backward (such a plan
+    serves the forward too)."""
 
-    def __init__(self, adj, graph_ptr, max_width):
+    def __init__(self, adj, graph_ptr, max_width, kind=_lib.SGX_BATCH_FORWARD):
         _dev(graph_ptr, "graph_ptr")
         if graph_ptr.dtype != torch.int32:
             raise TypeError("graph_ptr must be int32")
         self.dtype = adj.val.dtype
         self.n_rows, self.n_graphs, self.max_width = adj.n_rows, graph_ptr.numel() - 1, int(max_width)
+        self.kind = int(kind)
         h = ctypes.c_void_p()
-        check(lib.sgx_batch_plan_create(dtype_code(self.dtype), self.n_rows, self.n_graphs, _ptr(graph_ptr), _ptr(adj.rowptr),
-                                        _ptr(adj.col), self.max_width, ctypes.byref(h), _stream()), "sgx_batch_plan_create")
+        if self.kind == _lib.SGX_BATCH_FORWARD:
+            check(lib.sgx_batch_plan_create(dtype_code(self.dtype), self.n_rows, self.n_graphs, _ptr(graph_ptr),
+                                            _ptr(adj.rowptr), _ptr(adj.col), self.max_width, ctypes.byref(h), _stream()),
+                  "sgx_batch_plan_create")
+        else:
+            check(lib.sgx_batch_plan_create_ex(dtype_code(self.dtype), self.n_rows, self.n_graphs, _ptr(graph_ptr),
+                                               _ptr(adj.rowptr), _ptr(adj.col), self.max_width, self.kind, ctypes.byref(h),
+                                               _stream()), "sgx_batch_plan_create_ex")
         self._h = h
 
     @staticmethod
-    def cached(adj, graph_ptr, max_width):
-        """The plan of (adj, graph_ptr, max_width), kept on the adjacency's column array while both stay unchanged; None
-        when the batch is not block-diagonal under graph_ptr (remembered too, so that a caller falls back without a
+    def cached(adj, graph_ptr, max_width, kind=_lib.SGX_BATCH_FORWARD):
+        """The plan of (adj, graph_ptr, max_width, kind), kept on the adjacency's column array while both stay unchanged;
+        None when the batch is not block-diagonal under graph_ptr (remembered too, so that a caller falls back without a
         device sync per call)."""
-        hit = cached_on(adj.col, ("batch_plan", adj.val.dtype, int(max_width)), lambda: [None, -1, None])
+        key = ("batch_plan", adj.val.dtype, int(max_width)) + (() if kind == _lib.SGX_BATCH_FORWARD else (int(kind),))
+        hit = cached_on(adj.col, key, lambda: [None, -1, None])
         if hit[0] is not graph_ptr or hit[1] != graph_ptr._version:
             try:
-                plan = BatchPlan(adj, graph_ptr, max_width)
+                plan = BatchPlan(adj, graph_ptr, max_width, kind)
             except _lib.SgxError as e:
                 if e.status != _lib.SGX_ERR_BLOCKS:
                     raise
@@ -876,7 +886,7 @@ class BatchPlan:
 
 
 def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, head_bias=None, want_layer_outputs=False,
-                      want_pooled=False, plan=None):
+                      want_pooled=False, plan=None, keep=None):
     """n GCN layers, the per-graph mean and a Linear head in one call (sgx_stack_forward) -- exactly the chain
     layer_forward x n -> readout_mean_linear, bit for bit (include/sgx.h), in one launch where the batch's graphs fit
     the plan, through the chained kernels otherwise.
@@ -885,7 +895,8 @@ def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, hea
     x: Csr features (layer 0 sparse) or a dense [N, M] tensor; weights_t: 1 to 4 tensors W_l^T [P_l, M_l] in adj's
     dtype; relus: one flag per layer.  Returns logits [G, C] fp32 with a head ((logits, pooled) with want_pooled), the
     pooled means [G, P_last] fp32 without one, or with graph_ptr None the last layer's output [N, P_last]; with
-    want_layer_outputs also the list of every layer's output D_l [N, P_l]."""
+    want_layer_outputs also the list of every layer's output D_l [N, P_l] (keep: one flag per layer, which of them to
+    write; the others are None)."""
     n = len(weights_t)
     if not 1 <= n <= 4 or len(relus) != n:
         raise ValueError("gcn_stack_forward takes 1 to 4 layers and one relu flag per layer")
@@ -925,10 +936,12 @@ def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, hea
         L = d.layer[l]
         L.gemm_mode = 0 if (l == 0 and sparse) else 1
         L.relu, L.M_fea, L.P_w, L.B = int(bool(relu)), M, P, Wt.data_ptr()
-        if want_layer_outputs or (not readout and l == n - 1):
+        if (want_layer_outputs and (keep is None or keep[l])) or (not readout and l == n - 1):
             D = torch.empty((N, P), dtype=dtype, device=dev)
             L.D, L.ldd = D.data_ptr(), P
             outs.append(D)
+        elif want_layer_outputs:
+            outs.append(None)
         widths += [P] if (l == 0 and sparse) else [P, M]
         k_in = P
     G = d.n_graphs
@@ -964,3 +977,110 @@ def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, hea
     else:
         out = pooled
     return (out, outs) if want_layer_outputs else out
+
+
+# ---- the backward of that stack for training (sgx_stack_backward) ----------------------------------------------------
+def gcn_stack_backward(adj, x, weights, relus, graph_ptr, layer_outputs, grad_pooled, plan=None, want_G=False):
+    """Weight gradients of the stack sgx_stack_forward ran (include/sgx.h, "training"): one launch over the batch's graphs
+    and one reduction.  weights: the fp32 parameters W_l [M_l, P_l] (not transposed); layer_outputs: the forward's D_l
+    in adj's dtype (D_{L-1} may be None unless the last layer has ReLU); grad_pooled [G, P_last] fp32.  Returns the
+    list of dW_l [M_l, P_l] fp32 (and the list of G_l = A . g_l [N, P_l] fp32 with want_G).  plan: an SGX_BATCH_BACKWARD
+    BatchPlan (built and cached when None).  Raises SgxError SGX_ERR_UNSUPPORTED where the batch or the widths are
+    outside the kernel's limits -- the caller then runs the layers one by one."""
+    n = len(weights)
+    if not 1 <= n <= 4 or len(relus) != n or len(layer_outputs) != n:
+        raise ValueError("gcn_stack_backward takes 1 to 4 layers, one relu flag and one layer output per layer")
+    dtype = adj.val.dtype
+    N, dev = adj.n_rows, adj.val.device
+    _dev(graph_ptr, "graph_ptr")
+    d = _lib.StackGradDesc()
+    d.dtype, d.n_layers, d.n_rows, d.n_graphs = dtype_code(dtype), n, N, graph_ptr.numel() - 1
+    d.graph_ptr = graph_ptr.data_ptr()
+    d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
+    sparse = isinstance(x, Csr)
+    if sparse:
+        if x.val.dtype != dtype or x.n_rows != N:
+            raise ValueError("feature CSR does not match the adjacency")
+        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = x.rowptr.data_ptr(), x.col.data_ptr(), x.val.data_ptr()
+        k_in = x.n_cols
+    else:
+        _dev(x, "x")
+        if x.dtype != dtype or x.dim() != 2 or x.shape[0] != N:
+            raise ValueError(f"dense features must be [{N}, M] {dtype}")
+        d.values_fea = x.data_ptr()
+        k_in = x.shape[1]
+    grads, Gs, keep = [], [], []
+    for l, (W, relu, D) in enumerate(zip(weights, relus, layer_outputs)):
+        W = _dev(W.detach().float().contiguous(), f"weights[{l}]")
+        M, P = W.shape
+        if M != k_in:
+            raise ValueError(f"weights[{l}] must be [{k_in}, P], got {tuple(W.shape)}")
+        L = d.layer[l]
+        L.gemm_mode = 0 if (l == 0 and sparse) else 1
+        L.relu, L.M_fea, L.P_w, L.W = int(bool(relu)), M, P, W.data_ptr()
+        if D is not None:
+            _dev2d(D, f"layer_outputs[{l}]")
+            if D.dtype != dtype or D.shape != (N, P):
+                raise ValueError(f"layer_outputs[{l}] must be [{N}, {P}] {dtype}")
+            L.D, L.ldd = D.data_ptr(), D.stride(0)
+        gW = torch.empty((M, P), dtype=torch.float32, device=dev)
+        L.grad_W = gW.data_ptr()
+        grads.append(gW)
+        if want_G:
+            G = torch.empty((N, P), dtype=torch.float32, device=dev)
+            L.G = G.data_ptr()
+            Gs.append(G)
+        keep.append(W)
+        k_in = P
+    g = _dev(grad_pooled.detach().float().contiguous(), "grad_pooled")
+    if g.shape != (d.n_graphs, k_in):
+        raise ValueError(f"grad_pooled must be [{d.n_graphs}, {k_in}]")
+    d.grad_pooled = g.data_ptr()
+    if plan is None:
+        widths = [w.shape[1] for w in keep] + [w.shape[0] for l, w in enumerate(keep) if l > 0 or not sparse]
+        plan = BatchPlan.cached(adj, graph_ptr, max(widths), _lib.SGX_BATCH_BACKWARD)
+        if plan is None:
+            check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create_ex")
+    d.plan = plan.handle
+    nbytes = lib.sgx_stack_backward_workspace_bytes(ctypes.byref(d))
+    if nbytes:
+        ws = _workspace(dev, nbytes)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(lib.sgx_stack_backward(ctypes.byref(d), _stream()), "sgx_stack_backward")
+    return (grads, Gs) if want_G else grads
+
+
+class GcnStack(torch.autograd.Function):
+    """The GCN stack of a training step as two calls: forward = sgx_stack_forward without a head (the pooled fp32 means
+    [G, P_last], the D_l the backward reads saved), backward = sgx_stack_backward (fp32 gradients of the weight
+    parameters, [in, out] as FPYNQ.backward returns them).  No gradient for the features: a feature tensor that needs
+    one is refused.
+
+        pooled = GcnStack.apply(adj, x, graph_ptr, plan, relus, W_0, ..., W_{L-1})
+
+    adj: Csr in the accelerator's dtype; x: Csr or dense features in that dtype; plan: an SGX_BATCH_BACKWARD BatchPlan
+    that fits; W_l: the fp32 parameters [M_l, P_l]."""
+
+    @staticmethod
+    def forward(ctx, adj, x, graph_ptr, plan, relus, *weights):
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise ValueError("GcnStack gives no gradient for the features; x must not require grad")
+        dtype = adj.val.dtype
+        wts = [torch.transpose(w, 0, 1).detach().to(dtype).contiguous() for w in weights]
+        n = len(wts)
+        keep = [l < n - 1 or bool(relus[l]) for l in range(n)]
+        pooled, outs = gcn_stack_forward(adj, x, wts, relus, graph_ptr, want_layer_outputs=True, plan=plan, keep=keep)
+        ctx.adj, ctx.x, ctx.plan, ctx.relus = adj, x, plan, list(relus)
+        ctx.save_for_backward(graph_ptr, *[D for D in outs if D is not None], *weights)
+        ctx.keep = keep
+        return pooled
+
+    @staticmethod
+    def backward(ctx, grad_pooled):
+        saved = ctx.saved_tensors
+        n = len(ctx.relus)
+        graph_ptr, rest = saved[0], list(saved[1:])
+        outs = [rest.pop(0) if k else None for k in ctx.keep]
+        weights = rest
+        grads = gcn_stack_backward(ctx.adj, ctx.x, weights, ctx.relus, graph_ptr, outs, grad_pooled, plan=ctx.plan)
+        return (None, None, None, None, None) + tuple(grads[:n])

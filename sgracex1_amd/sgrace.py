@@ -177,7 +177,9 @@ class FPYNQ_GAT(torch.autograd.Function):
         if ctx.gat:
             output_cpu = torch.matmul(attentions, Wh)
         else:
-            output_cpu = torch.matmul(adj_d, Wh)
+            # the sparse product, as SG.py does it: the dense one sums in another order on some CPUs (MKL's code path
+            # depends on the instruction set), so only this form gives the reference's bits everywhere
+            output_cpu = torch.matmul(adj_d.to_sparse(), Wh)
         if relu == 1:
             output_cpu = torch.where(output_cpu > 0, output_cpu, torch.zeros_like(output_cpu))
         if qc is not None:
