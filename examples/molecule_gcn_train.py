@@ -10,6 +10,11 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
         (register layer_count, sgx_stack_forward); training steps run layer by layer unless --train-stack, which
         (with --layer-count >= 2) runs each step's two layers and the pooling as one forward call (sgx_stack_forward)
         and one backward call (sgx_stack_backward) -- GCN_PYNQ(train_stack=True)
+    python examples/molecule_gcn_train.py --batch-size 64 [--host-loader] [--layer-count 2 --train-stack]
+        --batch-size N > 0 = train the PyG way, on shuffled mini-batches of N graphs (MOL cell 10's
+        DataLoader(shuffle=True)), collated on the GPU (pyg_lite.GraphLoader), or on the host and copied
+        (pyg_lite.DataLoader) with --host-loader; both draw their permutations from a generator seeded 12345.
+        The default 0 keeps the single unshuffled batch.
 """
 import argparse
 import json
@@ -32,15 +37,24 @@ def main():
     ap.add_argument("--acc", type=int, default=1)
     ap.add_argument("--layer-count", type=int, default=1)
     ap.add_argument("--train-stack", action="store_true")
+    ap.add_argument("--batch-size", type=int, default=0)
+    ap.add_argument("--host-loader", action="store_true")
     args = ap.parse_args()
     if args.train_stack and args.layer_count < 2:
         ap.error("--train-stack needs --layer-count >= 2")
+    if args.host_loader and args.batch_size <= 0:
+        ap.error("--host-loader needs --batch-size > 0")
     dev = torch.device("cuda")
     raw = np.load(os.path.join(ROOT, "tests", "golden", "mutag_raw.npz"))
     graphs = G.load_tu_raw(raw["A"], raw["graph_indicator"], raw["graph_labels"], raw["node_labels"])
     torch.manual_seed(12345)                                  # MOL cell 6
     graphs = [graphs[i] for i in torch.randperm(len(graphs)).tolist()]
     train, test = G.collate(graphs[:2000]).to(dev), G.collate(graphs[50:100]).to(dev)
+    loader = [train]
+    if args.batch_size > 0:
+        gen = torch.Generator().manual_seed(12345)
+        loader = (G.DataLoader(graphs[:2000], batch_size=args.batch_size, shuffle=True, generator=gen) if args.host_loader
+                  else G.GraphLoader(graphs[:2000], batch_size=args.batch_size, shuffle=True, generator=gen, device=dev))
     my_ip = pynq_shim.Overlay("gnn_all.bit").mmult_top_0      # MOL cell 11
     my_ip.register_map.layer_count = args.layer_count          # layers per call (SG.py:1862)
     model = M.GCN_PYNQ(64, 7, 2, my_ip, train_stack=args.train_stack).to(dev)   # MOL cell 18 (seed 12345 inside)
@@ -57,12 +71,17 @@ def main():
     for epoch in range(1, args.epochs + 1):
         model.train()
         t0 = time.perf_counter()
-        opt.zero_grad()
-        loss = crit(model(args.acc, train.x, train.edge_index, train.batch), train.y)
-        loss.backward()
-        opt.step()
+        steps = 0
+        for b in loader:
+            if args.host_loader:
+                b = b.to(dev)
+            opt.zero_grad()
+            loss = crit(model(args.acc, b.x, b.edge_index, b.batch), b.y)
+            loss.backward()
+            opt.step()
+            steps += 1
         torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
+        dt = (time.perf_counter() - t0) / steps
         tr, te = accuracy(train), accuracy(test)
         best = max(best, te)
         log.append({"epoch": epoch, "loss": round(float(loss.detach()), 4), "train_acc": round(tr, 4),
@@ -70,7 +89,8 @@ def main():
         print(f"Epoch: {epoch:03d}, Train Acc: {tr:.4f}, Test Acc: {te:.4f}, loss {float(loss.detach()):.4f}, "
               f"step {dt * 1e3:.2f} ms", flush=True)
     print(json.dumps({"best_test_acc": best, "final_test_acc": log[-1]["test_acc"], "epochs": args.epochs,
-                      "acc": args.acc, "layer_count": args.layer_count, "train_stack": args.train_stack, "reference": "0.76 at epoch 34 (notebook cell 20 output)"}))
+                      "acc": args.acc, "layer_count": args.layer_count, "train_stack": args.train_stack,
+                      "batch_size": args.batch_size, "host_loader": args.host_loader, "reference": "0.76 at epoch 34 (notebook cell 20 output)"}))
 
 
 if __name__ == "__main__":

@@ -598,6 +598,80 @@ int sgx_batch_plan_create_ex(int dtype, int n_rows, int n_graphs, const int32_t 
 size_t sgx_stack_backward_workspace_bytes(const sgx_stack_grad_desc *d);
 int sgx_stack_backward(const sgx_stack_grad_desc *d, void *stream);
 
+/* ---- shuffled graph mini-batches collated on the device -------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * A graph-classification dataset is uploaded once (sgx_graph_set, device arrays in dataset order) and every mini-batch
+ * -- any list of graph ids, such as a slice of a shuffled epoch -- is built from it by one launch of
+ * sgx_collate_graphs, exactly as PyG's collation and the CSR builders of the host would build it:
+ *   x           the graphs' feature rows, one after another in batch order;
+ *   edge_index  int64 [2][n_edges]: each graph's stored edges in stored order plus the graph's first row in the batch;
+ *   batch       int64 [n_rows]: the batch position b of every row; y int64 [n_graphs]; graph_ptr int32 [n_graphs+1];
+ *   adjacency   the CSR of the edges sorted by (row, col), repeated edges summed, as one block-diagonal matrix: graph
+ *               idx[b]'s rows of the dataset's adjacency (whose columns stay inside the graph), columns shifted by
+ *               node_off[b] - node_ptr[idx[b]];
+ *   features    the CSR of x (zeros dropped): graph idx[b]'s rows of the dataset's, columns unchanged.
+ * Values are stored as fp32 and written in each dtype the caller asks for (values_*[SGX_F16] / [SGX_F32], either may be
+ * NULL), rounded to nearest even for fp16 -- the same bits as a cast of the fp32 values.
+ *
+ * The host holds the per-graph counts (rows, stored edges, adjacency and feature entries) and computes the batch's
+ * exclusive offsets node_off / edge_off / adj_off / fea_off [n_graphs+1] itself, so the call needs no read-back: one
+ * launch (a wavefront per graph), no allocation, no synchronisation; capturable.  Offsets that do not match the set's
+ * counts give wrong contents but no write outside the caller's buffers: a graph id outside the set, or a graph whose
+ * ranges do not fit the totals, is skipped.
+ *
+ * Argument errors, returned before anything reaches the device: set, b, any pointer of the set or of the batch that an
+ * element is read from or written to (x / edge_index only when there are rows / edges; the values arrays are optional):
+ * SGX_ERR_NULL; set->n_graphs < 1, set->n_feat < 1, b->n_graphs < 1, a negative total: SGX_ERR_SHAPE. */
+typedef struct sgx_graph_set {
+    int32_t n_graphs, n_feat;                  /* graphs of the dataset, feature columns */
+    int64_t n_edges;                           /* stored edges of the dataset: the row length of edge_index */
+    const int32_t *node_ptr;                   /* [n_graphs+1] first row of every graph */
+    const int32_t *edge_ptr;                   /* [n_graphs+1] first stored edge of every graph */
+    const int32_t *edge_index;                 /* [2][n_edges] graph-local ids (0 .. rows-1), stored order */
+    const float *x;                            /* [rows][n_feat] */
+    const int64_t *y;                          /* [n_graphs] */
+    const int32_t *rowPtr_adj, *columnIndex_adj; const float *values_adj;   /* block-diagonal adjacency, dataset ids */
+    const int32_t *rowPtr_fea, *columnIndex_fea; const float *values_fea;   /* CSR of x */
+} sgx_graph_set;
+
+typedef struct sgx_graph_batch {
+    int32_t n_graphs, n_rows;                  /* graphs of the batch (>= 1), rows = node_off[n_graphs] */
+    int64_t n_edges, nnz_adj, nnz_fea;         /* = edge_off / adj_off / fea_off [n_graphs] */
+    const int32_t *index;                      /* [n_graphs] dataset graph id of every batch position */
+    const int32_t *node_off, *edge_off, *adj_off, *fea_off;   /* [n_graphs+1] each, exclusive offsets */
+    float *x;                                  /* out [n_rows][n_feat] */
+    int64_t *edge_index;                       /* out [2][n_edges] */
+    int64_t *batch, *y;                        /* out [n_rows], [n_graphs] */
+    int32_t *graph_ptr;                        /* out [n_graphs+1] */
+    int32_t *rowPtr_adj, *columnIndex_adj;     /* out [n_rows+1], [nnz_adj] */
+    void *values_adj[2];                       /* out [nnz_adj] in SGX_F16 / SGX_F32, either may be NULL */
+    int32_t *rowPtr_fea, *columnIndex_fea;     /* out [n_rows+1], [nnz_fea] */
+    void *values_fea[2];                       /* out [nnz_fea] likewise */
+} sgx_graph_batch;
+
+int sgx_collate_graphs(const sgx_graph_set *set, const sgx_graph_batch *b, void *stream);
+
+/* A batch plan from facts the caller already knows (the collator's batches): graph_ptr cuts a block-diagonal adjacency
+ * and its largest graph has max_graph rows.  Neither is checked on the device, so nothing is read back:
+ * sgx_batch_plan_create_known gives the plan sgx_batch_plan_create_ex gives on the same batch (rows, groups, max_graph,
+ * fits and every group_graph entry), computed on the host, with one launch that writes the group_graph table into
+ * the caller's device buffer `group_graph` of sgx_batch_plan_group_count(...) + 1 int32 entries.  The plan does not own
+ * that buffer (sgx_batch_plan_destroy does not free it), which must outlive the plan's last use.  No allocation, no
+ * synchronisation; capturable.  The buffer is not written, and may be NULL, when the plan does not fit or n_graphs == 0.
+ * sgx_batch_plan_group_count is host-only: the plan's group count for a batch of n_rows rows in n_graphs >= 1 graphs
+ * (0 when the largest graph is over the row budget), or a negative status.
+ * Argument errors: plan NULL, graph_ptr NULL with rows or graphs, group_graph NULL where it is written: SGX_ERR_NULL;
+ * negative sizes, max_width < 1, max_graph outside [ceil(n_rows / n_graphs), n_rows], rows without graphs: SGX_ERR_SHAPE;
+ * a dtype other than SGX_F16 / SGX_F32, an unknown kind: SGX_ERR_UNSUPPORTED. */
+int sgx_batch_plan_group_count(int dtype, int n_rows, int max_graph, int max_width, int kind);
+int sgx_batch_plan_create_known(int dtype, int n_rows, int n_graphs, const int32_t *graph_ptr, int max_graph, int max_width,
+                                int kind, int32_t *group_graph, sgx_batch_plan **plan, void *stream);
+/* The plan's group_graph table ([groups + 1] int32: first graph of every group, then n_graphs) copied into dst on the
+ * stream (device to device).  Returns the entry count; with dst NULL or capacity below it only the count.  plan NULL:
+ * SGX_ERR_NULL. */
+int64_t sgx_batch_plan_export_groups(const sgx_batch_plan *plan, int32_t *dst, int64_t capacity, void *stream);
+
 /* A plain streaming copy (16 bytes per lane, non-temporal, each workgroup on a contiguous chunk), the kernel the attainable HBM rate of a device is
  * measured with next to the nominal 8 TB/s (bench.py reports it as roofline.stream_copy_GBps_this_device).
  * bytes must be a multiple of 16, both pointers 16-byte aligned. */

@@ -40,6 +40,7 @@ SYMBOLS = [
     "sgx_batch_plan_create", "sgx_batch_plan_destroy", "sgx_batch_plan_rows", "sgx_batch_plan_groups",
     "sgx_batch_plan_max_graph", "sgx_batch_plan_fits", "sgx_stack_workspace_bytes", "sgx_stack_forward",
     "sgx_batch_plan_create_ex", "sgx_stack_backward_workspace_bytes", "sgx_stack_backward",
+    "sgx_collate_graphs", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -131,6 +132,31 @@ class StackGradDesc(ctypes.Structure):
         ("grad_pooled", ctypes.c_void_p),
         ("plan", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class GraphSet(ctypes.Structure):
+    """struct sgx_graph_set -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("n_graphs", ctypes.c_int32), ("n_feat", ctypes.c_int32), ("n_edges", ctypes.c_int64),
+        ("node_ptr", ctypes.c_void_p), ("edge_ptr", ctypes.c_void_p), ("edge_index", ctypes.c_void_p),
+        ("x", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("rowPtr_adj", ctypes.c_void_p), ("columnIndex_adj", ctypes.c_void_p), ("values_adj", ctypes.c_void_p),
+        ("rowPtr_fea", ctypes.c_void_p), ("columnIndex_fea", ctypes.c_void_p), ("values_fea", ctypes.c_void_p),
+    ]
+
+
+class GraphBatch(ctypes.Structure):
+    """struct sgx_graph_batch -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("n_graphs", ctypes.c_int32), ("n_rows", ctypes.c_int32),
+        ("n_edges", ctypes.c_int64), ("nnz_adj", ctypes.c_int64), ("nnz_fea", ctypes.c_int64),
+        ("index", ctypes.c_void_p),
+        ("node_off", ctypes.c_void_p), ("edge_off", ctypes.c_void_p), ("adj_off", ctypes.c_void_p), ("fea_off", ctypes.c_void_p),
+        ("x", ctypes.c_void_p), ("edge_index", ctypes.c_void_p), ("batch", ctypes.c_void_p), ("y", ctypes.c_void_p),
+        ("graph_ptr", ctypes.c_void_p),
+        ("rowPtr_adj", ctypes.c_void_p), ("columnIndex_adj", ctypes.c_void_p), ("values_adj", ctypes.c_void_p * 2),
+        ("rowPtr_fea", ctypes.c_void_p), ("columnIndex_fea", ctypes.c_void_p), ("values_fea", ctypes.c_void_p * 2),
     ]
 
 
@@ -254,6 +280,14 @@ def _load():
     lib.sgx_stack_backward_workspace_bytes.restype = sz
     lib.sgx_stack_backward.argtypes = [ctypes.POINTER(StackGradDesc), vp]
     lib.sgx_stack_backward.restype = c_int
+    lib.sgx_collate_graphs.argtypes = [ctypes.POINTER(GraphSet), ctypes.POINTER(GraphBatch), vp]
+    lib.sgx_collate_graphs.restype = c_int
+    lib.sgx_batch_plan_group_count.argtypes = [c_int, c_int, c_int, c_int, c_int]
+    lib.sgx_batch_plan_group_count.restype = c_int
+    lib.sgx_batch_plan_create_known.argtypes = [c_int, c_int, c_int, vp, c_int, c_int, c_int, vp, ctypes.POINTER(vp), vp]
+    lib.sgx_batch_plan_create_known.restype = c_int
+    lib.sgx_batch_plan_export_groups.argtypes = [vp, vp, c_i64, vp]
+    lib.sgx_batch_plan_export_groups.restype = c_i64
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

@@ -1,0 +1,129 @@
+// Shuffled graph mini-batches collated on the device (sgx_collate_graphs, include/sgx.h).
+//
+// The dataset lives on the device in dataset order (sgx_graph_set); a batch is a list of graph ids plus the exclusive
+// offsets of every graph's rows, stored edges, adjacency entries and feature entries inside the batch, which the host
+// computes from its own copy of the per-graph counts.  One wavefront owns one graph of the batch and writes all of its
+// pieces -- feature rows, shifted edge list, batch vector, label, graph_ptr entry, both CSRs -- so a batch is one
+// launch whatever its size: at 64 MUTAG graphs (about 1 100 rows) the cost is the launch, at thousands of graphs it is
+// the bytes, which are read and written once each, coalesced across the wavefront (the feature rows 16 bytes a lane
+// where source and destination share their alignment).
+#include "sgx_device.h"
+
+namespace {
+
+constexpr int kWave = 64;
+constexpr int kWavesPerBlock = 4;
+
+struct CollateArgs {
+    sgx_graph_set s;
+    sgx_graph_batch b;
+};
+
+// dst[0 .. n) = src[0 .. n), one wavefront; float4 body where both pointers have the same offset modulo 16 bytes
+__device__ __forceinline__ void copy_f32(float *__restrict__ dst, const float *__restrict__ src, int64_t n, int lane)
+{
+    const uintptr_t da = (uintptr_t)dst & 15, sa = (uintptr_t)src & 15;
+    if (da == sa) {
+        int64_t head = (int64_t)((16 - da) & 15) / 4;
+        if (head > n) head = n;
+        if (lane < head) dst[lane] = src[lane];
+        const int64_t n4 = (n - head) / 4;
+        float4 *__restrict__ d4 = reinterpret_cast<float4 *>(dst + head);
+        const float4 *__restrict__ s4 = reinterpret_cast<const float4 *>(src + head);
+        for (int64_t i = lane; i < n4; i += kWave) d4[i] = s4[i];
+        for (int64_t i = head + n4 * 4 + lane; i < n; i += kWave) dst[i] = src[i];
+    } else {
+        for (int64_t i = lane; i < n; i += kWave) dst[i] = src[i];
+    }
+}
+
+// out[o + i] = rowptr[r0 + i] - rowptr[r0] + off (i < n); col / values of the graph's entries with `shift` added to
+// the columns; returns nothing, writes nothing for an empty range
+__device__ __forceinline__ void copy_csr(const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
+                                         const float *__restrict__ val, int r0, int n, int32_t e0, int64_t ne,
+                                         int32_t *__restrict__ rowptr_out, int32_t *__restrict__ col_out, f16 *__restrict__ v16,
+                                         float *__restrict__ v32, int o, int64_t off, int shift, int lane)
+{
+    for (int i = lane; i < n; i += kWave) rowptr_out[o + i] = (int32_t)(off + (rowptr[r0 + i] - e0));
+    for (int64_t i = lane; i < ne; i += kWave) {
+        const int c = col[e0 + i];
+        const float v = val[e0 + i];
+        col_out[off + i] = c + shift;
+        if (v16) v16[off + i] = (f16)v;
+        if (v32) v32[off + i] = v;
+    }
+}
+
+__global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_kernel(CollateArgs a)
+{
+    const int lane = threadIdx.x % kWave;
+    const int64_t bi = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+    const sgx_graph_set &s = a.s;
+    const sgx_graph_batch &b = a.b;
+    if (bi >= b.n_graphs) return;
+    const int pos = (int)bi;
+    const int g = b.index[pos];
+    if (g < 0 || g >= s.n_graphs) return;
+    const int r0 = s.node_ptr[g], n = s.node_ptr[g + 1] - r0;
+    const int64_t se0 = s.edge_ptr[g], ne = (int64_t)s.edge_ptr[g + 1] - se0;
+    const int32_t a0 = s.rowPtr_adj[r0], f0 = s.rowPtr_fea[r0];
+    const int64_t na = (int64_t)s.rowPtr_adj[r0 + n] - a0, nf = (int64_t)s.rowPtr_fea[r0 + n] - f0;
+    const int o = b.node_off[pos];
+    const int64_t eo = b.edge_off[pos], ao = b.adj_off[pos], fo = b.fea_off[pos];
+    // offsets that do not match the set's counts: skip the graph rather than write past a buffer
+    if (n < 0 || ne < 0 || na < 0 || nf < 0 || o < 0 || (int64_t)o + n > b.n_rows || eo < 0 || eo + ne > b.n_edges ||
+        ao < 0 || ao + na > b.nnz_adj || fo < 0 || fo + nf > b.nnz_fea)
+        return;
+    if (lane == 0) {
+        b.graph_ptr[pos] = o;
+        b.y[pos] = s.y[g];
+        if (pos == b.n_graphs - 1) {
+            b.graph_ptr[b.n_graphs] = b.n_rows;
+            b.rowPtr_adj[b.n_rows] = (int32_t)b.nnz_adj;
+            b.rowPtr_fea[b.n_rows] = (int32_t)b.nnz_fea;
+        }
+    }
+    for (int i = lane; i < n; i += kWave) b.batch[o + i] = pos;
+    copy_f32(b.x + (int64_t)o * s.n_feat, s.x + (int64_t)r0 * s.n_feat, (int64_t)n * s.n_feat, lane);
+    const int32_t *__restrict__ src = s.edge_index + se0, *__restrict__ dst = s.edge_index + s.n_edges + se0;
+    for (int64_t i = lane; i < ne; i += kWave) {
+        b.edge_index[eo + i] = (int64_t)src[i] + o;
+        b.edge_index[b.n_edges + eo + i] = (int64_t)dst[i] + o;
+    }
+    copy_csr(s.rowPtr_adj, s.columnIndex_adj, s.values_adj, r0, n, a0, na, b.rowPtr_adj, b.columnIndex_adj,
+             static_cast<f16 *>(b.values_adj[SGX_F16]), static_cast<float *>(b.values_adj[SGX_F32]), o, ao, o - r0, lane);
+    copy_csr(s.rowPtr_fea, s.columnIndex_fea, s.values_fea, r0, n, f0, nf, b.rowPtr_fea, b.columnIndex_fea,
+             static_cast<f16 *>(b.values_fea[SGX_F16]), static_cast<float *>(b.values_fea[SGX_F32]), o, fo, 0, lane);
+}
+
+int check_collate(const sgx_graph_set *s, const sgx_graph_batch *b)
+{
+    if (!s || !b) return SGX_ERR_NULL;
+    if (s->n_graphs < 1 || s->n_feat < 1 || s->n_edges < 0) return SGX_ERR_SHAPE;
+    if (b->n_graphs < 1 || b->n_rows < 0 || b->n_edges < 0 || b->nnz_adj < 0 || b->nnz_fea < 0) return SGX_ERR_SHAPE;
+    if (!s->node_ptr || !s->edge_ptr || !s->x || !s->y || !s->rowPtr_adj || !s->columnIndex_adj || !s->values_adj ||
+        !s->rowPtr_fea || !s->columnIndex_fea || !s->values_fea || (s->n_edges > 0 && !s->edge_index))
+        return SGX_ERR_NULL;
+    if (!b->index || !b->node_off || !b->edge_off || !b->adj_off || !b->fea_off || !b->batch || !b->y || !b->graph_ptr ||
+        !b->rowPtr_adj || !b->rowPtr_fea)
+        return SGX_ERR_NULL;
+    if ((b->n_rows > 0 && !b->x) || (b->n_edges > 0 && !b->edge_index) || (b->nnz_adj > 0 && !b->columnIndex_adj) ||
+        (b->nnz_fea > 0 && !b->columnIndex_fea))
+        return SGX_ERR_NULL;
+    return SGX_OK;
+}
+
+}  // namespace
+
+extern "C" int sgx_collate_graphs(const sgx_graph_set *set, const sgx_graph_batch *b, void *stream)
+{
+    const int rc = check_collate(set, b);
+    if (rc != SGX_OK) return rc;
+    CollateArgs a;
+    a.s = *set;
+    a.b = *b;
+    const unsigned grid = (unsigned)((b->n_graphs + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL(collate_graphs_kernel, dim3(grid), dim3(kWave * kWavesPerBlock), 0, (hipStream_t)stream, a);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}

@@ -32,6 +32,7 @@ struct sgx_batch_plan {
     int fits;
     int kind;            // SGX_BATCH_FORWARD / SGX_BATCH_BACKWARD: which kernel's LDS tiles set the row budget
     int32_t *group_graph;   // [n_groups + 1] device: first graph of every group, then n_graphs
+    int owns_groups;        // 0: group_graph is the caller's buffer (sgx_batch_plan_create_known), not freed here
 };
 
 #ifndef SGX_STACK_ROWS_CAP
@@ -138,6 +139,18 @@ __global__ void group_graphs_kernel(int n_groups, int n_graphs, int S, const int
         else hi = mid;
     }
     first[k] = k == 0 ? 0 : lo;
+}
+
+// S = the window of first rows a group takes: its rows are at most S - 1 + the largest graph <= R; about one group per
+// CU for a small batch, full groups for a large one.  Returns the group count of a batch that fits (n_graphs > 0).
+int plan_groups(int n_rows, int rows, int max_graph, int *S_out)
+{
+    const int target = (n_rows + kTargetGroups - 1) / kTargetGroups;
+    int S = rows - max_graph + 1;
+    if (target < S) S = target;
+    if (S < 1) S = 1;
+    *S_out = S;
+    return n_rows > 0 ? (n_rows + S - 1) / S : 1;
 }
 
 // ---- the fused kernel ---------------------------------------------------------------------------------------------
@@ -878,6 +891,7 @@ extern "C" int sgx_batch_plan_create_ex(int dtype, int n_rows, int n_graphs, con
     p->max_graph = 0;
     p->fits = 1;
     p->group_graph = nullptr;
+    p->owns_groups = 1;
     if (n_rows == 0 && n_graphs == 0) {             // nothing to check or to run
         *plan = p;
         return SGX_OK;
@@ -908,12 +922,8 @@ extern "C" int sgx_batch_plan_create_ex(int dtype, int n_rows, int n_graphs, con
     p->max_graph = host.max_graph;
     p->fits = (p->rows > 0 && host.max_graph <= p->rows) ? 1 : 0;
     if (p->fits && n_graphs > 0) {
-        // S = the window of first rows a group takes: its rows are at most S - 1 + the largest graph <= R
-        const int target = (n_rows + kTargetGroups - 1) / kTargetGroups;
-        int S = p->rows - host.max_graph + 1;
-        if (target < S) S = target;
-        if (S < 1) S = 1;
-        p->n_groups = n_rows > 0 ? (n_rows + S - 1) / S : 1;
+        int S = 1;
+        p->n_groups = plan_groups(n_rows, p->rows, host.max_graph, &S);
         if (hipMalloc((void **)&p->group_graph, sizeof(int32_t) * ((size_t)p->n_groups + 1)) != hipSuccess) return fail(SGX_ERR_HIP);
         hipLaunchKernelGGL(group_graphs_kernel, dim3((unsigned)((p->n_groups + 1 + 255) / 256)), dim3(256), 0, s, p->n_groups, n_graphs,
                            S, graph_ptr, p->group_graph);
@@ -936,9 +946,69 @@ extern "C" int sgx_batch_plan_create(int dtype, int n_rows, int n_graphs, const 
 extern "C" int sgx_batch_plan_destroy(sgx_batch_plan *plan)
 {
     if (!plan) return SGX_OK;
-    if (plan->group_graph) SGX_HIP_CHECK(hipFree(plan->group_graph));
+    if (plan->group_graph && plan->owns_groups) SGX_HIP_CHECK(hipFree(plan->group_graph));
     delete plan;
     return SGX_OK;
+}
+
+extern "C" int sgx_batch_plan_group_count(int dtype, int n_rows, int max_graph, int max_width, int kind)
+{
+    if (n_rows < 0 || max_graph < 0 || max_graph > n_rows || max_width < 1) return SGX_ERR_SHAPE;
+    if (dtype != SGX_F16 && dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;
+    if (kind != SGX_BATCH_FORWARD && kind != SGX_BATCH_BACKWARD) return SGX_ERR_UNSUPPORTED;
+    const int rows = rows_budget(dtype, max_width, kind);
+    if (rows <= 0 || max_graph > rows) return 0;
+    int S = 1;
+    return plan_groups(n_rows, rows, max_graph, &S);
+}
+
+extern "C" int sgx_batch_plan_create_known(int dtype, int n_rows, int n_graphs, const int32_t *graph_ptr, int max_graph,
+                                           int max_width, int kind, int32_t *group_graph, sgx_batch_plan **plan, void *stream)
+{
+    if (!plan) return SGX_ERR_NULL;
+    *plan = nullptr;
+    if (n_rows < 0 || n_graphs < 0 || max_width < 1 || max_graph < 0 || max_graph > n_rows) return SGX_ERR_SHAPE;
+    if (n_rows > 0 && (n_graphs == 0 || (int64_t)max_graph * n_graphs < n_rows)) return SGX_ERR_SHAPE;
+    if (dtype != SGX_F16 && dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;
+    if (kind != SGX_BATCH_FORWARD && kind != SGX_BATCH_BACKWARD) return SGX_ERR_UNSUPPORTED;
+    if ((n_rows > 0 || n_graphs > 0) && !graph_ptr) return SGX_ERR_NULL;
+    const int rows = rows_budget(dtype, max_width, kind);
+    // the same fields sgx_batch_plan_create_ex records once its checks pass
+    const int fits = (n_rows == 0 && n_graphs == 0) ? 1 : ((rows > 0 && max_graph <= rows) ? 1 : 0);
+    int S = 1;
+    const int n_groups = (fits && n_graphs > 0) ? plan_groups(n_rows, rows, max_graph, &S) : 0;
+    if (n_groups > 0 && !group_graph) return SGX_ERR_NULL;
+    sgx_batch_plan *p = new sgx_batch_plan;
+    p->dtype = dtype;
+    p->n_rows = n_rows;
+    p->n_graphs = n_graphs;
+    p->max_width = max_width;
+    p->kind = kind;
+    p->rows = rows;
+    p->n_groups = n_groups;
+    p->max_graph = max_graph;
+    p->fits = fits;
+    p->group_graph = n_groups > 0 ? group_graph : nullptr;
+    p->owns_groups = 0;
+    if (n_groups > 0) {
+        hipLaunchKernelGGL(group_graphs_kernel, dim3((unsigned)((n_groups + 1 + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
+                           n_groups, n_graphs, S, graph_ptr, group_graph);
+        if (hipGetLastError() != hipSuccess) {
+            delete p;
+            return SGX_ERR_HIP;
+        }
+    }
+    *plan = p;
+    return SGX_OK;
+}
+
+extern "C" int64_t sgx_batch_plan_export_groups(const sgx_batch_plan *plan, int32_t *dst, int64_t capacity, void *stream)
+{
+    if (!plan) return SGX_ERR_NULL;
+    const int64_t n = plan->group_graph ? (int64_t)plan->n_groups + 1 : 0;
+    if (!dst || capacity < n || n == 0) return n;
+    SGX_HIP_CHECK(hipMemcpyAsync(dst, plan->group_graph, sizeof(int32_t) * (size_t)n, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return n;
 }
 
 extern "C" int sgx_batch_plan_rows(const sgx_batch_plan *plan) { return plan ? plan->rows : SGX_ERR_NULL; }

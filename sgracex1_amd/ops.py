@@ -6,6 +6,7 @@ All tensors must live on a ROCm device ("cuda"); nothing in this module computes
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -70,6 +71,20 @@ def cached_on(tensor, key, build):
     if hit is None or hit[0] != tensor._version:
         hit = store[key] = (tensor._version, build())
     return hit[1]
+
+
+def attach(tensor, key, value):
+    """Fill the cached_on entry `key` of `tensor` with a value built elsewhere (the graph loader hands its batches over with
+    their CSRs and graph_ptr already in place); it holds while the tensor is unchanged, as a built entry does."""
+    tensor.__dict__.setdefault("_sgx_cache", {})[key] = (tensor._version, value)
+    return value
+
+
+def recorded(tensor, key):
+    """The cached_on entry `key` of `tensor` if there is one and the tensor is unchanged since; None otherwise (builds
+    nothing)."""
+    hit = tensor.__dict__.get("_sgx_cache", {}).get(key)
+    return hit[1] if hit is not None and hit[0] == tensor._version else None
 
 
 _workspaces = {}
@@ -842,22 +857,65 @@ class BatchPlan:
                                                _stream()), "sgx_batch_plan_create_ex")
         self._h = h
 
+    @classmethod
+    def known(cls, graph_ptr, n_rows, dtype, max_graph, max_width, kind=_lib.SGX_BATCH_FORWARD):
+        """The trusted plan (sgx_batch_plan_create_known) of a batch whose blocks the caller vouches for -- graph_ptr cuts
+        its adjacency into diagonal blocks, the largest of max_graph rows -- as the collator's batches are: the plan
+        BatchPlan gives on the same batch, without its device checks, read-back and stream synchronisation.  The
+        group_graph table lives in a tensor this object keeps."""
+        _dev(graph_ptr, "graph_ptr")
+        if graph_ptr.dtype != torch.int32:
+            raise TypeError("graph_ptr must be int32")
+        self = cls.__new__(cls)
+        self._h = None
+        self.dtype = dtype
+        self.n_rows, self.n_graphs, self.max_width, self.kind = int(n_rows), graph_ptr.numel() - 1, int(max_width), int(kind)
+        code = dtype_code(dtype)
+        n = lib.sgx_batch_plan_group_count(code, self.n_rows, int(max_graph), self.max_width, self.kind)
+        if n < 0:
+            check(n, "sgx_batch_plan_group_count")
+        self._group_graph = torch.empty(n + 1, dtype=torch.int32, device=graph_ptr.device) if n > 0 else None
+        h = ctypes.c_void_p()
+        check(lib.sgx_batch_plan_create_known(code, self.n_rows, self.n_graphs, _ptr(graph_ptr), int(max_graph), self.max_width,
+                                              self.kind, _ptr(self._group_graph), ctypes.byref(h), _stream()),
+              "sgx_batch_plan_create_known")
+        self._h = h
+        return self
+
     @staticmethod
     def cached(adj, graph_ptr, max_width, kind=_lib.SGX_BATCH_FORWARD):
         """The plan of (adj, graph_ptr, max_width, kind), kept on the adjacency's column array while both stay unchanged;
         None when the batch is not block-diagonal under graph_ptr (remembered too, so that a caller falls back without a
-        device sync per call)."""
+        device sync per call).  Where graph_ptr carries the block facts a GraphLoader recorded for this adjacency, the
+        plan is the trusted one (BatchPlan.known): no device check, no synchronisation."""
         key = ("batch_plan", adj.val.dtype, int(max_width)) + (() if kind == _lib.SGX_BATCH_FORWARD else (int(kind),))
         hit = cached_on(adj.col, key, lambda: [None, -1, None])
         if hit[0] is not graph_ptr or hit[1] != graph_ptr._version:
-            try:
-                plan = BatchPlan(adj, graph_ptr, max_width, kind)
-            except _lib.SgxError as e:
-                if e.status != _lib.SGX_ERR_BLOCKS:
-                    raise
-                plan = None
+            facts = recorded(graph_ptr, ("block_facts",))
+            if facts is not None and facts["n_rows"] == adj.n_rows and any(c() is adj.col for c in facts["cols"]):
+                plan = BatchPlan.known(graph_ptr, adj.n_rows, adj.val.dtype, facts["max_graph"], max_width, kind)
+            else:
+                try:
+                    plan = BatchPlan(adj, graph_ptr, max_width, kind)
+                except _lib.SgxError as e:
+                    if e.status != _lib.SGX_ERR_BLOCKS:
+                        raise
+                    plan = None
             hit[:] = [graph_ptr, graph_ptr._version, plan]
         return hit[2]
+
+    def export_groups(self):
+        """The plan's group_graph table (first graph of every group, then n_graphs) as an int32 tensor; empty when the
+        plan has none.  For tests."""
+        n = lib.sgx_batch_plan_export_groups(self._h, None, 0, _stream())
+        if n < 0:
+            check(int(n), "sgx_batch_plan_export_groups")
+        out = torch.empty(int(n), dtype=torch.int32, device="cuda")
+        if n:
+            got = lib.sgx_batch_plan_export_groups(self._h, _ptr(out), int(n), _stream())
+            if got < 0:
+                check(int(got), "sgx_batch_plan_export_groups")
+        return out
 
     @property
     def handle(self):
@@ -883,6 +941,171 @@ class BatchPlan:
         h, self._h = getattr(self, "_h", None), None
         if h:
             _destroy(h)
+
+
+# ---- shuffled graph mini-batches collated on the device (sgx_collate_graphs) -----------------------------------------
+class GraphSet:
+    """A graph-classification dataset uploaded once (include/sgx.h, "shuffled graph mini-batches"): the graphs collated
+    in dataset order -- x (fp32), the stored edge lists in graph-local ids, y -- plus the adjacency as
+    csr_from_edge_index builds it and the CSR of x, both with fp32 values, and on the host the per-graph counts every
+    batch's offsets are computed from.  Building it synchronises; collating from it does not.
+
+    graphs: pyg_lite.Graph objects (x [n, F], edge_index [2, E] in local ids 0 .. n-1, y of one element).  A graph with
+    no node, an edge outside its graph, or x widths that differ: ValueError.  Graphs without edges, self loops and
+    repeated edges are fine."""
+
+    def __init__(self, graphs, device="cuda"):
+        graphs = list(graphs)
+        if not graphs:
+            raise ValueError("GraphSet needs at least one graph")
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise ValueError("GraphSet lives on the GPU")
+        n_nodes = np.array([g.x.shape[0] for g in graphs], dtype=np.int64)
+        n_edges = np.array([g.edge_index.shape[1] for g in graphs], dtype=np.int64)
+        if (n_nodes < 1).any():
+            raise ValueError(f"graph {int(np.argmax(n_nodes < 1))} has no node; GraphSet refuses empty graphs")
+        F = graphs[0].x.shape[1]
+        if any(g.x.dim() != 2 or g.x.shape[1] != F for g in graphs):
+            raise ValueError("every graph's x must be [n, F] with the same F")
+        if any(g.y.numel() != 1 for g in graphs):
+            raise ValueError("every graph's y must hold one label")
+        ei = torch.cat([g.edge_index.reshape(2, -1).to(torch.int64).cpu() for g in graphs], dim=1)
+        owner = np.repeat(np.arange(len(graphs)), n_edges)
+        if ei.numel() and ((ei < 0).any() or (ei.numpy() >= n_nodes[owner][None, :]).any()):
+            raise ValueError("an edge leaves its graph (edge_index must hold graph-local ids 0 .. n-1)")
+        if n_nodes.sum() >= 2**31 or n_edges.sum() >= 2**31:
+            raise ValueError("GraphSet holds fewer than 2^31 rows and edges")
+        node_ptr = np.zeros(len(graphs) + 1, np.int64)
+        np.cumsum(n_nodes, out=node_ptr[1:])
+        edge_ptr = np.zeros(len(graphs) + 1, np.int64)
+        np.cumsum(n_edges, out=edge_ptr[1:])
+        self.device, self.n_feat, self.n_rows, self.n_edges = dev, int(F), int(node_ptr[-1]), int(edge_ptr[-1])
+        self.x = torch.cat([g.x.float().cpu() for g in graphs]).to(dev).contiguous()
+        self.y = torch.cat([g.y.reshape(1).to(torch.int64).cpu() for g in graphs]).to(dev)
+        self.edge_index = ei.to(torch.int32).to(dev).contiguous()
+        self.node_ptr = torch.as_tensor(node_ptr, dtype=torch.int32).to(dev)
+        self.edge_ptr = torch.as_tensor(edge_ptr, dtype=torch.int32).to(dev)
+        glob = ei + torch.as_tensor(node_ptr[owner], dtype=torch.int64).unsqueeze(0)
+        self.adj = csr_from_edge_index(glob.to(dev), self.n_rows, dtype=torch.float32)
+        self.fea = Csr.from_dense(self.x)
+        rp_a, rp_f = self.adj.rowptr.cpu().numpy().astype(np.int64), self.fea.rowptr.cpu().numpy().astype(np.int64)
+        # per-graph counts on the host: rows, stored edges, adjacency entries, feature entries
+        self.counts = (n_nodes, n_edges, np.diff(rp_a[node_ptr]), np.diff(rp_f[node_ptr]))
+        d = _lib.GraphSet()
+        d.n_graphs, d.n_feat, d.n_edges = len(graphs), self.n_feat, self.n_edges
+        d.node_ptr, d.edge_ptr = self.node_ptr.data_ptr(), self.edge_ptr.data_ptr()
+        d.edge_index = self.edge_index.data_ptr() if self.n_edges else None
+        d.x, d.y = self.x.data_ptr(), self.y.data_ptr()
+        d.rowPtr_adj, d.columnIndex_adj, d.values_adj = self.adj.rowptr.data_ptr(), self.adj.col.data_ptr(), self.adj.val.data_ptr()
+        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = self.fea.rowptr.data_ptr(), self.fea.col.data_ptr(), self.fea.val.data_ptr()
+        self.desc = d
+
+    def __len__(self):
+        return len(self.counts[0])
+
+    def prepare(self, idx):
+        """The batch of graph ids `idx` (a host sequence, in batch order) ready to collate: its exclusive offsets
+        computed here from the host counts and sent with idx through pinned memory on a non-blocking copy."""
+        if isinstance(idx, torch.Tensor):
+            if idx.is_cuda:
+                raise ValueError("prepare takes the graph ids on the host (the offsets are computed there)")
+            idx = idx.numpy()
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        B = idx.size
+        if B < 1:
+            raise ValueError("a batch holds at least one graph")
+        if idx.min() < 0 or idx.max() >= len(self):
+            raise ValueError(f"graph ids must lie in [0, {len(self)})")
+        host, totals = batch_offsets(self.counts, idx)
+        dev = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
+        return BatchIndex(dev, B, totals, int(self.counts[0][idx].max()))
+
+
+def batch_offsets(counts, idx):
+    """What GraphSet.prepare sends to the device for the graph ids idx [B]: one int32 array of idx followed by the
+    exclusive offsets [B+1] of rows, stored edges, adjacency entries and feature entries (counts: those four per-graph
+    count arrays), and the four totals.  Host only."""
+    idx = np.asarray(idx, dtype=np.int64)
+    B = idx.size
+    host = np.empty(B + 4 * (B + 1), dtype=np.int32)
+    host[:B] = idx
+    totals = []
+    for k, c in enumerate(counts):
+        off = np.zeros(B + 1, dtype=np.int64)
+        np.cumsum(np.asarray(c, dtype=np.int64)[idx], out=off[1:])
+        if off[-1] >= 2**31:
+            raise ValueError("a batch holds fewer than 2^31 rows, edges and entries")
+        host[B + k * (B + 1): B + (k + 1) * (B + 1)] = off
+        totals.append(int(off[-1]))
+    return host, totals
+
+
+class BatchIndex:
+    """A prepared batch (GraphSet.prepare): graph ids and offsets on the device, totals and the largest graph on the
+    host.  Reusable: collating the same BatchIndex again (a captured step) reads the same device buffer."""
+
+    def __init__(self, dev, n_graphs, totals, max_graph):
+        self.dev, self.n_graphs, self.max_graph = dev, int(n_graphs), int(max_graph)
+        self.n_rows, self.n_edges, self.nnz_adj, self.nnz_fea = totals
+        B = self.n_graphs
+        self.index, self.node_off, self.edge_off, self.adj_off, self.fea_off = (
+            dev[:B], dev[B:2 * B + 1], dev[2 * B + 1:3 * B + 2], dev[3 * B + 2:4 * B + 3], dev[4 * B + 3:])
+
+
+class Collated:
+    """One collated batch (collate_graphs): x [n, F] fp32, edge_index [2, E] int64, batch [n] int64, y [B] int64,
+    graph_ptr [B+1] int32, the adjacency (adj_rowptr, adj_col, adj_val {dtype: values}) and the feature CSR (fea_*)."""
+
+    FIELDS = ("x", "edge_index", "batch", "y", "graph_ptr", "adj_rowptr", "adj_col", "fea_rowptr", "fea_col")
+
+    def __init__(self, index, n_feat, dtypes, device):
+        e = lambda *shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=device)
+        i = index
+        self.index, self.n_feat = i, n_feat
+        self.x, self.edge_index = e(i.n_rows, n_feat, dt=torch.float32), e(2, i.n_edges, dt=torch.int64)
+        self.batch, self.y, self.graph_ptr = e(i.n_rows, dt=torch.int64), e(i.n_graphs, dt=torch.int64), e(i.n_graphs + 1)
+        self.adj_rowptr, self.adj_col = e(i.n_rows + 1), e(i.nnz_adj)
+        self.fea_rowptr, self.fea_col = e(i.n_rows + 1), e(i.nnz_fea)
+        self.adj_val = {dt: e(i.nnz_adj, dt=dt) for dt in dtypes}
+        self.fea_val = {dt: e(i.nnz_fea, dt=dt) for dt in dtypes}
+
+    def fits(self, index, n_feat, dtypes):
+        i, j = self.index, index
+        return ((i.n_graphs, i.n_rows, i.n_edges, i.nnz_adj, i.nnz_fea) == (j.n_graphs, j.n_rows, j.n_edges, j.nnz_adj, j.nnz_fea)
+                and self.n_feat == n_feat and set(self.adj_val) >= set(dtypes) and set(self.fea_val) >= set(dtypes))
+
+
+def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None):
+    """The batch of the graphs `idx` of `graphset` in that order, built on the device by one launch of
+    sgx_collate_graphs: the same x / edge_index / batch / y as pyg_lite.collate, the same adjacency as
+    csr_from_edge_index, the same feature CSR as Csr.from_dense, graph_ptr as graph_ptr_of -- with the CSR values in each
+    of `dtypes`.  idx: host graph ids, or a BatchIndex from graphset.prepare.  out: a Collated of the same sizes to write
+    into (a captured batch); a new one otherwise.  No synchronisation."""
+    index = idx if isinstance(idx, BatchIndex) else graphset.prepare(idx)
+    dtypes = tuple(dtypes)
+    for dt in dtypes:
+        dtype_code(dt)
+    if out is None:
+        out = Collated(index, graphset.n_feat, dtypes, graphset.device)
+    elif not out.fits(index, graphset.n_feat, dtypes):
+        raise ValueError("collate_graphs: `out` was made for a batch of other sizes or dtypes")
+    else:
+        out.index = index
+    b = _lib.GraphBatch()
+    b.n_graphs, b.n_rows = index.n_graphs, index.n_rows
+    b.n_edges, b.nnz_adj, b.nnz_fea = index.n_edges, index.nnz_adj, index.nnz_fea
+    b.index, b.node_off, b.edge_off = index.index.data_ptr(), index.node_off.data_ptr(), index.edge_off.data_ptr()
+    b.adj_off, b.fea_off = index.adj_off.data_ptr(), index.fea_off.data_ptr()
+    b.x, b.edge_index, b.batch, b.y = out.x.data_ptr(), out.edge_index.data_ptr(), out.batch.data_ptr(), out.y.data_ptr()
+    b.graph_ptr = out.graph_ptr.data_ptr()
+    b.rowPtr_adj, b.columnIndex_adj = out.adj_rowptr.data_ptr(), out.adj_col.data_ptr()
+    b.rowPtr_fea, b.columnIndex_fea = out.fea_rowptr.data_ptr(), out.fea_col.data_ptr()
+    for dt in dtypes:
+        b.values_adj[dtype_code(dt)] = out.adj_val[dt].data_ptr()
+        b.values_fea[dtype_code(dt)] = out.fea_val[dt].data_ptr()
+    check(lib.sgx_collate_graphs(ctypes.byref(graphset.desc), ctypes.byref(b), _stream()), "sgx_collate_graphs")
+    return out
 
 
 def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, head_bias=None, want_layer_outputs=False,

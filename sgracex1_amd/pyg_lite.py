@@ -1,9 +1,11 @@
 """The few torch_geometric pieces the reference's notebooks use around the hot path, restated
 with plain torch so the end-to-end runs do not need PyG (it is not installed here): the TU
 dataset reader for MUTAG (raw files -> graphs), DataLoader-style batching into one block-
-diagonal graph, `to_dense_adj`, `global_mean_pool` (MOL cells 4-10, 18), and the NeighborLoader
-of the node-classification demo's mini-batch mode (demo_sgrace.py:112-125), sampled on the GPU.
+diagonal graph, `to_dense_adj`, `global_mean_pool` (MOL cells 4-10, 18), the same shuffled batches collated on the GPU
+(GraphLoader), and the NeighborLoader of the node-classification demo's mini-batch mode (demo_sgrace.py:112-125),
+sampled on the GPU.
 """
+import weakref
 from dataclasses import dataclass
 from typing import List
 
@@ -86,6 +88,55 @@ class DataLoader:
 
     def __len__(self):
         return (len(self.dataset) + self.batch_size - 1) // self.batch_size
+
+
+class GraphLoader:
+    """DataLoader(dataset, batch_size, shuffle, generator) with the dataset on the GPU (ops.GraphSet, uploaded once) and
+    every batch collated there by one kernel launch (ops.collate_graphs): the same permutation rule as DataLoader --
+    torch.randperm(n, generator=generator) on the host, contiguous slices, a partial last batch kept -- and the same
+    Batch contents, as device tensors.  Each batch arrives with what the fused GCN stack needs already attached, so
+    GCN_PYNQ runs it without a device synchronisation: graph_ptr on `batch` (ops.graph_ptr_of), the adjacency on
+    `edge_index` ("adj_csr", n, dtype) and the feature CSR on `x` ("fea_csr", dtype) for each of `dtypes`, and on
+    graph_ptr the block facts (its largest graph) from which ops.BatchPlan.cached builds trusted plans.
+    dataset: a list of Graph, or an ops.GraphSet."""
+
+    def __init__(self, dataset, batch_size=1, shuffle=False, generator=None, device=None, dtypes=(torch.float16,)):
+        from . import ops
+        self.graphs = dataset if isinstance(dataset, ops.GraphSet) else ops.GraphSet(dataset, device or "cuda")
+        self.batch_size, self.shuffle, self.generator = int(batch_size), bool(shuffle), generator
+        self.dtypes = tuple(dtypes)
+        if self.batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+
+    def __len__(self):
+        return (len(self.graphs) + self.batch_size - 1) // self.batch_size
+
+    def __iter__(self):
+        n = len(self.graphs)
+        order = torch.randperm(n, generator=self.generator).numpy() if self.shuffle else np.arange(n)
+        for i in range(0, n, self.batch_size):
+            yield self.collate(order[i:i + self.batch_size])
+
+    def collate(self, idx, out=None):
+        """The Batch of graph ids `idx` (host, in batch order), caches attached; out: an ops.Collated to reuse."""
+        from . import ops
+        c = ops.collate_graphs(self.graphs, idx, self.dtypes, out=out)
+        return attach_batch(c)
+
+
+def attach_batch(c):
+    """A pyg_lite.Batch over the tensors of an ops.Collated, with its graph_ptr, CSRs and block facts attached."""
+    from . import ops
+    n, B = c.x.shape[0], c.index.n_graphs
+    ops.attach(c.batch, ("graph_ptr",), c.graph_ptr)
+    cols = []
+    for dt, val in c.adj_val.items():
+        A = ops.Csr(c.adj_rowptr, c.adj_col, val, n)
+        cols.append(weakref.ref(A.col))            # (weak: the adjacency's cache already holds graph_ptr)
+        ops.attach(c.edge_index, ("adj_csr", n, dt), A)
+        ops.attach(c.x, ("fea_csr", dt), ops.Csr(c.fea_rowptr, c.fea_col, c.fea_val[dt], c.n_feat))
+    ops.attach(c.graph_ptr, ("block_facts",), {"n_rows": n, "max_graph": c.index.max_graph, "cols": cols})
+    return Batch(c.x, c.edge_index, c.y, c.batch, B)
 
 
 def to_dense_adj(edge_index, num_nodes=None):

@@ -1,0 +1,179 @@
+#!/usr/bin/env python3
+"""What a shuffled training step costs with the batches collated on the host (pyg_lite.DataLoader: Python collate,
+host-to-device copies, then the synchronising builders -- graph_ptr_of, csr_from_edge_index, the feature CSR, the batch
+plan) against the device collator (pyg_lite.GraphLoader: one sgx_collate_graphs launch, attached CSRs, trusted plans).
+
+Workloads, MOL cell 18's model (7 -> 64 ReLU -> 64, mean pool, dropout, 64 -> 2 head, cross entropy, Adam) with
+GCN_PYNQ(train_stack=True), layer_count 2, fp16 layers:
+  step    MUTAG (188 graphs) at batch 256 (the notebook's; one shuffled batch per epoch) and 64; and the million-graph MUTAG
+          replica of tools/stack_train_probe.py at batch 4096.  step_ms = host wall clock of whole steps (loader
+          iteration, forward, loss, backward, Adam), the window closed by a device synchronisation, after three warm-up
+          steps; per loader.  cached: the same batch every step (the loop of examples/molecule_gcn_train.py), for reference.
+  collate sgx_collate_graphs alone on a prepared batch (hipEvents around --reps launches), and with GraphSet.prepare
+          (host offsets and the pinned upload) included: graphs/s, and GB/s over the bytes the kernel must move.
+One JSON line each.  --stats CSV turns a `rocprofv3 --kernel-trace --stats` kernel_stats file of a `--only collate` run
+into one line for the collate kernel.
+
+    python tools/graph_loader_probe.py > profiles/r06_graph_loader.jsonl
+"""
+import argparse
+import csv
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from sgracex1_amd import molecule_gcn as M, ops, pyg_lite as G, pynq_shim  # noqa: E402
+
+
+def mutag_graphs():
+    raw = np.load(os.path.join(ROOT, "tests", "golden", "mutag_raw.npz"))
+    return G.load_tu_raw(raw["A"], raw["graph_indicator"], raw["graph_labels"], raw["node_labels"])
+
+
+def model(dev):
+    ip = pynq_shim.Overlay("gnn_all.bit").mmult_top_0
+    ip.register_map.layer_count = 2
+    return M.GCN_PYNQ(64, 7, 2, ip, train_stack=True).to(dev).train()
+
+
+def step_times(graphs, batch_size, dev, max_steps, which):
+    """{loader: per-step ms} over up to max_steps steps after a warm-up of a few steps."""
+    out = {}
+    crit = torch.nn.CrossEntropyLoss()
+    for name in which:
+        torch.manual_seed(5)
+        m = model(dev)
+        opt = torch.optim.Adam(m.parameters(), lr=0.01)
+        gen = torch.Generator().manual_seed(12345)
+        if name == "host":
+            loader = G.DataLoader(graphs, batch_size=batch_size, shuffle=True, generator=gen)
+        elif name == "device":
+            loader = G.GraphLoader(graphs, batch_size=batch_size, shuffle=True, generator=gen, device=dev)
+        else:                                                            # cached: one batch, the same tensors every step
+            fixed = G.collate(graphs[:batch_size]).to(dev)
+            loader = [fixed] * len(G.DataLoader(graphs, batch_size=batch_size))
+
+        def batches():
+            while True:
+                for b in loader:
+                    yield b.to(dev) if name == "host" else b
+
+        it = batches()
+
+        def run(n):
+            for _ in range(n):
+                b = next(it)
+                opt.zero_grad()
+                crit(m(1, b.x, b.edge_index, b.batch), b.y).backward()
+                opt.step()
+
+        run(min(3, max_steps))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(max_steps)
+        torch.cuda.synchronize()
+        out[name] = (time.perf_counter() - t0) * 1e3 / max_steps
+        del m, opt, loader
+    return out
+
+
+def collate_bytes(gs, index):
+    """Bytes sgx_collate_graphs must read and write for a batch (fp16 CSR values out)."""
+    n, E, na, nf, B, F = index.n_rows, index.n_edges, index.nnz_adj, index.nnz_fea, index.n_graphs, gs.n_feat
+    read = n * F * 4 + 2 * E * 4 + 2 * (n * 4 + na * 8) + (nf * 8) + B * (4 * 4 + 5 * 4 + 8)
+    write = n * F * 4 + 2 * E * 8 + n * 8 + B * 8 + (B + 1) * 4 + 2 * (n + 1) * 4 + na * 6 + nf * 6
+    return read + write
+
+
+def collate_times(gs, batch_size, reps, trials, seed=3):
+    perm = torch.randperm(len(gs), generator=torch.Generator().manual_seed(seed)).numpy()[:batch_size]
+    index = gs.prepare(perm)
+    out = ops.collate_graphs(gs, index)
+
+    def timed(fn):
+        res = []
+        for _ in range(trials):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            a.record()
+            for _ in range(reps):
+                fn()
+            b.record()
+            b.synchronize()
+            res.append((a.elapsed_time(b) / reps, (time.perf_counter() - t0) * 1e3 / reps))
+        return [float(np.median([r[k] for r in res])) for k in range(2)]
+
+    kernel_ms, _ = timed(lambda: ops.collate_graphs(gs, index, out=out))
+    _, prepared_ms = timed(lambda: ops.collate_graphs(gs, perm, out=out))
+    nbytes = collate_bytes(gs, index)
+    return {"graphs": int(index.n_graphs), "rows": index.n_rows, "edges": index.n_edges, "adj_entries": index.nnz_adj,
+            "fea_entries": index.nnz_fea, "bytes": nbytes, "collate_ms": kernel_ms,
+            "collate_graphs_per_s": index.n_graphs / (kernel_ms * 1e-3), "collate_GBps": nbytes / (kernel_ms * 1e-3) / 1e9,
+            "prepare_and_collate_wall_ms": prepared_ms,
+            "prepare_and_collate_graphs_per_s": index.n_graphs / (prepared_ms * 1e-3)}
+
+
+def stats_line(path):
+    with open(path) as f:
+        for row in csv.DictReader(f):
+            if "collate_graphs_kernel" in row["Name"]:
+                return {"workload": "rocprofv3_kernel_stats", "kernel": "collate_graphs_kernel", "calls": int(row["Calls"]),
+                        "avg_us": float(row["AverageNs"]) / 1e3, "min_us": float(row["MinNs"]) / 1e3,
+                        "max_us": float(row["MaxNs"]) / 1e3, "source": os.path.basename(path)}
+    raise SystemExit(f"no collate kernel in {path}")
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--only", choices=["step", "big", "collate"], default=None)
+    ap.add_argument("--copies", type=int, default=5320)          # 5320 x 188 = 1,000,160 graphs
+    ap.add_argument("--steps", type=int, default=60)
+    ap.add_argument("--big-steps", type=int, default=8)
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--trials", type=int, default=5)
+    ap.add_argument("--stats", default=None)
+    args = ap.parse_args()
+    if args.stats is not None:
+        if not os.path.isfile(args.stats):
+            raise SystemExit(f"--stats: no such file {args.stats!r}")
+        print(json.dumps(stats_line(args.stats)), flush=True)
+        return
+    dev = torch.device("cuda")
+    graphs = mutag_graphs()
+    if args.only in (None, "step"):
+        for bs in (256, 64):
+            t = step_times(graphs, bs, dev, args.steps, ("cached", "host", "device"))
+            print(json.dumps({"workload": "mutag_train_stack", "graphs": len(graphs), "batch_size": bs,
+                              "step_ms_cached_batch": t["cached"], "step_ms_host_loader": t["host"],
+                              "step_ms_device_loader": t["device"], "host_over_device": t["host"] / t["device"]}), flush=True)
+    if args.only in (None, "collate"):
+        gs = ops.GraphSet(graphs, dev)
+        for bs in (64, 188):
+            print(json.dumps({"workload": "collate_mutag", **collate_times(gs, bs, args.reps, args.trials)}), flush=True)
+    if args.only in (None, "big", "collate"):
+        big = graphs * args.copies
+        t0 = time.perf_counter()
+        gs = ops.GraphSet(big, dev)
+        torch.cuda.synchronize()
+        upload_s = time.perf_counter() - t0
+        print(json.dumps({"workload": "collate_mutag_replica", "dataset_graphs": len(big), "upload_s": upload_s,
+                          **collate_times(gs, 4096, args.reps, args.trials)}), flush=True)
+        if args.only != "collate":
+            t = {}
+            for name, steps in (("host", args.big_steps), ("device", args.steps)):
+                t.update(step_times(big if name == "host" else gs, 4096, dev, steps, (name,)))
+            print(json.dumps({"workload": "mutag_replica_train_stack", "graphs": len(big), "batch_size": 4096,
+                              "step_ms_host_loader": t["host"], "step_ms_device_loader": t["device"],
+                              "host_steps": args.big_steps, "device_steps": args.steps,
+                              "host_over_device": t["host"] / t["device"]}), flush=True)
+
+
+if __name__ == "__main__":
+    main()
