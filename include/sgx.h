@@ -302,7 +302,8 @@ int sgx_transpose(int dtype, int rows, int cols, const void *in, int64_t ldi,
                   void *out, int64_t ldo, void *stream);
 
 /* GAT aggregation on an already computed Wh (SG.py:309-314, :634-661), single head:
- *   e_ij = LeakyReLU_alpha(Wh_i.a1 + Wh_j.a2) for stored edges with values[e] > 0,
+ *   e_ij = LeakyReLU_alpha(Wh_i.a1 + Wh_j.a2) for stored edges with values[e] > 0 (the stored value as stored: +0.0 and
+ *   -0.0 are masked, positive fp16 and fp32 subnormals are live; every form and the backward edge pass test it so),
  *   alpha_ij = softmax_j(e_ij),  D_i = act(sum_j alpha_ij Wh_j).
  * Wh has n_cols rows; row r of the adjacency is node r of Wh (n_rows <= n_cols: the reference's
  * square case is n_rows == n_cols, a rank of the partitioned graph passes its own rows first and
