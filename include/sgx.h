@@ -375,6 +375,65 @@ int sgx_gat_backward_edges(int dtype_values, int n_rows, int n_cols, int n_feat,
                            const float *E, const float *S, const float *G, int64_t ldg, const float *Wh, int64_t ldw,
                            const uint8_t *dead, const float *dead_row_sum, float *sg, float *g1, void *stream);
 
+/* ---- the GAT aggregate and its backward from row softmax statistics instead of E and S -----------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * E and S (2 nnz n_heads floats) are redundant: four small arrays hold what forms them again,
+ *     E_e = LeakyReLU_alpha(fp32(score_row[i] + score_col[c]))          stored entry e = (i, c), per head
+ *     live iff values[e] > 0, the stored value as stored (see sgx_gat_aggregate)
+ *     S_e = exp(E_e - row_max[i]) / row_sum[i]   on a live entry,   0 on a masked one
+ * A row without a live entry (a dead row) has row_max = 0 and row_sum = 0; S_e on each of its stored entries is the
+ * constant of the dead-row rule in force: 1/n_cols (fill_dead_rows), 1/n_nodes (sgx_gat_aggregate_fill) or 0, which the
+ * calls that read the statistics take as `dead_weight`.  Every call below forms E_e and S_e by exactly this expression
+ * (fp32 add, expf, one division), so they agree bit for bit among themselves.  All four arrays are required together. */
+typedef struct sgx_gat_stats {      /* all fp32, device */
+    float *score_row;   /* [n_rows][n_heads]  Wh_i . a1 of the head               */
+    float *score_col;   /* [n_cols][n_heads]  Wh_c . a2 of the head               */
+    float *row_max;     /* [n_rows][n_heads]  m_i: max of the row's LIVE scores   */
+    float *row_sum;     /* [n_rows][n_heads]  l_i: sum over live e of exp(E_e-m_i) */
+} sgx_gat_stats;
+
+/* sgx_gat_aggregate / sgx_gat_aggregate_fill without the E / S outputs, delivering the statistics.  D is formed by the
+ * very launches of those calls with E = S = NULL -- the one walk (gat_fused.hip) wherever they take it, the two stages or
+ * the one-pass kernels elsewhere -- so D is bit-equal to theirs on the same arguments.  The statistics come from the
+ * scores of the aggregate's pre-pass (s_scratch) and one more pass over the stored entries that moves no row of Wh (4-byte
+ * score gathers; rows over 256 entries by a whole workgroup): the (max, sum) of each row's live scores, the sum in the
+ * order of that pass.  The one walk forms a neighbour's score from the row it gathers, so the weights it used may differ
+ * from the S_e of the statistics in the last bits -- inside the error bound of either.
+ * Dead-row rule: fill != NULL -- the partitioned rule of sgx_gat_aggregate_fill (n_nodes >= 1); fill == NULL and
+ * n_nodes == 0 -- dead rows give 0 (fill_dead_rows = 0); fill == NULL and n_nodes == n_cols > 0 -- the mean of the rows
+ * of Wh (fill_dead_rows = 1); fill == NULL with any other n_nodes: SGX_ERR_SHAPE.  Scratch: sgx_gat_scratch_bytes with the
+ * fill_dead_rows of the rule (0 with a fill row).  stats or one of its members NULL: SGX_ERR_NULL, n_cols * n_heads * 4
+ * bytes of scores beyond 32-bit offsets: SGX_ERR_UNSUPPORTED; both before anything is launched. */
+int sgx_gat_aggregate_stats(int dtype, int relu, int n_rows, int n_cols, int n_feat, int n_heads, float alpha,
+                            const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                            const void *Wh, int64_t ldh, const void *attention, void *D, int64_t ldd,
+                            const float *fill, int64_t n_nodes, const sgx_plan *plan, float *s_scratch,
+                            const sgx_gat_stats *stats, void *stream);
+
+/* sgx_layer_forward for gat_mode = 1 with desc->E == desc->S == NULL, delivering the statistics of its aggregate (of the
+ * quantised operands when desc->quant is set: whatever the forward used).  D is bit-equal to sgx_layer_forward's on the
+ * same descriptor; the workspace is the same (sgx_layer_workspace_bytes).  gat_mode = 0, or E / S set:
+ * SGX_ERR_UNSUPPORTED; stats or a member NULL: SGX_ERR_NULL. */
+int sgx_layer_forward_stats(const sgx_layer_desc *desc, const sgx_gat_stats *stats, void *stream);
+
+/* E and / or S [nnz][n_heads] fp32 formed from the statistics (either may be NULL): the side outputs after a forward
+ * that did not write them.  dtype_values: the element type of `values`. */
+int sgx_gat_edge_outputs(int dtype_values, int n_rows, int n_cols, int n_heads, float alpha,
+                         const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                         const sgx_gat_stats *stats, float dead_weight, float *E, float *S, void *stream);
+
+/* sgx_gat_backward_edges with the statistics in place of E and S: the dots kernel forms S_e from score_row[row],
+ * score_col[col] (a 4-byte range-checked gather), row_max and row_sum instead of loading it, the row kernels take the
+ * LeakyReLU slope from the E_e they form again.  S_out (optional, [nnz]) receives S_e: the attention matrix the caller
+ * multiplies with next.  One head: the statistics are [n_rows] / [n_cols] arrays (n_heads = 1; more: SGX_ERR_UNSUPPORTED).
+ * dead / dead_row_sum as in sgx_gat_backward_edges; dead_weight: S_e of the stored entries of a row whose row_sum is 0. */
+int sgx_gat_backward_edges_stats(int dtype_values, int n_rows, int n_cols, int n_feat, int n_heads, float alpha,
+                                 const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                                 const sgx_gat_stats *stats, float dead_weight, const float *G, int64_t ldg,
+                                 const float *Wh, int64_t ldw, const uint8_t *dead, const float *dead_row_sum,
+                                 float *sg, float *g1, float *S_out, void *stream);
+
 /* Readout + classifier head of the graph-classification model (MOL cell 18 tail) in one launch:
  * pooled[g][:] = mean of X rows [graph_ptr[g], graph_ptr[g+1])  (global_mean_pool over a sorted
  * `batch` vector), logits[g][c] = bias[c] + W[c][:] . pooled[g][:]  (torch Linear, W [C][F] fp32).

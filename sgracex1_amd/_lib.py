@@ -41,6 +41,7 @@ SYMBOLS = [
     "sgx_batch_plan_max_graph", "sgx_batch_plan_fits", "sgx_stack_workspace_bytes", "sgx_stack_forward",
     "sgx_batch_plan_create_ex", "sgx_stack_backward_workspace_bytes", "sgx_stack_backward",
     "sgx_collate_graphs", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
+    "sgx_gat_aggregate_stats", "sgx_layer_forward_stats", "sgx_gat_edge_outputs", "sgx_gat_backward_edges_stats",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -86,6 +87,12 @@ class LayerDesc(ctypes.Structure):
         ("quant", ctypes.POINTER(Quant)),
         ("order", ctypes.c_int32),
     ]
+
+
+class GatStats(ctypes.Structure):
+    """struct sgx_gat_stats -- field order and types must match include/sgx.h."""
+    _fields_ = [("score_row", ctypes.c_void_p), ("score_col", ctypes.c_void_p), ("row_max", ctypes.c_void_p),
+                ("row_sum", ctypes.c_void_p)]
 
 
 class StackLayer(ctypes.Structure):
@@ -237,6 +244,17 @@ def _load():
     lib.sgx_gat_backward_edges.argtypes = [c_int, c_int, c_int, c_int, ctypes.c_float, vp, vp, vp, vp, vp, vp, c_i64, vp,
                                            c_i64, vp, vp, vp, vp, vp]
     lib.sgx_gat_backward_edges.restype = c_int
+    stp = ctypes.POINTER(GatStats)
+    lib.sgx_gat_aggregate_stats.argtypes = [c_int, c_int, c_int, c_int, c_int, c_int, ctypes.c_float, vp, vp, vp, vp, c_i64, vp,
+                                            vp, c_i64, vp, c_i64, vp, vp, stp, vp]
+    lib.sgx_gat_aggregate_stats.restype = c_int
+    lib.sgx_layer_forward_stats.argtypes = [ctypes.POINTER(LayerDesc), stp, vp]
+    lib.sgx_layer_forward_stats.restype = c_int
+    lib.sgx_gat_edge_outputs.argtypes = [c_int, c_int, c_int, c_int, ctypes.c_float, vp, vp, vp, stp, ctypes.c_float, vp, vp, vp]
+    lib.sgx_gat_edge_outputs.restype = c_int
+    lib.sgx_gat_backward_edges_stats.argtypes = [c_int, c_int, c_int, c_int, c_int, ctypes.c_float, vp, vp, vp, stp,
+                                                 ctypes.c_float, vp, c_i64, vp, c_i64, vp, vp, vp, vp, vp, vp]
+    lib.sgx_gat_backward_edges_stats.restype = c_int
     lib.sgx_readout_mean_linear.argtypes = [c_int, c_int, c_int, c_int, vp, c_i64, vp, vp, vp, vp, vp, vp]
     lib.sgx_readout_mean_linear.restype = c_int
     lib.sgx_readout_mean_backward.argtypes = [c_int, c_int, c_int, vp, vp, vp, c_i64, vp]

@@ -21,6 +21,10 @@ _FLAGS = {
     "accb": (0, "backward offload register path of the GAT bitstream (gemm_mode 2): not offered; "
                 "backward always runs on the device kernels"),
     "compute_attention": (0, "0 = GCN aggregate A.H, 1 = single-head GAT edge softmax (register gat_mode)"),
+    "gat_edge_outputs": (1, "GAT training on the kernels: 1 = the forward writes the per-edge outputs E and S and keeps them "
+                            "for the backward (the bitstream's E / S ports); 0 = it keeps the row softmax statistics "
+                            "(sgx_gat_stats: 3 n_rows + n_cols floats in place of 2 nnz) and the backward forms E and S "
+                            "again from them; no flag of this name in the reference"),
     "float_type": (_np.float32, "element type of the layer buffers; np.float16 selects the HALF build's type"),
     "layer_order": ("reference", "'reference': every layer forms X.W first, as the FPGA dataflow does; 'auto': a layer with "
                                  "dense features narrower than its output aggregates first, act((A.X).W) -- same sums, "

@@ -20,7 +20,15 @@
 //          the host never reads it.
 //   rows   8 lanes per row: the row sum of dx, then sg_e and g1; rows over 256 entries are left to a third launch in
 //          which a workgroup of 1024 takes each of them (a hub row of 20 K entries by one wavefront was 0.4 ms).
-#include "sgx_device.h"
+//
+// From statistics (sgx_gat_backward_edges_stats, STATS = true below): E and S are not read.  The dots kernel forms S_e of
+// its entry from the row's and the column's score halves (the latter a 4-byte range-checked gather from a table of n_cols
+// floats, L2-sized), the row's maximum and sum; the row kernels form E_e and S_e again for the slope and the row-sum
+// term, and write S_e out when the caller wants the attention matrix.  The STATS = false kernels do what they did before
+// (the added arguments are not read).
+#include "gat_device.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -28,12 +36,31 @@ constexpr int kDotBlock = 256;           // stored entries per workgroup pass of
 constexpr int kRowLanes = 8;             // lanes per row in the rows kernel
 constexpr int kRowLong = 256;            // rows over this many entries: the whole wavefront
 
+// what the STATS kernels read in place of E and S (one head): the statistics, the mask's values and the dead rows' weight
+struct StatsIn {
+    const float *score_row, *score_col, *row_max, *row_sum;
+    const void *val;
+    unsigned sc_bytes;
+    float alpha, dead_weight;
+    float *S_out;
+};
+
+// E_e and S_e of stored entry idx = (r, c) from the statistics
+template <typename TV>
+__device__ __forceinline__ void stats_entry(const StatsIn &st, __amdgpu_buffer_rsrc_t sc_rsrc, int64_t idx, int64_t r, int c,
+                                            float &x, float &w)
+{
+    x = leaky(st.score_row[r] + buffer_f32(sc_rsrc, (unsigned)c * 4u), st.alpha);
+    const bool live = Elem<TV>::to_f32(static_cast<const TV *>(st.val)[idx]) > 0.0f;
+    w = stats_weight(x, live, st.row_max[r], st.row_sum[r], st.dead_weight);
+}
+
 // dx_e = S_e (G[row e] . Wh[col e]) for every stored entry, into sg
-template <int LPR>
+template <int LPR, bool STATS = false, typename TV = float>
 __global__ __launch_bounds__(kDotBlock) void gat_bwd_dots_kernel(
     int n_rows, int n_feat, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const float *__restrict__ S, const float *__restrict__ G, unsigned g_bytes, unsigned ldg_bytes,
-    const float *__restrict__ Wh, unsigned w_bytes, unsigned ldw_bytes, float *__restrict__ sg, int g_vec)
+    const float *__restrict__ Wh, unsigned w_bytes, unsigned ldw_bytes, float *__restrict__ sg, int g_vec, StatsIn st)
 {
     constexpr int GROUPS = 64 / LPR;         // entries a wavefront works on at a time
     constexpr int TILE = LPR * 4;            // columns one pass of a lane group covers
@@ -53,7 +80,17 @@ __global__ __launch_bounds__(kDotBlock) void gat_bwd_dots_kernel(
         }
         const unsigned g_off = have ? (unsigned)lo * ldg_bytes : kOOB;
         const unsigned w_off = have ? (unsigned)col[have ? e : 0] * ldw_bytes : kOOB;
-        const float s_e = have ? S[have ? e : 0] : 0.0f;
+        float s_e = 0.0f;
+        if constexpr (STATS) {
+            if (have) {
+                const __amdgpu_buffer_rsrc_t sc_rsrc =
+                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(st.score_col), 0, st.sc_bytes, 0x00020000);
+                float x;
+                stats_entry<TV>(st, sc_rsrc, e, lo, col[e], x, s_e);
+            }
+        } else {
+            s_e = have ? S[have ? e : 0] : 0.0f;
+        }
         const int64_t wave_base = e - lane;
 #pragma unroll 2
         for (int j = 0; j < LPR; ++j) {
@@ -90,11 +127,11 @@ __global__ __launch_bounds__(kDotBlock) void gat_bwd_dots_kernel(
 }
 
 // softmax backward, mask, LeakyReLU backward on the parked dx; g1 = row sums of the result
-template <typename TV>
+template <typename TV, bool STATS = false>
 __global__ __launch_bounds__(kBlock) void gat_bwd_rows_kernel(
     int n_rows, const int32_t *__restrict__ rowptr, const TV *__restrict__ val, const float *__restrict__ E,
     const float *__restrict__ S, float alpha, const uint8_t *__restrict__ dead, const float *__restrict__ dead_row_sum,
-    float *__restrict__ sg, float *__restrict__ g1)
+    float *__restrict__ sg, float *__restrict__ g1, const int32_t *__restrict__ col, StatsIn st)
 {
     constexpr int RPW = 64 / kRowLanes;
     const int lane = threadIdx.x & 63, sub = lane % kRowLanes, grp = lane / kRowLanes;
@@ -104,9 +141,19 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_rows_kernel(
     if (live) { e0 = rowptr[r]; e1 = rowptr[r + 1]; }
     const bool is_long = e1 - e0 > kRowLong;
     auto finish = [&](int idx, float rs) -> float {
-        float v = sg[idx] - S[idx] * rs;
+        float e_x, s_w;
+        if constexpr (STATS) {
+            const __amdgpu_buffer_rsrc_t sc_rsrc =
+                __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(st.score_col), 0, st.sc_bytes, 0x00020000);
+            stats_entry<TV>(st, sc_rsrc, idx, r, col[idx], e_x, s_w);
+            if (st.S_out) st.S_out[idx] = s_w;
+        } else {
+            e_x = E[idx];
+            s_w = S[idx];
+        }
+        float v = sg[idx] - s_w * rs;
         if (!(Elem<TV>::to_f32(val[idx]) > 0.0f)) v = 0.0f;
-        if (!(E[idx] > 0.0f)) v *= alpha;
+        if (!(e_x > 0.0f)) v *= alpha;
         sg[idx] = v;
         return v;
     };
@@ -127,11 +174,11 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_rows_kernel(
 // rows over kRowLong entries: a workgroup of 1024 looks at 64 consecutive rows and takes the long ones among them one
 // after the other with all its threads (most workgroups find none and leave after reading 65 row pointers)
 constexpr int kLongThreads = 1024;
-template <typename TV>
+template <typename TV, bool STATS = false>
 __global__ __launch_bounds__(kLongThreads) void gat_bwd_long_rows_kernel(
     int n_rows, const int32_t *__restrict__ rowptr, const TV *__restrict__ val, const float *__restrict__ E,
     const float *__restrict__ S, float alpha, const uint8_t *__restrict__ dead, const float *__restrict__ dead_row_sum,
-    float *__restrict__ sg, float *__restrict__ g1)
+    float *__restrict__ sg, float *__restrict__ g1, const int32_t *__restrict__ col, StatsIn st)
 {
     __shared__ float part[kLongThreads / 64];
     __shared__ float total;
@@ -171,9 +218,19 @@ __global__ __launch_bounds__(kLongThreads) void gat_bwd_long_rows_kernel(
         if (dead != nullptr && dead[r]) rs = dead_row_sum[r];
         float acc = 0.0f;
         for (int idx = e0 + (int)threadIdx.x; idx < e1; idx += kLongThreads) {
-            float v = sg[idx] - S[idx] * rs;
+            float e_x, s_w;
+            if constexpr (STATS) {
+                const __amdgpu_buffer_rsrc_t sc_rsrc =
+                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(st.score_col), 0, st.sc_bytes, 0x00020000);
+                stats_entry<TV>(st, sc_rsrc, idx, r, col[idx], e_x, s_w);
+                if (st.S_out) st.S_out[idx] = s_w;
+            } else {
+                e_x = E[idx];
+                s_w = S[idx];
+            }
+            float v = sg[idx] - s_w * rs;
             if (!(Elem<TV>::to_f32(val[idx]) > 0.0f)) v = 0.0f;
-            if (!(E[idx] > 0.0f)) v *= alpha;
+            if (!(e_x > 0.0f)) v *= alpha;
             sg[idx] = v;
             acc += v;
         }
@@ -191,14 +248,75 @@ struct BwdArgs {
     hipStream_t stream;
     unsigned grid;
     int g_vec;
+    StatsIn st;
 };
 
-template <int LPR>
+template <int LPR, bool STATS, typename TV>
 int dots_launch(const BwdArgs &a)
 {
-    hipLaunchKernelGGL((gat_bwd_dots_kernel<LPR>), dim3(a.grid), dim3(kDotBlock), 0, a.stream, a.n_rows, a.n_feat, a.rowptr, a.col,
-                       a.S, a.G, a.g_bytes, a.ldg_bytes, a.Wh, a.w_bytes, a.ldw_bytes, a.sg, a.g_vec);
+    using DT = std::conditional_t<STATS, TV, float>;          // (only the STATS form reads the values)
+    hipLaunchKernelGGL((gat_bwd_dots_kernel<LPR, STATS, DT>), dim3(a.grid), dim3(kDotBlock), 0, a.stream, a.n_rows, a.n_feat, a.rowptr,
+                       a.col, a.S, a.G, a.g_bytes, a.ldg_bytes, a.Wh, a.w_bytes, a.ldw_bytes, a.sg, a.g_vec, a.st);
     SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}
+
+template <bool STATS, typename TV>
+int dots_launch_lpr(const BwdArgs &a, int lpr)
+{
+    switch (lpr) {
+    case 1: return dots_launch<1, STATS, TV>(a);
+    case 2: return dots_launch<2, STATS, TV>(a);
+    case 4: return dots_launch<4, STATS, TV>(a);
+    case 8: return dots_launch<8, STATS, TV>(a);
+    case 16: return dots_launch<16, STATS, TV>(a);
+    case 32: return dots_launch<32, STATS, TV>(a);
+    default: return dots_launch<64, STATS, TV>(a);
+    }
+}
+
+// the three launches; STATS: E / S are NULL and `st` holds the statistics
+template <bool STATS, typename TV>
+int edge_pass(BwdArgs &a, const TV *values, const float *E, float alpha, const uint8_t *dead, const float *dead_row_sum, float *g1)
+{
+    // lanes per entry: a quarter of the row's 16-byte chunks (four gathers per lane and table), at least 1, at most 64
+    int lpr = sgx_next_pow2((a.n_feat + 15) / 16);
+    if (lpr > 64) lpr = 64;
+    const int rc = dots_launch_lpr<STATS, TV>(a, lpr);
+    if (rc != SGX_OK) return rc;
+    const int rows_per_block = (64 / kRowLanes) * (kBlock / 64);
+    const unsigned grid = (unsigned)((a.n_rows + rows_per_block - 1) / rows_per_block);
+    hipLaunchKernelGGL((gat_bwd_rows_kernel<TV, STATS>), dim3(grid), dim3(kBlock), 0, a.stream, a.n_rows, a.rowptr, values, E, a.S, alpha,
+                       dead, dead_row_sum, a.sg, g1, a.col, a.st);
+    SGX_LAUNCH_CHECK();
+    const unsigned grid_long = (unsigned)((a.n_rows + 63) / 64);
+    hipLaunchKernelGGL((gat_bwd_long_rows_kernel<TV, STATS>), dim3(grid_long), dim3(kLongThreads), 0, a.stream, a.n_rows, a.rowptr, values,
+                       E, a.S, alpha, dead, dead_row_sum, a.sg, g1, a.col, a.st);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}
+
+// argument checks both entry points share, and the launch geometry
+int prepare(BwdArgs &a, int dtype_values, int n_rows, int n_cols, int n_feat, const int32_t *rowPtr, const int32_t *columnIndex,
+            const float *G, int64_t ldg, const float *Wh, int64_t ldw, float *sg, hipStream_t s)
+{
+    if (dtype_values != SGX_F16 && dtype_values != SGX_F32) return SGX_ERR_UNSUPPORTED;
+    if ((uintptr_t)Wh % 16 != 0 || (ldw * 4) % 16 != 0) return SGX_ERR_ALIGN;          // 16-byte gathers of fp32 rows
+    const unsigned long long w_bytes = (unsigned long long)n_cols * (unsigned long long)ldw * 4ull;
+    const unsigned long long g_bytes = (unsigned long long)n_rows * (unsigned long long)ldg * 4ull;
+    if (w_bytes >= 0xFFFFFFF0ull || g_bytes >= 0xFFFFFFF0ull) return SGX_ERR_UNSUPPORTED;
+    a.n_rows = n_rows; a.n_feat = n_feat; a.rowptr = rowPtr; a.col = columnIndex;
+    a.S = nullptr; a.G = G; a.Wh = Wh;
+    a.g_bytes = (unsigned)g_bytes; a.ldg_bytes = (unsigned)(ldg * 4);
+    a.w_bytes = (unsigned)w_bytes; a.ldw_bytes = (unsigned)(ldw * 4);
+    a.sg = sg; a.stream = s;
+    a.g_vec = ((uintptr_t)G % 16 == 0 && (ldg * 4) % 16 == 0) ? 1 : 0;     // 16-byte loads of G's rows too, where they are aligned
+    a.st = StatsIn{};
+    // persistent over the stored entries (their count is read on the device): 8 workgroups per CU
+    int cus = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+        cus = 256;
+    a.grid = (unsigned)cus * 8u;
     return SGX_OK;
 }
 
@@ -214,50 +332,33 @@ extern "C" int sgx_gat_backward_edges(int dtype_values, int n_rows, int n_cols, 
     if (n_rows == 0) return SGX_OK;
     if (!rowPtr || !columnIndex || !values || !E || !S || !G || !Wh || !sg || !g1) return SGX_ERR_NULL;
     if ((dead == nullptr) != (dead_row_sum == nullptr)) return SGX_ERR_NULL;
-    if (dtype_values != SGX_F16 && dtype_values != SGX_F32) return SGX_ERR_UNSUPPORTED;
-    if ((uintptr_t)Wh % 16 != 0 || (ldw * 4) % 16 != 0) return SGX_ERR_ALIGN;          // 16-byte gathers of fp32 rows
-    const unsigned long long w_bytes = (unsigned long long)n_cols * (unsigned long long)ldw * 4ull;
-    const unsigned long long g_bytes = (unsigned long long)n_rows * (unsigned long long)ldg * 4ull;
-    if (w_bytes >= 0xFFFFFFF0ull || g_bytes >= 0xFFFFFFF0ull) return SGX_ERR_UNSUPPORTED;
-    hipStream_t s = (hipStream_t)stream;
     BwdArgs a;
-    a.n_rows = n_rows; a.n_feat = n_feat; a.rowptr = rowPtr; a.col = columnIndex;
-    a.S = S; a.G = G; a.Wh = Wh;
-    a.g_bytes = (unsigned)g_bytes; a.ldg_bytes = (unsigned)(ldg * 4);
-    a.w_bytes = (unsigned)w_bytes; a.ldw_bytes = (unsigned)(ldw * 4);
-    a.sg = sg; a.stream = s;
-    a.g_vec = ((uintptr_t)G % 16 == 0 && (ldg * 4) % 16 == 0) ? 1 : 0;     // 16-byte loads of G's rows too, where they are aligned
-    // persistent over the stored entries (their count is read on the device): 8 workgroups per CU
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    a.grid = (unsigned)cus * 8u;
-    // lanes per entry: a quarter of the row's 16-byte chunks (four gathers per lane and table), at least 1, at most 64
-    int lpr = sgx_next_pow2((n_feat + 15) / 16);
-    if (lpr > 64) lpr = 64;
-    int rc;
-    switch (lpr) {
-    case 1: rc = dots_launch<1>(a); break;
-    case 2: rc = dots_launch<2>(a); break;
-    case 4: rc = dots_launch<4>(a); break;
-    case 8: rc = dots_launch<8>(a); break;
-    case 16: rc = dots_launch<16>(a); break;
-    case 32: rc = dots_launch<32>(a); break;
-    default: rc = dots_launch<64>(a); break;
-    }
+    const int rc = prepare(a, dtype_values, n_rows, n_cols, n_feat, rowPtr, columnIndex, G, ldg, Wh, ldw, sg, (hipStream_t)stream);
     if (rc != SGX_OK) return rc;
-    const int rows_per_block = (64 / kRowLanes) * (kBlock / 64);
-    const unsigned grid = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
-    if (dtype_values == SGX_F16)
-        hipLaunchKernelGGL(gat_bwd_rows_kernel<f16>, dim3(grid), dim3(kBlock), 0, s, n_rows, rowPtr, (const f16 *)values, E, S, alpha, dead, dead_row_sum, sg, g1);
-    else
-        hipLaunchKernelGGL(gat_bwd_rows_kernel<float>, dim3(grid), dim3(kBlock), 0, s, n_rows, rowPtr, (const float *)values, E, S, alpha, dead, dead_row_sum, sg, g1);
-    SGX_LAUNCH_CHECK();
-    const unsigned grid_long = (unsigned)((n_rows + 63) / 64);
-    if (dtype_values == SGX_F16)
-        hipLaunchKernelGGL(gat_bwd_long_rows_kernel<f16>, dim3(grid_long), dim3(kLongThreads), 0, s, n_rows, rowPtr, (const f16 *)values, E, S, alpha, dead, dead_row_sum, sg, g1);
-    else
-        hipLaunchKernelGGL(gat_bwd_long_rows_kernel<float>, dim3(grid_long), dim3(kLongThreads), 0, s, n_rows, rowPtr, (const float *)values, E, S, alpha, dead, dead_row_sum, sg, g1);
-    SGX_LAUNCH_CHECK();
-    return SGX_OK;
+    a.S = S;
+    if (dtype_values == SGX_F16) return edge_pass<false, f16>(a, (const f16 *)values, E, alpha, dead, dead_row_sum, g1);
+    return edge_pass<false, float>(a, (const float *)values, E, alpha, dead, dead_row_sum, g1);
+}
+
+extern "C" int sgx_gat_backward_edges_stats(int dtype_values, int n_rows, int n_cols, int n_feat, int n_heads, float alpha,
+                                            const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                                            const sgx_gat_stats *stats, float dead_weight, const float *G, int64_t ldg,
+                                            const float *Wh, int64_t ldw, const uint8_t *dead, const float *dead_row_sum,
+                                            float *sg, float *g1, float *S_out, void *stream)
+{
+    if (n_rows < 0 || n_cols < 0 || n_feat < 1 || ldg < n_feat || ldw < n_feat) return SGX_ERR_SHAPE;
+    if (n_heads > 1) return SGX_ERR_UNSUPPORTED;                      // one head, as the edge pass above
+    if (n_rows == 0) return SGX_OK;
+    if (!rowPtr || !columnIndex || !values || !G || !Wh || !sg || !g1) return SGX_ERR_NULL;
+    if ((dead == nullptr) != (dead_row_sum == nullptr)) return SGX_ERR_NULL;
+    int rc = sgx_gat_stats_check(stats, n_cols, 1);
+    if (rc != SGX_OK) return rc;
+    BwdArgs a;
+    rc = prepare(a, dtype_values, n_rows, n_cols, n_feat, rowPtr, columnIndex, G, ldg, Wh, ldw, sg, (hipStream_t)stream);
+    if (rc != SGX_OK) return rc;
+    a.st.score_row = stats->score_row; a.st.score_col = stats->score_col; a.st.row_max = stats->row_max; a.st.row_sum = stats->row_sum;
+    a.st.val = values; a.st.sc_bytes = (unsigned)((size_t)n_cols * 4); a.st.alpha = alpha; a.st.dead_weight = dead_weight;
+    a.st.S_out = S_out;
+    if (dtype_values == SGX_F16) return edge_pass<true, f16>(a, (const f16 *)values, nullptr, alpha, dead, dead_row_sum, g1);
+    return edge_pass<true, float>(a, (const float *)values, nullptr, alpha, dead, dead_row_sum, g1);
 }

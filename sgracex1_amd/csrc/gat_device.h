@@ -45,6 +45,28 @@ __device__ __forceinline__ float rescale_factor(float m_old, float m_new)
     return m_old == -INFINITY ? 0.0f : expf(m_old - m_new);        // (-inf) - (-inf) never reaches expf
 }
 
+// one more score into an online-softmax state
+__device__ __forceinline__ void softmax_push(float &m, float &l, float x)
+{
+    if (x > m) { l = l * rescale_factor(m, x) + 1.0f; m = x; }
+    else l += expf(x - m);
+}
+
+// a 4-byte gather through a range-checked buffer descriptor (an offset past the table reads 0 and touches nothing)
+__device__ __forceinline__ float buffer_f32(__amdgpu_buffer_rsrc_t rsrc, unsigned off)
+{
+    return __builtin_bit_cast(float, (unsigned)__builtin_amdgcn_raw_buffer_load_b32(rsrc, off, 0, 0));
+}
+
+// S_e of a stored entry formed again from its row's statistics (sgx.h, sgx_gat_stats): x = E_e, (m, l) the row's; a row
+// with l = 0 has no live entry and every stored entry of it carries the dead-row rule's constant.  The one expression
+// every reader of the statistics uses, so that their weights agree bit for bit.
+__device__ __forceinline__ float stats_weight(float x, bool live, float m, float l, float dead_weight)
+{
+    if (!(l > 0.0f)) return dead_weight;
+    return live ? expf(x - m) / l : 0.0f;
+}
+
 // the scores of heads [hb0, hb0 + 8) of node c: two 16-byte loads when the row of 8 floats is aligned (n_heads a
 // multiple of 8 and an aligned table), else element loads; entries past n_heads are 0
 __device__ __forceinline__ void load_scores8(const float *__restrict__ s2, int64_t c, int n_heads, int hb0, bool vec, float *out)

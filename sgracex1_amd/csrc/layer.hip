@@ -134,9 +134,9 @@ extern "C" int sgx_xw_sparse(int dtype, int acc_mode, int spmm_block, int n_rows
 
 namespace {
 int thread_count(int32_t t) { return t < 1 ? 1 : t; }
-}
 
-extern "C" int sgx_layer_forward(const sgx_layer_desc *d, void *stream)
+// the layer; stats (sgx_layer_forward_stats only): where the GAT aggregate's row statistics go
+int layer_forward(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *stream)
 {
     int rc = check_desc(d);
     if (rc != SGX_OK) return rc;
@@ -271,6 +271,9 @@ extern "C" int sgx_layer_forward(const sgx_layer_desc *d, void *stream)
                                   d->rowPtr_adj, d->columnIndex_adj,
                                   values_adj, H, ldh, attention, d->D, d->P_w, (float *)d->E, (float *)d->S, d->plan_adj,
                                   (float *)(ws + c.g_off), s, ep_d.out_scale, nullptr, 0, scores_ready);
+        if (rc == SGX_OK && stats)      // from the scores the aggregate has just used (of the quantised operands, if any)
+            rc = sgx_gat_row_stats(d->dtype, d->N_adj, d->M_adj, d->gat_heads, d->alpha, d->rowPtr_adj, d->columnIndex_adj,
+                                   values_adj, (const float *)(ws + c.g_off), stats, s);
     } else {
         rc = sgx_spmm_launch(d->dtype, d->acc_mode, d->spmm_block, d->relu, d->N_adj, d->M_adj, d->P_w,
                              d->rowPtr_adj, d->columnIndex_adj, values_adj, H, ldh, d->D, d->P_w, d->plan_adj,
@@ -280,6 +283,19 @@ extern "C" int sgx_layer_forward(const sgx_layer_desc *d, void *stream)
 
     if (d->ev_agg_end) SGX_HIP_CHECK(hipEventRecord((hipEvent_t)d->ev_agg_end, s));
     return SGX_OK;
+}
+}  // namespace
+
+extern "C" int sgx_layer_forward(const sgx_layer_desc *d, void *stream) { return layer_forward(d, nullptr, stream); }
+
+extern "C" int sgx_layer_forward_stats(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *stream)
+{
+    int rc = check_desc(d);
+    if (rc != SGX_OK) return rc;
+    if (!d->gat_mode || d->E || d->S) return SGX_ERR_UNSUPPORTED;
+    rc = sgx_gat_stats_check(stats, d->M_adj, d->gat_heads);
+    if (rc != SGX_OK) return rc;
+    return layer_forward(d, stats, stream);
 }
 
 extern "C" int sgx_event_create(void **event)

@@ -156,6 +156,12 @@ int sgx_gat_aggregate_ep(int dtype, int relu, int fill_dead_rows, int n_rows, in
                          const void *attention, void *D, int64_t ldd, float *E, float *S, const sgx_plan *plan,
                          float *s_scratch, hipStream_t stream, float out_scale, const float *ext_fill = nullptr, int ext_n = 0,
                          int scores_ready = 0);
+// gat_stats.hip: the row softmax statistics (sgx_gat_stats) of an aggregate that has just run on s_scratch, from the scores
+// its pre-pass left there; sgx_gat_stats_check: SGX_ERR_NULL for a missing array, SGX_ERR_UNSUPPORTED past 32-bit offsets
+int sgx_gat_stats_check(const sgx_gat_stats *st, int n_cols, int n_heads);
+int sgx_gat_row_stats(int dtype, int n_rows, int n_cols, int n_heads, float alpha, const int32_t *rowPtr,
+                      const int32_t *columnIndex, const void *values, const float *s_scratch, const sgx_gat_stats *st,
+                      hipStream_t stream);
 // gat_scan.hip: the softmax weights of the stored entries of every row of up to kScanMaxRow entries (stage A of the
 // two-stage aggregate) as a segmented scan in entry order; longer rows are the plan's tasks
 constexpr int kScanGranule = 64, kScanMaxRow = 256;

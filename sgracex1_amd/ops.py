@@ -100,6 +100,40 @@ def _workspace(device, nbytes):
     return ws
 
 
+class GatStats:
+    """The row softmax statistics of a GAT aggregate (struct sgx_gat_stats, include/sgx.h), fp32 on the device:
+    score_row [n_rows, heads] = Wh_i . a1, score_col [n_cols, heads] = Wh_c . a2, row_max / row_sum [n_rows, heads] = the
+    maximum m_i of a row's live scores and the sum of exp(E_e - m_i) over them (both 0 for a row without a live entry).
+    They stand for the per-edge outputs: E_e = LeakyReLU(score_row[i] + score_col[c]), S_e = exp(E_e - m_i) / l_i on a
+    live entry, 0 on a masked one (gat_edge_outputs forms them) -- 3 n_rows + n_cols floats per head in place of 2 nnz."""
+
+    def __init__(self, n_rows, n_cols, heads, device):
+        self.heads = int(heads)
+        shape = (lambda n: (n,)) if self.heads == 1 else (lambda n: (n, self.heads))
+        self.score_row = torch.empty(shape(n_rows), dtype=torch.float32, device=device)
+        self.score_col = torch.empty(shape(n_cols), dtype=torch.float32, device=device)
+        self.row_max = torch.empty(shape(n_rows), dtype=torch.float32, device=device)
+        self.row_sum = torch.empty(shape(n_rows), dtype=torch.float32, device=device)
+
+    def tensors(self):
+        return self.score_row, self.score_col, self.row_max, self.row_sum
+
+    @classmethod
+    def of(cls, score_row, score_col, row_max, row_sum):
+        """The statistics over four tensors that exist already (an autograd function's saved tensors)."""
+        st = cls.__new__(cls)
+        st.heads = 1 if score_row.dim() == 1 else int(score_row.shape[1])
+        st.score_row, st.score_col, st.row_max, st.row_sum = score_row, score_col, row_max, row_sum
+        return st
+
+    def struct(self):
+        for name, t in zip(("score_row", "score_col", "row_max", "row_sum"), self.tensors()):
+            _dev(t, name)
+            if t.dtype != torch.float32:
+                raise TypeError("the GAT statistics are float32 tensors")
+        return _lib.GatStats(*(t.data_ptr() for t in self.tensors()))
+
+
 class Plan:
     """Row schedule of one CSR matrix (sgx_plan): which rows are split across wavefronts."""
 
@@ -414,12 +448,14 @@ def transpose(x, ldo=None):
 def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_edge_outputs=False, quant_int8=False,
                   acc_mode=SGX_ACC_F32, spmm_block=1, bias_count=0, out=None, use_plan=True, agg_events=None,
                   quant=None, adj_quantized=False, cache_quantized_adj=True, fea_threads=1, adj_threads=1,
-                  gat_heads=1, order="reference"):
+                  gat_heads=1, order="reference", want_row_stats=False):
     """One fused layer  D = act(A . (X . W))  through sgx_layer_forward.
 
     adj : Csr [N, M_adj];  fea : Csr [M_adj, M_fea] (gemm_mode 0) or dense tensor (gemm_mode 1);
     Wt  : [P, M_fea] -- the weights TRANSPOSED, what the reference writes into B_buffer.
     Returns D [N, P] (and (E, S) per-edge tensors when want_edge_outputs with GAT).
+    want_row_stats (GAT, instead of want_edge_outputs): returns (D, GatStats) through sgx_layer_forward_stats -- the row
+    softmax statistics that stand for E and S; D is the layer's D without side outputs, bit for bit.
     quant: a quant.QuantConstants -- run the layer with the quantised arithmetic of the SGRACE
     bitstream (fp32 tensors only); quant_int8: with dense features, X and W go to the int8 matrix cores as the integer
     codes of their grids (SGX_QUANT_INT8: exact int32 sums, X read as bytes), "auto" = where that is the faster form
@@ -476,6 +512,8 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
         raise ValueError("the layer writes D densely ([N_adj][P_w], K.cpp:802): `out` must not have padded rows")
     d.D = out.data_ptr()
     E = S = None
+    if want_row_stats and (want_edge_outputs or gat_attention is None):
+        raise ValueError("want_row_stats needs the GAT aggregate and excludes want_edge_outputs")
     if gat_attention is not None:
         att = _dev(gat_attention, "attention").reshape(-1)
         if att.numel() != 2 * P or att.dtype != Wt.dtype:
@@ -501,6 +539,11 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
     nbytes = lib.sgx_layer_workspace_bytes(ctypes.byref(d))
     ws = _workspace(Wt.device, nbytes)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    if want_row_stats:
+        stats = GatStats(adj.n_rows, adj.n_cols, gat_heads, Wt.device)
+        st = stats.struct()
+        check(lib.sgx_layer_forward_stats(ctypes.byref(d), ctypes.byref(st), _stream()), "sgx_layer_forward_stats")
+        return out, stats
     check(lib.sgx_layer_forward(ctypes.byref(d), _stream()), "sgx_layer_forward")
     return (out, E, S) if want_edge_outputs else out
 
@@ -553,13 +596,15 @@ def requantize_(H, scale_fea, internal_bits):
 
 
 def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=False, fill_dead_rows=None, out=None,
-                  heads=1, use_plan=True, fill_row=None, n_nodes=None):
+                  heads=1, use_plan=True, fill_row=None, n_nodes=None, want_row_stats=False):
     """Edge-softmax aggregate over an already computed Wh [adj.n_cols, F]; row r of adj is node r of Wh.
     heads > 1: F/heads columns per head, attention = heads vectors of 2*F/heads (E, S become [nnz, heads]).
     fill_dead_rows: None = decide from the adjacency (rows without a positive entry get the mean of
     all rows of Wh, as in the reference's dense emulation), False = such rows give 0.
     fill_row (fp32 [F]) with n_nodes: one rank of a partitioned graph -- dead rows receive this row (the mean over
-    ALL nodes, reduced across ranks by the caller) and S = 1/n_nodes (sgx_gat_aggregate_fill)."""
+    ALL nodes, reduced across ranks by the caller) and S = 1/n_nodes (sgx_gat_aggregate_fill).
+    want_row_stats (instead of want_edge_outputs): returns (out, GatStats) through sgx_gat_aggregate_stats; `out` is what
+    the call without side outputs gives on the same arguments, bit for bit."""
     _dev2d(Wh, "Wh")
     code = dtype_code(Wh.dtype)
     N, F = Wh.shape
@@ -578,6 +623,9 @@ def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=F
         E = torch.empty(es_shape, dtype=torch.float32, device=Wh.device)
         S = torch.empty(es_shape, dtype=torch.float32, device=Wh.device)
     plan = adj.gat_plan.handle if (use_plan and adj.wants_plan) else None
+    if want_row_stats:
+        return _gat_aggregate_stats(adj, Wh, att, alpha, relu, want_edge_outputs, fill_dead_rows, out, heads, plan, fill_row,
+                                    n_nodes)
     if fill_row is not None:
         _dev(fill_row, "fill_row")
         if fill_row.dtype != torch.float32 or fill_row.numel() != F or not n_nodes:
@@ -594,6 +642,30 @@ def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=F
                                 _ptr(adj.val), _ptr(Wh), Wh.stride(0), _ptr(att), _ptr(out), out.stride(0),
                                 _ptr(E), _ptr(S), plan, _ptr(s), _stream()), "sgx_gat_aggregate")
     return (out, E, S) if want_edge_outputs else out
+
+
+def _gat_aggregate_stats(adj, Wh, att, alpha, relu, want_edge_outputs, fill_dead_rows, out, heads, plan, fill_row, n_nodes):
+    """gat_aggregate(..., want_row_stats=True) on its checked arguments: sgx_gat_aggregate_stats, whose fill / n_nodes pair
+    selects the dead-row rule (a fill row; n_nodes = 0: zero; n_nodes = n_cols: the mean of Wh's rows)."""
+    if want_edge_outputs:
+        raise ValueError("want_row_stats and want_edge_outputs exclude each other")
+    N, F = Wh.shape
+    if fill_row is not None:
+        _dev(fill_row, "fill_row")
+        if fill_row.dtype != torch.float32 or fill_row.numel() != F or not n_nodes:
+            raise ValueError("fill_row must be float32 [F] and come with n_nodes")
+        fill, nn = 0, int(n_nodes)
+    else:
+        fill = int(adj.has_dead_rows if fill_dead_rows is None else bool(fill_dead_rows))
+        nn = N if fill else 0
+    s = torch.empty(lib.sgx_gat_scratch_bytes(N, F, heads, fill, plan) // 4, dtype=torch.float32, device=Wh.device)
+    stats = GatStats(adj.n_rows, N, heads, Wh.device)
+    st = stats.struct()
+    check(lib.sgx_gat_aggregate_stats(dtype_code(Wh.dtype), int(bool(relu)), adj.n_rows, N, F, heads, float(alpha),
+                                      _ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(Wh), Wh.stride(0), _ptr(att),
+                                      _ptr(out), out.stride(0), _ptr(fill_row), nn, plan, _ptr(s), ctypes.byref(st), _stream()),
+          "sgx_gat_aggregate_stats")
+    return out, stats
 
 
 def col_sums(X, n_feat=None):
@@ -686,6 +758,54 @@ def gat_backward_edges(adj, E, S, G, Wh, alpha=0.2, dead=None):
                                      _ptr(g1), _stream()),
           "sgx_gat_backward_edges")
     return sg, g1
+
+
+def gat_edge_outputs(adj, stats, alpha=0.2, dead_weight=0.0):
+    """(E, S) fp32 [nnz] (heads > 1: [nnz, heads]) formed from the statistics of a forward that did not write them
+    (sgx_gat_edge_outputs).  dead_weight: S on the stored entries of a row without a live entry -- the forward's dead-row
+    rule: 1 / n_cols (mean fill), 1 / n_nodes (fill_row) or 0."""
+    es_shape = (adj.nnz,) if stats.heads == 1 else (adj.nnz, stats.heads)
+    E = torch.empty(es_shape, dtype=torch.float32, device=adj.val.device)
+    S = torch.empty(es_shape, dtype=torch.float32, device=adj.val.device)
+    st = stats.struct()
+    check(lib.sgx_gat_edge_outputs(dtype_code(adj.val.dtype), adj.n_rows, adj.n_cols, stats.heads, float(alpha), _ptr(adj.rowptr),
+                                   _ptr(adj.col), _ptr(adj.val), ctypes.byref(st), float(dead_weight), _ptr(E), _ptr(S),
+                                   _stream()), "sgx_gat_edge_outputs")
+    return E, S
+
+
+def gat_backward_edges_stats(adj, stats, G, Wh, alpha=0.2, dead=None, dead_weight=0.0, want_S=True):
+    """gat_backward_edges from the statistics instead of E and S (sgx_gat_backward_edges_stats, one head): returns
+    (sg [nnz], g1 [n_rows], S [nnz] or None) -- S is the attention matrix's values, formed on the way for the caller's next
+    product, not something the forward had to keep.  dead as in gat_backward_edges; dead_weight as in gat_edge_outputs."""
+    _dev2d(G, "G")
+    _dev2d(Wh, "Wh")
+    if G.dtype != torch.float32 or Wh.dtype != torch.float32:
+        raise TypeError("gat_backward_edges_stats works on float32 G, Wh (the reference's backward is fp32)")
+    if Wh.shape[0] != adj.n_cols or G.shape != (adj.n_rows, Wh.shape[1]):
+        raise ValueError("G must be [adj.n_rows, F] and Wh [adj.n_cols, F]")
+    if stats.heads != 1:
+        raise ValueError("the backward edge pass is single-head")
+    dead_rs = None
+    if dead is not None:
+        _dev(dead, "dead")
+        if dead.dtype != torch.bool or dead.shape != (adj.n_rows,):
+            raise ValueError("dead must be a bool [adj.n_rows] tensor")
+        wh_mean = (col_sums(Wh) / adj.n_cols).unsqueeze(0)                   # [1, F]
+        dead_rs = xw_dense(G if G.stride(0) == G.shape[1] else G.contiguous(), wh_mean)[:, 0].contiguous()
+    if Wh.stride(0) % 4 or Wh.data_ptr() % 16:           # rows are gathered 16 bytes at a time: pad them
+        padded = torch.zeros((Wh.shape[0], (Wh.shape[1] + 3) // 4 * 4), dtype=torch.float32, device=Wh.device)
+        padded[:, :Wh.shape[1]] = Wh
+        Wh = padded[:, :Wh.shape[1]]
+    sg = torch.empty(adj.nnz, dtype=torch.float32, device=G.device)
+    g1 = torch.empty(adj.n_rows, dtype=torch.float32, device=G.device)
+    S = torch.empty(adj.nnz, dtype=torch.float32, device=G.device) if want_S else None
+    st = stats.struct()
+    check(lib.sgx_gat_backward_edges_stats(dtype_code(adj.val.dtype), adj.n_rows, adj.n_cols, Wh.shape[1], 1, float(alpha),
+                                           _ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), ctypes.byref(st), float(dead_weight),
+                                           _ptr(G), G.stride(0), _ptr(Wh), Wh.stride(0), _ptr(dead), _ptr(dead_rs), _ptr(sg),
+                                           _ptr(g1), _ptr(S), _stream()), "sgx_gat_backward_edges_stats")
+    return sg, g1, S
 
 
 def readout_mean_linear(x, graph_ptr, weight=None, bias=None, want_pooled=False):

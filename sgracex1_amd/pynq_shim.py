@@ -258,9 +258,10 @@ class IP:
 
     # -- fast path: everything already in HBM ------------------------------------------------
     def run_layer(self, adj, fea, Wt, attention=None, want_edge_outputs=False, out=None, quant=None,
-                  adj_quantized=False, quant_int8=False):
+                  adj_quantized=False, quant_int8=False, want_row_stats=False):
         """One layer with the flags currently in the register map (relu, gat_mode; gemm_mode is
-        implied by the type of `fea` and checked against the register)."""
+        implied by the type of `fea` and checked against the register).  want_row_stats (GAT): returns
+        (out, ops.GatStats) -- the row softmax statistics in place of the E / S ports."""
         from . import ops
         rm = self.register_map
         gemm_mode = 0 if isinstance(fea, ops.Csr) else 1
@@ -274,7 +275,8 @@ class IP:
             raise ValueError(f"config.layer_order must be 'reference' or 'auto', not {config.layer_order!r}")
         return ops.layer_forward(adj, fea, Wt, relu=int(rm.relu), gat_attention=gat, alpha=self.alpha,
                                  want_edge_outputs=want_edge_outputs, bias_count=int(rm.bias_count), out=out,
-                                 quant=quant, adj_quantized=adj_quantized, quant_int8=quant_int8, order=config.layer_order)
+                                 quant=quant, adj_quantized=adj_quantized, quant_int8=quant_int8, order=config.layer_order,
+                                 **({"want_row_stats": True} if want_row_stats else {}))
 
     # -- compat path: host buffers behind fake physical addresses ------------------------------
     _TORCH_OF = {np.dtype(np.float16): torch.float16, np.dtype(np.float32): torch.float32, np.dtype(np.int32): torch.int32,

@@ -140,7 +140,13 @@ class FPYNQ_GAT(torch.autograd.Function):
             # they are the faster form (dense features wider than 128 columns; sgx.h SGX_QUANT_INT8_AUTO);
             # config.fake_quantization alone: the fp32 emulation of the grid, as the reference states it
             int8 = "auto" if (qc is not None and config.hardware_quantize) else False
-            if ctx.gat:
+            ctx.lean = bool(ctx.gat) and not int(config.gat_edge_outputs)
+            if ctx.lean:
+                # the row softmax statistics instead of E and S (3 n + n_cols floats in place of 2 nnz); the forward is
+                # the one without side outputs
+                out, stats = my_ip.run_layer(A, fea, Wt, attention=attention.detach().to(dt).reshape(-1).contiguous(),
+                                             quant=qc, quant_int8=int8, want_row_stats=True)
+            elif ctx.gat:
                 out, E, S = my_ip.run_layer(A, fea, Wt, attention=attention.detach().to(dt).reshape(-1).contiguous(),
                                             want_edge_outputs=True, quant=qc, quant_int8=int8)
             else:
@@ -152,6 +158,10 @@ class FPYNQ_GAT(torch.autograd.Function):
             if ctx.gat:
                 masked = A.quantized(qc) if qc is not None else A
                 ctx.dead = masked.dead_rows if masked.has_dead_rows else None
+            if ctx.lean:
+                ctx.masked = masked           # the adjacency the forward masked with: E and S are formed again on it
+                ctx.save_for_backward(input, weights, out, *stats.tensors())
+                return out.float()
             ctx.save_for_backward(input, weights, out, *([E, S] if ctx.gat else []))
             return out.float()                                            # SG.py:543 `.float()`
 
@@ -216,10 +226,26 @@ class FPYNQ_GAT(torch.autograd.Function):
             input = input.to_dense()
         A = ctx.csr
         if ctx.gat:
-            E, S = saved[3], saved[4]
-            P = ops.Csr(A.rowptr, A.col, S.contiguous(), A.n_cols, A.plan if A.wants_plan else None)   # attention matrix, fp32 values; A's schedule
             Wh = ops.xw_dense(input.contiguous(), weights.t().contiguous())       # X . W, fp32 (SG.py:601); rows padded to 16 B
-            sg, g1 = ops.gat_backward_edges(A, E, S, g.contiguous(), Wh, ctx.alpha, dead=ctx.dead)
+            if getattr(ctx, "lean", False):
+                # One values array decides both which entries carried weight in the forward and which the backward masks
+                # (SG.py masks with the UNquantised adjacency).  Unquantised they are the same array.  Quantised, a live row
+                # takes the quantised values (an entry that rounded to 0 had S = 0, so its sg is 0 under either mask) and a
+                # dead row -- uniform weight whatever the values -- the unquantised ones, whose mask is the one that shows.
+                M = ctx.masked
+                if M is not A and ctx.dead is not None:
+                    if getattr(M, "_lean_values", None) is None:
+                        deg = (A.rowptr[1:] - A.rowptr[:-1]).long()
+                        row = torch.repeat_interleave(torch.arange(A.n_rows, device=g.device), deg, output_size=A.nnz)
+                        M._lean_values = ops.Csr(A.rowptr, A.col, torch.where(ctx.dead[row], A.val[:A.nnz], M.val[:A.nnz]).contiguous(),
+                                                 A.n_cols)
+                    M = M._lean_values
+                sg, g1, S = ops.gat_backward_edges_stats(M, ops.GatStats.of(*saved[3:7]), g.contiguous(), Wh, ctx.alpha,
+                                                         dead=ctx.dead, dead_weight=1.0 / A.n_cols if ctx.dead is not None else 0.0)
+            else:
+                E, S = saved[3], saved[4]
+                sg, g1 = ops.gat_backward_edges(A, E, S, g.contiguous(), Wh, ctx.alpha, dead=ctx.dead)
+            P = ops.Csr(A.rowptr, A.col, S.contiguous(), A.n_cols, A.plan if A.wants_plan else None)   # attention matrix, fp32 values; A's schedule
             # column sums of sg = row sums over A^T; the transposed pattern is built once per graph
             if getattr(A, "_transpose_pattern", None) is None:
                 A._transpose_pattern = ops.csr_transpose(A, return_order=True)
