@@ -5,7 +5,7 @@ synthetic planted-partition graph because the demo's datasets (Planetoid Cora, A
 downloaded by torch_geometric and are not available offline.
 
     python examples/sgrace_node_classification.py [--attention [--lean-gat]] [--qbits 8] [--epochs 60] [--acc 0]
-                                                  [--batch-size 128 --num-neighbors 10,10]
+                                                  [--batch-size 128 --num-neighbors 10,10 [--device-batches]]
 
 --attention  GAT edge softmax instead of the GCN aggregate (config.compute_attention)
 --lean-gat   with --attention on the kernels: the forward keeps the row softmax statistics instead of the per-edge outputs
@@ -21,6 +21,10 @@ downloaded by torch_geometric and are not available offline.
              the demo's mini-batch mode (demo_sgrace.py:112-125, full_graph = 0): every epoch trains on
              pyg_lite.NeighborLoader batches of B training nodes with K1 sampled neighbours per node at hop 1, K2 at
              hop 2 ..., sampled on the GPU; evaluation stays on the full graph
+--device-batches
+             with --batch-size: the loader hands over layer-ready batches (NeighborLoader(..., prepare="sym_norm2")): the
+             normalised adjacency, the feature CSR, the labels and masks are built on the GPU behind the sample, and a
+             training step synchronises once, inside the sampler
 """
 import argparse
 import os
@@ -50,7 +54,7 @@ def planted_partition(n, classes, f_in, p_in, p_out, seed, device):
 
 
 def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, verbose=True, emulate=False,
-        batch_size=None, num_neighbors=None, lean_gat=False):
+        batch_size=None, num_neighbors=None, lean_gat=False, device_batches=False):
     from sgracex1_amd import config, sgrace
     config.acc = acc
     config.gat_edge_outputs = 0 if lean_gat else 1
@@ -76,7 +80,7 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         train_mask[train] = True
         data = pyg_lite.NodeData(x, edge_index, y, train_mask=train_mask)
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
-                                         shuffle=True, seed=seed)
+                                         shuffle=True, seed=seed, **({"prepare": "sym_norm2"} if device_batches else {}))
     t0 = time.time()
     for epoch in range(epochs):
         model.train()
@@ -90,8 +94,14 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
                 opt.zero_grad()
                 # the layers aggregate at edge_index[0]; PyG's batches put the seed in row 1, so flipped, each seed row
                 # holds its sampled neighbours (taken literally, it would hold its self loop and little else)
-                out = model(batch.x, batch.edge_index.flip(0))
-                loss = crit(out[batch.train_mask], batch.y[batch.train_mask])
+                if device_batches:
+                    # edge_index_agg is that flipped list with the normalised CSR attached; the seeds are rows
+                    # 0 .. batch_size-1 and every input node is a training node, so no mask (and no sync) is needed
+                    out = model(batch.x, batch.edge_index_agg)
+                    loss = crit(out[:batch.batch_size], batch.y[:batch.batch_size])
+                else:
+                    out = model(batch.x, batch.edge_index.flip(0))
+                    loss = crit(out[batch.train_mask], batch.y[batch.train_mask])
                 loss.backward()
                 opt.step()
         if verbose and (epoch + 1) % 20 == 0:
@@ -125,8 +135,11 @@ if __name__ == "__main__":
     ap.add_argument("--num-neighbors", type=lambda s: [int(k) for k in s.split(",")], default=None)
     ap.add_argument("--lean-gat", action="store_true")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--device-batches", action="store_true")
     a = ap.parse_args()
     if (a.batch_size is None) != (a.num_neighbors is None) or (a.batch_size is not None and a.acc != 1):
         ap.error("--batch-size and --num-neighbors go together, on the kernels (--acc 1)")
+    if a.device_batches and a.batch_size is None:
+        ap.error("--device-batches selects the loader of the mini-batch mode (--batch-size, --num-neighbors)")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
-        num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed)
+        num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches)

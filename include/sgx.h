@@ -732,6 +732,86 @@ int sgx_batch_plan_create_known(int dtype, int n_rows, int n_graphs, const int32
  * SGX_ERR_NULL. */
 int64_t sgx_batch_plan_export_groups(const sgx_batch_plan *plan, int32_t *dst, int64_t capacity, void *stream);
 
+/* ---- layer-ready node batches: a neighbour sample prepared on the device ----------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_node_batch_sample runs sgx_sample_neighbors (same arguments, same results) and, behind it on the same stream
+ * without reading anything back in between, builds what the SGRACE layers need from the sample (csrc/node_batch.hip).
+ * The counts the host needs ride the sampler's one read-back, which stays the only one of the call.
+ *
+ * Normalised adjacency -- sym_norm2 (SG.py:18-51) of the sampled CSR, in the orientation the layers aggregate in (row i =
+ * the neighbours sampled for local node i), as the CSR the layer reads; n = nodes rows and columns:
+ *   - entry weights w: edge_weight[edge_pos[e]] (edge_weight indexed like columnIndex of the input graph), or 1 when
+ *     edge_weight is NULL;
+ *   - every row without a stored self loop gets one of weight `fill`; stored loops keep their weight;
+ *   - the entries of a row are ordered by column, stably: repeated edges stay separate entries in sampled order, and the
+ *     added loop comes after stored entries of its column (there are none, or it would not be added -- the rule fixes
+ *     the order for the restatement all the same);
+ *   - deg[r] = the row's weights added one by one in that stored order, in fp32, starting from 0;
+ *   - dis[r] = deg[r] > 0 ? 1 / sqrt(deg[r]) : 0, the square root and then the division each the IEEE-754 correctly
+ *     rounded fp32 operation;
+ *   - value = (dis[r] * w) * dis[c]: the left product rounded to fp32, then the right one, then one rounding to `dtype`
+ *     (SGX_F32: none).
+ * The result is a pure function of the sample, edge_weight and fill: the same bits on every run.
+ *   rowPtr_norm [nodes+1] = out_rowPtr + the exclusive count of rows that got a loop; columnIndex_norm, values_norm
+ *   [nnz_norm <= edges + nodes]; dead_row [nodes] bytes: 1 where the row holds no stored value > 0 (after the rounding
+ *   to dtype) -- the rows the GAT mask `adj > 0` leaves without a neighbour.
+ *   edge_index_agg / edge_index: int64 [2][edges], written at [0, edges) and [edges, 2 edges) of buffers of 2 max_edges
+ *   entries: row 0 the aggregating node and row 1 its sampled neighbour / PyG's orientation, the two rows swapped.
+ *   Either may be NULL.
+ * Features (optional, rowPtr_x != NULL): the CSR (rowPtr_x, columnIndex_x, values_x fp32) of the whole graph's feature
+ * matrix; rows n_id of it, in that order, are copied to rowPtr_fea [nodes+1], columnIndex_fea, values_fea (in dtype, the
+ * fp32 value rounded to nearest even) -- the CSR a dense-to-CSR conversion of the gathered rows gives.  fea_capacity =
+ * the entries columnIndex_fea / values_fea hold; a batch that needs more fails with SGX_ERR_SHAPE, nothing written
+ * outside.  Labels (optional): y_out[i] = y[n_id[i]] (int64), mask_out[m][i] = mask[m][n_id[i]] (bytes), each NULL or
+ * given.
+ * Host results: hop_nodes / hop_edges as sgx_sample_neighbors; nnz_norm, nnz_fea, has_dead_rows (some dead_row is 1),
+ * max_row (the longest row of the normalised matrix).
+ *
+ * Capacity: sgx_node_batch_workspace_bytes is sgx_sample_workspace_bytes for this call (same bounds max_nodes /
+ * max_edges; more bytes).  rowPtr_norm holds max_nodes + 1 entries, columnIndex_norm / values_norm max_edges + max_nodes,
+ * dead_row / y_out / mask_out max_nodes, rowPtr_fea max_nodes + 1.  Nothing allocates.  Status codes and the node_map
+ * contract are the sampler's; dtype other than SGX_F16 / SGX_F32: SGX_ERR_UNSUPPORTED.  batch == 0: the three row
+ * pointers get their single 0 and the call returns without a read-back.  Not capturable. */
+typedef struct sgx_node_batch {
+    /* the sampler's arguments (sgx_sample_neighbors) */
+    const int32_t *rowPtr, *columnIndex;
+    int32_t n_nodes, batch, n_hops, dtype;     /* dtype: element type of values_norm and values_fea */
+    int64_t nnz;
+    const int32_t *seeds;
+    const int *fanouts;                        /* HOST [n_hops] */
+    uint64_t seed, step;
+    int32_t *node_map, *n_id, *out_rowPtr, *out_col, *edge_pos;
+    int64_t max_nodes, max_edges;
+    int64_t *hop_nodes, *hop_edges;            /* HOST out [n_hops+1] each */
+    /* normalised adjacency */
+    const float *edge_weight;                  /* [nnz] or NULL */
+    float fill;
+    int32_t *rowPtr_norm, *columnIndex_norm;
+    void *values_norm;
+    uint8_t *dead_row;
+    int64_t *edge_index, *edge_index_agg;
+    /* features and labels */
+    const int32_t *rowPtr_x, *columnIndex_x;
+    const float *values_x;
+    int32_t *rowPtr_fea, *columnIndex_fea;
+    void *values_fea;
+    int64_t fea_capacity;
+    const int64_t *y;
+    int64_t *y_out;
+    const uint8_t *mask[3];
+    uint8_t *mask_out[3];
+    /* host results */
+    int64_t nnz_norm, nnz_fea;
+    int32_t has_dead_rows, max_row;
+    void *workspace;
+    size_t workspace_bytes;
+} sgx_node_batch;
+
+size_t sgx_node_batch_workspace_bytes(int n_nodes, int64_t nnz, int batch, int n_hops, const int *fanouts,
+                                      int64_t *max_nodes, int64_t *max_edges);
+int sgx_node_batch_sample(sgx_node_batch *b, void *stream);
+
 /* A plain streaming copy (16 bytes per lane, non-temporal, each workgroup on a contiguous chunk), the kernel the attainable HBM rate of a device is
  * measured with next to the nominal 8 TB/s (bench.py reports it as roofline.stream_copy_GBps_this_device).
  * bytes must be a multiple of 16, both pointers 16-byte aligned. */

@@ -42,6 +42,7 @@ SYMBOLS = [
     "sgx_batch_plan_create_ex", "sgx_stack_backward_workspace_bytes", "sgx_stack_backward",
     "sgx_collate_graphs", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
     "sgx_gat_aggregate_stats", "sgx_layer_forward_stats", "sgx_gat_edge_outputs", "sgx_gat_backward_edges_stats",
+    "sgx_node_batch_workspace_bytes", "sgx_node_batch_sample",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -164,6 +165,32 @@ class GraphBatch(ctypes.Structure):
         ("graph_ptr", ctypes.c_void_p),
         ("rowPtr_adj", ctypes.c_void_p), ("columnIndex_adj", ctypes.c_void_p), ("values_adj", ctypes.c_void_p * 2),
         ("rowPtr_fea", ctypes.c_void_p), ("columnIndex_fea", ctypes.c_void_p), ("values_fea", ctypes.c_void_p * 2),
+    ]
+
+
+class NodeBatch(ctypes.Structure):
+    """struct sgx_node_batch -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("rowPtr", ctypes.c_void_p), ("columnIndex", ctypes.c_void_p),
+        ("n_nodes", ctypes.c_int32), ("batch", ctypes.c_int32), ("n_hops", ctypes.c_int32), ("dtype", ctypes.c_int32),
+        ("nnz", ctypes.c_int64),
+        ("seeds", ctypes.c_void_p), ("fanouts", ctypes.POINTER(ctypes.c_int32)),
+        ("seed", ctypes.c_uint64), ("step", ctypes.c_uint64),
+        ("node_map", ctypes.c_void_p), ("n_id", ctypes.c_void_p), ("out_rowPtr", ctypes.c_void_p),
+        ("out_col", ctypes.c_void_p), ("edge_pos", ctypes.c_void_p),
+        ("max_nodes", ctypes.c_int64), ("max_edges", ctypes.c_int64),
+        ("hop_nodes", ctypes.POINTER(ctypes.c_int64)), ("hop_edges", ctypes.POINTER(ctypes.c_int64)),
+        ("edge_weight", ctypes.c_void_p), ("fill", ctypes.c_float),
+        ("rowPtr_norm", ctypes.c_void_p), ("columnIndex_norm", ctypes.c_void_p), ("values_norm", ctypes.c_void_p),
+        ("dead_row", ctypes.c_void_p), ("edge_index", ctypes.c_void_p), ("edge_index_agg", ctypes.c_void_p),
+        ("rowPtr_x", ctypes.c_void_p), ("columnIndex_x", ctypes.c_void_p), ("values_x", ctypes.c_void_p),
+        ("rowPtr_fea", ctypes.c_void_p), ("columnIndex_fea", ctypes.c_void_p), ("values_fea", ctypes.c_void_p),
+        ("fea_capacity", ctypes.c_int64),
+        ("y", ctypes.c_void_p), ("y_out", ctypes.c_void_p),
+        ("mask", ctypes.c_void_p * 3), ("mask_out", ctypes.c_void_p * 3),
+        ("nnz_norm", ctypes.c_int64), ("nnz_fea", ctypes.c_int64),
+        ("has_dead_rows", ctypes.c_int32), ("max_row", ctypes.c_int32),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
 
 
@@ -306,6 +333,10 @@ def _load():
     lib.sgx_batch_plan_create_known.restype = c_int
     lib.sgx_batch_plan_export_groups.argtypes = [vp, vp, c_i64, vp]
     lib.sgx_batch_plan_export_groups.restype = c_i64
+    lib.sgx_node_batch_workspace_bytes.argtypes = [c_int, c_i64, c_int, c_int, i32p, i64p, i64p]
+    lib.sgx_node_batch_workspace_bytes.restype = sz
+    lib.sgx_node_batch_sample.argtypes = [ctypes.POINTER(NodeBatch), vp]
+    lib.sgx_node_batch_sample.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

@@ -12,27 +12,15 @@
 //   8    columns relabelled through node_map                                                 (relabel_kernel)
 // Kernel boundaries are the only ordering between workgroups.  A tail writes the row pointer of the last hop's new
 // nodes, and the map entries of every node of n_id are put back to the sentinel.
-#include "sgx_internal.h"
+// The counter block, the scan and the capacity bounds are in sample_device.h, shared with node_batch.hip.
+#include "sample_device.h"
+
+using namespace sgx_sample;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kPer = 8;                       // items per thread of a scan workgroup (contiguous)
-constexpr int kTile = kBlock * kPer;          // items per scan workgroup
-constexpr int kScanTop = 1024;                // threads of the one workgroup that scans the workgroup sums
 constexpr int kFast = 64;                     // fan-outs up to this keep the subset in registers, one element per lane
 constexpr int32_t kSentinel = 0x7fffffff;
-constexpr int kStatusSeeds = 1, kStatusCapacity = 2;
-
-// counter block: [0] status, then nodes(0..H), then edges(0..H)
-struct Counters {
-    int32_t *c;
-    int H;
-    __device__ int32_t &status() const { return c[0]; }
-    __device__ int32_t &nodes(int h) const { return c[1 + h]; }
-    __device__ int32_t &edges(int h) const { return c[2 + H + h]; }
-    __device__ int frontier_begin(int h) const { return h ? c[h] : 0; }
-};
 
 __host__ __device__ inline uint64_t mix64(uint64_t z)
 {
@@ -45,31 +33,6 @@ __device__ inline int draw(uint64_t key, int v, int j)
 {
     const uint64_t w = ((uint64_t)(uint32_t)v << 32) | (uint32_t)j;
     return (int)__umul64hi(mix64(key ^ mix64(w)), (uint64_t)j + 1);     // in [0, j]
-}
-
-template <int NT>
-__device__ inline int block_exclusive_scan(int x, int *total)
-{
-    __shared__ int wsum[NT / 64];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    int inc = x;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int y = __shfl_up(inc, d, 64);
-        if (lane >= d) inc += y;
-    }
-    if (lane == 63) wsum[w] = inc;
-    __syncthreads();
-    int off = 0, tot = 0;
-#pragma unroll
-    for (int i = 0; i < NT / 64; ++i) {
-        const int s = wsum[i];
-        off += i < w ? s : 0;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return off + inc - x;
 }
 
 // items: the frontier rows of hop h; value: the number of edges the row samples
@@ -116,64 +79,6 @@ struct FirstSeen {
     }
     __device__ void total(int t) const { ctr.nodes(h + 1) = ctr.nodes(h) + t; }
 };
-
-template <class F>
-__global__ __launch_bounds__(kBlock) void scan_reduce_kernel(F f, int32_t *__restrict__ bsum)
-{
-    if (f.ctr.status()) return;
-    const int n = f.n(), base = blockIdx.x * kTile;
-    if (base >= n) return;                                 // uniform over the workgroup
-    int s = 0;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-        const int i = base + u * kBlock + threadIdx.x;
-        if (i < n) s += f.value(i);
-    }
-    int tot;
-    block_exclusive_scan<kBlock>(s, &tot);
-    if (threadIdx.x == 0) bsum[blockIdx.x] = tot;
-}
-
-template <class F>
-__global__ __launch_bounds__(kScanTop) void scan_top_kernel(F f, int32_t *__restrict__ bsum)
-{
-    if (f.ctr.status()) return;
-    const int n = f.n(), nb = (n + kTile - 1) / kTile;
-    int carry = 0;
-    for (int b0 = 0; b0 < nb; b0 += kScanTop) {
-        const int i = b0 + threadIdx.x;
-        const int x = i < nb ? bsum[i] : 0;
-        int tot;
-        const int ex = block_exclusive_scan<kScanTop>(x, &tot);
-        if (i < nb) bsum[i] = carry + ex;
-        carry += tot;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) f.total(carry);
-}
-
-template <class F>
-__global__ __launch_bounds__(kBlock) void scan_emit_kernel(F f, const int32_t *__restrict__ bsum)
-{
-    if (f.ctr.status()) return;
-    const int n = f.n(), base = blockIdx.x * kTile;
-    if (base >= n) return;
-    const int i0 = base + threadIdx.x * kPer;
-    int v[kPer], s = 0;
-#pragma unroll
-    for (int u = 0; u < kPer; ++u) {
-        v[u] = i0 + u < n ? f.value(i0 + u) : 0;
-        s += v[u];
-    }
-    int tot;
-    int ex = block_exclusive_scan<kBlock>(s, &tot) + bsum[blockIdx.x];
-#pragma unroll
-    for (int u = 0; u < kPer; ++u)
-        if (i0 + u < n) {
-            f.emit(i0 + u, ex, v[u]);
-            ex += v[u];
-        }
-}
 
 __global__ __launch_bounds__(kBlock) void seed_kernel(const int32_t *__restrict__ seeds, int B, int n_nodes,
                                                       int32_t *__restrict__ map, int32_t *__restrict__ n_id, Counters ctr)
@@ -284,48 +189,53 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const int32_t *__restrict
     }
 }
 
-// the sizes of every hop, from the fan-outs alone (sgx.h): frontier rows, sampled edges; totals
-struct Bounds {
-    int64_t front[64], edges[64], max_nodes, max_edges, max_tiles;
-};
-
-bool bounds(int n_nodes, int64_t nnz, int B, int n_hops, const int *fanouts, Bounds *b)
-{
-    if (n_nodes < 0 || nnz < 0 || nnz > 0x7ffffffe || B < 0 || B > n_nodes || n_hops < 1 || n_hops > 64 || !fanouts)
-        return false;
-    // (a frontier is bounded by n_nodes - B, not by what the earlier bounds leave: a hop that finds fewer nodes than
-    // its bound leaves more for the next one)
-    int64_t front = B, nodes = B, edges = 0, tiles = 1;
-    for (int h = 0; h < n_hops; ++h) {
-        const int k = fanouts[h];
-        if (k < -1) return false;
-        int64_t e = k < 0 ? nnz : front * (int64_t)k;
-        if (e > nnz) e = nnz;
-        b->front[h] = front;
-        b->edges[h] = e;
-        const int64_t items = front > e ? front : e;
-        if ((items + kTile - 1) / kTile > tiles) tiles = (items + kTile - 1) / kTile;
-        edges += e;
-        front = e < n_nodes - B ? e : n_nodes - B;
-        nodes += front;
-    }
-    b->max_nodes = nodes < n_nodes ? nodes : n_nodes;
-    b->max_edges = edges < nnz ? edges : nnz;
-    b->max_tiles = tiles;
-    return true;
-}
-
-size_t counters_bytes(int n_hops) { return sgx_align_up(sizeof(int32_t) * (2 * n_hops + 3), 256); }
-
-unsigned grid_of(int64_t items, int per, int64_t cap)
-{
-    int64_t g = (items + per - 1) / per;
-    if (g < 1) g = 1;
-    if (cap > 0 && g > cap) g = cap;
-    return (unsigned)g;
-}
-
 }  // namespace
+
+int sgx_sample::sample_enqueue(const int32_t *rowPtr, const int32_t *columnIndex, int n_nodes, const int32_t *seeds, int batch,
+                               int n_hops, const int *fanouts, uint64_t seed, uint64_t step, int32_t *node_map, int32_t *n_id,
+                               int32_t *out_rowPtr, int32_t *out_col, int32_t *edge_pos, int64_t max_nodes, int64_t max_edges,
+                               const Bounds &b, int32_t *cbuf, int32_t *bsum, hipStream_t s)
+{
+    const Counters ctr{cbuf, n_hops};
+    SGX_HIP_CHECK(hipMemsetAsync(cbuf, 0, sizeof(int32_t) * counter_count(n_hops), s));
+    hipLaunchKernelGGL(seed_kernel, dim3(grid_of(batch, kBlock, 0)), dim3(kBlock), 0, s, seeds, batch, n_nodes, node_map,
+                       n_id, ctr);
+    SGX_LAUNCH_CHECK();
+    for (int h = 0; h < n_hops; ++h) {
+        const uint64_t key = mix64(mix64(mix64(seed) ^ step) ^ (uint64_t)h);
+        scan_launch(RowCounts{ctr, rowPtr, n_id, out_rowPtr, h, fanouts[h]}, b.front[h], bsum, s);
+        const SampleArgs sa{rowPtr, columnIndex, n_id, out_rowPtr, out_col, edge_pos, node_map, max_edges, key, h, fanouts[h]};
+        hipLaunchKernelGGL(sample_kernel, dim3(grid_of(b.front[h], kBlock / 64, 0)), dim3(kBlock), 0, s, sa, ctr);
+        scan_launch(FirstSeen{ctr, out_col, node_map, n_id, max_nodes, h}, b.edges[h], bsum, s);
+        hipLaunchKernelGGL(relabel_kernel, dim3(grid_of(b.edges[h], kBlock, 2048)), dim3(kBlock), 0, s, out_col, node_map,
+                           ctr, h);
+        SGX_LAUNCH_CHECK();
+    }
+    hipLaunchKernelGGL(tail_kernel, dim3(grid_of(b.front[n_hops - 1] + b.edges[n_hops - 1] + 1, kBlock, 2048)), dim3(kBlock),
+                       0, s, out_rowPtr, ctr, max_nodes);
+    hipLaunchKernelGGL(reset_kernel, dim3(grid_of(b.max_nodes, kBlock, 2048)), dim3(kBlock), 0, s, n_id, batch, n_nodes,
+                       node_map, ctr, max_nodes);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}
+
+int sgx_sample::sample_finish(const int32_t *cbuf, int n_hops, int64_t *hop_nodes, int64_t *hop_edges, int32_t *extras,
+                              hipStream_t s)
+{
+    // the one read-back of the call: status, the counts of every hop, and what a batch preparation left behind them
+    int32_t host[2 * 64 + 3 + kExtras];
+    SGX_HIP_CHECK(hipMemcpyAsync(host, cbuf, sizeof(int32_t) * counter_count(n_hops), hipMemcpyDeviceToHost, s));
+    SGX_HIP_CHECK(hipStreamSynchronize(s));
+    if (host[0] & kStatusSeeds) return SGX_ERR_SEEDS;
+    if (host[0]) return SGX_ERR_SHAPE;
+    for (int h = 0; h <= n_hops; ++h) {
+        hop_nodes[h] = host[1 + h];
+        hop_edges[h] = host[2 + n_hops + h];
+    }
+    if (extras)
+        for (int k = 0; k < kExtras; ++k) extras[k] = host[3 + 2 * n_hops + k];
+    return SGX_OK;
+}
 
 extern "C" size_t sgx_sample_workspace_bytes(int n_nodes, int64_t nnz, int batch, int n_hops, const int *fanouts,
                                              int64_t *max_nodes, int64_t *max_edges)
@@ -360,43 +270,8 @@ extern "C" int sgx_sample_neighbors(const int32_t *rowPtr, const int32_t *column
     }
     int32_t *cbuf = (int32_t *)workspace;
     int32_t *bsum = (int32_t *)((char *)workspace + counters_bytes(n_hops));
-    const Counters ctr{cbuf, n_hops};
-    SGX_HIP_CHECK(hipMemsetAsync(cbuf, 0, sizeof(int32_t) * (2 * n_hops + 3), s));
-    hipLaunchKernelGGL(seed_kernel, dim3(grid_of(batch, kBlock, 0)), dim3(kBlock), 0, s, seeds, batch, n_nodes, node_map,
-                       n_id, ctr);
-    SGX_LAUNCH_CHECK();
-    for (int h = 0; h < n_hops; ++h) {
-        const uint64_t key = mix64(mix64(mix64(seed) ^ step) ^ (uint64_t)h);
-        const RowCounts rc{ctr, rowPtr, n_id, out_rowPtr, h, fanouts[h]};
-        const unsigned gr = grid_of(b.front[h], kTile, 0);
-        hipLaunchKernelGGL(scan_reduce_kernel<RowCounts>, dim3(gr), dim3(kBlock), 0, s, rc, bsum);
-        hipLaunchKernelGGL(scan_top_kernel<RowCounts>, dim3(1), dim3(kScanTop), 0, s, rc, bsum);
-        hipLaunchKernelGGL(scan_emit_kernel<RowCounts>, dim3(gr), dim3(kBlock), 0, s, rc, bsum);
-        const SampleArgs sa{rowPtr, columnIndex, n_id, out_rowPtr, out_col, edge_pos, node_map, max_edges, key, h, fanouts[h]};
-        hipLaunchKernelGGL(sample_kernel, dim3(grid_of(b.front[h], kBlock / 64, 0)), dim3(kBlock), 0, s, sa, ctr);
-        const FirstSeen fs{ctr, out_col, node_map, n_id, max_nodes, h};
-        const unsigned ge = grid_of(b.edges[h], kTile, 0);
-        hipLaunchKernelGGL(scan_reduce_kernel<FirstSeen>, dim3(ge), dim3(kBlock), 0, s, fs, bsum);
-        hipLaunchKernelGGL(scan_top_kernel<FirstSeen>, dim3(1), dim3(kScanTop), 0, s, fs, bsum);
-        hipLaunchKernelGGL(scan_emit_kernel<FirstSeen>, dim3(ge), dim3(kBlock), 0, s, fs, bsum);
-        hipLaunchKernelGGL(relabel_kernel, dim3(grid_of(b.edges[h], kBlock, 2048)), dim3(kBlock), 0, s, out_col, node_map,
-                           ctr, h);
-        SGX_LAUNCH_CHECK();
-    }
-    hipLaunchKernelGGL(tail_kernel, dim3(grid_of(b.front[n_hops - 1] + b.edges[n_hops - 1] + 1, kBlock, 2048)), dim3(kBlock),
-                       0, s, out_rowPtr, ctr, max_nodes);
-    hipLaunchKernelGGL(reset_kernel, dim3(grid_of(b.max_nodes, kBlock, 2048)), dim3(kBlock), 0, s, n_id, batch, n_nodes,
-                       node_map, ctr, max_nodes);
-    SGX_LAUNCH_CHECK();
-    // the one read-back of the call: status and the counts of every hop
-    int32_t host[2 * 64 + 3];
-    SGX_HIP_CHECK(hipMemcpyAsync(host, cbuf, sizeof(int32_t) * (2 * n_hops + 3), hipMemcpyDeviceToHost, s));
-    SGX_HIP_CHECK(hipStreamSynchronize(s));
-    if (host[0] & kStatusSeeds) return SGX_ERR_SEEDS;
-    if (host[0]) return SGX_ERR_SHAPE;
-    for (int h = 0; h <= n_hops; ++h) {
-        hop_nodes[h] = host[1 + h];
-        hop_edges[h] = host[2 + n_hops + h];
-    }
-    return SGX_OK;
+    const int st = sample_enqueue(rowPtr, columnIndex, n_nodes, seeds, batch, n_hops, fanouts, seed, step, node_map, n_id,
+                                  out_rowPtr, out_col, edge_pos, max_nodes, max_edges, b, cbuf, bsum, s);
+    if (st != SGX_OK) return st;
+    return sample_finish(cbuf, n_hops, hop_nodes, hop_edges, nullptr, s);
 }

@@ -208,6 +208,7 @@ class Csr:
         self._plan = plan
         self._dead_rows = None
         self._dead_row_mask = None
+        self._max_row = None                   # the longest row, or a bound on it, where the builder knows it
         self._quantized = {}
 
     @property
@@ -263,13 +264,32 @@ class Csr:
     def wants_plan(self):
         """Building a plan costs one device->host copy and a stream sync; matrices this small finish
         in microseconds on any schedule, so they run without one unless a plan already exists."""
-        return self._plan is not None or self.nnz >= 8192
+        if self._plan is not None:
+            return True
+        if self._max_row is not None and self._max_row <= 64 and self.nnz < (1 << 20):
+            # known facts (a loader's batch): under 2^20 entries a plan cuts rows over 64 entries and there are none, so
+            # it would only reorder short rows -- not worth its read-back, synchronisation and allocations per batch
+            return False
+        return self.nnz >= 8192
+
+    def with_facts(self, dead_row_mask=None, has_dead_rows=None, max_row=None):
+        """Records what the builder of this matrix already knows, so that nothing is computed or read back for it:
+        dead_rows (bool [n_rows]), has_dead_rows, and the longest row (or a bound on it; see wants_plan)."""
+        if dead_row_mask is not None:
+            self._dead_row_mask = dead_row_mask
+        if has_dead_rows is not None:
+            self._dead_rows = bool(has_dead_rows)
+        if max_row is not None:
+            self._max_row = int(max_row)
+        return self
 
     def to(self, dtype):
         # (the schedule depends on rowptr only: the copy shares this matrix's -- built here if it is wanted and not there
         # yet, so that a copy made per training step does not build one per step)
-        return self if self.val.dtype == dtype else Csr(self.rowptr, self.col, self.val.to(dtype), self.n_cols,
-                                                        self.plan if self.wants_plan else None)
+        if self.val.dtype == dtype:
+            return self
+        return Csr(self.rowptr, self.col, self.val.to(dtype), self.n_cols,
+                   self.plan if self.wants_plan else None).with_facts(max_row=self._max_row)
 
     def validate(self):
         check(lib.sgx_csr_validate(_ptr(self.rowptr), _ptr(self.col), self.n_rows, self.n_cols, self.nnz, _stream()),
@@ -715,7 +735,7 @@ def csr_transpose(A, return_order=False):
     """CSR of A^T (values kept, same dtype); features are fixed across epochs, so callers cache it.
     return_order: also the edge permutation (edge k of A^T is edge order[k] of A)."""
     row = torch.repeat_interleave(torch.arange(A.n_rows, device=A.col.device, dtype=torch.int64),
-                                  (A.rowptr[1:] - A.rowptr[:-1]).long())
+                                  (A.rowptr[1:] - A.rowptr[:-1]).long(), output_size=A.nnz)
     col, val = A.col[:A.nnz], A.val[:A.nnz]
     key = col.to(torch.int64) * A.n_rows + row
     order = torch.argsort(key)
@@ -948,6 +968,109 @@ def sample_neighbors(csr, seeds, fanouts, seed=0, step=0, gather_values=False):
     val = csr.val[pos[:E].long()] if gather_values else torch.ones(E, dtype=torch.float32, device=dev)
     adj = Csr(rowptr[:N + 1], col[:E], val, N)
     return Sample(n_id[:N], adj, pos[:E], B, hop_nodes[:], hop_edges[:])
+
+
+class NodeSample(Sample):
+    """A Sample prepared for the layers on the device (sample_node_batch): besides the sample, adj_norm -- the Csr of
+    sym_norm2 over adj in the requested dtype, with its dead-row mask, flag and longest row recorded --, edge_index /
+    edge_index_agg (int64 [2, E]: PyG's orientation / row 0 the aggregating node), fea (the feature Csr of the rows
+    n_id, or None), y and masks (gathered at n_id, or None / empty)."""
+
+
+def feature_csr(x):
+    """The fp32 CSR of a dense feature matrix with its longest row recorded: what sample_node_batch gathers batches'
+    feature CSRs from.  Synchronises (once per dataset)."""
+    fea = Csr.from_dense(x.float())
+    longest = int((fea.rowptr[1:] - fea.rowptr[:-1]).max().item()) if fea.n_rows else 0
+    return fea.with_facts(max_row=longest)
+
+
+def sample_node_batch(csr, seeds, fanouts, seed=0, step=0, fill=0, dtype=torch.float32, edge_weight=None, features=None,
+                      y=None, masks=()):
+    """sample_neighbors plus, on the device right behind it and inside the same single synchronisation
+    (sgx_node_batch_sample, rule in include/sgx.h): the normalised adjacency sym_norm2 gives for the sampled rows,
+    the rows n_id of `features` (a feature_csr) as the batch's feature Csr, y[n_id] (int64) and each of up to three
+    bool `masks` at n_id.  edge_weight: fp32 [csr.nnz] weights of the graph's edges (None = 1).  -> NodeSample."""
+    _dev(seeds, "seeds")
+    fan = [int(k) for k in fanouts]
+    dev = csr.rowptr.device
+    seeds = seeds.to(torch.int32).contiguous()
+    B, H, n = seeds.numel(), len(fan), csr.n_rows
+    masks = list(masks)
+    if len(masks) > 3:
+        raise ValueError("sample_node_batch gathers up to three masks")
+    fan_c = (ctypes.c_int32 * max(H, 1))(*fan)
+    max_nodes, max_edges = ctypes.c_int64(0), ctypes.c_int64(0)
+    nbytes = lib.sgx_node_batch_workspace_bytes(n, csr.nnz, B, H, fan_c, ctypes.byref(max_nodes), ctypes.byref(max_edges))
+    if nbytes == 0:
+        raise ValueError(f"sample_node_batch: bad arguments (n_nodes {n}, nnz {csr.nnz}, batch {B}, fanouts {fan}): "
+                         "fan-outs must be >= -1, 1 to 64 hops, batch <= n_nodes")
+    mn, me = max_nodes.value, max_edges.value
+    i32 = lambda k: torch.empty(max(int(k), 1), dtype=torch.int32, device=dev)
+    n_id, rowptr, col, pos = i32(mn), i32(mn + 1), i32(me), i32(me)
+    n_rowptr, n_col = i32(mn + 1), i32(me + mn)
+    n_val = torch.empty(max(me + mn, 1), dtype=dtype, device=dev)
+    dead = torch.empty(max(mn, 1), dtype=torch.bool, device=dev)
+    ei = torch.empty(max(2 * me, 1), dtype=torch.int64, device=dev)
+    ei_agg = torch.empty(max(2 * me, 1), dtype=torch.int64, device=dev)
+    hop_nodes, hop_edges = (ctypes.c_int64 * (H + 1))(), (ctypes.c_int64 * (H + 1))()
+    node_map = _node_map(dev, n)
+    ws = _workspace(dev, nbytes)
+    b = _lib.NodeBatch()
+    b.rowPtr, b.columnIndex, b.n_nodes, b.nnz = csr.rowptr.data_ptr(), csr.col.data_ptr(), n, csr.nnz
+    b.seeds, b.batch, b.n_hops, b.fanouts = (seeds.data_ptr() if B else None), B, H, fan_c
+    b.dtype = dtype_code(dtype)
+    b.seed, b.step = int(seed) & (2**64 - 1), int(step) & (2**64 - 1)
+    b.node_map, b.n_id, b.out_rowPtr, b.out_col, b.edge_pos = (node_map.data_ptr(), n_id.data_ptr(), rowptr.data_ptr(),
+                                                               col.data_ptr(), pos.data_ptr())
+    b.max_nodes, b.max_edges, b.hop_nodes, b.hop_edges = mn, me, hop_nodes, hop_edges
+    if edge_weight is not None:
+        _dev(edge_weight, "edge_weight")
+        if edge_weight.dtype != torch.float32 or edge_weight.numel() != csr.nnz:
+            raise ValueError("edge_weight must be float32 [csr.nnz]")
+        b.edge_weight = edge_weight.data_ptr()
+    b.fill = float(fill)
+    b.rowPtr_norm, b.columnIndex_norm, b.values_norm = n_rowptr.data_ptr(), n_col.data_ptr(), n_val.data_ptr()
+    b.dead_row, b.edge_index, b.edge_index_agg = dead.data_ptr(), ei.data_ptr(), ei_agg.data_ptr()
+    f_rowptr = f_col = f_val = None
+    if features is not None:
+        if features.val.dtype != torch.float32 or features.n_rows != n or features._max_row is None:
+            raise ValueError("features must be the feature_csr of the graph's x (fp32 values, one row per node)")
+        cap = min(features.nnz, mn * features._max_row)
+        f_rowptr, f_col = i32(mn + 1), i32(cap)
+        f_val = torch.empty(max(cap, 1), dtype=dtype, device=dev)
+        b.rowPtr_x, b.columnIndex_x, b.values_x = features.rowptr.data_ptr(), features.col.data_ptr(), features.val.data_ptr()
+        b.rowPtr_fea, b.columnIndex_fea, b.values_fea, b.fea_capacity = f_rowptr.data_ptr(), f_col.data_ptr(), f_val.data_ptr(), cap
+    y_out = None
+    if y is not None:
+        _dev(y, "y")
+        if y.dtype != torch.int64 or y.numel() != n:
+            raise ValueError("y must be int64 [n_nodes]")
+        y_out = torch.empty(max(mn, 1), dtype=torch.int64, device=dev)
+        b.y, b.y_out = y.data_ptr(), y_out.data_ptr()
+    m_out = []
+    for k, m in enumerate(masks):
+        _dev(m, "mask")
+        if m.dtype != torch.bool or m.numel() != n:
+            raise ValueError("masks must be bool [n_nodes]")
+        m_out.append(torch.empty(max(mn, 1), dtype=torch.bool, device=dev))
+        b.mask[k], b.mask_out[k] = m.data_ptr(), m_out[k].data_ptr()
+    b.workspace, b.workspace_bytes = ws.data_ptr(), ws.numel()
+    status = lib.sgx_node_batch_sample(ctypes.byref(b), _stream())
+    if status not in (0, _lib.SGX_ERR_SEEDS):
+        node_map.fill_(SAMPLE_SENTINEL)                 # (sgx.h: the map is restored on success and on SGX_ERR_SEEDS only)
+    check(status, "sgx_node_batch_sample")
+    N, E, nn, nf = hop_nodes[H], hop_edges[H], b.nnz_norm, b.nnz_fea
+    adj = Csr(rowptr[:N + 1], col[:E], torch.ones(E, dtype=torch.float32, device=dev), N)
+    s = NodeSample(n_id[:N], adj, pos[:E], B, hop_nodes[:], hop_edges[:])
+    s.adj_norm = Csr(n_rowptr[:N + 1], n_col[:nn], n_val[:nn], N).with_facts(dead[:N], b.has_dead_rows, b.max_row)
+    s.edge_index, s.edge_index_agg = ei[:2 * E].view(2, E), ei_agg[:2 * E].view(2, E)
+    s.fea = None
+    if features is not None:
+        s.fea = Csr(f_rowptr[:N + 1], f_col[:nf], f_val[:nf], features.n_cols).with_facts(max_row=features._max_row)
+    s.y = None if y_out is None else y_out[:N]
+    s.masks = [m[:N] for m in m_out]
+    return s
 
 
 # ---- a batch of small graphs through the whole GCN stack in one launch (sgx_stack_forward) ----------------------------

@@ -191,7 +191,9 @@ class NodeBatch:
     """One NeighborLoader batch, PyG's surface: x / y / masks / n_id of the sampled nodes (seeds first), edge_index in
     local ids oriented as PyG does (row 0 = sampled neighbour, row 1 = the node it was sampled for), batch_size,
     input_id (positions of the seeds in input_nodes), num_sampled_nodes / num_sampled_edges per hop; plus adj, the same
-    edges as a Csr whose row i holds the neighbours sampled for local node i (aggregation at the seed rows)."""
+    edges as a Csr whose row i holds the neighbours sampled for local node i (aggregation at the seed rows).
+    From a loader with prepare="sym_norm2" also edge_index_agg (edge_index with its rows swapped: row 0 the aggregating
+    node, what the SGRACE layers take) and adj_norm (the Csr of sym_norm2 over it)."""
 
     def __init__(self, **fields):
         self.__dict__.update(fields)
@@ -209,9 +211,19 @@ class NeighborLoader:
     (ops.sample_neighbors, rule in include/sgx.h).  The CSR on the targets of edge_index (row v = the edges j -> v,
     flow="source_to_target", repeated edges kept) is built once per loader.  An epoch visits every input node once, in
     order or in a permutation drawn from `seed` and the epoch number; batch b of epoch e samples with step
-    e * len(loader) + b, so every batch is reproducible."""
+    e * len(loader) + b, so every batch is reproducible.
 
-    def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0):
+    prepare="sym_norm2" (with `fill` and `dtype`, the layer's element type): every batch arrives layer-ready, built on the
+    GPU right behind the sample inside the sampler's single synchronisation (ops.sample_node_batch): edge_index_agg
+    carries what GAT_PYNQ.forward looks up -- ("sym_norm2", n, 1, dtype) -> (edge list, values, normalised Csr with its
+    dead-row mask, flag and longest row) -- and x carries ("fea_csr", dtype), gathered from the CSR of data.x built once
+    here.  Pass batch.edge_index_agg to the model; it then computes nothing before its first kernel.  The list of the
+    attached triple is edge_index_agg itself (the sampled edges without the added loops); the kernels read the Csr.
+    The seeds are rows 0 .. batch_size-1, so a loss over them is out[:batch.batch_size].  prepare=None: the batches as
+    before."""
+
+    def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0, prepare=None, fill=0,
+                 dtype=torch.float32):
         from . import ops
         self.data, self.num_neighbors = data, [int(k) for k in num_neighbors]
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
@@ -228,6 +240,17 @@ class NeighborLoader:
         self.csr = ops.Csr.from_coo(dst[order].to(torch.int32), src[order].to(torch.int32),
                                     torch.ones(order.numel(), dtype=torch.float32, device=dev), n, n)
         self.epoch = 0
+        if prepare not in (None, "sym_norm2"):
+            raise ValueError(f"prepare must be None or 'sym_norm2', not {prepare!r}")
+        self.prepare, self.fill, self.dtype = prepare, fill, dtype
+        if prepare:
+            ops.dtype_code(dtype)
+            if x.dtype != torch.float32 or not x.is_contiguous():
+                raise TypeError("a preparing NeighborLoader takes data.x as a contiguous float32 tensor")
+            self.fea = ops.feature_csr(x)                           # once per loader; batches gather their rows from it
+            self.y = None if getattr(data, "y", None) is None else data.y.to(dev, torch.int64).contiguous()
+            self.masks = [(name, getattr(data, name).to(dev, torch.bool).contiguous()) for name in _MASKS
+                          if getattr(data, name, None) is not None]
 
     def __len__(self):
         return (self.input_nodes.numel() + self.batch_size - 1) // self.batch_size
@@ -236,7 +259,8 @@ class NeighborLoader:
         m = self.input_nodes.numel()
         if self.shuffle:
             g = torch.Generator().manual_seed(self.seed * 1000003 + self.epoch)
-            perm = torch.randperm(m, generator=g).to(self.input_nodes.device)
+            # (pinned and non-blocking: the epoch's one upload does not synchronise)
+            perm = torch.randperm(m, generator=g).pin_memory().to(self.input_nodes.device, non_blocking=True)
         else:
             perm = torch.arange(m, device=self.input_nodes.device)
         first_step, self.epoch = self.epoch * len(self), self.epoch + 1
@@ -244,8 +268,27 @@ class NeighborLoader:
             input_id = perm[i:i + self.batch_size]
             yield self._batch(self.input_nodes[input_id], input_id, first_step + b)
 
+    def _prepared(self, seeds, input_id, step):
+        from . import ops
+        s = ops.sample_node_batch(self.csr, seeds, self.num_neighbors, seed=self.seed, step=step, fill=self.fill,
+                                  dtype=self.dtype, features=self.fea, y=self.y, masks=[m for _, m in self.masks])
+        x = ops.pack_rows(self.data.x, s.n_id)
+        A, n = s.adj_norm, s.n_id.numel()
+        ops.attach(x, ("fea_csr", self.dtype), s.fea)
+        ops.attach(s.edge_index_agg, ("sym_norm2", n, 1, self.dtype), (s.edge_index_agg, A.val[:A.nnz], A))
+        fields = dict(x=x, edge_index=s.edge_index, edge_index_agg=s.edge_index_agg, adj_norm=A, n_id=s.n_id.long(),
+                      adj=s.adj, batch_size=s.batch_size, input_id=input_id, num_sampled_nodes=s.num_sampled_nodes,
+                      num_sampled_edges=s.num_sampled_edges)
+        if s.y is not None:
+            fields["y"] = s.y
+        for (name, _), m in zip(self.masks, s.masks):
+            fields[name] = m
+        return NodeBatch(**fields)
+
     def _batch(self, seeds, input_id, step):
         from . import ops
+        if self.prepare:
+            return self._prepared(seeds, input_id, step)
         d = self.data
         s = ops.sample_neighbors(self.csr, seeds, self.num_neighbors, seed=self.seed, step=step)
         A = s.adj

@@ -7,6 +7,13 @@ of examples/sgrace_node_classification.py (GCN and GAT).  One JSON line per meas
 
     python tools/sampler_probe.py > sampler.jsonl
     python tools/sampler_probe.py --quick          # only the kernels, for a rocprofv3 --kernel-trace --stats run
+    python tools/sampler_probe.py --node-batch [--arms default] [--trace]
+                                                   # the training step through the default and the prepared NeighborLoader
+                                                   # (GCN and GAT, the example's shape and the ogbn-products shape), the arms
+                                                   # interleaved, median of repeated windows and their spread; and the batch
+                                                   # preparation alone, device launches against the torch ops
+                                                   # (profiles/r08_node_batch.jsonl).  --arms default: on a tree without
+                                                   # the prepared loader.  --trace: few steps, for rocprofv3 --kernel-trace
 """
 import argparse
 import json
@@ -116,10 +123,131 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e3, out
 
 
+def node_batch(arms, trace):
+    """The training step (loader, forward, loss, backward, Adam) per loader, and the preparation alone."""
+    import importlib.util
+    import statistics
+    from sgracex1_amd import config, pyg_lite, sgrace
+    dev = torch.device("cuda")
+    spec = importlib.util.spec_from_file_location("nc", os.path.join(ROOT, "examples", "sgrace_node_classification.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+
+    def example_shape():
+        x, ei, y = mod.planted_partition(3000, 5, 200, 0.02, 0.002, 1, dev)
+        train = torch.zeros(3000, dtype=torch.bool, device=dev)
+        train[:600] = True
+        return "example (3 000 nodes)", x, ei, y, train, 128, [10, 10]
+
+    def products_shape():
+        n, f = 2_450_000, 100
+        A = graphs.uniform_graph(n, 122_000_000, dtype=torch.float32, normalize=False)
+        row = torch.repeat_interleave(torch.arange(n, device=dev), (A.rowptr[1:] - A.rowptr[:-1]).long(), output_size=A.nnz)
+        ei = torch.stack([A.col[:A.nnz].long(), row])           # CSR row = target of the edge
+        del A, row
+        g = torch.Generator(device=dev).manual_seed(1)
+        x = (torch.rand((n, f), device=dev, generator=g) < 0.1).float() * torch.rand((n, f), device=dev, generator=g)
+        y = torch.randint(0, 5, (n,), device=dev, generator=g)
+        train = torch.zeros(n, dtype=torch.bool, device=dev)
+        train[torch.randperm(n, device=dev, generator=g)[:200_000]] = True
+        return "products shape uniform", x, ei, y, train, 1024, [15, 10, 5]
+
+    for make in (example_shape, products_shape):
+        name, x, ei, y, train, bs, fan = make()
+        data = pyg_lite.NodeData(x, ei, y, train_mask=train)
+        loaders = {}
+        for arm in arms:
+            kw = {"prepare": "sym_norm2"} if arm == "prepared" else {}
+            loaders[arm] = pyg_lite.NeighborLoader(data, fan, batch_size=bs, input_nodes=train, shuffle=True, seed=1, **kw)
+        del ei
+        for attention in (0, 1):
+            config.acc, config.device, config.compute_attention = 1, "cuda", attention
+            sgrace.init_SGRACE()
+            steps = {}
+            for arm in arms:
+                torch.manual_seed(0)
+                model = sgrace.GAT_PYNQ(x.shape[1], 16, 1, 5).to(dev)
+                opt = torch.optim.Adam(model.parameters(), lr=0.01)
+                crit = torch.nn.CrossEntropyLoss()
+                state = {"it": iter(loaders[arm])}
+
+                def step(arm=arm, model=model, opt=opt, crit=crit, state=state):
+                    try:
+                        b = next(state["it"])
+                    except StopIteration:
+                        state["it"] = iter(loaders[arm])
+                        b = next(state["it"])
+                    opt.zero_grad()
+                    if arm == "prepared":
+                        out = model(b.x, b.edge_index_agg)
+                        loss = crit(out[:b.batch_size], b.y[:b.batch_size])
+                    else:
+                        out = model(b.x, b.edge_index.flip(0))
+                        loss = crit(out[b.train_mask], b.y[b.train_mask])
+                    loss.backward()
+                    opt.step()
+                    return b
+                steps[arm] = step
+            windows, reps = (1, 3) if trace else (7, 30)
+            times = {arm: [] for arm in arms}
+            for arm in arms:                                    # warm-up of every arm before any timed window
+                for _ in range(5):
+                    b = steps[arm]()
+            torch.cuda.synchronize()
+            for _ in range(windows):                            # the arms interleaved, window by window
+                for arm in arms:
+                    t0 = time.perf_counter()
+                    for _ in range(reps):
+                        b = steps[arm]()
+                    torch.cuda.synchronize()
+                    times[arm].append((time.perf_counter() - t0) / reps * 1e3)
+            for arm in arms:
+                v = times[arm]
+                print(json.dumps({"end_to_end": "mini-batch training step (loader + forward + loss + backward + Adam)",
+                                  "loader": arm, "model": "GAT" if attention else "GCN", "graph": name, "batch": bs,
+                                  "fanouts": fan, "batch_nodes_last": b.num_nodes, "step_ms_median": round(statistics.median(v), 4),
+                                  "step_ms_min": round(min(v), 4), "step_ms_max": round(max(v), 4), "windows": windows,
+                                  "steps_per_window": reps}), flush=True)
+        if "prepared" in arms and not trace:
+            # the batch preparation alone, on the same seeds: one device call against the sampler plus today's torch ops
+            ld = loaders["prepared"]
+            seeds = ld.input_nodes[:bs]
+            count = iter(range(10 ** 9))
+
+            def device_form():
+                return ld._prepared(seeds, None, next(count))
+
+            def torch_form():
+                s = ops.sample_neighbors(ld.csr, seeds, fan, seed=1, step=next(count))
+                A = s.adj
+                n_idx = s.n_id.long()
+                target = torch.repeat_interleave(torch.arange(A.n_rows, device=dev), (A.rowptr[1:] - A.rowptr[:-1]).long(),
+                                                 output_size=A.nnz)
+                bx = ops.pack_rows(x, s.n_id)
+                agg = torch.stack([A.col[:A.nnz].long(), target]).flip(0)
+                e2, norm = sgrace.sym_norm2(agg, A.n_rows)
+                adj = sgrace._edge_csr(None, e2, norm, A.n_rows, torch.float32)
+                fea = ops.Csr.from_dense(bx, torch.float32)
+                return adj.has_dead_rows, fea, y[n_idx], train[n_idx]
+
+            a_ms, _ = timed(device_form, 50)
+            b_ms, _ = timed(torch_form, 50)
+            print(json.dumps({"batch_preparation": "sample + normalised CSR + feature CSR + x, y, mask + dead rows", "graph": name,
+                              "batch": bs, "fanouts": fan, "device_launches_ms": round(a_ms, 4), "torch_ops_ms": round(b_ms, 4),
+                              "speedup": round(b_ms / a_ms, 2)}), flush=True)
+        del data, loaders, x, y, train
+        torch.cuda.empty_cache()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
+    ap.add_argument("--node-batch", action="store_true")
+    ap.add_argument("--arms", default="default,prepared")
+    ap.add_argument("--trace", action="store_true")
     a = ap.parse_args()
+    if a.node_batch:
+        return node_batch(a.arms.split(","), a.trace)
     dev = torch.device("cuda")
     shapes = [("products shape uniform", lambda: graphs.uniform_graph(2_450_000, 122_000_000, dtype=torch.float32,
                                                                       normalize=False)),
