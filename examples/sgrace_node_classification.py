@@ -5,12 +5,14 @@ synthetic planted-partition graph because the demo's datasets (Planetoid Cora, A
 downloaded by torch_geometric and are not available offline.
 
     python examples/sgrace_node_classification.py [--attention [--lean-gat]] [--qbits 8] [--epochs 60] [--acc 0]
-                                                  [--batch-size 128 --num-neighbors 10,10 [--device-batches]]
+                                                  [--batch-size 128 --num-neighbors 10,10 [--device-batches]] [--accb]
 
 --attention  GAT edge softmax instead of the GCN aggregate (config.compute_attention)
 --lean-gat   with --attention on the kernels: the forward keeps the row softmax statistics instead of the per-edge outputs
              E and S, and the backward forms them again (config.gat_edge_outputs = 0: 3 n + n_cols floats per layer
              in place of 2 nnz)
+--accb       on the kernels: every layer's backward as one call of the C ABI (config.accb = 1, sgx_layer_backward) instead
+             of the stage calls the autograd function composes; the same arithmetic
 --seed S     the seed of the graph, the split and the initial weights
 --qbits B    run the layers with the quantised arithmetic of the SGRACE bitstream (config.fake_quantization and
              config.hardware_quantize, as the reference's board configs set them: integer operands on the int8 matrix
@@ -54,9 +56,10 @@ def planted_partition(n, classes, f_in, p_in, p_out, seed, device):
 
 
 def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, verbose=True, emulate=False,
-        batch_size=None, num_neighbors=None, lean_gat=False, device_batches=False):
+        batch_size=None, num_neighbors=None, lean_gat=False, device_batches=False, accb=0):
     from sgracex1_amd import config, sgrace
     config.acc = acc
+    config.accb = int(accb)
     config.gat_edge_outputs = 0 if lean_gat else 1
     config.compute_attention = int(attention)
     config.fake_quantization = int(qbits != 32)
@@ -136,10 +139,12 @@ if __name__ == "__main__":
     ap.add_argument("--lean-gat", action="store_true")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device-batches", action="store_true")
+    ap.add_argument("--accb", action="store_true")
     a = ap.parse_args()
     if (a.batch_size is None) != (a.num_neighbors is None) or (a.batch_size is not None and a.acc != 1):
         ap.error("--batch-size and --num-neighbors go together, on the kernels (--acc 1)")
     if a.device_batches and a.batch_size is None:
         ap.error("--device-batches selects the loader of the mini-batch mode (--batch-size, --num-neighbors)")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
-        num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches)
+        num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches,
+        accb=int(a.accb))

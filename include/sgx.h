@@ -812,6 +812,103 @@ size_t sgx_node_batch_workspace_bytes(int n_nodes, int64_t nnz, int batch, int n
                                       int64_t *max_nodes, int64_t *max_edges);
 int sgx_node_batch_sample(sgx_node_batch *b, void *stream);
 
+/* ---- the layer's backward in one call ---------------------------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_layer_backward is the backward of sgx_layer_forward for the SGRACE layer (FPYNQ_GAT.backward, SG.py:884-1126, the
+ * `accb == 0` formulas on the stored entries), all in fp32, with P and not P^T as the reference multiplies:
+ *     GAT:  Wh = X . W                                       sgx_xw_dense (after sgx_transpose of W) / sgx_xw_sparse
+ *           sg, g1 = the edge pass                            sgx_gat_backward_edges (E, S) or ..._edges_stats (stats)
+ *           grad_attention = [ Wh^T g1 ; Wh^T colsum(sg) ]    sgx_gat_attention_grad
+ *           P = S on the stored entries; a dead row = 1/N on every column
+ *     GCN:  P = the adjacency values as fp32 (SGX_F16 values are cast into the workspace); grad_attention is not written
+ *     both: pg = P . G                                        sgx_spmm_csr; rows with dead[r]: colsum(G) * (1/N)
+ *           grad_input   = pg . W^T                           sgx_xw_dense(pg, Wt := W); not launched when grad_input is NULL
+ *           grad_weights = X^T . pg                           sgx_xt_g, or sgx_spmm_csr over the CSR of X^T (gemm_mode 0)
+ * 1/N is the fp32 reciprocal of N_adj, rounded once, and multiplies the fp32 column sums (sgx_col_sums); the softmax
+ * row sum the edge pass takes for a dead row is G[r] . (colsum(Wh) * (1/N)) through sgx_xw_dense.  Every product runs on
+ * the stage kernel named, so grad_input and grad_weights carry the bits those calls give on the same operands.
+ *
+ * The forward's state is given in ONE of two forms: E and S (both), or stats with dead_weight (the S of a dead row's
+ * stored entries, 1/N for the layer).  Neither, or only one of E / S: SGX_ERR_NULL; E / S and stats together:
+ * SGX_ERR_UNSUPPORTED.  values_adj is the array the edge-pass call of the form takes as `values`: the mask `adj > 0` is
+ * read from it.  dead (optional, bytes [N_adj]): the rows the forward found without a positive entry.
+ *
+ * Argument errors, returned before anything reaches the device: d or a required pointer NULL: SGX_ERR_NULL; a size
+ * below 1, N_adj != M_adj (P . G needs a square P), ldg < P_w, ldx < M_fea, ld_gi < M_fea: SGX_ERR_SHAPE; gat_heads > 1,
+ * a mode outside {0, 1}, a dtype other than SGX_F16 / SGX_F32, tables past 32-bit byte offsets: SGX_ERR_UNSUPPORTED;
+ * workspace missing or below sgx_layer_backward_workspace_bytes: SGX_ERR_WORKSPACE; not 256-byte aligned: SGX_ERR_ALIGN.
+ * Asynchronous on `stream`, no allocation, no synchronisation: capturable. */
+typedef struct sgx_layer_grad_desc {
+    int32_t gat_mode;    /* 0: GCN, 1: single-head GAT                                             */
+    int32_t gemm_mode;   /* 0: X as CSR (and the CSR of X^T), 1: X dense                           */
+    int32_t N_adj;       /* rows of the adjacency, of G and of grad_input                          */
+    int32_t M_adj;       /* columns of the adjacency = rows of X; must equal N_adj                 */
+    int32_t M_fea;       /* columns of X = rows of W                                               */
+    int32_t P_w;         /* columns of W and of G                                                  */
+    int32_t dtype_adj;   /* sgx_dtype of values_adj                                                */
+    int32_t dtype_x;     /* sgx_dtype of the dense X (gemm_mode 1); CSR feature values are fp32    */
+    int32_t gat_heads;   /* 0 or 1; more: SGX_ERR_UNSUPPORTED                                      */
+    float   alpha;       /* LeakyReLU slope                                                        */
+    int64_t nnz_adj;     /* stored entries of the adjacency (sizes the per-entry scratch)          */
+
+    const int32_t *rowPtr_adj;        /* [N_adj+1]                                                 */
+    const int32_t *columnIndex_adj;   /* [nnz_adj]                                                 */
+    const void    *values_adj;        /* [nnz_adj] in dtype_adj                                    */
+    const sgx_plan *plan_adj;         /* optional: the schedule of P . G                           */
+
+    const void    *X;                 /* gemm_mode 1: [M_adj][ldx] in dtype_x                      */
+    int64_t        ldx;
+    const int32_t *rowPtr_fea;        /* gemm_mode 0, GAT: the CSR of X, fp32 values (Wh = X . W)  */
+    const int32_t *columnIndex_fea;
+    const float   *values_fea;
+    const sgx_plan *plan_fea;         /* optional                                                  */
+    const int32_t *rowPtr_xt;         /* gemm_mode 0: the CSR of X^T [M_fea] x [M_adj], fp32       */
+    const int32_t *columnIndex_xt;
+    const float   *values_xt;
+    const sgx_plan *plan_xt;          /* optional                                                  */
+
+    const float   *W;                 /* the fp32 weight parameter [M_fea][P_w] (not transposed)   */
+    const float   *G;                 /* grad_output [N_adj][ldg] fp32                             */
+    int64_t        ldg;
+    const float   *E;                 /* GAT, form 1: the forward's per-entry outputs [nnz_adj]    */
+    const float   *S;
+    const sgx_gat_stats *stats;       /* GAT, form 2: the forward's row statistics                 */
+    float          dead_weight;       /* form 2: S on the stored entries of a dead row             */
+    const uint8_t *dead;              /* optional [N_adj]: 1 = the forward's dead rows             */
+
+    float         *grad_weights;      /* out [M_fea][P_w]                                          */
+    float         *grad_attention;    /* out [2 P_w], GAT only                                     */
+    float         *grad_input;        /* out [N_adj][ld_gi], pad columns zeroed; NULL = not formed */
+    int64_t        ld_gi;
+
+    void          *workspace;         /* sgx_layer_backward_workspace_bytes(d), 256-byte aligned   */
+    size_t         workspace_bytes;
+} sgx_layer_grad_desc;
+
+/* 0 for a descriptor the call refuses (workspace and workspace_bytes are not looked at) */
+size_t sgx_layer_backward_workspace_bytes(const sgx_layer_grad_desc *d);
+int    sgx_layer_backward(const sgx_layer_grad_desc *d, void *stream);
+
+/* The attention gradient of the GAT backward from the edge pass's outputs, without a transposed pattern:
+ *     grad_attention[0:F]  = Wh^T g1            = sum_r g1[r] Wh[r]
+ *     grad_attention[F:2F] = Wh^T colsum(sg)    = sum_r t_r,   t_r[f] = sum_{e in row r} sg_e Wh[col_e][f]
+ * t_r is an fp32 fma chain over the row's stored entries in CSR order from 0; a row over 256 entries is cut into chunks
+ * of 256 entries, each such a chain, whose sums are added in chunk order.  Rows of Wh are gathered through a range-checked
+ * buffer, 16 bytes per lane when Wh is 16-byte aligned and ldw a multiple of 4, one element at a time otherwise.
+ * Grid rule: slices = min(max(ceil(n_rows / 64), 1), 1024) workgroups of 256 threads whatever the device; workgroup b owns
+ * rows [b R, (b+1) R), R = ceil(n_rows / slices).  Its 4 * 64 / L lane groups (L = the power of two >= ceil(F / 4), at most
+ * 64) take rows b R + k, b R + k + 256 / L, ... in ascending order and add g1[r] Wh[r] and t_r into registers; the groups'
+ * sums are added in group order, then the rows over 256 entries in ascending order, and stored to the workgroup's slice
+ * (plain loads and stores, no atomics); a second launch adds the slices in slice order.  The same bits on every run and
+ * every device.  n_rows <= n_cols (row r of the adjacency is node r of Wh).  workspace:
+ * sgx_gat_attention_grad_workspace_bytes(n_rows, F) bytes (slices x 2 F floats), 256-byte aligned.  n_rows == 0, or a
+ * matrix without entries and g1 = 0: both halves are exactly 0. */
+size_t sgx_gat_attention_grad_workspace_bytes(int n_rows, int n_feat);
+int sgx_gat_attention_grad(int n_rows, int n_cols, int n_feat, const int32_t *rowPtr, const int32_t *columnIndex,
+                           const float *sg, const float *g1, const float *Wh, int64_t ldw, float *grad_attention,
+                           void *workspace, size_t workspace_bytes, void *stream);
+
 /* A plain streaming copy (16 bytes per lane, non-temporal, each workgroup on a contiguous chunk), the kernel the attainable HBM rate of a device is
  * measured with next to the nominal 8 TB/s (bench.py reports it as roofline.stream_copy_GBps_this_device).
  * bytes must be a multiple of 16, both pointers 16-byte aligned. */

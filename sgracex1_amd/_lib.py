@@ -43,6 +43,8 @@ SYMBOLS = [
     "sgx_collate_graphs", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
     "sgx_gat_aggregate_stats", "sgx_layer_forward_stats", "sgx_gat_edge_outputs", "sgx_gat_backward_edges_stats",
     "sgx_node_batch_workspace_bytes", "sgx_node_batch_sample",
+    "sgx_layer_backward_workspace_bytes", "sgx_layer_backward", "sgx_gat_attention_grad_workspace_bytes",
+    "sgx_gat_attention_grad",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -194,6 +196,28 @@ class NodeBatch(ctypes.Structure):
     ]
 
 
+class LayerGradDesc(ctypes.Structure):
+    """struct sgx_layer_grad_desc -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("gat_mode", ctypes.c_int32), ("gemm_mode", ctypes.c_int32), ("N_adj", ctypes.c_int32), ("M_adj", ctypes.c_int32),
+        ("M_fea", ctypes.c_int32), ("P_w", ctypes.c_int32), ("dtype_adj", ctypes.c_int32), ("dtype_x", ctypes.c_int32),
+        ("gat_heads", ctypes.c_int32), ("alpha", ctypes.c_float), ("nnz_adj", ctypes.c_int64),
+        ("rowPtr_adj", ctypes.c_void_p), ("columnIndex_adj", ctypes.c_void_p), ("values_adj", ctypes.c_void_p),
+        ("plan_adj", ctypes.c_void_p),
+        ("X", ctypes.c_void_p), ("ldx", ctypes.c_int64),
+        ("rowPtr_fea", ctypes.c_void_p), ("columnIndex_fea", ctypes.c_void_p), ("values_fea", ctypes.c_void_p),
+        ("plan_fea", ctypes.c_void_p),
+        ("rowPtr_xt", ctypes.c_void_p), ("columnIndex_xt", ctypes.c_void_p), ("values_xt", ctypes.c_void_p),
+        ("plan_xt", ctypes.c_void_p),
+        ("W", ctypes.c_void_p), ("G", ctypes.c_void_p), ("ldg", ctypes.c_int64),
+        ("E", ctypes.c_void_p), ("S", ctypes.c_void_p), ("stats", ctypes.POINTER(GatStats)), ("dead_weight", ctypes.c_float),
+        ("dead", ctypes.c_void_p),
+        ("grad_weights", ctypes.c_void_p), ("grad_attention", ctypes.c_void_p), ("grad_input", ctypes.c_void_p),
+        ("ld_gi", ctypes.c_int64),
+        ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -337,6 +361,14 @@ def _load():
     lib.sgx_node_batch_workspace_bytes.restype = sz
     lib.sgx_node_batch_sample.argtypes = [ctypes.POINTER(NodeBatch), vp]
     lib.sgx_node_batch_sample.restype = c_int
+    lib.sgx_layer_backward_workspace_bytes.argtypes = [ctypes.POINTER(LayerGradDesc)]
+    lib.sgx_layer_backward_workspace_bytes.restype = sz
+    lib.sgx_layer_backward.argtypes = [ctypes.POINTER(LayerGradDesc), vp]
+    lib.sgx_layer_backward.restype = c_int
+    lib.sgx_gat_attention_grad_workspace_bytes.argtypes = [c_int, c_int]
+    lib.sgx_gat_attention_grad_workspace_bytes.restype = sz
+    lib.sgx_gat_attention_grad.argtypes = [c_int, c_int, c_int, vp, vp, vp, vp, vp, c_i64, vp, vp, sz, vp]
+    lib.sgx_gat_attention_grad.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

@@ -18,8 +18,11 @@ _FLAGS = {
     # -- where and how a layer runs ------------------------------------------------------------
     "device": ("cuda", "torch device of the tensors; the accelerator is the GPU itself"),
     "acc": (1, "forward path: 1 = HIP kernels, 0 = the dense torch formulation (parity twin)"),
-    "accb": (0, "backward offload register path of the GAT bitstream (gemm_mode 2): not offered; "
-                "backward always runs on the device kernels"),
+    "accb": (0, "backward path of a layer that ran with acc = 1: 0 = composed from the stage kernels by the autograd "
+                "function, 1 = the whole layer backward as one call of the C ABI (sgx_layer_backward) on the same kernels "
+                "with the arithmetic of accb = 0.  The reference's accb = 1 branch (gemm_mode 2) quantises the gradient "
+                "operands with constants of its bitstream and returns no attention gradient: neither is reproduced.  "
+                "Ignored with acc = 0"),
     "compute_attention": (0, "0 = GCN aggregate A.H, 1 = single-head GAT edge softmax (register gat_mode)"),
     "gat_edge_outputs": (1, "GAT training on the kernels: 1 = the forward writes the per-edge outputs E and S and keeps them "
                             "for the backward (the bitstream's E / S ports); 0 = it keeps the row softmax statistics "

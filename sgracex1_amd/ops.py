@@ -828,6 +828,104 @@ def gat_backward_edges_stats(adj, stats, G, Wh, alpha=0.2, dead=None, dead_weigh
     return sg, g1, S
 
 
+def gat_attention_grad(adj, sg, g1, Wh):
+    """[Wh^T g1 ; Wh^T colsum(sg)] fp32 [2 F] from the edge pass's outputs, gathered over the stored entries in row order
+    (sgx_gat_attention_grad): no transposed pattern; the same bits on every run."""
+    _dev2d(Wh, "Wh")
+    if sg.dtype != torch.float32 or g1.dtype != torch.float32 or Wh.dtype != torch.float32:
+        raise TypeError("gat_attention_grad works on float32 sg, g1, Wh")
+    if Wh.shape[0] != adj.n_cols or adj.n_rows > adj.n_cols or g1.numel() != adj.n_rows or sg.numel() < adj.nnz:
+        raise ValueError("Wh must be [adj.n_cols, F], g1 [adj.n_rows], sg [nnz], n_rows <= n_cols")
+    F = Wh.shape[1]
+    out = torch.empty(2 * F, dtype=torch.float32, device=Wh.device)
+    nbytes = lib.sgx_gat_attention_grad_workspace_bytes(adj.n_rows, F)
+    ws = _workspace(Wh.device, nbytes)
+    check(lib.sgx_gat_attention_grad(adj.n_rows, adj.n_cols, F, _ptr(adj.rowptr), _ptr(adj.col), _ptr(sg), _ptr(g1), _ptr(Wh),
+                                     Wh.stride(0), _ptr(out), _ptr(ws), ws.numel(), _stream()), "sgx_gat_attention_grad")
+    return out
+
+
+def feature_csr32(x):
+    """The fp32 CSR of a feature tensor and of its transpose, each built once per tensor (cached on it, as the forward's
+    fea_csr is): what the one-call backward reads in gemm_mode 0 instead of a dense X."""
+    def build():
+        d = x.detach()
+        return Csr.from_dense(d if d.layout == torch.strided else d.to_dense(), torch.float32)     # (as the forward builds it)
+
+    Xc = cached_on(x, ("fea_csr", torch.float32), build)
+    return Xc, cached_on(x, ("fea_csr_t", torch.float32), lambda: csr_transpose(Xc))
+
+
+def layer_backward(adj, X, W, G, gat=False, gemm_mode=1, alpha=0.2, E=None, S=None, stats=None, dead_weight=0.0, dead=None,
+                   mask=None, want_grad_input=True):
+    """The SGRACE layer's backward in one call (sgx_layer_backward): -> (grad_input [n, M] or None, grad_weights [M, P],
+    grad_attention [2 P] or None), fp32.  adj: the forward's adjacency (GCN: its values are P); X: the layer's input -- a
+    dense fp16|fp32 tensor (gemm_mode 1) or, gemm_mode 0, the feature tensor whose CSRs feature_csr32 caches (or that pair
+    itself): never made dense; W [M, P] fp32; G = grad_output [n, P] fp32.  GAT: E and S, or stats with dead_weight; dead (bool [n]) the
+    forward's dead rows; mask: the Csr whose values the edge pass masks with (default adj).  want_grad_input False: that
+    product is not launched."""
+    _dev2d(G, "G")
+    _dev(W, "W")
+    if G.dtype != torch.float32 or W.dtype != torch.float32:
+        raise TypeError("the backward runs in float32: G and W must be float32")
+    n, (M, P) = adj.n_rows, W.shape
+    if adj.n_cols != n or G.shape != (n, P):
+        raise ValueError("the adjacency must be square and G [n, P]")
+    d = _lib.LayerGradDesc()
+    d.gat_mode, d.gemm_mode, d.N_adj, d.M_adj, d.M_fea, d.P_w = int(bool(gat)), int(gemm_mode), n, n, M, P
+    d.gat_heads, d.alpha, d.nnz_adj = 1, float(alpha), adj.nnz
+    vals = (mask if (gat and mask is not None) else adj).val
+    d.dtype_adj = dtype_code(vals.dtype)
+    d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), vals.data_ptr()
+    keep = [vals]
+    plan = adj.plan if adj.wants_plan else None
+    d.plan_adj = plan.handle if plan is not None else None
+    if gemm_mode == 1:
+        _dev2d(X, "X")
+        if X.shape != (n, M):
+            raise ValueError("X must be [n, M]")
+        d.dtype_x, d.X, d.ldx = dtype_code(X.dtype), X.data_ptr(), X.stride(0)
+    else:
+        Xc, Xt = X if isinstance(X, tuple) else feature_csr32(X)
+        if (Xc.n_rows, Xc.n_cols) != (n, M):
+            raise ValueError("X must be [n, M]")
+        d.dtype_x = SGX_F32
+        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = Xc.rowptr.data_ptr(), Xc.col.data_ptr(), Xc.val.data_ptr()
+        d.rowPtr_xt, d.columnIndex_xt, d.values_xt = Xt.rowptr.data_ptr(), Xt.col.data_ptr(), Xt.val.data_ptr()
+        d.plan_fea = Xc.plan.handle if Xc.wants_plan else None
+        d.plan_xt = Xt.plan.handle if Xt.wants_plan else None
+        keep += [Xc, Xt]
+    d.W, d.G, d.ldg = W.data_ptr(), G.data_ptr(), G.stride(0)
+    grad_attention = None
+    if gat:
+        if stats is not None:
+            st = stats.struct()
+            d.stats, d.dead_weight = ctypes.pointer(st), float(dead_weight)
+        else:
+            E, S = _dev(E, "E"), _dev(S, "S")
+            if E.dtype != torch.float32 or S.dtype != torch.float32:
+                raise TypeError("E and S are float32")
+            d.E, d.S = E.data_ptr(), S.data_ptr()
+        if dead is not None:
+            _dev(dead, "dead")
+            if dead.dtype != torch.bool or dead.shape != (n,):
+                raise ValueError("dead must be a bool [n] tensor")
+            d.dead = dead.data_ptr()                      # (a bool tensor is one byte of 0 / 1 per element)
+        grad_attention = torch.empty(2 * P, dtype=torch.float32, device=G.device)
+        d.grad_attention = grad_attention.data_ptr()
+    grad_weights = torch.empty((M, P), dtype=torch.float32, device=G.device)
+    d.grad_weights = grad_weights.data_ptr()
+    grad_input = None
+    if want_grad_input:
+        grad_input = torch.empty((n, table_pitch(M, 4)), dtype=torch.float32, device=G.device)
+        d.grad_input, d.ld_gi = grad_input.data_ptr(), grad_input.stride(0)
+    nbytes = lib.sgx_layer_backward_workspace_bytes(ctypes.byref(d))
+    ws = _workspace(G.device, nbytes)
+    d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(lib.sgx_layer_backward(ctypes.byref(d), _stream()), "sgx_layer_backward")
+    return (None if grad_input is None else grad_input[:, :M]), grad_weights, grad_attention
+
+
 def readout_mean_linear(x, graph_ptr, weight=None, bias=None, want_pooled=False):
     """global_mean_pool over contiguous graphs + Linear head in one launch (sgx_readout_mean_linear).
     x [n, F] fp16|fp32, graph_ptr int32 [n_graphs+1], weight [C, F] fp32, bias [C] fp32."""

@@ -26,6 +26,10 @@ N x N matrices: grad_input = P @ (g @ W^T), grad_weights = X^T @ (P @ g) with P 
 matrix (GAT) or adj (GCN) -- like the reference, P and not P^T -- and for GAT the attention-vector
 gradient through softmax and LeakyReLU.  A GAT row without a positive entry in the adjacency the forward masked
 with (the quantised one in quantised mode) has P = 1/N on all N columns, not only on its stored entries.
+
+`config.accb == 1` (with `config.acc == 1`) runs that backward as ONE call of the C ABI, sgx_layer_backward: the same
+arithmetic on the same kernels, the attention gradient gathered in row order instead of through a transposed pattern, a
+CSR feature matrix never made dense, and grad_input left out when the input needs no gradient.
 """
 import torch
 import torch.nn.functional as F
@@ -104,6 +108,20 @@ def _fq_unsigned(x, s, z, qbits):
     return q / 2 if qbits == 1 else q / (2 ** (qbits - 1))
 
 
+def _lean_mask(ctx, A):
+    """The values array the statistics form of the edge pass masks with (see FPYNQ_GAT.backward): the adjacency the forward
+    masked with, or -- quantised, with dead rows -- that array with the dead rows' unquantised values; composed once."""
+    M = ctx.masked
+    if M is not A and ctx.dead is not None:
+        if getattr(M, "_lean_values", None) is None:
+            deg = (A.rowptr[1:] - A.rowptr[:-1]).long()
+            row = torch.repeat_interleave(torch.arange(A.n_rows, device=A.val.device), deg, output_size=A.nnz)
+            M._lean_values = ops.Csr(A.rowptr, A.col, torch.where(ctx.dead[row], A.val[:A.nnz], M.val[:A.nnz]).contiguous(),
+                                     A.n_cols)
+        M = M._lean_values
+    return M
+
+
 class FPYNQ_GAT(torch.autograd.Function):
     @staticmethod
     def forward(ctx, my_ip, self, adj, nnz_adj, input, weights, attention, out_features, dropout, relu):
@@ -135,6 +153,11 @@ class FPYNQ_GAT(torch.autograd.Function):
                     fea if fea.layout == torch.strided else fea.to_dense(), dt))
             else:
                 fea = fea.to(dt).contiguous()
+            # config.accb = 1: the backward as one call (sgx_layer_backward); its fp32 CSRs of X and X^T are built here,
+            # once per feature tensor, so that the backward itself builds nothing
+            ctx.accb, ctx.gemm_mode = int(config.accb), int(rm.gemm_mode)
+            if ctx.accb == 1 and ctx.gemm_mode == 0:
+                ctx.fea32 = ops.feature_csr32(input)
             my_ip.alpha = self.alpha
             # config.hardware_quantize: the bitstream's own quantiser -- integer operands on the int8 matrix cores where
             # they are the faster form (dense features wider than 128 columns; sgx.h SGX_QUANT_INT8_AUTO);
@@ -221,6 +244,24 @@ class FPYNQ_GAT(torch.autograd.Function):
             return none, none, none, none, grad_input, grad_weights, grad_attention, none, none, none
 
         saved = ctx.saved_tensors
+        if getattr(ctx, "accb", 0) == 1:
+            # one call on the same kernels (include/sgx.h, sgx_layer_backward): no transposed pattern, a CSR X stays CSR,
+            # grad_input only when the input wants it
+            A, kw = ctx.csr, {}
+            if ctx.gat:
+                if ctx.lean:
+                    kw = dict(stats=ops.GatStats.of(*saved[3:7]), mask=_lean_mask(ctx, A),
+                              dead_weight=1.0 / A.n_cols if ctx.dead is not None else 0.0)
+                else:
+                    kw = dict(E=saved[3], S=saved[4])
+                kw.update(dead=ctx.dead, alpha=ctx.alpha)
+            X = ctx.fea32 if ctx.gemm_mode == 0 else saved[0].float().contiguous()
+            grad_input, grad_weights, ga = ops.layer_backward(A, X, saved[1].float().contiguous(), g.contiguous(), gat=bool(ctx.gat),
+                                                              gemm_mode=ctx.gemm_mode, want_grad_input=ctx.needs_input_grad[4], **kw)
+            if grad_input is not None and grad_input.stride(0) != grad_input.shape[1]:
+                grad_input = grad_input.contiguous()
+            grad_attention = ga.unsqueeze(1) if ctx.gat else torch.zeros((2 * saved[1].shape[1], 1), device=g.device)
+            return none, none, none, none, grad_input, grad_weights, grad_attention, none, none, none
         input, weights, out = saved[0].float(), saved[1].float(), saved[2]
         if input.layout != torch.strided:
             input = input.to_dense()
@@ -232,14 +273,7 @@ class FPYNQ_GAT(torch.autograd.Function):
                 # (SG.py masks with the UNquantised adjacency).  Unquantised they are the same array.  Quantised, a live row
                 # takes the quantised values (an entry that rounded to 0 had S = 0, so its sg is 0 under either mask) and a
                 # dead row -- uniform weight whatever the values -- the unquantised ones, whose mask is the one that shows.
-                M = ctx.masked
-                if M is not A and ctx.dead is not None:
-                    if getattr(M, "_lean_values", None) is None:
-                        deg = (A.rowptr[1:] - A.rowptr[:-1]).long()
-                        row = torch.repeat_interleave(torch.arange(A.n_rows, device=g.device), deg, output_size=A.nnz)
-                        M._lean_values = ops.Csr(A.rowptr, A.col, torch.where(ctx.dead[row], A.val[:A.nnz], M.val[:A.nnz]).contiguous(),
-                                                 A.n_cols)
-                    M = M._lean_values
+                M = _lean_mask(ctx, A)
                 sg, g1, S = ops.gat_backward_edges_stats(M, ops.GatStats.of(*saved[3:7]), g.contiguous(), Wh, ctx.alpha,
                                                          dead=ctx.dead, dead_weight=1.0 / A.n_cols if ctx.dead is not None else 0.0)
             else:

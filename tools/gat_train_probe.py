@@ -4,6 +4,11 @@ uniform and R-MAT degrees as tools/gat_probe.py builds them), with the per-edge 
 (config.gat_edge_outputs = 1, the default) and with the row softmax statistics instead (0, "lean"):
 
     python3 tools/gat_train_probe.py [--legs default,lean] [--label NAME] [--repeats 30] [--tree DIR]
+                                     [--accb 0,1] [--gat 0] [--steps-only]
+
+  --accb       config.accb of the step, a comma list run in that order (0,1,0,1 interleaves the two): 0 = the backward
+               composed from stage calls, 1 = the one call (sgx_layer_backward); a tree without the call ignores 1
+  --gat 0      the GCN aggregate instead of the edge softmax (the step only); --steps-only: no 8-head aggregates
 
   step   GATConv_SGRACE(128, 256), one head, dense features: forward + backward of FPYNQ_GAT, fp32 and fp16 storage
   agg8   ops.gat_aggregate at 8 heads x 32 columns, forward alone (there is no multi-head backward): with E / S as a
@@ -47,6 +52,9 @@ def main():
     ap.add_argument("--legs", default="default,lean")
     ap.add_argument("--label", default="this_commit")
     ap.add_argument("--repeats", type=int, default=30)
+    ap.add_argument("--accb", default="0", help="config.accb of the training step, a comma list: 0 = composed, 1 = one call")
+    ap.add_argument("--gat", type=int, default=1, choices=[0, 1], help="0: the GCN aggregate instead (steps only)")
+    ap.add_argument("--steps-only", action="store_true", help="the training step alone, not the 8-head aggregates")
     ap.add_argument("--tree", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.tree))
@@ -66,11 +74,12 @@ def main():
         for dt, npdt in ((torch.float32, np.float32), (torch.float16, np.float16)):
             A = A32.to(dt)
             A.gat_plan, A.plan
-            for leg in a.legs.split(","):
+            for leg, accb in [(l, int(b)) for l in a.legs.split(",") for b in a.accb.split(",")]:
                 flag = {"default": 1, "lean": 0}[leg]
                 old = config.snapshot()
                 try:
-                    config.acc, config.compute_attention, config.device, config.float_type = 1, 1, "cuda", npdt
+                    config.acc, config.compute_attention, config.device, config.float_type = 1, a.gat, "cuda", npdt
+                    config.accb = accb
                     config.fake_quantization, config.w_qbits = 0, 32
                     config.gat_edge_outputs = flag
                     sgrace.init_SGRACE()
@@ -80,14 +89,17 @@ def main():
                     def step():
                         x = X.detach().requires_grad_(True)
                         layer.zero_grad(set_to_none=True)
-                        layer(1, 1, 0, x, None, A.val, A).backward(G)          # (A is of the layer's type: no copy per step)
+                        layer(a.gat, 1, 0, x, None, A.val, A).backward(G)          # (A is of the layer's type: no copy per step)
 
                     res = timed(step, a.repeats)
                 finally:
                     config.restore(old)
                     sgrace.init_SGRACE()
-                base = dict(label=a.label, graph=gname, nodes=n, edges=A.nnz, dtype=str(dt).split(".")[1], leg=leg)
+                base = dict(label=a.label, graph=gname, nodes=n, edges=A.nnz, dtype=str(dt).split(".")[1], leg=leg, accb=accb,
+                            gat=a.gat)
                 print(json.dumps(dict(base, what="step_1x256_fwd_bwd", **res)), flush=True)
+                if a.steps_only or not a.gat:
+                    continue
                 Whd, attd = Wh.to(dt), att8.to(dt)
                 D = torch.empty((n, P), dtype=dt, device=dev)
                 forms = {"default": (("agg8_with_E_S", dict(want_edge_outputs=True)), ("agg8_no_side_outputs", {})),

@@ -14,6 +14,9 @@ of examples/sgrace_node_classification.py (GCN and GAT).  One JSON line per meas
                                                    # preparation alone, device launches against the torch ops
                                                    # (profiles/r08_node_batch.jsonl).  --arms default: on a tree without
                                                    # the prepared loader.  --trace: few steps, for rocprofv3 --kernel-trace
+                                                   # --accb 0,1: config.accb of the step (the layer backward composed /
+                                                   # as one call), every (arm, accb) pair a leg of the same windows
+                                                   # (profiles/r09_layer_backward.jsonl); --label NAME tags the run
 """
 import argparse
 import json
@@ -123,7 +126,7 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e3, out
 
 
-def node_batch(arms, trace):
+def node_batch(arms, trace, accbs=(0,)):
     """The training step (loader, forward, loss, backward, Adam) per loader, and the preparation alone."""
     import importlib.util
     import statistics
@@ -164,14 +167,17 @@ def node_batch(arms, trace):
             config.acc, config.device, config.compute_attention = 1, "cuda", attention
             sgrace.init_SGRACE()
             steps = {}
-            for arm in arms:
+            # a leg = (loader arm, config.accb): every leg has its own model and takes its turn in every window
+            legs = [(arm, accb) for arm in arms for accb in accbs]
+            for arm, accb in legs:
                 torch.manual_seed(0)
                 model = sgrace.GAT_PYNQ(x.shape[1], 16, 1, 5).to(dev)
                 opt = torch.optim.Adam(model.parameters(), lr=0.01)
                 crit = torch.nn.CrossEntropyLoss()
                 state = {"it": iter(loaders[arm])}
 
-                def step(arm=arm, model=model, opt=opt, crit=crit, state=state):
+                def step(arm=arm, model=model, opt=opt, crit=crit, state=state, accb=accb):
+                    config.accb = accb                          # read by the layers' forward, which fixes the backward's path
                     try:
                         b = next(state["it"])
                     except StopIteration:
@@ -187,24 +193,25 @@ def node_batch(arms, trace):
                     loss.backward()
                     opt.step()
                     return b
-                steps[arm] = step
+                steps[(arm, accb)] = step
             windows, reps = (1, 3) if trace else (7, 30)
-            times = {arm: [] for arm in arms}
-            for arm in arms:                                    # warm-up of every arm before any timed window
+            times = {leg: [] for leg in legs}
+            for leg in legs:                                    # warm-up of every leg before any timed window
                 for _ in range(5):
-                    b = steps[arm]()
+                    b = steps[leg]()
             torch.cuda.synchronize()
-            for _ in range(windows):                            # the arms interleaved, window by window
-                for arm in arms:
+            for _ in range(windows):                            # the legs interleaved, window by window
+                for leg in legs:
                     t0 = time.perf_counter()
                     for _ in range(reps):
-                        b = steps[arm]()
+                        b = steps[leg]()
                     torch.cuda.synchronize()
-                    times[arm].append((time.perf_counter() - t0) / reps * 1e3)
-            for arm in arms:
-                v = times[arm]
+                    times[leg].append((time.perf_counter() - t0) / reps * 1e3)
+            config.accb = 0
+            for arm, accb in legs:
+                v = times[(arm, accb)]
                 print(json.dumps({"end_to_end": "mini-batch training step (loader + forward + loss + backward + Adam)",
-                                  "loader": arm, "model": "GAT" if attention else "GCN", "graph": name, "batch": bs,
+                                  "loader": arm, "accb": accb, "model": "GAT" if attention else "GCN", "graph": name, "batch": bs,
                                   "fanouts": fan, "batch_nodes_last": b.num_nodes, "step_ms_median": round(statistics.median(v), 4),
                                   "step_ms_min": round(min(v), 4), "step_ms_max": round(max(v), 4), "windows": windows,
                                   "steps_per_window": reps}), flush=True)
@@ -243,11 +250,16 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--node-batch", action="store_true")
+    ap.add_argument("--accb", default="0", help="--node-batch: config.accb of the training steps, a comma list (0,1 times "
+                                                "both settings in the same interleaved windows)")
+    ap.add_argument("--label", default=None, help="--node-batch: a tag printed with the run (which checkout this is)")
     ap.add_argument("--arms", default="default,prepared")
     ap.add_argument("--trace", action="store_true")
     a = ap.parse_args()
     if a.node_batch:
-        return node_batch(a.arms.split(","), a.trace)
+        if a.label:
+            print(json.dumps({"label": a.label}), flush=True)
+        return node_batch(a.arms.split(","), a.trace, tuple(int(b) for b in a.accb.split(",")))
     dev = torch.device("cuda")
     shapes = [("products shape uniform", lambda: graphs.uniform_graph(2_450_000, 122_000_000, dtype=torch.float32,
                                                                       normalize=False)),
