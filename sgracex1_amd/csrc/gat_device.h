@@ -1,4 +1,4 @@
-// Device-side pieces shared by the GAT aggregate's kernels (gat.hip, gat_scan.hip).
+// Device-side pieces shared by the GAT aggregate's kernels (gat.hip and the forms behind it, gat_*.hip).
 #pragma once
 #include "sgx_device.h"
 

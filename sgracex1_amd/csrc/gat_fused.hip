@@ -1,6 +1,6 @@
 // The GAT aggregate in ONE walk over the rows, with no per-edge score gather (round 3; used when the caller wants no E / S):
 //     D_i = act( sum_j softmax_j(LeakyReLU(s1_i + Wh_j . a2)) Wh_j )                       (SG.py:634-661)
-// The two-stage form (gat.hip) spends its first stage gathering 4 bytes of s2 per stored entry -- one L2 line request
+// The two-stage form (gat_alpha.hip, gat_weighted.hip) spends its first stage gathering 4 bytes of s2 per stored entry -- one L2 line request
 // each, the rate that bounds it -- to weight rows that its second stage gathers anyway.  Here a lane group gathers a
 // piece of 8 neighbour rows (16 bytes per lane, the spmm_csr.hip layout), forms their second-half scores FROM the
 // gathered rows (8 fmas per lane and row against the attention fragment of the lane's columns, summed over the lanes

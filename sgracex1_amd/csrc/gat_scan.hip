@@ -9,7 +9,7 @@
 // The rows of the range: the next row starts, 64 at a time, each marked at its first entry's slot in LDS; a maximum scan
 // of the marks gives every entry its row.  Per head: the running maximum within rows (segmented scan over the lanes with
 // row_shr / row_bcast DPP steps, carried from chunk to chunk), the row total handed back to every entry of the row,
-// exp(x - m), the same for the sum, and the weights.  Rows over kScanMaxRow entries stay with the plan's tasks (gat.hip).
+// exp(x - m), the same for the sum, and the weights.  Rows over kScanMaxRow entries stay with the plan's tasks (gat_alpha.hip).
 // Numerics: the maximum is exact; the sum is added in scan order instead of the register pass's lane order, so a weight
 // may differ from that pass's in the last bits (tests/test_gpu_gat_scan.py states the bound against an fp64 softmax).
 #include "gat_device.h"

@@ -169,14 +169,14 @@ int sgx_gat_stats_check(const sgx_gat_stats *st, int n_cols, int n_heads)
     return SGX_OK;
 }
 
-// the statistics of an aggregate that has just run on `s_scratch` (its scores: s1 [n_cols][n_heads], then s2 likewise)
+// the statistics of an aggregate that has just run on `s_scratch`, laid out as `lay` (its scores: s1, s2 [n_cols][n_heads])
 int sgx_gat_row_stats(int dtype, int n_rows, int n_cols, int n_heads, float alpha, const int32_t *rowPtr,
-                      const int32_t *columnIndex, const void *values, const float *s_scratch, const sgx_gat_stats *st,
-                      hipStream_t stream)
+                      const int32_t *columnIndex, const void *values, const float *s_scratch, const sgx_gat_scratch &lay,
+                      const sgx_gat_stats *st, hipStream_t stream)
 {
     if (n_heads < 1) n_heads = 1;
     if (n_rows <= 0) return SGX_OK;
-    const float *s1 = s_scratch, *s2 = s_scratch + (size_t)n_cols * n_heads;
+    const float *s1 = s_scratch + lay.s1, *s2 = s_scratch + lay.s2;
     SGX_HIP_CHECK(hipMemcpyAsync(st->score_row, s1, (size_t)n_rows * n_heads * sizeof(float), hipMemcpyDeviceToDevice, stream));
     SGX_HIP_CHECK(hipMemcpyAsync(st->score_col, s2, (size_t)n_cols * n_heads * sizeof(float), hipMemcpyDeviceToDevice, stream));
     const unsigned s2_bytes = (unsigned)((size_t)n_cols * n_heads * 4);
@@ -221,8 +221,8 @@ extern "C" int sgx_gat_aggregate_stats(int dtype, int relu, int n_rows, int n_co
                                         values, Wh, ldh, attention, D, ldd, nullptr, nullptr, plan, s_scratch, (hipStream_t)stream,
                                         0.0f, fill, (int)n_nodes);
     if (rc != SGX_OK) return rc;
-    return sgx_gat_row_stats(dtype, n_rows, n_cols, n_heads, alpha, rowPtr, columnIndex, values, s_scratch, stats,
-                             (hipStream_t)stream);
+    return sgx_gat_row_stats(dtype, n_rows, n_cols, n_heads, alpha, rowPtr, columnIndex, values, s_scratch,
+                             sgx_gat_scratch_layout(n_cols, n_feat, n_heads, fill_dead_rows, plan), stats, (hipStream_t)stream);
 }
 
 extern "C" int sgx_gat_edge_outputs(int dtype_values, int n_rows, int n_cols, int n_heads, float alpha,

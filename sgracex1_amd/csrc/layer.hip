@@ -232,12 +232,13 @@ int layer_forward(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *str
         // heads of 32 columns: the scores themselves; wider heads: a partial per 64-column group, added up by a small kernel
         const int heads = d->gat_heads < 1 ? 1 : d->gat_heads;
         float *gs = (float *)(ws + c.g_off);
+        const sgx_gat_scratch lay = sgx_gat_scratch_layout(d->M_adj, d->P_w, heads, d->gat_fill_dead_rows, d->plan_adj);
         const bool direct = d->P_w / heads == 32;
-        float *s1 = direct ? gs : sgx_gat_score_partials(gs, d->M_adj, d->P_w, heads, d->gat_fill_dead_rows);
-        float *s2 = s1 ? s1 + (size_t)d->M_adj * (direct ? heads : d->P_w / 64) : nullptr;
-        rc = s1 ? sgx_xw_dense_scores(d->M_adj, d->M_fea, d->P_w, values_fea, d->M_fea, B, d->M_fea, H, ldh, attention, heads, s1, s2, s)
-                : SGX_ERR_UNSUPPORTED;
-        if (rc == SGX_OK && !direct) rc = sgx_gat_scores_combine(gs, d->M_adj, d->P_w, heads, d->gat_fill_dead_rows, s);
+        float *s1 = gs + (direct ? lay.s1 : lay.sp1), *s2 = gs + (direct ? lay.s2 : lay.sp2);
+        rc = (direct || lay.has_partials)
+                 ? sgx_xw_dense_scores(d->M_adj, d->M_fea, d->P_w, values_fea, d->M_fea, B, d->M_fea, H, ldh, attention, heads, s1, s2, s)
+                 : SGX_ERR_UNSUPPORTED;
+        if (rc == SGX_OK && !direct) rc = sgx_gat_scores_combine(gs, lay, d->M_adj, d->P_w, heads, s);
         if (rc == SGX_OK) scores_ready = 1;
         else if (rc != SGX_ERR_UNSUPPORTED) return rc;
     }
@@ -273,7 +274,8 @@ int layer_forward(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *str
                                   (float *)(ws + c.g_off), s, ep_d.out_scale, nullptr, 0, scores_ready);
         if (rc == SGX_OK && stats)      // from the scores the aggregate has just used (of the quantised operands, if any)
             rc = sgx_gat_row_stats(d->dtype, d->N_adj, d->M_adj, d->gat_heads, d->alpha, d->rowPtr_adj, d->columnIndex_adj,
-                                   values_adj, (const float *)(ws + c.g_off), stats, s);
+                                   values_adj, (const float *)(ws + c.g_off),
+                                   sgx_gat_scratch_layout(d->M_adj, d->P_w, d->gat_heads, d->gat_fill_dead_rows, d->plan_adj), stats, s);
     } else {
         rc = sgx_spmm_launch(d->dtype, d->acc_mode, d->spmm_block, d->relu, d->N_adj, d->M_adj, d->P_w,
                              d->rowPtr_adj, d->columnIndex_adj, values_adj, H, ldh, d->D, d->P_w, d->plan_adj,

@@ -1,4 +1,4 @@
-// Device-side helpers shared by the aggregation kernels (spmm_csr.hip, gat.hip).
+// Device-side helpers shared by the aggregation kernels (spmm_csr.hip, the GAT forms gat_*.hip).
 #pragma once
 #include "sgx_internal.h"
 

@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <type_traits>
+
 #include "sgx.h"
 
 #define SGX_HIP_CHECK(expr)                     \
@@ -156,12 +158,82 @@ int sgx_gat_aggregate_ep(int dtype, int relu, int fill_dead_rows, int n_rows, in
                          const void *attention, void *D, int64_t ldd, float *E, float *S, const sgx_plan *plan,
                          float *s_scratch, hipStream_t stream, float out_scale, const float *ext_fill = nullptr, int ext_n = 0,
                          int scores_ready = 0);
+
+// The GAT aggregate's one scratch buffer (sgx_gat_scratch_bytes floats behind s_scratch), laid out in ONE place
+// (sgx_gat_scratch_layout, gat.hip): the float offset of every region.  A region the call does not have is empty and
+// carries the offset of what follows it.
+struct sgx_gat_scratch {
+    size_t s1, s2;                        // the scores Wh.a1 / Wh.a2, [n_cols][n_heads] each
+    size_t slabs, mean;                   // fill_dead_rows: the column-sum slabs [slabs][n_feat], then the mean row [n_feat]
+    size_t sp1, sp2;                      // has_partials: the X.W epilogue's score partials, [n_cols][n_feat / 64] each
+    size_t pacc, pm, pl;                  // has_split: per task of the plan an fp32 partial row [ldp], (max, sum) per head
+    size_t row_m, row_l;                  //            per long row (max, sum) per head
+    size_t weights, dead;                 // has_two_stage: stage A's weights [nnz][n_heads], then the dead-row flags ([n_rows] bytes)
+    size_t total;                         // floats in all
+    int ldp;                              // pitch of a partial row
+    bool has_partials, has_split, has_two_stage;
+};
+sgx_gat_scratch sgx_gat_scratch_layout(int n_cols, int n_feat, int n_heads, int fill_dead_rows, const sgx_plan *plan);
+
+// One call of the aggregate, as its forms see it (gat.hip fills it in and chooses the form)
+struct sgx_gat_args {
+    int dtype, lpr;            // element type and lanes per row: with vec_ok the kernels' template arguments (sgx_gat_dispatch)
+    int relu, n_rows, n_cols, n_feat, n_heads;
+    float alpha;
+    const int32_t *rowptr, *col;
+    const void *val, *Wh, *att;
+    int64_t ldh, ldd;
+    unsigned h_bytes, ld_bytes;
+    void *D;
+    float *E, *S;
+    float *scratch;            // the caller's scratch
+    sgx_gat_scratch lay;       // and where everything lies in it
+    const float *fill;
+    int uniform_n;             // the N of the uniform softmax a dead row gets (S = 1/N): n_cols, or all nodes of a partitioned graph
+    float out_scale;           // deq_o of the quantised layer on fp32 outputs (0 = off)
+    const sgx_plan *plan_any;  // the caller's plan, long rows or not (two-stage form: it tells the stored-entry count)
+    const sgx_plan *plan;      // long rows -> split path
+    int vec_ok, vec_store;
+    int scores_ready;          // the scratch already holds Wh.a1 / Wh.a2 (formed in the epilogue of the X.W kernel that produced Wh)
+    hipStream_t stream;
+};
+
+// The kernels' template arguments from a call's runtime facts, for every form: f(T(), VEC, LPR) with the element type, the
+// elements a lane holds (16 bytes where the table allows, else 1) and the lanes per row as integral constants.
+template <typename T, int VEC, typename F>
+int sgx_gat_dispatch_lpr(int lpr, F &&f)
+{
+    switch (lpr) {
+    case 1: return f(T(), std::integral_constant<int, VEC>(), std::integral_constant<int, 1>());
+    case 2: return f(T(), std::integral_constant<int, VEC>(), std::integral_constant<int, 2>());
+    case 4: return f(T(), std::integral_constant<int, VEC>(), std::integral_constant<int, 4>());
+    case 8: return f(T(), std::integral_constant<int, VEC>(), std::integral_constant<int, 8>());
+    case 16: return f(T(), std::integral_constant<int, VEC>(), std::integral_constant<int, 16>());
+    case 32: return f(T(), std::integral_constant<int, VEC>(), std::integral_constant<int, 32>());
+    default: return f(T(), std::integral_constant<int, VEC>(), std::integral_constant<int, 64>());
+    }
+}
+template <typename F>
+int sgx_gat_dispatch(const sgx_gat_args &a, F &&f)
+{
+    if (a.dtype == SGX_F16) return a.vec_ok ? sgx_gat_dispatch_lpr<f16, 8>(a.lpr, f) : sgx_gat_dispatch_lpr<f16, 1>(a.lpr, f);
+    return a.vec_ok ? sgx_gat_dispatch_lpr<float, 4>(a.lpr, f) : sgx_gat_dispatch_lpr<float, 1>(a.lpr, f);
+}
+
+// The forms of the aggregate behind gat.hip's choice, each on scores already in the scratch:
+// gat_one_pass.hip: one walk per row with a running softmax state (any adjacency, no plan needed; E / S optional)
+int sgx_gat_one_pass(const sgx_gat_args &a);
+// gat_alpha.hip: stage A of the two-stage form by rows -- the softmax weights of the stored entries into W (the caller's S
+// or the scratch), the dead-row flags, E; scan: the rows up to the plan's cut in entry order instead (gat_scan.hip)
+int sgx_gat_alpha_stage(const sgx_gat_args &a, float *W, bool scan);
+// gat_weighted.hip: stage B -- D = act(sum_e W_e Wh[col_e]) and the dead rows' fill
+int sgx_gat_weighted(const sgx_gat_args &a, const float *W);
 // gat_stats.hip: the row softmax statistics (sgx_gat_stats) of an aggregate that has just run on s_scratch, from the scores
 // its pre-pass left there; sgx_gat_stats_check: SGX_ERR_NULL for a missing array, SGX_ERR_UNSUPPORTED past 32-bit offsets
 int sgx_gat_stats_check(const sgx_gat_stats *st, int n_cols, int n_heads);
 int sgx_gat_row_stats(int dtype, int n_rows, int n_cols, int n_heads, float alpha, const int32_t *rowPtr,
-                      const int32_t *columnIndex, const void *values, const float *s_scratch, const sgx_gat_stats *st,
-                      hipStream_t stream);
+                      const int32_t *columnIndex, const void *values, const float *s_scratch, const sgx_gat_scratch &lay,
+                      const sgx_gat_stats *st, hipStream_t stream);
 // gat_scan.hip: the softmax weights of the stored entries of every row of up to kScanMaxRow entries (stage A of the
 // two-stage aggregate) as a segmented scan in entry order; longer rows are the plan's tasks
 constexpr int kScanGranule = 64, kScanMaxRow = 256;
@@ -188,8 +260,7 @@ int sgx_gat_fused(const sgx_gat_fused_args &a);
 
 // GAT layer: the attention scores formed by the X.W kernel's epilogue (fp16, heads of 32 columns, two-stage aggregate)
 bool sgx_gat_scores_fusable(int dtype, int n_feat, int n_heads, const sgx_plan *plan);
-float *sgx_gat_score_partials(float *s_scratch, int n_cols, int n_feat, int n_heads, int fill_dead_rows);
-int sgx_gat_scores_combine(float *s_scratch, int n_cols, int n_feat, int n_heads, int fill_dead_rows, hipStream_t stream);
+int sgx_gat_scores_combine(float *s_scratch, const sgx_gat_scratch &lay, int n_cols, int n_feat, int n_heads, hipStream_t stream);
 // sgx_xw_dense_ep for that case: s1 / s2 [n_rows x n_heads] = H.a1 / H.a2 per head beside H; SGX_ERR_UNSUPPORTED when
 // the shape is not the stationary kernel's (the caller then runs the plain product and lets the aggregate form the scores)
 // (heads of 32 columns: s1 / s2 are the scores themselves; heads of 64 columns and more: one partial per (row, 64-column

@@ -251,7 +251,7 @@ class Csr:
     @property
     def gat_plan(self):
         """The schedule for the edge-softmax aggregate: hub rows cut at 256 edges.  Its first stage (the softmax weights,
-        csrc/gat.hip, gat_scan.hip) keeps a row of up to 256 edges in registers -- per row, or per window of stored entries
+        csrc/gat_alpha.hip, gat_scan.hip) keeps a row of up to 256 edges in registers -- per row, or per window of stored entries
         on a plan in degree order (the plan's scan_win, built for this cut) -- longer rows go through the plan's tasks.  Measured on
         R-MAT graphs of 2.4 M / 7.5 M / 29 M edges (tools/plan_cut_probe.py): 256 is the best or within 2 % of it for one
         head and for 8, while the plain aggregation prefers 512 / 1024 / 2048 (Plan's default).  The plan also tells the
@@ -615,6 +615,12 @@ def requantize_(H, scale_fea, internal_bits):
     return H
 
 
+def _check_fill_row(fill_row, F, n_nodes):
+    _dev(fill_row, "fill_row")
+    if fill_row.dtype != torch.float32 or fill_row.numel() != F or not n_nodes:
+        raise ValueError("fill_row must be float32 [F] and come with n_nodes")
+
+
 def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=False, fill_dead_rows=None, out=None,
                   heads=1, use_plan=True, fill_row=None, n_nodes=None, want_row_stats=False):
     """Edge-softmax aggregate over an already computed Wh [adj.n_cols, F]; row r of adj is node r of Wh.
@@ -647,9 +653,7 @@ def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=F
         return _gat_aggregate_stats(adj, Wh, att, alpha, relu, want_edge_outputs, fill_dead_rows, out, heads, plan, fill_row,
                                     n_nodes)
     if fill_row is not None:
-        _dev(fill_row, "fill_row")
-        if fill_row.dtype != torch.float32 or fill_row.numel() != F or not n_nodes:
-            raise ValueError("fill_row must be float32 [F] and come with n_nodes")
+        _check_fill_row(fill_row, F, n_nodes)
         s = torch.empty(lib.sgx_gat_scratch_bytes(N, F, heads, 0, plan) // 4, dtype=torch.float32, device=Wh.device)
         check(lib.sgx_gat_aggregate_fill(code, int(bool(relu)), adj.n_rows, N, F, heads, float(alpha), _ptr(adj.rowptr),
                                          _ptr(adj.col), _ptr(adj.val), _ptr(Wh), Wh.stride(0), _ptr(att), _ptr(out),
@@ -671,9 +675,7 @@ def _gat_aggregate_stats(adj, Wh, att, alpha, relu, want_edge_outputs, fill_dead
         raise ValueError("want_row_stats and want_edge_outputs exclude each other")
     N, F = Wh.shape
     if fill_row is not None:
-        _dev(fill_row, "fill_row")
-        if fill_row.dtype != torch.float32 or fill_row.numel() != F or not n_nodes:
-            raise ValueError("fill_row must be float32 [F] and come with n_nodes")
+        _check_fill_row(fill_row, F, n_nodes)
         fill, nn = 0, int(n_nodes)
     else:
         fill = int(adj.has_dead_rows if fill_dead_rows is None else bool(fill_dead_rows))
@@ -749,16 +751,9 @@ def csr_transpose(A, return_order=False):
     return (T, order) if return_order else T
 
 
-def gat_backward_edges(adj, E, S, G, Wh, alpha=0.2, dead=None):
-    """Edge pass of FPYNQ_GAT.backward (sgx_gat_backward_edges): returns (sg [nnz], g1 [n_rows]) fp32.
-    dead: None, or bool [n_rows] -- the rows the forward gave a uniform softmax over all n_cols columns (the dead rows
-    of the adjacency it masked with, quantised or not); their softmax row sum is G[r] . mean(Wh) (SG.py:884-1126)."""
-    _dev2d(G, "G")
-    _dev2d(Wh, "Wh")
-    if G.dtype != torch.float32 or Wh.dtype != torch.float32 or E.dtype != torch.float32 or S.dtype != torch.float32:
-        raise TypeError("gat_backward_edges works on float32 E, S, G, Wh (the reference's backward is fp32)")
-    if Wh.shape[0] != adj.n_cols or G.shape != (adj.n_rows, Wh.shape[1]):
-        raise ValueError("G must be [adj.n_rows, F] and Wh [adj.n_cols, F]")
+def _backward_edge_operands(adj, G, Wh, dead):
+    """What both backward edge passes hand the kernel beside G: (dead_rs, Wh) -- the dead rows' softmax row sum
+    G[r] . mean(Wh) (None without `dead`), and Wh with rows the kernel can gather 16 bytes at a time."""
     dead_rs = None
     if dead is not None:
         _dev(dead, "dead")
@@ -770,6 +765,20 @@ def gat_backward_edges(adj, E, S, G, Wh, alpha=0.2, dead=None):
         padded = torch.zeros((Wh.shape[0], (Wh.shape[1] + 3) // 4 * 4), dtype=torch.float32, device=Wh.device)
         padded[:, :Wh.shape[1]] = Wh
         Wh = padded[:, :Wh.shape[1]]
+    return dead_rs, Wh
+
+
+def gat_backward_edges(adj, E, S, G, Wh, alpha=0.2, dead=None):
+    """Edge pass of FPYNQ_GAT.backward (sgx_gat_backward_edges): returns (sg [nnz], g1 [n_rows]) fp32.
+    dead: None, or bool [n_rows] -- the rows the forward gave a uniform softmax over all n_cols columns (the dead rows
+    of the adjacency it masked with, quantised or not); their softmax row sum is G[r] . mean(Wh) (SG.py:884-1126)."""
+    _dev2d(G, "G")
+    _dev2d(Wh, "Wh")
+    if G.dtype != torch.float32 or Wh.dtype != torch.float32 or E.dtype != torch.float32 or S.dtype != torch.float32:
+        raise TypeError("gat_backward_edges works on float32 E, S, G, Wh (the reference's backward is fp32)")
+    if Wh.shape[0] != adj.n_cols or G.shape != (adj.n_rows, Wh.shape[1]):
+        raise ValueError("G must be [adj.n_rows, F] and Wh [adj.n_cols, F]")
+    dead_rs, Wh = _backward_edge_operands(adj, G, Wh, dead)
     sg = torch.empty(adj.nnz, dtype=torch.float32, device=G.device)
     g1 = torch.empty(adj.n_rows, dtype=torch.float32, device=G.device)
     check(lib.sgx_gat_backward_edges(dtype_code(adj.val.dtype), adj.n_rows, adj.n_cols, Wh.shape[1], float(alpha),
@@ -806,17 +815,7 @@ def gat_backward_edges_stats(adj, stats, G, Wh, alpha=0.2, dead=None, dead_weigh
         raise ValueError("G must be [adj.n_rows, F] and Wh [adj.n_cols, F]")
     if stats.heads != 1:
         raise ValueError("the backward edge pass is single-head")
-    dead_rs = None
-    if dead is not None:
-        _dev(dead, "dead")
-        if dead.dtype != torch.bool or dead.shape != (adj.n_rows,):
-            raise ValueError("dead must be a bool [adj.n_rows] tensor")
-        wh_mean = (col_sums(Wh) / adj.n_cols).unsqueeze(0)                   # [1, F]
-        dead_rs = xw_dense(G if G.stride(0) == G.shape[1] else G.contiguous(), wh_mean)[:, 0].contiguous()
-    if Wh.stride(0) % 4 or Wh.data_ptr() % 16:           # rows are gathered 16 bytes at a time: pad them
-        padded = torch.zeros((Wh.shape[0], (Wh.shape[1] + 3) // 4 * 4), dtype=torch.float32, device=Wh.device)
-        padded[:, :Wh.shape[1]] = Wh
-        Wh = padded[:, :Wh.shape[1]]
+    dead_rs, Wh = _backward_edge_operands(adj, G, Wh, dead)
     sg = torch.empty(adj.nnz, dtype=torch.float32, device=G.device)
     g1 = torch.empty(adj.n_rows, dtype=torch.float32, device=G.device)
     S = torch.empty(adj.nnz, dtype=torch.float32, device=G.device) if want_S else None

@@ -1,6 +1,6 @@
-"""Every form of the GAT edge-softmax aggregate -- one pass (gat.hip: per row, long rows split, several heads), two stages
-(stage A per row for 1 head / 2..64 heads / more than 64 heads, as a scan in entry order (gat_scan.hip), long rows through
-the plan's tasks; stage B with and without the degree order's one-step tail), one walk (gat_fused.hip), the scores from
+"""Every form of the GAT edge-softmax aggregate -- one pass (gat_one_pass.hip: per row, long rows split, several heads), two stages
+(stage A per row for 1 head / 2..64 heads / more than 64 heads (gat_alpha.hip), as a scan in entry order (gat_scan.hip), long rows through
+the plan's tasks; stage B (gat_weighted.hip) with and without the degree order's one-step tail), one walk (gat_fused.hip), the scores from
 the X.W epilogue (xw_dense.hip) and the dead-row fills -- against the float64 restatement of tests/_gat_ref.py, element
 by element inside its stated error bound, on graphs built where softmax code breaks: live scores tens to hundreds apart,
 masked entries with the highest scores, the mask's edge values (+0.0, -0.0, tiny negatives, fp16 and fp32 subnormals),

@@ -1,5 +1,5 @@
 """The one-step tail of a degree-ordered plan -- rows of at most 8 edges, 64 to a wavefront (spmm_short_rows in
-csrc/spmm_csr.hip; the same walk in the GAT aggregate's second stage, csrc/gat.hip) -- against the sblock walk of the
+csrc/spmm_csr.hip; the same walk in the GAT aggregate's second stage, csrc/gat_weighted.hip) -- against the sblock walk of the
 same rows (SGX_SPMM_NO_SHORT_TAIL): the same fma chain per output element, so the same BITS, for every lane split, element
 type and entry point that takes the path, and against the oracle on sampled rows.  The reference groups rows per pipelined
 loop by a build constant (SPMM_BLOCK, K.cpp:826-845); this is the same idea with the group chosen by row length."""
