@@ -26,7 +26,9 @@ downloaded by torch_geometric and are not available offline.
 --device-batches
              with --batch-size: the loader hands over layer-ready batches (NeighborLoader(..., prepare="sym_norm2")): the
              normalised adjacency, the feature CSR, the labels and masks are built on the GPU behind the sample, and a
-             training step synchronises once, inside the sampler
+             training step synchronises once, inside the sampler; with --accb or --attention the batches also carry
+             the transposed matrices the backward reads (transposed=True: X^T for grad_weights over CSR features, the
+             transposed pattern of the GAT backward), built on the GPU by sgx_csr_transpose instead of a sort per batch
 """
 import argparse
 import os
@@ -83,15 +85,19 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         train_mask[train] = True
         data = pyg_lite.NodeData(x, edge_index, y, train_mask=train_mask)
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
-                                         shuffle=True, seed=seed, **({"prepare": "sym_norm2"} if device_batches else {}))
+                                         shuffle=True, seed=seed,
+                                         **({"prepare": "sym_norm2", "transposed": bool(accb or attention)} if device_batches else {}))
     t0 = time.time()
+    epoch_loss = []                                         # mean training loss of every epoch, kept on the device
     for epoch in range(epochs):
         model.train()
+        total, steps = 0, 0
         if loader is None:
             opt.zero_grad()
             loss = crit(model(x, edge_index)[train], y[train])
             loss.backward()
             opt.step()
+            total, steps = loss.detach(), 1
         else:
             for batch in loader:                            # demo_sgrace.py train(), :476-507
                 opt.zero_grad()
@@ -107,6 +113,8 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
                     loss = crit(out[batch.train_mask], batch.y[batch.train_mask])
                 loss.backward()
                 opt.step()
+                total, steps = total + loss.detach(), steps + 1
+        epoch_loss.append(total / max(steps, 1))
         if verbose and (epoch + 1) % 20 == 0:
             print(f"epoch {epoch + 1:3d}  loss {float(loss):.4f}", flush=True)
     if device.type == "cuda":
@@ -117,7 +125,8 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         pred = model(x, edge_index).argmax(1)
     result = {"train_acc": float((pred[train] == y[train]).float().mean()),
               "test_acc": float((pred[test] == y[test]).float().mean()),
-              "edges": int(edge_index.shape[1]), "ms_per_epoch": 1000 * elapsed / epochs}
+              "edges": int(edge_index.shape[1]), "ms_per_epoch": 1000 * elapsed / epochs,
+              "epoch_loss": [float(v) for v in epoch_loss]}
     if loader is not None:
         result["batches_per_epoch"] = len(loader)
     if verbose:

@@ -909,6 +909,42 @@ int sgx_gat_attention_grad(int n_rows, int n_cols, int n_feat, const int32_t *ro
                            const float *sg, const float *g1, const float *Wh, int64_t ldw, float *grad_attention,
                            void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the transpose of a CSR matrix -------------------------------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_csr_transpose writes the CSR of A^T ([n_cols] rows, [n_rows] columns) for a CSR A of n_rows x n_cols with nnz stored
+ * entries: rowPtr_t [n_cols + 1], columnIndex_t [nnz], values_t [nnz], and optionally order [nnz].  Rule:
+ *     entry k of A^T is stored entry order[k] of A;  columnIndex_t[k] = the row of A that holds entry order[k];
+ *     values_t[k] = values[order[k]], copied bit for bit (-0.0, NaN payloads and subnormals survive);
+ *     within a row of A^T the entries stand in ascending order[k]: the transpose is STABLE.
+ * Where every (row, col) pair of A is stored once that is the order by (col, row); copies of a pair keep their source
+ * order.  order = the stable sort of the positions 0 .. nnz-1 by columnIndex; rowPtr_t[c] = the number of stored entries
+ * with a column below c.  The result is a pure function of the input: the same bits on every run, every device and every
+ * grid size (a least-significant-digit radix sort, 8 bits a pass, ceil(bits(n_cols - 1) / 8) passes over tiles of
+ * SGX_CSR_TRANSPOSE_TILE entries; integer atomics only count, no output position depends on the order in which one
+ * returns).  The work is O(nnz x passes + n_cols log nnz) whatever the lengths of the rows of A^T.
+ *
+ * values and values_t are both NULL (a pattern only; dtype_values is then not looked at) or both given (dtype_values:
+ * SGX_F16 or SGX_F32).  order may be NULL.  The input arrays are not modified; no output may alias an input or another
+ * output.  Index and order arrays need 4-byte alignment only, fp16 values 2-byte (slices of larger buffers are fine).
+ * workspace: sgx_csr_transpose_workspace_bytes(n_rows, n_cols, nnz) bytes, 256-byte aligned.  The contents of an invalid
+ * CSR are the caller's to check (sgx_csr_validate); whatever they are, nothing is read or written out of bounds.
+ * n_rows == 0 or nnz == 0: rowPtr_t becomes all zeros and nothing else is written.
+ *
+ * Argument errors, returned before anything reaches the device: rowPtr, columnIndex, rowPtr_t or columnIndex_t NULL, or
+ * exactly one of values / values_t NULL: SGX_ERR_NULL; n_rows, n_cols or nnz below 0: SGX_ERR_SHAPE; nnz > INT32_MAX, or
+ * (with values) a dtype other than SGX_F16 / SGX_F32: SGX_ERR_UNSUPPORTED; workspace missing or too small:
+ * SGX_ERR_WORKSPACE; not 256-byte aligned: SGX_ERR_ALIGN.  Asynchronous on `stream`, no allocation, no synchronisation:
+ * capturable. */
+#define SGX_CSR_TRANSPOSE_TILE 2048   /* stored entries per workgroup of a sort pass */
+
+/* 0 for sizes the call refuses; otherwise positive and a multiple of 256 */
+size_t sgx_csr_transpose_workspace_bytes(int n_rows, int n_cols, int64_t nnz);
+int sgx_csr_transpose(int dtype_values, int n_rows, int n_cols, int64_t nnz,
+                      const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                      int32_t *rowPtr_t, int32_t *columnIndex_t, void *values_t, int32_t *order,
+                      void *workspace, size_t workspace_bytes, void *stream);
+
 /* A plain streaming copy (16 bytes per lane, non-temporal, each workgroup on a contiguous chunk), the kernel the attainable HBM rate of a device is
  * measured with next to the nominal 8 TB/s (bench.py reports it as roofline.stream_copy_GBps_this_device).
  * bytes must be a multiple of 16, both pointers 16-byte aligned. */

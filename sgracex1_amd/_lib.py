@@ -23,6 +23,7 @@ SGX_QUANT_INT8_AUTO = 4                                     # ... where they are
 SGX_ERR_SEEDS = -8                                          # sgx_sample_neighbors: a repeated or out-of-range seed
 SGX_ERR_BLOCKS = -9                                         # sgx_batch_plan_create: an edge leaves its graph / bad graph_ptr
 SGX_BATCH_FORWARD, SGX_BATCH_BACKWARD = 0, 1                # sgx_batch_kind: whose LDS tiles set a batch plan's row budget
+SGX_CSR_TRANSPOSE_TILE = 2048                               # sgx_csr_transpose: stored entries per workgroup of a sort pass
 
 # every symbol include/sgx.h declares (tests/test_abi.py checks header and library against this)
 SYMBOLS = [
@@ -45,6 +46,7 @@ SYMBOLS = [
     "sgx_node_batch_workspace_bytes", "sgx_node_batch_sample",
     "sgx_layer_backward_workspace_bytes", "sgx_layer_backward", "sgx_gat_attention_grad_workspace_bytes",
     "sgx_gat_attention_grad",
+    "sgx_csr_transpose_workspace_bytes", "sgx_csr_transpose",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -369,6 +371,10 @@ def _load():
     lib.sgx_gat_attention_grad_workspace_bytes.restype = sz
     lib.sgx_gat_attention_grad.argtypes = [c_int, c_int, c_int, vp, vp, vp, vp, vp, c_i64, vp, vp, sz, vp]
     lib.sgx_gat_attention_grad.restype = c_int
+    lib.sgx_csr_transpose_workspace_bytes.argtypes = [c_int, c_int, c_i64]
+    lib.sgx_csr_transpose_workspace_bytes.restype = sz
+    lib.sgx_csr_transpose.argtypes = [c_int, c_int, c_int, c_i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.sgx_csr_transpose.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

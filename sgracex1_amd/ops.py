@@ -733,9 +733,42 @@ def xt_g(X, G):
     return out
 
 
-def csr_transpose(A, return_order=False):
+# the form csr_transpose(method=None) takes: "device" (sgx_csr_transpose) or "torch" (sort plumbing); DESIGN 4.13 holds the
+# measurement that chose it
+CSR_TRANSPOSE_DEFAULT = "device"
+
+
+def _transposed(T, return_order, order):
+    if T.n_rows > 0 and T.nnz >= 64 * T.n_rows:
+        # a feature matrix transposed: a handful of rows, each as long as the graph is wide (MUTAG: 7 rows of ~500 entries) --
+        # below the size at which a plan is built by itself, and exactly the shape that needs one: without it 7 lane groups
+        # walk 60 dependent steps each (58 us for a 3.4 K-entry matrix) where the plan's 64-edge tasks take a few
+        T.plan
+    return (T, order) if return_order else T
+
+
+def csr_transpose(A, return_order=False, method=None):
     """CSR of A^T (values kept, same dtype); features are fixed across epochs, so callers cache it.
-    return_order: also the edge permutation (edge k of A^T is edge order[k] of A)."""
+    return_order: also the edge permutation (edge k of A^T is edge order[k] of A), int64.
+    method: "device" -- sgx_csr_transpose, the stable transpose of include/sgx.h in four launches per sort pass and no
+    synchronisation; "torch" -- the int64 key, argsort and gathers this function was before; None -- CSR_TRANSPOSE_DEFAULT.
+    On a matrix that stores every (row, col) pair once both give the same arrays; copies of a pair keep their source order
+    on the device and stand in no defined order under "torch"."""
+    method = CSR_TRANSPOSE_DEFAULT if method is None else method
+    if method == "device":
+        nnz, dev = A.nnz, A.rowptr.device
+        rowptr_t = torch.empty(A.n_cols + 1, dtype=torch.int32, device=dev)
+        col_t = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev)
+        val_t = torch.empty(max(nnz, 1), dtype=A.val.dtype, device=dev)
+        order = torch.empty(max(nnz, 1), dtype=torch.int32, device=dev) if return_order else None
+        ws = _workspace(dev, lib.sgx_csr_transpose_workspace_bytes(A.n_rows, A.n_cols, nnz))
+        check(lib.sgx_csr_transpose(dtype_code(A.val.dtype), A.n_rows, A.n_cols, nnz, _ptr(A.rowptr), _ptr(A.col), _ptr(A.val),
+                                    _ptr(rowptr_t), _ptr(col_t), _ptr(val_t), _ptr(order), _ptr(ws), ws.numel(), _stream()),
+              "sgx_csr_transpose")
+        T = Csr(rowptr_t, col_t[:nnz], val_t[:nnz], A.n_rows)
+        return _transposed(T, return_order, order[:nnz].long() if return_order else None)
+    if method != "torch":
+        raise ValueError(f"csr_transpose: method must be None, 'device' or 'torch', not {method!r}")
     row = torch.repeat_interleave(torch.arange(A.n_rows, device=A.col.device, dtype=torch.int64),
                                   (A.rowptr[1:] - A.rowptr[:-1]).long(), output_size=A.nnz)
     col, val = A.col[:A.nnz], A.val[:A.nnz]
@@ -743,12 +776,7 @@ def csr_transpose(A, return_order=False):
     order = torch.argsort(key)
     T = Csr.from_coo(col[order].contiguous(), row[order].to(torch.int32).contiguous(), val[order].contiguous(),
                      A.n_cols, A.n_rows)
-    if T.n_rows > 0 and T.nnz >= 64 * T.n_rows:
-        # a feature matrix transposed: a handful of rows, each as long as the graph is wide (MUTAG: 7 rows of ~500 entries) --
-        # below the size at which a plan is built by itself, and exactly the shape that needs one: without it 7 lane groups
-        # walk 60 dependent steps each (58 us for a 3.4 K-entry matrix) where the plan's 64-edge tasks take a few
-        T.plan
-    return (T, order) if return_order else T
+    return _transposed(T, return_order, order)
 
 
 def _backward_edge_operands(adj, G, Wh, dead):

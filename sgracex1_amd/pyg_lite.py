@@ -220,10 +220,17 @@ class NeighborLoader:
     here.  Pass batch.edge_index_agg to the model; it then computes nothing before its first kernel.  The list of the
     attached triple is edge_index_agg itself (the sampled edges without the added loops); the kernels read the Csr.
     The seeds are rows 0 .. batch_size-1, so a loss over them is out[:batch.batch_size].  prepare=None: the batches as
-    before."""
+    before.
+
+    transposed=True (with prepare): every batch also carries what the backward would otherwise build per batch from a
+    sort -- x the fp32 feature CSR under ("fea_csr", float32) and its transpose under ("fea_csr_t", float32), the two
+    entries ops.feature_csr32 looks up (config.accb = 1 over CSR features), and adj_norm._transpose_pattern = (A^T,
+    order), what the default GAT backward looks up -- from two sgx_csr_transpose calls on the same stream behind the
+    sampler, with no synchronisation of their own (a transposed matrix that wants a plan by ops.csr_transpose's rule
+    still builds it, with the plan's read-back)."""
 
     def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0, prepare=None, fill=0,
-                 dtype=torch.float32):
+                 dtype=torch.float32, transposed=False):
         from . import ops
         self.data, self.num_neighbors = data, [int(k) for k in num_neighbors]
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
@@ -243,6 +250,9 @@ class NeighborLoader:
         if prepare not in (None, "sym_norm2"):
             raise ValueError(f"prepare must be None or 'sym_norm2', not {prepare!r}")
         self.prepare, self.fill, self.dtype = prepare, fill, dtype
+        if transposed and not prepare:
+            raise ValueError("transposed=True needs prepare='sym_norm2'")
+        self.transposed = bool(transposed)
         if prepare:
             ops.dtype_code(dtype)
             if x.dtype != torch.float32 or not x.is_contiguous():
@@ -276,6 +286,14 @@ class NeighborLoader:
         A, n = s.adj_norm, s.n_id.numel()
         ops.attach(x, ("fea_csr", self.dtype), s.fea)
         ops.attach(s.edge_index_agg, ("sym_norm2", n, 1, self.dtype), (s.edge_index_agg, A.val[:A.nnz], A))
+        if self.transposed:
+            fea32 = s.fea
+            if self.dtype != torch.float32:              # (the values alone are cast: never through a dense tensor)
+                fea32 = ops.attach(x, ("fea_csr", torch.float32),
+                                   ops.Csr(s.fea.rowptr, s.fea.col[:s.fea.nnz], s.fea.val[:s.fea.nnz].float(),
+                                           s.fea.n_cols).with_facts(max_row=s.fea._max_row))
+            ops.attach(x, ("fea_csr_t", torch.float32), ops.csr_transpose(fea32, method="device"))
+            A._transpose_pattern = ops.csr_transpose(A, return_order=True, method="device")
         fields = dict(x=x, edge_index=s.edge_index, edge_index_agg=s.edge_index_agg, adj_norm=A, n_id=s.n_id.long(),
                       adj=s.adj, batch_size=s.batch_size, input_id=input_id, num_sampled_nodes=s.num_sampled_nodes,
                       num_sampled_edges=s.num_sampled_edges)

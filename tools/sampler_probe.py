@@ -17,6 +17,10 @@ of examples/sgrace_node_classification.py (GCN and GAT).  One JSON line per meas
                                                    # --accb 0,1: config.accb of the step (the layer backward composed /
                                                    # as one call), every (arm, accb) pair a leg of the same windows
                                                    # (profiles/r09_layer_backward.jsonl); --label NAME tags the run
+                                                   # --transposed: beside the prepared arm a "prepared_t" arm, the same
+                                                   # loader with transposed=True (X^T and the GAT backward's transposed
+                                                   # pattern built behind the sampler), in the same windows
+                                                   # (profiles/r11_step_*.jsonl)
 """
 import argparse
 import json
@@ -160,7 +164,9 @@ def node_batch(arms, trace, accbs=(0,)):
         data = pyg_lite.NodeData(x, ei, y, train_mask=train)
         loaders = {}
         for arm in arms:
-            kw = {"prepare": "sym_norm2"} if arm == "prepared" else {}
+            kw = {"prepare": "sym_norm2"} if arm.startswith("prepared") else {}
+            if arm == "prepared_t":
+                kw["transposed"] = True
             loaders[arm] = pyg_lite.NeighborLoader(data, fan, batch_size=bs, input_nodes=train, shuffle=True, seed=1, **kw)
         del ei
         for attention in (0, 1):
@@ -184,7 +190,7 @@ def node_batch(arms, trace, accbs=(0,)):
                         state["it"] = iter(loaders[arm])
                         b = next(state["it"])
                     opt.zero_grad()
-                    if arm == "prepared":
+                    if arm.startswith("prepared"):
                         out = model(b.x, b.edge_index_agg)
                         loss = crit(out[:b.batch_size], b.y[:b.batch_size])
                     else:
@@ -255,11 +261,14 @@ def main():
     ap.add_argument("--label", default=None, help="--node-batch: a tag printed with the run (which checkout this is)")
     ap.add_argument("--arms", default="default,prepared")
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--transposed", action="store_true", help="--node-batch: add the arm prepared_t (the prepared loader with "
+                                                              "transposed=True) to the same windows")
     a = ap.parse_args()
     if a.node_batch:
         if a.label:
             print(json.dumps({"label": a.label}), flush=True)
-        return node_batch(a.arms.split(","), a.trace, tuple(int(b) for b in a.accb.split(",")))
+        arms = a.arms.split(",") + (["prepared_t"] if a.transposed else [])
+        return node_batch(arms, a.trace, tuple(int(b) for b in a.accb.split(",")))
     dev = torch.device("cuda")
     shapes = [("products shape uniform", lambda: graphs.uniform_graph(2_450_000, 122_000_000, dtype=torch.float32,
                                                                       normalize=False)),
