@@ -1,7 +1,10 @@
 """The quantised layer on the GPU (sgx_fake_quantize, sgx_requantize, sgx_layer_forward with a
 sgx_quant block) against the CPU restatement of SG.py:565-667 (oracle/quant_oracle.py).  The two
 rounding kernels are compared bit for bit; the layer within the fp32 band of the plain fp32 layer
-(sums are formed in another order than torch.mm / torch.matmul).  Parity unpinned -- see the oracle."""
+(sums are formed in another order than torch.mm / torch.matmul).  Parity unpinned -- see the oracle.
+Every layer here has one family of small shapes, which reach the same few store sites each time: the epilogue on each
+kernel path (LDS form, cut rows, degree order and its tail, element stores, every dense and GAT form) is pinned bit for
+bit in tests/test_gpu_quant_paths.py against the sparse reference of tests/_quant_ref.py."""
 import numpy as np
 import pytest
 import torch
