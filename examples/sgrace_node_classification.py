@@ -28,7 +28,9 @@ downloaded by torch_geometric and are not available offline.
              normalised adjacency, the feature CSR, the labels and masks are built on the GPU behind the sample, and a
              training step synchronises once, inside the sampler; with --accb or --attention the batches also carry
              the transposed matrices the backward reads (transposed=True: X^T for grad_weights over CSR features, the
-             transposed pattern of the GAT backward), built on the GPU by sgx_csr_transpose instead of a sort per batch
+             transposed pattern of the GAT backward), built on the GPU by sgx_csr_transpose instead of a sort per batch;
+             with --qbits the batches also carry the quantised adjacency of both layers with its dead-row facts
+             (quant=sgrace.quant_constants), so the quantised layers too launch nothing and read nothing back for it
 """
 import argparse
 import os
@@ -84,9 +86,9 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         train_mask = torch.zeros(n, dtype=torch.bool, device=device)
         train_mask[train] = True
         data = pyg_lite.NodeData(x, edge_index, y, train_mask=train_mask)
+        ready = {"prepare": "sym_norm2", "transposed": bool(accb or attention), "quant": sgrace.quant_constants}
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
-                                         shuffle=True, seed=seed,
-                                         **({"prepare": "sym_norm2", "transposed": bool(accb or attention)} if device_batches else {}))
+                                         shuffle=True, seed=seed, **(ready if device_batches else {}))
     t0 = time.time()
     epoch_loss = []                                         # mean training loss of every epoch, kept on the device
     for epoch in range(epochs):

@@ -812,6 +812,39 @@ size_t sgx_node_batch_workspace_bytes(int n_nodes, int64_t nnz, int batch, int n
                                       int64_t *max_nodes, int64_t *max_edges);
 int sgx_node_batch_sample(sgx_node_batch *b, void *stream);
 
+/* Layer-ready for the QUANTISED layers.  Added without a version bump (SGX_VERSION stays 110): the two declarations below
+ * are new, sgx_node_batch and everything above it are unchanged.
+ *
+ * sgx_node_batch_sample_quant(b, q) is sgx_node_batch_sample(b) -- same arguments, same results, bit for bit -- and, on the
+ * same stream before the call's one read-back, for each of the q->n_sets constant sets k (the adjacency constants of the
+ * layers that will read the batch: layer 1 / layer 2 of the demo) also writes what the quantised layers otherwise build
+ * per batch from values_norm:
+ *   values_q[k][e]   = the unsigned-grid value sgx_fake_quantize(0, qbits, inv_scale_adj[k], zero_adj[k]) gives for
+ *                      values_norm[e], e < nnz_norm: computed by the device function that call runs (csrc/quant_device.h),
+ *                      so the bits equal a sgx_fake_quantize launch over values_norm;
+ *   dead_row_q[k][r] = 1 where row r holds no values_q[k] > 0: the rows the GAT mask leaves without a neighbour once the
+ *                      adjacency is quantised (an entry may round to 0, so a row live in values_norm may be dead here);
+ *   values_lean[k][e] (optional, NULL = not written) = values_norm[e] on the rows with dead_row_q[k], values_q[k][e]
+ *                      elsewhere: the one values array the statistics form of the GAT backward masks with;
+ *   has_dead_rows_q[k] (host) = some dead_row_q[k] is 1.  It rides the sampler's counter block, so the call still has
+ *                      exactly one device-to-host copy.
+ * values_q / values_lean hold max_edges + max_nodes fp32 entries, dead_row_q max_nodes bytes.  Nothing allocates; no
+ * workspace beyond sgx_node_batch_workspace_bytes.  Two sets may carry equal constants; both are then written.
+ * Argument errors, returned before anything is launched and with the node_map untouched: b or q NULL: SGX_ERR_NULL;
+ * b->dtype other than SGX_F32 (the quantised layer works on fp32): SGX_ERR_UNSUPPORTED; n_sets outside {1, 2} or qbits
+ * outside {8, 4, 2, 1}: SGX_ERR_SHAPE; values_q[k] or dead_row_q[k] NULL for a k < n_sets: SGX_ERR_NULL; then those of
+ * sgx_node_batch_sample.  batch == 0 returns as sgx_node_batch_sample does, has_dead_rows_q = 0.  Not capturable. */
+typedef struct sgx_node_batch_quant {
+    int32_t n_sets;                 /* 1 or 2 constant sets (layer 1 / layer 2) */
+    int32_t qbits;                  /* 8, 4, 2, 1 */
+    float   inv_scale_adj[2], zero_adj[2];
+    float  *values_q[2];            /* out [max_edges + max_nodes] fp32 */
+    uint8_t *dead_row_q[2];         /* out [max_nodes] */
+    float  *values_lean[2];         /* out, optional (NULL = not written) */
+    int32_t has_dead_rows_q[2];     /* HOST out */
+} sgx_node_batch_quant;
+int sgx_node_batch_sample_quant(sgx_node_batch *b, sgx_node_batch_quant *q, void *stream);
+
 /* ---- the layer's backward in one call ---------------------------------------------------------
  * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
  *

@@ -43,7 +43,7 @@ SYMBOLS = [
     "sgx_batch_plan_create_ex", "sgx_stack_backward_workspace_bytes", "sgx_stack_backward",
     "sgx_collate_graphs", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
     "sgx_gat_aggregate_stats", "sgx_layer_forward_stats", "sgx_gat_edge_outputs", "sgx_gat_backward_edges_stats",
-    "sgx_node_batch_workspace_bytes", "sgx_node_batch_sample",
+    "sgx_node_batch_workspace_bytes", "sgx_node_batch_sample", "sgx_node_batch_sample_quant",
     "sgx_layer_backward_workspace_bytes", "sgx_layer_backward", "sgx_gat_attention_grad_workspace_bytes",
     "sgx_gat_attention_grad",
     "sgx_csr_transpose_workspace_bytes", "sgx_csr_transpose",
@@ -195,6 +195,16 @@ class NodeBatch(ctypes.Structure):
         ("nnz_norm", ctypes.c_int64), ("nnz_fea", ctypes.c_int64),
         ("has_dead_rows", ctypes.c_int32), ("max_row", ctypes.c_int32),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
+    ]
+
+
+class NodeBatchQuant(ctypes.Structure):
+    """struct sgx_node_batch_quant -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("n_sets", ctypes.c_int32), ("qbits", ctypes.c_int32),
+        ("inv_scale_adj", ctypes.c_float * 2), ("zero_adj", ctypes.c_float * 2),
+        ("values_q", ctypes.c_void_p * 2), ("dead_row_q", ctypes.c_void_p * 2), ("values_lean", ctypes.c_void_p * 2),
+        ("has_dead_rows_q", ctypes.c_int32 * 2),
     ]
 
 
@@ -363,6 +373,8 @@ def _load():
     lib.sgx_node_batch_workspace_bytes.restype = sz
     lib.sgx_node_batch_sample.argtypes = [ctypes.POINTER(NodeBatch), vp]
     lib.sgx_node_batch_sample.restype = c_int
+    lib.sgx_node_batch_sample_quant.argtypes = [ctypes.POINTER(NodeBatch), ctypes.POINTER(NodeBatchQuant), vp]
+    lib.sgx_node_batch_sample_quant.restype = c_int
     lib.sgx_layer_backward_workspace_bytes.argtypes = [ctypes.POINTER(LayerGradDesc)]
     lib.sgx_layer_backward_workspace_bytes.restype = sz
     lib.sgx_layer_backward.argtypes = [ctypes.POINTER(LayerGradDesc), vp]

@@ -7,10 +7,13 @@
 //   2-4   exclusive scan of the flags -> rowPtr of the normalised matrix                     (scan_*<LoopMissing>)
 //   5     rows ordered by column, the loop put in; deg and 1 / sqrt(deg) of every row        (order_kernel)
 //   6     values dis[r] * w * dis[c], dead-row mask, "some row is dead", the longest row     (values_kernel)
+//         sgx_node_batch_sample_quant: in the same pass the values on the unsigned w_qbits grid of one or two
+//         constant sets, their dead-row masks and flags, and the lean form's mask values
 //   7-9   exclusive scan of the lengths of the feature rows n_id -> rowPtr                   (scan_*<FeatureRows>)
 //   10    those rows' columns and values copied; y and the masks gathered                    (gather_kernel)
 // Kernel boundaries are the only ordering between workgroups.
 #include "sample_device.h"
+#include "quant_device.h"
 
 using namespace sgx_sample;
 
@@ -196,8 +199,20 @@ __global__ __launch_bounds__(kBlock) void order_kernel(Args a)
     }
 }
 
-template <class T>
-__global__ __launch_bounds__(kBlock) void values_kernel(Args a)
+// the NQ constant sets of sgx_node_batch_quant as the values pass takes them; NQ = 0: sgx_node_batch_sample, nothing of it
+template <int NQ>
+struct QuantSets {
+    int qbits;
+    float inv_scale[NQ], zero[NQ];
+    float *val[NQ], *lean[NQ];
+    uint8_t *dead[NQ];
+};
+template <>
+struct QuantSets<0> {};
+
+// bit 0 of the kDeadRows counter: some row of values_norm is dead; bit 1 + k: some row of constant set k is
+template <class T, int NQ>
+__global__ __launch_bounds__(kBlock) void values_kernel(Args a, QuantSets<NQ> qs)
 {
     if (a.ctr.status()) return;
     const int N = a.N(), lane = threadIdx.x & 63;
@@ -206,18 +221,37 @@ __global__ __launch_bounds__(kBlock) void values_kernel(Args a)
     for (int r = blockIdx.x * kWaves + (threadIdx.x >> 6); r < N; r += gridDim.x * kWaves) {
         const int q0 = b.rowPtr_norm[r], q1 = b.rowPtr_norm[r + 1];
         const float dr = a.dis[r];
-        bool live = false;
+        bool live = false, live_q[NQ ? NQ : 1] = {};
         for (int q = q0 + lane; q < q1; q += 64) {
             const float left = dr * a.w[q];                // (dis[r] * w) * dis[c]: two products, each rounded to fp32
             const T v = (T)(left * a.dis[b.columnIndex_norm[q]]);
             val[q] = v;
             live |= (float)v > 0.0f;
+            if constexpr (NQ > 0) {
+#pragma unroll
+                for (int k = 0; k < NQ; ++k) {
+                    const float vq = sgx_quantizer::fake_quantize_value(0, qs.qbits, qs.inv_scale[k], qs.zero[k], (float)v);
+                    qs.val[k][q] = vq;
+                    live_q[k] |= vq > 0.0f;
+                }
+            }
         }
-        const bool any = __ballot(live) != 0;
+        int dead = __ballot(live) == 0;                    // uniform over the wavefront
+        if constexpr (NQ > 0) {
+#pragma unroll
+            for (int k = 0; k < NQ; ++k) {
+                const bool dead_q = __ballot(live_q[k]) == 0;
+                dead |= (int)dead_q << (1 + k);
+                if (lane == 0) qs.dead[k][r] = dead_q;
+                // the lean form's mask: a dead row keeps its unquantised values; every lane reads back its own stores
+                if (qs.lean[k])
+                    for (int q = q0 + lane; q < q1; q += 64) qs.lean[k][q] = dead_q ? (float)val[q] : qs.val[k][q];
+            }
+        }
         if (lane == 0) {
-            b.dead_row[r] = !any;
+            b.dead_row[r] = dead & 1;
             // both counters are looked at first: hundreds of thousands of rows on one address serialise in L2 otherwise
-            if (!any && !__atomic_load_n(&a.ctr.extra(kDeadRows), __ATOMIC_RELAXED)) atomicOr(&a.ctr.extra(kDeadRows), 1);
+            if (dead & ~__atomic_load_n(&a.ctr.extra(kDeadRows), __ATOMIC_RELAXED)) atomicOr(&a.ctr.extra(kDeadRows), dead);
             if (q1 - q0 > __atomic_load_n(&a.ctr.extra(kMaxRow), __ATOMIC_RELAXED)) atomicMax(&a.ctr.extra(kMaxRow), q1 - q0);
         }
     }
@@ -263,9 +297,28 @@ extern "C" size_t sgx_node_batch_workspace_bytes(int n_nodes, int64_t nnz, int b
            region(sizeof(float) * (bd.max_edges + bd.max_nodes + 1));
 }
 
-extern "C" int sgx_node_batch_sample(sgx_node_batch *b, void *stream)
+namespace {
+
+template <int NQ>
+QuantSets<NQ> quant_sets(const sgx_node_batch_quant *q)
 {
-    if (!b) return SGX_ERR_NULL;
+    QuantSets<NQ> qs{};
+    if constexpr (NQ > 0) {
+        qs.qbits = q->qbits;
+        for (int k = 0; k < NQ; ++k) {
+            qs.inv_scale[k] = q->inv_scale_adj[k];
+            qs.zero[k] = q->zero_adj[k];
+            qs.val[k] = q->values_q[k];
+            qs.lean[k] = q->values_lean[k];
+            qs.dead[k] = q->dead_row_q[k];
+        }
+    }
+    return qs;
+}
+
+// sgx_node_batch_sample (q == NULL) and sgx_node_batch_sample_quant on their checked quantiser arguments
+int node_batch_sample(sgx_node_batch *b, sgx_node_batch_quant *q, void *stream)
+{
     if (!b->fanouts || !b->hop_nodes || !b->hop_edges) return SGX_ERR_NULL;
     Bounds bd;
     if (!bounds(b->n_nodes, b->nnz, b->batch, b->n_hops, b->fanouts, &bd)) return SGX_ERR_SHAPE;
@@ -287,6 +340,7 @@ extern "C" int sgx_node_batch_sample(sgx_node_batch *b, void *stream)
     for (int h = 0; h <= H; ++h) b->hop_nodes[h] = b->hop_edges[h] = 0;
     b->nnz_norm = b->nnz_fea = 0;
     b->has_dead_rows = b->max_row = 0;
+    if (q) q->has_dead_rows_q[0] = q->has_dead_rows_q[1] = 0;
     if (b->batch == 0) {
         SGX_HIP_CHECK(hipMemsetAsync(b->out_rowPtr, 0, sizeof(int32_t), s));
         SGX_HIP_CHECK(hipMemsetAsync(b->rowPtr_norm, 0, sizeof(int32_t), s));
@@ -313,10 +367,14 @@ extern "C" int sgx_node_batch_sample(sgx_node_batch *b, void *stream)
     hipLaunchKernelGGL(loops_kernel, dim3(rows), dim3(kBlock), 0, s, a);
     scan_launch(LoopMissing{a.ctr, a.miss, b->out_rowPtr, b->rowPtr_norm}, bd.max_nodes, bsum, s);
     hipLaunchKernelGGL(order_kernel, dim3(rows), dim3(kBlock), 0, s, a);
-    if (b->dtype == SGX_F16)
-        hipLaunchKernelGGL(values_kernel<f16>, dim3(rows), dim3(kBlock), 0, s, a);
+    if (q && q->n_sets == 2)
+        hipLaunchKernelGGL((values_kernel<float, 2>), dim3(rows), dim3(kBlock), 0, s, a, quant_sets<2>(q));
+    else if (q)
+        hipLaunchKernelGGL((values_kernel<float, 1>), dim3(rows), dim3(kBlock), 0, s, a, quant_sets<1>(q));
+    else if (b->dtype == SGX_F16)
+        hipLaunchKernelGGL((values_kernel<f16, 0>), dim3(rows), dim3(kBlock), 0, s, a, QuantSets<0>{});
     else
-        hipLaunchKernelGGL(values_kernel<float>, dim3(rows), dim3(kBlock), 0, s, a);
+        hipLaunchKernelGGL((values_kernel<float, 0>), dim3(rows), dim3(kBlock), 0, s, a, QuantSets<0>{});
     SGX_LAUNCH_CHECK();
     if (b->rowPtr_x)
         scan_launch(FeatureRows{a.ctr, b->n_id, b->rowPtr_x, b->rowPtr_fea, b->fea_capacity}, bd.max_nodes, bsum, s);
@@ -332,7 +390,28 @@ extern "C" int sgx_node_batch_sample(sgx_node_batch *b, void *stream)
     if (done != SGX_OK) return done;
     b->nnz_norm = extras[kNormNnz];
     b->nnz_fea = extras[kFeaNnz];
-    b->has_dead_rows = extras[kDeadRows];
+    b->has_dead_rows = extras[kDeadRows] & 1;
     b->max_row = extras[kMaxRow];
+    if (q)
+        for (int k = 0; k < q->n_sets; ++k) q->has_dead_rows_q[k] = (extras[kDeadRows] >> (1 + k)) & 1;
     return SGX_OK;
+}
+
+}  // namespace
+
+extern "C" int sgx_node_batch_sample(sgx_node_batch *b, void *stream)
+{
+    if (!b) return SGX_ERR_NULL;
+    return node_batch_sample(b, nullptr, stream);
+}
+
+extern "C" int sgx_node_batch_sample_quant(sgx_node_batch *b, sgx_node_batch_quant *q, void *stream)
+{
+    if (!b || !q) return SGX_ERR_NULL;
+    if (b->dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;   // the quantised layer works on fp32
+    if (q->n_sets != 1 && q->n_sets != 2) return SGX_ERR_SHAPE;
+    if (q->qbits != 8 && q->qbits != 4 && q->qbits != 2 && q->qbits != 1) return SGX_ERR_SHAPE;
+    for (int k = 0; k < q->n_sets; ++k)
+        if (!q->values_q[k] || !q->dead_row_q[k]) return SGX_ERR_NULL;
+    return node_batch_sample(b, q, stream);
 }

@@ -11,40 +11,23 @@
 // rounded sum in the reference (two torch ops), not one fma.
 #include "sgx_internal.h"
 #include "sgx_device.h"
+#include "quant_device.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-__device__ __forceinline__ float clipf(float v, float lo, float hi)
-{
-    // torch.clip: min(max(v, lo), hi); NaN propagates
-    v = v < lo ? lo : v;
-    return v > hi ? hi : v;
-}
+using sgx_quantizer::clipf;
+using sgx_quantizer::fake_quantize_value;
 
-// kind 0: quantization_ufbits (SG.py:253-265): unsigned grid 0 .. 2^q - 1
-// kind 1: quantization_fbits  (SG.py:238-251): signed grid -(2^(q-1) - 1) .. 2^(q-1) - 1
+// sgx_fake_quantize: fake_quantize_value (quant_device.h) over an array; kind 0 the unsigned grid, 1 the signed one
 __global__ __launch_bounds__(kBlock) void fake_quantize_kernel(int kind, int qbits, float inv_scale, float zero,
                                                                int64_t n, const float *__restrict__ x,
                                                                float *__restrict__ out)
 {
     const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     const int64_t stride = (int64_t)gridDim.x * kBlock;
-    const float lo = kind ? -(float)((1 << (qbits - 1)) - 1) : 0.0f;
-    const float hi = kind ? (float)((1 << (qbits - 1)) - 1) : (float)((1 << qbits) - 1);
-    const float back = 1.0f / (float)(1 << (qbits - 1));          // x_q / 2^(w_qbits - 1), SG.py:220
-    for (int64_t i = gid; i < n; i += stride) {
-        const float t = inv_scale * x[i] + zero;                   // 1 / s * x + z
-        float q;
-        if (qbits == 1 && kind == 1)
-            q = t < 0.0f ? -0.5f : 0.5f;                           // fake_quantization_b, SG.py:177-182
-        else if (qbits == 1)
-            q = clipf(rintf(t), 0.0f, 1.0f) * 0.5f;                // fake_quantization_b2, SG.py:184-189
-        else
-            q = clipf(rintf(t), lo, hi) * back;                    // fake_quantization, SG.py:191-235
-        out[i] = q;
-    }
+    for (int64_t i = gid; i < n; i += stride) out[i] = fake_quantize_value(kind, qbits, inv_scale, zero, x[i]);
 }
 
 // SG.py:607-616: Wh / 2^scale_fea, clip to +-(2^iq - 1) / 2^iq, torch.round(decimals = iq - 1)

@@ -232,7 +232,7 @@ class Csr:
 
     def quantized(self, qc):
         """The adjacency on the unsigned w_qbits grid (SG.py:626), quantised once per graph and constants."""
-        key = (qc.w_qbits, qc.a_s, qc.a_z)
+        key = _adj_quant_key(qc)
         if key not in self._quantized:
             self._quantized[key] = Csr(self.rowptr, self.col, fake_quantize(self.val, 0, qc.w_qbits, qc.a_s, qc.a_z),
                                        self.n_cols, self._plan)
@@ -1110,15 +1110,27 @@ def feature_csr(x):
     return fea.with_facts(max_row=longest)
 
 
+def _adj_quant_key(qc):
+    """The key Csr.quantized files a quantised adjacency under: the constants the adjacency's quantiser reads."""
+    return (qc.w_qbits, qc.a_s, qc.a_z)
+
+
 def sample_node_batch(csr, seeds, fanouts, seed=0, step=0, fill=0, dtype=torch.float32, edge_weight=None, features=None,
-                      y=None, masks=()):
+                      y=None, masks=(), quant=None):
     """sample_neighbors plus, on the device right behind it and inside the same single synchronisation
     (sgx_node_batch_sample, rule in include/sgx.h): the normalised adjacency sym_norm2 gives for the sampled rows,
     the rows n_id of `features` (a feature_csr) as the batch's feature Csr, y[n_id] (int64) and each of up to three
-    bool `masks` at n_id.  edge_weight: fp32 [csr.nnz] weights of the graph's edges (None = 1).  -> NodeSample."""
+    bool `masks` at n_id.  edge_weight: fp32 [csr.nnz] weights of the graph's edges (None = 1).  -> NodeSample.
+    quant (a quant.QuantConstants, fp32 only): the batch is also ready for the quantised layers
+    (sgx_node_batch_sample_quant, same single synchronisation): adj_norm.quantized(qc) for quant and for
+    quant.second_layer() is delivered -- the values on the unsigned w_qbits grid with their dead-row mask, flag and
+    longest row recorded, and the mask values of the lean GAT backward (sgrace._lean_mask) -- so that the layers launch no
+    quantiser for the adjacency and read nothing back."""
     _dev(seeds, "seeds")
     fan = [int(k) for k in fanouts]
     dev = csr.rowptr.device
+    if quant is not None and dtype != torch.float32:
+        raise ValueError("sample_node_batch: quant needs dtype=torch.float32 (the quantised layer works on float32 buffers)")
     seeds = seeds.to(torch.int32).contiguous()
     B, H, n = seeds.numel(), len(fan), csr.n_rows
     masks = list(masks)
@@ -1181,14 +1193,34 @@ def sample_node_batch(csr, seeds, fanouts, seed=0, step=0, fill=0, dtype=torch.f
         m_out.append(torch.empty(max(mn, 1), dtype=torch.bool, device=dev))
         b.mask[k], b.mask_out[k] = m.data_ptr(), m_out[k].data_ptr()
     b.workspace, b.workspace_bytes = ws.data_ptr(), ws.numel()
-    status = lib.sgx_node_batch_sample(ctypes.byref(b), _stream())
+    if quant is None:
+        status = lib.sgx_node_batch_sample(ctypes.byref(b), _stream())
+    else:
+        # one constant set per distinct key of the two layers' constants (the demo's layers share the adjacency's)
+        sets = {_adj_quant_key(qc): qc for qc in (quant, quant.second_layer())}
+        q = _lib.NodeBatchQuant()
+        q.n_sets, q.qbits = len(sets), int(quant.w_qbits)
+        q_out = []
+        for k, qc in enumerate(sets.values()):
+            q_val, q_lean = (torch.empty(max(me + mn, 1), dtype=torch.float32, device=dev) for _ in range(2))
+            q_dead = torch.empty(max(mn, 1), dtype=torch.bool, device=dev)
+            q.inv_scale_adj[k], q.zero_adj[k] = float(1 / qc.a_s), float(qc.a_z)
+            q.values_q[k], q.dead_row_q[k], q.values_lean[k] = q_val.data_ptr(), q_dead.data_ptr(), q_lean.data_ptr()
+            q_out.append((q_val, q_dead, q_lean))
+        status = lib.sgx_node_batch_sample_quant(ctypes.byref(b), ctypes.byref(q), _stream())
     if status not in (0, _lib.SGX_ERR_SEEDS):
         node_map.fill_(SAMPLE_SENTINEL)                 # (sgx.h: the map is restored on success and on SGX_ERR_SEEDS only)
-    check(status, "sgx_node_batch_sample")
+    check(status, "sgx_node_batch_sample" if quant is None else "sgx_node_batch_sample_quant")
     N, E, nn, nf = hop_nodes[H], hop_edges[H], b.nnz_norm, b.nnz_fea
     adj = Csr(rowptr[:N + 1], col[:E], torch.ones(E, dtype=torch.float32, device=dev), N)
     s = NodeSample(n_id[:N], adj, pos[:E], B, hop_nodes[:], hop_edges[:])
     s.adj_norm = Csr(n_rowptr[:N + 1], n_col[:nn], n_val[:nn], N).with_facts(dead[:N], b.has_dead_rows, b.max_row)
+    if quant is not None:
+        A = s.adj_norm
+        for k, (key, (q_val, q_dead, q_lean)) in enumerate(zip(sets, q_out)):
+            Q = Csr(A.rowptr, A.col[:nn], q_val[:nn], N).with_facts(q_dead[:N], q.has_dead_rows_q[k], b.max_row)
+            Q._lean_values = Csr(A.rowptr, A.col[:nn], q_lean[:nn], N)
+            A._quantized[key] = Q
     s.edge_index, s.edge_index_agg = ei[:2 * E].view(2, E), ei_agg[:2 * E].view(2, E)
     s.fea = None
     if features is not None:

@@ -227,11 +227,22 @@ class NeighborLoader:
     entries ops.feature_csr32 looks up (config.accb = 1 over CSR features), and adj_norm._transpose_pattern = (A^T,
     order), what the default GAT backward looks up -- from two sgx_csr_transpose calls on the same stream behind the
     sampler, with no synchronisation of their own (a transposed matrix that wants a plan by ops.csr_transpose's rule
-    still builds it, with the plan's read-back)."""
+    still builds it, with the plan's read-back).
+
+    quant=qc (a quant.QuantConstants such as sgrace.quant_constants; with prepare and dtype float32): the batches are ready
+    for the QUANTISED layers as well -- adj_norm.quantized(qc) and .quantized(qc.second_layer()), what the layers look up,
+    are delivered with their dead-row facts and the lean GAT backward's mask values, from the sampler's own launches and
+    single read-back (ops.sample_node_batch(quant=)).  A training step of the quantised model then synchronises nowhere
+    outside the sampler."""
 
     def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0, prepare=None, fill=0,
-                 dtype=torch.float32, transposed=False):
+                 dtype=torch.float32, transposed=False, quant=None):
         from . import ops
+        if quant is not None and not prepare:
+            raise ValueError("quant needs prepare='sym_norm2'")
+        if quant is not None and dtype != torch.float32:
+            raise ValueError("quant needs dtype=torch.float32: the quantised layer works on float32 buffers")
+        self.quant = quant
         self.data, self.num_neighbors = data, [int(k) for k in num_neighbors]
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
         x, ei = data.x, data.edge_index
@@ -281,7 +292,8 @@ class NeighborLoader:
     def _prepared(self, seeds, input_id, step):
         from . import ops
         s = ops.sample_node_batch(self.csr, seeds, self.num_neighbors, seed=self.seed, step=step, fill=self.fill,
-                                  dtype=self.dtype, features=self.fea, y=self.y, masks=[m for _, m in self.masks])
+                                  dtype=self.dtype, features=self.fea, y=self.y, masks=[m for _, m in self.masks],
+                                  quant=self.quant)
         x = ops.pack_rows(self.data.x, s.n_id)
         A, n = s.adj_norm, s.n_id.numel()
         ops.attach(x, ("fea_csr", self.dtype), s.fea)

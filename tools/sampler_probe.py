@@ -21,6 +21,12 @@ of examples/sgrace_node_classification.py (GCN and GAT).  One JSON line per meas
                                                    # loader with transposed=True (X^T and the GAT backward's transposed
                                                    # pattern built behind the sampler), in the same windows
                                                    # (profiles/r11_step_*.jsonl)
+                                                   # --quant QBITS: the QUANTISED model (config.fake_quantization and
+                                                   # hardware_quantize, w_qbits = QBITS), GCN, GAT and lean GAT, through
+                                                   # the prepared loader without quant= (arm "prepared") and with it (arm
+                                                   # "prepared_q", beside --arms), and the preparation alone of both
+                                                   # (profiles/r12_node_batch_quant.jsonl; --arms prepared runs on a tree
+                                                   # without quant=)
 """
 import argparse
 import json
@@ -130,11 +136,11 @@ def timed(fn, reps):
     return (time.perf_counter() - t0) / reps * 1e3, out
 
 
-def node_batch(arms, trace, accbs=(0,)):
+def node_batch(arms, trace, accbs=(0,), qbits=None):
     """The training step (loader, forward, loss, backward, Adam) per loader, and the preparation alone."""
     import importlib.util
     import statistics
-    from sgracex1_amd import config, pyg_lite, sgrace
+    from sgracex1_amd import config, pyg_lite, quant, sgrace
     dev = torch.device("cuda")
     spec = importlib.util.spec_from_file_location("nc", os.path.join(ROOT, "examples", "sgrace_node_classification.py"))
     mod = importlib.util.module_from_spec(spec)
@@ -167,10 +173,16 @@ def node_batch(arms, trace, accbs=(0,)):
             kw = {"prepare": "sym_norm2"} if arm.startswith("prepared") else {}
             if arm == "prepared_t":
                 kw["transposed"] = True
+            if arm == "prepared_q":
+                kw["quant"] = quant.constants(qbits)
             loaders[arm] = pyg_lite.NeighborLoader(data, fan, batch_size=bs, input_nodes=train, shuffle=True, seed=1, **kw)
         del ei
-        for attention in (0, 1):
+        for attention, lean in ((0, False), (1, False)) + (((1, True),) if qbits else ()):
             config.acc, config.device, config.compute_attention = 1, "cuda", attention
+            config.gat_edge_outputs = 0 if lean else 1
+            if qbits:
+                config.fake_quantization = config.hardware_quantize = 1
+                config.w_qbits = qbits
             sgrace.init_SGRACE()
             steps = {}
             # a leg = (loader arm, config.accb): every leg has its own model and takes its turn in every window
@@ -217,11 +229,22 @@ def node_batch(arms, trace, accbs=(0,)):
             for arm, accb in legs:
                 v = times[(arm, accb)]
                 print(json.dumps({"end_to_end": "mini-batch training step (loader + forward + loss + backward + Adam)",
-                                  "loader": arm, "accb": accb, "model": "GAT" if attention else "GCN", "graph": name, "batch": bs,
+                                  "loader": arm, "accb": accb, "model": ("GAT lean" if lean else "GAT") if attention else "GCN",
+                                  **({"w_qbits": qbits} if qbits else {}), "graph": name, "batch": bs,
                                   "fanouts": fan, "batch_nodes_last": b.num_nodes, "step_ms_median": round(statistics.median(v), 4),
                                   "step_ms_min": round(min(v), 4), "step_ms_max": round(max(v), 4), "windows": windows,
                                   "steps_per_window": reps}), flush=True)
-        if "prepared" in arms and not trace:
+        config.gat_edge_outputs = 1
+        if qbits and not trace:
+            # the batch preparation alone, on the same seeds, with and without the quantised adjacency
+            count = iter(range(10 ** 9))
+            for arm in arms:
+                if arm.startswith("prepared"):
+                    ld = loaders[arm]
+                    ms, _ = timed(lambda: ld._prepared(ld.input_nodes[:bs], None, next(count)), 50)
+                    print(json.dumps({"batch_preparation": "NeighborLoader._prepared, stream synchronised", "loader": arm,
+                                      "w_qbits": qbits, "graph": name, "batch": bs, "fanouts": fan, "ms": round(ms, 4)}), flush=True)
+        elif "prepared" in arms and not trace:
             # the batch preparation alone, on the same seeds: one device call against the sampler plus today's torch ops
             ld = loaders["prepared"]
             seeds = ld.input_nodes[:bs]
@@ -261,6 +284,9 @@ def main():
     ap.add_argument("--label", default=None, help="--node-batch: a tag printed with the run (which checkout this is)")
     ap.add_argument("--arms", default="default,prepared")
     ap.add_argument("--trace", action="store_true")
+    ap.add_argument("--quant", type=int, default=None, choices=[8, 4, 2, 1],
+                    help="--node-batch: the quantised model at this w_qbits; adds the arm prepared_q where --arms holds prepared_q "
+                         "or is left at its default")
     ap.add_argument("--transposed", action="store_true", help="--node-batch: add the arm prepared_t (the prepared loader with "
                                                               "transposed=True) to the same windows")
     a = ap.parse_args()
@@ -268,7 +294,9 @@ def main():
         if a.label:
             print(json.dumps({"label": a.label}), flush=True)
         arms = a.arms.split(",") + (["prepared_t"] if a.transposed else [])
-        return node_batch(arms, a.trace, tuple(int(b) for b in a.accb.split(",")))
+        if a.quant and a.arms == "default,prepared":
+            arms = ["prepared", "prepared_q"] + arms[2:]
+        return node_batch(arms, a.trace, tuple(int(b) for b in a.accb.split(",")), a.quant)
     dev = torch.device("cuda")
     shapes = [("products shape uniform", lambda: graphs.uniform_graph(2_450_000, 122_000_000, dtype=torch.float32,
                                                                       normalize=False)),
