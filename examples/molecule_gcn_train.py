@@ -15,6 +15,11 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
         DataLoader(shuffle=True)), collated on the GPU (pyg_lite.GraphLoader), or on the host and copied
         (pyg_lite.DataLoader) with --host-loader; both draw their permutations from a generator seeded 12345.
         The default 0 keeps the single unshuffled batch.
+    python examples/molecule_gcn_train.py --model gat [--layer-count 2]
+        --model gat = the SGRACE demo's graph classifier of attention layers (sgrace.GAT_POOL_PYNQ: sym_norm2, two
+        GATConv_SGRACE layers with the edge softmax, mean pool, head; fp32 layer buffers), trained layer by layer through
+        FPYNQ_GAT's autograd; --layer-count 2 = the accuracy passes run the whole model in one call
+        (sgx_gat_stack_forward).  It prints accuracy only: the reference records no GAT output (parity unpinned).
 """
 import argparse
 import json
@@ -39,7 +44,10 @@ def main():
     ap.add_argument("--train-stack", action="store_true")
     ap.add_argument("--batch-size", type=int, default=0)
     ap.add_argument("--host-loader", action="store_true")
+    ap.add_argument("--model", choices=["gcn", "gat"], default="gcn")
     args = ap.parse_args()
+    if args.model == "gat" and (args.train_stack or args.acc != 1):
+        ap.error("--model gat trains layer by layer on the kernels (no --train-stack, --acc 1)")
     if args.train_stack and args.layer_count < 2:
         ap.error("--train-stack needs --layer-count >= 2")
     if args.host_loader and args.batch_size <= 0:
@@ -55,9 +63,19 @@ def main():
         gen = torch.Generator().manual_seed(12345)
         loader = (G.DataLoader(graphs[:2000], batch_size=args.batch_size, shuffle=True, generator=gen) if args.host_loader
                   else G.GraphLoader(graphs[:2000], batch_size=args.batch_size, shuffle=True, generator=gen, device=dev))
-    my_ip = pynq_shim.Overlay("gnn_all.bit").mmult_top_0      # MOL cell 11
-    my_ip.register_map.layer_count = args.layer_count          # layers per call (SG.py:1862)
-    model = M.GCN_PYNQ(64, 7, 2, my_ip, train_stack=args.train_stack).to(dev)   # MOL cell 18 (seed 12345 inside)
+    if args.model == "gat":
+        from sgracex1_amd import config, sgrace
+        config.acc, config.compute_attention = 1, 1
+        my_ip = sgrace.init_SGRACE()
+        my_ip.register_map.layer_count = args.layer_count
+        torch.manual_seed(12345)
+        gat = sgrace.GAT_POOL_PYNQ(7, 64, 2).to(dev)           # demo_sgrace.py:137-190
+        model = lambda _acc, x, edge_index, batch: gat(x, edge_index, batch)
+        model.train, model.eval, model.parameters = gat.train, gat.eval, gat.parameters
+    else:
+        my_ip = pynq_shim.Overlay("gnn_all.bit").mmult_top_0      # MOL cell 11
+        my_ip.register_map.layer_count = args.layer_count          # layers per call (SG.py:1862)
+        model = M.GCN_PYNQ(64, 7, 2, my_ip, train_stack=args.train_stack).to(dev)   # MOL cell 18 (seed 12345 inside)
     opt = torch.optim.Adam(model.parameters(), lr=0.01)       # MOL cell 20
     crit = torch.nn.CrossEntropyLoss()
 
@@ -89,8 +107,8 @@ def main():
         print(f"Epoch: {epoch:03d}, Train Acc: {tr:.4f}, Test Acc: {te:.4f}, loss {float(loss.detach()):.4f}, "
               f"step {dt * 1e3:.2f} ms", flush=True)
     print(json.dumps({"best_test_acc": best, "final_test_acc": log[-1]["test_acc"], "epochs": args.epochs,
-                      "acc": args.acc, "layer_count": args.layer_count, "train_stack": args.train_stack,
-                      "batch_size": args.batch_size, "host_loader": args.host_loader, "reference": "0.76 at epoch 34 (notebook cell 20 output)"}))
+                      "acc": args.acc, "model": args.model, "layer_count": args.layer_count, "train_stack": args.train_stack,
+                      "batch_size": args.batch_size, "host_loader": args.host_loader, "reference": "0.76 at epoch 34 (notebook cell 20 output)" if args.model == "gcn" else "none (parity unpinned)"}))
 
 
 if __name__ == "__main__":

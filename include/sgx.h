@@ -536,7 +536,7 @@ int sgx_sample_neighbors(const int32_t *rowPtr, const int32_t *columnIndex, int 
  * Where the plan fits (no graph over its row budget) and every width is within the fused kernel's limits
  * (M_fea, P_w <= the plan's max_width <= 256; a sparse layer 0 may have any M_fea), one launch computes it all.
  * Otherwise sgx_stack_forward runs the chained kernels through the workspace -- same results, so a call always
- * works (single large graphs such as Cora take this path).  Quantised and GAT layers are not offered here. */
+ * works (single large graphs such as Cora take this path).  Quantised layers are not offered here; GAT layers: `sgx_gat_stack_forward`. */
 typedef struct sgx_batch_plan sgx_batch_plan;
 
 typedef struct sgx_stack_layer {
@@ -977,6 +977,77 @@ int sgx_csr_transpose(int dtype_values, int n_rows, int n_cols, int64_t nnz,
                       const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
                       int32_t *rowPtr_t, int32_t *columnIndex_t, void *values_t, int32_t *order,
                       void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- GAT layers in the small-graph stack ------------------------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_gat_stack_forward is sgx_stack_forward with a per-layer choice of the aggregate: the reference's `layer_count`
+ * register sits on the same bitstream as `gat_mode` (SG.py:1862).  It takes the same sgx_batch_plan, of either kind --
+ * the row budget and the grouping of plans are those of sgx_stack_forward, so one plan (cached on a batch) serves the
+ * GCN and the GAT calls -- and runs the same one launch: a 256-thread workgroup per group of whole graphs, every stage
+ * in LDS, nothing exchanged between workgroups (no flags, no grid barrier; the grid is the plan's group count).
+ *
+ * Semantics, per layer l:
+ *     H_l = dtype(X_l . W_l)            exactly as in sgx_stack_forward: the sparse layer 0 by the fma chain in CSR order,
+ *                                       dense layers in the MFMA layout and K order of sgx_xw_dense -- bit-equal to them
+ *   gat_mode = 0:
+ *     D_l = dtype(act_l(A . H_l))       the GCN layer of sgx_stack_forward, bit for bit
+ *   gat_mode = 1: sgx_gat_aggregate's single-head formula on H_l as stored, attention = [a1 ; a2], [2 * P_w] in dtype:
+ *     s1_i = H_i . a1,  s2_c = H_c . a2                                  in fp32
+ *     x_e  = LeakyReLU_alpha(s1_i + s2_c)                                on stored entries e = (i, c) with values[e] > 0, the
+ *                                                                        stored value as stored (+0.0, -0.0 and negative
+ *                                                                        values are masked, positive subnormals are live)
+ *     m_i  = max over the row's live entries;  S_e = exp(x_e - m_i) / sum_live exp(x - m_i)
+ *     D_i  = dtype(act_l(sum_e S_e H_c))                                 summed in fp32
+ *     a row without a live entry gives 0 (the gat_fill_dead_rows = 0 rule; the mean-of-all-rows rule reaches across the
+ *     batch's graphs and is not offered).  E, S and the row statistics are not outputs: this is the inference path.
+ *     One head only.
+ *   readout and head: as in sgx_stack_forward, the same bits for the same D_{n_layers-1}.
+ * Summation order of the attention path is not pinned: its results lie inside the bound of tests/_gat_ref.py (whose
+ * docstring derives it; the exponential is the hardware's v_exp_f32 on (x - m) log2(e), the division one reciprocal of
+ * the sum and a product) and are the same bits on every run, on every device and for every grouping of the graphs: no
+ * atomics, and no order that depends on the grid -- a row's sums are split over lanes by the layer's width alone.
+ *
+ * Where the plan fits and every width is within the fused kernel's limits (those of sgx_stack_forward), one launch
+ * computes it all; sgx_gat_stack_workspace_bytes is 0 exactly then.  The four fp32 arrays s1, s2, m, 1 / sum of a group's
+ * rows lie in LDS behind the two tiles (16 bytes per row of the budget, at most 2 KiB; where the tiles fill 64 KiB --
+ * fp32 at width 252 -- the launch asks for that much more, still two workgroups per CU).  Otherwise the call runs the
+ * chained kernels through the workspace: per layer X.W as in sgx_stack_forward's chain, then
+ * sgx_gat_aggregate(fill_dead_rows = 0, one head, no plan) or the GCN aggregate, then sgx_readout_mean_linear -- inside
+ * the same bound, so a call always works.
+ *
+ * Argument errors, returned before anything reaches the device: those of sgx_stack_forward, and attention NULL on a layer
+ * with gat_mode = 1: SGX_ERR_NULL; gat_mode outside {0, 1}: SGX_ERR_UNSUPPORTED.  Capturable on the fused path: no
+ * allocation and no host synchronisation. */
+typedef struct sgx_gat_stack_layer {
+    int32_t gemm_mode;    /* as sgx_stack_layer */
+    int32_t relu;
+    int32_t M_fea, P_w;
+    const void *B;
+    void *D;
+    int64_t ldd;
+    int32_t gat_mode;     /* 0: GCN aggregate (A . H); 1: the edge softmax above */
+    const void *attention;   /* gat_mode = 1: [2 * P_w] in dtype, a1 then a2, as sgx_layer_desc.attention */
+    float alpha;          /* LeakyReLU slope of the scores */
+} sgx_gat_stack_layer;
+
+typedef struct sgx_gat_stack_desc {
+    int32_t dtype, n_layers;                   /* as sgx_stack_desc, field for field */
+    int32_t n_rows, n_graphs;
+    const int32_t *graph_ptr;
+    const int32_t *rowPtr_adj, *columnIndex_adj; const void *values_adj;
+    const int32_t *rowPtr_fea, *columnIndex_fea; const void *values_fea;
+    sgx_gat_stack_layer layer[4];
+    int32_t C;
+    const float *W_head, *bias;
+    float *pooled, *logits;
+    const sgx_batch_plan *plan;                /* from sgx_batch_plan_create / _create_ex / _create_known, either kind */
+    void *workspace; size_t workspace_bytes;   /* sgx_gat_stack_workspace_bytes(d), 256-byte aligned (0 on the fused path) */
+} sgx_gat_stack_desc;
+
+/* 0 for the fused path, the chained path's scratch otherwise (and for a bad descriptor) */
+size_t sgx_gat_stack_workspace_bytes(const sgx_gat_stack_desc *d);
+int sgx_gat_stack_forward(const sgx_gat_stack_desc *d, void *stream);
 
 /* A plain streaming copy (16 bytes per lane, non-temporal, each workgroup on a contiguous chunk), the kernel the attainable HBM rate of a device is
  * measured with next to the nominal 8 TB/s (bench.py reports it as roofline.stream_copy_GBps_this_device).

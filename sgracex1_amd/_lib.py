@@ -47,6 +47,7 @@ SYMBOLS = [
     "sgx_layer_backward_workspace_bytes", "sgx_layer_backward", "sgx_gat_attention_grad_workspace_bytes",
     "sgx_gat_attention_grad",
     "sgx_csr_transpose_workspace_bytes", "sgx_csr_transpose",
+    "sgx_gat_stack_workspace_bytes", "sgx_gat_stack_forward",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -122,6 +123,18 @@ class StackDesc(ctypes.Structure):
         ("plan", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
+
+
+class GatStackLayer(ctypes.Structure):
+    """struct sgx_gat_stack_layer -- field order and types must match include/sgx.h."""
+    _fields_ = StackLayer._fields_ + [
+        ("gat_mode", ctypes.c_int32), ("attention", ctypes.c_void_p), ("alpha", ctypes.c_float),
+    ]
+
+
+class GatStackDesc(ctypes.Structure):
+    """struct sgx_gat_stack_desc -- field order and types must match include/sgx.h."""
+    _fields_ = [(n, GatStackLayer * 4 if n == "layer" else t) for n, t in StackDesc._fields_]
 
 
 class StackGradLayer(ctypes.Structure):
@@ -357,6 +370,10 @@ def _load():
     lib.sgx_stack_forward.restype = c_int
     lib.sgx_batch_plan_create_ex.argtypes = [c_int, c_int, c_int, vp, vp, vp, c_int, c_int, ctypes.POINTER(vp), vp]
     lib.sgx_batch_plan_create_ex.restype = c_int
+    lib.sgx_gat_stack_workspace_bytes.argtypes = [ctypes.POINTER(GatStackDesc)]
+    lib.sgx_gat_stack_workspace_bytes.restype = sz
+    lib.sgx_gat_stack_forward.argtypes = [ctypes.POINTER(GatStackDesc), vp]
+    lib.sgx_gat_stack_forward.restype = c_int
     lib.sgx_stack_backward_workspace_bytes.argtypes = [ctypes.POINTER(StackGradDesc)]
     lib.sgx_stack_backward_workspace_bytes.restype = sz
     lib.sgx_stack_backward.argtypes = [ctypes.POINTER(StackGradDesc), vp]

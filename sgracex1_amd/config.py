@@ -37,7 +37,8 @@ _FLAGS = {
     "layer_count": (1, "layers per hardware call (SG.py:1862).  Live for the graph-classification model: with "
                        "my_ip.register_map.layer_count >= 2, GCN_PYNQ's eval forward over a sorted batch of graphs runs "
                        "both layers, the mean pool and the head in one call (sgx_stack_forward, bit-equal to the "
-                       "layer-by-layer path); training and every other model run one launch per stage"),
+                       "layer-by-layer path), and so does sgrace.GAT_POOL_PYNQ's (sgx_gat_stack_forward; GAT layers inside "
+                       "the float64 bound, parity unpinned); training and every other model run one launch per stage"),
     # -- accepted, no effect on this path --------------------------------------------------------
     "load_weights": (1, "FPGA weight preload switch"),
     "stream_mode": (0, "FPGA streaming I/O switch"),

@@ -1520,9 +1520,31 @@ def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, hea
     pooled means [G, P_last] fp32 without one, or with graph_ptr None the last layer's output [N, P_last]; with
     want_layer_outputs also the list of every layer's output D_l [N, P_l] (keep: one flag per layer, which of them to
     write; the others are None)."""
+    return _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, want_layer_outputs, want_pooled, plan,
+                          keep)
+
+
+def gat_stack_forward(adj, x, weights_t, attentions, relus, graph_ptr, head_weight=None, head_bias=None, alpha=0.2,
+                      want_layer_outputs=False, plan=None):
+    """gcn_stack_forward with a per-layer choice of the aggregate (sgx_gat_stack_forward, include/sgx.h "GAT layers in the
+    small-graph stack"): attentions[l] is layer l's attention vector [2 * P_l] (a1 then a2) in adj's dtype -- the
+    single-head edge softmax of gat_aggregate on H_l, rows without a live entry giving 0 -- or None for a GCN layer.  One
+    launch where the batch's graphs fit the plan (the plan of gcn_stack_forward: BatchPlan.cached), the chained kernels
+    otherwise.  Arguments and results as gcn_stack_forward's; alpha is the LeakyReLU slope of the scores."""
+    if len(attentions) != len(weights_t):
+        raise ValueError("gat_stack_forward takes one attention vector (or None) per layer")
+    return _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, want_layer_outputs, False, plan, None,
+                          attentions=list(attentions), alpha=alpha)
+
+
+def _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, want_layer_outputs, want_pooled, plan, keep,
+                   attentions=None, alpha=0.2):
+    """The descriptor of sgx_stack_forward (attentions None) or sgx_gat_stack_forward, its workspace and the call."""
+    gat = attentions is not None
+    name = "sgx_gat_stack" if gat else "sgx_stack"
     n = len(weights_t)
     if not 1 <= n <= 4 or len(relus) != n:
-        raise ValueError("gcn_stack_forward takes 1 to 4 layers and one relu flag per layer")
+        raise ValueError(f"{'gat' if gat else 'gcn'}_stack_forward takes 1 to 4 layers and one relu flag per layer")
     dtype = adj.val.dtype
     code = dtype_code(dtype)
     N, dev = adj.n_rows, adj.val.device
@@ -1533,7 +1555,7 @@ def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, hea
         graph_ptr = cached_on(adj.rowptr, ("one_graph_ptr",),
                               lambda: torch.tensor([0, N], dtype=torch.int32, device=dev))
     _dev(graph_ptr, "graph_ptr")
-    d = _lib.StackDesc()
+    d = _lib.GatStackDesc() if gat else _lib.StackDesc()
     d.dtype, d.n_layers, d.n_rows, d.n_graphs = code, n, N, graph_ptr.numel() - 1
     d.graph_ptr = graph_ptr.data_ptr()
     d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
@@ -1559,6 +1581,11 @@ def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, hea
         L = d.layer[l]
         L.gemm_mode = 0 if (l == 0 and sparse) else 1
         L.relu, L.M_fea, L.P_w, L.B = int(bool(relu)), M, P, Wt.data_ptr()
+        if gat and attentions[l] is not None:
+            att = attentions[l] = _dev(attentions[l], f"attentions[{l}]").reshape(-1)      # (held until the call returns)
+            if att.dtype != dtype or att.numel() != 2 * P:
+                raise ValueError(f"attentions[{l}] must hold 2 * {P} elements of {dtype}")
+            L.gat_mode, L.attention, L.alpha = 1, att.data_ptr(), float(alpha)
         if (want_layer_outputs and (keep is None or keep[l])) or (not readout and l == n - 1):
             D = torch.empty((N, P), dtype=dtype, device=dev)
             L.D, L.ldd = D.data_ptr(), P
@@ -1588,11 +1615,11 @@ def gcn_stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight=None, hea
         if plan is None:
             check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create")
     d.plan = plan.handle
-    nbytes = lib.sgx_stack_workspace_bytes(ctypes.byref(d))
+    nbytes = getattr(lib, name + "_workspace_bytes")(ctypes.byref(d))
     if nbytes:
         ws = _workspace(dev, nbytes)
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(lib.sgx_stack_forward(ctypes.byref(d), _stream()), "sgx_stack_forward")
+    check(getattr(lib, name + "_forward")(ctypes.byref(d), _stream()), name + "_forward")
     if not readout:
         out = outs[-1]
     elif logits is not None:

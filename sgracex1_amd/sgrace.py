@@ -8,6 +8,8 @@
     GATConv_SGRACE            SG.py:1164-1260  forward(compute_attention, dense, relu, input,
                                                edge_index, norm, adj)
     GAT_PYNQ                  demo/emulation/demo_sgrace.py:271-400 (the demo's two-layer model)
+    GAT_POOL_PYNQ             demo/emulation/demo_sgrace.py:137-190 (the demo's graph classifier: the same two layers,
+                                               global_mean_pool and a Linear head)
     init_SGRACE               SG.py:1271
 
 `config.acc == 1` runs the layer on the GPU through the C ABI (GCN aggregate or single-head GAT
@@ -41,7 +43,7 @@ import numpy as np
 
 from . import config, ops, quant
 from .molecule_gcn import RPYNQ  # noqa: F401  (same Function in both reference files)
-from .pyg_lite import add_remaining_self_loops, sort_edge_index
+from .pyg_lite import add_remaining_self_loops, global_mean_pool, sort_edge_index
 
 my_ip = None
 quant_constants = None        # set by init_SGRACE when the quantised path is selected
@@ -393,6 +395,72 @@ class GAT_PYNQ(Module):
         x = self.conv22(config.compute_attention, 1, 0, x, ei, norm, adj)
         x = F.dropout(x.float(), p=0.5, training=self.training)
         return self.lin(x)
+
+
+class GAT_POOL_PYNQ(Module):
+    """The graph classifier of the SGRACE demo (demo/emulation/demo_sgrace.py:137-190) on a PyG batch of graphs:
+    sym_norm2 -> GATConv_SGRACE(compute_attention, dense=0, relu=1) -> Relu_SGRACE -> GATConv_SGRACE(dense=1, relu=0) ->
+    global_mean_pool -> dropout(0.5) -> Linear.  Training runs layer by layer through FPYNQ_GAT's autograd.
+
+    With register layer_count >= 2 (layers per hardware call, SG.py:1862) the eval forward runs as ONE call,
+    ops.gat_stack_forward (GCN layers in it when config.compute_attention == 0), where all of these hold: eval mode with
+    gradients off, config.acc == 1, the quantiser off, `batch` sorted with no edge between two of its graphs, and no row
+    of the adjacency without a positive entry (the stack gives such a row 0, the layer the mean of all rows; sym_norm2's
+    self loops leave none).  Every other case runs the layers one by one."""
+
+    def __init__(self, num_node_features, hidden_channels, num_classes):
+        super(GAT_POOL_PYNQ, self).__init__()
+        self.att1 = GATConv_SGRACE(num_node_features, hidden_channels, 1)
+        self.att2 = GATConv_SGRACE(hidden_channels, hidden_channels, 1)
+        self.reluh = Relu_SGRACE()
+        self.lin = torch.nn.Linear(hidden_channels, num_classes)
+
+    def forward(self, x, edge_index, batch):
+        def normalise():                                          # once per batch, not per call
+            ei, norm = sym_norm2(edge_index, x.size(0))
+            adj = _edge_csr(None, ei, norm, x.size(0), _torch_dtype()) if config.acc == 1 else \
+                torch.sparse_coo_tensor(ei, norm, (x.size(0), x.size(0)))
+            return ei, norm, adj
+
+        ei, norm, adj = ops.cached_on(edge_index, ("sym_norm2", x.size(0), config.acc, _torch_dtype()), normalise)
+        if config.acc == 1 and not self.training and not torch.is_grad_enabled() and not _quantised() and \
+                my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2:
+            out = self._forward_stack(x, adj, batch)
+            if out is not None:
+                return out
+        x = self.att1(config.compute_attention, 0, 1, x, ei, norm, adj)
+        x = self.reluh(x)
+        x = self.att2(config.compute_attention, 1, 0, x, ei, norm, adj)
+        # a sorted `batch` makes a graph a row segment; an unsorted one does not
+        ptr = ops.graph_ptr_of(batch) if config.acc == 1 else None
+        if ptr is not None and not self.training and not torch.is_grad_enabled():
+            return ops.readout_mean_linear(x.contiguous(), ptr, self.lin.weight, self.lin.bias)
+        if ptr is not None:
+            x = ops.ReadoutMean.apply(x, ptr, batch.numel() == x.shape[0])
+        else:
+            x = global_mean_pool(x.float(), batch)
+        x = F.dropout(x, p=0.5, training=self.training)
+        return self.lin(x)
+
+    def _forward_stack(self, x, adj, batch):
+        """Both layers, the mean pool and the head through ops.gat_stack_forward; None (the caller then runs the layers
+        one by one) where the stack does not compute what they do."""
+        dt = _torch_dtype()
+        ptr = ops.graph_ptr_of(batch)
+        gat = int(config.compute_attention)
+        if ptr is None or (gat and (self.att1.alpha != self.att2.alpha or adj.has_dead_rows is not False)):
+            return None
+        layers = (self.att1, self.att2)
+        plan = ops.BatchPlan.cached(adj, ptr, max(self.att1.weight.shape[1], self.att2.weight.shape[0],
+                                                  self.att2.weight.shape[1]))
+        if plan is None:
+            return None
+        fea = ops.cached_on(x, ("fea_csr", dt), lambda: ops.Csr.from_dense(
+            x.detach() if x.layout == torch.strided else x.detach().to_dense(), dt))
+        weights = [c.weight.detach().t().to(dt).contiguous() for c in layers]
+        atts = [c.attention.detach().to(dt).reshape(-1).contiguous() if gat else None for c in layers]
+        return ops.gat_stack_forward(adj, fea, weights, atts, [True, False], ptr, self.lin.weight, self.lin.bias,
+                                     alpha=self.att1.alpha, plan=plan)
 
 
 def init_SGRACE(device=None):
