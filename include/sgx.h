@@ -353,9 +353,11 @@ int sgx_coo_to_csr(const int32_t *rowIndex, int64_t nnz, int n_rows, int32_t *ro
 /* Weight gradient of the layer's backward pass, grad_W = X^T . G with G = adj @ grad_output already
  * aggregated by sgx_spmm_csr (FPYNQ.backward, MOL cell 16; the reference runs it in torch on the CPU).
  * X [n_rows][ldx] fp16|fp32 dense, G [n_rows][ldg] fp32, out [M][ldo] fp32 (exact fp32 fma chains,
- * slab sums added in a fixed order).  The other two products of the backward pass are existing
- * entry points: adj @ g = sgx_spmm_csr, grad_x = G . W^T = sgx_xw_dense(G, Wt := W [M][P]); for a CSR
- * X, X^T . G = sgx_spmm_csr over the CSR of X^T. */
+ * slab sums added in a fixed order).  Columns P .. ldo-1 of out are not written; n_rows = 0 clears
+ * out[M][P] and reads neither X nor G (both may be NULL), and sgx_xt_g_workspace_bytes(0, M, P) is a
+ * valid, non-zero size.  The other two products of the backward pass are existing entry points:
+ * adj @ g = sgx_spmm_csr, grad_x = G . W^T = sgx_xw_dense(G, Wt := W [M][P]); for a CSR X,
+ * X^T . G = sgx_spmm_csr over the CSR of X^T. */
 size_t sgx_xt_g_workspace_bytes(int n_rows, int M, int P);
 int sgx_xt_g(int dtype_x, int n_rows, int M, int P, const void *X, int64_t ldx, const float *G, int64_t ldg,
              float *out, int64_t ldo, void *workspace, size_t workspace_bytes, void *stream);
@@ -443,8 +445,9 @@ int sgx_readout_mean_linear(int dtype, int n_graphs, int F, int C, const void *X
                             float *logits, void *stream);
 
 /* Backward of that pooling for the training step (the autograd of global_mean_pool in MOL cell 18's forward, cell 20's
- * loop): grad_X[r][:] = grad_pooled[g][:] / (graph_ptr[g+1] - graph_ptr[g]) for the rows r of graph g, written in
- * `dtype` (the element type of the layer output the pooling read); rows outside every graph are not written. */
+ * loop): grad_X[r][:] = dtype(grad_pooled[g][:] * (1 / (graph_ptr[g+1] - graph_ptr[g]))) for the rows r of graph g -- the
+ * fp32 reciprocal of the graph's size rounded once, the fp32 product, then `dtype` (the element type of the layer output
+ * the pooling read); rows outside every graph and columns F .. ldg-1 are not written. */
 int sgx_readout_mean_backward(int dtype, int n_graphs, int F, const float *grad_pooled, const int32_t *graph_ptr,
                               void *grad_X, int64_t ldg, void *stream);
 

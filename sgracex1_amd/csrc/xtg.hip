@@ -323,6 +323,7 @@ XtgGeom geometry(int n_rows, int M, int P)
     if (slabs < 1) slabs = 1;
     int64_t rps = (n_rows + slabs - 1) / slabs;
     rps = (rps + 15) / 16 * 16;
+    if (rps < 16) rps = 16;                                      // n_rows == 0 (sgx_xt_g_workspace_bytes takes it): no division by 0 below
     g.rows_per_slab = (int)rps;
     g.n_slabs = (int)((n_rows + rps - 1) / rps);
     if (g.n_slabs < 1) g.n_slabs = 1;
