@@ -119,8 +119,10 @@ class HaloPlan:
         return self.n_own + sum(self.recv_counts)
 
 
-def build_halo_plan(col_global: torch.Tensor, bounds: List[int], rank: int, group=None) -> HaloPlan:
-    """Needs one all_to_all of the request lists (preprocessing, once per graph)."""
+def halo_requests(col_global: torch.Tensor, bounds: List[int], rank: int):
+    """The part of a rank's halo plan that needs no other rank: (need, col_compact, recv_counts).  need[g] = the sorted
+    unique GLOBAL rows this rank reads from owner g (empty for g = rank), col_compact = every column renumbered into the
+    compact table [own rows | need[0] | need[1] | ...] (int64), recv_counts[g] = len(need[g])."""
     world = len(bounds) - 1
     lo, hi = bounds[rank], bounds[rank + 1]
     dev = col_global.device
@@ -142,17 +144,45 @@ def build_halo_plan(col_global: torch.Tensor, bounds: List[int], rank: int, grou
         m = owner == g
         col_compact[m] = off + torch.searchsorted(need[g], col64[m])
         off += recv_counts[g]
+    return need, col_compact, recv_counts
+
+
+def build_halo_plan(col_global: torch.Tensor, bounds: List[int], rank: int, group=None) -> HaloPlan:
+    """Needs one all_to_all of the request lists (preprocessing, once per graph)."""
+    lo, hi = bounds[rank], bounds[rank + 1]
+    dev = col_global.device
+    need, col_compact, recv_counts = halo_requests(col_global, bounds, rank)
     # tell every owner which of its rows we need
     counts_out = torch.tensor(recv_counts, dtype=torch.int64, device=dev)
     counts_in = torch.empty_like(counts_out)
     all_to_all_rows(counts_in, counts_out, None, None, group=group)
     send_counts = [int(c) for c in counts_in.tolist()]
-    req_out = torch.cat(need) if sum(recv_counts) else col64.new_empty(0)
-    req_in = col64.new_empty(sum(send_counts))
+    req_out = torch.cat(need) if sum(recv_counts) else col_compact.new_empty(0)
+    req_in = col_compact.new_empty(sum(send_counts))
     all_to_all_rows(req_in, req_out, send_counts, recv_counts, group=group)
     send_rows = (req_in - lo).contiguous()
     return HaloPlan(bounds, rank, col_compact.to(torch.int32), send_rows, send_counts, recv_counts, hi - lo,
                     send_rows32=send_rows.to(torch.int32))
+
+
+def build_halo_plans_local(cols_per_rank: List[torch.Tensor], bounds: List[int]) -> List[HaloPlan]:
+    """Every rank's HaloPlan in one process, without a collective: what build_halo_plan's all-to-all delivers to owner r
+    -- consumer c's request list for r, consumers in rank order -- is read from the other ranks' halo_requests directly.
+    cols_per_rank[r] = the global column indices of rank r's rows.  For tests and single-process rehearsals."""
+    world = len(bounds) - 1
+    if len(cols_per_rank) != world:
+        raise ValueError(f"{len(cols_per_rank)} column arrays for a partition into {world}")
+    local = [halo_requests(cols_per_rank[r], bounds, r) for r in range(world)]
+    plans = []
+    for r in range(world):
+        lo, hi = bounds[r], bounds[r + 1]
+        _, col_compact, recv_counts = local[r]
+        send_counts = [local[c][2][r] for c in range(world)]
+        asked = [local[c][0][r] for c in range(world)]
+        send_rows = ((torch.cat(asked) if sum(send_counts) else col_compact.new_empty(0)) - lo).contiguous()
+        plans.append(HaloPlan(bounds, r, col_compact.to(torch.int32), send_rows, send_counts, recv_counts, hi - lo,
+                              send_rows32=send_rows.to(torch.int32)))
+    return plans
 
 
 def any_rank_has_dead_rows(adj_local, group=None, device=None):

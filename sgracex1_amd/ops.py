@@ -208,26 +208,31 @@ class Csr:
         self._plan = plan
         self._dead_rows = None
         self._dead_row_mask = None
+        self._dead_rows_version = self._dead_row_mask_version = None      # the values' version a computed answer holds for
         self._max_row = None                   # the longest row, or a bound on it, where the builder knows it
         self._quantized = {}
 
     @property
     def dead_rows(self):
         """bool [n_rows] on the device: the rows that hold no positive value, which the GAT mask `adj > 0` (SG.py:640)
-        leaves without a neighbour.  Built once per matrix, without a sync."""
-        if self._dead_row_mask is None:
+        leaves without a neighbour.  Built once per matrix and state of the values (the value tensor's version counter: an
+        in-place change builds it again), without a sync.  A mask given through with_facts stays as given."""
+        if self._dead_row_mask is None or self._dead_row_mask_version not in (None, self.val._version):
             deg = (self.rowptr[1:] - self.rowptr[:-1]).long()
             row = torch.repeat_interleave(torch.arange(self.n_rows, device=self.val.device), deg, output_size=self.nnz)
             live = torch.zeros(self.n_rows, dtype=torch.int32, device=self.val.device)
             live.index_add_(0, row, (self.val[:self.nnz] > 0).to(torch.int32))
             self._dead_row_mask = live == 0
+            self._dead_row_mask_version = self.val._version
         return self._dead_row_mask
 
     @property
     def has_dead_rows(self):
-        """True when some row is one of dead_rows.  One device->host sync, once per matrix."""
-        if self._dead_rows is None:
+        """True when some row is one of dead_rows.  One device->host sync, once per matrix and state of the values (as
+        dead_rows); a fact given through with_facts stays as given."""
+        if self._dead_rows is None or self._dead_rows_version not in (None, self.val._version):
             self._dead_rows = bool(self.dead_rows.any().item())
+            self._dead_rows_version = self.val._version
         return self._dead_rows
 
     def quantized(self, qc):
@@ -276,9 +281,9 @@ class Csr:
         """Records what the builder of this matrix already knows, so that nothing is computed or read back for it:
         dead_rows (bool [n_rows]), has_dead_rows, and the longest row (or a bound on it; see wants_plan)."""
         if dead_row_mask is not None:
-            self._dead_row_mask = dead_row_mask
+            self._dead_row_mask, self._dead_row_mask_version = dead_row_mask, None
         if has_dead_rows is not None:
-            self._dead_rows = bool(has_dead_rows)
+            self._dead_rows, self._dead_rows_version = bool(has_dead_rows), None
         if max_row is not None:
             self._max_row = int(max_row)
         return self
