@@ -20,6 +20,10 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
         GATConv_SGRACE layers with the edge softmax, mean pool, head; fp32 layer buffers), trained layer by layer through
         FPYNQ_GAT's autograd; --layer-count 2 = the accuracy passes run the whole model in one call
         (sgx_gat_stack_forward).  It prints accuracy only: the reference records no GAT output (parity unpinned).
+    python examples/molecule_gcn_train.py --model gat --layer-count 2 --qbits 8
+        --qbits N (8, 4, 2 or 1; with --model gat) = the layers run the quantised arithmetic of the SGRACE bitstream
+        (config.fake_quantization, fp32 emulation of the grid); with --layer-count 2 the accuracy passes are one call of
+        sgx_quant_stack_forward.  Parity unpinned here too: the reference records no quantised output.
 """
 import argparse
 import json
@@ -45,7 +49,10 @@ def main():
     ap.add_argument("--batch-size", type=int, default=0)
     ap.add_argument("--host-loader", action="store_true")
     ap.add_argument("--model", choices=["gcn", "gat"], default="gcn")
+    ap.add_argument("--qbits", type=int, default=32, choices=[32, 8, 4, 2, 1])
     args = ap.parse_args()
+    if args.qbits != 32 and args.model != "gat":
+        ap.error("--qbits runs the quantised layers of the SGRACE library: --model gat")
     if args.model == "gat" and (args.train_stack or args.acc != 1):
         ap.error("--model gat trains layer by layer on the kernels (no --train-stack, --acc 1)")
     if args.train_stack and args.layer_count < 2:
@@ -66,6 +73,7 @@ def main():
     if args.model == "gat":
         from sgracex1_amd import config, sgrace
         config.acc, config.compute_attention = 1, 1
+        config.fake_quantization, config.w_qbits = int(args.qbits != 32), args.qbits
         my_ip = sgrace.init_SGRACE()
         my_ip.register_map.layer_count = args.layer_count
         torch.manual_seed(12345)
@@ -107,7 +115,7 @@ def main():
         print(f"Epoch: {epoch:03d}, Train Acc: {tr:.4f}, Test Acc: {te:.4f}, loss {float(loss.detach()):.4f}, "
               f"step {dt * 1e3:.2f} ms", flush=True)
     print(json.dumps({"best_test_acc": best, "final_test_acc": log[-1]["test_acc"], "epochs": args.epochs,
-                      "acc": args.acc, "model": args.model, "layer_count": args.layer_count, "train_stack": args.train_stack,
+                      "acc": args.acc, "model": args.model, "qbits": args.qbits, "layer_count": args.layer_count, "train_stack": args.train_stack,
                       "batch_size": args.batch_size, "host_loader": args.host_loader, "reference": "0.76 at epoch 34 (notebook cell 20 output)" if args.model == "gcn" else "none (parity unpinned)"}))
 
 

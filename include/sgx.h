@@ -539,7 +539,8 @@ int sgx_sample_neighbors(const int32_t *rowPtr, const int32_t *columnIndex, int 
  * Where the plan fits (no graph over its row budget) and every width is within the fused kernel's limits
  * (M_fea, P_w <= the plan's max_width <= 256; a sparse layer 0 may have any M_fea), one launch computes it all.
  * Otherwise sgx_stack_forward runs the chained kernels through the workspace -- same results, so a call always
- * works (single large graphs such as Cora take this path).  Quantised layers are not offered here; GAT layers: `sgx_gat_stack_forward`. */
+ * works (single large graphs such as Cora take this path).  GAT layers: `sgx_gat_stack_forward`; quantised layers (GCN or
+ * GAT): `sgx_quant_stack_forward`. */
 typedef struct sgx_batch_plan sgx_batch_plan;
 
 typedef struct sgx_stack_layer {
@@ -1072,6 +1073,83 @@ const char *sgx_status_string(int status);
  * of them later (a test comparing two kernel forms) calls this to have them read again.  Not for concurrent use with
  * other calls into the library. */
 void sgx_reload_env(void);
+
+/* ---- quantised layers in the small-graph stack -------------------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_quant_stack_forward is sgx_gat_stack_forward with a per-layer quantiser: the reference's `layer_count` register
+ * belongs to the quantised bitstream (gat_all_unsigned.bit), whose every board config ships with the quantiser on.  It
+ * takes the same sgx_batch_plan, of either kind, so one plan cached on a batch serves all three stack calls, and on the
+ * fused path it is the same one launch: the quantisers sit on the operand loads and the two stores of the stages.
+ * Parity of the quantised layer is UNPINNED, here as everywhere: the reference records no quantised output; what is
+ * pinned is equality with this library's own sgx_layer_forward (tests/test_gpu_quant_stack.py).
+ *
+ * Semantics: layer l with quant = q is sgx_layer_forward with desc->quant = q and gat_fill_dead_rows = 0 on the same
+ * operands in fp32 (quant = NULL: the plain layer of sgx_gat_stack_forward).  Operands arrive UNQUANTISED and each is
+ * quantised exactly once (the quantiser is not idempotent: inv_scale_w = 127 against a grid step of 1 / 128 at 8 bits),
+ * with the one device quantiser of sgx_fake_quantize, so the bits are those of a sgx_fake_quantize launch over them:
+ *   - B and attention go to the signed q->qbits grid (inv_scale_w, zero_w) as the kernel loads them;
+ *   - X_l goes to the unsigned grid with (inv_scale_fea, zero_fea) of layer l: the stored CSR entries of a sparse layer 0
+ *     as they are read, a dense layer 0 as it is copied into LDS, and for l >= 1 the previous layer's D_{l-1} where the
+ *     aggregate stores it into the X tile -- the value written to the caller's layer[l-1].D is the unquantised D_{l-1},
+ *     and the last layer's tile stays unquantised for the readout;
+ *   - adjacency values go to the unsigned grid with (inv_scale_adj, zero_adj) as they are read, or are taken as stored
+ *     with SGX_QUANT_ADJ_DONE; in a GAT layer the mask is on the quantised value (> 0 is live);
+ *   - H_l = requant(X_q . W_q): the shift by scale_fea, the clip to +-(2^ib - 1) / 2^ib and the decimal rounding that
+ *     sgx_xw_dense / sgx_xw_sparse apply on their stores (one fp32 operation per rounding point, contraction off);
+ *   - D_l = act(aggregate) * deq_factor: ReLU first, then the scale; GAT rows without a live entry give 0;
+ *   - readout and head: those of sgx_stack_forward.
+ * The stack always takes the fp32 form: SGX_QUANT_INT8 and SGX_QUANT_INT8_AUTO in `flags` are ignored.  Fields of
+ * sgx_quant read on the fused path: qbits, scale_fea, internal_bits, flags (SGX_QUANT_ADJ_DONE only), the three
+ * (inv_scale, zero) pairs and deq_factor; nnz_adj and nnz_fea are not needed there.  The chained path hands the block
+ * to sgx_layer_forward, which sizes its quantised copies by them: nnz_adj (unless SGX_QUANT_ADJ_DONE) and, for a sparse
+ * layer 0, nnz_fea must then hold the stored entries of A and X.
+ *
+ * GCN layers are bit-equal to the chain sgx_layer_forward x n -> sgx_readout_mean_linear wherever X_q . W_q is exact in
+ * fp32 (|sum of code products| < 2^24: every M_fea <= 256 at 8 bits), the aggregate being the same fma chain in CSR
+ * order; GAT layers lie inside the bound of sgx_gat_stack_forward times deq_factor.  Same bits on every run and for every
+ * grouping: no atomics, no order that depends on the grid.  LDS use and the row budget are those of
+ * sgx_gat_stack_forward in fp32.
+ *
+ * Where the plan does not fit or a width is over the limit the call runs, per layer, sgx_layer_forward with the layer's
+ * quant (gat_fill_dead_rows = 0, no plan), then sgx_readout_mean_linear, all through the workspace, so a call always
+ * works; sgx_quant_stack_workspace_bytes is 0 exactly when the fused path is taken.  A descriptor with every quant NULL
+ * is exactly sgx_gat_stack_forward.
+ *
+ * Argument errors, returned before anything reaches the device: those of sgx_gat_stack_forward; a layer with quant set
+ * while dtype != SGX_F32, qbits outside {8, 4, 2, 1}, scale_fea outside 0..30, internal_bits outside 1..30, zero_adj
+ * != 0, or zero_fea != 0 on a sparse layer 0 (entries that are not stored must stay zero): SGX_ERR_UNSUPPORTED.
+ * Capturable on the fused path: no allocation and no host synchronisation. */
+typedef struct sgx_quant_stack_layer {
+    int32_t gemm_mode;    /* as sgx_gat_stack_layer, field for field */
+    int32_t relu;
+    int32_t M_fea, P_w;
+    const void *B;
+    void *D;
+    int64_t ldd;
+    int32_t gat_mode;
+    const void *attention;
+    float alpha;
+    const sgx_quant *quant;   /* this layer's quantiser; NULL = the plain layer of sgx_gat_stack_forward */
+} sgx_quant_stack_layer;
+
+typedef struct sgx_quant_stack_desc {
+    int32_t dtype, n_layers;                   /* as sgx_gat_stack_desc, field for field */
+    int32_t n_rows, n_graphs;
+    const int32_t *graph_ptr;
+    const int32_t *rowPtr_adj, *columnIndex_adj; const void *values_adj;
+    const int32_t *rowPtr_fea, *columnIndex_fea; const void *values_fea;
+    sgx_quant_stack_layer layer[4];
+    int32_t C;
+    const float *W_head, *bias;
+    float *pooled, *logits;
+    const sgx_batch_plan *plan;                /* from sgx_batch_plan_create / _create_ex / _create_known, either kind */
+    void *workspace; size_t workspace_bytes;   /* sgx_quant_stack_workspace_bytes(d), 256-byte aligned (0 on the fused path) */
+} sgx_quant_stack_desc;
+
+/* 0 for the fused path, the chained path's scratch otherwise (and for a bad descriptor) */
+size_t sgx_quant_stack_workspace_bytes(const sgx_quant_stack_desc *d);
+int sgx_quant_stack_forward(const sgx_quant_stack_desc *d, void *stream);
 
 #ifdef __cplusplus
 }

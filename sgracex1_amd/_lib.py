@@ -48,6 +48,7 @@ SYMBOLS = [
     "sgx_gat_attention_grad",
     "sgx_csr_transpose_workspace_bytes", "sgx_csr_transpose",
     "sgx_gat_stack_workspace_bytes", "sgx_gat_stack_forward",
+    "sgx_quant_stack_workspace_bytes", "sgx_quant_stack_forward",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -135,6 +136,16 @@ class GatStackLayer(ctypes.Structure):
 class GatStackDesc(ctypes.Structure):
     """struct sgx_gat_stack_desc -- field order and types must match include/sgx.h."""
     _fields_ = [(n, GatStackLayer * 4 if n == "layer" else t) for n, t in StackDesc._fields_]
+
+
+class QuantStackLayer(ctypes.Structure):
+    """struct sgx_quant_stack_layer -- field order and types must match include/sgx.h."""
+    _fields_ = GatStackLayer._fields_ + [("quant", ctypes.POINTER(Quant))]
+
+
+class QuantStackDesc(ctypes.Structure):
+    """struct sgx_quant_stack_desc -- field order and types must match include/sgx.h."""
+    _fields_ = [(n, QuantStackLayer * 4 if n == "layer" else t) for n, t in StackDesc._fields_]
 
 
 class StackGradLayer(ctypes.Structure):
@@ -374,6 +385,10 @@ def _load():
     lib.sgx_gat_stack_workspace_bytes.restype = sz
     lib.sgx_gat_stack_forward.argtypes = [ctypes.POINTER(GatStackDesc), vp]
     lib.sgx_gat_stack_forward.restype = c_int
+    lib.sgx_quant_stack_workspace_bytes.argtypes = [ctypes.POINTER(QuantStackDesc)]
+    lib.sgx_quant_stack_workspace_bytes.restype = sz
+    lib.sgx_quant_stack_forward.argtypes = [ctypes.POINTER(QuantStackDesc), vp]
+    lib.sgx_quant_stack_forward.restype = c_int
     lib.sgx_stack_backward_workspace_bytes.argtypes = [ctypes.POINTER(StackGradDesc)]
     lib.sgx_stack_backward_workspace_bytes.restype = sz
     lib.sgx_stack_backward.argtypes = [ctypes.POINTER(StackGradDesc), vp]

@@ -38,7 +38,7 @@ _FLAGS = {
                        "my_ip.register_map.layer_count >= 2, GCN_PYNQ's eval forward over a sorted batch of graphs runs "
                        "both layers, the mean pool and the head in one call (sgx_stack_forward, bit-equal to the "
                        "layer-by-layer path), and so does sgrace.GAT_POOL_PYNQ's (sgx_gat_stack_forward; GAT layers inside "
-                       "the float64 bound, parity unpinned); training and every other model run one launch per stage"),
+                       "the float64 bound, parity unpinned; with the quantiser on sgx_quant_stack_forward); training and every other model run one launch per stage"),
     # -- accepted, no effect on this path --------------------------------------------------------
     "load_weights": (1, "FPGA weight preload switch"),
     "stream_mode": (0, "FPGA streaming I/O switch"),

@@ -1,8 +1,9 @@
 // What the small-graph stack kernels share (stack.hip: sgx_stack_forward / sgx_stack_backward; stack_gat.hip:
-// sgx_gat_stack_forward): the batch plan and its row budget, the LDS tiles' pitch, the matrix-core X.W on an LDS tile, the
+// sgx_gat_stack_forward; stack_quant.hip: sgx_quant_stack_forward): the batch plan and its row budget, the LDS tiles' pitch, the matrix-core X.W on an LDS tile, the
 // stages of the forward kernel, and the descriptor checks and the chained path, which are the same for both descriptors.
 #pragma once
 #include "sgx_device.h"
+#include "quant_device.h"
 
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
@@ -72,6 +73,72 @@ struct StackArgs {
     int rows;
 };
 
+// What a layer's quantiser (sgx_quant) does inside the stages, as a policy of the stage templates.  StackPlain: nothing --
+// every hook below is compiled out, so the plain kernels keep their code.  StackQuant (fp32 only, sgx_quant_stack_forward):
+// per layer the operand grids (W and the attention vector signed, X and the adjacency values unsigned, one
+// fake_quantize_value per element as it is read) and the two store epilogues of sgx_layer_forward.
+struct StackPlain {
+    static constexpr bool kQuant = false;
+};
+struct StackQuant {
+    static constexpr bool kQuant = true;
+    int on[kMaxLayers];          // the layer has a quantiser; every other field of an `off` layer is unused
+    int qbits[kMaxLayers];
+    int adj_done[kMaxLayers];    // SGX_QUANT_ADJ_DONE: the adjacency values are taken as stored
+    float inv_fea[kMaxLayers], zero_fea[kMaxLayers], inv_w[kMaxLayers], zero_w[kMaxLayers], inv_adj[kMaxLayers],
+        zero_adj[kMaxLayers];
+    sgx_epilogue ep_h[kMaxLayers], ep_d[kMaxLayers];
+};
+
+// a weight or an attention element of layer l
+template <typename Q> __device__ __forceinline__ float stack_q_w(const Q &q, int l, float v)
+{
+    if constexpr (Q::kQuant) {
+        if (q.on[l]) return sgx_quantizer::fake_quantize_value(1, q.qbits[l], q.inv_w[l], q.zero_w[l], v);
+    }
+    return v;
+}
+// an element of X_l
+template <typename Q> __device__ __forceinline__ float stack_q_x(const Q &q, int l, float v)
+{
+    if constexpr (Q::kQuant) {
+        if (q.on[l]) return sgx_quantizer::fake_quantize_value(0, q.qbits[l], q.inv_fea[l], q.zero_fea[l], v);
+    }
+    return v;
+}
+// a stored adjacency value as layer l reads it
+template <typename Q> __device__ __forceinline__ float stack_q_adj(const Q &q, int l, float v)
+{
+    if constexpr (Q::kQuant) {
+        if (q.on[l] && !q.adj_done[l]) return sgx_quantizer::fake_quantize_value(0, q.qbits[l], q.inv_adj[l], q.zero_adj[l], v);
+    }
+    return v;
+}
+// the epilogues of layer l's two stores (none for a plain layer)
+template <typename Q> __device__ __forceinline__ sgx_epilogue stack_ep_h(const Q &q, int l)
+{
+    if constexpr (Q::kQuant) {
+        if (q.on[l]) return q.ep_h[l];
+    }
+    return sgx_epilogue{0.0f, 0.0f, 0.0f, 0.0f};
+}
+template <typename Q> __device__ __forceinline__ sgx_epilogue stack_ep_d(const Q &q, int l)
+{
+    if constexpr (Q::kQuant) {
+        if (q.on[l]) return q.ep_d[l];
+    }
+    return sgx_epilogue{0.0f, 0.0f, 0.0f, 0.0f};
+}
+// what the aggregate of layer l leaves in the X tile for D_l = v: X_{l+1} on layer l + 1's feature grid where that layer
+// has a quantiser (the caller's D gets v itself; the last layer's tile stays as it is for the readout)
+template <typename T, typename Q> __device__ __forceinline__ T stack_next_x(const Q &q, int l, int n_layers, T v)
+{
+    if constexpr (Q::kQuant && sizeof(T) == 4) {
+        if (l + 1 < n_layers) return stack_q_x(q, l + 1, v);
+    }
+    return v;
+}
+
 template <typename T> struct Mfma;
 
 // fp16: a k-step of 32; lane quad lq holds k = k0 + 8 lq .. + 7 of its row (xw_dense_f16_kernel's layout)
@@ -122,9 +189,10 @@ template <> struct Mfma<float> {
 // H[0:nr][0:P] = X[0:nr][0:K] . Wt^T, X in LDS, Wt [P][K] in global.  A wavefront takes (16-row tile, 64-column
 // group) items: the MFMA forms the transposed tile H^T = Wt . X^T as in xw_dense.hip, so a lane ends with four
 // consecutive columns of one row, handed to store(m, n, fp32 sum).
-template <typename T, typename Store>
+// q, l: the quantiser of W (layer l's signed grid on every element the operand load brings in; pad elements stay 0).
+template <typename T, typename Store, typename Q = StackPlain>
 __device__ __forceinline__ void xw_dense_lds_apply(const T *__restrict__ X, int pitch, int nr, int K, int P,
-                                                   const T *__restrict__ Wt, Store store)
+                                                   const T *__restrict__ Wt, Store store, const Q &q = Q(), int l = 0)
 {
     typedef Mfma<T> M;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -143,7 +211,14 @@ __device__ __forceinline__ void xw_dense_lds_apply(const T *__restrict__ X, int 
             for (int nt = 0; nt < 4; ++nt) {
                 if (cg * 64 + nt * 16 >= P) break;                       // (wave-uniform)
                 const int n = cg * 64 + nt * 16 + l15;
-                const typename M::frag a = M::load(Wt + (size_t)n * K, k, K, n < P);
+                typename M::frag a = M::load(Wt + (size_t)n * K, k, K, n < P);
+                if constexpr (Q::kQuant && sizeof(T) == 4) {
+                    if (q.on[l] && n < P) {
+#pragma unroll
+                        for (int j = 0; j < 4; ++j)
+                            if (k + j < K) a[j] = stack_q_w(q, l, a[j]);
+                    }
+                }
                 acc[nt] = M::step(a, b, acc[nt]);
             }
         }
@@ -158,18 +233,28 @@ __device__ __forceinline__ void xw_dense_lds_apply(const T *__restrict__ X, int 
     }
 }
 
-template <typename T>
+template <typename T, typename Q = StackPlain>
 __device__ __forceinline__ void xw_dense_lds(const T *__restrict__ X, T *__restrict__ H, int pitch, int nr, int K, int P,
-                                             const T *__restrict__ Wt)
+                                             const T *__restrict__ Wt, const Q &q = Q(), int l = 0)
 {
-    xw_dense_lds_apply<T>(X, pitch, nr, K, P, Wt,
-                          [&](int m, int n, float v) { H[(size_t)m * pitch + n] = Elem<T>::from_f32(v); });
+    if constexpr (Q::kQuant && sizeof(T) == 4) {
+        // H = requant(X_q . W_q): the epilogue sgx_xw_dense applies on its stores
+        const sgx_epilogue ep = stack_ep_h(q, l);
+        xw_dense_lds_apply<T>(X, pitch, nr, K, P, Wt,
+                              [&](int m, int n, float v) { H[(size_t)m * pitch + n] = finish_value<T>(v, 0, ep); }, q, l);
+    } else {
+        xw_dense_lds_apply<T>(X, pitch, nr, K, P, Wt,
+                              [&](int m, int n, float v) { H[(size_t)m * pitch + n] = Elem<T>::from_f32(v); });
+    }
 }
 
 // Stage 1 of layer l for the group of rows [r0, r0 + nr): Hs = dtype(X_l . W_l), X_l = XD (layers >= 1) or the caller's
-// features.  The caller puts a __syncthreads behind it.
-template <typename T>
-__device__ __forceinline__ void stack_form_h(const StackArgs &a, int l, int r0, int nr, T *__restrict__ XD, T *__restrict__ Hs)
+// features.  The caller puts a __syncthreads behind it.  With a quantiser: layer 0's features go to their grid as they are
+// read (CSR entries) or copied into LDS (dense rows), W as it is read, H through the re-quantisation on its store; the
+// X tile of a layer >= 1 is already on its grid (stack_next_x).
+template <typename T, typename Q = StackPlain>
+__device__ __forceinline__ void stack_form_h(const StackArgs &a, int l, int r0, int nr, T *__restrict__ XD, T *__restrict__ Hs,
+                                             const Q &q = Q())
 {
     const int K = a.K[l], P = a.P[l], pitch = a.pitch;
     const T *__restrict__ Wt = static_cast<const T *>(a.B[l]);
@@ -184,14 +269,18 @@ __device__ __forceinline__ void stack_form_h(const StackArgs &a, int l, int r0, 
             for (int e = e0; e < e1; ++e) {
                 const int k = a.col_f[e];
                 if ((unsigned)k >= (unsigned)K) continue;          // (the chained gather reads 0 there)
-                const float x = Elem<T>::to_f32(vf[e]);
+                const float x = stack_q_x(q, l, Elem<T>::to_f32(vf[e]));
 #pragma unroll
                 for (int u = 0; u < 4; ++u)
-                    if (c0 + u < P) acc[u] = __builtin_fmaf(x, Elem<T>::to_f32(Wt[(size_t)(c0 + u) * K + k]), acc[u]);
+                    if (c0 + u < P)
+                        acc[u] = __builtin_fmaf(x, stack_q_w(q, l, Elem<T>::to_f32(Wt[(size_t)(c0 + u) * K + k])), acc[u]);
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-                if (c0 + u < P) Hs[(size_t)i * pitch + c0 + u] = Elem<T>::from_f32(acc[u]);
+            for (int u = 0; u < 4; ++u) {
+                if (c0 + u >= P) continue;
+                if constexpr (Q::kQuant && sizeof(T) == 4) Hs[(size_t)i * pitch + c0 + u] = finish_value<T>(acc[u], 0, stack_ep_h(q, l));
+                else Hs[(size_t)i * pitch + c0 + u] = Elem<T>::from_f32(acc[u]);
+            }
         }
     } else {
         if (l == 0) {
@@ -199,23 +288,25 @@ __device__ __forceinline__ void stack_form_h(const StackArgs &a, int l, int r0, 
             const T *__restrict__ X = static_cast<const T *>(a.val_f) + (size_t)r0 * K;
             for (int it = threadIdx.x; it < nr * K; it += kBlock) {
                 const int i = it / K, k = it - i * K;
-                XD[(size_t)i * pitch + k] = X[it];
+                if constexpr (Q::kQuant && sizeof(T) == 4) XD[(size_t)i * pitch + k] = stack_q_x(q, l, X[it]);
+                else XD[(size_t)i * pitch + k] = X[it];
             }
             __syncthreads();
         }
-        xw_dense_lds<T>(XD, Hs, pitch, nr, K, P, Wt);
+        xw_dense_lds<T, Q>(XD, Hs, pitch, nr, K, P, Wt, q, l);
     }
 }
 
 // Stage 2, the GCN form: XD = D_l = act(A . H_l), rows of A from global, columns rebased to the group's first row, H
-// gathered from LDS; also to the caller's D when asked.  The caller puts a __syncthreads behind it.
-template <typename T>
+// gathered from LDS; also to the caller's D when asked.  The caller puts a __syncthreads behind it.  With a quantiser: the
+// adjacency values on their grid as they are read, D = act(sum) * deq_factor, the X tile through stack_next_x.
+template <typename T, typename Q = StackPlain>
 __device__ __forceinline__ void stack_gcn_aggregate(const StackArgs &a, int l, int r0, int nr, T *__restrict__ XD,
-                                                    const T *__restrict__ Hs)
+                                                    const T *__restrict__ Hs, const Q &q = Q())
 {
     const int P = a.P[l], pitch = a.pitch;
     const int nch = (P + 3) / 4;
-    const sgx_epilogue no_ep{0.0f, 0.0f, 0.0f, 0.0f};
+    const sgx_epilogue ep = stack_ep_d(q, l);
     const T *__restrict__ val = static_cast<const T *>(a.val);
     T *__restrict__ Dg = static_cast<T *>(a.D[l]);
     const int64_t ldd = a.ldd[l];
@@ -227,7 +318,7 @@ __device__ __forceinline__ void stack_gcn_aggregate(const StackArgs &a, int l, i
         for (int e = e0; e < e1; ++e) {
             const int c = a.col[e] - r0;
             if ((unsigned)c >= (unsigned)nr) continue;         // (the plan admits no such edge)
-            const float w = Elem<T>::to_f32(val[e]);
+            const float w = stack_q_adj(q, l, Elem<T>::to_f32(val[e]));
             const T *h = Hs + (size_t)c * pitch + c0;
 #pragma unroll
             for (int u = 0; u < 4; ++u) acc[u] = __builtin_fmaf(w, Elem<T>::to_f32(h[u]), acc[u]);
@@ -235,8 +326,8 @@ __device__ __forceinline__ void stack_gcn_aggregate(const StackArgs &a, int l, i
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             if (c0 + u >= P) break;
-            const T v = finish_value<T>(acc[u], relu, no_ep);
-            XD[(size_t)i * pitch + c0 + u] = v;
+            const T v = finish_value<T>(acc[u], relu, ep);
+            XD[(size_t)i * pitch + c0 + u] = stack_next_x<T>(q, l, a.n_layers, v);
             if (Dg) Dg[(int64_t)(r0 + i) * ldd + c0 + u] = v;
         }
     }

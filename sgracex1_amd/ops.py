@@ -1542,14 +1542,31 @@ def gat_stack_forward(adj, x, weights_t, attentions, relus, graph_ptr, head_weig
                           attentions=list(attentions), alpha=alpha)
 
 
+def quant_stack_forward(adj, x, weights_t, attentions, relus, graph_ptr, quants, head_weight=None, head_bias=None, alpha=0.2,
+                        plan=None, adj_quantised=False, want_layer_outputs=False, want_pooled=False):
+    """gat_stack_forward with a per-layer quantiser (sgx_quant_stack_forward, include/sgx.h "quantised layers in the
+    small-graph stack"): quants[l] is layer l's quant.QuantConstants -- the layer is then layer_forward(..., quant=
+    quants[l]) with the zero dead-row rule, on float32 tensors -- or None for the plain layer.  Every operand arrives
+    UNQUANTISED (the quantiser is not idempotent) except the adjacency with adj_quantised=True, which is taken as stored
+    (Csr.quantized(qc)).  One launch where the batch's graphs fit the plan, layer_forward per layer otherwise.  Parity of
+    the quantised layer is unpinned: the reference records no quantised output.  Arguments and results as
+    gcn_stack_forward's."""
+    if len(attentions) != len(weights_t) or len(quants) != len(weights_t):
+        raise ValueError("quant_stack_forward takes one attention vector (or None) and one QuantConstants (or None) per layer")
+    return _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, want_layer_outputs, want_pooled, plan,
+                          None, attentions=list(attentions), alpha=alpha, quants=list(quants), adj_quantised=adj_quantised)
+
+
 def _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, want_layer_outputs, want_pooled, plan, keep,
-                   attentions=None, alpha=0.2):
-    """The descriptor of sgx_stack_forward (attentions None) or sgx_gat_stack_forward, its workspace and the call."""
+                   attentions=None, alpha=0.2, quants=None, adj_quantised=False):
+    """The descriptor of sgx_stack_forward (attentions None), sgx_gat_stack_forward or sgx_quant_stack_forward (quants
+    given), its workspace and the call."""
     gat = attentions is not None
-    name = "sgx_gat_stack" if gat else "sgx_stack"
+    name = "sgx_quant_stack" if quants is not None else "sgx_gat_stack" if gat else "sgx_stack"
     n = len(weights_t)
     if not 1 <= n <= 4 or len(relus) != n:
-        raise ValueError(f"{'gat' if gat else 'gcn'}_stack_forward takes 1 to 4 layers and one relu flag per layer")
+        label = "quant" if quants is not None else "gat" if gat else "gcn"
+        raise ValueError(f"{label}_stack_forward takes 1 to 4 layers and one relu flag per layer")
     dtype = adj.val.dtype
     code = dtype_code(dtype)
     N, dev = adj.n_rows, adj.val.device
@@ -1560,8 +1577,9 @@ def _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, 
         graph_ptr = cached_on(adj.rowptr, ("one_graph_ptr",),
                               lambda: torch.tensor([0, N], dtype=torch.int32, device=dev))
     _dev(graph_ptr, "graph_ptr")
-    d = _lib.GatStackDesc() if gat else _lib.StackDesc()
+    d = _lib.QuantStackDesc() if quants is not None else _lib.GatStackDesc() if gat else _lib.StackDesc()
     d.dtype, d.n_layers, d.n_rows, d.n_graphs = code, n, N, graph_ptr.numel() - 1
+    qstructs = []                                                                              # (held until the call returns)
     d.graph_ptr = graph_ptr.data_ptr()
     d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
     sparse = isinstance(x, Csr)
@@ -1591,6 +1609,10 @@ def _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, 
             if att.dtype != dtype or att.numel() != 2 * P:
                 raise ValueError(f"attentions[{l}] must hold 2 * {P} elements of {dtype}")
             L.gat_mode, L.attention, L.alpha = 1, att.data_ptr(), float(alpha)
+        if quants is not None and quants[l] is not None:
+            qstructs.append(quants[l].as_struct(nnz_adj=adj.nnz, nnz_fea=x.nnz if (l == 0 and sparse) else 0,
+                                                adj_done=adj_quantised))
+            L.quant = ctypes.pointer(qstructs[-1])
         if (want_layer_outputs and (keep is None or keep[l])) or (not readout and l == n - 1):
             D = torch.empty((N, P), dtype=dtype, device=dev)
             L.D, L.ldd = D.data_ptr(), P

@@ -404,9 +404,15 @@ class GAT_POOL_PYNQ(Module):
 
     With register layer_count >= 2 (layers per hardware call, SG.py:1862) the eval forward runs as ONE call,
     ops.gat_stack_forward (GCN layers in it when config.compute_attention == 0), where all of these hold: eval mode with
-    gradients off, config.acc == 1, the quantiser off, `batch` sorted with no edge between two of its graphs, and no row
-    of the adjacency without a positive entry (the stack gives such a row 0, the layer the mean of all rows; sym_norm2's
-    self loops leave none).  Every other case runs the layers one by one."""
+    gradients off, config.acc == 1, `batch` sorted with no edge between two of its graphs, and no row of the adjacency
+    without a positive entry (the stack gives such a row 0, the layer the mean of all rows; sym_norm2's self loops leave
+    none).  With the quantiser on (config.fake_quantization / hardware_quantize) the one call is
+    ops.quant_stack_forward -- layer 1 on quant_constants, layer 2 on its second_layer(), the cached quantised adjacency,
+    `layern` and the quantiser registers left as the two layer calls leave them -- where also config.float_type is
+    float32, the dead-row condition holds on the QUANTISED adjacency (at 4 bits and below the quantiser can kill a row),
+    and not both config.hardware_quantize and a hidden width over 128 (there the layer takes the int8 form, whose sums may
+    round differently).  Parity of the quantised layers is unpinned, as everywhere: the reference records no quantised
+    output.  Every other case runs the layers one by one."""
 
     def __init__(self, num_node_features, hidden_channels, num_classes):
         super(GAT_POOL_PYNQ, self).__init__()
@@ -423,7 +429,7 @@ class GAT_POOL_PYNQ(Module):
             return ei, norm, adj
 
         ei, norm, adj = ops.cached_on(edge_index, ("sym_norm2", x.size(0), config.acc, _torch_dtype()), normalise)
-        if config.acc == 1 and not self.training and not torch.is_grad_enabled() and not _quantised() and \
+        if config.acc == 1 and not self.training and not torch.is_grad_enabled() and \
                 my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2:
             out = self._forward_stack(x, adj, batch)
             if out is not None:
@@ -443,12 +449,20 @@ class GAT_POOL_PYNQ(Module):
         return self.lin(x)
 
     def _forward_stack(self, x, adj, batch):
-        """Both layers, the mean pool and the head through ops.gat_stack_forward; None (the caller then runs the layers
-        one by one) where the stack does not compute what they do."""
+        """Both layers, the mean pool and the head through ops.gat_stack_forward (ops.quant_stack_forward with the
+        quantiser on); None (the caller then runs the layers one by one) where the stack does not compute what they do."""
+        global layern
         dt = _torch_dtype()
         ptr = ops.graph_ptr_of(batch)
         gat = int(config.compute_attention)
-        if ptr is None or (gat and (self.att1.alpha != self.att2.alpha or adj.has_dead_rows is not False)):
+        qc = None
+        if _quantised():
+            qc = quant_constants
+            # (no constants, fp16: the layer's own errors; int8 operands: the layer's own form)
+            if qc is None or dt != torch.float32 or (config.hardware_quantize and self.att2.weight.shape[0] > 128):
+                return None
+        masked = adj if qc is None else adj.quantized(qc)                  # the adjacency a GAT layer masks with
+        if ptr is None or (gat and (self.att1.alpha != self.att2.alpha or masked.has_dead_rows is not False)):
             return None
         layers = (self.att1, self.att2)
         plan = ops.BatchPlan.cached(adj, ptr, max(self.att1.weight.shape[1], self.att2.weight.shape[0],
@@ -459,6 +473,12 @@ class GAT_POOL_PYNQ(Module):
             x.detach() if x.layout == torch.strided else x.detach().to_dense(), dt))
         weights = [c.weight.detach().t().to(dt).contiguous() for c in layers]
         atts = [c.attention.detach().to(dt).reshape(-1).contiguous() if gat else None for c in layers]
+        if qc is not None:
+            # the constants and registers of the two layer calls (FPYNQ_GAT.forward): `layern` alternates the two sets
+            quants = [qc.second_layer() if layern == 2 else qc, qc if layern == 2 else qc.second_layer()]
+            _program_quant_registers(my_ip.register_map, quants[1])
+            return ops.quant_stack_forward(masked, fea, weights, atts, [True, False], ptr, quants, self.lin.weight,
+                                           self.lin.bias, alpha=self.att1.alpha, plan=plan, adj_quantised=True)
         return ops.gat_stack_forward(adj, fea, weights, atts, [True, False], ptr, self.lin.weight, self.lin.bias,
                                      alpha=self.att1.alpha, plan=plan)
 

@@ -15,6 +15,10 @@ of --trials); the outputs of the two are checked bit-equal first.  One JSON line
         workloads: "chained" is the model with register layer_count 1 (its layer-by-layer path: per layer X.W and the edge
         softmax aggregate, then the readout), "fused" the same model with layer_count 2 (ops.gat_stack_forward, one launch).
         The two are checked against each other loosely only (the attention path's order is not pinned).
+    python tools/stack_probe.py --gat --quant 8 > quant_stack.jsonl
+        --quant N = that model with the quantiser on (config.fake_quantization = 1, w_qbits = N, fp32 buffers; without
+        --gat its GCN layers): "chained" is the layer-by-layer path (per layer the quantiser passes over W, the attention
+        vector and X, X.W, the scores, the aggregate; then the readout), "fused" ops.quant_stack_forward, one launch.
 """
 import argparse
 import json
@@ -61,9 +65,11 @@ def setup(copies, dev):
     return dict(chained=chained, fused=fused, n_graphs=n_graphs, nodes=x.shape[0], edges=adj.nnz, adj=adj, ptr=ptr)
 
 
-def setup_gat(copies, dev):
+def setup_gat(copies, dev, attention=1, quant=0):
     from sgracex1_amd import config, sgrace
-    config.acc, config.compute_attention, config.float_type = 1, 1, np.float16
+    config.acc, config.compute_attention, config.float_type = 1, attention, np.float32 if quant else np.float16
+    if quant:
+        config.fake_quantization, config.w_qbits = 1, quant
     ip = sgrace.init_SGRACE()
     x, ei, batch, n_graphs = mutag_batch(copies, dev)
     torch.manual_seed(12345)
@@ -77,7 +83,7 @@ def setup_gat(copies, dev):
         return fn
 
     run(1)()                                               # builds the cached adjacency the plan below is for
-    _ei, _norm, adj = ops.recorded(ei, ("sym_norm2", x.shape[0], 1, DT))
+    _ei, _norm, adj = ops.recorded(ei, ("sym_norm2", x.shape[0], 1, torch.float32 if quant else DT))
     return dict(chained=run(1), fused=run(2), n_graphs=n_graphs, nodes=x.shape[0], edges=adj.nnz, adj=adj,
                 ptr=ops.graph_ptr_of(batch))
 
@@ -103,15 +109,19 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--gat", action="store_true")
+    ap.add_argument("--quant", type=int, choices=[8, 4, 2, 1], default=0)
     args = ap.parse_args()
     dev = torch.device("cuda")
     work = [("mutag", 1), ("big", max(1, args.graphs // 188))]
     for name, copies in work:
         if args.only and name != args.only:
             continue
-        s = setup_gat(copies, dev) if args.gat else setup(copies, dev)
+        model = args.gat or args.quant
+        s = setup_gat(copies, dev, int(args.gat), args.quant) if model else setup(copies, dev)
         plan = ops.BatchPlan.cached(s["adj"], s["ptr"], 64)
-        if args.gat:
+        if args.quant and not args.gat:
+            assert torch.equal(s["chained"]().view(torch.int32), s["fused"]().view(torch.int32)), "fused != chained"
+        elif model:
             assert torch.allclose(s["chained"](), s["fused"](), rtol=1e-2, atol=1e-2), "fused far from chained"
         else:
             assert torch.equal(s["chained"]().view(torch.int32), s["fused"]().view(torch.int32)), "fused != chained"
@@ -123,8 +133,12 @@ def main():
             for _ in range(3):
                 fn()
             rec = {"workload": name, "form": form, "graphs": s["n_graphs"], "nodes": s["nodes"], "edges": s["edges"],
-                   "plan_groups": plan.groups, "plan_rows": plan.rows, "dtype": "f16",
-                   "model": "GAT_POOL_PYNQ" if args.gat else "GCN"}
+                   "plan_groups": plan.groups, "plan_rows": plan.rows, "dtype": "f32" if args.quant else "f16",
+                   "model": "GAT_POOL_PYNQ" if model else "GCN"}
+            if model:
+                rec["attention"] = int(args.gat)
+            if args.quant:
+                rec["w_qbits"] = args.quant
             rec["eager_ms"] = time_ms(fn, reps, args.trials)
             g = graphed.Graphed(fn)
             rec["graph_ms"] = time_ms(g, reps, args.trials)
