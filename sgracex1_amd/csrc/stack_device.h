@@ -1,6 +1,8 @@
-// What the small-graph stack kernels share (stack.hip: sgx_stack_forward / sgx_stack_backward; stack_gat.hip:
-// sgx_gat_stack_forward; stack_quant.hip: sgx_quant_stack_forward): the batch plan and its row budget, the LDS tiles' pitch, the matrix-core X.W on an LDS tile, the
-// stages of the forward kernel, and the descriptor checks and the chained path, which are the same for both descriptors.
+// What the small-graph stack's files share.  With all of them (stack_plan.hip: sgx_batch_plan_*; stack.hip: sgx_stack_forward;
+// stack_bwd.hip: sgx_stack_backward; stack_gat.hip: sgx_gat_stack_forward; stack_quant.hip: sgx_quant_stack_forward): the batch
+// plan and its row budget, the LDS tiles' pitch, a workgroup's group of graphs (stack_group), the matrix-core X.W on an LDS
+// tile, and the descriptor checks common to the forward and the backward descriptors (stack_check_*, stack_widths_fit).
+// With the three forward files: the stages of the forward kernel, check_stack_desc and the chained path.
 #pragma once
 #include "sgx_device.h"
 #include "quant_device.h"
@@ -54,6 +56,20 @@ inline int rows_budget(int dtype, int max_width, int kind)
                                                      : 2 * lds_pitch(dtype, max_width) * (int)sgx_elem_size(dtype);   // X/D + H
     const int rows = kStackLds / row_bytes / 16 * 16;                                         // whole 16-row MFMA tiles
     return rows < SGX_STACK_ROWS_CAP ? rows : SGX_STACK_ROWS_CAP;
+}
+
+// graphs [gf, gl) = rows [r0, r0 + nr) of the batch: group `grp` of the plan.  Empty (gf >= gl, nr = 0) when the group has
+// no graph or more rows than the tiles (the plan never makes such a group).
+struct StackGroup { int gf, gl, r0, nr; };
+__device__ __forceinline__ StackGroup stack_group(const int32_t *group_graph, const int32_t *graph_ptr, int rows, int grp)
+{
+    StackGroup g = {group_graph[grp], group_graph[grp + 1], 0, 0};
+    if (g.gf < g.gl) {
+        g.r0 = graph_ptr[g.gf];
+        g.nr = graph_ptr[g.gl] - g.r0;
+    }
+    if (g.nr > rows) g = {g.gf, g.gf, g.r0, 0};
+    return g;
 }
 
 // ---- the forward kernel's arguments and stages ----------------------------------------------------------------------
@@ -373,30 +389,34 @@ __device__ __forceinline__ void stack_readout(const StackArgs &a, int gf, int gl
     }
 }
 
-// ---- descriptor checks and the chained path, for sgx_stack_desc and sgx_gat_stack_desc alike ------------------------
+// ---- descriptor checks for the forward descriptors and sgx_stack_grad_desc alike; a caller's own go between them ------
 template <typename Layer> int64_t layer_ldd(const Layer &L) { return L.ldd == 0 ? L.P_w : L.ldd; }
 
-// layer_extra(L): what the descriptor's layer type adds to a layer's checks (SGX_OK for sgx_stack_layer)
-template <typename Desc, typename LayerExtra>
-int check_stack_desc(const Desc *d, LayerExtra layer_extra)
+// the descriptor itself: layer count, dtype, the plan and its batch
+template <typename Desc> int stack_check_head(const Desc *d)
 {
     if (!d) return SGX_ERR_NULL;
     if (d->n_layers < 1 || d->n_layers > kMaxLayers) return SGX_ERR_SHAPE;
     if (d->dtype != SGX_F16 && d->dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;
     if (!d->plan) return SGX_ERR_NULL;
     if (d->n_rows != d->plan->n_rows || d->n_graphs != d->plan->n_graphs) return SGX_ERR_SHAPE;
-    if (d->C < 0) return SGX_ERR_SHAPE;
-    for (int l = 0; l < d->n_layers; ++l) {
-        const auto &L = d->layer[l];
-        if (L.gemm_mode != 0 && L.gemm_mode != 1) return SGX_ERR_UNSUPPORTED;
-        if (l > 0 && L.gemm_mode != 1) return SGX_ERR_UNSUPPORTED;
-        if (L.M_fea < 1 || L.P_w < 1 || L.ldd < 0 || (L.ldd != 0 && L.ldd < L.P_w)) return SGX_ERR_SHAPE;
-        if (l > 0 && L.M_fea != d->layer[l - 1].P_w) return SGX_ERR_SHAPE;
-        if (!L.B) return SGX_ERR_NULL;
-        const int rc = layer_extra(L);
-        if (rc != SGX_OK) return rc;
-    }
-    if (d->C > 0 && !d->W_head) return SGX_ERR_NULL;
+    return SGX_OK;
+}
+
+// layer l's gemm_mode, widths and ldd
+template <typename Desc> int stack_check_layer_shape(const Desc *d, int l)
+{
+    const auto &L = d->layer[l];
+    if (L.gemm_mode != 0 && L.gemm_mode != 1) return SGX_ERR_UNSUPPORTED;
+    if (l > 0 && L.gemm_mode != 1) return SGX_ERR_UNSUPPORTED;
+    if (L.M_fea < 1 || L.P_w < 1 || L.ldd < 0 || (L.ldd != 0 && L.ldd < L.P_w)) return SGX_ERR_SHAPE;
+    if (l > 0 && L.M_fea != d->layer[l - 1].P_w) return SGX_ERR_SHAPE;
+    return SGX_OK;
+}
+
+// graph_ptr, the adjacency and the features of a batch that has any
+template <typename Desc> int stack_check_batch(const Desc *d)
+{
     if (d->n_graphs > 0 && !d->graph_ptr) return SGX_ERR_NULL;
     if (d->n_rows > 0) {
         if (!d->rowPtr_adj || !d->columnIndex_adj || !d->values_adj || !d->values_fea) return SGX_ERR_NULL;
@@ -405,17 +425,39 @@ int check_stack_desc(const Desc *d, LayerExtra layer_extra)
     return SGX_OK;
 }
 
+// every width the kernels put into an LDS tile is within the plan's
+template <typename Desc> bool stack_widths_fit(const Desc *d)
+{
+    for (int l = 0; l < d->n_layers; ++l) {
+        const auto &L = d->layer[l];
+        if (L.P_w > d->plan->max_width || ((l > 0 || L.gemm_mode == 1) && L.M_fea > d->plan->max_width)) return false;
+    }
+    return true;
+}
+
+// ---- the forward descriptors (sgx_stack_desc, sgx_gat_stack_desc, sgx_quant_stack_desc): checks and the chained path --
+// layer_extra(L): what the descriptor's layer type adds to a layer's checks (SGX_OK for sgx_stack_layer)
+template <typename Desc, typename LayerExtra>
+int check_stack_desc(const Desc *d, LayerExtra layer_extra)
+{
+    int rc = stack_check_head(d);
+    if (rc != SGX_OK) return rc;
+    if (d->C < 0) return SGX_ERR_SHAPE;
+    for (int l = 0; l < d->n_layers; ++l) {
+        if ((rc = stack_check_layer_shape(d, l)) != SGX_OK) return rc;
+        if (!d->layer[l].B) return SGX_ERR_NULL;
+        if ((rc = layer_extra(d->layer[l])) != SGX_OK) return rc;
+    }
+    if (d->C > 0 && !d->W_head) return SGX_ERR_NULL;
+    return stack_check_batch(d);
+}
+
 template <typename Desc>
 bool stack_fused_applies(const Desc *d)
 {
     const sgx_batch_plan *p = d->plan;
     if (!p->fits || p->n_groups < 1 || p->dtype != d->dtype || p->max_width > kStackMaxWidth) return false;
-    for (int l = 0; l < d->n_layers; ++l) {
-        const auto &L = d->layer[l];
-        if (L.P_w > p->max_width) return false;
-        if ((l > 0 || L.gemm_mode == 1) && L.M_fea > p->max_width) return false;
-    }
-    return true;
+    return stack_widths_fit(d);
 }
 
 struct ChainCarve {

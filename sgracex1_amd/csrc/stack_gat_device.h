@@ -147,11 +147,9 @@ __device__ __forceinline__ void gat_stack_body(const GatStackArgs &g, const Q &q
     T *const XD = reinterpret_cast<T *>(stack_lds);                 // X_l, then D_l      [rows][pitch]
     T *const Hs = XD + (size_t)a.rows * a.pitch;                    // H_l                [rows][pitch]
     float *const sc = reinterpret_cast<float *>(Hs + (size_t)a.rows * a.pitch);   // s1, s2, m, 1/l  [4][rows]
-    const int gf = a.group_graph[blockIdx.x], gl = a.group_graph[blockIdx.x + 1];
-    if (gf >= gl) return;
-    const int r0 = a.graph_ptr[gf], r1 = a.graph_ptr[gl];
-    const int nr = r1 - r0;
-    if (nr > a.rows) return;                                        // (the plan never makes such a group)
+    const StackGroup grp = stack_group(a.group_graph, a.graph_ptr, a.rows, blockIdx.x);
+    if (grp.gf >= grp.gl) return;
+    const int r0 = grp.r0, nr = grp.nr;
 
     for (int l = 0; l < a.n_layers; ++l) {
         stack_form_h<T, Q>(a, l, r0, nr, XD, Hs, q);
@@ -160,7 +158,7 @@ __device__ __forceinline__ void gat_stack_body(const GatStackArgs &g, const Q &q
         else stack_gcn_aggregate<T, Q>(a, l, r0, nr, XD, Hs, q);
         __syncthreads();
     }
-    stack_readout<T>(a, gf, gl, r0, XD);
+    stack_readout<T>(a, grp.gf, grp.gl, r0, XD);
 }
 
 // two workgroups per CU: 2 x (64 KiB of tiles + the score arrays) of the CU's 160 KiB, 8 of its 32 wavefronts
@@ -223,4 +221,3 @@ int check_gat_layer(const Layer &L)
 }
 
 }  // namespace
-
