@@ -70,8 +70,10 @@ __global__ __launch_bounds__(kBlock) void refhalf_csr_kernel(
     out[(int64_t)r * ldo + j] = v;
 }
 
-// The same arithmetic in the lane-group layout of the fast kernels (rows of at least 25 halves, 16-byte
-// aligned table): a group of LPR lanes owns a row, a lane 8 columns of it with its 4 x 8 partial sums in
+// The same arithmetic in the lane-group layout of the fast kernels, taken for every width when the table's
+// pointer and pitch are 16-byte aligned (LPR = next_pow2(ceil(P / 8)) clamped to 4..64: rows narrower than 25
+// halves leave lanes of the group idle, rows wider than 512 walk column tiles; the kernel above serves the
+// unaligned tables): a group of LPR lanes owns a row, a lane 8 columns of it with its 4 x 8 partial sums in
 // packed half registers; the row's entries are broadcast in order and every lane does the 8 rounded
 // products and the 8 rounded adds of its columns (v_pk_mul_f16 / v_pk_add_f16: one rounding each, what
 // the reference's half type does).  The partial an entry goes to is (phase + i) mod 4; the walk starts
