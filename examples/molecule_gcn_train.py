@@ -24,6 +24,9 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
         --qbits N (8, 4, 2 or 1; with --model gat) = the layers run the quantised arithmetic of the SGRACE bitstream
         (config.fake_quantization, fp32 emulation of the grid); with --layer-count 2 the accuracy passes are one call of
         sgx_quant_stack_forward.  Parity unpinned here too: the reference records no quantised output.
+    python examples/molecule_gcn_train.py --model gat --layer-count 2 --train-stack
+        --train-stack (without --qbits) = each training step's two attention layers and the pooling run as one forward
+        call (sgx_gat_stack_forward) and one backward call (sgx_gat_stack_backward) -- GAT_POOL_PYNQ(train_stack=True)
 """
 import argparse
 import json
@@ -53,8 +56,10 @@ def main():
     args = ap.parse_args()
     if args.qbits != 32 and args.model != "gat":
         ap.error("--qbits runs the quantised layers of the SGRACE library: --model gat")
-    if args.model == "gat" and (args.train_stack or args.acc != 1):
-        ap.error("--model gat trains layer by layer on the kernels (no --train-stack, --acc 1)")
+    if args.model == "gat" and args.acc != 1:
+        ap.error("--model gat trains on the kernels (--acc 1)")
+    if args.model == "gat" and args.train_stack and args.qbits != 32:
+        ap.error("--train-stack trains the unquantised layers (no --qbits)")
     if args.train_stack and args.layer_count < 2:
         ap.error("--train-stack needs --layer-count >= 2")
     if args.host_loader and args.batch_size <= 0:
@@ -77,7 +82,7 @@ def main():
         my_ip = sgrace.init_SGRACE()
         my_ip.register_map.layer_count = args.layer_count
         torch.manual_seed(12345)
-        gat = sgrace.GAT_POOL_PYNQ(7, 64, 2).to(dev)           # demo_sgrace.py:137-190
+        gat = sgrace.GAT_POOL_PYNQ(7, 64, 2, train_stack=args.train_stack).to(dev)   # demo_sgrace.py:137-190
         model = lambda _acc, x, edge_index, batch: gat(x, edge_index, batch)
         model.train, model.eval, model.parameters = gat.train, gat.eval, gat.parameters
     else:

@@ -1151,6 +1151,87 @@ typedef struct sgx_quant_stack_desc {
 size_t sgx_quant_stack_workspace_bytes(const sgx_quant_stack_desc *d);
 int sgx_quant_stack_forward(const sgx_quant_stack_desc *d, void *stream);
 
+/* ---- training the GAT stack ---------------------------------------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_gat_stack_backward is sgx_stack_backward with a per-layer choice of the matrix P in G_l = P . g_l: the adjacency
+ * (gat_mode 0) or the layer's attention matrix S (gat_mode 1), as the reference's FPYNQ_GAT.backward multiplies --
+ * grad_input = P (g W^T), grad_weights = X^T (P g), P and never P^T -- plus the gradient of the attention vector.  Every
+ * sum stays inside one graph, so inside one workgroup.  Parity of the GAT layer is UNPINNED: the reference records no GAT
+ * output; what is pinned is the float64 restatement of tests/_gat_stack_grad_ref.py.
+ *
+ * Plans: an SGX_BATCH_BACKWARD plan exactly as sgx_stack_backward takes it (same row budget R, same groups): one plan
+ * cached on a batch serves sgx_gat_stack_forward, sgx_stack_backward and this call.  Beside sgx_stack_backward's three
+ * tiles a row the kernel keeps Wh in fp32 and six floats (s1, s2, m, 1 / l, rs, g1): the launch asks for
+ * R x (grad_row_bytes + 4 lds_pitch(fp32, max_width) + 24) bytes of dynamic LDS (sgx_gat_stack_backward_lds_bytes; fp16
+ * at width 64: R = 80, 78 720 B; fp32 at width 256: R = 16, 66 944 B; under 100 KiB at every dtype and width), and
+ * SGX_ERR_UNSUPPORTED should that ever pass the 160 KiB a workgroup may declare.
+ *
+ * Semantics, per group of graphs, layers from the top down; g_{L-1}, the ReLU mask (where relu is set and D_l == 0) and
+ * the rounding of a handed-down gradient to dtype are sgx_stack_backward's:
+ *   gat_mode = 0: sgx_stack_backward's layer; G_l is bit-equal to it.
+ *   gat_mode = 1: the forward quantities are formed again from X_l (layer 0's features, or D_{l-1} as stored in dtype)
+ *     and the fp32 parameters:
+ *       Wh  = fp32(X_l) . W_l          fp32: dense layers in the MFMA layout and K order of sgx_xw_dense's fp32 kernel, a
+ *                                      sparse layer 0 by the fma chain in CSR order
+ *       s1  = Wh . a1, s2 = Wh . a2;   E_e = LeakyReLU_alpha(s1_i + s2_c) on every stored entry e = (i, c)
+ *       an entry is live iff values[e] > 0; m_i and l_i over the row's live entries;
+ *       S_e = exp(E_e - m_i) / l_i on live entries, 0 on masked ones
+ *     then, as sgx_gat_backward_edges:
+ *       d_e = g_i . Wh_c;  dx_e = S_e d_e;  rs_i = sum_row dx
+ *       sg_e = (dx_e - S_e rs_i) (E_e > 0 ? 1 : alpha), 0 on masked entries;  g1_i = sum_row sg
+ *       G_l = sum_e S_e g_c  (P . g);   T_i = sum_e sg_e Wh_c
+ *       grad_attention = [sum_i g1_i Wh_i ; sum_i T_i]     (sgx_gat_attention_grad's row-order form)
+ *       dW_l = X_l^T G_l;   g_{l-1} = dtype(G_l W_l^T), then the mask of layer l - 1
+ *     A row without a live entry has S = 0 on every entry and contributes nothing (the stack's zero rule; the
+ *     mean-of-all-rows rule is not offered).  One head.
+ * dW_l and grad_attention are summed as sgx_stack_backward sums dW: every workgroup of a persistent grid of
+ * min(max(groups, 1), 512) adds its groups (rows in order) into its own fp32 slice of the workspace with plain loads and
+ * stores, and a second launch adds the slices in slice order -- no atomics, the same bits on every run.  The summation
+ * order of the attention path is fixed by the layer's width alone and is not pinned to the chained kernels'.
+ *
+ * Limits: those of sgx_stack_backward.  No chained form inside the call: the model's layer-by-layer path is that form.
+ * Capturable: no allocation and no host synchronisation.
+ *
+ * Argument errors, returned before anything reaches the device: those of sgx_stack_backward; attention or
+ * grad_attention NULL on a layer with gat_mode = 1: SGX_ERR_NULL; gat_mode outside {0, 1}, a forward-kind plan:
+ * SGX_ERR_UNSUPPORTED.  n_rows == 0: every gradient is set to zero. */
+typedef struct sgx_gat_stack_grad_layer {
+    int32_t gemm_mode;    /* as sgx_stack_grad_layer, field for field */
+    int32_t relu;
+    int32_t M_fea, P_w;
+    const float *W;
+    const void *D;
+    int64_t ldd;
+    float *grad_W;
+    float *G;
+    int32_t gat_mode;         /* 0: P = the adjacency; 1: P = the edge softmax above */
+    const float *attention;   /* gat_mode = 1: the fp32 parameter [2 * P_w], a1 then a2 */
+    float alpha;              /* LeakyReLU slope of the scores */
+    float *grad_attention;    /* gat_mode = 1, out: [2 * P_w] fp32 */
+    float *S, *E;             /* gat_mode = 1, optional outs: [nnz_adj] fp32 (NULL = not written) */
+} sgx_gat_stack_grad_layer;
+
+typedef struct sgx_gat_stack_grad_desc {
+    int32_t dtype, n_layers;                   /* as sgx_stack_grad_desc, field for field */
+    int32_t n_rows, n_graphs;
+    const int32_t *graph_ptr;
+    const int32_t *rowPtr_adj, *columnIndex_adj; const void *values_adj;
+    const int32_t *rowPtr_fea, *columnIndex_fea; const void *values_fea;
+    sgx_gat_stack_grad_layer layer[4];
+    const float *grad_pooled;
+    const sgx_batch_plan *plan;                /* an SGX_BATCH_BACKWARD plan */
+    void *workspace; size_t workspace_bytes;   /* sgx_gat_stack_backward_workspace_bytes(d), 256-byte aligned */
+} sgx_gat_stack_grad_desc;
+
+/* the gradient slices: min(max(groups, 1), 512) x (sum_l M_fea P_w + sum over GAT layers 2 P_w) floats, every block
+ * padded to 16 bytes; 0 for a descriptor the call refuses */
+size_t sgx_gat_stack_backward_workspace_bytes(const sgx_gat_stack_grad_desc *d);
+/* informational: the dynamic LDS of the launch in bytes, computed on the host (no caller needs it to make the call; the
+ * tests check the formula above with it); 0 for a descriptor the call refuses */
+size_t sgx_gat_stack_backward_lds_bytes(const sgx_gat_stack_grad_desc *d);
+int sgx_gat_stack_backward(const sgx_gat_stack_grad_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

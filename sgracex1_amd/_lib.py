@@ -49,6 +49,7 @@ SYMBOLS = [
     "sgx_csr_transpose_workspace_bytes", "sgx_csr_transpose",
     "sgx_gat_stack_workspace_bytes", "sgx_gat_stack_forward",
     "sgx_quant_stack_workspace_bytes", "sgx_quant_stack_forward",
+    "sgx_gat_stack_backward_workspace_bytes", "sgx_gat_stack_backward_lds_bytes", "sgx_gat_stack_backward",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -169,6 +170,19 @@ class StackGradDesc(ctypes.Structure):
         ("plan", ctypes.c_void_p),
         ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_size_t),
     ]
+
+
+class GatStackGradLayer(ctypes.Structure):
+    """struct sgx_gat_stack_grad_layer -- field order and types must match include/sgx.h."""
+    _fields_ = StackGradLayer._fields_ + [
+        ("gat_mode", ctypes.c_int32), ("attention", ctypes.c_void_p), ("alpha", ctypes.c_float),
+        ("grad_attention", ctypes.c_void_p), ("S", ctypes.c_void_p), ("E", ctypes.c_void_p),
+    ]
+
+
+class GatStackGradDesc(ctypes.Structure):
+    """struct sgx_gat_stack_grad_desc -- field order and types must match include/sgx.h."""
+    _fields_ = [(n, GatStackGradLayer * 4 if n == "layer" else t) for n, t in StackGradDesc._fields_]
 
 
 class GraphSet(ctypes.Structure):
@@ -393,6 +407,12 @@ def _load():
     lib.sgx_stack_backward_workspace_bytes.restype = sz
     lib.sgx_stack_backward.argtypes = [ctypes.POINTER(StackGradDesc), vp]
     lib.sgx_stack_backward.restype = c_int
+    lib.sgx_gat_stack_backward_workspace_bytes.argtypes = [ctypes.POINTER(GatStackGradDesc)]
+    lib.sgx_gat_stack_backward_workspace_bytes.restype = sz
+    lib.sgx_gat_stack_backward_lds_bytes.argtypes = [ctypes.POINTER(GatStackGradDesc)]
+    lib.sgx_gat_stack_backward_lds_bytes.restype = sz
+    lib.sgx_gat_stack_backward.argtypes = [ctypes.POINTER(GatStackGradDesc), vp]
+    lib.sgx_gat_stack_backward.restype = c_int
     lib.sgx_collate_graphs.argtypes = [ctypes.POINTER(GraphSet), ctypes.POINTER(GraphBatch), vp]
     lib.sgx_collate_graphs.restype = c_int
     lib.sgx_batch_plan_group_count.argtypes = [c_int, c_int, c_int, c_int, c_int]

@@ -1761,3 +1761,127 @@ class GcnStack(torch.autograd.Function):
         weights = rest
         grads = gcn_stack_backward(ctx.adj, ctx.x, weights, ctx.relus, graph_ptr, outs, grad_pooled, plan=ctx.plan)
         return (None, None, None, None, None) + tuple(grads[:n])
+
+
+# ---- the backward of the GAT stack for training (sgx_gat_stack_backward) -----------------------------------------------
+def gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha=0.2, plan=None,
+                       want_G=False, want_edge_outputs=False):
+    """gcn_stack_backward with a per-layer choice of P in G_l = P . g_l (include/sgx.h, "training the GAT stack"):
+    attentions[l] is layer l's fp32 attention parameter (2 * P_l elements, a1 then a2) -- P is then the layer's edge
+    softmax, formed again from X_l and the fp32 parameters -- or None for a GCN layer (P = the adjacency).  The other
+    arguments are gcn_stack_backward's.  Returns (dW list, grad_attention list -- [2 * P_l] fp32, None for a GCN layer
+    [, G list] [, (E, S) list -- [nnz] fp32 each, None for a GCN layer]).  Raises SgxError SGX_ERR_UNSUPPORTED where the
+    batch or the widths are outside the kernel's limits -- the caller then runs the layers one by one."""
+    n = len(weights)
+    if not 1 <= n <= 4 or len(relus) != n or len(layer_outputs) != n or len(attentions) != n:
+        raise ValueError("gat_stack_backward takes 1 to 4 layers; one attention vector (or None), one relu flag and one "
+                         "layer output per layer")
+    dtype = adj.val.dtype
+    N, dev = adj.n_rows, adj.val.device
+    _dev(graph_ptr, "graph_ptr")
+    d = _lib.GatStackGradDesc()
+    d.dtype, d.n_layers, d.n_rows, d.n_graphs = dtype_code(dtype), n, N, graph_ptr.numel() - 1
+    d.graph_ptr = graph_ptr.data_ptr()
+    d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
+    sparse = isinstance(x, Csr)
+    if sparse:
+        if x.val.dtype != dtype or x.n_rows != N:
+            raise ValueError("feature CSR does not match the adjacency")
+        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = x.rowptr.data_ptr(), x.col.data_ptr(), x.val.data_ptr()
+        k_in = x.n_cols
+    else:
+        _dev(x, "x")
+        if x.dtype != dtype or x.dim() != 2 or x.shape[0] != N:
+            raise ValueError(f"dense features must be [{N}, M] {dtype}")
+        d.values_fea = x.data_ptr()
+        k_in = x.shape[1]
+    grads, gatts, Gs, edges, keep = [], [], [], [], []
+    for l, (W, att, relu, D) in enumerate(zip(weights, attentions, relus, layer_outputs)):
+        W = _dev(W.detach().float().contiguous(), f"weights[{l}]")
+        M, P = W.shape
+        if M != k_in:
+            raise ValueError(f"weights[{l}] must be [{k_in}, P], got {tuple(W.shape)}")
+        L = d.layer[l]
+        L.gemm_mode = 0 if (l == 0 and sparse) else 1
+        L.relu, L.M_fea, L.P_w, L.W = int(bool(relu)), M, P, W.data_ptr()
+        if D is not None:
+            _dev2d(D, f"layer_outputs[{l}]")
+            if D.dtype != dtype or D.shape != (N, P):
+                raise ValueError(f"layer_outputs[{l}] must be [{N}, {P}] {dtype}")
+            L.D, L.ldd = D.data_ptr(), D.stride(0)
+        gW = torch.empty((M, P), dtype=torch.float32, device=dev)
+        L.grad_W = gW.data_ptr()
+        grads.append(gW)
+        ga = ES = None
+        if att is not None:
+            att = _dev(att.detach().float().reshape(-1).contiguous(), f"attentions[{l}]")
+            if att.numel() != 2 * P:
+                raise ValueError(f"attentions[{l}] must hold 2 * {P} elements")
+            ga = torch.empty(2 * P, dtype=torch.float32, device=dev)
+            L.gat_mode, L.attention, L.alpha, L.grad_attention = 1, att.data_ptr(), float(alpha), ga.data_ptr()
+            if want_edge_outputs:
+                ES = (torch.zeros(adj.nnz, dtype=torch.float32, device=dev), torch.zeros(adj.nnz, dtype=torch.float32, device=dev))
+                L.E, L.S = ES[0].data_ptr(), ES[1].data_ptr()
+        gatts.append(ga)
+        edges.append(ES)
+        if want_G:
+            G = torch.empty((N, P), dtype=torch.float32, device=dev)
+            L.G = G.data_ptr()
+            Gs.append(G)
+        keep.append((W, att))
+        k_in = P
+    g = _dev(grad_pooled.detach().float().contiguous(), "grad_pooled")
+    if g.shape != (d.n_graphs, k_in):
+        raise ValueError(f"grad_pooled must be [{d.n_graphs}, {k_in}]")
+    d.grad_pooled = g.data_ptr()
+    if plan is None:
+        widths = [w.shape[1] for w, _ in keep] + [w.shape[0] for l, (w, _) in enumerate(keep) if l > 0 or not sparse]
+        plan = BatchPlan.cached(adj, graph_ptr, max(widths), _lib.SGX_BATCH_BACKWARD)
+        if plan is None:
+            check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create_ex")
+    d.plan = plan.handle
+    nbytes = lib.sgx_gat_stack_backward_workspace_bytes(ctypes.byref(d))
+    if nbytes:
+        ws = _workspace(dev, nbytes)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(lib.sgx_gat_stack_backward(ctypes.byref(d), _stream()), "sgx_gat_stack_backward")
+    return (grads, gatts) + ((Gs,) if want_G else ()) + ((edges,) if want_edge_outputs else ())
+
+
+class GatStack(torch.autograd.Function):
+    """GcnStack with GAT layers: forward = sgx_gat_stack_forward without a head (the pooled fp32 means, every D_l saved),
+    backward = sgx_gat_stack_backward (fp32 gradients of the weights [in, out] and of the attention vectors [2 P, 1], as
+    FPYNQ_GAT.backward returns them).  No gradient for the features: a feature tensor that needs one is refused.
+
+        pooled = GatStack.apply(adj, x, graph_ptr, plan, relus, alpha, W_0, ..., W_{L-1}, a_0, ..., a_{L-1})
+
+    plan: an SGX_BATCH_BACKWARD BatchPlan that fits; W_l: the fp32 parameters [M_l, P_l]; a_l: the fp32 attention
+    parameter [2 P_l, 1], or None for a GCN layer."""
+
+    @staticmethod
+    def forward(ctx, adj, x, graph_ptr, plan, relus, alpha, *params):
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise ValueError("GatStack gives no gradient for the features; x must not require grad")
+        n = len(relus)
+        if len(params) != 2 * n:
+            raise ValueError("GatStack takes one weight and one attention vector (or None) per layer")
+        weights, atts = params[:n], params[n:]
+        dtype = adj.val.dtype
+        wts = [torch.transpose(w, 0, 1).detach().to(dtype).contiguous() for w in weights]
+        ats = [None if a is None else a.detach().to(dtype).reshape(-1).contiguous() for a in atts]
+        pooled, outs = gat_stack_forward(adj, x, wts, ats, relus, graph_ptr, alpha=alpha, want_layer_outputs=True, plan=plan)
+        ctx.adj, ctx.x, ctx.plan, ctx.relus, ctx.alpha = adj, x, plan, list(relus), alpha
+        ctx.gat = [a is not None for a in atts]
+        ctx.save_for_backward(graph_ptr, *outs, *weights, *[a for a in atts if a is not None])
+        return pooled
+
+    @staticmethod
+    def backward(ctx, grad_pooled):
+        saved = ctx.saved_tensors
+        n = len(ctx.relus)
+        graph_ptr, outs, weights, rest = saved[0], list(saved[1:1 + n]), list(saved[1 + n:1 + 2 * n]), list(saved[1 + 2 * n:])
+        atts = [rest.pop(0) if g else None for g in ctx.gat]
+        dW, dA = gat_stack_backward(ctx.adj, ctx.x, weights, atts, ctx.relus, graph_ptr, outs, grad_pooled, alpha=ctx.alpha,
+                                    plan=ctx.plan)
+        dA = [None if g is None else g.reshape(a.shape) for g, a in zip(dA, atts)]
+        return (None,) * 6 + tuple(dW) + tuple(dA)

@@ -412,10 +412,18 @@ class GAT_POOL_PYNQ(Module):
     float32, the dead-row condition holds on the QUANTISED adjacency (at 4 bits and below the quantiser can kill a row),
     and not both config.hardware_quantize and a hidden width over 128 (there the layer takes the int8 form, whose sums may
     round differently).  Parity of the quantised layers is unpinned, as everywhere: the reference records no quantised
-    output.  Every other case runs the layers one by one."""
+    output.  Every other case runs the layers one by one.
 
-    def __init__(self, num_node_features, hidden_channels, num_classes):
+    train_stack (opt-in, also settable as an attribute): with layer_count >= 2 a training step's two layers and the mean
+    pool run as one forward and one backward call (ops.GatStack: sgx_gat_stack_forward, sgx_gat_stack_backward; GCN layers
+    in them when config.compute_attention == 0) where all of these hold: config.acc == 1, the quantiser off, x needing no
+    gradient, `batch` sorted with no edge between two of its graphs, no row of the adjacency without a positive entry,
+    one alpha for both layers, and every graph within the backward plan's row budget.  Dropout and the head stay in torch
+    behind the pooled output.  Every other case runs the layers one by one."""
+
+    def __init__(self, num_node_features, hidden_channels, num_classes, train_stack=False):
         super(GAT_POOL_PYNQ, self).__init__()
+        self.train_stack = bool(train_stack)
         self.att1 = GATConv_SGRACE(num_node_features, hidden_channels, 1)
         self.att2 = GATConv_SGRACE(hidden_channels, hidden_channels, 1)
         self.reluh = Relu_SGRACE()
@@ -434,6 +442,12 @@ class GAT_POOL_PYNQ(Module):
             out = self._forward_stack(x, adj, batch)
             if out is not None:
                 return out
+        if config.acc == 1 and getattr(self, "train_stack", False) and torch.is_grad_enabled() and \
+                my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2:
+            # the training step's two layers and the pooling as one forward and one backward call
+            pooled = self._train_stack(x, adj, batch)
+            if pooled is not None:
+                return self.lin(F.dropout(pooled, p=0.5, training=self.training))
         x = self.att1(config.compute_attention, 0, 1, x, ei, norm, adj)
         x = self.reluh(x)
         x = self.att2(config.compute_attention, 1, 0, x, ei, norm, adj)
@@ -481,6 +495,29 @@ class GAT_POOL_PYNQ(Module):
                                            self.lin.bias, alpha=self.att1.alpha, plan=plan, adj_quantised=True)
         return ops.gat_stack_forward(adj, fea, weights, atts, [True, False], ptr, self.lin.weight, self.lin.bias,
                                      alpha=self.att1.alpha, plan=plan)
+
+    def _train_stack(self, x, adj, batch):
+        """Both layers and the mean pool through ops.GatStack: the pooled means [G, hidden] fp32 with the gradients of the
+        weights and the attention vectors behind them.  None (the caller then runs the layers one by one) where one of the
+        class docstring's conditions fails."""
+        if _quantised() or x.requires_grad:
+            return None
+        dt = _torch_dtype()
+        ptr = ops.graph_ptr_of(batch)
+        gat = int(config.compute_attention)
+        if ptr is None or (gat and (self.att1.alpha != self.att2.alpha or adj.has_dead_rows is not False)):
+            return None
+        width = max(self.att1.weight.shape[1], self.att2.weight.shape[0], self.att2.weight.shape[1])
+        if width > 256:
+            return None
+        plan = ops.BatchPlan.cached(adj, ptr, width, ops._lib.SGX_BATCH_BACKWARD)
+        if plan is None or not plan.fits:
+            return None
+        fea = ops.cached_on(x, ("fea_csr", dt), lambda: ops.Csr.from_dense(
+            x.detach() if x.layout == torch.strided else x.detach().to_dense(), dt))
+        layers = (self.att1, self.att2)
+        atts = [c.attention if gat else None for c in layers]
+        return ops.GatStack.apply(adj, fea, ptr, plan, (True, False), self.att1.alpha, *[c.weight for c in layers], *atts)
 
 
 def init_SGRACE(device=None):

@@ -10,6 +10,11 @@ difference; hipEvents around --reps calls after warm-up, median of --trials.  gr
 hipGraph (null where the capture fails).  The two forms' losses are checked bit-equal first.  One JSON line each.
 
     python tools/stack_train_probe.py > stack_train.jsonl
+    python tools/stack_train_probe.py --gat > profiles/r15_gat_stack_train.jsonl
+        --gat = the SGRACE demo's graph classifier of attention layers instead (sgrace.GAT_POOL_PYNQ, fp32 layer buffers):
+        GAT_POOL_PYNQ(train_stack=True) (sgx_gat_stack_forward + sgx_gat_stack_backward) against its layer-by-layer step,
+        on the MUTAG batch only, eager and replayed.  The two forms' losses are not bit-equal there (the attention path's
+        summation order is unpinned); the line records both.
 """
 import argparse
 import json
@@ -32,14 +37,71 @@ def model(form, dev):
     return M.GCN_PYNQ(64, 7, 2, ip, train_stack=form == "fused").to(dev).train()
 
 
+def gat_main(args, dev):
+    """The --gat lines: one per form on the MUTAG batch."""
+    from sgracex1_amd import config, sgrace
+    config.acc, config.compute_attention, config.float_type = 1, 1, np.float32
+    ip = sgrace.init_SGRACE()
+    x, ei, batch, n_graphs = mutag_batch(1, dev)
+    y = torch.randint(0, 2, (n_graphs,), device=dev, generator=torch.Generator(device=dev).manual_seed(1))
+    crit = torch.nn.CrossEntropyLoss()
+    torch.manual_seed(12345)
+    models = {form: sgrace.GAT_POOL_PYNQ(7, 64, 2, train_stack=form == "fused").to(dev).train() for form in ("fused", "chained")}
+    models["chained"].load_state_dict(models["fused"].state_dict())
+
+    def fwd(m):
+        return crit(m(x, ei, batch), y)
+
+    def step(m):
+        m.zero_grad(set_to_none=True)
+        loss = fwd(m)
+        loss.backward()
+        return loss
+
+    for form, m in models.items():
+        ip.register_map.layer_count = 2 if form == "fused" else 1
+        torch.manual_seed(7)
+        loss = float(step(m).detach())
+        for _ in range(3):
+            step(m)
+        rec = {"workload": "mutag", "model": "gat", "form": form, "graphs": n_graphs, "nodes": x.shape[0], "edges": ei.shape[1],
+               "dtype": "f32", "first_loss": loss}
+        rec["fwd_ms"] = time_ms(lambda: fwd(m), args.reps, args.trials)
+        rec["step_ms"] = time_ms(lambda: step(m), args.reps, args.trials)
+        rec["bwd_ms"] = rec["step_ms"] - rec["fwd_ms"]
+        rec["graph_step_ms"] = None
+        try:
+            side = torch.cuda.Stream()
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    step(m)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize()
+            m.zero_grad(set_to_none=True)
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                fwd(m).backward()
+            rec["graph_step_ms"] = time_ms(g.replay, args.reps, args.trials)
+            del g
+        except Exception as e:                          # (a path that synchronises cannot be captured)
+            rec["graph_error"] = f"{type(e).__name__}: {str(e)[:120]}"
+            torch.cuda.synchronize()
+        rec["graphs_per_s_step"] = n_graphs / (rec["step_ms"] * 1e-3)
+        print(json.dumps(rec), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--gat", action="store_true")
     ap.add_argument("--only", choices=["mutag", "big"], default=None)
     ap.add_argument("--graphs", type=int, default=1_000_160)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--trials", type=int, default=5)
     args = ap.parse_args()
     dev = torch.device("cuda")
+    if args.gat:
+        return gat_main(args, dev)
     for name, copies in (("mutag", 1), ("big", max(1, args.graphs // 188))):
         if args.only and name != args.only:
             continue
