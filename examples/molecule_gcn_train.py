@@ -25,8 +25,9 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
         (config.fake_quantization, fp32 emulation of the grid); with --layer-count 2 the accuracy passes are one call of
         sgx_quant_stack_forward.  Parity unpinned here too: the reference records no quantised output.
     python examples/molecule_gcn_train.py --model gat --layer-count 2 --train-stack
-        --train-stack (without --qbits) = each training step's two attention layers and the pooling run as one forward
-        call (sgx_gat_stack_forward) and one backward call (sgx_gat_stack_backward) -- GAT_POOL_PYNQ(train_stack=True)
+        --train-stack = each training step's two attention layers and the pooling run as one forward call
+        (sgx_gat_stack_forward) and one backward call (sgx_gat_stack_backward) -- GAT_POOL_PYNQ(train_stack=True); with
+        --qbits N the two calls are sgx_quant_stack_forward and sgx_quant_stack_backward
 """
 import argparse
 import json
@@ -58,8 +59,6 @@ def main():
         ap.error("--qbits runs the quantised layers of the SGRACE library: --model gat")
     if args.model == "gat" and args.acc != 1:
         ap.error("--model gat trains on the kernels (--acc 1)")
-    if args.model == "gat" and args.train_stack and args.qbits != 32:
-        ap.error("--train-stack trains the unquantised layers (no --qbits)")
     if args.train_stack and args.layer_count < 2:
         ap.error("--train-stack needs --layer-count >= 2")
     if args.host_loader and args.batch_size <= 0:

@@ -1232,6 +1232,80 @@ size_t sgx_gat_stack_backward_workspace_bytes(const sgx_gat_stack_grad_desc *d);
 size_t sgx_gat_stack_backward_lds_bytes(const sgx_gat_stack_grad_desc *d);
 int sgx_gat_stack_backward(const sgx_gat_stack_grad_desc *d, void *stream);
 
+/* ---- training the quantised stack ---------------------------------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_quant_stack_backward is sgx_gat_stack_backward with a per-layer quantiser: the backward of the stack that
+ * sgx_quant_stack_forward runs, by the rule of the reference's FPYNQ_GAT.backward under fake quantisation -- "the
+ * backward pass uses the unquantised operands".  The attention matrix of a quantised GAT layer is the QUANTISED
+ * forward's S, formed again in the kernel; everything a gradient multiplies with is unquantised.  Parity of the
+ * quantised layer is UNPINNED; what is pinned is the float64 restatement of tests/_quant_stack_grad_ref.py.
+ *
+ * Plans, LDS, workspace: the same SGX_BATCH_BACKWARD plan as sgx_stack_backward and sgx_gat_stack_backward, the LDS
+ * formula of sgx_gat_stack_backward_lds_bytes (H_q and the unquantised Wh share one tile), the same gradient slices and
+ * reduction launch.  No atomics, no order that depends on the grid, capturable.  No chained form inside the call.
+ *
+ * Semantics, per layer l from the top down; g_{L-1}, the ReLU mask (relu set and D_l == 0) and the rounding of
+ * handed-down gradients are sgx_stack_backward's.  D_l is the quantised forward's output, act(aggregate) * deq_factor, as
+ * sgx_quant_stack_forward stored it; deq_factor is applied to no gradient (straight-through):
+ *   gat_mode = 0, quantised or not: P is the UNQUANTISED adjacency (values_adj), X_l the unquantised input (layer 0's
+ *     features, or D_{l-1} as stored), W_l the fp32 parameter: sgx_stack_backward's layer, G_l bit-equal to it.
+ *   gat_mode = 1 with quant = q:
+ *     1. H_q = requant(X_q . W_q) as sgx_quant_stack_forward forms it: X on the unsigned grid with layer l's
+ *        (inv_scale_fea, zero_fea), W on the signed grid, then the shift by scale_fea, the clip and the decimal
+ *        rounding; one device quantiser statement per rounding point, contraction off; pad elements stay 0.
+ *     2. s1 = H_q . a1_q, s2 = H_q . a2_q with the attention vector on the signed grid; E_e = LeakyReLU(s1_i + s2_c);
+ *        an entry is live iff its QUANTISED adjacency value is > 0 -- values_adj_q[e] as stored where q->flags has
+ *        SGX_QUANT_ADJ_DONE, values_adj[e] quantised with (inv_scale_adj, zero_adj) as it is read otherwise; m_i, l_i
+ *        and S_e as in sgx_gat_stack_backward.
+ *     3. Wh = fp32(X_l) . W_l UNQUANTISED, written over H_q's LDS tile (H_q is dead once s1, s2, m and 1 / l exist).
+ *     4. sgx_gat_stack_backward's passes on S, E and the unquantised Wh: G_l = sum_e S_e g_c; sg, g1 and T;
+ *        grad_attention = [sum_i g1_i Wh_i ; sum_i T_i]; dW_l = X_l^T G_l; g_{l-1} = dtype(G_l W_l^T).
+ *     A row without a live entry contributes nothing (the stack's zero rule).
+ *   quant = NULL: sgx_gat_stack_backward's layer bit for bit; a descriptor without a quantised GAT layer is that call.
+ * Fields of sgx_quant read: qbits, scale_fea, internal_bits, flags (SGX_QUANT_ADJ_DONE only), the three (inv_scale,
+ * zero) pairs.
+ *
+ * Argument errors, returned before anything reaches the device: those of sgx_gat_stack_backward; a layer with quant set
+ * while dtype != SGX_F32, qbits outside {8, 4, 2, 1}, scale_fea outside 0..30, internal_bits outside 1..30, zero_adj
+ * != 0, or zero_fea != 0 on a sparse layer 0: SGX_ERR_UNSUPPORTED; a GAT layer with SGX_QUANT_ADJ_DONE while
+ * values_adj_q == NULL: SGX_ERR_NULL.  n_rows == 0: every gradient is set to zero. */
+typedef struct sgx_quant_stack_grad_layer {
+    int32_t gemm_mode;    /* as sgx_gat_stack_grad_layer, field for field */
+    int32_t relu;
+    int32_t M_fea, P_w;
+    const float *W;
+    const void *D;
+    int64_t ldd;
+    float *grad_W;
+    float *G;
+    int32_t gat_mode;
+    const float *attention;
+    float alpha;
+    float *grad_attention;
+    float *S, *E;
+    const sgx_quant *quant;   /* this layer's quantiser; NULL = the plain layer of sgx_gat_stack_backward */
+} sgx_quant_stack_grad_layer;
+
+typedef struct sgx_quant_stack_grad_desc {
+    int32_t dtype, n_layers;                   /* as sgx_gat_stack_grad_desc, field for field */
+    int32_t n_rows, n_graphs;
+    const int32_t *graph_ptr;
+    const int32_t *rowPtr_adj, *columnIndex_adj; const void *values_adj;   /* the UNQUANTISED adjacency */
+    const int32_t *rowPtr_fea, *columnIndex_fea; const void *values_fea;
+    sgx_quant_stack_grad_layer layer[4];
+    const float *grad_pooled;
+    const sgx_batch_plan *plan;                /* an SGX_BATCH_BACKWARD plan */
+    void *workspace; size_t workspace_bytes;   /* sgx_quant_stack_backward_workspace_bytes(d), 256-byte aligned */
+    const float *values_adj_q;                 /* [nnz_adj] fp32, the quantised adjacency: what a GAT layer whose quant has
+                                                  SGX_QUANT_ADJ_DONE masks with; NULL where no layer has the flag */
+} sgx_quant_stack_grad_desc;
+
+/* sgx_gat_stack_backward_workspace_bytes' and _lds_bytes' formulas; 0 for a descriptor the call refuses */
+size_t sgx_quant_stack_backward_workspace_bytes(const sgx_quant_stack_grad_desc *d);
+size_t sgx_quant_stack_backward_lds_bytes(const sgx_quant_stack_grad_desc *d);
+int sgx_quant_stack_backward(const sgx_quant_stack_grad_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -50,6 +50,7 @@ SYMBOLS = [
     "sgx_gat_stack_workspace_bytes", "sgx_gat_stack_forward",
     "sgx_quant_stack_workspace_bytes", "sgx_quant_stack_forward",
     "sgx_gat_stack_backward_workspace_bytes", "sgx_gat_stack_backward_lds_bytes", "sgx_gat_stack_backward",
+    "sgx_quant_stack_backward_workspace_bytes", "sgx_quant_stack_backward_lds_bytes", "sgx_quant_stack_backward",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -183,6 +184,17 @@ class GatStackGradLayer(ctypes.Structure):
 class GatStackGradDesc(ctypes.Structure):
     """struct sgx_gat_stack_grad_desc -- field order and types must match include/sgx.h."""
     _fields_ = [(n, GatStackGradLayer * 4 if n == "layer" else t) for n, t in StackGradDesc._fields_]
+
+
+class QuantStackGradLayer(ctypes.Structure):
+    """struct sgx_quant_stack_grad_layer -- field order and types must match include/sgx.h."""
+    _fields_ = GatStackGradLayer._fields_ + [("quant", ctypes.POINTER(Quant))]
+
+
+class QuantStackGradDesc(ctypes.Structure):
+    """struct sgx_quant_stack_grad_desc -- field order and types must match include/sgx.h."""
+    _fields_ = [(n, QuantStackGradLayer * 4 if n == "layer" else t) for n, t in StackGradDesc._fields_] + [
+        ("values_adj_q", ctypes.c_void_p)]
 
 
 class GraphSet(ctypes.Structure):
@@ -413,6 +425,12 @@ def _load():
     lib.sgx_gat_stack_backward_lds_bytes.restype = sz
     lib.sgx_gat_stack_backward.argtypes = [ctypes.POINTER(GatStackGradDesc), vp]
     lib.sgx_gat_stack_backward.restype = c_int
+    lib.sgx_quant_stack_backward_workspace_bytes.argtypes = [ctypes.POINTER(QuantStackGradDesc)]
+    lib.sgx_quant_stack_backward_workspace_bytes.restype = sz
+    lib.sgx_quant_stack_backward_lds_bytes.argtypes = [ctypes.POINTER(QuantStackGradDesc)]
+    lib.sgx_quant_stack_backward_lds_bytes.restype = sz
+    lib.sgx_quant_stack_backward.argtypes = [ctypes.POINTER(QuantStackGradDesc), vp]
+    lib.sgx_quant_stack_backward.restype = c_int
     lib.sgx_collate_graphs.argtypes = [ctypes.POINTER(GraphSet), ctypes.POINTER(GraphBatch), vp]
     lib.sgx_collate_graphs.restype = c_int
     lib.sgx_batch_plan_group_count.argtypes = [c_int, c_int, c_int, c_int, c_int]

@@ -1772,14 +1772,31 @@ def gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outp
     arguments are gcn_stack_backward's.  Returns (dW list, grad_attention list -- [2 * P_l] fp32, None for a GCN layer
     [, G list] [, (E, S) list -- [nnz] fp32 each, None for a GCN layer]).  Raises SgxError SGX_ERR_UNSUPPORTED where the
     batch or the widths are outside the kernel's limits -- the caller then runs the layers one by one."""
+    return _gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha, plan, want_G,
+                               want_edge_outputs)
+
+
+def _gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha, plan, want_G,
+                        want_edge_outputs, quants=None, adj_q=None):
+    """The descriptor of sgx_gat_stack_backward or sgx_quant_stack_backward (quants given), its workspace and the call."""
+    name = "sgx_quant_stack_backward" if quants is not None else "sgx_gat_stack_backward"
     n = len(weights)
-    if not 1 <= n <= 4 or len(relus) != n or len(layer_outputs) != n or len(attentions) != n:
-        raise ValueError("gat_stack_backward takes 1 to 4 layers; one attention vector (or None), one relu flag and one "
-                         "layer output per layer")
+    if not 1 <= n <= 4 or len(relus) != n or len(layer_outputs) != n or len(attentions) != n or \
+            (quants is not None and len(quants) != n):
+        raise ValueError(f"{'quant' if quants is not None else 'gat'}_stack_backward takes 1 to 4 layers; one attention vector "
+                         "(or None), one relu flag and one layer output per layer"
+                         + (", one QuantConstants (or None) per layer" if quants is not None else ""))
     dtype = adj.val.dtype
     N, dev = adj.n_rows, adj.val.device
     _dev(graph_ptr, "graph_ptr")
-    d = _lib.GatStackGradDesc()
+    d = _lib.QuantStackGradDesc() if quants is not None else _lib.GatStackGradDesc()
+    qstructs = []                                                                              # (held until the call returns)
+    if adj_q is not None:
+        if quants is None:
+            raise ValueError("adj_q goes with quants: gat_stack_backward has no quantised adjacency")
+        if adj_q.val.dtype != torch.float32 or adj_q.nnz != adj.nnz or adj_q.n_rows != N:
+            raise ValueError("adj_q must be the float32 quantised values on adj's pattern")
+        d.values_adj_q = adj_q.val.data_ptr()
     d.dtype, d.n_layers, d.n_rows, d.n_graphs = dtype_code(dtype), n, N, graph_ptr.numel() - 1
     d.graph_ptr = graph_ptr.data_ptr()
     d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
@@ -1822,6 +1839,10 @@ def gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outp
             if want_edge_outputs:
                 ES = (torch.zeros(adj.nnz, dtype=torch.float32, device=dev), torch.zeros(adj.nnz, dtype=torch.float32, device=dev))
                 L.E, L.S = ES[0].data_ptr(), ES[1].data_ptr()
+        if quants is not None and quants[l] is not None:
+            qstructs.append(quants[l].as_struct(nnz_adj=adj.nnz, nnz_fea=x.nnz if (l == 0 and sparse) else 0,
+                                                adj_done=adj_q is not None))
+            L.quant = ctypes.pointer(qstructs[-1])
         gatts.append(ga)
         edges.append(ES)
         if want_G:
@@ -1840,11 +1861,11 @@ def gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outp
         if plan is None:
             check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create_ex")
     d.plan = plan.handle
-    nbytes = lib.sgx_gat_stack_backward_workspace_bytes(ctypes.byref(d))
+    nbytes = getattr(lib, name + "_workspace_bytes")(ctypes.byref(d))
     if nbytes:
         ws = _workspace(dev, nbytes)
         d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(lib.sgx_gat_stack_backward(ctypes.byref(d), _stream()), "sgx_gat_stack_backward")
+    check(getattr(lib, name)(ctypes.byref(d), _stream()), name)
     return (grads, gatts) + ((Gs,) if want_G else ()) + ((edges,) if want_edge_outputs else ())
 
 
@@ -1885,3 +1906,59 @@ class GatStack(torch.autograd.Function):
                                     plan=ctx.plan)
         dA = [None if g is None else g.reshape(a.shape) for g, a in zip(dA, atts)]
         return (None,) * 6 + tuple(dW) + tuple(dA)
+
+
+# ---- the backward of the quantised stack for training (sgx_quant_stack_backward) ---------------------------------------
+def quant_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, quants, alpha=0.2, plan=None,
+                         adj_q=None, want_G=False, want_edge_outputs=False):
+    """gat_stack_backward with a per-layer quantiser (include/sgx.h, "training the quantised stack"): the backward of the
+    stack quant_stack_forward ran, by FPYNQ_GAT.backward's rule under fake quantisation.  quants[l] is layer l's
+    quant.QuantConstants or None.  A quantised GAT layer's attention matrix is the quantised forward's S, formed again in
+    the kernel (X_l, W_l and the attention vector on their grids, H requantised, the mask on the quantised adjacency);
+    everything a gradient multiplies with -- X_l, W_l, Wh, a GCN layer's adjacency -- is unquantised, and deq_factor
+    reaches no gradient.  adj: the UNQUANTISED float32 adjacency; adj_q: adj.quantized(qc), taken as stored for the masks
+    (None: adj's values are quantised as they are read); layer_outputs: the quantised forward's D_l.  Returns what
+    gat_stack_backward returns.  Parity of the quantised layer is unpinned."""
+    return _gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha, plan, want_G,
+                               want_edge_outputs, quants=list(quants), adj_q=adj_q)
+
+
+class QuantStack(torch.autograd.Function):
+    """GatStack with a per-layer quantiser: forward = sgx_quant_stack_forward without a head (the pooled fp32 means, every
+    D_l saved), backward = sgx_quant_stack_backward.  No gradient for the features.
+
+        pooled = QuantStack.apply(adj, adj_q, x, graph_ptr, plan, relus, alpha, quants, W_0, ..., W_{L-1}, a_0, ..., a_{L-1})
+
+    adj: the unquantised float32 Csr; adj_q: adj.quantized(qc) (the forward aggregates and both passes mask with it as
+    stored) or None (adj is quantised as it is read); quants: one quant.QuantConstants (or None) per layer; the other
+    arguments are GatStack's."""
+
+    @staticmethod
+    def forward(ctx, adj, adj_q, x, graph_ptr, plan, relus, alpha, quants, *params):
+        if isinstance(x, torch.Tensor) and x.requires_grad:
+            raise ValueError("QuantStack gives no gradient for the features; x must not require grad")
+        n = len(relus)
+        if len(params) != 2 * n or len(quants) != n:
+            raise ValueError("QuantStack takes one weight, one attention vector (or None) and one quantiser (or None) per layer")
+        weights, atts = params[:n], params[n:]
+        dtype = adj.val.dtype
+        wts = [torch.transpose(w, 0, 1).detach().to(dtype).contiguous() for w in weights]
+        ats = [None if a is None else a.detach().to(dtype).reshape(-1).contiguous() for a in atts]
+        pooled, outs = quant_stack_forward(adj if adj_q is None else adj_q, x, wts, ats, relus, graph_ptr, list(quants),
+                                           alpha=alpha, plan=plan, adj_quantised=adj_q is not None, want_layer_outputs=True)
+        ctx.adj, ctx.adj_q, ctx.x, ctx.plan, ctx.relus, ctx.alpha = adj, adj_q, x, plan, list(relus), alpha
+        ctx.quants = list(quants)
+        ctx.gat = [a is not None for a in atts]
+        ctx.save_for_backward(graph_ptr, *outs, *weights, *[a for a in atts if a is not None])
+        return pooled
+
+    @staticmethod
+    def backward(ctx, grad_pooled):
+        saved = ctx.saved_tensors
+        n = len(ctx.relus)
+        graph_ptr, outs, weights, rest = saved[0], list(saved[1:1 + n]), list(saved[1 + n:1 + 2 * n]), list(saved[1 + 2 * n:])
+        atts = [rest.pop(0) if g else None for g in ctx.gat]
+        dW, dA = quant_stack_backward(ctx.adj, ctx.x, weights, atts, ctx.relus, graph_ptr, outs, grad_pooled, ctx.quants,
+                                      alpha=ctx.alpha, plan=ctx.plan, adj_q=ctx.adj_q)
+        dA = [None if g is None else g.reshape(a.shape) for g, a in zip(dA, atts)]
+        return (None,) * 8 + tuple(dW) + tuple(dA)

@@ -416,10 +416,14 @@ class GAT_POOL_PYNQ(Module):
 
     train_stack (opt-in, also settable as an attribute): with layer_count >= 2 a training step's two layers and the mean
     pool run as one forward and one backward call (ops.GatStack: sgx_gat_stack_forward, sgx_gat_stack_backward; GCN layers
-    in them when config.compute_attention == 0) where all of these hold: config.acc == 1, the quantiser off, x needing no
-    gradient, `batch` sorted with no edge between two of its graphs, no row of the adjacency without a positive entry,
-    one alpha for both layers, and every graph within the backward plan's row budget.  Dropout and the head stay in torch
-    behind the pooled output.  Every other case runs the layers one by one."""
+    in them when config.compute_attention == 0) where all of these hold: config.acc == 1, x needing no gradient, `batch`
+    sorted with no edge between two of its graphs, no row of the adjacency without a positive entry, one alpha for both
+    layers, and every graph within the backward plan's row budget.  With the quantiser on the two calls are ops.QuantStack
+    (sgx_quant_stack_forward, sgx_quant_stack_backward: the quantised forward's attention matrix, unquantised operands in
+    every gradient, as FPYNQ_GAT.backward) under the quantised eval route's conditions as well -- float32,
+    quant_constants set, the dead-row condition on the QUANTISED adjacency, not both config.hardware_quantize and a hidden
+    width over 128 -- with `layern` and the quantiser registers left as the two layer calls leave them; parity unpinned.
+    Dropout and the head stay in torch behind the pooled output.  Every other case runs the layers one by one."""
 
     def __init__(self, num_node_features, hidden_channels, num_classes, train_stack=False):
         super(GAT_POOL_PYNQ, self).__init__()
@@ -497,15 +501,22 @@ class GAT_POOL_PYNQ(Module):
                                      alpha=self.att1.alpha, plan=plan)
 
     def _train_stack(self, x, adj, batch):
-        """Both layers and the mean pool through ops.GatStack: the pooled means [G, hidden] fp32 with the gradients of the
-        weights and the attention vectors behind them.  None (the caller then runs the layers one by one) where one of the
-        class docstring's conditions fails."""
-        if _quantised() or x.requires_grad:
+        """Both layers and the mean pool through ops.GatStack (ops.QuantStack with the quantiser on): the pooled means
+        [G, hidden] fp32 with the gradients of the weights and the attention vectors behind them.  None (the caller then
+        runs the layers one by one) where one of the class docstring's conditions fails."""
+        if x.requires_grad:
             return None
         dt = _torch_dtype()
         ptr = ops.graph_ptr_of(batch)
         gat = int(config.compute_attention)
-        if ptr is None or (gat and (self.att1.alpha != self.att2.alpha or adj.has_dead_rows is not False)):
+        qc = None
+        if _quantised():
+            qc = quant_constants
+            # (_forward_stack's conditions: no constants, fp16: the layer's own errors; int8 operands: the layer's own form)
+            if qc is None or dt != torch.float32 or (config.hardware_quantize and self.att2.weight.shape[0] > 128):
+                return None
+        masked = adj if qc is None else adj.quantized(qc)                  # the adjacency a GAT layer masks with
+        if ptr is None or (gat and (self.att1.alpha != self.att2.alpha or masked.has_dead_rows is not False)):
             return None
         width = max(self.att1.weight.shape[1], self.att2.weight.shape[0], self.att2.weight.shape[1])
         if width > 256:
@@ -517,6 +528,12 @@ class GAT_POOL_PYNQ(Module):
             x.detach() if x.layout == torch.strided else x.detach().to_dense(), dt))
         layers = (self.att1, self.att2)
         atts = [c.attention if gat else None for c in layers]
+        if qc is not None:
+            # the constants and registers of the two layer calls (FPYNQ_GAT.forward): `layern` alternates the two sets
+            quants = (qc.second_layer() if layern == 2 else qc, qc if layern == 2 else qc.second_layer())
+            _program_quant_registers(my_ip.register_map, quants[1])
+            return ops.QuantStack.apply(adj, masked, fea, ptr, plan, (True, False), self.att1.alpha, quants,
+                                        *[c.weight for c in layers], *atts)
         return ops.GatStack.apply(adj, fea, ptr, plan, (True, False), self.att1.alpha, *[c.weight for c in layers], *atts)
 
 

@@ -15,6 +15,11 @@ hipGraph (null where the capture fails).  The two forms' losses are checked bit-
         GAT_POOL_PYNQ(train_stack=True) (sgx_gat_stack_forward + sgx_gat_stack_backward) against its layer-by-layer step,
         on the MUTAG batch only, eager and replayed.  The two forms' losses are not bit-equal there (the attention path's
         summation order is unpinned); the line records both.
+    python tools/stack_train_probe.py --gat --quant 8 >> profiles/r16_quant_stack_train.jsonl
+    python tools/stack_train_probe.py --quant 8 >> profiles/r16_quant_stack_train.jsonl
+        --quant BITS = the same model under config.fake_quantization at BITS bits (with --gat attention layers, without it
+        the library's GCN layers: config.compute_attention = 0): GAT_POOL_PYNQ(train_stack=True) (sgx_quant_stack_forward +
+        sgx_quant_stack_backward) against its layer-by-layer quantised step.  --only big runs the repeated batch instead.
 """
 import argparse
 import json
@@ -40,9 +45,13 @@ def model(form, dev):
 def gat_main(args, dev):
     """The --gat lines: one per form on the MUTAG batch."""
     from sgracex1_amd import config, sgrace
-    config.acc, config.compute_attention, config.float_type = 1, 1, np.float32
+    config.acc, config.compute_attention, config.float_type = 1, int(args.gat), np.float32
+    if args.quant:
+        config.fake_quantization, config.w_qbits = 1, args.quant
     ip = sgrace.init_SGRACE()
-    x, ei, batch, n_graphs = mutag_batch(1, dev)
+    big = args.only == "big"
+    x, ei, batch, n_graphs = mutag_batch(max(1, args.graphs // 188) if big else 1, dev)
+    reps = max(1, args.reps // 10) if big else args.reps
     y = torch.randint(0, 2, (n_graphs,), device=dev, generator=torch.Generator(device=dev).manual_seed(1))
     crit = torch.nn.CrossEntropyLoss()
     torch.manual_seed(12345)
@@ -64,10 +73,12 @@ def gat_main(args, dev):
         loss = float(step(m).detach())
         for _ in range(3):
             step(m)
-        rec = {"workload": "mutag", "model": "gat", "form": form, "graphs": n_graphs, "nodes": x.shape[0], "edges": ei.shape[1],
-               "dtype": "f32", "first_loss": loss}
-        rec["fwd_ms"] = time_ms(lambda: fwd(m), args.reps, args.trials)
-        rec["step_ms"] = time_ms(lambda: step(m), args.reps, args.trials)
+        rec = {"workload": "big" if big else "mutag", "model": "gat" if args.gat else "gcn", "form": form, "graphs": n_graphs,
+               "nodes": x.shape[0], "edges": ei.shape[1], "dtype": "f32", "first_loss": loss}
+        if args.quant:
+            rec["qbits"] = args.quant
+        rec["fwd_ms"] = time_ms(lambda: fwd(m), reps, args.trials)
+        rec["step_ms"] = time_ms(lambda: step(m), reps, args.trials)
         rec["bwd_ms"] = rec["step_ms"] - rec["fwd_ms"]
         rec["graph_step_ms"] = None
         try:
@@ -82,7 +93,7 @@ def gat_main(args, dev):
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 fwd(m).backward()
-            rec["graph_step_ms"] = time_ms(g.replay, args.reps, args.trials)
+            rec["graph_step_ms"] = time_ms(g.replay, reps, args.trials)
             del g
         except Exception as e:                          # (a path that synchronises cannot be captured)
             rec["graph_error"] = f"{type(e).__name__}: {str(e)[:120]}"
@@ -94,13 +105,14 @@ def gat_main(args, dev):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gat", action="store_true")
+    ap.add_argument("--quant", type=int, default=0, choices=[0, 8, 4, 2, 1], metavar="BITS")
     ap.add_argument("--only", choices=["mutag", "big"], default=None)
     ap.add_argument("--graphs", type=int, default=1_000_160)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--trials", type=int, default=5)
     args = ap.parse_args()
     dev = torch.device("cuda")
-    if args.gat:
+    if args.gat or args.quant:
         return gat_main(args, dev)
     for name, copies in (("mutag", 1), ("big", max(1, args.graphs // 188))):
         if args.only and name != args.only:
