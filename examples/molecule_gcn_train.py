@@ -28,6 +28,12 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
         --train-stack = each training step's two attention layers and the pooling run as one forward call
         (sgx_gat_stack_forward) and one backward call (sgx_gat_stack_backward) -- GAT_POOL_PYNQ(train_stack=True); with
         --qbits N the two calls are sgx_quant_stack_forward and sgx_quant_stack_backward
+    python examples/molecule_gcn_train.py --model gat --batch-size 64 --layer-count 2 --train-stack [--qbits 8] [--plain-loader]
+        --model gat with --batch-size N on the device loader = the shuffled batches arrive ready for the attention layers
+        (pyg_lite.GraphLoader(prepare="sym_norm2", quant=sgrace.quant_constants under --qbits): the normalised adjacency,
+        its quantised forms and their dead-row facts gathered by the collation launch from what was built once for the
+        set), so a step synchronises nowhere; --plain-loader keeps the batches without them (the model then normalises,
+        quantises and reads the dead-row flag back per batch), for comparison
 """
 import argparse
 import json
@@ -52,6 +58,7 @@ def main():
     ap.add_argument("--train-stack", action="store_true")
     ap.add_argument("--batch-size", type=int, default=0)
     ap.add_argument("--host-loader", action="store_true")
+    ap.add_argument("--plain-loader", action="store_true")
     ap.add_argument("--model", choices=["gcn", "gat"], default="gcn")
     ap.add_argument("--qbits", type=int, default=32, choices=[32, 8, 4, 2, 1])
     args = ap.parse_args()
@@ -82,6 +89,10 @@ def main():
         my_ip.register_map.layer_count = args.layer_count
         torch.manual_seed(12345)
         gat = sgrace.GAT_POOL_PYNQ(7, 64, 2, train_stack=args.train_stack).to(dev)   # demo_sgrace.py:137-190
+        if args.batch_size > 0 and not args.host_loader and not args.plain_loader:
+            # the batches layer-ready: normalised (and quantised) once per set, gathered per batch by the collation launch
+            loader = G.GraphLoader(loader.graphs, batch_size=args.batch_size, shuffle=True, generator=gen, device=dev,
+                                   dtypes=(sgrace._torch_dtype(),), prepare="sym_norm2", quant=sgrace.quant_constants)
         model = lambda _acc, x, edge_index, batch: gat(x, edge_index, batch)
         model.train, model.eval, model.parameters = gat.train, gat.eval, gat.parameters
     else:
@@ -120,7 +131,8 @@ def main():
               f"step {dt * 1e3:.2f} ms", flush=True)
     print(json.dumps({"best_test_acc": best, "final_test_acc": log[-1]["test_acc"], "epochs": args.epochs,
                       "acc": args.acc, "model": args.model, "qbits": args.qbits, "layer_count": args.layer_count, "train_stack": args.train_stack,
-                      "batch_size": args.batch_size, "host_loader": args.host_loader, "reference": "0.76 at epoch 34 (notebook cell 20 output)" if args.model == "gcn" else "none (parity unpinned)"}))
+                      "batch_size": args.batch_size, "host_loader": args.host_loader,
+                      "prepared_loader": bool(getattr(loader, "prepare", None)), "reference": "0.76 at epoch 34 (notebook cell 20 output)" if args.model == "gcn" else "none (parity unpinned)"}))
 
 
 if __name__ == "__main__":

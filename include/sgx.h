@@ -716,6 +716,62 @@ typedef struct sgx_graph_batch {
 
 int sgx_collate_graphs(const sgx_graph_set *set, const sgx_graph_batch *b, void *stream);
 
+/* ---- shuffled graph mini-batches with prepared adjacencies ("extras") --------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * Rule.  Let norm_csr(batch) be the adjacency the SGRACE graph classifier builds for a collated batch: sym_norm2 over
+ * the batch's edge_index (a self loop of weight fill = 0 for every node without one, unit weights in fp32, the edges
+ * sorted by (row, col) with repeated edges kept, value = deg^-1/2[row] * w * deg^-1/2[col] with deg = the row sums)
+ * and the row pointer of the sorted rows.  The prepared loader delivers, for every batch, rowPtr / columnIndex /
+ * values bit-equal to norm_csr(batch), without computing any of it per batch: it gathers graph idx[b]'s rows of
+ * norm_csr(the whole dataset in dataset order) with the columns shifted by node_off[b] - node_ptr[idx[b]].  The two
+ * agree because everything in the rule is local to a graph:
+ *   - the degree sums add integers (unit weights), so they are exact in fp32 in any order of summation;
+ *   - pow(-0.5) and the two multiplications are elementwise, on operands that depend on the graph alone;
+ *   - repeated edges stay repeated entries with equal values, in the dataset and in the batch;
+ *   - no edge leaves its graph, so the (row, col) sort orders a graph's entries among themselves the same way in the
+ *     dataset and in any batch, and a graph's entries are one contiguous range of either.
+ * What depends only on a graph's entries can be carried along the same way: the values quantised onto the unsigned
+ * adjacency grid (sgx_fake_quantize with signed = 0: csrc/quant_device.h is the one quantiser, run once per dataset
+ * and constants) and the dead-row mask (a row with no positive value), of the unquantised and of each quantised
+ * value array.
+ *
+ * sgx_collate_graphs_extras collates the batch exactly as sgx_collate_graphs does and, in the same launch, gathers
+ * n_extras (0 .. SGX_COLLATE_MAX_EXTRAS) such dataset-side matrices into the batch.  An extra is a CSR over the
+ * dataset's rows (rowPtr / columnIndex in dataset ids, fp32 values, optionally one byte per row) plus the exclusive
+ * offsets entry_off [n_graphs+1] of its entries inside the batch, which the host computes from its per-graph entry
+ * counts as it does adj_off.  Written per graph: the row pointer (shifted to the batch's entry offsets), the columns
+ * (shifted as the adjacency's), the values in each dtype asked for (rounded to nearest even for fp16) and the row
+ * bytes, copied.  Several extras may share one pattern (the quantised adjacencies share the normalised one's): an
+ * extra with rowPtr_out == NULL and columnIndex_out == NULL writes values and row bytes only, and its rowPtr is read
+ * only to find each graph's entry range.
+ *
+ * The collator's contracts hold: one wavefront per graph, one launch, no allocation, no synchronisation, capturable.
+ * A graph id outside the set, or a graph one of whose ranges -- of the batch or of any extra -- does not fit the
+ * totals, is skipped as a whole: none of its outputs is written, and nothing is written outside the caller's buffers.
+ * n_extras == 0 writes exactly what sgx_collate_graphs writes.
+ *
+ * Argument errors, returned before anything reaches the device: n_extras outside 0 .. SGX_COLLATE_MAX_EXTRAS:
+ * SGX_ERR_SHAPE; then those of sgx_collate_graphs; extras NULL with n_extras > 0, an extra's rowPtr, values or
+ * entry_off NULL, columnIndex NULL where the pattern is written, columnIndex_out without rowPtr_out or (with entries)
+ * rowPtr_out without columnIndex_out, exactly one of dead_row / dead_row_out NULL (with rows): SGX_ERR_NULL; an
+ * extra's nnz < 0: SGX_ERR_SHAPE. */
+#define SGX_COLLATE_MAX_EXTRAS 3
+
+typedef struct sgx_collate_extra {
+    const int32_t *rowPtr, *columnIndex;       /* dataset side: [rows+1], [entries], dataset ids */
+    const float *values;                       /* dataset side: [entries] fp32 */
+    const uint8_t *dead_row;                   /* dataset side: [rows], one byte per row; may be NULL */
+    int64_t nnz;                               /* entries of the batch = entry_off[n_graphs] */
+    const int32_t *entry_off;                  /* device [n_graphs+1], exclusive offsets of every graph's entries */
+    int32_t *rowPtr_out, *columnIndex_out;     /* out [n_rows+1], [nnz]; both NULL: the pattern is not written */
+    void *values_out[2];                       /* out [nnz] in SGX_F16 / SGX_F32, either may be NULL */
+    uint8_t *dead_row_out;                     /* out [n_rows]; NULL exactly when dead_row is */
+} sgx_collate_extra;
+
+int sgx_collate_graphs_extras(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
+                              int n_extras, void *stream);
+
 /* A batch plan from facts the caller already knows (the collator's batches): graph_ptr cuts a block-diagonal adjacency
  * and its largest graph has max_graph rows.  Neither is checked on the device, so nothing is read back:
  * sgx_batch_plan_create_known gives the plan sgx_batch_plan_create_ex gives on the same batch (rows, groups, max_graph,

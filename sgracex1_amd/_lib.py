@@ -41,7 +41,7 @@ SYMBOLS = [
     "sgx_batch_plan_create", "sgx_batch_plan_destroy", "sgx_batch_plan_rows", "sgx_batch_plan_groups",
     "sgx_batch_plan_max_graph", "sgx_batch_plan_fits", "sgx_stack_workspace_bytes", "sgx_stack_forward",
     "sgx_batch_plan_create_ex", "sgx_stack_backward_workspace_bytes", "sgx_stack_backward",
-    "sgx_collate_graphs", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
+    "sgx_collate_graphs", "sgx_collate_graphs_extras", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
     "sgx_gat_aggregate_stats", "sgx_layer_forward_stats", "sgx_gat_edge_outputs", "sgx_gat_backward_edges_stats",
     "sgx_node_batch_workspace_bytes", "sgx_node_batch_sample", "sgx_node_batch_sample_quant",
     "sgx_layer_backward_workspace_bytes", "sgx_layer_backward", "sgx_gat_attention_grad_workspace_bytes",
@@ -219,6 +219,19 @@ class GraphBatch(ctypes.Structure):
         ("graph_ptr", ctypes.c_void_p),
         ("rowPtr_adj", ctypes.c_void_p), ("columnIndex_adj", ctypes.c_void_p), ("values_adj", ctypes.c_void_p * 2),
         ("rowPtr_fea", ctypes.c_void_p), ("columnIndex_fea", ctypes.c_void_p), ("values_fea", ctypes.c_void_p * 2),
+    ]
+
+
+SGX_COLLATE_MAX_EXTRAS = 3
+
+
+class CollateExtra(ctypes.Structure):
+    """struct sgx_collate_extra -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("rowPtr", ctypes.c_void_p), ("columnIndex", ctypes.c_void_p), ("values", ctypes.c_void_p), ("dead_row", ctypes.c_void_p),
+        ("nnz", ctypes.c_int64), ("entry_off", ctypes.c_void_p),
+        ("rowPtr_out", ctypes.c_void_p), ("columnIndex_out", ctypes.c_void_p), ("values_out", ctypes.c_void_p * 2),
+        ("dead_row_out", ctypes.c_void_p),
     ]
 
 
@@ -433,6 +446,9 @@ def _load():
     lib.sgx_quant_stack_backward.restype = c_int
     lib.sgx_collate_graphs.argtypes = [ctypes.POINTER(GraphSet), ctypes.POINTER(GraphBatch), vp]
     lib.sgx_collate_graphs.restype = c_int
+    lib.sgx_collate_graphs_extras.argtypes = [ctypes.POINTER(GraphSet), ctypes.POINTER(GraphBatch), ctypes.POINTER(CollateExtra),
+                                              c_int, vp]
+    lib.sgx_collate_graphs_extras.restype = c_int
     lib.sgx_batch_plan_group_count.argtypes = [c_int, c_int, c_int, c_int, c_int]
     lib.sgx_batch_plan_group_count.restype = c_int
     lib.sgx_batch_plan_create_known.argtypes = [c_int, c_int, c_int, vp, c_int, c_int, c_int, vp, ctypes.POINTER(vp), vp]

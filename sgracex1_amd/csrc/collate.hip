@@ -1,4 +1,4 @@
-// Shuffled graph mini-batches collated on the device (sgx_collate_graphs, include/sgx.h).
+// Shuffled graph mini-batches collated on the device (sgx_collate_graphs, sgx_collate_graphs_extras, include/sgx.h).
 //
 // The dataset lives on the device in dataset order (sgx_graph_set); a batch is a list of graph ids plus the exclusive
 // offsets of every graph's rows, stored edges, adjacency entries and feature entries inside the batch, which the host
@@ -54,16 +54,12 @@ __device__ __forceinline__ void copy_csr(const int32_t *__restrict__ rowptr, con
     }
 }
 
-__global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_kernel(CollateArgs a)
+// everything sgx_collate_graphs writes for batch position `pos`, one wavefront; false (nothing written) for a graph id
+// outside the set or ranges that do not fit the totals
+__device__ __forceinline__ bool collate_one(const sgx_graph_set &s, const sgx_graph_batch &b, int pos, int lane)
 {
-    const int lane = threadIdx.x % kWave;
-    const int64_t bi = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
-    const sgx_graph_set &s = a.s;
-    const sgx_graph_batch &b = a.b;
-    if (bi >= b.n_graphs) return;
-    const int pos = (int)bi;
     const int g = b.index[pos];
-    if (g < 0 || g >= s.n_graphs) return;
+    if (g < 0 || g >= s.n_graphs) return false;
     const int r0 = s.node_ptr[g], n = s.node_ptr[g + 1] - r0;
     const int64_t se0 = s.edge_ptr[g], ne = (int64_t)s.edge_ptr[g + 1] - se0;
     const int32_t a0 = s.rowPtr_adj[r0], f0 = s.rowPtr_fea[r0];
@@ -73,7 +69,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_kernel(
     // offsets that do not match the set's counts: skip the graph rather than write past a buffer
     if (n < 0 || ne < 0 || na < 0 || nf < 0 || o < 0 || (int64_t)o + n > b.n_rows || eo < 0 || eo + ne > b.n_edges ||
         ao < 0 || ao + na > b.nnz_adj || fo < 0 || fo + nf > b.nnz_fea)
-        return;
+        return false;
     if (lane == 0) {
         b.graph_ptr[pos] = o;
         b.y[pos] = s.y[g];
@@ -94,6 +90,78 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_kernel(
              static_cast<f16 *>(b.values_adj[SGX_F16]), static_cast<float *>(b.values_adj[SGX_F32]), o, ao, o - r0, lane);
     copy_csr(s.rowPtr_fea, s.columnIndex_fea, s.values_fea, r0, n, f0, nf, b.rowPtr_fea, b.columnIndex_fea,
              static_cast<f16 *>(b.values_fea[SGX_F16]), static_cast<float *>(b.values_fea[SGX_F32]), o, fo, 0, lane);
+    return true;
+}
+
+__global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_kernel(CollateArgs a)
+{
+    const int lane = threadIdx.x % kWave;
+    const int64_t bi = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+    if (bi >= a.b.n_graphs) return;
+    collate_one(a.s, a.b, (int)bi, lane);
+}
+
+struct CollateExtraArgs {
+    sgx_graph_set s;
+    sgx_graph_batch b;
+    sgx_collate_extra x[SGX_COLLATE_MAX_EXTRAS];
+    int n_extras;
+};
+
+// sgx_collate_graphs_extras: the batch as above plus, per extra, the graph's entry range of a dataset-side CSR copied as
+// one contiguous, lane-strided run (a graph's rows are consecutive in the set, so its entries are too) -- columns shifted,
+// values cast per dtype -- the shifted row pointer and the row bytes.  Every range of every extra is checked before the
+// first store, so a graph is written as a whole or not at all.
+__global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_extras_kernel(CollateExtraArgs a)
+{
+    const int lane = threadIdx.x % kWave;
+    const int64_t bi = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+    const sgx_graph_set &s = a.s;
+    const sgx_graph_batch &b = a.b;
+    if (bi >= b.n_graphs) return;
+    const int pos = (int)bi;
+    const int g = b.index[pos];
+    if (g < 0 || g >= s.n_graphs) return;
+    const int r0 = s.node_ptr[g], n = s.node_ptr[g + 1] - r0;
+    const int o = b.node_off[pos];
+    if (n < 0 || o < 0 || (int64_t)o + n > b.n_rows) return;
+    int32_t e0[SGX_COLLATE_MAX_EXTRAS];
+    int64_t ne[SGX_COLLATE_MAX_EXTRAS], eo[SGX_COLLATE_MAX_EXTRAS];
+#pragma unroll
+    for (int k = 0; k < SGX_COLLATE_MAX_EXTRAS; ++k) {
+        if (k >= a.n_extras) break;
+        const sgx_collate_extra &x = a.x[k];
+        e0[k] = x.rowPtr[r0];
+        ne[k] = (int64_t)x.rowPtr[r0 + n] - e0[k];
+        eo[k] = x.entry_off[pos];
+        if (ne[k] < 0 || eo[k] < 0 || eo[k] + ne[k] > x.nnz) return;
+    }
+    if (!collate_one(s, b, pos, lane)) return;
+#pragma unroll
+    for (int k = 0; k < SGX_COLLATE_MAX_EXTRAS; ++k) {
+        if (k >= a.n_extras) break;
+        const sgx_collate_extra &x = a.x[k];
+        const int64_t off = eo[k];
+        if (x.rowPtr_out) {
+            for (int i = lane; i < n; i += kWave) x.rowPtr_out[o + i] = (int32_t)(off + (x.rowPtr[r0 + i] - e0[k]));
+            if (lane == 0 && pos == b.n_graphs - 1) x.rowPtr_out[b.n_rows] = (int32_t)x.nnz;
+            const int32_t *__restrict__ col = x.columnIndex + e0[k];
+            const int shift = o - r0;
+            for (int64_t i = lane; i < ne[k]; i += kWave) x.columnIndex_out[off + i] = col[i] + shift;
+        }
+        const float *__restrict__ val = x.values + e0[k];
+        f16 *__restrict__ v16 = static_cast<f16 *>(x.values_out[SGX_F16]);
+        float *__restrict__ v32 = static_cast<float *>(x.values_out[SGX_F32]);
+        if (v16 || v32) {
+            for (int64_t i = lane; i < ne[k]; i += kWave) {
+                const float v = val[i];
+                if (v16) v16[off + i] = (f16)v;
+                if (v32) v32[off + i] = v;
+            }
+        }
+        if (x.dead_row)
+            for (int i = lane; i < n; i += kWave) x.dead_row_out[o + i] = x.dead_row[r0 + i];
+    }
 }
 
 int check_collate(const sgx_graph_set *s, const sgx_graph_batch *b)
@@ -113,6 +181,20 @@ int check_collate(const sgx_graph_set *s, const sgx_graph_batch *b)
     return SGX_OK;
 }
 
+int check_extras(const sgx_graph_batch *b, const sgx_collate_extra *extras, int n_extras)
+{
+    if (n_extras > 0 && !extras) return SGX_ERR_NULL;
+    for (int k = 0; k < n_extras; ++k) {
+        const sgx_collate_extra &x = extras[k];
+        if (x.nnz < 0) return SGX_ERR_SHAPE;
+        if (!x.rowPtr || !x.values || !x.entry_off) return SGX_ERR_NULL;
+        if (!x.rowPtr_out && x.columnIndex_out) return SGX_ERR_NULL;
+        if (x.rowPtr_out && (!x.columnIndex || (x.nnz > 0 && !x.columnIndex_out))) return SGX_ERR_NULL;
+        if (b->n_rows > 0 && (x.dead_row == nullptr) != (x.dead_row_out == nullptr)) return SGX_ERR_NULL;
+    }
+    return SGX_OK;
+}
+
 }  // namespace
 
 extern "C" int sgx_collate_graphs(const sgx_graph_set *set, const sgx_graph_batch *b, void *stream)
@@ -124,6 +206,25 @@ extern "C" int sgx_collate_graphs(const sgx_graph_set *set, const sgx_graph_batc
     a.b = *b;
     const unsigned grid = (unsigned)((b->n_graphs + kWavesPerBlock - 1) / kWavesPerBlock);
     hipLaunchKernelGGL(collate_graphs_kernel, dim3(grid), dim3(kWave * kWavesPerBlock), 0, (hipStream_t)stream, a);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}
+
+extern "C" int sgx_collate_graphs_extras(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
+                                         int n_extras, void *stream)
+{
+    if (n_extras < 0 || n_extras > SGX_COLLATE_MAX_EXTRAS) return SGX_ERR_SHAPE;
+    int rc = check_collate(set, b);
+    if (rc != SGX_OK) return rc;
+    rc = check_extras(b, extras, n_extras);
+    if (rc != SGX_OK) return rc;
+    CollateExtraArgs a = {};
+    a.s = *set;
+    a.b = *b;
+    for (int k = 0; k < n_extras; ++k) a.x[k] = extras[k];
+    a.n_extras = n_extras;
+    const unsigned grid = (unsigned)((b->n_graphs + kWavesPerBlock - 1) / kWavesPerBlock);
+    hipLaunchKernelGGL(collate_graphs_extras_kernel, dim3(grid), dim3(kWave * kWavesPerBlock), 0, (hipStream_t)stream, a);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }

@@ -1405,9 +1405,57 @@ class GraphSet:
         d.rowPtr_adj, d.columnIndex_adj, d.values_adj = self.adj.rowptr.data_ptr(), self.adj.col.data_ptr(), self.adj.val.data_ptr()
         d.rowPtr_fea, d.columnIndex_fea, d.values_fea = self.fea.rowptr.data_ptr(), self.fea.col.data_ptr(), self.fea.val.data_ptr()
         self.desc = d
+        self._node_ptr_host = node_ptr
+        self._sym_norm2 = None                 # the dataset-side normalised adjacency (prepare_sym_norm2), built on demand
 
     def __len__(self):
         return len(self.counts[0])
+
+    def _dead_facts(self, M):
+        """(dead-row mask bool [n_rows] on the device, host bool [n_graphs]: the graph has a dead row) of a dataset-side
+        matrix.  One read-back."""
+        dead = M.dead_rows
+        run = torch.zeros(self.n_rows + 1, dtype=torch.int64, device=self.device)
+        run[1:] = torch.cumsum(dead, 0)
+        ptr = self.node_ptr.long()
+        return dead.contiguous(), (run[ptr[1:]] > run[ptr[:-1]]).cpu().numpy()
+
+    def prepare_sym_norm2(self, dtypes=(torch.float16,), quant=None):
+        """What a batch of GAT_POOL_PYNQ needs besides the collated tensors, built ONCE for the whole set so that a batch
+        only gathers it (include/sgx.h, "shuffled graph mini-batches with prepared adjacencies"): the adjacency sym_norm2
+        (fill 0, unit fp32 weights) gives over the set in dataset order, as the Csr _edge_csr builds from it, its dead-row
+        mask, per graph whether it has a dead row (host), per graph its entry count (host) and the set's longest row; with
+        quant (a quant.QuantConstants; float32 must be among dtypes) also, for quant and quant.second_layer(), the values on
+        the unsigned w_qbits grid (Csr.quantized, filed under the same key) with their mask and per-graph flags.  Cached on
+        the set; every new matrix costs the torch plumbing once and one read-back.  -> GraphExtras, what
+        collate_graphs(extras=) takes; dtypes: the element types the normalised values are delivered in."""
+        from .sgrace import _edge_csr, sym_norm2        # (imported here: sgrace imports this module)
+        dtypes = tuple(dtypes)
+        for dt in dtypes:
+            dtype_code(dt)
+        if quant is not None and torch.float32 not in dtypes:
+            raise ValueError("quant needs torch.float32 among dtypes: the quantised layer works on float32 buffers")
+        p = self._sym_norm2
+        if p is None:
+            owner = torch.repeat_interleave(torch.arange(len(self), device=self.device),
+                                            (self.edge_ptr[1:] - self.edge_ptr[:-1]).long(), output_size=self.n_edges)
+            glob = self.edge_index.long() + self.node_ptr[owner].long().unsqueeze(0)
+            ei, norm = sym_norm2(glob, self.n_rows)
+            A = _edge_csr(None, ei, norm, self.n_rows, torch.float32)
+            rp = A.rowptr.cpu().numpy().astype(np.int64)
+            if rp[-1] >= 2**31:
+                raise ValueError("GraphSet holds fewer than 2^31 normalised entries")
+            p = self._sym_norm2 = _PreparedAdjacency(A, np.diff(rp[self._node_ptr_host]), int(np.diff(rp).max()))
+            p.dead, p.has_dead = self._dead_facts(A)
+        keys = []
+        for qc in (() if quant is None else (quant, quant.second_layer())):
+            key = _adj_quant_key(qc)
+            if key not in p.quant:
+                Q = p.adj.quantized(qc)
+                p.quant[key] = (Q.val,) + self._dead_facts(Q)
+            if key not in keys:                  # (the demo's two layers share the adjacency's constants)
+                keys.append(key)
+        return GraphExtras(p, dtypes, tuple(keys))
 
     def prepare(self, idx):
         """The batch of graph ids `idx` (a host sequence, in batch order) ready to collate: its exclusive offsets
@@ -1422,18 +1470,19 @@ class GraphSet:
             raise ValueError("a batch holds at least one graph")
         if idx.min() < 0 or idx.max() >= len(self):
             raise ValueError(f"graph ids must lie in [0, {len(self)})")
-        host, totals = batch_offsets(self.counts, idx)
+        counts = self.counts if self._sym_norm2 is None else self.counts + (self._sym_norm2.counts,)
+        host, totals = batch_offsets(counts, idx)
         dev = torch.from_numpy(host).pin_memory().to(self.device, non_blocking=True)
-        return BatchIndex(dev, B, totals, int(self.counts[0][idx].max()))
+        return BatchIndex(dev, B, totals, int(self.counts[0][idx].max()), ids=idx)
 
 
 def batch_offsets(counts, idx):
     """What GraphSet.prepare sends to the device for the graph ids idx [B]: one int32 array of idx followed by the
     exclusive offsets [B+1] of rows, stored edges, adjacency entries and feature entries (counts: those four per-graph
-    count arrays), and the four totals.  Host only."""
+    count arrays; a fifth, of a prepared set: the normalised adjacency's entries), and the totals.  Host only."""
     idx = np.asarray(idx, dtype=np.int64)
     B = idx.size
-    host = np.empty(B + 4 * (B + 1), dtype=np.int32)
+    host = np.empty(B + len(counts) * (B + 1), dtype=np.int32)
     host[:B] = idx
     totals = []
     for k, c in enumerate(counts):
@@ -1448,23 +1497,50 @@ def batch_offsets(counts, idx):
 
 class BatchIndex:
     """A prepared batch (GraphSet.prepare): graph ids and offsets on the device, totals and the largest graph on the
-    host.  Reusable: collating the same BatchIndex again (a captured step) reads the same device buffer."""
+    host.  Reusable: collating the same BatchIndex again (a captured step) reads the same device buffer.  From a set
+    with a prepared adjacency (GraphSet.prepare_sym_norm2) it also holds that adjacency's offsets (norm_off, nnz_norm;
+    None otherwise); ids: the graph ids on the host, where the prepared batches look their per-graph facts up."""
 
-    def __init__(self, dev, n_graphs, totals, max_graph):
+    def __init__(self, dev, n_graphs, totals, max_graph, ids=None):
         self.dev, self.n_graphs, self.max_graph = dev, int(n_graphs), int(max_graph)
-        self.n_rows, self.n_edges, self.nnz_adj, self.nnz_fea = totals
+        self.n_rows, self.n_edges, self.nnz_adj, self.nnz_fea = totals[:4]
+        self.ids = ids
         B = self.n_graphs
         self.index, self.node_off, self.edge_off, self.adj_off, self.fea_off = (
-            dev[:B], dev[B:2 * B + 1], dev[2 * B + 1:3 * B + 2], dev[3 * B + 2:4 * B + 3], dev[4 * B + 3:])
+            dev[:B], dev[B:2 * B + 1], dev[2 * B + 1:3 * B + 2], dev[3 * B + 2:4 * B + 3], dev[4 * B + 3:5 * B + 4])
+        self.norm_off, self.nnz_norm = (dev[5 * B + 4:6 * B + 5], totals[4]) if len(totals) > 4 else (None, None)
+
+
+class _PreparedAdjacency:
+    """The dataset-side state of GraphSet.prepare_sym_norm2: adj (the normalised Csr of the whole set, fp32), counts (host,
+    entries per graph), max_row, dead / has_dead (device mask, host per-graph flags) and quant {key: (values, dead,
+    has_dead)}."""
+
+    def __init__(self, adj, counts, max_row):
+        self.adj, self.counts, self.max_row = adj, counts, max_row
+        self.dead = self.has_dead = None
+        self.quant = {}
+
+
+class GraphExtras:
+    """What collate_graphs(extras=) gathers besides the batch (GraphSet.prepare_sym_norm2): the prepared adjacency, the
+    dtypes its values are delivered in and the keys (_adj_quant_key) of the quantised value arrays delivered with it."""
+
+    def __init__(self, prepared, dtypes, keys):
+        if 1 + len(keys) > _lib.SGX_COLLATE_MAX_EXTRAS:
+            raise ValueError(f"a batch gathers up to {_lib.SGX_COLLATE_MAX_EXTRAS} extras")
+        self.prepared, self.dtypes, self.keys = prepared, tuple(dtypes), tuple(keys)
 
 
 class Collated:
     """One collated batch (collate_graphs): x [n, F] fp32, edge_index [2, E] int64, batch [n] int64, y [B] int64,
-    graph_ptr [B+1] int32, the adjacency (adj_rowptr, adj_col, adj_val {dtype: values}) and the feature CSR (fea_*)."""
+    graph_ptr [B+1] int32, the adjacency (adj_rowptr, adj_col, adj_val {dtype: values}) and the feature CSR (fea_*).
+    With extras (a GraphExtras) also the normalised adjacency -- norm_rowptr, norm_col, norm_val {dtype: values}, norm_dead
+    (bool [n]) -- and per quantiser key q_val {key: fp32 values over the same pattern} and q_dead {key: bool [n]}."""
 
     FIELDS = ("x", "edge_index", "batch", "y", "graph_ptr", "adj_rowptr", "adj_col", "fea_rowptr", "fea_col")
 
-    def __init__(self, index, n_feat, dtypes, device):
+    def __init__(self, index, n_feat, dtypes, device, extras=None):
         e = lambda *shape, dt=torch.int32: torch.empty(shape, dtype=dt, device=device)
         i = index
         self.index, self.n_feat = i, n_feat
@@ -1474,29 +1550,27 @@ class Collated:
         self.fea_rowptr, self.fea_col = e(i.n_rows + 1), e(i.nnz_fea)
         self.adj_val = {dt: e(i.nnz_adj, dt=dt) for dt in dtypes}
         self.fea_val = {dt: e(i.nnz_fea, dt=dt) for dt in dtypes}
+        self.extras = extras
+        self.norm_rowptr = self.norm_col = self.norm_dead = None
+        self.norm_val, self.q_val, self.q_dead = {}, {}, {}
+        if extras is not None:
+            self.norm_rowptr, self.norm_col = e(i.n_rows + 1), e(i.nnz_norm)
+            self.norm_dead = e(i.n_rows, dt=torch.bool)
+            self.norm_val = {dt: e(i.nnz_norm, dt=dt) for dt in extras.dtypes}
+            self.q_val = {key: e(i.nnz_norm, dt=torch.float32) for key in extras.keys}
+            self.q_dead = {key: e(i.n_rows, dt=torch.bool) for key in extras.keys}
 
-    def fits(self, index, n_feat, dtypes):
+    def fits(self, index, n_feat, dtypes, extras=None):
         i, j = self.index, index
+        if extras is not None and (self.norm_rowptr is None or i.nnz_norm != j.nnz_norm or
+                                   not set(self.norm_val) >= set(extras.dtypes) or not set(self.q_val) >= set(extras.keys)):
+            return False
         return ((i.n_graphs, i.n_rows, i.n_edges, i.nnz_adj, i.nnz_fea) == (j.n_graphs, j.n_rows, j.n_edges, j.nnz_adj, j.nnz_fea)
                 and self.n_feat == n_feat and set(self.adj_val) >= set(dtypes) and set(self.fea_val) >= set(dtypes))
 
 
-def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None):
-    """The batch of the graphs `idx` of `graphset` in that order, built on the device by one launch of
-    sgx_collate_graphs: the same x / edge_index / batch / y as pyg_lite.collate, the same adjacency as
-    csr_from_edge_index, the same feature CSR as Csr.from_dense, graph_ptr as graph_ptr_of -- with the CSR values in each
-    of `dtypes`.  idx: host graph ids, or a BatchIndex from graphset.prepare.  out: a Collated of the same sizes to write
-    into (a captured batch); a new one otherwise.  No synchronisation."""
-    index = idx if isinstance(idx, BatchIndex) else graphset.prepare(idx)
-    dtypes = tuple(dtypes)
-    for dt in dtypes:
-        dtype_code(dt)
-    if out is None:
-        out = Collated(index, graphset.n_feat, dtypes, graphset.device)
-    elif not out.fits(index, graphset.n_feat, dtypes):
-        raise ValueError("collate_graphs: `out` was made for a batch of other sizes or dtypes")
-    else:
-        out.index = index
+def _graph_batch(index, out, dtypes):
+    """struct sgx_graph_batch of the prepared batch `index` over the buffers of the Collated `out`."""
     b = _lib.GraphBatch()
     b.n_graphs, b.n_rows = index.n_graphs, index.n_rows
     b.n_edges, b.nnz_adj, b.nnz_fea = index.n_edges, index.nnz_adj, index.nnz_fea
@@ -1509,7 +1583,56 @@ def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None):
     for dt in dtypes:
         b.values_adj[dtype_code(dt)] = out.adj_val[dt].data_ptr()
         b.values_fea[dtype_code(dt)] = out.fea_val[dt].data_ptr()
-    check(lib.sgx_collate_graphs(ctypes.byref(graphset.desc), ctypes.byref(b), _stream()), "sgx_collate_graphs")
+    return b
+
+
+def _collate_extras(index, out, extras):
+    """The sgx_collate_extra array of `extras` over the buffers of `out`: the normalised adjacency (pattern, values per
+    dtype, dead rows), then one entry per quantiser key over the same pattern (fp32 values and dead rows only)."""
+    p = extras.prepared
+    xs = (_lib.CollateExtra * _lib.SGX_COLLATE_MAX_EXTRAS)()
+    for k, key in enumerate((None,) + extras.keys):
+        x = xs[k]
+        val, dead = (p.adj.val, p.dead) if key is None else p.quant[key][:2]
+        x.rowPtr, x.columnIndex, x.values, x.dead_row = p.adj.rowptr.data_ptr(), p.adj.col.data_ptr(), val.data_ptr(), dead.data_ptr()
+        x.nnz, x.entry_off = index.nnz_norm, index.norm_off.data_ptr()
+        if key is None:
+            x.rowPtr_out, x.columnIndex_out = out.norm_rowptr.data_ptr(), out.norm_col.data_ptr()
+            for dt in extras.dtypes:
+                x.values_out[dtype_code(dt)] = out.norm_val[dt].data_ptr()
+            x.dead_row_out = out.norm_dead.data_ptr()
+        else:
+            x.values_out[SGX_F32], x.dead_row_out = out.q_val[key].data_ptr(), out.q_dead[key].data_ptr()
+    return xs, 1 + len(extras.keys)
+
+
+def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None, extras=None):
+    """The batch of the graphs `idx` of `graphset` in that order, built on the device by one launch of
+    sgx_collate_graphs: the same x / edge_index / batch / y as pyg_lite.collate, the same adjacency as
+    csr_from_edge_index, the same feature CSR as Csr.from_dense, graph_ptr as graph_ptr_of -- with the CSR values in each
+    of `dtypes`.  idx: host graph ids, or a BatchIndex from graphset.prepare.  out: a Collated of the same sizes to write
+    into (a captured batch); a new one otherwise.  No synchronisation.
+    extras (a GraphExtras from graphset.prepare_sym_norm2): the same launch (sgx_collate_graphs_extras) also gathers the
+    batch's normalised adjacency, its dead-row mask and the quantised values with theirs into out.norm_* / out.q_*."""
+    index = idx if isinstance(idx, BatchIndex) else graphset.prepare(idx)
+    dtypes = tuple(dtypes)
+    for dt in dtypes:
+        dtype_code(dt)
+    if extras is not None and (index.norm_off is None or extras.prepared is not graphset._sym_norm2):
+        raise ValueError("collate_graphs: extras need a batch prepared after graphset.prepare_sym_norm2, and extras of this set")
+    if out is None:
+        out = Collated(index, graphset.n_feat, dtypes, graphset.device, extras)
+    elif not out.fits(index, graphset.n_feat, dtypes, extras):
+        raise ValueError("collate_graphs: `out` was made for a batch of other sizes or dtypes")
+    else:
+        out.index = index
+    b = _graph_batch(index, out, dtypes)
+    if extras is None:
+        check(lib.sgx_collate_graphs(ctypes.byref(graphset.desc), ctypes.byref(b), _stream()), "sgx_collate_graphs")
+    else:
+        xs, n = _collate_extras(index, out, extras)
+        check(lib.sgx_collate_graphs_extras(ctypes.byref(graphset.desc), ctypes.byref(b), xs, n, _stream()),
+              "sgx_collate_graphs_extras")
     return out
 
 

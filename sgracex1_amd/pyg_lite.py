@@ -98,15 +98,35 @@ class GraphLoader:
     GCN_PYNQ runs it without a device synchronisation: graph_ptr on `batch` (ops.graph_ptr_of), the adjacency on
     `edge_index` ("adj_csr", n, dtype) and the feature CSR on `x` ("fea_csr", dtype) for each of `dtypes`, and on
     graph_ptr the block facts (its largest graph) from which ops.BatchPlan.cached builds trusted plans.
-    dataset: a list of Graph, or an ops.GraphSet."""
+    dataset: a list of Graph, or an ops.GraphSet.
 
-    def __init__(self, dataset, batch_size=1, shuffle=False, generator=None, device=None, dtypes=(torch.float16,)):
+    prepare="sym_norm2": every batch also arrives ready for sgrace.GAT_POOL_PYNQ, whose forward then computes nothing
+    before its first kernel and reads nothing back.  The normalised adjacency of the whole set is built once
+    (ops.GraphSet.prepare_sym_norm2; rule in include/sgx.h) and the same collation launch gathers each batch's rows of it:
+    edge_index carries what the model looks up -- ("sym_norm2", n, 1, dtype) -> (edge_index, values, normalised Csr) for
+    each of `dtypes`, the Csr with its dead-row mask, flag and longest row recorded -- and graph_ptr's block facts name
+    that Csr's column array, so that the batch plans of the fused stack are the trusted ones.  The kernels read the Csr;
+    the list of the attached triple is edge_index itself (the stored edges without the added loops).
+    quant=qc (a quant.QuantConstants such as sgrace.quant_constants; with prepare, and float32 among dtypes): the float32
+    Csr also holds .quantized(qc) and .quantized(qc.second_layer()) with their dead-row facts, gathered from values
+    quantised once per set.  prepare=None: the batches as before."""
+
+    def __init__(self, dataset, batch_size=1, shuffle=False, generator=None, device=None, dtypes=(torch.float16,),
+                 prepare=None, quant=None):
         from . import ops
+        if quant is not None and not prepare:
+            raise ValueError("quant needs prepare='sym_norm2'")
+        if prepare not in (None, "sym_norm2"):
+            raise ValueError(f"prepare must be None or 'sym_norm2', not {prepare!r}")
+        if quant is not None and torch.float32 not in tuple(dtypes):
+            raise ValueError("quant needs dtype=torch.float32: the quantised layer works on float32 buffers")
         self.graphs = dataset if isinstance(dataset, ops.GraphSet) else ops.GraphSet(dataset, device or "cuda")
         self.batch_size, self.shuffle, self.generator = int(batch_size), bool(shuffle), generator
         self.dtypes = tuple(dtypes)
         if self.batch_size < 1:
             raise ValueError("batch_size must be >= 1")
+        self.prepare, self.quant = prepare, quant
+        self.extras = self.graphs.prepare_sym_norm2(self.dtypes, quant) if prepare else None
 
     def __len__(self):
         return (len(self.graphs) + self.batch_size - 1) // self.batch_size
@@ -120,16 +140,27 @@ class GraphLoader:
     def collate(self, idx, out=None):
         """The Batch of graph ids `idx` (host, in batch order), caches attached; out: an ops.Collated to reuse."""
         from . import ops
-        c = ops.collate_graphs(self.graphs, idx, self.dtypes, out=out)
+        c = ops.collate_graphs(self.graphs, idx, self.dtypes, out=out, extras=self.extras)
         return attach_batch(c)
 
 
 def attach_batch(c):
-    """A pyg_lite.Batch over the tensors of an ops.Collated, with its graph_ptr, CSRs and block facts attached."""
+    """A pyg_lite.Batch over the tensors of an ops.Collated, with its graph_ptr, CSRs and block facts attached -- and,
+    where it was collated with extras, the normalised adjacency with its facts and quantised forms."""
     from . import ops
     n, B = c.x.shape[0], c.index.n_graphs
     ops.attach(c.batch, ("graph_ptr",), c.graph_ptr)
     cols = []
+    if c.extras is not None:
+        p, ids = c.extras.prepared, c.index.ids
+        for dt in c.extras.dtypes:
+            N = ops.Csr(c.norm_rowptr, c.norm_col, c.norm_val[dt], n).with_facts(c.norm_dead, p.has_dead[ids].any(), p.max_row)
+            if dt == torch.float32:
+                for key in c.extras.keys:
+                    N._quantized[key] = ops.Csr(N.rowptr, N.col, c.q_val[key], n).with_facts(
+                        c.q_dead[key], p.quant[key][2][ids].any(), p.max_row)
+            ops.attach(c.edge_index, ("sym_norm2", n, 1, dt), (c.edge_index, N.val, N))
+        cols.append(weakref.ref(c.norm_col))
     for dt, val in c.adj_val.items():
         A = ops.Csr(c.adj_rowptr, c.adj_col, val, n)
         cols.append(weakref.ref(A.col))            # (weak: the adjacency's cache already holds graph_ptr)

@@ -11,6 +11,12 @@ GCN_PYNQ(train_stack=True), layer_count 2, fp16 layers:
           steps; per loader.  cached: the same batch every step (the loop of examples/molecule_gcn_train.py), for reference.
   collate sgx_collate_graphs alone on a prepared batch (hipEvents around --reps launches), and with GraphSet.prepare
           (host offsets and the pinned upload) included: graphs/s, and GB/s over the bytes the kernel must move.
+  --model gat [--quant 8]: the shuffled GAT_POOL_PYNQ(train_stack=True) step (fp32 layers, layer_count 2; quantised at N
+          bits under --quant) on MUTAG at batch 64 and on the million-graph replica at batch 4096, through the plain
+          GraphLoader (the model normalises, quantises and reads the dead-row flag back per batch) and the prepared one
+          (GraphLoader(prepare="sym_norm2", quant=): everything gathered by the collation launch); and the collation alone
+          without and with the extras.  --leg plain runs the plain leg alone (it uses nothing a tree without the prepared
+          loader lacks).
 One JSON line each.  --stats CSV turns a `rocprofv3 --kernel-trace --stats` kernel_stats file of a `--only collate` run
 into one line for the collate kernel.
 
@@ -83,6 +89,73 @@ def step_times(graphs, batch_size, dev, max_steps, which):
     return out
 
 
+def gat_model(dev, qbits):
+    from sgracex1_amd import config, sgrace
+    config.acc, config.compute_attention, config.float_type = 1, 1, np.float32
+    config.fake_quantization, config.w_qbits = int(qbits is not None), qbits or 8
+    sgrace.init_SGRACE().register_map.layer_count = 2
+    return sgrace.GAT_POOL_PYNQ(7, 64, 2, train_stack=True).to(dev).train(), sgrace.quant_constants
+
+
+def gat_step_times(gs, batch_size, dev, max_steps, qbits, legs):
+    """{leg: per-step ms} of the shuffled train_stack step of the attention model; the plain leg first, on the set as
+    uploaded (prepare_sym_norm2 adds to it)."""
+    out = {}
+    crit = torch.nn.CrossEntropyLoss()
+    for name in legs:
+        torch.manual_seed(5)
+        m, qc = gat_model(dev, qbits)
+        opt = torch.optim.Adam(m.parameters(), lr=0.01)
+        gen = torch.Generator().manual_seed(12345)
+        kw = dict(prepare="sym_norm2", quant=qc) if name == "prepared" else {}
+        loader = G.GraphLoader(gs, batch_size=batch_size, shuffle=True, generator=gen, device=dev, dtypes=(torch.float32,), **kw)
+
+        def batches():
+            while True:
+                for b in loader:
+                    yield b
+
+        it = batches()
+
+        def run(n):
+            for _ in range(n):
+                b = next(it)
+                opt.zero_grad()
+                crit(m(b.x, b.edge_index, b.batch), b.y).backward()
+                opt.step()
+
+        run(min(3, max_steps))
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(max_steps)
+        torch.cuda.synchronize()
+        out[name] = (time.perf_counter() - t0) * 1e3 / max_steps
+        del m, opt, loader
+    return out
+
+
+def gat_lines(gs, name, batch_size, dev, args):
+    legs = ("plain", "prepared") if args.leg == "both" else (args.leg,)
+    if "plain" not in legs or not hasattr(gs, "prepare_sym_norm2"):
+        plain_collate = None
+    else:
+        plain_collate = collate_times(gs, batch_size, args.reps, args.trials, dtypes=(torch.float32,))["collate_ms"]
+    t = gat_step_times(gs, batch_size, dev, args.steps, args.quant, legs)
+    line = {"workload": f"{name}_gat_train_stack", "graphs": len(gs), "batch_size": batch_size, "quant": args.quant,
+            "steps": args.steps, **{f"step_ms_{k}_loader": v for k, v in t.items()}}
+    if len(t) == 2:
+        line["plain_over_prepared"] = t["plain"] / t["prepared"]
+    print(json.dumps(line), flush=True)
+    if "prepared" in legs:
+        from sgracex1_amd import sgrace
+        extras = gs.prepare_sym_norm2((torch.float32,), sgrace.quant_constants)
+        c = collate_times(gs, batch_size, args.reps, args.trials, dtypes=(torch.float32,), extras=extras)
+        print(json.dumps({"workload": f"collate_{name}_gat", "quant": args.quant, "graphs": c["graphs"], "rows": c["rows"],
+                          "norm_entries": c["norm_entries"], "extras": 1 + len(extras.keys),
+                          "collate_ms_plain": plain_collate, "collate_ms_extras": c["collate_ms"],
+                          "prepare_and_collate_wall_ms_extras": c["prepare_and_collate_wall_ms"]}), flush=True)
+
+
 def collate_bytes(gs, index):
     """Bytes sgx_collate_graphs must read and write for a batch (fp16 CSR values out)."""
     n, E, na, nf, B, F = index.n_rows, index.n_edges, index.nnz_adj, index.nnz_fea, index.n_graphs, gs.n_feat
@@ -91,10 +164,11 @@ def collate_bytes(gs, index):
     return read + write
 
 
-def collate_times(gs, batch_size, reps, trials, seed=3):
+def collate_times(gs, batch_size, reps, trials, seed=3, dtypes=(torch.float16,), extras=None):
     perm = torch.randperm(len(gs), generator=torch.Generator().manual_seed(seed)).numpy()[:batch_size]
     index = gs.prepare(perm)
-    out = ops.collate_graphs(gs, index)
+    kw = {} if extras is None else {"extras": extras}
+    out = ops.collate_graphs(gs, index, dtypes, **kw)
 
     def timed(fn):
         res = []
@@ -110,10 +184,10 @@ def collate_times(gs, batch_size, reps, trials, seed=3):
             res.append((a.elapsed_time(b) / reps, (time.perf_counter() - t0) * 1e3 / reps))
         return [float(np.median([r[k] for r in res])) for k in range(2)]
 
-    kernel_ms, _ = timed(lambda: ops.collate_graphs(gs, index, out=out))
-    _, prepared_ms = timed(lambda: ops.collate_graphs(gs, perm, out=out))
-    nbytes = collate_bytes(gs, index)
-    return {"graphs": int(index.n_graphs), "rows": index.n_rows, "edges": index.n_edges, "adj_entries": index.nnz_adj,
+    kernel_ms, _ = timed(lambda: ops.collate_graphs(gs, index, dtypes, out=out, **kw))
+    _, prepared_ms = timed(lambda: ops.collate_graphs(gs, perm, dtypes, out=out, **kw))
+    nbytes = collate_bytes(gs, index)                       # (the batch's own bytes, fp16 values: the extras are not counted)
+    return {"graphs": int(index.n_graphs), "norm_entries": getattr(index, "nnz_norm", None), "rows": index.n_rows, "edges": index.n_edges, "adj_entries": index.nnz_adj,
             "fea_entries": index.nnz_fea, "bytes": nbytes, "collate_ms": kernel_ms,
             "collate_graphs_per_s": index.n_graphs / (kernel_ms * 1e-3), "collate_GBps": nbytes / (kernel_ms * 1e-3) / 1e9,
             "prepare_and_collate_wall_ms": prepared_ms,
@@ -139,7 +213,12 @@ def main():
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--trials", type=int, default=5)
     ap.add_argument("--stats", default=None)
+    ap.add_argument("--model", choices=["gcn", "gat"], default="gcn")
+    ap.add_argument("--quant", type=int, default=None, choices=[8, 4, 2, 1])
+    ap.add_argument("--leg", choices=["both", "plain", "prepared"], default="both")
     args = ap.parse_args()
+    if args.quant is not None and args.model != "gat":
+        ap.error("--quant times the quantised attention layers: --model gat")
     if args.stats is not None:
         if not os.path.isfile(args.stats):
             raise SystemExit(f"--stats: no such file {args.stats!r}")
@@ -147,6 +226,12 @@ def main():
         return
     dev = torch.device("cuda")
     graphs = mutag_graphs()
+    if args.model == "gat":
+        if args.only in (None, "step"):
+            gat_lines(ops.GraphSet(graphs, dev), "mutag", 64, dev, args)
+        if args.only in (None, "big"):
+            gat_lines(ops.GraphSet(graphs * args.copies, dev), "mutag_replica", 4096, dev, args)
+        return
     if args.only in (None, "step"):
         for bs in (256, 64):
             t = step_times(graphs, bs, dev, args.steps, ("cached", "host", "device"))
