@@ -34,6 +34,11 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
         its quantised forms and their dead-row facts gathered by the collation launch from what was built once for the
         set), so a step synchronises nowhere; --plain-loader keeps the batches without them (the model then normalises,
         quantises and reads the dead-row flag back per batch), for comparison
+    python examples/molecule_gcn_train.py --layer-count 2 --train-stack --trainer [--replay] [--model gat [--qbits 8]]
+        --trainer = the tail of every step on the kernels too (train.StackTrainer): dropout, the head, the loss and their
+        gradients as one call (sgx_head_loss), Adam over every parameter as one launch (sgx_adam_step), both on a device
+        step counter; the dropout stream is the trainer's counter-based mask, not torch's generator.  --replay (only with
+        --batch-size 0, the single fixed batch) records the whole step once and replays it every epoch.
 """
 import argparse
 import json
@@ -61,6 +66,8 @@ def main():
     ap.add_argument("--plain-loader", action="store_true")
     ap.add_argument("--model", choices=["gcn", "gat"], default="gcn")
     ap.add_argument("--qbits", type=int, default=32, choices=[32, 8, 4, 2, 1])
+    ap.add_argument("--trainer", action="store_true")
+    ap.add_argument("--replay", action="store_true")
     args = ap.parse_args()
     if args.qbits != 32 and args.model != "gat":
         ap.error("--qbits runs the quantised layers of the SGRACE library: --model gat")
@@ -68,6 +75,10 @@ def main():
         ap.error("--model gat trains on the kernels (--acc 1)")
     if args.train_stack and args.layer_count < 2:
         ap.error("--train-stack needs --layer-count >= 2")
+    if args.trainer and not (args.train_stack and args.acc == 1):
+        ap.error("--trainer runs the fused training route: --acc 1 --layer-count 2 --train-stack")
+    if args.replay and (not args.trainer or args.batch_size != 0):
+        ap.error("--replay replays the step of one fixed batch: --trainer with --batch-size 0")
     if args.host_loader and args.batch_size <= 0:
         ap.error("--host-loader needs --batch-size > 0")
     dev = torch.device("cuda")
@@ -101,6 +112,13 @@ def main():
         model = M.GCN_PYNQ(64, 7, 2, my_ip, train_stack=args.train_stack).to(dev)   # MOL cell 18 (seed 12345 inside)
     opt = torch.optim.Adam(model.parameters(), lr=0.01)       # MOL cell 20
     crit = torch.nn.CrossEntropyLoss()
+    trainer = replay = None
+    if args.trainer:
+        from sgracex1_amd.train import StackTrainer
+        trainer = StackTrainer(gat if args.model == "gat" else model, lr=0.01)      # the same Adam, the state on the device
+        if args.replay:
+            model.train()
+            replay = trainer.capture(train.x, train.edge_index, train.batch, train.y)
 
     def accuracy(batch):
         model.eval()
@@ -116,10 +134,15 @@ def main():
         for b in loader:
             if args.host_loader:
                 b = b.to(dev)
-            opt.zero_grad()
-            loss = crit(model(args.acc, b.x, b.edge_index, b.batch), b.y)
-            loss.backward()
-            opt.step()
+            if replay is not None:
+                loss = replay()
+            elif trainer is not None:
+                loss = trainer.step(b.x, b.edge_index, b.batch, b.y)
+            else:
+                opt.zero_grad()
+                loss = crit(model(args.acc, b.x, b.edge_index, b.batch), b.y)
+                loss.backward()
+                opt.step()
             steps += 1
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / steps
@@ -132,6 +155,7 @@ def main():
     print(json.dumps({"best_test_acc": best, "final_test_acc": log[-1]["test_acc"], "epochs": args.epochs,
                       "acc": args.acc, "model": args.model, "qbits": args.qbits, "layer_count": args.layer_count, "train_stack": args.train_stack,
                       "batch_size": args.batch_size, "host_loader": args.host_loader,
+                      **({"trainer": True, "replay": args.replay} if args.trainer else {}),
                       "prepared_loader": bool(getattr(loader, "prepare", None)), "reference": "0.76 at epoch 34 (notebook cell 20 output)" if args.model == "gcn" else "none (parity unpinned)"}))
 
 

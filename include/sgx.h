@@ -1362,6 +1362,89 @@ size_t sgx_quant_stack_backward_workspace_bytes(const sgx_quant_stack_grad_desc 
 size_t sgx_quant_stack_backward_lds_bytes(const sgx_quant_stack_grad_desc *d);
 int sgx_quant_stack_backward(const sgx_quant_stack_grad_desc *d, void *stream);
 
+/* ---- the loss head: dropout, the Linear head, cross entropy and their gradients in one call --------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_head_loss is the classifier tail of GCN_PYNQ / GAT_POOL_PYNQ behind the pooled means -- dropout(p), Linear
+ * [C][P], CrossEntropyLoss(reduction = mean) -- with its whole gradient: grad_pooled for the stack's backward, grad_W
+ * and grad_bias for the optimiser.  All arrays fp32 on the device, target int64.  u64 arithmetic wraps.
+ *   step_total = step + (step_dev ? (uint64)step_dev[0] : 0)            step_dev is read on the device, by the launch
+ *   dropout    k = mix64(mix64(mix64(seed) ^ step_total) ^ (uint64)(g * P + j))       mix64: the sampler's, above
+ *              keep(g, j) iff (k >> 40) >= floor(p * 2^24)              the hash's top 24 bits against p as a float's value
+ *              scale = 1.0f / (1.0f - p)                                two fp32 operations, formed once
+ *              x[g][j] = keep ? pooled[g][j] * scale : 0                p == 0: every element kept, x == pooled bit for bit
+ *   logits     z[g][c] = bias[c] + sum_j W[c][j] x[g][j] in sgx_readout_mean_linear's order: 64 lanes, lane l an fmaf
+ *              chain from 0 over j = l, l + 64, ...; the lanes added by the xor butterfly 32, 16, .. 1; then + bias[c]
+ *              (0 without a bias).  At p == 0 bit-equal to sgx_readout_mean_linear on one-row graphs.
+ *   loss       m = max_c z_c;  lse = m + logf(sum_c expf(z_c - m)), c ascending from 0;  loss_g = lse - z[target_g]
+ *              loss = (sum over slices b ascending of (sum of loss_g over g = b, b + S, ... ascending)) / (float)G
+ *   gradients  gs = grad_scale / (float)G
+ *              dz[g][c] = (expf(z_c - lse) - (c == target_g ? 1 : 0)) * gs
+ *              grad_pooled[g][j] = keep ? scale * (fmaf chain from 0 over c ascending of dz[g][c] * W[c][j]) : 0
+ *              grad_W[c][j] = sum_g dz[g][c] x[g][j];  grad_bias[c] = sum_g dz[g][c]
+ * A target outside [0, C) gives loss_g = 0 and dz[g][.] = 0 and indexes nothing; the divisor stays G.
+ * Sums over graphs are the only sums across workgroups, done as sgx_stack_backward does its weight gradients: S =
+ * min(G, 256) workgroups whatever the device; workgroup b adds its graphs b, b + S, ... in that order into its own fp32
+ * slice of the workspace (an fmaf on the slice's previous value for grad_W, an add for grad_bias and the loss; the first
+ * graph stores; plain loads and stores, no atomics), and a second launch adds the slices from 0 in slice order.  The same
+ * bits on every run and every device.
+ *
+ * Limits: P <= 1024, C <= 64; beyond: SGX_ERR_UNSUPPORTED.  Capturable: no allocation, no synchronisation.
+ * Argument errors, returned before anything reaches the device: n_graphs, P or C below 1: SGX_ERR_SHAPE; pooled, W,
+ * target, loss, grad_pooled or grad_W NULL, grad_bias NULL with a bias: SGX_ERR_NULL (bias NULL: grad_bias is not
+ * written; logits NULL: not written); p outside [0, 1) or over a limit: SGX_ERR_UNSUPPORTED; workspace missing or
+ * below sgx_head_loss_workspace_bytes: SGX_ERR_WORKSPACE; not 256-byte aligned: SGX_ERR_ALIGN. */
+/* min(G, 256) * (C * P + C + 1) floats, rounded up to 256 bytes; 0 for a shape the call refuses */
+size_t sgx_head_loss_workspace_bytes(int n_graphs, int P, int C);
+int sgx_head_loss(int n_graphs, int P, int C, const float *pooled, const float *W, const float *bias,
+                  const int64_t *target, float p_drop, uint64_t seed, uint64_t step, const int64_t *step_dev,
+                  float grad_scale, float *loss, float *logits, float *grad_pooled, float *grad_W, float *grad_bias,
+                  void *workspace, size_t workspace_bytes, void *stream);
+
+/* ---- the optimiser: multi-tensor Adam on a device step counter ---------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_adam_step is torch.optim.Adam (no amsgrad, weight_decay as L2 added to the gradient) on up to
+ * SGX_ADAM_MAX_TENSORS fp32 tensors in one launch; the tensor table travels in the kernel arguments.  The step counter
+ * is a device int64: the call reads t - 1 from it, uses t, and a trailing one-thread launch leaves t there -- one
+ * captured call is the right update at every replay.  Per element, every operation an individually rounded fp32 one
+ * (no contraction), the constants rounded once from the doubles of the descriptor:
+ *     b1 = (float)beta1, ob1 = (float)(1 - beta1), b2 = (float)beta2, ob2 = (float)(1 - beta2)     (1 - beta in double)
+ *     bc1 = (float)(1 - pow(beta1, t)),  sqrt_bc2 = (float)sqrt(1 - pow(beta2, t))                  (in double, then rounded)
+ *     step_size = (float)lr / bc1
+ *     g = grad;  weight_decay != 0:  r = (float)weight_decay * param;  g = g + r
+ *     m = b1 * m + ob1 * g                  (two products, one sum)
+ *     v = b2 * v + ob2 * (g * g)            (three products, one sum)
+ *     denom = sqrtf(v) / sqrt_bc2 + (float)eps
+ *     param = param - step_size * (m / denom)
+ * param, m, v are updated in place.  A tensor with n == 0 or grad == NULL is skipped, as torch skips p.grad is None.
+ * param_t_out (optional): the updated parameter seen as [rows][cols] row-major, written transposed [cols][rows] and
+ * cast to dtype_t -- bit-equal to torch.transpose(param, 0, 1).to(dtype).contiguous() on the updated parameter, the
+ * W^T a stack forward takes.
+ *
+ * Capturable: no allocation, no synchronisation.  Argument errors, returned before anything reaches the device: d or
+ * step NULL, param / m / v NULL on a tensor that is not skipped: SGX_ERR_NULL; n_tensors outside 0 ..
+ * SGX_ADAM_MAX_TENSORS, n < 0, param_t_out with rows * cols != n: SGX_ERR_SHAPE; a negative or NaN hyper-parameter,
+ * a beta outside [0, 1), a dtype_t other than SGX_F16 / SGX_F32: SGX_ERR_UNSUPPORTED. */
+#define SGX_ADAM_MAX_TENSORS 16
+
+typedef struct sgx_adam_tensor {
+    float *param, *m, *v;        /* [n] fp32, updated in place */
+    const float *grad;           /* [n] fp32; NULL = the tensor is skipped */
+    int64_t n;                   /* elements; 0 = skipped */
+    void *param_t_out;           /* optional [cols][rows] in dtype_t */
+    int32_t dtype_t, rows, cols; /* read only with param_t_out */
+} sgx_adam_tensor;
+
+typedef struct sgx_adam_desc {
+    int32_t n_tensors;           /* 0 .. SGX_ADAM_MAX_TENSORS */
+    double lr, beta1, beta2, eps, weight_decay;
+    int64_t *step;               /* device: t - 1 on entry, t after the call's launches */
+    sgx_adam_tensor tensor[SGX_ADAM_MAX_TENSORS];
+} sgx_adam_desc;
+
+int sgx_adam_step(const sgx_adam_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -51,6 +51,7 @@ SYMBOLS = [
     "sgx_quant_stack_workspace_bytes", "sgx_quant_stack_forward",
     "sgx_gat_stack_backward_workspace_bytes", "sgx_gat_stack_backward_lds_bytes", "sgx_gat_stack_backward",
     "sgx_quant_stack_backward_workspace_bytes", "sgx_quant_stack_backward_lds_bytes", "sgx_quant_stack_backward",
+    "sgx_head_loss_workspace_bytes", "sgx_head_loss", "sgx_adam_step",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -293,6 +294,29 @@ class LayerGradDesc(ctypes.Structure):
     ]
 
 
+SGX_ADAM_MAX_TENSORS = 16
+
+
+class AdamTensor(ctypes.Structure):
+    """struct sgx_adam_tensor -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("param", ctypes.c_void_p), ("m", ctypes.c_void_p), ("v", ctypes.c_void_p), ("grad", ctypes.c_void_p),
+        ("n", ctypes.c_int64), ("param_t_out", ctypes.c_void_p),
+        ("dtype_t", ctypes.c_int32), ("rows", ctypes.c_int32), ("cols", ctypes.c_int32),
+    ]
+
+
+class AdamDesc(ctypes.Structure):
+    """struct sgx_adam_desc -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("n_tensors", ctypes.c_int32),
+        ("lr", ctypes.c_double), ("beta1", ctypes.c_double), ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+        ("weight_decay", ctypes.c_double),
+        ("step", ctypes.c_void_p),
+        ("tensor", AdamTensor * SGX_ADAM_MAX_TENSORS),
+    ]
+
+
 def _load():
     if not os.path.exists(LIB_PATH):
         raise ImportError(
@@ -473,6 +497,13 @@ def _load():
     lib.sgx_csr_transpose_workspace_bytes.restype = sz
     lib.sgx_csr_transpose.argtypes = [c_int, c_int, c_int, c_i64, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.sgx_csr_transpose.restype = c_int
+    lib.sgx_head_loss_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.sgx_head_loss_workspace_bytes.restype = sz
+    lib.sgx_head_loss.argtypes = [c_int, c_int, c_int, vp, vp, vp, vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64, vp,
+                                  ctypes.c_float, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.sgx_head_loss.restype = c_int
+    lib.sgx_adam_step.argtypes = [ctypes.POINTER(AdamDesc), vp]
+    lib.sgx_adam_step.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

@@ -6,6 +6,8 @@
 // Nodes of one graph are contiguous (PyG batching, `batch` sorted), so a graph is a row segment
 // [ptr[g], ptr[g+1]).  One workgroup per graph: the segment mean is accumulated in fp32 with one
 // column per lane (coalesced row reads), then the C output classes are C wave reductions.
+// The training tail behind the pooled means -- dropout, this head (in this kernel's summation order), the loss and
+// their gradients -- is head_loss.hip (sgx_head_loss).
 #include "sgx_internal.h"
 
 namespace {

@@ -236,6 +236,21 @@ class GCN_PYNQ(torch.nn.Module):
             if pooled is not None:
                 x = F.dropout(pooled, p=0.5, training=self.training)
                 return self.lin(x)
+        x, ptr = self._layers(acc, x, edge_index, batch, bufs)
+        if ptr is not None and not self.training and not torch.is_grad_enabled():
+            # inference: pooling and the Linear head in one launch (dropout is the identity in eval)
+            return ops.readout_mean_linear(x.contiguous(), ptr, self.lin.weight, self.lin.bias)
+        if ptr is not None:
+            # training: the pooling as one launch each way (the same fp32 means as the inference kernel); dropout and
+            # the 64 x 2 head stay torch's here (train.StackTrainer runs them as one call, ops.head_loss)
+            x = ops.ReadoutMean.apply(x, ptr, batch.numel() == x.shape[0])
+        else:
+            x = global_mean_pool(x.float(), batch)
+        x = F.dropout(x, p=0.5, training=self.training)
+        return self.lin(x)
+
+    def _layers(self, acc, x, edge_index, batch, bufs=(None,) * 8):
+        """The two layers one by one: (the second layer's output, graph_ptr of a sorted `batch` with acc = 1, else None)."""
         if acc == 1:
             # pynq_adj = to_dense_adj(edge_index)._to_sparse_csr() of the notebook, built from the
             # edge list directly (same CSR, no dense N x N intermediate); the batch of an epoch loop is
@@ -251,17 +266,16 @@ class GCN_PYNQ(torch.nn.Module):
         x = self.conv2(acc, dense, relu, x, adj, *bufs)
         # a sorted `batch` (PyG's collation: graphs are contiguous) makes a graph a row segment; an unsorted one does not
         ptr = ops.graph_ptr_of(batch) if acc == 1 else None
-        if ptr is not None and not self.training and not torch.is_grad_enabled():
-            # inference: pooling and the Linear head in one launch (dropout is the identity in eval)
-            return ops.readout_mean_linear(x.contiguous(), ptr, self.lin.weight, self.lin.bias)
-        if ptr is not None:
-            # training: the pooling as one launch each way (the same fp32 means as the inference kernel); dropout and
-            # the 64 x 2 head stay torch's
-            x = ops.ReadoutMean.apply(x, ptr, batch.numel() == x.shape[0])
-        else:
-            x = global_mean_pool(x.float(), batch)
-        x = F.dropout(x, p=0.5, training=self.training)
-        return self.lin(x)
+        return x, ptr
+
+    def layers_pooled(self, x, edge_index, batch):
+        """The pooled means of the layer-by-layer training route on their own (acc = 1), for a caller that runs the tail
+        itself on a batch train_pooled declines (train.StackTrainer): ops.ReadoutMean behind the two layers' autograd;
+        None where `batch` is not sorted (the pooling is then torch's inside forward)."""
+        h, ptr = self._layers(1, x, edge_index, batch)
+        if ptr is None:
+            return None
+        return ops.ReadoutMean.apply(h, ptr, batch.numel() == h.shape[0])
 
     def _forward_stack(self, x, edge_index, batch):
         """Both layers, the mean pool and the head through ops.gcn_stack_forward: bit-equal to the layer-by-layer
@@ -279,6 +293,14 @@ class GCN_PYNQ(torch.nn.Module):
             return None
         return ops.gcn_stack_forward(adj, feature_csr(x, ACC_DTYPE), weights, [True, False], ptr, self.lin.weight,
                                      self.lin.bias, plan=plan)
+
+    def train_pooled(self, x, edge_index, batch):
+        """The fused training route on its own, for a caller that runs the tail itself (train.StackTrainer): the pooled
+        means behind ops.GcnStack where forward(acc = 1, ...) would take that route, None where it would not."""
+        if not (getattr(self, "train_stack", False) and torch.is_grad_enabled() and
+                getattr(self.conv1.my_ip.register_map, "layer_count", 1) >= 2):
+            return None
+        return self._train_stack(x, edge_index, batch)
 
     def _train_stack(self, x, edge_index, batch):
         """Both layers and the mean pool through ops.GcnStack (one sgx_stack_forward, one sgx_stack_backward): the pooled

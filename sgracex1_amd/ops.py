@@ -2085,3 +2085,106 @@ class QuantStack(torch.autograd.Function):
                                       alpha=ctx.alpha, plan=ctx.plan, adj_q=ctx.adj_q)
         dA = [None if g is None else g.reshape(a.shape) for g, a in zip(dA, atts)]
         return (None,) * 8 + tuple(dW) + tuple(dA)
+
+
+# ---- the tail of a training step: the loss head and the optimiser (sgx_head_loss, sgx_adam_step) ----------------------------
+def head_loss(pooled, weight, bias, target, p=0.0, seed=0, step=0, step_dev=None, grad_scale=1.0, want_logits=False):
+    """Dropout(p), the Linear head and the mean cross entropy with every gradient, in one call (sgx_head_loss; the rule is
+    in include/sgx.h, "the loss head").  pooled [G, P] fp32, weight [C, P] fp32, bias [C] fp32 or None, target [G] int64;
+    the dropout mask is a fixed function of (seed, step + step_dev[0], element); step_dev: a device int64 tensor (the
+    optimiser's counter) or None.  Returns (loss [1], grad_pooled [G, P], grad_W [C, P], grad_bias [C] or None), and the
+    logits [G, C] behind them with want_logits.  Never synchronises."""
+    pooled = _dev(pooled.detach(), "pooled")
+    w = _dev(weight.detach(), "weight")
+    b = None if bias is None else _dev(bias.detach(), "bias")
+    _dev(target, "target")
+    if pooled.dtype != torch.float32 or w.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
+        raise TypeError("head_loss works on float32 tensors")
+    if target.dtype != torch.int64:
+        raise TypeError("head_loss takes int64 targets")
+    if pooled.dim() != 2 or w.dim() != 2 or w.shape[1] != pooled.shape[1] or target.shape != (pooled.shape[0],) or \
+            (b is not None and b.shape != (w.shape[0],)):
+        raise ValueError("head_loss takes pooled [G, P], weight [C, P], bias [C], target [G]")
+    if step_dev is not None:
+        _dev(step_dev, "step_dev")
+        if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
+            raise TypeError("step_dev must be a device int64 tensor")
+    G, P = pooled.shape
+    C, dev = w.shape[0], pooled.device
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    grad_pooled = torch.empty((G, P), dtype=torch.float32, device=dev)
+    grad_W = torch.empty((C, P), dtype=torch.float32, device=dev)
+    grad_b = None if b is None else torch.empty(C, dtype=torch.float32, device=dev)
+    logits = torch.empty((G, C), dtype=torch.float32, device=dev) if want_logits else None
+    nbytes = lib.sgx_head_loss_workspace_bytes(G, P, C)
+    ws = _workspace(dev, nbytes) if nbytes else None
+    check(lib.sgx_head_loss(G, P, C, _ptr(pooled), _ptr(w), _ptr(b), _ptr(target), float(p), int(seed) & (2 ** 64 - 1),
+                            int(step) & (2 ** 64 - 1), _ptr(step_dev), float(grad_scale), _ptr(loss), _ptr(logits),
+                            _ptr(grad_pooled), _ptr(grad_W), _ptr(grad_b), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+          "sgx_head_loss")
+    out = (loss, grad_pooled, grad_W, grad_b)
+    return out + (logits,) if want_logits else out
+
+
+class HeadLoss(torch.autograd.Function):
+    """head_loss inside an ordinary autograd loop: forward runs the one call (with grad_scale 1) and keeps its gradients,
+    backward hands them on times grad_output.
+
+        loss = HeadLoss.apply(pooled, weight, bias, target, p, seed, step, step_dev)        # a 0-dim tensor"""
+
+    @staticmethod
+    def forward(ctx, pooled, weight, bias, target, p=0.0, seed=0, step=0, step_dev=None):
+        loss, gp, gw, gb = head_loss(pooled, weight, bias, target, p, seed, step, step_dev)
+        ctx.save_for_backward(gp, gw, *([] if gb is None else [gb]))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gp, gw, *gb = ctx.saved_tensors
+        return (gp * grad_output, gw * grad_output, gb[0] * grad_output if gb else None, None, None, None, None, None)
+
+
+def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
+              transposed_out=None):
+    """torch.optim.Adam's update (no amsgrad) of up to 16 tensors in one launch (sgx_adam_step; the rule is in
+    include/sgx.h, "the optimiser").  params, exp_avgs, exp_avg_sqs: fp32 tensors updated in place; grads: fp32 tensors,
+    None = that parameter is skipped; step: the device int64 counter [1], t - 1 before and t after the call.
+    transposed_out: per parameter None or a [cols, rows] fp16 / fp32 tensor that receives the updated 2-D parameter
+    transposed and cast.  More than 16 tensors: ValueError (one call is one step of the counter).  Never synchronises."""
+    n = len(params)
+    if not (len(grads) == len(exp_avgs) == len(exp_avg_sqs) == n):
+        raise ValueError("adam_step takes one gradient (or None), one exp_avg and one exp_avg_sq per parameter")
+    _dev(step, "step")
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise TypeError("step must be a device int64 tensor of one element")
+    entries = []
+    for k in range(n):
+        p, g = params[k].detach(), grads[k]
+        if g is None or p.numel() == 0:           # the call skips these itself, as torch skips p.grad is None
+            entries.append((p, None, None, None, None))
+            continue
+        for name, t in (("param", p), ("grad", g), ("exp_avg", exp_avgs[k]), ("exp_avg_sq", exp_avg_sqs[k])):
+            _dev(t, name)
+            if t.dtype != torch.float32 or t.numel() != p.numel():
+                raise ValueError(f"{name}[{k}] must be a float32 tensor of the parameter's size")
+        t_out = None if transposed_out is None else transposed_out[k]
+        if t_out is not None:
+            _dev(t_out, "transposed_out")
+            if p.dim() != 2 or t_out.shape != (p.shape[1], p.shape[0]):
+                raise ValueError(f"transposed_out[{k}] must be [{p.shape[-1]}, {p.shape[0]}]")
+        entries.append((p, g, exp_avgs[k], exp_avg_sqs[k], t_out))
+    if len(entries) > _lib.SGX_ADAM_MAX_TENSORS:
+        raise ValueError(f"adam_step takes at most {_lib.SGX_ADAM_MAX_TENSORS} tensors in a call (got {len(entries)})")
+    d = _lib.AdamDesc()
+    d.n_tensors = len(entries)
+    d.lr, d.beta1, d.beta2, d.eps, d.weight_decay = float(lr), float(betas[0]), float(betas[1]), float(eps), float(weight_decay)
+    d.step = step.data_ptr()
+    for k, (p, g, m, v, t_out) in enumerate(entries):
+        T = d.tensor[k]
+        T.n = p.numel()
+        if g is None:
+            continue
+        T.param, T.m, T.v, T.grad = p.data_ptr(), m.data_ptr(), v.data_ptr(), g.data_ptr()
+        if t_out is not None:
+            T.param_t_out, T.dtype_t, T.rows, T.cols = t_out.data_ptr(), dtype_code(t_out.dtype), p.shape[0], p.shape[1]
+    check(lib.sgx_adam_step(ctypes.byref(d), _stream()), "sgx_adam_step")

@@ -433,14 +433,26 @@ class GAT_POOL_PYNQ(Module):
         self.reluh = Relu_SGRACE()
         self.lin = torch.nn.Linear(hidden_channels, num_classes)
 
-    def forward(self, x, edge_index, batch):
+    @staticmethod
+    def _normalised(x, edge_index):
         def normalise():                                          # once per batch, not per call
             ei, norm = sym_norm2(edge_index, x.size(0))
             adj = _edge_csr(None, ei, norm, x.size(0), _torch_dtype()) if config.acc == 1 else \
                 torch.sparse_coo_tensor(ei, norm, (x.size(0), x.size(0)))
             return ei, norm, adj
 
-        ei, norm, adj = ops.cached_on(edge_index, ("sym_norm2", x.size(0), config.acc, _torch_dtype()), normalise)
+        return ops.cached_on(edge_index, ("sym_norm2", x.size(0), config.acc, _torch_dtype()), normalise)
+
+    def train_pooled(self, x, edge_index, batch):
+        """The fused training route on its own, for a caller that runs the tail itself (train.StackTrainer): the pooled
+        means behind ops.GatStack / ops.QuantStack where forward would take that route, None where it would not."""
+        if not (config.acc == 1 and getattr(self, "train_stack", False) and torch.is_grad_enabled() and
+                my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2):
+            return None
+        return self._train_stack(x, self._normalised(x, edge_index)[2], batch)
+
+    def forward(self, x, edge_index, batch):
+        ei, norm, adj = self._normalised(x, edge_index)
         if config.acc == 1 and not self.training and not torch.is_grad_enabled() and \
                 my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2:
             out = self._forward_stack(x, adj, batch)
@@ -452,11 +464,7 @@ class GAT_POOL_PYNQ(Module):
             pooled = self._train_stack(x, adj, batch)
             if pooled is not None:
                 return self.lin(F.dropout(pooled, p=0.5, training=self.training))
-        x = self.att1(config.compute_attention, 0, 1, x, ei, norm, adj)
-        x = self.reluh(x)
-        x = self.att2(config.compute_attention, 1, 0, x, ei, norm, adj)
-        # a sorted `batch` makes a graph a row segment; an unsorted one does not
-        ptr = ops.graph_ptr_of(batch) if config.acc == 1 else None
+        x, ptr = self._layers(x, ei, norm, adj, batch)
         if ptr is not None and not self.training and not torch.is_grad_enabled():
             return ops.readout_mean_linear(x.contiguous(), ptr, self.lin.weight, self.lin.bias)
         if ptr is not None:
@@ -465,6 +473,27 @@ class GAT_POOL_PYNQ(Module):
             x = global_mean_pool(x.float(), batch)
         x = F.dropout(x, p=0.5, training=self.training)
         return self.lin(x)
+
+    def _layers(self, x, ei, norm, adj, batch):
+        """The two layers one by one: (the second layer's output, graph_ptr of a sorted `batch` with acc = 1, else None)."""
+        x = self.att1(config.compute_attention, 0, 1, x, ei, norm, adj)
+        x = self.reluh(x)
+        x = self.att2(config.compute_attention, 1, 0, x, ei, norm, adj)
+        # a sorted `batch` makes a graph a row segment; an unsorted one does not
+        ptr = ops.graph_ptr_of(batch) if config.acc == 1 else None
+        return x, ptr
+
+    def layers_pooled(self, x, edge_index, batch):
+        """The pooled means of the layer-by-layer training route on their own, for a caller that runs the tail itself on a
+        batch train_pooled declines (train.StackTrainer): ops.ReadoutMean behind the two layers' autograd; None where
+        config.acc != 1 or `batch` is not sorted (the pooling is then torch's inside forward)."""
+        if config.acc != 1:
+            return None
+        ei, norm, adj = self._normalised(x, edge_index)
+        h, ptr = self._layers(x, ei, norm, adj, batch)
+        if ptr is None:
+            return None
+        return ops.ReadoutMean.apply(h, ptr, batch.numel() == h.shape[0])
 
     def _forward_stack(self, x, adj, batch):
         """Both layers, the mean pool and the head through ops.gat_stack_forward (ops.quant_stack_forward with the
