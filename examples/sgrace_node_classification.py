@@ -6,6 +6,7 @@ downloaded by torch_geometric and are not available offline.
 
     python examples/sgrace_node_classification.py [--attention [--lean-gat]] [--qbits 8] [--epochs 60] [--acc 0]
                                                   [--batch-size 128 --num-neighbors 10,10 [--device-batches]] [--accb]
+                                                  [--trainer [--replay]]
 
 --attention  GAT edge softmax instead of the GCN aggregate (config.compute_attention)
 --lean-gat   with --attention on the kernels: the forward keeps the row softmax statistics instead of the per-edge outputs
@@ -31,6 +32,12 @@ downloaded by torch_geometric and are not available offline.
              transposed pattern of the GAT backward), built on the GPU by sgx_csr_transpose instead of a sort per batch;
              with --qbits the batches also carry the quantised adjacency of both layers with its dead-row facts
              (quant=sgrace.quant_constants), so the quantised layers too launch nothing and read nothing back for it
+--trainer    on the kernels: the tail of every step -- dropout, the Linear head, the cross entropy over the training rows,
+             their gradients and Adam -- as train.NodeTrainer runs it (sgx_node_loss, sgx_adam_step) instead of torch's;
+             the plain mini-batch mode hands batch.train_mask over as the mask (no boolean index, no read-back per step),
+             and the final accuracies are counted on the device (NodeTrainer.evaluate)
+--replay     with --trainer on the full graph: the whole step captured once (torch.cuda.graph) and replayed every epoch;
+             mini-batches run eager only, their shapes vary
 """
 import argparse
 import os
@@ -60,7 +67,8 @@ def planted_partition(n, classes, f_in, p_in, p_out, seed, device):
 
 
 def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, verbose=True, emulate=False,
-        batch_size=None, num_neighbors=None, lean_gat=False, device_batches=False, accb=0):
+        batch_size=None, num_neighbors=None, lean_gat=False, device_batches=False, accb=0, trainer=False,
+        replay=False):
     from sgracex1_amd import config, sgrace
     config.acc = acc
     config.accb = int(accb)
@@ -78,8 +86,15 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
     perm = torch.randperm(n, generator=torch.Generator().manual_seed(seed)).to(device)
     train, test = perm[: n // 5], perm[n // 5:]
     model = sgrace.GAT_PYNQ(x.shape[1], hidden, 1, 5).to(device)
-    opt = torch.optim.Adam(model.parameters(), lr=0.01, weight_decay=5e-4)
-    crit = torch.nn.CrossEntropyLoss()
+    node_trainer = replay_step = None
+    if trainer:
+        from sgracex1_amd.train import NodeTrainer
+        node_trainer = NodeTrainer(model, lr=0.01, weight_decay=5e-4, seed=seed)
+        full_mask = torch.zeros(n, dtype=torch.bool, device=device)
+        full_mask[train] = True
+    else:
+        opt = torch.optim.Adam(model.parameters(), lr=0.01, weight_decay=5e-4)
+        crit = torch.nn.CrossEntropyLoss()
     loader = None
     if batch_size:
         from sgracex1_amd import pyg_lite
@@ -94,7 +109,19 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
     for epoch in range(epochs):
         model.train()
         total, steps = 0, 0
-        if loader is None:
+        if loader is None and node_trainer is not None:
+            if replay and replay_step is None:
+                replay_step = node_trainer.capture(x, edge_index, y, full_mask)
+            loss = replay_step() if replay else node_trainer.step(x, edge_index, y, full_mask)
+            total, steps = loss[0], 1
+        elif node_trainer is not None:
+            for batch in loader:
+                if device_batches:
+                    loss = node_trainer.step(batch.x, batch.edge_index_agg, batch.y, n_prefix=batch.batch_size)
+                else:
+                    loss = node_trainer.step(batch.x, batch.edge_index.flip(0), batch.y, mask=batch.train_mask)
+                total, steps = total + loss[0], steps + 1
+        elif loader is None:
             opt.zero_grad()
             loss = crit(model(x, edge_index)[train], y[train])
             loss.backward()
@@ -123,10 +150,14 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         torch.cuda.synchronize()
     elapsed = time.time() - t0
     model.eval()
-    with torch.no_grad():
-        pred = model(x, edge_index).argmax(1)
-    result = {"train_acc": float((pred[train] == y[train]).float().mean()),
-              "test_acc": float((pred[test] == y[test]).float().mean()),
+    if node_trainer is not None:
+        (m_tr, hit_tr), (m_te, hit_te) = (node_trainer.evaluate(x, edge_index, y, m)[0].tolist() for m in (full_mask, ~full_mask))
+        train_acc, test_acc = hit_tr / m_tr, hit_te / m_te
+    else:
+        with torch.no_grad():
+            pred = model(x, edge_index).argmax(1)
+        train_acc, test_acc = float((pred[train] == y[train]).float().mean()), float((pred[test] == y[test]).float().mean())
+    result = {"train_acc": train_acc, "test_acc": test_acc,
               "edges": int(edge_index.shape[1]), "ms_per_epoch": 1000 * elapsed / epochs,
               "epoch_loss": [float(v) for v in epoch_loss]}
     if loader is not None:
@@ -151,11 +182,17 @@ if __name__ == "__main__":
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--device-batches", action="store_true")
     ap.add_argument("--accb", action="store_true")
+    ap.add_argument("--trainer", action="store_true")
+    ap.add_argument("--replay", action="store_true")
     a = ap.parse_args()
     if (a.batch_size is None) != (a.num_neighbors is None) or (a.batch_size is not None and a.acc != 1):
         ap.error("--batch-size and --num-neighbors go together, on the kernels (--acc 1)")
     if a.device_batches and a.batch_size is None:
         ap.error("--device-batches selects the loader of the mini-batch mode (--batch-size, --num-neighbors)")
+    if a.trainer and a.acc != 1:
+        ap.error("--trainer runs the tail on the kernels (--acc 1)")
+    if a.replay and (not a.trainer or a.batch_size is not None):
+        ap.error("--replay replays the full-graph step of --trainer; mini-batches run eager only")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
         num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches,
-        accb=int(a.accb))
+        accb=int(a.accb), trainer=a.trainer, replay=a.replay)

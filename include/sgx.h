@@ -1445,6 +1445,58 @@ typedef struct sgx_adam_desc {
 
 int sgx_adam_step(const sgx_adam_desc *d, void *stream);
 
+/* ---- the node loss head: the loss head over selected rows of a node matrix ----------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_node_loss is the classifier tail of GAT_PYNQ's training loop behind the last layer -- dropout(p), Linear [C][P],
+ * CrossEntropyLoss(reduction = mean) over out[train] / out[batch.train_mask] / out[:batch_size] -- with its whole
+ * gradient, the selected rows' count and the arg-max's hits.  All arrays fp32 on the device, H [n_rows][P], W [C][P],
+ * target int64 [n_rows], mask bytes [n_rows] (a bool array as its bytes).  u64 arithmetic wraps.
+ *   selection  row i is selected iff i < n_prefix && (mask == NULL || mask[i] != 0).  M = the number of selected rows,
+ *              counted on the device by a launch of its own (integer partial counts); the host never learns it.
+ *              n_prefix = n_rows with a mask: the full graph; n_prefix = batch_size without one: a seeds-first batch.
+ *   dropout    sgx_head_loss's exactly, element (i, j) at index i * P + j, step_total = step + step_dev[0]:
+ *              keep(i, j), scale = 1.0f / (1.0f - p), x[i][j] = keep ? H[i][j] * scale : 0; p == 0: x == H bit for bit
+ *   logits     z[i][c] = (fmaf chain from 0 over j ascending from 0 of W[c][j] * x[i][j]) + bias[c]     (0 without a bias)
+ *   per selected row:  m = max_c z_c;  lse = m + logf(sum_c expf(z_c - m)), c ascending from 0;  loss_i = lse - z[target_i]
+ *              gs = grad_scale / (float)M
+ *              dz[i][c] = (expf(z_c - lse) - (c == target_i ? 1 : 0)) * gs
+ *              a target outside [0, C): loss_i = 0, dz[i][.] = 0, nothing is indexed, the row is not a hit; it counts in M
+ *              hit_i: arg-max of z[i] == target_i, the arg-max over c ascending with a strict > from z[0] (a NaN z[0]
+ *              counts as -inf): the lowest index wins a tie, a NaN never wins
+ *   unselected rows have dz = 0 and take part in no sum
+ *   grad_H[i][j] = keep ? scale * (fmaf chain from 0 over c ascending of dz[i][c] * W[c][j]) : 0   for EVERY i < n_rows;
+ *              exact zeros in unselected rows
+ *   sums over rows: rows are cut into blocks of SGX_NODE_LOSS_ROWS consecutive rows; block b belongs to slice b mod S,
+ *              S = min(number of blocks, SGX_NODE_LOSS_GRID) whatever the device.  Within a slice, blocks ascending:
+ *              grad_W[c][j]: ONE fmaf chain from 0 over the slice's selected rows in ascending row order of dz[i][c] * x[i][j]
+ *              grad_bias[c]: one chain of additions from 0 over the same rows in the same order
+ *              loss: per row position r = i mod SGX_NODE_LOSS_ROWS a chain of additions from 0 over the slice's
+ *              selected rows at that position, ascending; then the positions r = 0, 1, .. added from 0
+ *              Then the slices are added from 0 in slice order (fp32 additions), and loss = sum / (float)M.
+ *              Plain loads and stores, no floating-point atomics: the same bits on every run and every device.
+ *   M == 0     loss = 0 and every gradient 0 (torch gives NaN for the mean over no row).
+ *   counts     optional, int64 [2] = {M, hits}.   logits: optional, z for every i < n_rows, selected or not.
+ *   grad_H, grad_W and grad_bias all NULL: evaluation mode -- loss, counts and logits only; a row that feeds none of
+ *              them is not read.  In either mode a block without a needed row (selected, or any row when logits are
+ *              wanted) is not read either: its grad_H rows are zero-filled.
+ * Limits: P <= 1024, C <= 64, C * P <= 16384 (64 accumulators a thread, 64 KiB of W in LDS); beyond: SGX_ERR_UNSUPPORTED
+ * and a workspace size of 0.  Capturable: no allocation, no synchronisation (three kernel nodes).
+ * Argument errors, returned before anything reaches the device: n_rows, P or C below 1, n_prefix < 0: SGX_ERR_SHAPE; H, W,
+ * target or loss NULL, or only part of grad_H / grad_W / grad_bias NULL (grad_bias is required exactly when bias is
+ * given; without a bias it is not written): SGX_ERR_NULL; p outside [0, 1) or over a limit: SGX_ERR_UNSUPPORTED;
+ * workspace missing or below sgx_node_loss_workspace_bytes: SGX_ERR_WORKSPACE; not 256-byte aligned: SGX_ERR_ALIGN. */
+#define SGX_NODE_LOSS_ROWS 16
+#define SGX_NODE_LOSS_GRID 512
+
+/* 2048 + min(ceil(n_rows / SGX_NODE_LOSS_ROWS), SGX_NODE_LOSS_GRID) * (C * P + C + 2) floats rounded up to 256 bytes; 0 for
+ * a shape the call refuses */
+size_t sgx_node_loss_workspace_bytes(int64_t n_rows, int P, int C);
+int sgx_node_loss(int64_t n_rows, int64_t n_prefix, int P, int C, const float *H, const float *W, const float *bias,
+                  const int64_t *target, const uint8_t *mask, float p_drop, uint64_t seed, uint64_t step,
+                  const int64_t *step_dev, float grad_scale, float *loss, int64_t *counts, float *logits, float *grad_H,
+                  float *grad_W, float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -23,6 +23,7 @@ SGX_QUANT_INT8_AUTO = 4                                     # ... where they are
 SGX_ERR_SEEDS = -8                                          # sgx_sample_neighbors: a repeated or out-of-range seed
 SGX_ERR_BLOCKS = -9                                         # sgx_batch_plan_create: an edge leaves its graph / bad graph_ptr
 SGX_BATCH_FORWARD, SGX_BATCH_BACKWARD = 0, 1                # sgx_batch_kind: whose LDS tiles set a batch plan's row budget
+SGX_NODE_LOSS_ROWS, SGX_NODE_LOSS_GRID = 16, 512                  # sgx_node_loss: rows of a block, slices at most
 SGX_CSR_TRANSPOSE_TILE = 2048                               # sgx_csr_transpose: stored entries per workgroup of a sort pass
 
 # every symbol include/sgx.h declares (tests/test_abi.py checks header and library against this)
@@ -52,6 +53,7 @@ SYMBOLS = [
     "sgx_gat_stack_backward_workspace_bytes", "sgx_gat_stack_backward_lds_bytes", "sgx_gat_stack_backward",
     "sgx_quant_stack_backward_workspace_bytes", "sgx_quant_stack_backward_lds_bytes", "sgx_quant_stack_backward",
     "sgx_head_loss_workspace_bytes", "sgx_head_loss", "sgx_adam_step",
+    "sgx_node_loss_workspace_bytes", "sgx_node_loss",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -504,6 +506,11 @@ def _load():
     lib.sgx_head_loss.restype = c_int
     lib.sgx_adam_step.argtypes = [ctypes.POINTER(AdamDesc), vp]
     lib.sgx_adam_step.restype = c_int
+    lib.sgx_node_loss_workspace_bytes.argtypes = [c_i64, c_int, c_int]
+    lib.sgx_node_loss_workspace_bytes.restype = sz
+    lib.sgx_node_loss.argtypes = [c_i64, c_i64, c_int, c_int, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
+                                  vp, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.sgx_node_loss.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

@@ -2188,3 +2188,74 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr=1e-3, betas=(0.9, 0
         if t_out is not None:
             T.param_t_out, T.dtype_t, T.rows, T.cols = t_out.data_ptr(), dtype_code(t_out.dtype), p.shape[0], p.shape[1]
     check(lib.sgx_adam_step(ctypes.byref(d), _stream()), "sgx_adam_step")
+
+
+# ---- the tail of a node-classification step: the loss head over selected rows (sgx_node_loss) ----------------------------------
+def node_loss(H, weight, bias, target, mask=None, n_prefix=None, p=0.0, seed=0, step=0, step_dev=None, grad_scale=1.0,
+              want_logits=False, want_counts=False, grads=True):
+    """Dropout(p), the Linear head and the mean cross entropy over the SELECTED rows of H with every gradient, in one call
+    (sgx_node_loss; the rule is in include/sgx.h, "the node loss head").  H [n, P] fp32, weight [C, P] fp32, bias [C] fp32
+    or None, target [n] int64; row i is selected iff i < n_prefix (default n) and mask[i] (a bool or uint8 tensor [n],
+    passed as its bytes; None: every row).  The count of selected rows stays on the device.  Returns
+    (loss [1], grad_H [n, P], grad_W [C, P], grad_bias [C] or None) -- the three gradients None with grads=False, the
+    evaluation mode -- then counts (int64 [2]: selected rows, arg-max hits among them) with want_counts and the logits
+    [n, C] of every row with want_logits.  Never synchronises."""
+    H = _dev(H.detach(), "H")
+    w = _dev(weight.detach(), "weight")
+    b = None if bias is None else _dev(bias.detach(), "bias")
+    _dev(target, "target")
+    if H.dtype != torch.float32 or w.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
+        raise TypeError("node_loss works on float32 tensors")
+    if target.dtype != torch.int64:
+        raise TypeError("node_loss takes int64 targets")
+    if H.dim() != 2 or w.dim() != 2 or w.shape[1] != H.shape[1] or target.shape != (H.shape[0],) or \
+            (b is not None and b.shape != (w.shape[0],)):
+        raise ValueError("node_loss takes H [n, P], weight [C, P], bias [C], target [n]")
+    n, P = H.shape
+    C, dev = w.shape[0], H.device
+    if mask is not None:
+        _dev(mask, "mask")
+        if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != (n,):
+            raise TypeError("mask must be a bool or uint8 tensor [n]")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+    if step_dev is not None:
+        _dev(step_dev, "step_dev")
+        if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
+            raise TypeError("step_dev must be a device int64 tensor")
+    n_prefix = n if n_prefix is None else int(n_prefix)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    grad_H = torch.empty((n, P), dtype=torch.float32, device=dev) if grads else None
+    grad_W = torch.empty((C, P), dtype=torch.float32, device=dev) if grads else None
+    grad_b = torch.empty(C, dtype=torch.float32, device=dev) if grads and b is not None else None
+    counts = torch.empty(2, dtype=torch.int64, device=dev) if want_counts else None
+    logits = torch.empty((n, C), dtype=torch.float32, device=dev) if want_logits else None
+    nbytes = lib.sgx_node_loss_workspace_bytes(n, P, C)
+    ws = _workspace(dev, nbytes) if nbytes else None
+    check(lib.sgx_node_loss(n, n_prefix, P, C, _ptr(H), _ptr(w), _ptr(b), _ptr(target), _ptr(mask), float(p),
+                            int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _ptr(step_dev), float(grad_scale), _ptr(loss),
+                            _ptr(counts), _ptr(logits), _ptr(grad_H), _ptr(grad_W), _ptr(grad_b), _ptr(ws),
+                            0 if ws is None else ws.numel(), _stream()),
+          "sgx_node_loss")
+    out = (loss, grad_H, grad_W, grad_b)
+    if want_counts:
+        out = out + (counts,)
+    return out + (logits,) if want_logits else out
+
+
+class NodeLoss(torch.autograd.Function):
+    """node_loss inside an ordinary autograd loop: forward runs the one call (with grad_scale 1) and keeps its gradients,
+    backward hands them on times grad_output.
+
+        loss = NodeLoss.apply(H, weight, bias, target, mask, n_prefix, p, seed, step, step_dev)        # a 0-dim tensor"""
+
+    @staticmethod
+    def forward(ctx, H, weight, bias, target, mask=None, n_prefix=None, p=0.0, seed=0, step=0, step_dev=None):
+        loss, gh, gw, gb = node_loss(H, weight, bias, target, mask, n_prefix, p, seed, step, step_dev)
+        ctx.save_for_backward(gh, gw, *([] if gb is None else [gb]))
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gh, gw, *gb = ctx.saved_tensors
+        return (gh * grad_output, gw * grad_output, gb[0] * grad_output if gb else None) + (None,) * 7

@@ -382,7 +382,9 @@ class GAT_PYNQ(Module):
         self.reluh = Relu_SGRACE()
         self.lin = torch.nn.Linear(hidden_channels, num_classes)
 
-    def forward(self, x, edge_index):
+    def features(self, x, edge_index):
+        """The two layers without the classifier tail: what dropout and self.lin receive, in fp32 (train.NodeTrainer runs
+        that tail as one call, ops.node_loss)."""
         def normalise():                                          # once per graph, not per call
             ei, norm = sym_norm2(edge_index, x.size(0))
             adj = _edge_csr(None, ei, norm, x.size(0), _torch_dtype()) if config.acc == 1 else \
@@ -393,7 +395,10 @@ class GAT_PYNQ(Module):
         x = self.att2(config.compute_attention, 0, 1, x, ei, norm, adj)
         x = self.reluh(x)
         x = self.conv22(config.compute_attention, 1, 0, x, ei, norm, adj)
-        x = F.dropout(x.float(), p=0.5, training=self.training)
+        return x.float()
+
+    def forward(self, x, edge_index):
+        x = F.dropout(self.features(x, edge_index), p=0.5, training=self.training)
         return self.lin(x)
 
 

@@ -5,6 +5,9 @@
 
 on a device step counter that both the dropout mask and Adam's bias corrections read, so the whole step of a fixed batch
 can be captured once (torch.cuda.graph) and replayed: the regime of the notebook, one 188-graph batch for 60 steps.
+
+NodeTrainer is the same for node classification (sgrace.GAT_PYNQ): the model's two layers through their own autograd,
+ops.NodeLoss (the tail over the selected rows, the count of which never leaves the device) and ops.adam_step.
 """
 import torch
 import torch.nn.functional as F
@@ -106,6 +109,119 @@ class StackTrainer:
         with torch.cuda.graph(graph):
             loss = self.step(x, edge_index, batch, y)
         self.fused_steps = fused
+
+        def replay():
+            graph.replay()
+            return loss
+
+        replay.graph = graph
+        return replay
+
+
+class NodeTrainer:
+    """Adam on the kernels for sgrace.GAT_PYNQ, the node classifier of the demo.
+
+        trainer = NodeTrainer(model, lr=0.01, weight_decay=5e-4)
+        loss = trainer.step(x, edge_index, y, mask=train_mask)            # full graph: a device tensor [1]
+        loss = trainer.step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size)      # a seeds-first mini-batch
+        counts, loss = trainer.evaluate(x, edge_index, y, test_mask)      # device int64 [selected, hits], device loss [1]
+        replay = trainer.capture(x, edge_index, y, train_mask)            # the full-graph step, recorded once
+
+    A step is model.features -> ops.NodeLoss on the device counter `t` -> loss.backward() through the layers' own autograd
+    -> one ops.adam_step over every parameter that received a gradient (the layers' never-used `bias` parameters receive
+    none and are skipped, as torch skips them).  The rows that count are `mask` (bool [n]) and / or the first `n_prefix`
+    rows; how many they are is counted on the device, so a step synchronises nothing of its own.  The dropout stream is
+    ops.node_loss's counter-based mask of (seed, t), not torch's generator; the layers run in whatever mode the model is in."""
+
+    def __init__(self, model, lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, p_drop=0.5, seed=12345):
+        if not hasattr(model, "features") or not hasattr(model, "lin"):
+            raise TypeError("NodeTrainer takes a GAT_PYNQ")
+        self.model = model
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.p_drop, self.seed = float(p_drop), int(seed)
+        self.params = [p for p in model.parameters() if p.requires_grad]
+        dev = self.params[0].device
+        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.last_grads = None        # the gradients handed to the last ops.adam_step, in self.params' order
+
+    def step(self, x, edge_index, y, mask=None, n_prefix=None):
+        model = self.model
+        for p in self.params:
+            p.grad = None
+        H = model.features(x, edge_index).contiguous()
+        loss = ops.NodeLoss.apply(H, model.lin.weight, model.lin.bias, y, mask, n_prefix, self.p_drop, self.seed, 0, self.t)
+        loss.backward()
+        grads = [None if p.grad is None else p.grad.contiguous() for p in self.params]
+        ops.adam_step(self.params, grads, self.exp_avg, self.exp_avg_sq, self.t, lr=self.lr, betas=self.betas, eps=self.eps,
+                      weight_decay=self.weight_decay)
+        self.last_grads = grads
+        return loss.detach().reshape(1)
+
+    def evaluate(self, x, edge_index, y, mask=None, n_prefix=None):
+        """(counts, loss) of the selected rows in eval mode without dropout: counts = device int64 [selected rows, rows
+        whose arg-max class is the target].  No logits leave the device; the model's mode is put back."""
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                H = model.features(x, edge_index).contiguous()
+                loss, _, _, _, counts = ops.node_loss(H, model.lin.weight, model.lin.bias, y, mask=mask, n_prefix=n_prefix, p=0.0,
+                                                      want_counts=True, grads=False)
+        finally:
+            model.train(was_training)
+        return counts, loss
+
+    def state(self):
+        """Copies of everything a step changes: the parameters, both moments, the counter."""
+        return [t.detach().clone() for t in (*self.params, *self.exp_avg, *self.exp_avg_sq, self.t)]
+
+    def load_state(self, state):
+        with torch.no_grad():
+            for dst, src in zip((*self.params, *self.exp_avg, *self.exp_avg_sq, self.t), state):
+                dst.copy_(src)
+
+    def _configuration(self):
+        from . import config
+        return (f"compute_attention={config.compute_attention} accb={config.accb} fake_quantization={config.fake_quantization} "
+                f"hardware_quantize={config.hardware_quantize} gat_edge_outputs={config.gat_edge_outputs} "
+                f"float_type={getattr(config.float_type, '__name__', config.float_type)}")
+
+    def capture(self, x, edge_index, y, mask=None, n_prefix=None, warmup=2):
+        """Record the full-graph step with torch.cuda.graph (one stream) and return a callable that replays it and returns
+        the loss tensor the replay fills.  The warm-up steps (they build what a step caches: the CSRs, the plans, the
+        workspaces) run on a copy of the state, which is put back before the capture: n replays equal n eager steps.  The
+        last warm-up step runs under torch.cuda.set_sync_debug_mode("error"): a layer path that synchronises cannot be
+        captured, and capture() raises a RuntimeError that names the configuration instead of recording it."""
+        saved = self.state()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        failure = None
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                self.step(x, edge_index, y, mask, n_prefix)
+            mode = torch.cuda.get_sync_debug_mode()
+            torch.cuda.set_sync_debug_mode("error")
+            try:
+                self.step(x, edge_index, y, mask, n_prefix)
+            except RuntimeError as e:
+                if "synchroniz" not in str(e):        # torch's sync-debug message; any other error is the caller's to see
+                    raise
+                failure = e
+            finally:
+                torch.cuda.set_sync_debug_mode(mode)
+        torch.cuda.current_stream().wait_stream(side)
+        self.load_state(saved)
+        for p in self.params:
+            p.grad = None
+        if failure is not None:
+            raise RuntimeError(f"NodeTrainer.capture: the layer path synchronises with {self._configuration()}; "
+                               f"the step is not captured ({failure})") from failure
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            loss = self.step(x, edge_index, y, mask, n_prefix)
 
         def replay():
             graph.replay()
