@@ -223,14 +223,12 @@ class GCN_PYNQ(torch.nn.Module):
                 values_adj_buffer=None, B_buffer=None, D_buffer=None):
         bufs = (rowPtr_fea_buffer, columnIndex_fea_buffer, values_fea_buffer, rowPtr_adj_buffer,
                 columnIndex_adj_buffer, values_adj_buffer, B_buffer, D_buffer)
-        if acc == 1 and not self.training and not torch.is_grad_enabled() and \
-                getattr(self.conv1.my_ip.register_map, "layer_count", 1) >= 2:
+        if acc == 1 and not self.training and not torch.is_grad_enabled() and self._stack_enabled():
             # layer_count >= 2 (the SGRACE register: layers per hardware call): the whole eval forward in one call
             out = self._forward_stack(x, edge_index, batch)
             if out is not None:
                 return out
-        if acc == 1 and getattr(self, "train_stack", False) and torch.is_grad_enabled() and \
-                getattr(self.conv1.my_ip.register_map, "layer_count", 1) >= 2:
+        if acc == 1 and getattr(self, "train_stack", False) and torch.is_grad_enabled() and self._stack_enabled():
             # the training step's GCN part as one forward and one backward call
             pooled = self._train_stack(x, edge_index, batch)
             if pooled is not None:
@@ -277,28 +275,43 @@ class GCN_PYNQ(torch.nn.Module):
             return None
         return ops.ReadoutMean.apply(h, ptr, batch.numel() == h.shape[0])
 
-    def _forward_stack(self, x, edge_index, batch):
-        """Both layers, the mean pool and the head through ops.gcn_stack_forward: bit-equal to the layer-by-layer
-        eval forward below, one launch for a batch of small graphs.  None (the caller then runs the layers one by one)
-        when `batch` is not sorted or an edge joins two of its graphs."""
+    def _stack_enabled(self):
+        """The register layer_count (the SGRACE register: layers per hardware call) asks for both layers in one call."""
+        return getattr(self.conv1.my_ip.register_map, "layer_count", 1) >= 2
+
+    def _stack_operands(self, x, edge_index, batch, backward):
+        """What both stack routes need of a batch: (graph_ptr, the cached adjacency, the plan -- an SGX_BATCH_BACKWARD one
+        that fits with `backward`, else the forward plan), or None when `batch` is not sorted, an edge joins two of its
+        graphs or, with `backward`, a graph is over the plan's row budget or a width over its limit."""
         ptr = ops.graph_ptr_of(batch)
         if ptr is None:
             return None
         adj = ops.cached_on(edge_index, ("adj_csr", x.shape[0], ACC_DTYPE),
                             lambda: ops.csr_from_edge_index(edge_index, x.shape[0], dtype=ACC_DTYPE))
-        weights = [torch.transpose(c.weight, 0, 1).detach().to(ACC_DTYPE).contiguous() for c in (self.conv1, self.conv2)]
-        plan = ops.BatchPlan.cached(adj, ptr, max(self.conv1.out_features, self.conv2.in_features,
-                                                  self.conv2.out_features))
-        if plan is None:
+        width = max(self.conv1.out_features, self.conv2.in_features, self.conv2.out_features)
+        if backward and width > 256:
             return None
+        plan = ops.BatchPlan.cached(adj, ptr, width, ops._lib.SGX_BATCH_BACKWARD if backward else ops._lib.SGX_BATCH_FORWARD)
+        if plan is None or (backward and not plan.fits):
+            return None
+        return ptr, adj, plan
+
+    def _forward_stack(self, x, edge_index, batch):
+        """Both layers, the mean pool and the head through ops.gcn_stack_forward: bit-equal to the layer-by-layer
+        eval forward below, one launch for a batch of small graphs.  None (the caller then runs the layers one by one)
+        when `batch` is not sorted or an edge joins two of its graphs."""
+        ready = self._stack_operands(x, edge_index, batch, backward=False)
+        if ready is None:
+            return None
+        ptr, adj, plan = ready
+        weights = [torch.transpose(c.weight, 0, 1).detach().to(ACC_DTYPE).contiguous() for c in (self.conv1, self.conv2)]
         return ops.gcn_stack_forward(adj, feature_csr(x, ACC_DTYPE), weights, [True, False], ptr, self.lin.weight,
                                      self.lin.bias, plan=plan)
 
     def train_pooled(self, x, edge_index, batch):
         """The fused training route on its own, for a caller that runs the tail itself (train.StackTrainer): the pooled
         means behind ops.GcnStack where forward(acc = 1, ...) would take that route, None where it would not."""
-        if not (getattr(self, "train_stack", False) and torch.is_grad_enabled() and
-                getattr(self.conv1.my_ip.register_map, "layer_count", 1) >= 2):
+        if not (getattr(self, "train_stack", False) and torch.is_grad_enabled() and self._stack_enabled()):
             return None
         return self._train_stack(x, edge_index, batch)
 
@@ -307,18 +320,9 @@ class GCN_PYNQ(torch.nn.Module):
         means [G, hidden] fp32, bit-equal to the layer-by-layer forward.  None (the caller then runs the layers one by
         one) when x needs a gradient, `batch` is not sorted, an edge joins two of its graphs, a graph is over the
         backward plan's row budget or a width is over its limit."""
-        if x.requires_grad:
+        ready = None if x.requires_grad else self._stack_operands(x, edge_index, batch, backward=True)
+        if ready is None:
             return None
-        ptr = ops.graph_ptr_of(batch)
-        if ptr is None:
-            return None
-        adj = ops.cached_on(edge_index, ("adj_csr", x.shape[0], ACC_DTYPE),
-                            lambda: ops.csr_from_edge_index(edge_index, x.shape[0], dtype=ACC_DTYPE))
-        width = max(self.conv1.out_features, self.conv2.in_features, self.conv2.out_features)
-        if width > 256:
-            return None
-        plan = ops.BatchPlan.cached(adj, ptr, width, ops._lib.SGX_BATCH_BACKWARD)
-        if plan is None or not plan.fits:
-            return None
+        ptr, adj, plan = ready
         return ops.GcnStack.apply(adj, feature_csr(x, ACC_DTYPE), ptr, plan, (True, False), self.conv1.weight,
                                   self.conv2.weight)

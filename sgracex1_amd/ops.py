@@ -1680,18 +1680,53 @@ def quant_stack_forward(adj, x, weights_t, attentions, relus, graph_ptr, quants,
                           None, attentions=list(attentions), alpha=alpha, quants=list(quants), adj_quantised=adj_quantised)
 
 
+def _stack_desc(d, adj, x, graph_ptr, n):
+    """What the six stack descriptors share (struct sgx_stack_desc ... sgx_quant_stack_grad_desc), filled into d: the
+    element type, the counts, graph_ptr, the adjacency and the features, sparse (a Csr: layer 0 reads it) or dense.
+    -> (sparse, k_in: the width layer 0 reads).  Every route's descriptor starts here; a new route adds only its own
+    per-layer fields and outputs, then _stack_call."""
+    dtype, N = adj.val.dtype, adj.n_rows
+    _dev(graph_ptr, "graph_ptr")
+    d.dtype, d.n_layers, d.n_rows, d.n_graphs = dtype_code(dtype), n, N, graph_ptr.numel() - 1
+    d.graph_ptr = graph_ptr.data_ptr()
+    d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
+    if isinstance(x, Csr):
+        if x.val.dtype != dtype or x.n_rows != N:
+            raise ValueError("feature CSR does not match the adjacency")
+        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = x.rowptr.data_ptr(), x.col.data_ptr(), x.val.data_ptr()
+        return True, x.n_cols
+    _dev(x, "x")
+    if x.dtype != dtype or x.dim() != 2 or x.shape[0] != N:
+        raise ValueError(f"dense features must be [{N}, M] {dtype}")
+    d.values_fea = x.data_ptr()
+    return False, x.shape[1]
+
+
+def _stack_call(d, name, adj, graph_ptr, plan, widths, kind):
+    """The last step of every stack route: the plan of `kind` (looked up for the widest of `widths` when the caller gave
+    none), the workspace of entry point `name` and the call, under check."""
+    if plan is None:
+        plan = BatchPlan.cached(adj, graph_ptr, max(widths), kind)
+        if plan is None:
+            check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create" if kind == _lib.SGX_BATCH_FORWARD else "sgx_batch_plan_create_ex")
+    d.plan = plan.handle
+    nbytes = getattr(lib, name.replace("_forward", "") + "_workspace_bytes")(ctypes.byref(d))
+    if nbytes:
+        ws = _workspace(adj.val.device, nbytes)
+        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
+    check(getattr(lib, name)(ctypes.byref(d), _stream()), name)
+
+
 def _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, want_layer_outputs, want_pooled, plan, keep,
                    attentions=None, alpha=0.2, quants=None, adj_quantised=False):
     """The descriptor of sgx_stack_forward (attentions None), sgx_gat_stack_forward or sgx_quant_stack_forward (quants
     given), its workspace and the call."""
     gat = attentions is not None
-    name = "sgx_quant_stack" if quants is not None else "sgx_gat_stack" if gat else "sgx_stack"
+    label = "quant" if quants is not None else "gat" if gat else "gcn"
     n = len(weights_t)
     if not 1 <= n <= 4 or len(relus) != n:
-        label = "quant" if quants is not None else "gat" if gat else "gcn"
         raise ValueError(f"{label}_stack_forward takes 1 to 4 layers and one relu flag per layer")
     dtype = adj.val.dtype
-    code = dtype_code(dtype)
     N, dev = adj.n_rows, adj.val.device
     if adj.n_cols != N:
         raise ValueError("the adjacency must be square")
@@ -1699,24 +1734,9 @@ def _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, 
     if graph_ptr is None:
         graph_ptr = cached_on(adj.rowptr, ("one_graph_ptr",),
                               lambda: torch.tensor([0, N], dtype=torch.int32, device=dev))
-    _dev(graph_ptr, "graph_ptr")
     d = _lib.QuantStackDesc() if quants is not None else _lib.GatStackDesc() if gat else _lib.StackDesc()
-    d.dtype, d.n_layers, d.n_rows, d.n_graphs = code, n, N, graph_ptr.numel() - 1
+    sparse, k_in = _stack_desc(d, adj, x, graph_ptr, n)
     qstructs = []                                                                              # (held until the call returns)
-    d.graph_ptr = graph_ptr.data_ptr()
-    d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
-    sparse = isinstance(x, Csr)
-    if sparse:
-        if x.val.dtype != dtype or x.n_rows != N:
-            raise ValueError("feature CSR does not match the adjacency")
-        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = x.rowptr.data_ptr(), x.col.data_ptr(), x.val.data_ptr()
-        k_in = x.n_cols
-    else:
-        _dev(x, "x")
-        if x.dtype != dtype or x.dim() != 2 or x.shape[0] != N:
-            raise ValueError(f"dense features must be [{N}, M] {dtype}")
-        d.values_fea = x.data_ptr()
-        k_in = x.shape[1]
     outs = []
     widths = []
     for l, (Wt, relu) in enumerate(zip(weights_t, relus)):
@@ -1760,16 +1780,8 @@ def _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, 
         if head_weight is None or want_pooled:
             pooled = torch.empty((G, k_in), dtype=torch.float32, device=dev)
             d.pooled = pooled.data_ptr()
-    if plan is None:
-        plan = BatchPlan.cached(adj, graph_ptr, max(widths))
-        if plan is None:
-            check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create")
-    d.plan = plan.handle
-    nbytes = getattr(lib, name + "_workspace_bytes")(ctypes.byref(d))
-    if nbytes:
-        ws = _workspace(dev, nbytes)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(getattr(lib, name + "_forward")(ctypes.byref(d), _stream()), name + "_forward")
+    _stack_call(d, f"sgx_{'' if label == 'gcn' else label + '_'}stack_forward", adj, graph_ptr, plan, widths,
+                _lib.SGX_BATCH_FORWARD)
     if not readout:
         out = outs[-1]
     elif logits is not None:
@@ -1779,7 +1791,7 @@ def _stack_forward(adj, x, weights_t, relus, graph_ptr, head_weight, head_bias, 
     return (out, outs) if want_layer_outputs else out
 
 
-# ---- the backward of that stack for training (sgx_stack_backward) ----------------------------------------------------
+# ---- the backward of that stack for training (sgx_stack_backward, sgx_gat_stack_backward, sgx_quant_stack_backward) ----
 def gcn_stack_backward(adj, x, weights, relus, graph_ptr, layer_outputs, grad_pooled, plan=None, want_G=False):
     """Weight gradients of the stack sgx_stack_forward ran (include/sgx.h, "training"): one launch over the batch's graphs
     and one reduction.  weights: the fp32 parameters W_l [M_l, P_l] (not transposed); layer_outputs: the forward's D_l
@@ -1787,106 +1799,11 @@ def gcn_stack_backward(adj, x, weights, relus, graph_ptr, layer_outputs, grad_po
     list of dW_l [M_l, P_l] fp32 (and the list of G_l = A . g_l [N, P_l] fp32 with want_G).  plan: an SGX_BATCH_BACKWARD
     BatchPlan (built and cached when None).  Raises SgxError SGX_ERR_UNSUPPORTED where the batch or the widths are
     outside the kernel's limits -- the caller then runs the layers one by one."""
-    n = len(weights)
-    if not 1 <= n <= 4 or len(relus) != n or len(layer_outputs) != n:
-        raise ValueError("gcn_stack_backward takes 1 to 4 layers, one relu flag and one layer output per layer")
-    dtype = adj.val.dtype
-    N, dev = adj.n_rows, adj.val.device
-    _dev(graph_ptr, "graph_ptr")
-    d = _lib.StackGradDesc()
-    d.dtype, d.n_layers, d.n_rows, d.n_graphs = dtype_code(dtype), n, N, graph_ptr.numel() - 1
-    d.graph_ptr = graph_ptr.data_ptr()
-    d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
-    sparse = isinstance(x, Csr)
-    if sparse:
-        if x.val.dtype != dtype or x.n_rows != N:
-            raise ValueError("feature CSR does not match the adjacency")
-        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = x.rowptr.data_ptr(), x.col.data_ptr(), x.val.data_ptr()
-        k_in = x.n_cols
-    else:
-        _dev(x, "x")
-        if x.dtype != dtype or x.dim() != 2 or x.shape[0] != N:
-            raise ValueError(f"dense features must be [{N}, M] {dtype}")
-        d.values_fea = x.data_ptr()
-        k_in = x.shape[1]
-    grads, Gs, keep = [], [], []
-    for l, (W, relu, D) in enumerate(zip(weights, relus, layer_outputs)):
-        W = _dev(W.detach().float().contiguous(), f"weights[{l}]")
-        M, P = W.shape
-        if M != k_in:
-            raise ValueError(f"weights[{l}] must be [{k_in}, P], got {tuple(W.shape)}")
-        L = d.layer[l]
-        L.gemm_mode = 0 if (l == 0 and sparse) else 1
-        L.relu, L.M_fea, L.P_w, L.W = int(bool(relu)), M, P, W.data_ptr()
-        if D is not None:
-            _dev2d(D, f"layer_outputs[{l}]")
-            if D.dtype != dtype or D.shape != (N, P):
-                raise ValueError(f"layer_outputs[{l}] must be [{N}, {P}] {dtype}")
-            L.D, L.ldd = D.data_ptr(), D.stride(0)
-        gW = torch.empty((M, P), dtype=torch.float32, device=dev)
-        L.grad_W = gW.data_ptr()
-        grads.append(gW)
-        if want_G:
-            G = torch.empty((N, P), dtype=torch.float32, device=dev)
-            L.G = G.data_ptr()
-            Gs.append(G)
-        keep.append(W)
-        k_in = P
-    g = _dev(grad_pooled.detach().float().contiguous(), "grad_pooled")
-    if g.shape != (d.n_graphs, k_in):
-        raise ValueError(f"grad_pooled must be [{d.n_graphs}, {k_in}]")
-    d.grad_pooled = g.data_ptr()
-    if plan is None:
-        widths = [w.shape[1] for w in keep] + [w.shape[0] for l, w in enumerate(keep) if l > 0 or not sparse]
-        plan = BatchPlan.cached(adj, graph_ptr, max(widths), _lib.SGX_BATCH_BACKWARD)
-        if plan is None:
-            check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create_ex")
-    d.plan = plan.handle
-    nbytes = lib.sgx_stack_backward_workspace_bytes(ctypes.byref(d))
-    if nbytes:
-        ws = _workspace(dev, nbytes)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(lib.sgx_stack_backward(ctypes.byref(d), _stream()), "sgx_stack_backward")
+    grads, _, Gs, _ = _stack_backward(adj, x, weights, None, relus, graph_ptr, layer_outputs, grad_pooled, 0.2, plan, want_G,
+                                      False)
     return (grads, Gs) if want_G else grads
 
 
-class GcnStack(torch.autograd.Function):
-    """The GCN stack of a training step as two calls: forward = sgx_stack_forward without a head (the pooled fp32 means
-    [G, P_last], the D_l the backward reads saved), backward = sgx_stack_backward (fp32 gradients of the weight
-    parameters, [in, out] as FPYNQ.backward returns them).  No gradient for the features: a feature tensor that needs
-    one is refused.
-
-        pooled = GcnStack.apply(adj, x, graph_ptr, plan, relus, W_0, ..., W_{L-1})
-
-    adj: Csr in the accelerator's dtype; x: Csr or dense features in that dtype; plan: an SGX_BATCH_BACKWARD BatchPlan
-    that fits; W_l: the fp32 parameters [M_l, P_l]."""
-
-    @staticmethod
-    def forward(ctx, adj, x, graph_ptr, plan, relus, *weights):
-        if isinstance(x, torch.Tensor) and x.requires_grad:
-            raise ValueError("GcnStack gives no gradient for the features; x must not require grad")
-        dtype = adj.val.dtype
-        wts = [torch.transpose(w, 0, 1).detach().to(dtype).contiguous() for w in weights]
-        n = len(wts)
-        keep = [l < n - 1 or bool(relus[l]) for l in range(n)]
-        pooled, outs = gcn_stack_forward(adj, x, wts, relus, graph_ptr, want_layer_outputs=True, plan=plan, keep=keep)
-        ctx.adj, ctx.x, ctx.plan, ctx.relus = adj, x, plan, list(relus)
-        ctx.save_for_backward(graph_ptr, *[D for D in outs if D is not None], *weights)
-        ctx.keep = keep
-        return pooled
-
-    @staticmethod
-    def backward(ctx, grad_pooled):
-        saved = ctx.saved_tensors
-        n = len(ctx.relus)
-        graph_ptr, rest = saved[0], list(saved[1:])
-        outs = [rest.pop(0) if k else None for k in ctx.keep]
-        weights = rest
-        grads = gcn_stack_backward(ctx.adj, ctx.x, weights, ctx.relus, graph_ptr, outs, grad_pooled, plan=ctx.plan)
-        return (None, None, None, None, None) + tuple(grads[:n])
-
-
-# ---- the backward of the GAT stack for training (sgx_gat_stack_backward) -----------------------------------------------
 def gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha=0.2, plan=None,
                        want_G=False, want_edge_outputs=False):
     """gcn_stack_backward with a per-layer choice of P in G_l = P . g_l (include/sgx.h, "training the GAT stack"):
@@ -1895,48 +1812,52 @@ def gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outp
     arguments are gcn_stack_backward's.  Returns (dW list, grad_attention list -- [2 * P_l] fp32, None for a GCN layer
     [, G list] [, (E, S) list -- [nnz] fp32 each, None for a GCN layer]).  Raises SgxError SGX_ERR_UNSUPPORTED where the
     batch or the widths are outside the kernel's limits -- the caller then runs the layers one by one."""
-    return _gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha, plan, want_G,
-                               want_edge_outputs)
+    grads, gatts, Gs, edges = _stack_backward(adj, x, weights, list(attentions), relus, graph_ptr, layer_outputs, grad_pooled,
+                                              alpha, plan, want_G, want_edge_outputs)
+    return (grads, gatts) + ((Gs,) if want_G else ()) + ((edges,) if want_edge_outputs else ())
 
 
-def _gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha, plan, want_G,
-                        want_edge_outputs, quants=None, adj_q=None):
-    """The descriptor of sgx_gat_stack_backward or sgx_quant_stack_backward (quants given), its workspace and the call."""
-    name = "sgx_quant_stack_backward" if quants is not None else "sgx_gat_stack_backward"
+def quant_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, quants, alpha=0.2, plan=None,
+                         adj_q=None, want_G=False, want_edge_outputs=False):
+    """gat_stack_backward with a per-layer quantiser (include/sgx.h, "training the quantised stack"): the backward of the
+    stack quant_stack_forward ran, by FPYNQ_GAT.backward's rule under fake quantisation.  quants[l] is layer l's
+    quant.QuantConstants or None.  A quantised GAT layer's attention matrix is the quantised forward's S, formed again in
+    the kernel (X_l, W_l and the attention vector on their grids, H requantised, the mask on the quantised adjacency);
+    everything a gradient multiplies with -- X_l, W_l, Wh, a GCN layer's adjacency -- is unquantised, and deq_factor
+    reaches no gradient.  adj: the UNQUANTISED float32 adjacency; adj_q: adj.quantized(qc), taken as stored for the masks
+    (None: adj's values are quantised as they are read); layer_outputs: the quantised forward's D_l.  Returns what
+    gat_stack_backward returns.  Parity of the quantised layer is unpinned."""
+    grads, gatts, Gs, edges = _stack_backward(adj, x, weights, list(attentions), relus, graph_ptr, layer_outputs, grad_pooled,
+                                              alpha, plan, want_G, want_edge_outputs, quants=list(quants), adj_q=adj_q)
+    return (grads, gatts) + ((Gs,) if want_G else ()) + ((edges,) if want_edge_outputs else ())
+
+
+def _stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha, plan, want_G,
+                    want_edge_outputs, quants=None, adj_q=None):
+    """The descriptor of sgx_stack_backward (attentions None: an sgx_stack_grad_desc, no attention field is touched),
+    sgx_gat_stack_backward or sgx_quant_stack_backward (quants given), its workspace and the call.
+    -> (dW list, grad_attention list, G list, (E, S) list), the last three as far as they were asked for."""
+    label = "quant" if quants is not None else "gat" if attentions is not None else "gcn"
     n = len(weights)
-    if not 1 <= n <= 4 or len(relus) != n or len(layer_outputs) != n or len(attentions) != n or \
-            (quants is not None and len(quants) != n):
-        raise ValueError(f"{'quant' if quants is not None else 'gat'}_stack_backward takes 1 to 4 layers; one attention vector "
-                         "(or None), one relu flag and one layer output per layer"
+    per_layer = [relus, layer_outputs] + [v for v in (attentions, quants) if v is not None]
+    if not 1 <= n <= 4 or any(len(v) != n for v in per_layer):
+        raise ValueError(f"{label}_stack_backward takes 1 to 4 layers; "
+                         + ("one attention vector (or None), " if attentions is not None else "")
+                         + "one relu flag and one layer output per layer"
                          + (", one QuantConstants (or None) per layer" if quants is not None else ""))
     dtype = adj.val.dtype
     N, dev = adj.n_rows, adj.val.device
-    _dev(graph_ptr, "graph_ptr")
-    d = _lib.QuantStackGradDesc() if quants is not None else _lib.GatStackGradDesc()
-    qstructs = []                                                                              # (held until the call returns)
+    d = {"gcn": _lib.StackGradDesc, "gat": _lib.GatStackGradDesc, "quant": _lib.QuantStackGradDesc}[label]()
     if adj_q is not None:
         if quants is None:
             raise ValueError("adj_q goes with quants: gat_stack_backward has no quantised adjacency")
         if adj_q.val.dtype != torch.float32 or adj_q.nnz != adj.nnz or adj_q.n_rows != N:
             raise ValueError("adj_q must be the float32 quantised values on adj's pattern")
         d.values_adj_q = adj_q.val.data_ptr()
-    d.dtype, d.n_layers, d.n_rows, d.n_graphs = dtype_code(dtype), n, N, graph_ptr.numel() - 1
-    d.graph_ptr = graph_ptr.data_ptr()
-    d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
-    sparse = isinstance(x, Csr)
-    if sparse:
-        if x.val.dtype != dtype or x.n_rows != N:
-            raise ValueError("feature CSR does not match the adjacency")
-        d.rowPtr_fea, d.columnIndex_fea, d.values_fea = x.rowptr.data_ptr(), x.col.data_ptr(), x.val.data_ptr()
-        k_in = x.n_cols
-    else:
-        _dev(x, "x")
-        if x.dtype != dtype or x.dim() != 2 or x.shape[0] != N:
-            raise ValueError(f"dense features must be [{N}, M] {dtype}")
-        d.values_fea = x.data_ptr()
-        k_in = x.shape[1]
-    grads, gatts, Gs, edges, keep = [], [], [], [], []
-    for l, (W, att, relu, D) in enumerate(zip(weights, attentions, relus, layer_outputs)):
+    sparse, k_in = _stack_desc(d, adj, x, graph_ptr, n)
+    grads, gatts, Gs, edges, widths = [], [], [], [], []
+    held = []                                                            # (fp32 copies and structs, held until the call returns)
+    for l, (W, att, relu, D) in enumerate(zip(weights, attentions or [None] * n, relus, layer_outputs)):
         W = _dev(W.detach().float().contiguous(), f"weights[{l}]")
         M, P = W.shape
         if M != k_in:
@@ -1963,33 +1884,92 @@ def _gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_out
                 ES = (torch.zeros(adj.nnz, dtype=torch.float32, device=dev), torch.zeros(adj.nnz, dtype=torch.float32, device=dev))
                 L.E, L.S = ES[0].data_ptr(), ES[1].data_ptr()
         if quants is not None and quants[l] is not None:
-            qstructs.append(quants[l].as_struct(nnz_adj=adj.nnz, nnz_fea=x.nnz if (l == 0 and sparse) else 0,
-                                                adj_done=adj_q is not None))
-            L.quant = ctypes.pointer(qstructs[-1])
+            held.append(quants[l].as_struct(nnz_adj=adj.nnz, nnz_fea=x.nnz if (l == 0 and sparse) else 0,
+                                            adj_done=adj_q is not None))
+            L.quant = ctypes.pointer(held[-1])
         gatts.append(ga)
         edges.append(ES)
         if want_G:
             G = torch.empty((N, P), dtype=torch.float32, device=dev)
             L.G = G.data_ptr()
             Gs.append(G)
-        keep.append((W, att))
+        held.append((W, att))
+        widths += [P] if (l == 0 and sparse) else [P, M]
         k_in = P
     g = _dev(grad_pooled.detach().float().contiguous(), "grad_pooled")
     if g.shape != (d.n_graphs, k_in):
         raise ValueError(f"grad_pooled must be [{d.n_graphs}, {k_in}]")
     d.grad_pooled = g.data_ptr()
-    if plan is None:
-        widths = [w.shape[1] for w, _ in keep] + [w.shape[0] for l, (w, _) in enumerate(keep) if l > 0 or not sparse]
-        plan = BatchPlan.cached(adj, graph_ptr, max(widths), _lib.SGX_BATCH_BACKWARD)
-        if plan is None:
-            check(_lib.SGX_ERR_BLOCKS, "sgx_batch_plan_create_ex")
-    d.plan = plan.handle
-    nbytes = getattr(lib, name + "_workspace_bytes")(ctypes.byref(d))
-    if nbytes:
-        ws = _workspace(dev, nbytes)
-        d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
-    check(getattr(lib, name)(ctypes.byref(d), _stream()), name)
-    return (grads, gatts) + ((Gs,) if want_G else ()) + ((edges,) if want_edge_outputs else ())
+    _stack_call(d, f"sgx_{'' if label == 'gcn' else label + '_'}stack_backward", adj, graph_ptr, plan, widths,
+                _lib.SGX_BATCH_BACKWARD)
+    return grads, gatts, Gs, edges
+
+
+# ---- the three stacks as autograd functions ------------------------------------------------------------------------------
+def _stack_fn_forward(ctx, name, n_leading, adj, adj_q, x, graph_ptr, plan, relus, alpha, quants, params):
+    """forward of GcnStack (alpha None: params are the weights), GatStack (quants None) and QuantStack: the stack's forward
+    call without a head, and on ctx what _stack_fn_backward needs.  n_leading: how many arguments precede the parameters."""
+    if isinstance(x, torch.Tensor) and x.requires_grad:
+        raise ValueError(f"{name} gives no gradient for the features; x must not require grad")
+    n = len(relus)
+    gcn = alpha is None
+    if not gcn and (len(params) != 2 * n or (quants is not None and len(quants) != n)):
+        raise ValueError(f"{name} takes one weight" + (" and" if quants is None else ",") + " one attention vector (or None)"
+                         + ("" if quants is None else " and one quantiser (or None)") + " per layer")
+    weights, atts = (params, ()) if gcn else (params[:n], params[n:])
+    dtype = adj.val.dtype
+    wts = [torch.transpose(w, 0, 1).detach().to(dtype).contiguous() for w in weights]
+    ats = [None if a is None else a.detach().to(dtype).reshape(-1).contiguous() for a in atts]
+    if gcn:
+        # the last layer's D is read by the backward only through that layer's ReLU mask
+        keep = [l < len(wts) - 1 or bool(relus[l]) for l in range(len(wts))]
+        pooled, outs = gcn_stack_forward(adj, x, wts, relus, graph_ptr, want_layer_outputs=True, plan=plan, keep=keep)
+    elif quants is None:
+        pooled, outs = gat_stack_forward(adj, x, wts, ats, relus, graph_ptr, alpha=alpha, want_layer_outputs=True, plan=plan)
+    else:
+        pooled, outs = quant_stack_forward(adj if adj_q is None else adj_q, x, wts, ats, relus, graph_ptr, list(quants),
+                                           alpha=alpha, plan=plan, adj_quantised=adj_q is not None, want_layer_outputs=True)
+    ctx.stack = (n_leading, adj, adj_q, x, plan, list(relus), alpha, None if quants is None else list(quants))
+    ctx.kept, ctx.gat = [D is not None for D in outs], [a is not None for a in atts]
+    ctx.save_for_backward(graph_ptr, *[D for D in outs if D is not None], *weights, *[a for a in atts if a is not None])
+    return pooled
+
+
+def _stack_fn_backward(ctx, grad_pooled):
+    """backward of the three: the stack's backward call on what forward saved -> one None per leading argument, then the
+    fp32 gradients of the weights and of the attention vectors in their parameters' shapes."""
+    n_leading, adj, adj_q, x, plan, relus, alpha, quants = ctx.stack
+    graph_ptr, *rest = ctx.saved_tensors
+    outs = [rest.pop(0) if k else None for k in ctx.kept]
+    weights = [rest.pop(0) for _ in ctx.kept]
+    atts = [rest.pop(0) if g else None for g in ctx.gat]
+    if alpha is None:
+        dW, dA = gcn_stack_backward(adj, x, weights, relus, graph_ptr, outs, grad_pooled, plan=plan), ()
+    elif quants is None:
+        dW, dA = gat_stack_backward(adj, x, weights, atts, relus, graph_ptr, outs, grad_pooled, alpha=alpha, plan=plan)
+    else:
+        dW, dA = quant_stack_backward(adj, x, weights, atts, relus, graph_ptr, outs, grad_pooled, quants, alpha=alpha, plan=plan,
+                                      adj_q=adj_q)
+    dA = [None if g is None else g.reshape(a.shape) for g, a in zip(dA, atts)]
+    return (None,) * n_leading + tuple(dW) + tuple(dA)
+
+
+class GcnStack(torch.autograd.Function):
+    """The GCN stack of a training step as two calls: forward = sgx_stack_forward without a head (the pooled fp32 means
+    [G, P_last], the D_l the backward reads saved), backward = sgx_stack_backward (fp32 gradients of the weight
+    parameters, [in, out] as FPYNQ.backward returns them).  No gradient for the features: a feature tensor that needs
+    one is refused.
+
+        pooled = GcnStack.apply(adj, x, graph_ptr, plan, relus, W_0, ..., W_{L-1})
+
+    adj: Csr in the accelerator's dtype; x: Csr or dense features in that dtype; plan: an SGX_BATCH_BACKWARD BatchPlan
+    that fits; W_l: the fp32 parameters [M_l, P_l]."""
+
+    @staticmethod
+    def forward(ctx, adj, x, graph_ptr, plan, relus, *weights):
+        return _stack_fn_forward(ctx, "GcnStack", 5, adj, None, x, graph_ptr, plan, relus, None, None, weights)
+
+    backward = staticmethod(_stack_fn_backward)
 
 
 class GatStack(torch.autograd.Function):
@@ -2004,46 +1984,9 @@ class GatStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, adj, x, graph_ptr, plan, relus, alpha, *params):
-        if isinstance(x, torch.Tensor) and x.requires_grad:
-            raise ValueError("GatStack gives no gradient for the features; x must not require grad")
-        n = len(relus)
-        if len(params) != 2 * n:
-            raise ValueError("GatStack takes one weight and one attention vector (or None) per layer")
-        weights, atts = params[:n], params[n:]
-        dtype = adj.val.dtype
-        wts = [torch.transpose(w, 0, 1).detach().to(dtype).contiguous() for w in weights]
-        ats = [None if a is None else a.detach().to(dtype).reshape(-1).contiguous() for a in atts]
-        pooled, outs = gat_stack_forward(adj, x, wts, ats, relus, graph_ptr, alpha=alpha, want_layer_outputs=True, plan=plan)
-        ctx.adj, ctx.x, ctx.plan, ctx.relus, ctx.alpha = adj, x, plan, list(relus), alpha
-        ctx.gat = [a is not None for a in atts]
-        ctx.save_for_backward(graph_ptr, *outs, *weights, *[a for a in atts if a is not None])
-        return pooled
+        return _stack_fn_forward(ctx, "GatStack", 6, adj, None, x, graph_ptr, plan, relus, alpha, None, params)
 
-    @staticmethod
-    def backward(ctx, grad_pooled):
-        saved = ctx.saved_tensors
-        n = len(ctx.relus)
-        graph_ptr, outs, weights, rest = saved[0], list(saved[1:1 + n]), list(saved[1 + n:1 + 2 * n]), list(saved[1 + 2 * n:])
-        atts = [rest.pop(0) if g else None for g in ctx.gat]
-        dW, dA = gat_stack_backward(ctx.adj, ctx.x, weights, atts, ctx.relus, graph_ptr, outs, grad_pooled, alpha=ctx.alpha,
-                                    plan=ctx.plan)
-        dA = [None if g is None else g.reshape(a.shape) for g, a in zip(dA, atts)]
-        return (None,) * 6 + tuple(dW) + tuple(dA)
-
-
-# ---- the backward of the quantised stack for training (sgx_quant_stack_backward) ---------------------------------------
-def quant_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, quants, alpha=0.2, plan=None,
-                         adj_q=None, want_G=False, want_edge_outputs=False):
-    """gat_stack_backward with a per-layer quantiser (include/sgx.h, "training the quantised stack"): the backward of the
-    stack quant_stack_forward ran, by FPYNQ_GAT.backward's rule under fake quantisation.  quants[l] is layer l's
-    quant.QuantConstants or None.  A quantised GAT layer's attention matrix is the quantised forward's S, formed again in
-    the kernel (X_l, W_l and the attention vector on their grids, H requantised, the mask on the quantised adjacency);
-    everything a gradient multiplies with -- X_l, W_l, Wh, a GCN layer's adjacency -- is unquantised, and deq_factor
-    reaches no gradient.  adj: the UNQUANTISED float32 adjacency; adj_q: adj.quantized(qc), taken as stored for the masks
-    (None: adj's values are quantised as they are read); layer_outputs: the quantised forward's D_l.  Returns what
-    gat_stack_backward returns.  Parity of the quantised layer is unpinned."""
-    return _gat_stack_backward(adj, x, weights, attentions, relus, graph_ptr, layer_outputs, grad_pooled, alpha, plan, want_G,
-                               want_edge_outputs, quants=list(quants), adj_q=adj_q)
+    backward = staticmethod(_stack_fn_backward)
 
 
 class QuantStack(torch.autograd.Function):
@@ -2058,75 +2001,84 @@ class QuantStack(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, adj, adj_q, x, graph_ptr, plan, relus, alpha, quants, *params):
-        if isinstance(x, torch.Tensor) and x.requires_grad:
-            raise ValueError("QuantStack gives no gradient for the features; x must not require grad")
-        n = len(relus)
-        if len(params) != 2 * n or len(quants) != n:
-            raise ValueError("QuantStack takes one weight, one attention vector (or None) and one quantiser (or None) per layer")
-        weights, atts = params[:n], params[n:]
-        dtype = adj.val.dtype
-        wts = [torch.transpose(w, 0, 1).detach().to(dtype).contiguous() for w in weights]
-        ats = [None if a is None else a.detach().to(dtype).reshape(-1).contiguous() for a in atts]
-        pooled, outs = quant_stack_forward(adj if adj_q is None else adj_q, x, wts, ats, relus, graph_ptr, list(quants),
-                                           alpha=alpha, plan=plan, adj_quantised=adj_q is not None, want_layer_outputs=True)
-        ctx.adj, ctx.adj_q, ctx.x, ctx.plan, ctx.relus, ctx.alpha = adj, adj_q, x, plan, list(relus), alpha
-        ctx.quants = list(quants)
-        ctx.gat = [a is not None for a in atts]
-        ctx.save_for_backward(graph_ptr, *outs, *weights, *[a for a in atts if a is not None])
-        return pooled
+        return _stack_fn_forward(ctx, "QuantStack", 8, adj, adj_q, x, graph_ptr, plan, relus, alpha, quants, params)
 
-    @staticmethod
-    def backward(ctx, grad_pooled):
-        saved = ctx.saved_tensors
-        n = len(ctx.relus)
-        graph_ptr, outs, weights, rest = saved[0], list(saved[1:1 + n]), list(saved[1 + n:1 + 2 * n]), list(saved[1 + 2 * n:])
-        atts = [rest.pop(0) if g else None for g in ctx.gat]
-        dW, dA = quant_stack_backward(ctx.adj, ctx.x, weights, atts, ctx.relus, graph_ptr, outs, grad_pooled, ctx.quants,
-                                      alpha=ctx.alpha, plan=ctx.plan, adj_q=ctx.adj_q)
-        dA = [None if g is None else g.reshape(a.shape) for g, a in zip(dA, atts)]
-        return (None,) * 8 + tuple(dW) + tuple(dA)
+    backward = staticmethod(_stack_fn_backward)
 
 
 # ---- the tail of a training step: the loss head and the optimiser (sgx_head_loss, sgx_adam_step) ----------------------------
+def _loss_operands(fn, rows_name, rows, weight, bias, target, step_dev):
+    """The operand check head_loss and node_loss share -> (rows, weight, bias) detached: float32 tensors on the device,
+    int64 targets, rows [n, P] against weight [C, P], bias [C] and target [n]; step_dev a device int64 tensor or None."""
+    rows = _dev(rows.detach(), rows_name)
+    w = _dev(weight.detach(), "weight")
+    b = None if bias is None else _dev(bias.detach(), "bias")
+    _dev(target, "target")
+    if rows.dtype != torch.float32 or w.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
+        raise TypeError(f"{fn} works on float32 tensors")
+    if target.dtype != torch.int64:
+        raise TypeError(f"{fn} takes int64 targets")
+    if rows.dim() != 2 or w.dim() != 2 or w.shape[1] != rows.shape[1] or target.shape != (rows.shape[0],) or \
+            (b is not None and b.shape != (w.shape[0],)):
+        n = "G" if fn == "head_loss" else "n"
+        raise ValueError(f"{fn} takes {rows_name} [{n}, P], weight [C, P], bias [C], target [{n}]")
+    if step_dev is not None:
+        _dev(step_dev, "step_dev")
+        if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
+            raise TypeError("step_dev must be a device int64 tensor")
+    return rows, w, b
+
+
+def _loss_outputs(rows, w, b, grads, want_logits):
+    """(loss [1], grad_rows, grad_W, grad_bias, logits) of a loss head over `rows`: fp32 buffers for the call to fill, None
+    for what was not asked for."""
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=rows.device)
+    C = w.shape[0]
+    return (f32(1), f32(*rows.shape) if grads else None, f32(*w.shape) if grads else None,
+            f32(C) if grads and b is not None else None, f32(rows.shape[0], C) if want_logits else None)
+
+
+def _u64(v):
+    return int(v) & (2 ** 64 - 1)
+
+
 def head_loss(pooled, weight, bias, target, p=0.0, seed=0, step=0, step_dev=None, grad_scale=1.0, want_logits=False):
     """Dropout(p), the Linear head and the mean cross entropy with every gradient, in one call (sgx_head_loss; the rule is
     in include/sgx.h, "the loss head").  pooled [G, P] fp32, weight [C, P] fp32, bias [C] fp32 or None, target [G] int64;
     the dropout mask is a fixed function of (seed, step + step_dev[0], element); step_dev: a device int64 tensor (the
     optimiser's counter) or None.  Returns (loss [1], grad_pooled [G, P], grad_W [C, P], grad_bias [C] or None), and the
     logits [G, C] behind them with want_logits.  Never synchronises."""
-    pooled = _dev(pooled.detach(), "pooled")
-    w = _dev(weight.detach(), "weight")
-    b = None if bias is None else _dev(bias.detach(), "bias")
-    _dev(target, "target")
-    if pooled.dtype != torch.float32 or w.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
-        raise TypeError("head_loss works on float32 tensors")
-    if target.dtype != torch.int64:
-        raise TypeError("head_loss takes int64 targets")
-    if pooled.dim() != 2 or w.dim() != 2 or w.shape[1] != pooled.shape[1] or target.shape != (pooled.shape[0],) or \
-            (b is not None and b.shape != (w.shape[0],)):
-        raise ValueError("head_loss takes pooled [G, P], weight [C, P], bias [C], target [G]")
-    if step_dev is not None:
-        _dev(step_dev, "step_dev")
-        if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
-            raise TypeError("step_dev must be a device int64 tensor")
-    G, P = pooled.shape
-    C, dev = w.shape[0], pooled.device
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    grad_pooled = torch.empty((G, P), dtype=torch.float32, device=dev)
-    grad_W = torch.empty((C, P), dtype=torch.float32, device=dev)
-    grad_b = None if b is None else torch.empty(C, dtype=torch.float32, device=dev)
-    logits = torch.empty((G, C), dtype=torch.float32, device=dev) if want_logits else None
+    pooled, w, b = _loss_operands("head_loss", "pooled", pooled, weight, bias, target, step_dev)
+    (G, P), C = pooled.shape, w.shape[0]
+    loss, grad_pooled, grad_W, grad_b, logits = _loss_outputs(pooled, w, b, True, want_logits)
     nbytes = lib.sgx_head_loss_workspace_bytes(G, P, C)
-    ws = _workspace(dev, nbytes) if nbytes else None
-    check(lib.sgx_head_loss(G, P, C, _ptr(pooled), _ptr(w), _ptr(b), _ptr(target), float(p), int(seed) & (2 ** 64 - 1),
-                            int(step) & (2 ** 64 - 1), _ptr(step_dev), float(grad_scale), _ptr(loss), _ptr(logits),
-                            _ptr(grad_pooled), _ptr(grad_W), _ptr(grad_b), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+    ws = _workspace(pooled.device, nbytes) if nbytes else None
+    check(lib.sgx_head_loss(G, P, C, _ptr(pooled), _ptr(w), _ptr(b), _ptr(target), float(p), _u64(seed), _u64(step),
+                            _ptr(step_dev), float(grad_scale), _ptr(loss), _ptr(logits), _ptr(grad_pooled), _ptr(grad_W),
+                            _ptr(grad_b), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
           "sgx_head_loss")
     out = (loss, grad_pooled, grad_W, grad_b)
     return out + (logits,) if want_logits else out
 
 
-class HeadLoss(torch.autograd.Function):
+class _LossFn(torch.autograd.Function):
+    """What HeadLoss and NodeLoss share: forward (_run) makes the one call with grad_scale 1 and keeps its gradients,
+    backward hands them on times grad_output; no other argument has a gradient."""
+
+    @staticmethod
+    def _run(ctx, call, *args):
+        loss, gx, gw, gb = call(*args)
+        ctx.save_for_backward(gx, gw, *([] if gb is None else [gb]))
+        ctx.n_rest = len(args) - 3
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        gx, gw, *gb = ctx.saved_tensors
+        return (gx * grad_output, gw * grad_output, gb[0] * grad_output if gb else None) + (None,) * ctx.n_rest
+
+
+class HeadLoss(_LossFn):
     """head_loss inside an ordinary autograd loop: forward runs the one call (with grad_scale 1) and keeps its gradients,
     backward hands them on times grad_output.
 
@@ -2134,14 +2086,7 @@ class HeadLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, pooled, weight, bias, target, p=0.0, seed=0, step=0, step_dev=None):
-        loss, gp, gw, gb = head_loss(pooled, weight, bias, target, p, seed, step, step_dev)
-        ctx.save_for_backward(gp, gw, *([] if gb is None else [gb]))
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        gp, gw, *gb = ctx.saved_tensors
-        return (gp * grad_output, gw * grad_output, gb[0] * grad_output if gb else None, None, None, None, None, None)
+        return _LossFn._run(ctx, head_loss, pooled, weight, bias, target, p, seed, step, step_dev)
 
 
 def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0,
@@ -2200,42 +2145,22 @@ def node_loss(H, weight, bias, target, mask=None, n_prefix=None, p=0.0, seed=0, 
     (loss [1], grad_H [n, P], grad_W [C, P], grad_bias [C] or None) -- the three gradients None with grads=False, the
     evaluation mode -- then counts (int64 [2]: selected rows, arg-max hits among them) with want_counts and the logits
     [n, C] of every row with want_logits.  Never synchronises."""
-    H = _dev(H.detach(), "H")
-    w = _dev(weight.detach(), "weight")
-    b = None if bias is None else _dev(bias.detach(), "bias")
-    _dev(target, "target")
-    if H.dtype != torch.float32 or w.dtype != torch.float32 or (b is not None and b.dtype != torch.float32):
-        raise TypeError("node_loss works on float32 tensors")
-    if target.dtype != torch.int64:
-        raise TypeError("node_loss takes int64 targets")
-    if H.dim() != 2 or w.dim() != 2 or w.shape[1] != H.shape[1] or target.shape != (H.shape[0],) or \
-            (b is not None and b.shape != (w.shape[0],)):
-        raise ValueError("node_loss takes H [n, P], weight [C, P], bias [C], target [n]")
-    n, P = H.shape
-    C, dev = w.shape[0], H.device
+    H, w, b = _loss_operands("node_loss", "H", H, weight, bias, target, step_dev)
+    (n, P), C = H.shape, w.shape[0]
     if mask is not None:
         _dev(mask, "mask")
         if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != (n,):
             raise TypeError("mask must be a bool or uint8 tensor [n]")
         if mask.dtype == torch.bool:
             mask = mask.view(torch.uint8)
-    if step_dev is not None:
-        _dev(step_dev, "step_dev")
-        if step_dev.dtype != torch.int64 or step_dev.numel() < 1:
-            raise TypeError("step_dev must be a device int64 tensor")
     n_prefix = n if n_prefix is None else int(n_prefix)
-    loss = torch.empty(1, dtype=torch.float32, device=dev)
-    grad_H = torch.empty((n, P), dtype=torch.float32, device=dev) if grads else None
-    grad_W = torch.empty((C, P), dtype=torch.float32, device=dev) if grads else None
-    grad_b = torch.empty(C, dtype=torch.float32, device=dev) if grads and b is not None else None
-    counts = torch.empty(2, dtype=torch.int64, device=dev) if want_counts else None
-    logits = torch.empty((n, C), dtype=torch.float32, device=dev) if want_logits else None
+    loss, grad_H, grad_W, grad_b, logits = _loss_outputs(H, w, b, grads, want_logits)
+    counts = torch.empty(2, dtype=torch.int64, device=H.device) if want_counts else None
     nbytes = lib.sgx_node_loss_workspace_bytes(n, P, C)
-    ws = _workspace(dev, nbytes) if nbytes else None
-    check(lib.sgx_node_loss(n, n_prefix, P, C, _ptr(H), _ptr(w), _ptr(b), _ptr(target), _ptr(mask), float(p),
-                            int(seed) & (2 ** 64 - 1), int(step) & (2 ** 64 - 1), _ptr(step_dev), float(grad_scale), _ptr(loss),
-                            _ptr(counts), _ptr(logits), _ptr(grad_H), _ptr(grad_W), _ptr(grad_b), _ptr(ws),
-                            0 if ws is None else ws.numel(), _stream()),
+    ws = _workspace(H.device, nbytes) if nbytes else None
+    check(lib.sgx_node_loss(n, n_prefix, P, C, _ptr(H), _ptr(w), _ptr(b), _ptr(target), _ptr(mask), float(p), _u64(seed),
+                            _u64(step), _ptr(step_dev), float(grad_scale), _ptr(loss), _ptr(counts), _ptr(logits), _ptr(grad_H),
+                            _ptr(grad_W), _ptr(grad_b), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
           "sgx_node_loss")
     out = (loss, grad_H, grad_W, grad_b)
     if want_counts:
@@ -2243,7 +2168,7 @@ def node_loss(H, weight, bias, target, mask=None, n_prefix=None, p=0.0, seed=0, 
     return out + (logits,) if want_logits else out
 
 
-class NodeLoss(torch.autograd.Function):
+class NodeLoss(_LossFn):
     """node_loss inside an ordinary autograd loop: forward runs the one call (with grad_scale 1) and keeps its gradients,
     backward hands them on times grad_output.
 
@@ -2251,11 +2176,4 @@ class NodeLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, H, weight, bias, target, mask=None, n_prefix=None, p=0.0, seed=0, step=0, step_dev=None):
-        loss, gh, gw, gb = node_loss(H, weight, bias, target, mask, n_prefix, p, seed, step, step_dev)
-        ctx.save_for_backward(gh, gw, *([] if gb is None else [gb]))
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, grad_output):
-        gh, gw, *gb = ctx.saved_tensors
-        return (gh * grad_output, gw * grad_output, gb[0] * grad_output if gb else None) + (None,) * 7
+        return _LossFn._run(ctx, node_loss, H, weight, bias, target, mask, n_prefix, p, seed, step, step_dev)

@@ -448,23 +448,25 @@ class GAT_POOL_PYNQ(Module):
 
         return ops.cached_on(edge_index, ("sym_norm2", x.size(0), config.acc, _torch_dtype()), normalise)
 
+    @staticmethod
+    def _stack_enabled():
+        """The kernels are on and the register layer_count asks for both layers in one call."""
+        return config.acc == 1 and my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2
+
     def train_pooled(self, x, edge_index, batch):
         """The fused training route on its own, for a caller that runs the tail itself (train.StackTrainer): the pooled
         means behind ops.GatStack / ops.QuantStack where forward would take that route, None where it would not."""
-        if not (config.acc == 1 and getattr(self, "train_stack", False) and torch.is_grad_enabled() and
-                my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2):
+        if not (self._stack_enabled() and getattr(self, "train_stack", False) and torch.is_grad_enabled()):
             return None
         return self._train_stack(x, self._normalised(x, edge_index)[2], batch)
 
     def forward(self, x, edge_index, batch):
         ei, norm, adj = self._normalised(x, edge_index)
-        if config.acc == 1 and not self.training and not torch.is_grad_enabled() and \
-                my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2:
+        if self._stack_enabled() and not self.training and not torch.is_grad_enabled():
             out = self._forward_stack(x, adj, batch)
             if out is not None:
                 return out
-        if config.acc == 1 and getattr(self, "train_stack", False) and torch.is_grad_enabled() and \
-                my_ip is not None and getattr(my_ip.register_map, "layer_count", 1) >= 2:
+        if self._stack_enabled() and getattr(self, "train_stack", False) and torch.is_grad_enabled():
             # the training step's two layers and the pooling as one forward and one backward call
             pooled = self._train_stack(x, adj, batch)
             if pooled is not None:
@@ -500,10 +502,10 @@ class GAT_POOL_PYNQ(Module):
             return None
         return ops.ReadoutMean.apply(h, ptr, batch.numel() == h.shape[0])
 
-    def _forward_stack(self, x, adj, batch):
-        """Both layers, the mean pool and the head through ops.gat_stack_forward (ops.quant_stack_forward with the
-        quantiser on); None (the caller then runs the layers one by one) where the stack does not compute what they do."""
-        global layern
+    def _stack_operands(self, x, adj, batch, backward):
+        """What both stack routes need of a batch: (graph_ptr, the plan -- an SGX_BATCH_BACKWARD one that fits with
+        `backward`, else the forward plan --, the feature CSR, the adjacency a GAT layer masks with, the two layers'
+        quantisers or None), or None where one of the class docstring's conditions fails."""
         dt = _torch_dtype()
         ptr = ops.graph_ptr_of(batch)
         gat = int(config.compute_attention)
@@ -513,22 +515,33 @@ class GAT_POOL_PYNQ(Module):
             # (no constants, fp16: the layer's own errors; int8 operands: the layer's own form)
             if qc is None or dt != torch.float32 or (config.hardware_quantize and self.att2.weight.shape[0] > 128):
                 return None
-        masked = adj if qc is None else adj.quantized(qc)                  # the adjacency a GAT layer masks with
+        masked = adj if qc is None else adj.quantized(qc)
         if ptr is None or (gat and (self.att1.alpha != self.att2.alpha or masked.has_dead_rows is not False)):
             return None
-        layers = (self.att1, self.att2)
-        plan = ops.BatchPlan.cached(adj, ptr, max(self.att1.weight.shape[1], self.att2.weight.shape[0],
-                                                  self.att2.weight.shape[1]))
-        if plan is None:
+        width = max(self.att1.weight.shape[1], self.att2.weight.shape[0], self.att2.weight.shape[1])
+        if backward and width > 256:
+            return None
+        plan = ops.BatchPlan.cached(adj, ptr, width, ops._lib.SGX_BATCH_BACKWARD if backward else ops._lib.SGX_BATCH_FORWARD)
+        if plan is None or (backward and not plan.fits):
             return None
         fea = ops.cached_on(x, ("fea_csr", dt), lambda: ops.Csr.from_dense(
             x.detach() if x.layout == torch.strided else x.detach().to_dense(), dt))
+        # the constants of the two layer calls (FPYNQ_GAT.forward): `layern` alternates the two sets
+        quants = None if qc is None else (qc.second_layer() if layern == 2 else qc, qc if layern == 2 else qc.second_layer())
+        return ptr, plan, fea, masked, quants
+
+    def _forward_stack(self, x, adj, batch):
+        """Both layers, the mean pool and the head through ops.gat_stack_forward (ops.quant_stack_forward with the
+        quantiser on); None (the caller then runs the layers one by one) where the stack does not compute what they do."""
+        ready = self._stack_operands(x, adj, batch, backward=False)
+        if ready is None:
+            return None
+        ptr, plan, fea, masked, quants = ready
+        dt, gat, layers = _torch_dtype(), int(config.compute_attention), (self.att1, self.att2)
         weights = [c.weight.detach().t().to(dt).contiguous() for c in layers]
         atts = [c.attention.detach().to(dt).reshape(-1).contiguous() if gat else None for c in layers]
-        if qc is not None:
-            # the constants and registers of the two layer calls (FPYNQ_GAT.forward): `layern` alternates the two sets
-            quants = [qc.second_layer() if layern == 2 else qc, qc if layern == 2 else qc.second_layer()]
-            _program_quant_registers(my_ip.register_map, quants[1])
+        if quants is not None:
+            _program_quant_registers(my_ip.register_map, quants[1])                # the registers of the two layer calls
             return ops.quant_stack_forward(masked, fea, weights, atts, [True, False], ptr, quants, self.lin.weight,
                                            self.lin.bias, alpha=self.att1.alpha, plan=plan, adj_quantised=True)
         return ops.gat_stack_forward(adj, fea, weights, atts, [True, False], ptr, self.lin.weight, self.lin.bias,
@@ -538,34 +551,14 @@ class GAT_POOL_PYNQ(Module):
         """Both layers and the mean pool through ops.GatStack (ops.QuantStack with the quantiser on): the pooled means
         [G, hidden] fp32 with the gradients of the weights and the attention vectors behind them.  None (the caller then
         runs the layers one by one) where one of the class docstring's conditions fails."""
-        if x.requires_grad:
+        ready = None if x.requires_grad else self._stack_operands(x, adj, batch, backward=True)
+        if ready is None:
             return None
-        dt = _torch_dtype()
-        ptr = ops.graph_ptr_of(batch)
-        gat = int(config.compute_attention)
-        qc = None
-        if _quantised():
-            qc = quant_constants
-            # (_forward_stack's conditions: no constants, fp16: the layer's own errors; int8 operands: the layer's own form)
-            if qc is None or dt != torch.float32 or (config.hardware_quantize and self.att2.weight.shape[0] > 128):
-                return None
-        masked = adj if qc is None else adj.quantized(qc)                  # the adjacency a GAT layer masks with
-        if ptr is None or (gat and (self.att1.alpha != self.att2.alpha or masked.has_dead_rows is not False)):
-            return None
-        width = max(self.att1.weight.shape[1], self.att2.weight.shape[0], self.att2.weight.shape[1])
-        if width > 256:
-            return None
-        plan = ops.BatchPlan.cached(adj, ptr, width, ops._lib.SGX_BATCH_BACKWARD)
-        if plan is None or not plan.fits:
-            return None
-        fea = ops.cached_on(x, ("fea_csr", dt), lambda: ops.Csr.from_dense(
-            x.detach() if x.layout == torch.strided else x.detach().to_dense(), dt))
+        ptr, plan, fea, masked, quants = ready
         layers = (self.att1, self.att2)
-        atts = [c.attention if gat else None for c in layers]
-        if qc is not None:
-            # the constants and registers of the two layer calls (FPYNQ_GAT.forward): `layern` alternates the two sets
-            quants = (qc.second_layer() if layern == 2 else qc, qc if layern == 2 else qc.second_layer())
-            _program_quant_registers(my_ip.register_map, quants[1])
+        atts = [c.attention if int(config.compute_attention) else None for c in layers]
+        if quants is not None:
+            _program_quant_registers(my_ip.register_map, quants[1])                # the registers of the two layer calls
             return ops.QuantStack.apply(adj, masked, fea, ptr, plan, (True, False), self.att1.alpha, quants,
                                         *[c.weight for c in layers], *atts)
         return ops.GatStack.apply(adj, fea, ptr, plan, (True, False), self.att1.alpha, *[c.weight for c in layers], *atts)

@@ -15,7 +15,73 @@ import torch.nn.functional as F
 from . import ops
 
 
-class StackTrainer:
+class _Trainer:
+    """What the two trainers share: the optimiser state (exp_avg, exp_avg_sq per parameter, the device step counter `t`),
+    its copies, the Adam call that ends a step and the capture of a step.  A trainer adds step(*batch)."""
+
+    def __init__(self, model, lr, betas, eps, weight_decay, p_drop, seed):
+        self.model = model
+        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
+        self.p_drop, self.seed = float(p_drop), int(seed)
+        self.params = [p for p in model.parameters() if p.requires_grad]
+        dev = self.params[0].device
+        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
+        self.t = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.last_grads = None        # the gradients handed to the last ops.adam_step, in self.params' order
+
+    def _adam(self, grads):
+        """One ops.adam_step over self.params with `grads` (None: that parameter is skipped), kept as last_grads."""
+        grads = [None if g is None else g.contiguous() for g in grads]
+        ops.adam_step(self.params, grads, self.exp_avg, self.exp_avg_sq, self.t, lr=self.lr, betas=self.betas, eps=self.eps,
+                      weight_decay=self.weight_decay)
+        self.last_grads = grads
+
+    def state(self):
+        """Copies of everything a step changes: the parameters, both moments, the counter."""
+        return [t.detach().clone() for t in (*self.params, *self.exp_avg, *self.exp_avg_sq, self.t)]
+
+    def load_state(self, state):
+        with torch.no_grad():
+            for dst, src in zip((*self.params, *self.exp_avg, *self.exp_avg_sq, self.t), state):
+                dst.copy_(src)
+
+    def _capture(self, batch, warmup, probe=None, counters=()):
+        """Record self.step(*batch) with torch.cuda.graph (one stream, no parallel branches) and return a callable that
+        replays it and returns the loss tensor the replay fills.  The warm-up steps it needs first (they build what a step
+        caches: the CSRs, the plans, the workspaces) run on a side stream on a copy of the state, which is put back before
+        the capture: the trainer is where it was, and n replays equal n eager steps.  probe: run on the side stream after
+        the warm-up steps; what it returns is raised once the state is back.  counters: the names of host-side counts that
+        the recorded step (which computes nothing until it is replayed) must leave as the warm-up left them."""
+        saved = self.state()
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            for _ in range(max(1, warmup)):
+                self.step(*batch)
+            failure = probe() if probe is not None else None
+        torch.cuda.current_stream().wait_stream(side)
+        self.load_state(saved)
+        for p in self.params:
+            p.grad = None
+        if failure is not None:
+            raise failure
+        kept = [(name, getattr(self, name)) for name in counters]
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            loss = self.step(*batch)
+        for name, value in kept:
+            setattr(self, name, value)
+
+        def replay():
+            graph.replay()
+            return loss
+
+        replay.graph = graph
+        return replay
+
+
+class StackTrainer(_Trainer):
     """Adam on the kernels for GCN_PYNQ(train_stack=True) / GAT_POOL_PYNQ(train_stack=True) (fake quantisation included).
 
         trainer = StackTrainer(model, lr=0.01)
@@ -35,16 +101,8 @@ class StackTrainer:
     def __init__(self, model, lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, p_drop=0.5, seed=12345):
         if not hasattr(model, "train_pooled") or not hasattr(model, "layers_pooled") or not hasattr(model, "lin"):
             raise TypeError("StackTrainer takes a GCN_PYNQ or a GAT_POOL_PYNQ")
-        self.model = model
-        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
-        self.p_drop, self.seed = float(p_drop), int(seed)
-        self.params = [p for p in model.parameters() if p.requires_grad]
-        dev = self.params[0].device
-        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
-        self.t = torch.zeros(1, dtype=torch.int64, device=dev)
+        super().__init__(model, lr, betas, eps, weight_decay, p_drop, seed)
         self.fused_steps = 0          # steps that took the fused route (host-side count; a replay counts nothing)
-        self.last_grads = None        # the gradients handed to the last ops.adam_step, in self.params' order
 
     def _forward(self, x, edge_index, batch):
         from .molecule_gcn import GCN_PYNQ
@@ -73,52 +131,18 @@ class StackTrainer:
                 loss = F.cross_entropy(self._forward(x, edge_index, batch), y)
             loss.backward()
             loss = loss.detach().reshape(1)
-        grads = [head.get(id(p)) if head.get(id(p)) is not None else p.grad for p in self.params]
-        grads = [None if g is None else g.contiguous() for g in grads]
-        ops.adam_step(self.params, grads, self.exp_avg, self.exp_avg_sq, self.t, lr=self.lr, betas=self.betas, eps=self.eps,
-                      weight_decay=self.weight_decay)
-        self.last_grads = grads
+        self._adam([head.get(id(p)) if head.get(id(p)) is not None else p.grad for p in self.params])
         return loss
-
-    def state(self):
-        """Copies of everything a step changes: the parameters, both moments, the counter."""
-        return [t.detach().clone() for t in (*self.params, *self.exp_avg, *self.exp_avg_sq, self.t)]
-
-    def load_state(self, state):
-        with torch.no_grad():
-            for dst, src in zip((*self.params, *self.exp_avg, *self.exp_avg_sq, self.t), state):
-                dst.copy_(src)
 
     def capture(self, x, edge_index, batch, y, warmup=2):
         """Record one step on this batch with torch.cuda.graph (one stream, no parallel branches) and return a callable
         that replays it and returns the loss tensor the replay fills.  The warm-up steps it needs first (they build what
         a step caches: the CSRs, the plan, the workspace) run on a copy of the state, which is put back before the
         capture: the trainer is where it was, and n replays equal n eager steps."""
-        saved = self.state()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self.step(x, edge_index, batch, y)
-        torch.cuda.current_stream().wait_stream(side)
-        self.load_state(saved)
-        for p in self.params:
-            p.grad = None
-        fused = self.fused_steps
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            loss = self.step(x, edge_index, batch, y)
-        self.fused_steps = fused
-
-        def replay():
-            graph.replay()
-            return loss
-
-        replay.graph = graph
-        return replay
+        return self._capture((x, edge_index, batch, y), warmup, counters=("fused_steps",))
 
 
-class NodeTrainer:
+class NodeTrainer(_Trainer):
     """Adam on the kernels for sgrace.GAT_PYNQ, the node classifier of the demo.
 
         trainer = NodeTrainer(model, lr=0.01, weight_decay=5e-4)
@@ -136,15 +160,7 @@ class NodeTrainer:
     def __init__(self, model, lr=0.01, betas=(0.9, 0.999), eps=1e-8, weight_decay=0, p_drop=0.5, seed=12345):
         if not hasattr(model, "features") or not hasattr(model, "lin"):
             raise TypeError("NodeTrainer takes a GAT_PYNQ")
-        self.model = model
-        self.lr, self.betas, self.eps, self.weight_decay = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(weight_decay)
-        self.p_drop, self.seed = float(p_drop), int(seed)
-        self.params = [p for p in model.parameters() if p.requires_grad]
-        dev = self.params[0].device
-        self.exp_avg = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
-        self.exp_avg_sq = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self.params]
-        self.t = torch.zeros(1, dtype=torch.int64, device=dev)
-        self.last_grads = None        # the gradients handed to the last ops.adam_step, in self.params' order
+        super().__init__(model, lr, betas, eps, weight_decay, p_drop, seed)
 
     def step(self, x, edge_index, y, mask=None, n_prefix=None):
         model = self.model
@@ -153,10 +169,7 @@ class NodeTrainer:
         H = model.features(x, edge_index).contiguous()
         loss = ops.NodeLoss.apply(H, model.lin.weight, model.lin.bias, y, mask, n_prefix, self.p_drop, self.seed, 0, self.t)
         loss.backward()
-        grads = [None if p.grad is None else p.grad.contiguous() for p in self.params]
-        ops.adam_step(self.params, grads, self.exp_avg, self.exp_avg_sq, self.t, lr=self.lr, betas=self.betas, eps=self.eps,
-                      weight_decay=self.weight_decay)
-        self.last_grads = grads
+        self._adam([p.grad for p in self.params])
         return loss.detach().reshape(1)
 
     def evaluate(self, x, edge_index, y, mask=None, n_prefix=None):
@@ -174,15 +187,6 @@ class NodeTrainer:
             model.train(was_training)
         return counts, loss
 
-    def state(self):
-        """Copies of everything a step changes: the parameters, both moments, the counter."""
-        return [t.detach().clone() for t in (*self.params, *self.exp_avg, *self.exp_avg_sq, self.t)]
-
-    def load_state(self, state):
-        with torch.no_grad():
-            for dst, src in zip((*self.params, *self.exp_avg, *self.exp_avg_sq, self.t), state):
-                dst.copy_(src)
-
     def _configuration(self):
         from . import config
         return (f"compute_attention={config.compute_attention} accb={config.accb} fake_quantization={config.fake_quantization} "
@@ -195,37 +199,21 @@ class NodeTrainer:
         workspaces) run on a copy of the state, which is put back before the capture: n replays equal n eager steps.  The
         last warm-up step runs under torch.cuda.set_sync_debug_mode("error"): a layer path that synchronises cannot be
         captured, and capture() raises a RuntimeError that names the configuration instead of recording it."""
-        saved = self.state()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        failure = None
-        with torch.cuda.stream(side):
-            for _ in range(max(1, warmup)):
-                self.step(x, edge_index, y, mask, n_prefix)
+        batch = (x, edge_index, y, mask, n_prefix)
+
+        def probe():
             mode = torch.cuda.get_sync_debug_mode()
             torch.cuda.set_sync_debug_mode("error")
             try:
-                self.step(x, edge_index, y, mask, n_prefix)
+                self.step(*batch)
             except RuntimeError as e:
                 if "synchroniz" not in str(e):        # torch's sync-debug message; any other error is the caller's to see
                     raise
-                failure = e
+                failure = RuntimeError(f"NodeTrainer.capture: the layer path synchronises with {self._configuration()}; "
+                                       f"the step is not captured ({e})")
+                failure.__cause__ = e
+                return failure
             finally:
                 torch.cuda.set_sync_debug_mode(mode)
-        torch.cuda.current_stream().wait_stream(side)
-        self.load_state(saved)
-        for p in self.params:
-            p.grad = None
-        if failure is not None:
-            raise RuntimeError(f"NodeTrainer.capture: the layer path synchronises with {self._configuration()}; "
-                               f"the step is not captured ({failure})") from failure
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            loss = self.step(x, edge_index, y, mask, n_prefix)
 
-        def replay():
-            graph.replay()
-            return loss
-
-        replay.graph = graph
-        return replay
+        return self._capture(batch, warmup, probe)

@@ -7,7 +7,11 @@ gives the sizes, then the weights, then grad_pooled, as in the test), with six r
 row budget, a 1-row and an empty graph; then an empty batch and the 20 000 small graphs of that file's
 test_more_groups_than_the_grid: more groups than the backward's 512-wide grid (asserted), so that its workgroups take
 several groups and all but the first add into the slice.
-Run it on each build and diff the outputs: a refactor of the stack's files changes no line."""
+Before those, the Python above the library: train.StackTrainer (GCN and GAT model) and train.NodeTrainer (with a mask) on
+the small fixtures of tests/test_gpu_trainer.py and tests/test_gpu_node_trainer.py, eager and replayed (trainer_lines),
+and ops.GcnStack / GatStack / QuantStack through .apply and backward (autograd_lines).
+Run it on each build and diff the outputs: a refactor of the stack's files, or of the Python that fills their
+descriptors, changes no line."""
 import hashlib
 import json
 import os
@@ -84,8 +88,113 @@ def forms_lines(dtype):
     yield dict({"dtype": NAMES[dtype], "case": "quant", "pooled": sha(pooled)}, **{f"D{l}": sha(o) for l, o in enumerate(outs)})
 
 
+def autograd_lines(dtype):
+    """ops.GcnStack, ops.GatStack and (float32: the quantised layers work on float32 buffers) ops.QuantStack through
+    .apply and pooled.backward(gp) on CASES[0] and CASES[1]: the pooled output, every dW_l and every attention gradient.
+    The quantised line of case 0 has a GCN layer 0 and the adjacency quantised beforehand, that of case 1 quantises it
+    as it is read."""
+    for case in (0, 1):
+        widths, relus, sparse = CASES[case]
+        relus = tuple(bool(r) for r in relus)
+        n = len(relus)
+        seed = 6000 + 10 * case + (dtype == torch.float16)
+        width = max(widths[1:] + (() if sparse else widths[:1]))
+        rng = np.random.default_rng(seed)
+        sizes = sizes_of(rng, _budget(dtype, width), 6)
+        adj, x, ptr = random_batch(seed, dtype, sizes, widths[0], sparse)
+        adj = ops.Csr(adj.rowptr, adj.col, adj.val.abs(), adj.n_rows)     # (an edge is live where its value is positive)
+        plan = ops.BatchPlan.cached(adj, ptr, width, _lib.SGX_BATCH_BACKWARD)
+        assert plan.fits, (case, plan.rows)
+        Ws = [w.requires_grad_(True) for w in weights_of(rng, widths)]
+        atts = [torch.tensor(rng.standard_normal((2 * p, 1)) * 0.3, device=DEV, dtype=torch.float32).requires_grad_(True)
+                for p in widths[1:]]
+        gp = torch.tensor(rng.standard_normal((len(sizes), widths[-1])), device=DEV, dtype=torch.float32)
+        qs = tuple(quant.constants(8) for _ in range(n))
+        forms = [("GcnStack", Ws, lambda: ops.GcnStack.apply(adj, x, ptr, plan, relus, *Ws)),
+                 ("GatStack", Ws + atts, lambda: ops.GatStack.apply(adj, x, ptr, plan, relus, 0.2, *Ws, *atts))]
+        if dtype == torch.float32:
+            q_atts = [None] + atts[1:] if case == 0 else atts
+            adj_q = adj.quantized(qs[0]) if case == 0 else None
+            forms.append(("QuantStack", Ws + [a for a in q_atts if a is not None],
+                          lambda: ops.QuantStack.apply(adj, adj_q, x, ptr, plan, relus, 0.2, qs, *Ws, *q_atts)))
+        for name, params, apply in forms:
+            for p in params:
+                p.grad = None
+            pooled = apply()
+            pooled.backward(gp)
+            torch.cuda.synchronize()
+            rec = {"dtype": NAMES[dtype], "case": f"{name}{case}", "pooled": sha(pooled.detach())}
+            rec.update({f"dW{l}": sha(w.grad) for l, w in enumerate(Ws)})
+            rec.update({f"dA{l}": sha(a.grad) for l, a in enumerate(atts) if any(a is p for p in params)})
+            yield rec
+
+
+def _mutag_models():
+    """The models and the batch of tests/test_gpu_trainer.py: GCN_PYNQ (fp16) and GAT_POOL_PYNQ (fp32, attention) with
+    train_stack on the 188 graphs of MUTAG."""
+    import test_gpu_trainer as T
+    from sgracex1_amd import config, sgrace
+    b = T._mutag()
+    yield "StackTrainer_gcn", T._gcn()[0], (b.x, b.edge_index, b.batch, b.y)
+    saved = config.snapshot()
+    config.acc, config.float_type, config.compute_attention = 1, np.float32, 1
+    sgrace.init_SGRACE().register_map.layer_count = 2
+    try:
+        yield "StackTrainer_gat", T._gat(sgrace)[0], (b.x, b.edge_index, b.batch, b.y)
+    finally:
+        config.restore(saved)
+        sgrace.init_SGRACE()
+
+
+def _node_model():
+    """The model, the 300-node graph and the mask of tests/test_gpu_node_trainer.py's `env`, with the attention aggregate."""
+    import test_gpu_node_trainer as T
+    from sgracex1_amd import config, sgrace
+    saved = config.snapshot()
+    config.acc, config.accb, config.float_type, config.compute_attention = 1, 0, np.float32, 1
+    config.fake_quantization = config.hardware_quantize = 0
+    config.w_qbits, config.gat_edge_outputs, config.device = 32, 1, "cuda"
+    sgrace.init_SGRACE()
+    torch.manual_seed(7)
+    x, ei, y = T._example().planted_partition(300, 5, 200, 0.05, 0.005, 3, torch.device(DEV))
+    mask = torch.zeros(300, dtype=torch.bool, device=DEV)
+    mask[torch.randperm(300, generator=torch.Generator().manual_seed(3)).to(DEV)[:60]] = True
+    try:
+        yield "NodeTrainer_mask", sgrace.GAT_PYNQ(200, 16, 1, 5).to(DEV).train(), (x, ei, y, mask)
+    finally:
+        config.restore(saved)
+        sgrace.init_SGRACE()
+
+
+def trainer_lines():
+    """The three losses, and the parameters and both Adam moments after three eager steps and after three replays of a
+    captured step from the same start (the parameters that receive a gradient: the others are never initialised)."""
+    from sgracex1_amd import train
+    for source, cls in ((_mutag_models, train.StackTrainer), (_node_model, train.NodeTrainer)):
+        for name, model, batch in source():
+            trainer = cls(model, lr=0.01, p_drop=0.5, seed=99)
+            start = trainer.state()
+            for leg in ("eager", "replay"):
+                trainer.load_state(start)
+                torch.manual_seed(5)
+                step = (lambda: trainer.step(*batch)) if leg == "eager" else trainer.capture(*batch)
+                losses = [step().clone() for _ in range(3)]
+                torch.cuda.synchronize()
+                n = len(trainer.params)
+                live = [k for k, g in enumerate(trainer.last_grads) if g is not None]
+                state = trainer.state()
+                rec = {"case": name, "leg": leg, "t": int(state[-1].item()), "loss": [sha(v) for v in losses]}
+                for tag, part in (("param", state[:n]), ("exp_avg", state[n:2 * n]), ("exp_avg_sq", state[2 * n:3 * n])):
+                    rec[tag] = [sha(part[k]) for k in live]
+                yield rec
+
+
 def main():
+    for rec in trainer_lines():
+        print(json.dumps(rec), flush=True)
     for dtype in (torch.float16, torch.float32):
+        for rec in autograd_lines(dtype):
+            print(json.dumps(rec), flush=True)
         for case, (widths, relus, sparse) in enumerate(CASES):
             seed = 200 * case + (dtype == torch.float16)
             width = max(widths[1:] + (() if sparse else widths[:1]))
