@@ -37,8 +37,12 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
     python examples/molecule_gcn_train.py --layer-count 2 --train-stack --trainer [--replay] [--model gat [--qbits 8]]
         --trainer = the tail of every step on the kernels too (train.StackTrainer): dropout, the head, the loss and their
         gradients as one call (sgx_head_loss), Adam over every parameter as one launch (sgx_adam_step), both on a device
-        step counter; the dropout stream is the trainer's counter-based mask, not torch's generator.  --replay (only with
-        --batch-size 0, the single fixed batch) records the whole step once and replays it every epoch.
+        step counter; the dropout stream is the trainer's counter-based mask, not torch's generator.  --replay with
+        --batch-size 0 (the single fixed batch) records the whole step once and replays it every epoch.
+    python examples/molecule_gcn_train.py --batch-size 64 --layer-count 2 --train-stack --trainer --replay [--model gat]
+        --replay on the shuffled batches of the device loader: every full batch arrives padded to one fixed capacity
+        (pyg_lite.GraphLoader(pad=True)), and one recorded step -- collation, plan table, forward, loss head, backward,
+        Adam -- serves every batch of every epoch (StackTrainer.capture_loader); the short last batch runs eagerly
 """
 import argparse
 import json
@@ -77,8 +81,10 @@ def main():
         ap.error("--train-stack needs --layer-count >= 2")
     if args.trainer and not (args.train_stack and args.acc == 1):
         ap.error("--trainer runs the fused training route: --acc 1 --layer-count 2 --train-stack")
-    if args.replay and (not args.trainer or args.batch_size != 0):
-        ap.error("--replay replays the step of one fixed batch: --trainer with --batch-size 0")
+    if args.replay and not args.trainer:
+        ap.error("--replay replays the trainer's step: --trainer")
+    if args.replay and args.batch_size > 0 and (args.host_loader or args.plain_loader or args.qbits != 32):
+        ap.error("--replay with --batch-size > 0 takes the device loader's prepared, unquantised batches")
     if args.host_loader and args.batch_size <= 0:
         ap.error("--host-loader needs --batch-size > 0")
     dev = torch.device("cuda")
@@ -91,7 +97,8 @@ def main():
     if args.batch_size > 0:
         gen = torch.Generator().manual_seed(12345)
         loader = (G.DataLoader(graphs[:2000], batch_size=args.batch_size, shuffle=True, generator=gen) if args.host_loader
-                  else G.GraphLoader(graphs[:2000], batch_size=args.batch_size, shuffle=True, generator=gen, device=dev))
+                  else G.GraphLoader(graphs[:2000], batch_size=args.batch_size, shuffle=True, generator=gen, device=dev,
+                                       pad=args.replay))
     if args.model == "gat":
         from sgracex1_amd import config, sgrace
         config.acc, config.compute_attention = 1, 1
@@ -103,7 +110,8 @@ def main():
         if args.batch_size > 0 and not args.host_loader and not args.plain_loader:
             # the batches layer-ready: normalised (and quantised) once per set, gathered per batch by the collation launch
             loader = G.GraphLoader(loader.graphs, batch_size=args.batch_size, shuffle=True, generator=gen, device=dev,
-                                   dtypes=(sgrace._torch_dtype(),), prepare="sym_norm2", quant=sgrace.quant_constants)
+                                   dtypes=(sgrace._torch_dtype(),), prepare="sym_norm2", quant=sgrace.quant_constants,
+                                   pad=args.replay)
         model = lambda _acc, x, edge_index, batch: gat(x, edge_index, batch)
         model.train, model.eval, model.parameters = gat.train, gat.eval, gat.parameters
     else:
@@ -112,11 +120,14 @@ def main():
         model = M.GCN_PYNQ(64, 7, 2, my_ip, train_stack=args.train_stack).to(dev)   # MOL cell 18 (seed 12345 inside)
     opt = torch.optim.Adam(model.parameters(), lr=0.01)       # MOL cell 20
     crit = torch.nn.CrossEntropyLoss()
-    trainer = replay = None
+    trainer = replay = replay_epoch = None
     if args.trainer:
         from sgracex1_amd.train import StackTrainer
         trainer = StackTrainer(gat if args.model == "gat" else model, lr=0.01)      # the same Adam, the state on the device
-        if args.replay:
+        if args.replay and args.batch_size > 0:
+            model.train()
+            replay_epoch = trainer.capture_loader(loader)      # one recorded step for every padded batch
+        elif args.replay:
             model.train()
             replay = trainer.capture(train.x, train.edge_index, train.batch, train.y)
 
@@ -131,19 +142,23 @@ def main():
         model.train()
         t0 = time.perf_counter()
         steps = 0
-        for b in loader:
-            if args.host_loader:
-                b = b.to(dev)
-            if replay is not None:
-                loss = replay()
-            elif trainer is not None:
-                loss = trainer.step(b.x, b.edge_index, b.batch, b.y)
-            else:
-                opt.zero_grad()
-                loss = crit(model(args.acc, b.x, b.edge_index, b.batch), b.y)
-                loss.backward()
-                opt.step()
-            steps += 1
+        if replay_epoch is not None:
+            losses = replay_epoch()
+            loss, steps = losses[-1], len(losses)
+        else:
+            for b in loader:
+                if args.host_loader:
+                    b = b.to(dev)
+                if replay is not None:
+                    loss = replay()
+                elif trainer is not None:
+                    loss = trainer.step(b.x, b.edge_index, b.batch, b.y, getattr(b, "num_real_graphs", None))
+                else:
+                    opt.zero_grad()
+                    loss = crit(model(args.acc, b.x, b.edge_index, b.batch), b.y)
+                    loss.backward()
+                    opt.step()
+                steps += 1
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / steps
         tr, te = accuracy(train), accuracy(test)

@@ -792,6 +792,66 @@ int sgx_batch_plan_create_known(int dtype, int n_rows, int n_graphs, const int32
  * SGX_ERR_NULL. */
 int64_t sgx_batch_plan_export_groups(const sgx_batch_plan *plan, int32_t *dst, int64_t capacity, void *stream);
 
+/* ---- padded batches: every full batch of a loader in buffers of one fixed capacity ---------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * A shuffled batch has its own row, edge and entry counts, and those are launch arguments of everything behind the
+ * collator, so a recorded step fits one batch.  A PADDED batch has the counts of a capacity the host computes once per
+ * (set, B), the spare rows held by well-defined filler graphs; one recorded step then serves every batch of B graphs.
+ *
+ * Capacity, from the set's per-graph counts:
+ *   N         the sum of the B largest row counts (or a row count the caller chooses);
+ *   n_min     the sum of the B smallest row counts;  R_f  the largest row count of the set;
+ *   F         ceil((N - n_min) / R_f) filler graphs;  G = B + F;
+ *   E_cap, fea_cap   the sums of the B largest stored-edge and feature-entry counts;
+ *   adj_cap   the sum of the B largest adjacency-entry counts plus N - n_min; an extra's capacity likewise.
+ * A batch fits when it has exactly B graphs and its row total n <= N; with the default N every batch of B graphs fits.
+ *
+ * A padded batch holds its B graphs exactly as sgx_collate_graphs[_extras] writes them, in the live prefix of every
+ * array, and behind them P = N - n filler rows in F trailing filler graphs (a the batch's adjacency entries, f its
+ * feature entries, E its stored edges):
+ *   filler graphs   graph B + k holds clamp(P - k R_f, 0, R_f) rows: graph_ptr[B + k + 1] = n + min(P, (k + 1) R_f);
+ *                   the empty ones trail at N (the batch plan's last group takes them, and they pool to 0);
+ *                   y[B + k] = 0;
+ *   filler row n+j  batch[n + j] = B + j / R_f; its x row is 0; its feature row is empty (rowPtr_fea[n + j] = f); its
+ *                   adjacency row holds one diagonal entry of value 1 in each dtype: rowPtr_adj[n + j] = a + j,
+ *                   columnIndex_adj[a + j] = n + j, rowPtr_adj[N] = a + P.  The same in every extra, whose row byte is
+ *                   0: a GAT row is never dead.  Every filler row's D is 0 in every layer and its gradient is 0;
+ *   tails           the entries past the live count up to the capacity are 0, and edge_index[:, E:E_cap] = -1 (the
+ *                   padded edge_index is a key, not an edge list, past E).
+ * An extra without a pattern of its own (values only: the quantised adjacencies) is refused: SGX_ERR_UNSUPPORTED.
+ *
+ * sgx_collate_graphs_padded(set, b, extras, n_extras, pad, stream): b->n_graphs = B, and the totals of b and the nnz
+ * of the extras are not read -- pad's capacities take their place, as the sizes of the output arrays (graph_ptr
+ * [G + 1], y [G]) and as the totals every range is tested against.  The live totals are read on the device from
+ * node_off[B], edge_off[B], adj_off[B], fea_off[B] and entry_off[B], so they are no launch arguments.  A graph id
+ * outside the set, or a graph whose ranges do not fit the capacities, is skipped as a whole; whatever the offsets
+ * hold, nothing is written outside [0, capacity) of any array.  One launch: a wavefront per graph as before, and
+ * further workgroups that write the filler rows and the tails with coalesced stores, 16 bytes a lane over the
+ * constant ranges.  No allocation, no synchronisation, no atomics; capturable; the same bits on every run.
+ *
+ * Argument errors: those of sgx_collate_graphs_extras (with the capacities for the totals), pad NULL: SGX_ERR_NULL;
+ * G < B, R_f < 0, G R_f < N, a pattern capacity below N - B R_f (what every batch leaves to the fillers) or an entry
+ * capacity over INT32_MAX: SGX_ERR_SHAPE. */
+typedef struct sgx_collate_pad {
+    int32_t n_rows;                            /* N */
+    int32_t n_graphs;                          /* G = B + F */
+    int32_t filler_rows;                       /* R_f */
+    int32_t reserved;
+    int64_t n_edges, nnz_adj, nnz_fea;         /* E_cap, adj_cap, fea_cap */
+    int64_t nnz_extra[SGX_COLLATE_MAX_EXTRAS]; /* the capacity of every extra */
+} sgx_collate_pad;
+
+int sgx_collate_graphs_padded(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
+                              int n_extras, const sgx_collate_pad *pad, void *stream);
+
+/* The group table of a plan from sgx_batch_plan_create_known written again from `graph_ptr` -- the same n_rows, n_graphs
+ * and max_graph, other contents, as a padded batch's buffers hold after the next collation: one launch with the plan's own
+ * window and group count into the plan's table.  No allocation, no synchronisation; capturable.  A plan without a table
+ * (it does not fit) is left alone.  plan NULL, graph_ptr NULL: SGX_ERR_NULL; a plan that owns its table (its batch was
+ * checked on the device, and another is not): SGX_ERR_UNSUPPORTED. */
+int sgx_batch_plan_regroup(const sgx_batch_plan *plan, const int32_t *graph_ptr, void *stream);
+
 /* ---- layer-ready node batches: a neighbour sample prepared on the device ----------------------
  * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
  *

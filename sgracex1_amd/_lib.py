@@ -42,6 +42,7 @@ SYMBOLS = [
     "sgx_batch_plan_create", "sgx_batch_plan_destroy", "sgx_batch_plan_rows", "sgx_batch_plan_groups",
     "sgx_batch_plan_max_graph", "sgx_batch_plan_fits", "sgx_stack_workspace_bytes", "sgx_stack_forward",
     "sgx_batch_plan_create_ex", "sgx_stack_backward_workspace_bytes", "sgx_stack_backward",
+    "sgx_collate_graphs_padded", "sgx_batch_plan_regroup",
     "sgx_collate_graphs", "sgx_collate_graphs_extras", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
     "sgx_gat_aggregate_stats", "sgx_layer_forward_stats", "sgx_gat_edge_outputs", "sgx_gat_backward_edges_stats",
     "sgx_node_batch_workspace_bytes", "sgx_node_batch_sample", "sgx_node_batch_sample_quant",
@@ -235,6 +236,15 @@ class CollateExtra(ctypes.Structure):
         ("nnz", ctypes.c_int64), ("entry_off", ctypes.c_void_p),
         ("rowPtr_out", ctypes.c_void_p), ("columnIndex_out", ctypes.c_void_p), ("values_out", ctypes.c_void_p * 2),
         ("dead_row_out", ctypes.c_void_p),
+    ]
+
+
+class CollatePad(ctypes.Structure):
+    """struct sgx_collate_pad -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("n_rows", ctypes.c_int32), ("n_graphs", ctypes.c_int32), ("filler_rows", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("n_edges", ctypes.c_int64), ("nnz_adj", ctypes.c_int64), ("nnz_fea", ctypes.c_int64),
+        ("nnz_extra", ctypes.c_int64 * SGX_COLLATE_MAX_EXTRAS),
     ]
 
 
@@ -475,6 +485,11 @@ def _load():
     lib.sgx_collate_graphs_extras.argtypes = [ctypes.POINTER(GraphSet), ctypes.POINTER(GraphBatch), ctypes.POINTER(CollateExtra),
                                               c_int, vp]
     lib.sgx_collate_graphs_extras.restype = c_int
+    lib.sgx_collate_graphs_padded.argtypes = [ctypes.POINTER(GraphSet), ctypes.POINTER(GraphBatch), ctypes.POINTER(CollateExtra),
+                                              c_int, ctypes.POINTER(CollatePad), vp]
+    lib.sgx_collate_graphs_padded.restype = c_int
+    lib.sgx_batch_plan_regroup.argtypes = [vp, vp, vp]
+    lib.sgx_batch_plan_regroup.restype = c_int
     lib.sgx_batch_plan_group_count.argtypes = [c_int, c_int, c_int, c_int, c_int]
     lib.sgx_batch_plan_group_count.restype = c_int
     lib.sgx_batch_plan_create_known.argtypes = [c_int, c_int, c_int, vp, c_int, c_int, c_int, vp, ctypes.POINTER(vp), vp]

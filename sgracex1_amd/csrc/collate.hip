@@ -1,4 +1,5 @@
-// Shuffled graph mini-batches collated on the device (sgx_collate_graphs, sgx_collate_graphs_extras, include/sgx.h).
+// Shuffled graph mini-batches collated on the device (sgx_collate_graphs, sgx_collate_graphs_extras,
+// sgx_collate_graphs_padded, include/sgx.h).
 //
 // The dataset lives on the device in dataset order (sgx_graph_set); a batch is a list of graph ids plus the exclusive
 // offsets of every graph's rows, stored edges, adjacency entries and feature entries inside the batch, which the host
@@ -7,6 +8,12 @@
 // launch whatever its size: at 64 MUTAG graphs (about 1 100 rows) the cost is the launch, at thousands of graphs it is
 // the bytes, which are read and written once each, coalesced across the wavefront (the feature rows 16 bytes a lane
 // where source and destination share their alignment).
+//
+// sgx_collate_graphs_padded is the same gather into buffers of one fixed capacity, in one launch of two kinds of
+// workgroup: the first (graph blocks) run the per-graph gather above, a wavefront per graph, without the entries behind
+// the last graph; the others (fill blocks) read the live totals from the offset arrays' last entries and write what lies
+// behind them -- the filler rows in their trailing filler graphs, those end entries, and the tails up to every capacity --
+// striding over the ranges together, 16 bytes a lane where the value is constant.  The two kinds write disjoint ranges.
 #include "sgx_device.h"
 
 namespace {
@@ -55,7 +62,9 @@ __device__ __forceinline__ void copy_csr(const int32_t *__restrict__ rowptr, con
 }
 
 // everything sgx_collate_graphs writes for batch position `pos`, one wavefront; false (nothing written) for a graph id
-// outside the set or ranges that do not fit the totals
+// outside the set or ranges that do not fit the totals.  kEnds: the last position also writes the entries behind the
+// last graph (graph_ptr[n_graphs] and both row pointers' last); a padded batch's lie behind its filler rows instead
+template <bool kEnds = true>
 __device__ __forceinline__ bool collate_one(const sgx_graph_set &s, const sgx_graph_batch &b, int pos, int lane)
 {
     const int g = b.index[pos];
@@ -73,7 +82,7 @@ __device__ __forceinline__ bool collate_one(const sgx_graph_set &s, const sgx_gr
     if (lane == 0) {
         b.graph_ptr[pos] = o;
         b.y[pos] = s.y[g];
-        if (pos == b.n_graphs - 1) {
+        if (kEnds && pos == b.n_graphs - 1) {
             b.graph_ptr[b.n_graphs] = b.n_rows;
             b.rowPtr_adj[b.n_rows] = (int32_t)b.nnz_adj;
             b.rowPtr_fea[b.n_rows] = (int32_t)b.nnz_fea;
@@ -112,14 +121,11 @@ struct CollateExtraArgs {
 // one contiguous, lane-strided run (a graph's rows are consecutive in the set, so its entries are too) -- columns shifted,
 // values cast per dtype -- the shifted row pointer and the row bytes.  Every range of every extra is checked before the
 // first store, so a graph is written as a whole or not at all.
-__global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_extras_kernel(CollateExtraArgs a)
+template <bool kEnds>
+__device__ __forceinline__ void collate_one_extras(const CollateExtraArgs &a, int pos, int lane)
 {
-    const int lane = threadIdx.x % kWave;
-    const int64_t bi = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
     const sgx_graph_set &s = a.s;
     const sgx_graph_batch &b = a.b;
-    if (bi >= b.n_graphs) return;
-    const int pos = (int)bi;
     const int g = b.index[pos];
     if (g < 0 || g >= s.n_graphs) return;
     const int r0 = s.node_ptr[g], n = s.node_ptr[g + 1] - r0;
@@ -136,7 +142,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_extras_
         eo[k] = x.entry_off[pos];
         if (ne[k] < 0 || eo[k] < 0 || eo[k] + ne[k] > x.nnz) return;
     }
-    if (!collate_one(s, b, pos, lane)) return;
+    if (!collate_one<kEnds>(s, b, pos, lane)) return;
 #pragma unroll
     for (int k = 0; k < SGX_COLLATE_MAX_EXTRAS; ++k) {
         if (k >= a.n_extras) break;
@@ -144,7 +150,7 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_extras_
         const int64_t off = eo[k];
         if (x.rowPtr_out) {
             for (int i = lane; i < n; i += kWave) x.rowPtr_out[o + i] = (int32_t)(off + (x.rowPtr[r0 + i] - e0[k]));
-            if (lane == 0 && pos == b.n_graphs - 1) x.rowPtr_out[b.n_rows] = (int32_t)x.nnz;
+            if (kEnds && lane == 0 && pos == b.n_graphs - 1) x.rowPtr_out[b.n_rows] = (int32_t)x.nnz;
             const int32_t *__restrict__ col = x.columnIndex + e0[k];
             const int shift = o - r0;
             for (int64_t i = lane; i < ne[k]; i += kWave) x.columnIndex_out[off + i] = col[i] + shift;
@@ -162,6 +168,111 @@ __global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_extras_
         if (x.dead_row)
             for (int i = lane; i < n; i += kWave) x.dead_row_out[o + i] = x.dead_row[r0 + i];
     }
+}
+
+__global__ __launch_bounds__(kWave * kWavesPerBlock) void collate_graphs_extras_kernel(CollateExtraArgs a)
+{
+    const int lane = threadIdx.x % kWave;
+    const int64_t bi = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+    if (bi >= a.b.n_graphs) return;
+    collate_one_extras<true>(a, (int)bi, lane);
+}
+
+// ---- padded batches (sgx_collate_graphs_padded, include/sgx.h "padded batches") ----------------------------------------
+// The totals of a.c.b and the nnz of every extra are the CAPACITIES; the live totals are the offset arrays' last entries.
+struct CollatePadArgs {
+    CollateExtraArgs c;
+    int G, R_f;                  // graphs with the fillers, rows of a full filler graph
+    unsigned graph_blocks;       // blocks [0, graph_blocks) gather the graphs, the others write the filler rows and the tails
+};
+
+constexpr int kFillThreads = kWave * kWavesPerBlock;
+
+__device__ __forceinline__ int64_t clamp_to(int64_t v, int64_t hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+
+struct alignas(16) Vec16 {
+    uint32_t w[4];
+};
+
+// p[lo .. hi) = v by the fill threads (t of nt >= 16): 16-byte stores over the aligned body, single elements at both ends
+template <typename T>
+__device__ __forceinline__ void fill_range(T *__restrict__ p, int64_t lo, int64_t hi, T v, int64_t t, int64_t nt)
+{
+    if (!p || lo >= hi) return;
+    constexpr int kPer = 16 / (int)sizeof(T);
+    T e[kPer];
+#pragma unroll
+    for (int i = 0; i < kPer; ++i) e[i] = v;
+    Vec16 v16;
+    __builtin_memcpy(&v16, e, 16);
+    int64_t head = (int64_t)((16 - ((uintptr_t)(p + lo) & 15)) & 15) / (int64_t)sizeof(T);
+    if (head > hi - lo) head = hi - lo;
+    const int64_t body = (hi - lo - head) / kPer;
+    if (t < head) p[lo + t] = v;
+    Vec16 *__restrict__ q = reinterpret_cast<Vec16 *>(p + lo + head);
+    for (int64_t i = t; i < body; i += nt) q[i] = v16;
+    for (int64_t i = lo + head + body * kPer + t; i < hi; i += nt) p[i] = v;
+}
+
+// behind a CSR's live entries [0, a): one diagonal entry of value 1 per filler row n + j (j < P, as far as the capacity
+// goes), zeros up to the capacity; the filler rows' pointers and the last one
+__device__ __forceinline__ void fill_pattern(int32_t *__restrict__ rowptr, int32_t *__restrict__ col, f16 *__restrict__ v16,
+                                             float *__restrict__ v32, int n, int N, int64_t a, int64_t cap, int64_t t, int64_t nt)
+{
+    const int64_t P = N - n;
+    for (int64_t j = t; j <= P; j += nt) rowptr[n + j] = (int32_t)(a + j < cap ? a + j : cap);      // (j == P: rowptr[N])
+    for (int64_t i = a + t; i < cap; i += nt) {
+        const bool diag = i - a < P;
+        col[i] = diag ? (int32_t)(n + (i - a)) : 0;
+        if (v16) v16[i] = diag ? (f16)1.0f : (f16)0.0f;
+        if (v32) v32[i] = diag ? 1.0f : 0.0f;
+    }
+}
+
+__device__ __forceinline__ void fill_padding(const CollatePadArgs &a, int64_t t, int64_t nt)
+{
+    const sgx_graph_set &s = a.c.s;
+    const sgx_graph_batch &b = a.c.b;
+    const int B = b.n_graphs, N = b.n_rows, G = a.G, R = a.R_f;
+    const int n = (int)clamp_to(b.node_off[B], N);
+    const int64_t E = clamp_to(b.edge_off[B], b.n_edges), na = clamp_to(b.adj_off[B], b.nnz_adj), nf = clamp_to(b.fea_off[B], b.nnz_fea);
+    const int64_t P = N - n;
+    for (int64_t j = t; j < P; j += nt) {
+        const int64_t g = B + (R > 0 ? j / R : 0);
+        b.batch[n + j] = g < G ? g : G - 1;
+        b.rowPtr_fea[n + j] = (int32_t)nf;
+    }
+    if (t == 0) b.rowPtr_fea[N] = (int32_t)nf;
+    for (int64_t k = t; k <= G - B; k += nt) {
+        const int64_t rows = k * (int64_t)R;
+        b.graph_ptr[B + k] = (int32_t)(n + (rows < P ? rows : P));
+        if (k < G - B) b.y[B + k] = 0;
+    }
+    fill_range(b.x, (int64_t)n * s.n_feat, (int64_t)N * s.n_feat, 0.0f, t, nt);
+    fill_range(b.edge_index, E, b.n_edges, (int64_t)-1, t, nt);
+    fill_range(b.edge_index, b.n_edges + E, 2 * b.n_edges, (int64_t)-1, t, nt);
+    fill_pattern(b.rowPtr_adj, b.columnIndex_adj, static_cast<f16 *>(b.values_adj[SGX_F16]), static_cast<float *>(b.values_adj[SGX_F32]),
+                 n, N, na, b.nnz_adj, t, nt);
+    fill_range(b.columnIndex_fea, nf, b.nnz_fea, (int32_t)0, t, nt);
+    fill_range(static_cast<f16 *>(b.values_fea[SGX_F16]), nf, b.nnz_fea, (f16)0.0f, t, nt);
+    fill_range(static_cast<float *>(b.values_fea[SGX_F32]), nf, b.nnz_fea, 0.0f, t, nt);
+    for (int k = 0; k < a.c.n_extras; ++k) {
+        const sgx_collate_extra &x = a.c.x[k];
+        if (!x.rowPtr_out) continue;
+        fill_pattern(x.rowPtr_out, x.columnIndex_out, static_cast<f16 *>(x.values_out[SGX_F16]), static_cast<float *>(x.values_out[SGX_F32]),
+                     n, N, clamp_to(x.entry_off[B], x.nnz), x.nnz, t, nt);
+        fill_range(x.dead_row_out, (int64_t)n, (int64_t)N, (uint8_t)0, t, nt);
+    }
+}
+
+__global__ __launch_bounds__(kFillThreads) void collate_graphs_padded_kernel(CollatePadArgs a)
+{
+    if (blockIdx.x < a.graph_blocks) {
+        const int64_t bi = (int64_t)blockIdx.x * kWavesPerBlock + threadIdx.x / kWave;
+        if (bi < a.c.b.n_graphs) collate_one_extras<false>(a.c, (int)bi, threadIdx.x % kWave);
+        return;
+    }
+    fill_padding(a, (int64_t)(blockIdx.x - a.graph_blocks) * kFillThreads + threadIdx.x, (int64_t)(gridDim.x - a.graph_blocks) * kFillThreads);
 }
 
 int check_collate(const sgx_graph_set *s, const sgx_graph_batch *b)
@@ -225,6 +336,50 @@ extern "C" int sgx_collate_graphs_extras(const sgx_graph_set *set, const sgx_gra
     a.n_extras = n_extras;
     const unsigned grid = (unsigned)((b->n_graphs + kWavesPerBlock - 1) / kWavesPerBlock);
     hipLaunchKernelGGL(collate_graphs_extras_kernel, dim3(grid), dim3(kWave * kWavesPerBlock), 0, (hipStream_t)stream, a);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}
+
+extern "C" int sgx_collate_graphs_padded(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
+                                         int n_extras, const sgx_collate_pad *pad, void *stream)
+{
+    if (n_extras < 0 || n_extras > SGX_COLLATE_MAX_EXTRAS) return SGX_ERR_SHAPE;
+    if (!b || !pad) return SGX_ERR_NULL;
+    CollatePadArgs a = {};
+    a.c.b = *b;                                   // the capacities take the totals' place: every range is tested against them
+    a.c.b.n_rows = pad->n_rows;
+    a.c.b.n_edges = pad->n_edges;
+    a.c.b.nnz_adj = pad->nnz_adj;
+    a.c.b.nnz_fea = pad->nnz_fea;
+    if (n_extras > 0 && !extras) return SGX_ERR_NULL;
+    for (int k = 0; k < n_extras; ++k) {
+        a.c.x[k] = extras[k];
+        a.c.x[k].nnz = pad->nnz_extra[k];
+    }
+    int rc = check_collate(set, &a.c.b);
+    if (rc != SGX_OK) return rc;
+    rc = check_extras(&a.c.b, a.c.x, n_extras);
+    if (rc != SGX_OK) return rc;
+    const int64_t B = b->n_graphs, N = pad->n_rows, G = pad->n_graphs, R = pad->filler_rows;
+    // the least that every batch of B graphs of at most R rows leaves to the fillers: an entry per row in every pattern
+    const int64_t least = N > B * R ? N - B * R : 0;
+    if (G < B || R < 0 || G * R < N || pad->nnz_adj < least || pad->nnz_adj > INT32_MAX || pad->nnz_fea > INT32_MAX) return SGX_ERR_SHAPE;
+    for (int k = 0; k < n_extras; ++k) {
+        if (!a.c.x[k].rowPtr_out) return SGX_ERR_UNSUPPORTED;         // values only (the quantised adjacencies)
+        if (a.c.x[k].nnz < least || a.c.x[k].nnz > INT32_MAX) return SGX_ERR_SHAPE;
+    }
+    a.c.s = *set;
+    a.c.n_extras = n_extras;
+    a.G = (int)G;
+    a.R_f = (int)R;
+    a.graph_blocks = (unsigned)((B + kWavesPerBlock - 1) / kWavesPerBlock);
+    // the filler rows and the tails: a block per 8 192 elements of capacity, 64 at the most
+    int64_t work = N * (set->n_feat + 3) + 2 * pad->n_edges + 2 * pad->nnz_adj + 2 * pad->nnz_fea;
+    for (int k = 0; k < n_extras; ++k) work += 2 * pad->nnz_extra[k];
+    int64_t fill_blocks = (work + 8191) / 8192;
+    fill_blocks = fill_blocks < 1 ? 1 : (fill_blocks > 64 ? 64 : fill_blocks);
+    hipLaunchKernelGGL(collate_graphs_padded_kernel, dim3(a.graph_blocks + (unsigned)fill_blocks), dim3(kFillThreads), 0,
+                       (hipStream_t)stream, a);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }

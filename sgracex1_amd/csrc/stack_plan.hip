@@ -212,6 +212,18 @@ extern "C" int sgx_batch_plan_create_known(int dtype, int n_rows, int n_graphs, 
     return SGX_OK;
 }
 
+extern "C" int sgx_batch_plan_regroup(const sgx_batch_plan *plan, const int32_t *graph_ptr, void *stream)
+{
+    if (!plan) return SGX_ERR_NULL;
+    if (plan->owns_groups) return SGX_ERR_UNSUPPORTED;      // a checked plan: its table belongs to the batch it was checked on
+    if (plan->n_groups == 0) return SGX_OK;                 // no table (the plan does not fit, or has no graph)
+    if (!graph_ptr || !plan->group_graph) return SGX_ERR_NULL;
+    int S = 1;
+    const int n_groups = plan_groups(plan->n_rows, plan->rows, plan->max_graph, &S);      // the S the table was built with
+    if (n_groups != plan->n_groups) return SGX_ERR_SHAPE;
+    return launch_group_graphs(n_groups, plan->n_graphs, S, graph_ptr, plan->group_graph, (hipStream_t)stream);
+}
+
 extern "C" int64_t sgx_batch_plan_export_groups(const sgx_batch_plan *plan, int32_t *dst, int64_t capacity, void *stream)
 {
     if (!plan) return SGX_ERR_NULL;

@@ -1251,6 +1251,7 @@ class BatchPlan:
         self.dtype = adj.val.dtype
         self.n_rows, self.n_graphs, self.max_width = adj.n_rows, graph_ptr.numel() - 1, int(max_width)
         self.kind = int(kind)
+        self.trusted = False                   # (checked on the device; BatchPlan.known: True)
         h = ctypes.c_void_p()
         if self.kind == _lib.SGX_BATCH_FORWARD:
             check(lib.sgx_batch_plan_create(dtype_code(self.dtype), self.n_rows, self.n_graphs, _ptr(graph_ptr),
@@ -1273,6 +1274,7 @@ class BatchPlan:
             raise TypeError("graph_ptr must be int32")
         self = cls.__new__(cls)
         self._h = None
+        self.trusted = True
         self.dtype = dtype
         self.n_rows, self.n_graphs, self.max_width, self.kind = int(n_rows), graph_ptr.numel() - 1, int(max_width), int(kind)
         code = dtype_code(dtype)
@@ -1293,7 +1295,7 @@ class BatchPlan:
         None when the batch is not block-diagonal under graph_ptr (remembered too, so that a caller falls back without a
         device sync per call).  Where graph_ptr carries the block facts a GraphLoader recorded for this adjacency, the
         plan is the trusted one (BatchPlan.known): no device check, no synchronisation."""
-        key = ("batch_plan", adj.val.dtype, int(max_width)) + (() if kind == _lib.SGX_BATCH_FORWARD else (int(kind),))
+        key = (BatchPlan._CACHE_KEY, adj.val.dtype, int(max_width)) + (() if kind == _lib.SGX_BATCH_FORWARD else (int(kind),))
         hit = cached_on(adj.col, key, lambda: [None, -1, None])
         if hit[0] is not graph_ptr or hit[1] != graph_ptr._version:
             facts = recorded(graph_ptr, ("block_facts",))
@@ -1308,6 +1310,29 @@ class BatchPlan:
                     plan = None
             hit[:] = [graph_ptr, graph_ptr._version, plan]
         return hit[2]
+
+    _CACHE_KEY = "batch_plan"                  # cached(): entries [graph_ptr, its version, plan] on the adjacency's column array
+
+    @staticmethod
+    def cached_for(col, graph_ptr):
+        """The plans cached() holds on the column array `col` for `graph_ptr` as it stands (any width, any kind)."""
+        plans = []
+        for key, (version, hit) in tuple(col.__dict__.get("_sgx_cache", {}).items()):
+            if key[0] == BatchPlan._CACHE_KEY and version == col._version and hit[0] is graph_ptr and \
+                    hit[1] == graph_ptr._version and hit[2] is not None:
+                plans.append(hit[2])
+        return plans
+
+    def regroup(self, graph_ptr):
+        """The trusted plan's group table written again from graph_ptr (sgx_batch_plan_regroup): the same buffer with
+        the next padded batch in it -- the same n_rows, n_graphs and max_graph, other contents.  One launch, no
+        synchronisation; capturable.  A plan that checked its batch on the device (BatchPlan(...)) refuses:
+        SgxError SGX_ERR_UNSUPPORTED."""
+        _dev(graph_ptr, "graph_ptr")
+        if graph_ptr.dtype != torch.int32 or graph_ptr.numel() != self.n_graphs + 1:
+            raise ValueError(f"graph_ptr must hold {self.n_graphs + 1} int32 entries, as the plan's own")
+        check(lib.sgx_batch_plan_regroup(self._h, _ptr(graph_ptr), _stream()), "sgx_batch_plan_regroup")
+        return self
 
     def export_groups(self):
         """The plan's group_graph table (first graph of every group, then n_graphs) as an int32 tensor; empty when the
@@ -1510,6 +1535,59 @@ class BatchIndex:
             dev[:B], dev[B:2 * B + 1], dev[2 * B + 1:3 * B + 2], dev[3 * B + 2:4 * B + 3], dev[4 * B + 3:5 * B + 4])
         self.norm_off, self.nnz_norm = (dev[5 * B + 4:6 * B + 5], totals[4]) if len(totals) > 4 else (None, None)
 
+    def refill(self, src, ids=None):
+        """Another batch of as many graphs copied into this one's device buffer, whose address stays -- what a recorded
+        padded collation reads on its next replay.  src: the other batch's `dev` array (device int32, as batch_offsets
+        lays it out), copied device to device on the current stream.  The host totals keep describing the batch this
+        object was prepared for: a padded collation reads the live totals on the device."""
+        if src.shape != self.dev.shape or src.dtype != self.dev.dtype:
+            raise ValueError("refill takes the `dev` array of a batch of as many graphs from the same set")
+        self.dev.copy_(src, non_blocking=True)
+        if ids is not None:
+            self.ids = ids
+        return self
+
+
+class PadCapacity:
+    """The fixed capacity of the padded batches of one (set, batch size) (include/sgx.h, "padded batches"), host only:
+    batch_size B, n_rows N, n_graphs G = B + fillers, filler_rows R_f, n_min, and the entry capacities n_edges, nnz_adj,
+    nnz_fea and nnz_norm (None without a prepared adjacency)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def key(self):
+        return tuple(sorted(self.__dict__.items()))
+
+    def fits(self, n_graphs, n_rows):
+        """A batch fits when it has exactly B graphs and at most N rows."""
+        return n_graphs == self.batch_size and n_rows <= self.n_rows
+
+
+def pad_capacity(graphset, batch_size, pad_rows=None):
+    """The PadCapacity of the batches of `batch_size` graphs of `graphset` (anything with GraphSet's host `counts`; a
+    prepared set's normalised adjacency counts too) by the rule of include/sgx.h: N = the sum of the B largest row
+    counts, or pad_rows; n_min = the sum of the B smallest; R_f = the largest row count; F = ceil((N - n_min) / R_f)
+    filler graphs; the edge and feature capacities the sums of the B largest counts, a pattern's that sum plus
+    N - n_min.  Host only."""
+    B = int(batch_size)
+    rows = np.asarray(graphset.counts[0], dtype=np.int64)
+    if not 1 <= B <= rows.size:
+        raise ValueError(f"batch_size must lie in [1, {rows.size}], the graphs of the set")
+    top = lambda c: int(np.sort(np.asarray(c, dtype=np.int64))[-B:].sum())
+    n_min, R_f = int(np.sort(rows)[:B].sum()), int(rows.max())
+    N = top(rows) if pad_rows is None else int(pad_rows)
+    if N < n_min:
+        raise ValueError(f"pad_rows = {N} is under the smallest batch's {n_min} rows: no batch would fit")
+    spare = N - n_min
+    prepared = getattr(graphset, "_sym_norm2", None)
+    cap = PadCapacity(batch_size=B, n_rows=N, n_min=n_min, filler_rows=R_f, n_graphs=B + (spare + R_f - 1) // R_f,
+                      n_edges=top(graphset.counts[1]), nnz_adj=top(graphset.counts[2]) + spare, nnz_fea=top(graphset.counts[3]),
+                      nnz_norm=None if prepared is None else top(prepared.counts) + spare)
+    if max(cap.n_rows, cap.n_edges, cap.nnz_adj, cap.nnz_fea, cap.nnz_norm or 0) >= 2**31:
+        raise ValueError("a padded batch holds fewer than 2^31 rows, edges and entries")
+    return cap
+
 
 class _PreparedAdjacency:
     """The dataset-side state of GraphSet.prepare_sym_norm2: adj (the normalised Csr of the whole set, fp32), counts (host,
@@ -1551,6 +1629,7 @@ class Collated:
         self.adj_val = {dt: e(i.nnz_adj, dt=dt) for dt in dtypes}
         self.fea_val = {dt: e(i.nnz_fea, dt=dt) for dt in dtypes}
         self.extras = extras
+        self.pad = None                        # the PadCapacity of a padded batch (collate_graphs(pad=))
         self.norm_rowptr = self.norm_col = self.norm_dead = None
         self.norm_val, self.q_val, self.q_dead = {}, {}, {}
         if extras is not None:
@@ -1560,7 +1639,22 @@ class Collated:
             self.q_val = {key: e(i.nnz_norm, dt=torch.float32) for key in extras.keys}
             self.q_dead = {key: e(i.n_rows, dt=torch.bool) for key in extras.keys}
 
-    def fits(self, index, n_feat, dtypes, extras=None):
+    @classmethod
+    def for_capacity(cls, pad, n_feat, dtypes, device, extras=None):
+        """The buffers of the padded batches of capacity `pad` (a PadCapacity, which names its sizes as a BatchIndex
+        does): every array capacity-sized, y and graph_ptr over pad.n_graphs graphs.  `index` is set by the collation."""
+        self = cls(pad, n_feat, dtypes, device, extras)
+        self.index, self.pad = None, pad
+        return self
+
+    def fits(self, index, n_feat, dtypes, extras=None, pad=None):
+        if (self.pad is None) != (pad is None):
+            return False
+        if pad is not None:
+            if self.pad.key() != pad.key() or (extras is not None and (self.norm_rowptr is None or not
+                                                                       set(self.norm_val) >= set(extras.dtypes))):
+                return False
+            return self.n_feat == n_feat and set(self.adj_val) >= set(dtypes) and set(self.fea_val) >= set(dtypes)
         i, j = self.index, index
         if extras is not None and (self.norm_rowptr is None or i.nnz_norm != j.nnz_norm or
                                    not set(self.norm_val) >= set(extras.dtypes) or not set(self.q_val) >= set(extras.keys)):
@@ -1606,20 +1700,64 @@ def _collate_extras(index, out, extras):
     return xs, 1 + len(extras.keys)
 
 
-def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None, extras=None):
+def _regroup_cached_plans(out):
+    """The table launch of every trusted plan cached for the buffers of the padded Collated `out` (BatchPlan.cached keeps
+    them on the adjacencies' column arrays), run again on its graph_ptr: the plan a warm-up step built follows the batch
+    the buffers hold now, inside a recorded step as well."""
+    for col in (out.adj_col, out.norm_col):
+        for plan in (() if col is None else BatchPlan.cached_for(col, out.graph_ptr)):
+            if plan.trusted:
+                plan.regroup(out.graph_ptr)
+
+
+def _collate_padded(graphset, index, dtypes, out, extras, pad):
+    """collate_graphs(pad=): the checks, the capacity-sized Collated and the one launch of sgx_collate_graphs_padded."""
+    if extras is not None and extras.keys:
+        raise ValueError("collate_graphs: padded batches do not carry the quantised adjacencies (pad with quant=)")
+    if extras is not None and pad.nnz_norm is None:
+        raise ValueError("collate_graphs: `pad` was computed before graphset.prepare_sym_norm2; compute it after")
+    if not pad.fits(index.n_graphs, index.n_rows):
+        raise ValueError(f"collate_graphs: a batch of {index.n_graphs} graphs and {index.n_rows} rows does not fit the capacity "
+                         f"of {pad.batch_size} graphs and {pad.n_rows} rows")
+    if out is None:
+        out = Collated.for_capacity(pad, graphset.n_feat, dtypes, graphset.device, extras)
+    elif not out.fits(index, graphset.n_feat, dtypes, extras, pad):
+        raise ValueError("collate_graphs: `out` was made for another capacity or other dtypes")
+    out.index = index
+    b = _graph_batch(index, out, dtypes)
+    c = _lib.CollatePad()
+    c.n_rows, c.n_graphs, c.filler_rows = pad.n_rows, pad.n_graphs, pad.filler_rows
+    c.n_edges, c.nnz_adj, c.nnz_fea = pad.n_edges, pad.nnz_adj, pad.nnz_fea
+    xs, n = (None, 0) if extras is None else _collate_extras(index, out, extras)
+    for k in range(n):
+        c.nnz_extra[k] = pad.nnz_norm
+    check(lib.sgx_collate_graphs_padded(ctypes.byref(graphset.desc), ctypes.byref(b), xs, n, ctypes.byref(c), _stream()),
+          "sgx_collate_graphs_padded")
+    _regroup_cached_plans(out)
+    return out
+
+
+def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None, extras=None, pad=None):
     """The batch of the graphs `idx` of `graphset` in that order, built on the device by one launch of
     sgx_collate_graphs: the same x / edge_index / batch / y as pyg_lite.collate, the same adjacency as
     csr_from_edge_index, the same feature CSR as Csr.from_dense, graph_ptr as graph_ptr_of -- with the CSR values in each
     of `dtypes`.  idx: host graph ids, or a BatchIndex from graphset.prepare.  out: a Collated of the same sizes to write
     into (a captured batch); a new one otherwise.  No synchronisation.
     extras (a GraphExtras from graphset.prepare_sym_norm2): the same launch (sgx_collate_graphs_extras) also gathers the
-    batch's normalised adjacency, its dead-row mask and the quantised values with theirs into out.norm_* / out.q_*."""
+    batch's normalised adjacency, its dead-row mask and the quantised values with theirs into out.norm_* / out.q_*.
+    pad (a PadCapacity from pad_capacity(graphset, B)): the batch padded to that capacity (include/sgx.h, "padded
+    batches"; one launch of sgx_collate_graphs_padded) -- every tensor has the capacity's size whatever the batch, the
+    batch's graphs in the live prefix and filler graphs behind (y, graph_ptr: pad.n_graphs entries) -- and the trusted
+    batch plans cached for the buffers of `out` have their tables written again, so that a recorded step which collates
+    into `out` serves every batch that fits.  Extras with quantised values are refused."""
     index = idx if isinstance(idx, BatchIndex) else graphset.prepare(idx)
     dtypes = tuple(dtypes)
     for dt in dtypes:
         dtype_code(dt)
     if extras is not None and (index.norm_off is None or extras.prepared is not graphset._sym_norm2):
         raise ValueError("collate_graphs: extras need a batch prepared after graphset.prepare_sym_norm2, and extras of this set")
+    if pad is not None:
+        return _collate_padded(graphset, index, dtypes, out, extras, pad)
     if out is None:
         out = Collated(index, graphset.n_feat, dtypes, graphset.device, extras)
     elif not out.fits(index, graphset.n_feat, dtypes, extras):

@@ -31,6 +31,11 @@ class Batch:
     y: torch.Tensor
     batch: torch.Tensor        # [n] graph id of every node
     num_graphs: int
+    num_real_graphs: int = None    # a padded batch (GraphLoader(pad=True)): its first graphs are the real ones; else all
+
+    def __post_init__(self):
+        if self.num_real_graphs is None:
+            self.num_real_graphs = self.num_graphs
 
     @property
     def num_nodes(self):
@@ -38,7 +43,7 @@ class Batch:
 
     def to(self, device):
         return Batch(self.x.to(device), self.edge_index.to(device), self.y.to(device), self.batch.to(device),
-                     self.num_graphs)
+                     self.num_graphs, self.num_real_graphs)
 
 
 def load_tu_raw(A, graph_indicator, graph_labels, node_labels) -> List[Graph]:
@@ -109,11 +114,30 @@ class GraphLoader:
     the list of the attached triple is edge_index itself (the stored edges without the added loops).
     quant=qc (a quant.QuantConstants such as sgrace.quant_constants; with prepare, and float32 among dtypes): the float32
     Csr also holds .quantized(qc) and .quantized(qc.second_layer()) with their dead-row facts, gathered from values
-    quantised once per set.  prepare=None: the batches as before."""
+    quantised once per set.  prepare=None: the batches as before.
+
+    pad=True: the same permutation rule and the same batches, and every batch that fits -- exactly batch_size graphs, at
+    most pad_rows rows (default: the batch_size largest graphs' rows, so every full batch fits) -- arrives PADDED to one
+    fixed capacity (ops.pad_capacity; rule in include/sgx.h, "padded batches"): every tensor has the same size in every
+    batch, the batch's graphs come first (Batch.num_real_graphs of them) and filler graphs behind -- rows whose x is 0
+    and whose adjacency row is one diagonal 1, labels 0 -- which pool to 0 and receive no gradient.  A loss takes
+    out[:batch.num_real_graphs] and y[:batch.num_real_graphs]; past the stored edges edge_index holds -1: it is the key
+    of the attached CSRs, which the kernels read, not an edge list.  One recorded training step then serves every such
+    batch (train.StackTrainer.capture_loader).  A short last batch, a batch over pad_rows and, from a prepared loader, a
+    batch with a dead-row graph (a host fact of the prepared set: the fused attention route declines such a batch, and
+    the layer-by-layer route it then takes was written for CSRs without spare capacity) arrive unpadded, as before.  A
+    padded batch is made for the fused stack routes, which read the attached CSRs through their row pointers;
+    train.StackTrainer.step refuses to run one layer by layer, and the attention model takes padded batches from a
+    prepare="sym_norm2" loader only (it would otherwise normalise the padded edge_index).  pad=True with quant= raises
+    ValueError: padding the quantised adjacencies is not built."""
 
     def __init__(self, dataset, batch_size=1, shuffle=False, generator=None, device=None, dtypes=(torch.float16,),
-                 prepare=None, quant=None):
+                 prepare=None, quant=None, pad=False, pad_rows=None):
         from . import ops
+        if pad and quant is not None:
+            raise ValueError("pad=True does not go with quant=: padded batches do not carry the quantised adjacencies")
+        if pad_rows is not None and not pad:
+            raise ValueError("pad_rows needs pad=True")
         if quant is not None and not prepare:
             raise ValueError("quant needs prepare='sym_norm2'")
         if prepare not in (None, "sym_norm2"):
@@ -127,20 +151,39 @@ class GraphLoader:
             raise ValueError("batch_size must be >= 1")
         self.prepare, self.quant = prepare, quant
         self.extras = self.graphs.prepare_sym_norm2(self.dtypes, quant) if prepare else None
+        self.pad = bool(pad)
+        # (after the set is prepared: the capacity counts the normalised adjacency's entries too)
+        self.capacity = ops.pad_capacity(self.graphs, min(self.batch_size, len(self.graphs)), pad_rows) if self.pad else None
 
     def __len__(self):
         return (len(self.graphs) + self.batch_size - 1) // self.batch_size
 
-    def __iter__(self):
+    def batches(self):
+        """The graph ids of the next epoch's batches (host arrays, in order): one draw from the generator, as an epoch of
+        __iter__ takes."""
         n = len(self.graphs)
         order = torch.randperm(n, generator=self.generator).numpy() if self.shuffle else np.arange(n)
-        for i in range(0, n, self.batch_size):
-            yield self.collate(order[i:i + self.batch_size])
+        return [order[i:i + self.batch_size] for i in range(0, n, self.batch_size)]
+
+    def __iter__(self):
+        for ids in self.batches():
+            yield self.collate(ids)
+
+    def padded(self, idx):
+        """Whether the batch of graph ids `idx` arrives padded: pad=True, exactly batch_size graphs, rows within the
+        capacity and, with a prepared adjacency, no graph with a dead row.  Host only."""
+        idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+        if not self.pad or not self.capacity.fits(idx.size, int(self.graphs.counts[0][idx].sum())):
+            return False
+        return self.extras is None or not bool(self.extras.prepared.has_dead[idx].any())
 
     def collate(self, idx, out=None):
-        """The Batch of graph ids `idx` (host, in batch order), caches attached; out: an ops.Collated to reuse."""
+        """The Batch of graph ids `idx` (host, in batch order, or an ops.BatchIndex of them), caches attached; out: an
+        ops.Collated to reuse."""
         from . import ops
-        c = ops.collate_graphs(self.graphs, idx, self.dtypes, out=out, extras=self.extras)
+        ids = idx.ids if isinstance(idx, ops.BatchIndex) else idx
+        c = ops.collate_graphs(self.graphs, idx, self.dtypes, out=out, extras=self.extras,
+                               pad=self.capacity if self.padded(ids) else None)
         return attach_batch(c)
 
 
@@ -149,6 +192,7 @@ def attach_batch(c):
     where it was collated with extras, the normalised adjacency with its facts and quantised forms."""
     from . import ops
     n, B = c.x.shape[0], c.index.n_graphs
+    G, max_graph = (B, c.index.max_graph) if c.pad is None else (c.pad.n_graphs, c.pad.filler_rows)
     ops.attach(c.batch, ("graph_ptr",), c.graph_ptr)
     cols = []
     if c.extras is not None:
@@ -166,8 +210,8 @@ def attach_batch(c):
         cols.append(weakref.ref(A.col))            # (weak: the adjacency's cache already holds graph_ptr)
         ops.attach(c.edge_index, ("adj_csr", n, dt), A)
         ops.attach(c.x, ("fea_csr", dt), ops.Csr(c.fea_rowptr, c.fea_col, c.fea_val[dt], c.n_feat))
-    ops.attach(c.graph_ptr, ("block_facts",), {"n_rows": n, "max_graph": c.index.max_graph, "cols": cols})
-    return Batch(c.x, c.edge_index, c.y, c.batch, B)
+    ops.attach(c.graph_ptr, ("block_facts",), {"n_rows": n, "max_graph": max_graph, "cols": cols, "padded": c.pad is not None})
+    return Batch(c.x, c.edge_index, c.y, c.batch, G, B)
 
 
 def to_dense_adj(edge_index, num_nodes=None):

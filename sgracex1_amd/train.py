@@ -9,6 +9,7 @@ can be captured once (torch.cuda.graph) and replayed: the regime of the notebook
 NodeTrainer is the same for node classification (sgrace.GAT_PYNQ): the model's two layers through their own autograd,
 ops.NodeLoss (the tail over the selected rows, the count of which never leaves the device) and ops.adam_step.
 """
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -46,19 +47,21 @@ class _Trainer:
             for dst, src in zip((*self.params, *self.exp_avg, *self.exp_avg_sq, self.t), state):
                 dst.copy_(src)
 
-    def _capture(self, batch, warmup, probe=None, counters=()):
-        """Record self.step(*batch) with torch.cuda.graph (one stream, no parallel branches) and return a callable that
+    def _capture(self, batch, warmup, probe=None, counters=(), run=None):
+        """Record self.step(*batch) (or run(), where a step has more in front of it) with torch.cuda.graph (one stream, no parallel branches) and return a callable that
         replays it and returns the loss tensor the replay fills.  The warm-up steps it needs first (they build what a step
         caches: the CSRs, the plans, the workspaces) run on a side stream on a copy of the state, which is put back before
         the capture: the trainer is where it was, and n replays equal n eager steps.  probe: run on the side stream after
         the warm-up steps; what it returns is raised once the state is back.  counters: the names of host-side counts that
         the recorded step (which computes nothing until it is replayed) must leave as the warm-up left them."""
+        if run is None:
+            run = lambda: self.step(*batch)
         saved = self.state()
         side = torch.cuda.Stream()
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side):
             for _ in range(max(1, warmup)):
-                self.step(*batch)
+                run()
             failure = probe() if probe is not None else None
         torch.cuda.current_stream().wait_stream(side)
         self.load_state(saved)
@@ -69,7 +72,7 @@ class _Trainer:
         kept = [(name, getattr(self, name)) for name in counters]
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
-            loss = self.step(*batch)
+            loss = run()
         for name, value in kept:
             setattr(self, name, value)
 
@@ -88,6 +91,8 @@ class StackTrainer(_Trainer):
         loss = trainer.step(x, edge_index, batch, y)          # a device tensor [1]; nothing synchronises
         replay = trainer.capture(x, edge_index, batch, y)     # the step of this batch, recorded once
         loss = replay()
+        epoch = trainer.capture_loader(loader)                # a GraphLoader(pad=True): one recorded step for every batch
+        losses = epoch()                                      # one shuffled epoch, a loss tensor per batch
 
     The trainer owns the optimiser state (exp_avg, exp_avg_sq per parameter, the device step counter `t`); its dropout
     stream is ops.head_loss's counter-based mask of (seed, t), not torch's generator.  step() is a training step whatever
@@ -110,25 +115,41 @@ class StackTrainer(_Trainer):
             return self.model(1, x, edge_index, batch)
         return self.model(x, edge_index, batch)
 
-    def step(self, x, edge_index, batch, y):
+    def step(self, x, edge_index, batch, y, n_real=None):
+        """One training step -> the loss, a device tensor [1].  n_real: the real graph count of a padded batch
+        (Batch.num_real_graphs); the loss head then runs on the first n_real pooled rows and labels, and the filler graphs
+        behind them receive a zero gradient.  A padded batch runs the fused route or not at all: where the model declines
+        it, RuntimeError names the reason before anything is changed (the layer-by-layer routes were written for CSRs
+        without spare capacity; pyg_lite.GraphLoader(pad=True) delivers the batches it knows to be declined unpadded)."""
         model = self.model
         for p in self.params:
             p.grad = None
         head = {id(model.lin.weight): None, id(model.lin.bias): None}
         pooled = model.train_pooled(x, edge_index, batch)
+        if n_real is not None and n_real != y.shape[0]:
+            y = y[:n_real]
+        else:
+            n_real = None
         if pooled is not None:
-            loss, grad_pooled, grad_w, grad_b = ops.head_loss(pooled, model.lin.weight, model.lin.bias, y, p=self.p_drop,
+            rows = pooled if n_real is None else pooled.detach()[:n_real]
+            loss, grad_pooled, grad_w, grad_b = ops.head_loss(rows, model.lin.weight, model.lin.bias, y, p=self.p_drop,
                                                               seed=self.seed, step=0, step_dev=self.t)
+            if n_real is not None:
+                grad_pooled = F.pad(grad_pooled, (0, 0, 0, pooled.shape[0] - n_real))
             pooled.backward(grad_pooled)
             head = {id(model.lin.weight): grad_w, id(model.lin.bias): grad_b}
             self.fused_steps += 1
         else:
+            if self._is_padded(batch):
+                raise RuntimeError(f"StackTrainer.step: the fused route declined a padded batch: {self._declined(batch)}")
             pooled = model.layers_pooled(x, edge_index, batch)
             if pooled is not None:
                 # the layers one by one with their own autograd; the tail is still the one call, on the same mask stream
-                loss = ops.HeadLoss.apply(pooled, model.lin.weight, model.lin.bias, y, self.p_drop, self.seed, 0, self.t)
+                rows = pooled if n_real is None else pooled[:n_real].contiguous()
+                loss = ops.HeadLoss.apply(rows, model.lin.weight, model.lin.bias, y, self.p_drop, self.seed, 0, self.t)
             else:
-                loss = F.cross_entropy(self._forward(x, edge_index, batch), y)
+                logits = self._forward(x, edge_index, batch)
+                loss = F.cross_entropy(logits if n_real is None else logits[:n_real], y)
             loss.backward()
             loss = loss.detach().reshape(1)
         self._adam([head.get(id(p)) if head.get(id(p)) is not None else p.grad for p in self.params])
@@ -140,6 +161,86 @@ class StackTrainer(_Trainer):
         a step caches: the CSRs, the plan, the workspace) run on a copy of the state, which is put back before the
         capture: the trainer is where it was, and n replays equal n eager steps."""
         return self._capture((x, edge_index, batch, y), warmup, counters=("fused_steps",))
+
+    @staticmethod
+    def _block_facts(batch):
+        """The block facts a GraphLoader recorded for the batch vector `batch`, or None (nothing is built or read back)."""
+        ptr = ops.recorded(batch, ("graph_ptr",))
+        return None if ptr is None else ops.recorded(ptr, ("block_facts",))
+
+    def _is_padded(self, batch):
+        return bool((self._block_facts(batch) or {}).get("padded"))
+
+    def _declined(self, batch):
+        """Why model.train_pooled declined the padded batch of batch vector `batch`, as far as it can be told from outside."""
+        model = self.model
+        if not getattr(model, "train_stack", False):
+            return "the model was not built with train_stack=True"
+        if not model._stack_enabled():
+            return "the register layer_count is under 2 (or the kernels are off): the layers run one by one"
+        if not torch.is_grad_enabled():
+            return "gradients are disabled"
+        facts = self._block_facts(batch)
+        return (f"a condition of the model's fused training route fails on the padded batch (its class docstring lists "
+                f"them); the largest graph of the set has {facts['max_graph'] if facts else '?'} rows, which must be within "
+                f"the backward plan's row budget, and no row of the adjacency may be dead")
+
+    def capture_loader(self, loader, warmup=2):
+        """One recorded step for every padded batch of `loader` (a pyg_lite.GraphLoader(pad=True)) -> a callable that runs
+        one epoch and returns its losses, one device tensor [1] per batch, in the loader's order.
+
+        The recorded step is the padded collation (ops.collate_graphs(pad=) into one capacity-sized ops.Collated, with the
+        cached plans' table launches behind it), the fused forward, ops.head_loss on the real graphs, the fused backward and
+        ops.adam_step -- one stream, no parallel branches, as capture().  An epoch draws its batches as iterating the
+        loader would (one draw from its generator), uploads the graph ids and offsets of all its padded batches once, and
+        per padded batch copies that batch's row into the static index buffer (device to device) and replays.  A batch
+        that arrives unpadded -- a short last batch, a batch over pad_rows, a batch with a dead-row graph (a host fact of
+        the prepared set; the fused GAT route declines it) -- runs through step() unpadded in its place, so an epoch
+        takes exactly the steps of `for b in loader: step(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs)`.
+        The warm-up steps run on a padded batch of the set's smallest graphs without a dead row, on a copy of the state.
+        If the model's fused route declines that batch, RuntimeError names the reason: a padded batch never falls back."""
+        from . import pyg_lite
+        if not getattr(loader, "pad", False):
+            raise ValueError("capture_loader takes a GraphLoader(pad=True)")
+        gs, cap, B = loader.graphs, loader.capacity, loader.capacity.batch_size
+        rows = gs.counts[0]
+        dead = loader.extras.prepared.has_dead if loader.extras is not None else np.zeros(len(gs), dtype=bool)
+        first = [int(g) for g in np.argsort(rows, kind="stable") if not dead[g]][:B]
+        if len(first) < B or not loader.padded(first):
+            raise RuntimeError("capture_loader: the set has no padded batch without a dead-row graph to record a step on")
+        index = gs.prepare(first)                      # the static index buffer: every replay reads this address
+        c = ops.collate_graphs(gs, index, loader.dtypes, extras=loader.extras, pad=cap)
+        b = pyg_lite.attach_batch(c)
+
+        def run():
+            ops.collate_graphs(gs, index, loader.dtypes, out=c, extras=loader.extras, pad=cap)
+            return self.step(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs)
+
+        with torch.enable_grad():                      # (before any state is touched: step() raises on a declined padded batch)
+            if self.model.train_pooled(b.x, b.edge_index, b.batch) is None:
+                raise RuntimeError(f"StackTrainer.capture_loader: the fused route declined the padded batch: {self._declined(b.batch)}")
+        replay = self._capture((), warmup, counters=("fused_steps",), run=run)
+        counts = gs.counts if gs._sym_norm2 is None else gs.counts + (gs._sym_norm2.counts,)
+
+        def epoch():
+            batches = loader.batches()
+            recorded = [loader.padded(ids) for ids in batches]
+            host = [ops.batch_offsets(counts, ids)[0] for ids, r in zip(batches, recorded) if r]
+            if host:
+                dev = torch.from_numpy(np.stack(host)).pin_memory().to(gs.device, non_blocking=True)
+            losses, k = [], 0
+            for ids, r in zip(batches, recorded):
+                if r:
+                    index.refill(dev[k], ids)
+                    k += 1
+                    losses.append(replay().clone())
+                else:
+                    e = loader.collate(ids)
+                    losses.append(self.step(e.x, e.edge_index, e.batch, e.y, e.num_real_graphs))
+            return losses
+
+        epoch.graph, epoch.collated = replay.graph, c
+        return epoch
 
 
 class NodeTrainer(_Trainer):

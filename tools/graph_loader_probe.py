@@ -17,6 +17,12 @@ GCN_PYNQ(train_stack=True), layer_count 2, fp16 layers:
           (GraphLoader(prepare="sym_norm2", quant=): everything gathered by the collation launch); and the collation alone
           without and with the extras.  --leg plain runs the plain leg alone (it uses nothing a tree without the prepared
           loader lacks).
+  --only replay [--model gat] [--replay-leg eager|replay] [--big] [--pad-rows N]: the shuffled epoch through
+          train.StackTrainer -- eager: trainer.step over the plain (gat: prepared) GraphLoader's batches, which runs on a
+          tree without padded batches too; replay: StackTrainer.capture_loader over GraphLoader(pad=True), one recorded
+          step for every full batch -- on MUTAG at batch 64, or with --big on the million-graph replica at batch 4096.
+          step_ms = host wall clock of whole epochs over their steps, closed by a synchronisation, after one warm-up
+          epoch; the replay line also gives the padding overhead N over the mean n.
 One JSON line each.  --stats CSV turns a `rocprofv3 --kernel-trace --stats` kernel_stats file of a `--only collate` run
 into one line for the collate kernel.
 
@@ -156,6 +162,40 @@ def gat_lines(gs, name, batch_size, dev, args):
                           "prepare_and_collate_wall_ms_extras": c["prepare_and_collate_wall_ms"]}), flush=True)
 
 
+def replay_line(graphs, name, batch_size, dev, args):
+    """One line: the shuffled epoch's step through StackTrainer, eager on unpadded batches or replayed on padded ones."""
+    from sgracex1_amd import train
+    torch.manual_seed(5)
+    gat = args.model == "gat"
+    m = gat_model(dev, None)[0] if gat else model(dev)
+    kw = dict(dtypes=(torch.float32,), prepare="sym_norm2") if gat else {}
+    gs = ops.GraphSet(graphs, dev)
+    replay = args.replay_leg == "replay"
+    if replay:
+        kw.update(pad=True, pad_rows=args.pad_rows)
+    loader = G.GraphLoader(gs, batch_size=batch_size, shuffle=True, generator=torch.Generator().manual_seed(12345), **kw)
+    trainer = train.StackTrainer(m, lr=0.01)
+    line = {"workload": f"{name}_{args.model}_trainer_epoch", "leg": args.replay_leg, "graphs": len(gs), "batch_size": batch_size}
+    if replay:
+        epoch = trainer.capture_loader(loader)
+        cap = loader.capacity
+        line.update(pad_rows=cap.n_rows, pad_graphs=cap.n_graphs, filler_rows=cap.filler_rows,
+                    rows_over_mean_rows=cap.n_rows / (float(np.mean(gs.counts[0])) * batch_size))
+    else:
+        def epoch():
+            return [trainer.step(b.x, b.edge_index, b.batch, b.y) for b in loader]
+    epochs = max(1, args.steps // len(loader))
+    epoch()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(epochs):
+        steps = len(epoch())
+    torch.cuda.synchronize()
+    line.update(epochs=epochs, steps_per_epoch=steps, step_ms=(time.perf_counter() - t0) * 1e3 / (epochs * steps),
+                fused_steps=trainer.fused_steps)
+    print(json.dumps(line), flush=True)
+
+
 def collate_bytes(gs, index):
     """Bytes sgx_collate_graphs must read and write for a batch (fp16 CSR values out)."""
     n, E, na, nf, B, F = index.n_rows, index.n_edges, index.nnz_adj, index.nnz_fea, index.n_graphs, gs.n_feat
@@ -206,7 +246,10 @@ def stats_line(path):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--only", choices=["step", "big", "collate"], default=None)
+    ap.add_argument("--only", choices=["step", "big", "collate", "replay"], default=None)
+    ap.add_argument("--replay-leg", choices=["eager", "replay"], default="replay")
+    ap.add_argument("--big", action="store_true")
+    ap.add_argument("--pad-rows", type=int, default=None)
     ap.add_argument("--copies", type=int, default=5320)          # 5320 x 188 = 1,000,160 graphs
     ap.add_argument("--steps", type=int, default=60)
     ap.add_argument("--big-steps", type=int, default=8)
@@ -226,6 +269,12 @@ def main():
         return
     dev = torch.device("cuda")
     graphs = mutag_graphs()
+    if args.only == "replay":
+        if args.big:
+            replay_line(graphs * args.copies, "mutag_replica", 4096, dev, args)
+        else:
+            replay_line(graphs, "mutag", 64, dev, args)
+        return
     if args.model == "gat":
         if args.only in (None, "step"):
             gat_lines(ops.GraphSet(graphs, dev), "mutag", 64, dev, args)
