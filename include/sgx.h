@@ -104,6 +104,18 @@ int sgx_plan_reordered(const sgx_plan *plan);
  * longer row).  Returns the array's length
  * (dst NULL: the length only) or a negative sgx error. */
 int64_t sgx_plan_export(const sgx_plan *plan, int which, int32_t *dst, int64_t capacity, void *stream);
+/* Which kernel form sgx_xw_sparse (and the first stage of sgx_layer_forward in gemm_mode 0) takes for these operands, for
+ * reports and tests (added without a version bump, SGX_VERSION stays 110: a new declaration, nothing else changes): a
+ * host query without a launch, answered by the functions the launch itself uses.  0 = the gather
+ * kernel (W read through L2); otherwise the form with W's column slices resident in LDS, as
+ *   lpr | n_split << 8 | full << 16 | w_vec << 17 | wgs_per_cu << 18 | streams << 20
+ * lpr = lanes per row (2, 4, 8, 16; a slice is lpr x 16 bytes wide), n_split = column slices (1 .. 4), full = one 16-byte
+ * store per lane and row (P a multiple of the slice width, H and its pitch 16-byte aligned; element stores otherwise),
+ * w_vec = the slice filled with 16-byte loads (W and its pitch 16-byte aligned), wgs_per_cu = workgroups a CU holds
+ * (1, 2), streams = the row-tile streams of the persistent grid (a multiple of 8; window w of 64 rows belongs to
+ * wavefront w mod 16 streams).  W, H: the pointers the call would get (only their alignment is read); ldw, ldh in elements. */
+int sgx_xw_sparse_form(int dtype, int n_rows, int M_fea, int P, const void *W, int64_t ldw, const void *H, int64_t ldh,
+                       const sgx_plan *plan);
 
 /* ---- quantised layer of the SGRACE bitstream (SG.py:53-265, :570-667, :1645-1848) -------
  * The reference quantises inside the device kernel from scale registers and states the arithmetic

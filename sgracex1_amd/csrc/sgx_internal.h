@@ -34,6 +34,7 @@ struct sgx_tuning {
     bool spmm_no_short_tail;      // the one-step tail of a degree order through the sblock path (as in round 2)
     int spmm_cpl;                 // 0 = unset
     int xw_sparse_lpr;            // 0 = unset: lanes per row (slice width / 16 bytes) of the sparse X.W stage's LDS form, at most
+    int xw_sparse_streams;        // 0 = unset: streams of row tiles of that form, at most (whole groups of 8; tests and probes)
     int plan_long_threshold;      // 0 = unset
     int plan_chunk;               // 0 = unset
     float plan_reorder_below;     // < 0 = unset
@@ -134,6 +135,9 @@ int sgx_spmm_launch(int dtype, int acc_mode, int spmm_block, int relu, int n_row
                     const sgx_plan *plan, void *scratch, size_t scratch_bytes, hipStream_t stream,
                     const float *acc_in = nullptr, float *acc_out = nullptr, int64_t ld_acc = 0,
                     bool fea_stage = false, int ref_threads = 1, sgx_epilogue ep = sgx_no_epilogue());
+
+// whether a gathered table [n_cols][ldh] is past what 32-bit buffer offsets reach (spmm_csr.hip): 64-bit pointers then
+bool sgx_spmm_table_big(int dtype, int n_cols, int64_t ldh, int n_feat);
 
 // X.W for a CSR X with the weight slice resident in LDS (xw_sparse_lds.hip); the caller checks _applicable first
 bool sgx_xw_sparse_lds_applicable(int dtype, int n_rows, int m_fea, int n_feat, int64_t ldh, const sgx_plan *plan);

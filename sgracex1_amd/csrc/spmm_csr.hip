@@ -564,6 +564,13 @@ size_t sgx_spmm_scratch_bytes(const sgx_plan *plan, int n_feat)
     return sgx_align_up((size_t)plan->n_tasks * (size_t)sgx_align_up((size_t)n_feat, 4) * sizeof(float), 256);
 }
 
+// 32-bit buffer offsets need the whole table below kOOBRow and a row below 1 MiB (sgx_device.h)
+bool sgx_spmm_table_big(int dtype, int n_cols, int64_t ldh, int n_feat)
+{
+    const size_t es = sgx_elem_size(dtype);
+    return (unsigned long long)n_cols * (unsigned long long)ldh * es > kOOBRow || (unsigned long long)n_feat * es > kMaxRowBytes;
+}
+
 int sgx_spmm_launch(int dtype, int acc_mode, int spmm_block, int relu, int n_rows, int n_cols, int n_feat,
                     const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
                     const void *H, int64_t ldh, void *D, int64_t ldd,
@@ -586,8 +593,7 @@ int sgx_spmm_launch(int dtype, int acc_mode, int spmm_block, int relu, int n_row
     if (plan && plan->n_rows != n_rows) return SGX_ERR_SHAPE;
     const size_t es = sgx_elem_size(dtype);
     const unsigned long long table_bytes = (unsigned long long)n_cols * (unsigned long long)ldh * es;
-    // 32-bit buffer offsets need the whole table below kOOBRow and a row below 1 MiB (sgx_device.h)
-    const bool big = table_bytes > kOOBRow || (unsigned long long)n_feat * es > kMaxRowBytes;
+    const bool big = sgx_spmm_table_big(dtype, n_cols, ldh, n_feat);
     if ((unsigned long long)ldh * es >= 0xFFFFFFF0ull) return SGX_ERR_UNSUPPORTED;
     if (n_cols > 0 && (!H || !columnIndex || !values)) return SGX_ERR_NULL;
     // X.W over a large CSR X: the weight slice resident in LDS instead of gathered through L2 (same sums, same order)

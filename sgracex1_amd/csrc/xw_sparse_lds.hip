@@ -462,43 +462,6 @@ int device_cus()
     return cus;
 }
 
-template <typename T, int VEC, int LPR, bool FULL>
-int launch_lds_impl(int n_work, int n_feat, int m_fea, const int32_t *rowptr, const int32_t *col, const void *val, const void *W,
-               int64_t ldw, void *H, int64_t ldh, int64_t nnz, const uint8_t *win_order, sgx_epilogue ep, hipStream_t stream)
-{
-    auto kernel = xw_sparse_lds_kernel<T, VEC, LPR, FULL>;
-    const size_t lds_bytes = (size_t)(m_fea + 1) * LPR * 16;
-    static bool attr_set = false;                     // per instantiation
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kLdsBudget) != hipSuccess)
-            return SGX_ERR_HIP;
-        attr_set = true;
-    }
-    const int n_split = (n_feat + LPR * VEC - 1) / (LPR * VEC);
-    const int wgs_per_cu = lds_bytes * 2 <= kLdsBudget ? 2 : 1;       // 32 wavefronts per CU at most
-    int grid = device_cus() / 8 * 8 * wgs_per_cu;
-    // no more streams than row tiles
-    const int64_t tiles = ((int64_t)n_work + 64 * kWaves - 1) / (64 * kWaves);
-    const int64_t want = (tiles + 7) / 8 * 8 * n_split;
-    if (want < grid) grid = (int)want;
-    if (grid < 8 * n_split) grid = 8 * n_split;
-    const int w_vec = ((uintptr_t)W % 16 == 0) && ((ldw * (int64_t)sizeof(T)) % 16 == 0);
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kThreads), lds_bytes, stream, n_work, n_feat, m_fea, rowptr, col,
-                       (const T *)val, (const T *)W, ldw, w_vec, (T *)H, ldh, n_split, (unsigned)(nnz * 4), win_order, ep);
-    SGX_LAUNCH_CHECK();
-    return SGX_OK;
-}
-
-template <typename T, int VEC, int LPR>
-int launch_lds(int n_work, int n_feat, int m_fea, const int32_t *rowptr, const int32_t *col, const void *val, const void *W,
-               int64_t ldw, void *H, int64_t ldh, int64_t nnz, const uint8_t *win_order, sgx_epilogue ep, hipStream_t stream)
-{
-    const bool full = n_feat % (LPR * VEC) == 0 && ((uintptr_t)H % 16 == 0) && ((ldh * (int64_t)sizeof(T)) % 16 == 0);
-    return full ? launch_lds_impl<T, VEC, LPR, true>(n_work, n_feat, m_fea, rowptr, col, val, W, ldw, H, ldh, nnz, win_order, ep, stream)
-                : launch_lds_impl<T, VEC, LPR, false>(n_work, n_feat, m_fea, rowptr, col, val, W, ldw, H, ldh, nnz, win_order, ep, stream);
-}
-
 // lanes per row of the LDS tile: the widest slice (power-of-two lanes x 16 bytes) whose (M_fea + 1) rows fit
 int choose_lpr(int dtype, int m_fea, int n_feat)
 {
@@ -509,6 +472,75 @@ int choose_lpr(int dtype, int m_fea, int n_feat)
     while (lpr >= 1 && (size_t)(m_fea + 1) * lpr * 16 > kLdsBudget) lpr >>= 1;
     if (sgx_tune().xw_sparse_lpr > 0 && sgx_tune().xw_sparse_lpr < lpr) lpr = sgx_tune().xw_sparse_lpr;      // tuning override: narrower slices
     return lpr >= 2 ? lpr : 0;                                      // 0: not even a 32-byte slice fits (one-lane rows stay with the gather kernel)
+}
+
+// The arm a launch takes, decided in ONE place: the launch below and sgx_xw_sparse_form (what the tests assert on) both
+// read it from here.
+struct LdsForm {
+    int lpr;                // lanes per row, 0 = no LDS form at this shape
+    int n_split;            // column slices (workgroups per stream)
+    int full;               // 16-byte stores (the FULL instantiation)
+    int w_vec;              // W's slice filled with 16-byte loads
+    int wgs_per_cu;
+    int grid;
+    size_t lds_bytes;
+    int streams() const { return grid / 8 / n_split * 8; }      // as the kernel counts them: whole groups of n_split blocks per XCD
+};
+
+LdsForm lds_form(int dtype, int n_work, int m_fea, int n_feat, const void *W, int64_t ldw, const void *H, int64_t ldh)
+{
+    LdsForm f{};
+    f.lpr = choose_lpr(dtype, m_fea, n_feat);
+    if (f.lpr < 2) return f;
+    const int64_t es = dtype == SGX_F16 ? 2 : 4;
+    const int cp = f.lpr * (int)(16 / es);             // columns per slice
+    f.lds_bytes = (size_t)(m_fea + 1) * f.lpr * 16;
+    f.n_split = (n_feat + cp - 1) / cp;
+    f.full = n_feat % cp == 0 && ((uintptr_t)H % 16 == 0) && ((ldh * es) % 16 == 0);
+    f.w_vec = ((uintptr_t)W % 16 == 0) && ((ldw * es) % 16 == 0);
+    f.wgs_per_cu = f.lds_bytes * 2 <= kLdsBudget ? 2 : 1;       // 32 wavefronts per CU at most
+    int grid = device_cus() / 8 * 8 * f.wgs_per_cu;
+    // no more streams than row tiles
+    const int64_t tiles = ((int64_t)n_work + 64 * kWaves - 1) / (64 * kWaves);
+    const int64_t want = (tiles + 7) / 8 * 8 * f.n_split;
+    if (want < grid) grid = (int)want;
+    // test and probe override: fewer streams, so that a small matrix makes every wavefront walk several windows
+    if (sgx_tune().xw_sparse_streams > 0) {
+        const int streams = sgx_tune().xw_sparse_streams / 8 * 8;
+        const int cap = (streams < 8 ? 8 : streams) * f.n_split;
+        if (cap < grid) grid = cap;
+    }
+    if (grid < 8 * f.n_split) grid = 8 * f.n_split;
+    f.grid = grid;
+    return f;
+}
+
+template <typename T, int VEC, int LPR, bool FULL>
+int launch_lds_impl(const LdsForm &f, int n_work, int n_feat, int m_fea, const int32_t *rowptr, const int32_t *col, const void *val,
+                    const void *W, int64_t ldw, void *H, int64_t ldh, int64_t nnz, const uint8_t *win_order, sgx_epilogue ep,
+                    hipStream_t stream)
+{
+    auto kernel = xw_sparse_lds_kernel<T, VEC, LPR, FULL>;
+    static bool attr_set = false;                     // per instantiation
+    if (!attr_set) {
+        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)kLdsBudget) != hipSuccess)
+            return SGX_ERR_HIP;
+        attr_set = true;
+    }
+    hipLaunchKernelGGL(kernel, dim3(f.grid), dim3(kThreads), f.lds_bytes, stream, n_work, n_feat, m_fea, rowptr, col,
+                       (const T *)val, (const T *)W, ldw, f.w_vec, (T *)H, ldh, f.n_split, (unsigned)(nnz * 4), win_order, ep);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}
+
+template <typename T, int VEC, int LPR>
+int launch_lds(const LdsForm &f, int n_work, int n_feat, int m_fea, const int32_t *rowptr, const int32_t *col, const void *val,
+               const void *W, int64_t ldw, void *H, int64_t ldh, int64_t nnz, const uint8_t *win_order, sgx_epilogue ep,
+               hipStream_t stream)
+{
+    return f.full ? launch_lds_impl<T, VEC, LPR, true>(f, n_work, n_feat, m_fea, rowptr, col, val, W, ldw, H, ldh, nnz, win_order, ep, stream)
+                  : launch_lds_impl<T, VEC, LPR, false>(f, n_work, n_feat, m_fea, rowptr, col, val, W, ldw, H, ldh, nnz, win_order, ep, stream);
 }
 
 }  // namespace
@@ -535,14 +567,14 @@ int sgx_xw_sparse_lds(int dtype, int n_rows, int m_fea, int n_feat, const int32_
                       sgx_epilogue ep, hipStream_t stream)
 {
     const int n_work = n_rows;            // rows are dealt by length inside windows of 64 (plan->win_order), not in the plan's degree order
-    const int lpr = choose_lpr(dtype, m_fea, n_feat);
+    const LdsForm f = lds_form(dtype, n_work, m_fea, n_feat, W, ldw, H, ldh);
 #define SGX_LDS_CASE(L)                                                                                                     \
     case L:                                                                                                                 \
-        return dtype == SGX_F16 ? launch_lds<f16, 8, L>(n_work, n_feat, m_fea, rowPtr, columnIndex, values, W, ldw, H, ldh, \
-                                                        plan->nnz, plan->win_order, ep, stream)                               \
-                                : launch_lds<float, 4, L>(n_work, n_feat, m_fea, rowPtr, columnIndex, values, W, ldw, H,    \
+        return dtype == SGX_F16 ? launch_lds<f16, 8, L>(f, n_work, n_feat, m_fea, rowPtr, columnIndex, values, W, ldw, H,   \
+                                                        ldh, plan->nnz, plan->win_order, ep, stream)                        \
+                                : launch_lds<float, 4, L>(f, n_work, n_feat, m_fea, rowPtr, columnIndex, values, W, ldw, H, \
                                                           ldh, plan->nnz, plan->win_order, ep, stream);
-    switch (lpr) {
+    switch (f.lpr) {
         SGX_LDS_CASE(2)
         SGX_LDS_CASE(4)
         SGX_LDS_CASE(8)
@@ -550,4 +582,18 @@ int sgx_xw_sparse_lds(int dtype, int n_rows, int m_fea, int n_feat, const int32_
     default: return SGX_ERR_UNSUPPORTED;
     }
 #undef SGX_LDS_CASE
+}
+
+// Which form sgx_xw_sparse takes for these operands (include/sgx.h): the gate of sgx_spmm_launch and the arm of the launch
+// above, from the functions they use.
+extern "C" int sgx_xw_sparse_form(int dtype, int n_rows, int M_fea, int P, const void *W, int64_t ldw, const void *H, int64_t ldh,
+                                  const sgx_plan *plan)
+{
+    if ((dtype != SGX_F16 && dtype != SGX_F32) || n_rows < 1 || M_fea < 0 || P < 1 || ldw < P || ldh < P) return 0;
+    if (plan && plan->n_rows != n_rows) return 0;
+    if (sgx_spmm_table_big(dtype, M_fea, ldw, P)) return 0;
+    if (!sgx_xw_sparse_lds_applicable(dtype, n_rows, M_fea, P, ldh, plan)) return 0;
+    const LdsForm f = lds_form(dtype, n_rows, M_fea, P, W, ldw, H, ldh);
+    if (f.lpr < 2) return 0;
+    return f.lpr | f.n_split << 8 | f.full << 16 | f.w_vec << 17 | f.wgs_per_cu << 18 | f.streams() << 20;
 }

@@ -4,6 +4,7 @@ PyTorch is plumbing here: it owns device memory and the stream.  Every function 
 device pointers to libsgx.so and returns torch tensors that alias buffers the call filled.
 All tensors must live on a ROCm device ("cuda"); nothing in this module computes on the CPU.
 """
+import collections
 import ctypes
 
 import numpy as np
@@ -341,15 +342,19 @@ def _gatherable(H, n_feat=None, nnz=0):
     table whose pitch lets rows straddle 128-byte lines (100 halves) is copied too when every row is gathered
     often enough (32 edges per table row) for the 18-25 % the gathers gain to outweigh the copy."""
     n_feat = H.shape[1] if n_feat is None else n_feat
-    if (H.stride(0) * H.element_size()) % 4 == 0 and H.data_ptr() % 4 == 0:
-        straddles = H.stride(0) != table_pitch(n_feat, H.element_size()) and (H.stride(0) * H.element_size()) % 128 != 0
-        if not (straddles and H.shape[0] * n_feat >= (1 << 22) and nnz >= 32 * H.shape[0]):
-            return H
-    elif H.shape[0] * n_feat < (1 << 16):
+    if not _gatherable_copies(H, n_feat, nnz):
         return H
     padded = torch.empty((H.shape[0], table_pitch(n_feat, H.element_size())), dtype=H.dtype, device=H.device)
     padded[:, :n_feat] = H[:, :n_feat]
     return padded
+
+
+def _gatherable_copies(H, n_feat, nnz):
+    """whether _gatherable copies the table (into fresh rows of table_pitch() elements) instead of passing it on"""
+    if (H.stride(0) * H.element_size()) % 4 == 0 and H.data_ptr() % 4 == 0:
+        straddles = H.stride(0) != table_pitch(n_feat, H.element_size()) and (H.stride(0) * H.element_size()) % 128 != 0
+        return straddles and H.shape[0] * n_feat >= (1 << 22) and nnz >= 32 * H.shape[0]
+    return H.shape[0] * n_feat >= (1 << 16)
 
 
 def spmm(adj, H, relu=False, n_feat=None, out=None, use_plan=True, acc_mode=SGX_ACC_F32, spmm_block=1):
@@ -392,6 +397,33 @@ def xw_sparse(X, W, out=None, use_plan=True):
                             _ptr(X.val), _ptr(W), W.stride(0), _ptr(out), out.stride(0),
                             plan.handle if plan is not None else None, _ptr(scratch), sbytes, _stream()), "sgx_xw_sparse")
     return out
+
+
+XwSparseForm = collections.namedtuple("XwSparseForm", "lpr n_split full w_vec wgs_per_cu streams")
+
+
+def xw_sparse_form(X, W, out=None, use_plan=True):
+    """Which kernel form xw_sparse(X, W, out) takes (sgx_xw_sparse_form; no launch): None = the gather kernel, otherwise the
+    LDS form's arm -- lanes per row, column slices, 16-byte stores, 16-byte fills of W's slice, workgroups per CU, row-tile
+    streams of the grid.  The operands are prepared as xw_sparse prepares them, without the copy of W it may make (a copy
+    is 16-byte aligned at a pitch of table_pitch() elements, which is all the answer depends on)."""
+    _dev2d(W, "W")
+    P = W.shape[1]
+    if _gatherable_copies(W, P, X.nnz):
+        w_ptr, ldw = None, table_pitch(P, W.element_size())
+    else:
+        w_ptr, ldw = _ptr(W), W.stride(0)
+    if out is None:                                         # a fresh [n_rows, P] tensor: aligned, unpadded
+        h_ptr, ldh = None, P
+    else:
+        out = _out(out, X.n_rows, P, W.dtype, W.device)
+        h_ptr, ldh = _ptr(out), out.stride(0)
+    plan = X.plan if (use_plan and X.wants_plan) else None
+    word = lib.sgx_xw_sparse_form(dtype_code(W.dtype), X.n_rows, X.n_cols, P, w_ptr, ldw, h_ptr, ldh,
+                                  plan.handle if plan is not None else None)
+    if word == 0:
+        return None
+    return XwSparseForm(word & 0xFF, (word >> 8) & 0xFF, bool(word >> 16 & 1), bool(word >> 17 & 1), (word >> 18) & 3, word >> 20)
 
 
 def spmm_acc(adj, H, relu=False, acc_in=None, partial_out=False, out=None, use_plan=True):

@@ -54,6 +54,13 @@ SHAPES = [
 ]
 
 
+# what sgx_xw_sparse_form answers for SHAPES at 70 001 rows: (lanes per row, slices), None = the gather kernel (8 fp16 columns
+# are one lane's 16 bytes, and one-lane rows stay with it)
+FORMS = {(torch.float16, 1433, 64): (4, 2), (torch.float16, 500, 64): (8, 1), (torch.float16, 3703, 21): (2, 2),
+         (torch.float16, 1433, 47): (4, 2), (torch.float16, 700, 8): None, (torch.float16, 300, 200): (16, 2),
+         (torch.float32, 1433, 64): (4, 4), (torch.float32, 300, 16): (4, 1), (torch.float32, 1000, 41): (8, 2)}
+
+
 @pytest.mark.parametrize("dtype,M,P,_what", SHAPES)
 def test_lds_path_equals_gather_kernel_and_oracle(sgx, oracle, dtype, M, P, _what):
     n = 70_001
@@ -63,6 +70,8 @@ def test_lds_path_equals_gather_kernel_and_oracle(sgx, oracle, dtype, M, P, _wha
     g = torch.Generator(device="cuda")
     g.manual_seed(7)
     W = ((torch.rand((M, P), generator=g, device="cuda") * 2 - 1) / 8).to(dtype)
+    form = sgx.xw_sparse_form(X, W)
+    assert (form and (form.lpr, form.n_split)) == FORMS[(dtype, M, P)]
     got = sgx.xw_sparse(X, W)
     ref = sgx.spmm(X, W, relu=False)                       # the gather kernel (A.H entry point), same operands
     assert torch.equal(got, ref)
@@ -90,6 +99,7 @@ def test_lds_path_inside_the_layer(sgx):
     g = torch.Generator(device="cuda")
     g.manual_seed(11)
     Wt = ((torch.rand((P, M), generator=g, device="cuda") * 2 - 1) / 8).half()
+    assert sgx.xw_sparse_form(X, sgx.transpose(Wt))[:2] == (4, 2)
     got = sgx.layer_forward(eye, X, Wt, relu=True)
     H = sgx.spmm(X, sgx.transpose(Wt), relu=False)
     assert torch.equal(got, torch.where(H > 0, H, torch.zeros_like(H)))
@@ -106,6 +116,7 @@ def test_lds_path_degree_ordered_plan(sgx):
     g = torch.Generator(device="cuda")
     g.manual_seed(3)
     W = ((torch.rand((M, P), generator=g, device="cuda") * 2 - 1) / 8).half()
+    assert sgx.xw_sparse_form(X, W)[:2] == (4, 2)
     assert torch.equal(sgx.xw_sparse(X, W), sgx.spmm(X, W, relu=False))
 
 
@@ -118,5 +129,6 @@ def test_lds_path_empty_slots_read_the_zero_row(sgx):
     X = sgx.Csr(rp, col, val, M)
     W = torch.full((M, P), 0.25, dtype=torch.float16, device="cuda")
     W[0] = float("inf")
+    assert sgx.xw_sparse_form(X, W)[:2] == (4, 2)
     got = sgx.xw_sparse(X, W)
     assert torch.isfinite(got.float()).all()
