@@ -42,7 +42,10 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
     python examples/molecule_gcn_train.py --batch-size 64 --layer-count 2 --train-stack --trainer --replay [--model gat]
         --replay on the shuffled batches of the device loader: every full batch arrives padded to one fixed capacity
         (pyg_lite.GraphLoader(pad=True)), and one recorded step -- collation, plan table, forward, loss head, backward,
-        Adam -- serves every batch of every epoch (StackTrainer.capture_loader); the short last batch runs eagerly
+        Adam -- serves every batch of every epoch (StackTrainer.capture_loader); the short last batch runs eagerly.
+        With --trainer the accuracies are counted on the device (StackTrainer.evaluate) and read back in one transfer per
+        epoch; with --replay --batch-size N the evaluation replays as well (StackTrainer.capture_eval_loader over
+        unshuffled padded loaders of the train and test sets).  Without --trainer nothing changes
 """
 import argparse
 import json
@@ -131,11 +134,35 @@ def main():
             model.train()
             replay = trainer.capture(train.x, train.edge_index, train.batch, train.y)
 
+    eval_passes = None
+    if replay_epoch is not None:
+        # the accuracy pass replayed too: one recorded evaluation per set over unshuffled padded loaders
+        prepared = dict(dtypes=loader.dtypes, prepare=loader.prepare) if args.model == "gat" else {}
+        eval_passes = [trainer.capture_eval_loader(G.GraphLoader(gs, batch_size=args.batch_size, shuffle=False, device=dev,
+                                                                 pad=True, **prepared))
+                       for gs in (loader.graphs, graphs[50:100])]
+
     def accuracy(batch):
         model.eval()
         with torch.no_grad():
             pred = model(args.acc, batch.x, batch.edge_index, batch.batch).argmax(dim=1)
         return float((pred == batch.y).float().mean())
+
+    def accuracies():
+        """(train, test) accuracy.  With --trainer the hits are counted on the device (StackTrainer.evaluate, or the
+        replayed passes) and both sets' counts come back in ONE transfer; the quotient is the float32 one of accuracy()."""
+        if trainer is None:
+            return accuracy(train), accuracy(test)
+        from sgracex1_amd.train import EvalSums
+        if eval_passes is not None:
+            for run_pass in eval_passes:
+                run_pass()
+            sums = [run_pass.sums for run_pass in eval_passes]
+        else:
+            sums = [EvalSums(dev), EvalSums(dev)]
+            for b, into in zip((train, test), sums):
+                trainer.evaluate(b.x, b.edge_index, b.batch, b.y, into=into)
+        return [float(np.float32(hits) / np.float32(n)) for n, hits, _ in EvalSums.read(*sums)]
 
     best, log = 0.0, []
     for epoch in range(1, args.epochs + 1):
@@ -161,7 +188,7 @@ def main():
                 steps += 1
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / steps
-        tr, te = accuracy(train), accuracy(test)
+        tr, te = accuracies()
         best = max(best, te)
         log.append({"epoch": epoch, "loss": round(float(loss.detach()), 4), "train_acc": round(tr, 4),
                     "test_acc": round(te, 4), "step_ms": round(dt * 1e3, 3)})

@@ -1569,6 +1569,44 @@ int sgx_node_loss(int64_t n_rows, int64_t n_prefix, int P, int C, const float *H
                   const int64_t *step_dev, float grad_scale, float *loss, int64_t *counts, float *logits, float *grad_H,
                   float *grad_W, float *grad_bias, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- the evaluation head: hits and the summed loss of a pass, kept on the device across batches --------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_head_eval is the evaluation of GCN_PYNQ / GAT_POOL_PYNQ behind the pooled means -- Linear [C][P], arg-max against
+ * the label, CrossEntropyLoss(reduction = sum) -- for one batch of a pass over a loader.  It ADDS to accumulators the
+ * caller zeroes once per pass, so batches of unequal size accumulate on the device and a pass is read back once
+ * (sgx_node_loss's counts are overwritten per call and its loss is that call's mean).  pooled [n_graphs][P], W [C][P],
+ * bias [C] or NULL fp32, target int64 [n_graphs], all on the device.  Rows n_real .. n_graphs - 1 are the filler graphs
+ * of a padded batch.
+ *   logits     z[g][c] of sgx_head_loss with p_drop = 0, bit for bit (x == pooled; 64 lanes, lane l an fmaf chain from
+ *              0 over j = l, l + 64, ...; the xor butterfly 32, 16, .. 1; then + bias[c], 0 without a bias)
+ *   per row g < n_real:  sgx_head_loss's per-row term, bit for bit: m = max_c z_c;  lse = m + logf(sum_c expf(z_c - m)),
+ *              c ascending from 0;  loss_g = lse - z[target_g]
+ *              hit_g: arg-max of z[g] == target_g, sgx_node_loss's arg-max: over c ascending with a strict > from z[0]
+ *              (a NaN z[0] counts as -inf): the lowest index wins a tie (torch's rule), a NaN never wins
+ *              a target outside [0, C): loss_g = 0, no hit, nothing is indexed; the row still counts in totals[0]
+ *   the call adds:  totals[0] += n_real;  totals[1] += sum_g hit_g;
+ *              loss_sum[0] += (double)loss_0 + (double)loss_1 + ... : the rows' fp32 losses added from 0.0 in row order
+ *              in double, and that double added to loss_sum[0] once
+ *   rows n_real .. n_graphs - 1 are never read for the sums (they may hold anything, NaN included); without `logits` they
+ *              are not read at all.  logits, when given, receives all n_graphs rows.
+ *   n_real = 0 is valid: nothing is added; only `logits` is written.
+ * Two launches, as sgx_head_loss: a wavefront per row, every row's loss to a slot of its own in the workspace and the
+ * hit counts (integers) per wavefront, so nothing that is summed depends on the grid; then one workgroup adds the slots
+ * in row order and adds to the accumulators.  No atomics: the same bits on every run, for any grid and on every device.
+ * Capturable: no allocation, no synchronisation.  The accumulators are read and written by the launch, on the stream.
+ *
+ * Limits: sgx_head_loss's, P <= 1024, C <= 64; beyond: SGX_ERR_UNSUPPORTED and a workspace size of 0.
+ * Argument errors, returned before anything reaches the device: n_graphs, P or C below 1, n_real outside 0 .. n_graphs:
+ * SGX_ERR_SHAPE; pooled, W, target, totals or loss_sum NULL: SGX_ERR_NULL (bias NULL: no bias; logits NULL: not
+ * written); over a limit: SGX_ERR_UNSUPPORTED; workspace missing or below sgx_head_eval_workspace_bytes:
+ * SGX_ERR_WORKSPACE; not 256-byte aligned: SGX_ERR_ALIGN. */
+/* 256 + n_graphs floats rounded up to 256 bytes + 4096; 0 for a shape the call refuses */
+size_t sgx_head_eval_workspace_bytes(int n_graphs, int P, int C);
+int sgx_head_eval(int n_graphs, int n_real, int P, int C, const float *pooled, const float *W, const float *bias,
+                  const int64_t *target, int64_t *totals /* [2] */, double *loss_sum /* [1] */, float *logits /* or NULL */,
+                  void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -55,6 +55,7 @@ SYMBOLS = [
     "sgx_quant_stack_backward_workspace_bytes", "sgx_quant_stack_backward_lds_bytes", "sgx_quant_stack_backward",
     "sgx_head_loss_workspace_bytes", "sgx_head_loss", "sgx_adam_step",
     "sgx_node_loss_workspace_bytes", "sgx_node_loss",
+    "sgx_head_eval_workspace_bytes", "sgx_head_eval",
     "sgx_version", "sgx_status_string", "sgx_reload_env",
 ]
 
@@ -528,6 +529,10 @@ def _load():
     lib.sgx_node_loss.argtypes = [c_i64, c_i64, c_int, c_int, vp, vp, vp, vp, vp, ctypes.c_float, ctypes.c_uint64, ctypes.c_uint64,
                                   vp, ctypes.c_float, vp, vp, vp, vp, vp, vp, vp, sz, vp]
     lib.sgx_node_loss.restype = c_int
+    lib.sgx_head_eval_workspace_bytes.argtypes = [c_int, c_int, c_int]
+    lib.sgx_head_eval_workspace_bytes.restype = sz
+    lib.sgx_head_eval.argtypes = [c_int, c_int, c_int, c_int, vp, vp, vp, vp, vp, vp, vp, vp, sz, vp]
+    lib.sgx_head_eval.restype = c_int
     lib.sgx_version.argtypes = []
     lib.sgx_version.restype = c_int
     lib.sgx_status_string.argtypes = [c_int]

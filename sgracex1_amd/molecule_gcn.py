@@ -296,17 +296,25 @@ class GCN_PYNQ(torch.nn.Module):
             return None
         return ptr, adj, plan
 
-    def _forward_stack(self, x, edge_index, batch):
+    def _forward_stack(self, x, edge_index, batch, head=True):
         """Both layers, the mean pool and the head through ops.gcn_stack_forward: bit-equal to the layer-by-layer
         eval forward below, one launch for a batch of small graphs.  None (the caller then runs the layers one by one)
-        when `batch` is not sorted or an edge joins two of its graphs."""
+        when `batch` is not sorted or an edge joins two of its graphs.  head=False: the pooled means, without the head."""
         ready = self._stack_operands(x, edge_index, batch, backward=False)
         if ready is None:
             return None
         ptr, adj, plan = ready
         weights = [torch.transpose(c.weight, 0, 1).detach().to(ACC_DTYPE).contiguous() for c in (self.conv1, self.conv2)]
-        return ops.gcn_stack_forward(adj, feature_csr(x, ACC_DTYPE), weights, [True, False], ptr, self.lin.weight,
-                                     self.lin.bias, plan=plan)
+        return ops.gcn_stack_forward(adj, feature_csr(x, ACC_DTYPE), weights, [True, False], ptr, self.lin.weight if head else None,
+                                     self.lin.bias if head else None, plan=plan)
+
+    def eval_pooled(self, x, edge_index, batch):
+        """The fused eval route up to the pooled means, for a caller that runs the tail itself (train.StackTrainer.evaluate):
+        what forward(acc = 1, ...) pools in eval mode with gradients off where it takes the one call, None where it would
+        not."""
+        if self.training or torch.is_grad_enabled() or not self._stack_enabled():
+            return None
+        return self._forward_stack(x, edge_index, batch, head=False)
 
     def train_pooled(self, x, edge_index, batch):
         """The fused training route on its own, for a caller that runs the tail itself (train.StackTrainer): the pooled

@@ -2347,3 +2347,33 @@ class NodeLoss(_LossFn):
     @staticmethod
     def forward(ctx, H, weight, bias, target, mask=None, n_prefix=None, p=0.0, seed=0, step=0, step_dev=None):
         return _LossFn._run(ctx, node_loss, H, weight, bias, target, mask, n_prefix, p, seed, step, step_dev)
+
+
+# ---- the tail of an evaluation pass: hits and the summed loss, kept on the device across batches (sgx_head_eval) ---------------
+def head_eval(pooled, weight, bias, target, n_real=None, totals=None, loss_sum=None, want_logits=False):
+    """The Linear head, the arg-max's hits and the summed cross entropy of the first n_real rows (default: all) of pooled,
+    ADDED to accumulators that stay on the device, in one launch (sgx_head_eval; the rule is in include/sgx.h, "the
+    evaluation head").  pooled [G, P] fp32, weight [C, P] fp32, bias [C] fp32 or None, target [G] int64; rows n_real ..
+    G - 1, the filler graphs of a padded batch, reach no sum.  totals: a device int64 [2] that receives += (n_real, hits);
+    loss_sum: a device float64 [1] that receives += the rows' losses; zeroed ones are made where none is passed.  Returns
+    (totals, loss_sum), and the logits [G, C] of every row behind them with want_logits.  Never synchronises."""
+    pooled, w, b = _loss_operands("head_eval", "pooled", pooled, weight, bias, target, None)
+    (G, P), C = pooled.shape, w.shape[0]
+    n_real = G if n_real is None else int(n_real)
+    if not 0 <= n_real <= G:
+        raise ValueError(f"head_eval: n_real = {n_real} is outside 0 .. G = {G}")
+    if totals is None:
+        totals = torch.zeros(2, dtype=torch.int64, device=pooled.device)
+    if loss_sum is None:
+        loss_sum = torch.zeros(1, dtype=torch.float64, device=pooled.device)
+    _dev(totals, "totals"), _dev(loss_sum, "loss_sum")
+    if totals.dtype != torch.int64 or totals.numel() != 2 or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise TypeError("head_eval accumulates into totals int64 [2] and loss_sum float64 [1]")
+    logits = torch.empty((G, C), dtype=torch.float32, device=pooled.device) if want_logits else None
+    nbytes = lib.sgx_head_eval_workspace_bytes(G, P, C)
+    ws = _workspace(pooled.device, nbytes) if nbytes else None
+    check(lib.sgx_head_eval(G, n_real, P, C, _ptr(pooled), _ptr(w), _ptr(b), _ptr(target), _ptr(totals), _ptr(loss_sum),
+                            _ptr(logits), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+          "sgx_head_eval")
+    return (totals, loss_sum, logits) if want_logits else (totals, loss_sum)
+

@@ -530,9 +530,17 @@ class GAT_POOL_PYNQ(Module):
         quants = None if qc is None else (qc.second_layer() if layern == 2 else qc, qc if layern == 2 else qc.second_layer())
         return ptr, plan, fea, masked, quants
 
-    def _forward_stack(self, x, adj, batch):
+    def eval_pooled(self, x, edge_index, batch):
+        """The fused eval route up to the pooled means, for a caller that runs the tail itself (train.StackTrainer.evaluate):
+        what forward pools in eval mode with gradients off where it takes the one call, None where it would not."""
+        if self.training or torch.is_grad_enabled() or not self._stack_enabled():
+            return None
+        return self._forward_stack(x, self._normalised(x, edge_index)[2], batch, head=False)
+
+    def _forward_stack(self, x, adj, batch, head=True):
         """Both layers, the mean pool and the head through ops.gat_stack_forward (ops.quant_stack_forward with the
-        quantiser on); None (the caller then runs the layers one by one) where the stack does not compute what they do."""
+        quantiser on); None (the caller then runs the layers one by one) where the stack does not compute what they do.
+        head=False: the pooled means, without the head."""
         ready = self._stack_operands(x, adj, batch, backward=False)
         if ready is None:
             return None
@@ -540,12 +548,12 @@ class GAT_POOL_PYNQ(Module):
         dt, gat, layers = _torch_dtype(), int(config.compute_attention), (self.att1, self.att2)
         weights = [c.weight.detach().t().to(dt).contiguous() for c in layers]
         atts = [c.attention.detach().to(dt).reshape(-1).contiguous() if gat else None for c in layers]
+        lin_w, lin_b = (self.lin.weight, self.lin.bias) if head else (None, None)
         if quants is not None:
             _program_quant_registers(my_ip.register_map, quants[1])                # the registers of the two layer calls
-            return ops.quant_stack_forward(masked, fea, weights, atts, [True, False], ptr, quants, self.lin.weight,
-                                           self.lin.bias, alpha=self.att1.alpha, plan=plan, adj_quantised=True)
-        return ops.gat_stack_forward(adj, fea, weights, atts, [True, False], ptr, self.lin.weight, self.lin.bias,
-                                     alpha=self.att1.alpha, plan=plan)
+            return ops.quant_stack_forward(masked, fea, weights, atts, [True, False], ptr, quants, lin_w, lin_b,
+                                           alpha=self.att1.alpha, plan=plan, adj_quantised=True)
+        return ops.gat_stack_forward(adj, fea, weights, atts, [True, False], ptr, lin_w, lin_b, alpha=self.att1.alpha, plan=plan)
 
     def _train_stack(self, x, adj, batch):
         """Both layers and the mean pool through ops.GatStack (ops.QuantStack with the quantiser on): the pooled means

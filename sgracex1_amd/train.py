@@ -93,6 +93,9 @@ class StackTrainer(_Trainer):
         loss = replay()
         epoch = trainer.capture_loader(loader)                # a GraphLoader(pad=True): one recorded step for every batch
         losses = epoch()                                      # one shuffled epoch, a loss tensor per batch
+        totals, loss_sum = trainer.evaluate(x, edge_index, batch, y)      # device int64 [graphs, hits], device float64 [1]
+        test = trainer.capture_eval_loader(test_loader)       # a GraphLoader(pad=True): one recorded evaluation for every batch
+        totals, loss_sum = test()                             # one pass over the set, summed on the device
 
     The trainer owns the optimiser state (exp_avg, exp_avg_sq per parameter, the device step counter `t`); its dropout
     stream is ops.head_loss's counter-based mask of (seed, t), not torch's generator.  step() is a training step whatever
@@ -171,16 +174,20 @@ class StackTrainer(_Trainer):
     def _is_padded(self, batch):
         return bool((self._block_facts(batch) or {}).get("padded"))
 
-    def _declined(self, batch):
-        """Why model.train_pooled declined the padded batch of batch vector `batch`, as far as it can be told from outside."""
+    def _declined(self, batch, training=True):
+        """Why model.train_pooled (training=False: model.eval_pooled) declined the padded batch of batch vector `batch`, as
+        far as it can be told from outside."""
         model = self.model
-        if not getattr(model, "train_stack", False):
+        if training and not getattr(model, "train_stack", False):
             return "the model was not built with train_stack=True"
         if not model._stack_enabled():
             return "the register layer_count is under 2 (or the kernels are off): the layers run one by one"
-        if not torch.is_grad_enabled():
+        if training and not torch.is_grad_enabled():
             return "gradients are disabled"
         facts = self._block_facts(batch)
+        if not training:
+            return ("a condition of the model's fused eval route fails on the padded batch (its class docstring lists them): "
+                    "no row of the adjacency may be dead")
         return (f"a condition of the model's fused training route fails on the padded batch (its class docstring lists "
                 f"them); the largest graph of the set has {facts['max_graph'] if facts else '?'} rows, which must be within "
                 f"the backward plan's row budget, and no row of the adjacency may be dead")
@@ -199,48 +206,158 @@ class StackTrainer(_Trainer):
         takes exactly the steps of `for b in loader: step(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs)`.
         The warm-up steps run on a padded batch of the set's smallest graphs without a dead row, on a copy of the state.
         If the model's fused route declines that batch, RuntimeError names the reason: a padded batch never falls back."""
+        def accepts(b):
+            with torch.enable_grad():                  # (before any state is touched: step() raises on a declined padded batch)
+                if self.model.train_pooled(b.x, b.edge_index, b.batch) is None:
+                    raise RuntimeError(f"StackTrainer.capture_loader: the fused route declined the padded batch: {self._declined(b.batch)}")
+
+        replay, c, walk = self._capture_padded(loader, warmup, "capture_loader", accepts,
+                                               lambda b: self.step(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs),
+                                               counters=("fused_steps",))
+
+        def epoch():
+            losses = []
+            walk(lambda loss: losses.append(loss.clone()),
+                 lambda e: losses.append(self.step(e.x, e.edge_index, e.batch, e.y, e.num_real_graphs)))
+            return losses
+
+        epoch.graph, epoch.collated = replay.graph, c
+        return epoch
+
+    def _capture_padded(self, loader, warmup, name, accepts, run_batch, counters=()):
+        """What capture_loader and capture_eval_loader share: ONE recording of run_batch(b) on the padded batch b of
+        `loader` (a pyg_lite.GraphLoader(pad=True); anything else: ValueError) behind its collation -> (replay, the
+        capacity-sized ops.Collated the recording reads, walk).  The recording runs on a padded batch of the set's
+        smallest graphs without a dead row; accepts(b) raises first where the model would decline it.  walk(replayed,
+        eager) takes one pass over the loader as iterating it would (one draw from its generator): the graph ids and
+        offsets of all its padded batches are uploaded once (pinned, non-blocking), and per padded batch that batch's row
+        is copied into the static index buffer (device to device), the recording replayed and replayed(what run_batch
+        returned) called; a batch that arrives unpadded is collated unpadded and handed to eager(batch) in its place."""
         from . import pyg_lite
         if not getattr(loader, "pad", False):
-            raise ValueError("capture_loader takes a GraphLoader(pad=True)")
+            raise ValueError(f"{name} takes a GraphLoader(pad=True)")
         gs, cap, B = loader.graphs, loader.capacity, loader.capacity.batch_size
         rows = gs.counts[0]
         dead = loader.extras.prepared.has_dead if loader.extras is not None else np.zeros(len(gs), dtype=bool)
         first = [int(g) for g in np.argsort(rows, kind="stable") if not dead[g]][:B]
         if len(first) < B or not loader.padded(first):
-            raise RuntimeError("capture_loader: the set has no padded batch without a dead-row graph to record a step on")
+            raise RuntimeError(f"{name}: the set has no padded batch without a dead-row graph to record a step on")
         index = gs.prepare(first)                      # the static index buffer: every replay reads this address
         c = ops.collate_graphs(gs, index, loader.dtypes, extras=loader.extras, pad=cap)
         b = pyg_lite.attach_batch(c)
 
         def run():
             ops.collate_graphs(gs, index, loader.dtypes, out=c, extras=loader.extras, pad=cap)
-            return self.step(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs)
+            return run_batch(b)
 
-        with torch.enable_grad():                      # (before any state is touched: step() raises on a declined padded batch)
-            if self.model.train_pooled(b.x, b.edge_index, b.batch) is None:
-                raise RuntimeError(f"StackTrainer.capture_loader: the fused route declined the padded batch: {self._declined(b.batch)}")
-        replay = self._capture((), warmup, counters=("fused_steps",), run=run)
+        accepts(b)
+        replay = self._capture((), warmup, counters=counters, run=run)
         counts = gs.counts if gs._sym_norm2 is None else gs.counts + (gs._sym_norm2.counts,)
 
-        def epoch():
+        def walk(replayed, eager):
             batches = loader.batches()
             recorded = [loader.padded(ids) for ids in batches]
             host = [ops.batch_offsets(counts, ids)[0] for ids, r in zip(batches, recorded) if r]
             if host:
                 dev = torch.from_numpy(np.stack(host)).pin_memory().to(gs.device, non_blocking=True)
-            losses, k = [], 0
+            k = 0
             for ids, r in zip(batches, recorded):
                 if r:
                     index.refill(dev[k], ids)
                     k += 1
-                    losses.append(replay().clone())
+                    replayed(replay())
                 else:
-                    e = loader.collate(ids)
-                    losses.append(self.step(e.x, e.edge_index, e.batch, e.y, e.num_real_graphs))
-            return losses
+                    eager(loader.collate(ids))
 
-        epoch.graph, epoch.collated = replay.graph, c
-        return epoch
+        return replay, c, walk
+
+    def evaluate(self, x, edge_index, batch, y, n_real=None, into=None):
+        """One batch of an evaluation pass -> (totals, loss_sum), device tensors: totals int64 [2] = (graphs, graphs whose
+        arg-max class is the label), loss_sum float64 [1] = their summed cross entropy.  into: an EvalSums to ADD to (the
+        batches of a pass accumulate on the device; the tensors returned are its own); a fresh zeroed one otherwise.
+        n_real: the real graph count of a padded batch (Batch.num_real_graphs); the filler graphs behind them reach no sum.
+
+        The model runs in eval mode (its mode is put back) with gradients off: its fused eval forward up to the pooled
+        means (model.eval_pooled), then ops.head_eval -- no logits leave the device, nothing synchronises, and no
+        parameter, moment or `t` is touched.  Where the fused route declines a batch the layers run one by one
+        (model.layers_pooled) with the same tail, as in step(); a padded batch is refused there with step()'s
+        RuntimeError, and so is a batch whose `batch` vector is not sorted (its pooling exists only inside the model's
+        forward)."""
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                pooled = model.eval_pooled(x, edge_index, batch)
+                if pooled is None:
+                    if self._is_padded(batch):
+                        raise RuntimeError(f"StackTrainer.evaluate: the fused route declined a padded batch: "
+                                           f"{self._declined(batch, training=False)}")
+                    pooled = model.layers_pooled(x, edge_index, batch)
+                if pooled is None:
+                    raise RuntimeError("StackTrainer.evaluate: `batch` is not sorted (or the kernels are off): the model pools "
+                                       "inside its own forward")
+                if into is None:
+                    into = EvalSums(pooled.device)
+                pooled = pooled.float().contiguous()
+                if n_real is not None and y.shape[0] == n_real < pooled.shape[0]:
+                    pooled = pooled[:n_real]           # the labels of the real graphs only
+                ops.head_eval(pooled, model.lin.weight, model.lin.bias, y, n_real=n_real, totals=into.totals,
+                              loss_sum=into.loss_sum)
+        finally:
+            model.train(was_training)
+        return into.totals, into.loss_sum
+
+    def capture_eval_loader(self, loader, warmup=2):
+        """ONE recorded evaluation for every padded batch of `loader` (a pyg_lite.GraphLoader(pad=True), shuffled or not)
+        -> a callable that runs a whole pass and returns (totals, loss_sum) on the device, as evaluate() gives them.
+
+        The recording is the padded collation (with the cached plans' table launches behind it), the fused eval forward
+        and ops.head_eval on the real graphs, adding into one EvalSums -- capture_loader's machinery (_capture_padded)
+        around evaluate() in place of step().  A pass zeroes the sums (one launch), replays every padded batch and runs
+        the batches that arrive unpadded -- the short last batch among them -- through evaluate() into the same sums:
+        every graph of the set is counted exactly once, and the pass equals
+        `for b in loader: evaluate(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs, into=sums)` bit for bit.  Nothing
+        synchronises; the tensors returned are the pass's own (pass.sums), overwritten by the next pass.  If the model's
+        fused eval route declines the padded batch, RuntimeError names the reason: a padded batch never falls back."""
+        sums = None
+
+        def accepts(b):
+            nonlocal sums
+            sums = EvalSums(b.x.device)
+            one(b)                                     # raises where the fused route declines the padded batch
+
+        def one(b):
+            return self.evaluate(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs, into=sums)
+
+        replay, c, walk = self._capture_padded(loader, warmup, "capture_eval_loader", accepts, one)
+
+        def run_pass():
+            sums.zero_()
+            walk(lambda _: None, one)
+            return sums.totals, sums.loss_sum
+
+        run_pass.graph, run_pass.collated, run_pass.sums = replay.graph, c, sums
+        return run_pass
+
+
+class EvalSums:
+    """The accumulators of an evaluation pass, on the device: totals int64 [2] = (graphs, hits) and loss_sum float64 [1],
+    views of one 24-byte buffer (`buffer`, int64 [3]: one zero_() clears them, one copy reads them back)."""
+
+    def __init__(self, device):
+        self.buffer = torch.zeros(3, dtype=torch.int64, device=device)
+        self.totals, self.loss_sum = self.buffer[:2], self.buffer[2:].view(torch.float64)
+
+    def zero_(self):
+        self.buffer.zero_()
+        return self
+
+    @staticmethod
+    def read(*sums):
+        """[(graphs, hits, loss_sum)] of several EvalSums on the host, by ONE device-to-host copy (it synchronises)."""
+        host = torch.stack([s.buffer for s in sums]).cpu()
+        return [(int(row[0]), int(row[1]), float(row[2:].view(torch.float64)[0])) for row in host]
 
 
 class NodeTrainer(_Trainer):
