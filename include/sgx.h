@@ -253,7 +253,17 @@ typedef struct sgx_layer_desc {
      * With a dense X narrower than the output (M_fea < P_w: ogbn-products' 100 -> 256) aggregating first,
      * D = act((A.X).W), gathers M_fea instead of P_w columns per edge: the same sums in another association,
      * one rounding to the storage type in between as in the reference's order (Z = A.X in place of H).
-     * Only gemm_mode 1, gat_mode 0, SGX_ACC_F32, no quant block; SGX_ERR_UNSUPPORTED otherwise. */
+     * Only gemm_mode 1, gat_mode 0, SGX_ACC_F32, no quant block; SGX_ERR_UNSUPPORTED otherwise.
+     * A square dense fp16 layer (gemm_mode 1, M_fea = P_w = 64, GCN aggregate, SGX_ACC_F32, no quant block) runs as ONE
+     * launch, the aggregation of X with W applied in its epilogue: D = act(f16(A.X).W), neither H nor Z in memory and no
+     * workspace.  Under SGX_ORDER_AGGREGATE_FIRST that is bit-equal to the two launches.  SGX_ORDER_REFERENCE MAY apply W
+     * after the aggregation for this shape too, and does: both associations gather 64 columns per edge, and the default
+     * arithmetic is bound to the reference within a tolerance, not bit for bit (SGX_ACC_REF_HALF, which is, keeps the
+     * reference's order).  The fused form needs a table below 4 GiB, X on a 4-byte boundary and a plan_adj that is
+     * absent or neither cuts rows into tasks nor lists them in degree order; otherwise, or with
+     * SGX_LAYER_NO_FUSED_DENSE set in the environment, the layer runs the staged launches of its order.
+     * sgx_layer_workspace_bytes answers for the form the descriptor it is given will take: size the workspace with the
+     * descriptor that runs, pointers and plans set. */
     int32_t order;
 } sgx_layer_desc;
 
@@ -534,7 +544,9 @@ int sgx_sample_neighbors(const int32_t *rowPtr, const int32_t *columnIndex, int 
  *
  * Semantics: exactly the chain
  *     sgx_layer_forward(layer 0) -> ... -> sgx_layer_forward(layer n_layers-1) -> sgx_readout_mean_linear
- * (GCN aggregate, SGX_ACC_F32, no plans), with the same rounding points:
+ * (GCN aggregate, SGX_ACC_F32, no plans; every layer as its two stages, sgx_xw_dense / sgx_xw_sparse then sgx_spmm_csr --
+ * also the square dense fp16 layer that sgx_layer_forward itself runs with W applied after the aggregation, see
+ * sgx_layer_desc.order), with the same rounding points:
  *     H_l = dtype(X_l . W_l)            summed in fp32;  X_0 = the features, X_l = D_{l-1}
  *     D_l = dtype(act_l(A . H_l))       act_l = ReLU where layer[l].relu, else identity
  *     pooled[g][:] = fp32 mean of the rows of graph g of D_{n_layers-1};  logits = bias + W_head . pooled (fp32)

@@ -40,6 +40,18 @@ bool int8_form(const sgx_layer_desc *d)
     return (d->quant->flags & SGX_QUANT_INT8_AUTO) && d->M_fea > 128;
 }
 
+// The fused form of a square dense fp16 layer: D = act(f16(A.X) . W) in ONE launch, W applied in the aggregation's epilogue
+// (spmm_dense_f16_kernel, spmm_csr.hip), neither H nor Z in memory.  Under SGX_ORDER_AGGREGATE_FIRST it gives the bits of the
+// two launches; under SGX_ORDER_REFERENCE it is the association the layer takes for this shape -- both gather 64 columns per
+// edge, and the default arithmetic is bound to the reference by a tolerance, not bit for bit (SGX_ACC_REF_HALF is, and stays
+// on the reference's order).  X comes dense at pitch M_fea = 64.
+bool fused_dense_form(const sgx_layer_desc *d)
+{
+    if (d->dtype != SGX_F16 || d->gemm_mode != 1 || d->gat_mode || d->quant || d->acc_mode != SGX_ACC_F32) return false;
+    if (d->M_fea != 64 || d->P_w != 64 || sgx_tune().layer_no_fused_dense) return false;
+    return sgx_spmm_dense_applicable(d->M_adj, d->values_fea, d->B, d->D, d->plan_adj);
+}
+
 Carve carve(const sgx_layer_desc *d)
 {
     Carve c;
@@ -48,6 +60,13 @@ Carve carve(const sgx_layer_desc *d)
     const size_t es = sgx_elem_size(d->dtype);
     const size_t ldh = (size_t)sgx_ldh(d->dtype, d->P_w);
     size_t off = 0;
+    if (fused_dense_form(d)) {
+        c.h_off = c.w_off = c.s_off = c.g_off = c.q_off = 0;
+        c.h_bytes = c.w_bytes = c.s_bytes = c.g_bytes = c.q_bytes = 0;
+        c.qb = c.qx = c.qa = c.qt = 0;
+        c.total = 0;
+        return c;
+    }
     if (d->order == SGX_ORDER_AGGREGATE_FIRST) {
         // Z = A.X  [N_adj][ldz] takes the place of H; split-row partials are M_fea wide
         const size_t ldz = (size_t)sgx_ldh(d->dtype, d->M_fea);
@@ -146,10 +165,20 @@ int layer_forward(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *str
     if (!d->B || !d->D || !d->rowPtr_adj || !d->values_fea) return SGX_ERR_NULL;
     if (d->gemm_mode == 0 && (!d->rowPtr_fea)) return SGX_ERR_NULL;
     const Carve c = carve(d);
+    hipStream_t s = (hipStream_t)stream;
+    if (fused_dense_form(d)) {
+        // one launch, no workspace: the aggregation of X with W in its epilogue (either order, see fused_dense_form)
+        if (!d->values_adj && d->M_adj > 0) return SGX_ERR_NULL;
+        if (d->ev_agg_begin) SGX_HIP_CHECK(hipEventRecord((hipEvent_t)d->ev_agg_begin, s));
+        rc = sgx_spmm_dense(d->relu, d->N_adj, d->M_adj, d->rowPtr_adj, d->columnIndex_adj, d->values_adj, d->values_fea, d->B,
+                            d->D, s);
+        if (rc != SGX_OK) return rc;
+        if (d->ev_agg_end) SGX_HIP_CHECK(hipEventRecord((hipEvent_t)d->ev_agg_end, s));
+        return SGX_OK;
+    }
     if (!d->workspace || d->workspace_bytes < c.total) return SGX_ERR_WORKSPACE;
     if ((uintptr_t)d->workspace % 256 != 0) return SGX_ERR_ALIGN;
 
-    hipStream_t s = (hipStream_t)stream;
     char *ws = (char *)d->workspace;
     void *H = ws + c.h_off;
     void *W = ws + c.w_off;

@@ -32,6 +32,8 @@ struct sgx_tuning {
     bool xw_no_wlds, xw_no_stationary_f32, xw_sparse_no_lds, xw_short_tiles, xw_no_lds;
     bool xtg_scalar, xtg_wave_tiles;
     bool spmm_no_short_tail;      // the one-step tail of a degree order through the sblock path (as in round 2)
+    bool layer_no_fused_dense;    // a square dense fp16 layer as two launches (X.W, then A.H) instead of the fused aggregation
+    int spmm_fused_blocks_per_cu; // 0 = unset: grid cap of the fused aggregation (workgroups per CU; tools and probes)
     int spmm_cpl;                 // 0 = unset
     int xw_sparse_lpr;            // 0 = unset: lanes per row (slice width / 16 bytes) of the sparse X.W stage's LDS form, at most
     int xw_sparse_streams;        // 0 = unset: streams of row tiles of that form, at most (whole groups of 8; tests and probes)
@@ -138,6 +140,14 @@ int sgx_spmm_launch(int dtype, int acc_mode, int spmm_block, int relu, int n_row
 
 // whether a gathered table [n_cols][ldh] is past what 32-bit buffer offsets reach (spmm_csr.hip): 64-bit pointers then
 bool sgx_spmm_table_big(int dtype, int n_cols, int64_t ldh, int n_feat);
+
+// The aggregation of a square dense fp16 layer with W applied in its epilogue (spmm_csr.hip): D = act(f16(A.X) . Wt^T) for
+// X [n_cols][64], Wt [64][64], D [n_rows][64], all dense -- the bits of sgx_spmm_launch into a Z of pitch 64 followed by
+// sgx_xw_dense_ep, without Z in memory.  _applicable: what the kernel asks of the table, the pointers and the plan (the
+// layer's own conditions are layer.hip's); the caller checks it first.
+bool sgx_spmm_dense_applicable(int n_cols, const void *X, const void *Wt, const void *D, const sgx_plan *plan);
+int sgx_spmm_dense(int relu, int n_rows, int n_cols, const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                   const void *X, const void *Wt, void *D, hipStream_t stream);
 
 // X.W for a CSR X with the weight slice resident in LDS (xw_sparse_lds.hip); the caller checks _applicable first
 bool sgx_xw_sparse_lds_applicable(int dtype, int n_rows, int m_fea, int n_feat, int64_t ldh, const sgx_plan *plan);

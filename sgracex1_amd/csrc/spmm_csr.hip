@@ -413,6 +413,119 @@ __global__ __launch_bounds__(kBlock, SGX_SPMM_MINWAVES) void xw_sparse_kernel(SG
     spmm_body<T, VEC, LPR, CPL, BIG, SGX_SPMM_FEA_STYLE, false>(SGX_SPMM_ARGS);
 }
 
+// ---------------------------------------------------------------------------------------
+// The aggregation of a square dense fp16 layer (64 -> 64) with W applied in its epilogue:  D = act(f16(A.X) . W).
+// (A.X).W gathers the same 64 columns per edge as A.(X.W) and applies W once per output row, so H = X.W is never
+// written or read.  A wavefront sums 16 consecutive rows of Z = A.X, 8 at a time exactly as the sblock path does (the same
+// fma chain per element), rounds them to fp16 -- the rounding the two-launch aggregate-first order applies when it stores Z
+// -- into its own LDS slab, and multiplies the 16 x 64 tile by W on the matrix cores in the orientation, the fragment
+// layout and the K order of xw_dense.hip's fp16 arm (D^T tile = Wt rows x Z rows, k = 32 s + 8 (lane >> 4) + j, two K
+// steps from a zero accumulator, tiles paired so that a lane ends up with 8 consecutive columns): the bits of
+// spmm_kernel into Z followed by sgx_xw_dense_ep.  W's fragments are staged in LDS once per workgroup; the result goes
+// back through the slab so that D leaves as whole 128-byte rows from 8 consecutive lanes, the way store_row writes them.
+// Slab rows lie 144 bytes apart: the 16-byte fragment reads of 16 consecutive rows then fall into disjoint banks.
+// ---------------------------------------------------------------------------------------
+typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+typedef f16x8 f16x8_u __attribute__((aligned(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int kDenseF = 64;                      // M_fea = P_w: one 128-byte row per 8 lanes, 2 K steps, 4 column tiles
+constexpr int kDenseTile = 16;                   // rows of Z per MFMA tile = two 8-row groups of the wavefront
+constexpr int kDensePitch = kDenseF + 8;         // halves between slab rows
+#ifndef SGX_SPMM_DENSE_BLOCKS_PER_CU
+#define SGX_SPMM_DENSE_BLOCKS_PER_CU 256         // grid cap (64 rows per workgroup); tiles beyond it are grid-strided
+#endif                                           // S-100M layer 2, one run each: 4.688 ms per step at 256, 4.699 at 64, 4.707 at 16
+
+// the lanes of a wavefront hand rows to one another through its slab: LDS operations of one wavefront complete in
+// order, the fences keep the compiler from moving them across
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+__global__ __launch_bounds__(kBlock, SGX_SPMM_MINWAVES) void spmm_dense_f16_kernel(
+    int n_rows, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const f16 *__restrict__ val,
+    const f16 *__restrict__ X, unsigned x_bytes, const f16 *__restrict__ Wt, f16 *__restrict__ D, int relu)
+{
+    constexpr int VEC = 8, LPR = 8, RPW = 64 / LPR, KS = kDenseF / 32, NT = kDenseF / 16;
+    __shared__ __attribute__((aligned(16))) f16x8 sW[KS][NT][64];                          // 8 KB, fragment layout
+    __shared__ __attribute__((aligned(16))) f16 sZ[kBlock / 64][kDenseTile * kDensePitch];  // 2304 bytes per wavefront
+    const int lane = threadIdx.x & 63;
+    const int sub = lane % LPR, grp = lane / LPR;
+    const int l15 = lane & 15, lq = lane >> 4;
+
+    // MFMA row i of column tile nt stands for output column 32 (nt / 2) + 8 (i / 4) + 4 (nt % 2) + i % 4 (the pairing of
+    // xw_dense_stationary_f16_kernel); lane ln of fragment (s, nt) holds k = 32 s + 8 (ln >> 4) .. + 7 of that row of Wt
+    for (int i = threadIdx.x; i < KS * NT * 64; i += kBlock) {
+        const int ln = i & 63, nt = (i >> 6) % NT, s = i / (64 * NT);
+        const int n = (nt / 2) * 32 + 8 * ((ln & 15) / 4) + 4 * (nt % 2) + (ln & 15) % 4;
+        sW[s][nt][ln] = *reinterpret_cast<const f16x8_u *>(Wt + n * kDenseF + s * 32 + 8 * (ln >> 4));
+    }
+    __syncthreads();
+
+    const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<f16 *>(X), 0, x_bytes, 0x00020000);
+    const unsigned chunk_off[1] = {(unsigned)(sub * VEC) * (unsigned)sizeof(f16)};
+    f16 *slab = sZ[threadIdx.x >> 6];
+    const int64_t wave = (int64_t)blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    const int64_t n_waves = (int64_t)gridDim.x * (kBlock / 64);
+    for (int64_t r0 = wave * kDenseTile; r0 < n_rows; r0 += n_waves * kDenseTile) {
+        // ---- Z: two groups of 8 rows, a row past the end (a tail's upper rows) sums nothing and leaves zeros ----
+#pragma unroll 1
+        for (int h = 0; h < kDenseTile / RPW; ++h) {
+            const int64_t r = r0 + h * RPW + grp;
+            int e0 = 0, e1 = 0;
+            if (r < n_rows) {
+                e0 = rowptr[r];
+                e1 = rowptr[r + 1];
+            }
+            float acc[VEC];
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) acc[i] = 0.0f;
+            accumulate_edges<f16, VEC, LPR, 1, false, SGX_SPMM_ADJ_STYLE>(acc, e0, e1, LPR, sub, col, val, rsrc, X,
+                                                                          kDenseF * (unsigned)sizeof(f16), chunk_off);
+            f16x8 z;
+#pragma unroll
+            for (int i = 0; i < VEC; ++i) z[i] = (f16)acc[i];
+            *reinterpret_cast<f16x8 *>(slab + (h * RPW + grp) * kDensePitch + sub * VEC) = z;
+        }
+        wave_lds_sync();
+        // ---- D^T tile = Wt rows x Z rows ----
+        f32x4 d[NT];
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt) d[nt] = (f32x4){0, 0, 0, 0};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            const f16x8 b = *reinterpret_cast<const f16x8 *>(slab + l15 * kDensePitch + s * 32 + 8 * lq);
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) d[nt] = __builtin_amdgcn_mfma_f32_16x16x32_f16(sW[s][nt][lane], b, d[nt], 0, 0, 0);
+        }
+        wave_lds_sync();                         // every lane holds its fragments of Z: the slab takes the result
+        // lane (l15, lq) holds columns 32 q + 8 lq .. + 7 of row l15; the ReLU on the rounded value as xw_dense applies it
+#pragma unroll
+        for (int q = 0; q < NT / 2; ++q) {
+            f16x8 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const f16 lo = (f16)d[2 * q][j], hi = (f16)d[2 * q + 1][j];
+                o[j] = (!relu || lo > (f16)0) ? lo : (f16)0;
+                o[4 + j] = (!relu || hi > (f16)0) ? hi : (f16)0;
+            }
+            *reinterpret_cast<f16x8 *>(slab + l15 * kDensePitch + q * 32 + 8 * lq) = o;
+        }
+        wave_lds_sync();
+        // ---- rows of D: 8 lanes x 16 bytes = one 128-byte line each ----
+#pragma unroll
+        for (int h = 0; h < kDenseTile / RPW; ++h) {
+            const int64_t r = r0 + h * RPW + grp;
+            const u32x4 v = *reinterpret_cast<const u32x4 *>(slab + (h * RPW + grp) * kDensePitch + sub * VEC);
+            if (r < n_rows) *reinterpret_cast<Elem<f16>::vec16_u *>(D + r * kDenseF + sub * VEC) = v;
+        }
+        wave_lds_sync();                         // before the next tile's Z lands in the slab
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(kBlock) void spmm_split_finalize_kernel(
     int n_long, int n_feat, const int32_t *__restrict__ long_row, const int32_t *__restrict__ long_first,
@@ -569,6 +682,37 @@ bool sgx_spmm_table_big(int dtype, int n_cols, int64_t ldh, int n_feat)
 {
     const size_t es = sgx_elem_size(dtype);
     return (unsigned long long)n_cols * (unsigned long long)ldh * es > kOOBRow || (unsigned long long)n_feat * es > kMaxRowBytes;
+}
+
+// The fused form walks the rows in natural order with one lane group per row: a plan that cuts rows into tasks or lists
+// them in degree order (with or without a one-step tail) keeps the staged path, and so does a table past 32-bit buffer
+// offsets.  16-byte gathers and fragment loads: X on a dword, Wt and D on an element (any fp16 pointer).
+// (Below 5 entries per row the staged aggregation halves its lane groups, choose_cpl; this form keeps 8 lanes per row
+// there -- it loses less by that than the dense pass it saves: 0.34 vs 0.47 ms at 2 entries per row on 4 M rows.)
+bool sgx_spmm_dense_applicable(int n_cols, const void *X, const void *Wt, const void *D, const sgx_plan *plan)
+{
+    if (plan && (plan->n_tasks > 0 || plan->row_order)) return false;
+    if (sgx_spmm_table_big(SGX_F16, n_cols, kDenseF, kDenseF)) return false;
+    return (uintptr_t)X % 4 == 0 && (uintptr_t)Wt % 2 == 0 && (uintptr_t)D % 2 == 0;
+}
+
+int sgx_spmm_dense(int relu, int n_rows, int n_cols, const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                   const void *X, const void *Wt, void *D, hipStream_t stream)
+{
+    if (n_rows < 0 || n_cols < 0) return SGX_ERR_SHAPE;
+    if (n_rows == 0) return SGX_OK;
+    if (!rowPtr || !Wt || !D) return SGX_ERR_NULL;
+    if (n_cols > 0 && (!X || !columnIndex || !values)) return SGX_ERR_NULL;
+    if (!sgx_spmm_dense_applicable(n_cols, X, Wt, D, nullptr)) return SGX_ERR_UNSUPPORTED;
+    const int64_t rows_per_block = (int64_t)kDenseTile * (kBlock / 64);
+    int64_t blocks = ((int64_t)n_rows + rows_per_block - 1) / rows_per_block;
+    const int per_cu = sgx_tune().spmm_fused_blocks_per_cu > 0 ? sgx_tune().spmm_fused_blocks_per_cu : SGX_SPMM_DENSE_BLOCKS_PER_CU;
+    if (blocks > (int64_t)256 * per_cu) blocks = (int64_t)256 * per_cu;
+    hipLaunchKernelGGL(spmm_dense_f16_kernel, dim3((unsigned)blocks), dim3(kBlock), 0, stream, n_rows, rowPtr, columnIndex,
+                       (const f16 *)values, (const f16 *)X, (unsigned)((size_t)n_cols * kDenseF * sizeof(f16)), (const f16 *)Wt,
+                       (f16 *)D, relu);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
 }
 
 int sgx_spmm_launch(int dtype, int acc_mode, int spmm_block, int relu, int n_rows, int n_cols, int n_feat,

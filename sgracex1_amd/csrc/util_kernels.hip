@@ -293,6 +293,8 @@ void load_tuning()
     t.xtg_scalar = flag("SGX_XTG_SCALAR");
     t.xtg_wave_tiles = flag("SGX_XTG_WAVE_TILES");
     t.spmm_no_short_tail = flag("SGX_SPMM_NO_SHORT_TAIL");
+    t.layer_no_fused_dense = flag("SGX_LAYER_NO_FUSED_DENSE");
+    t.spmm_fused_blocks_per_cu = num("SGX_SPMM_FUSED_BLOCKS_PER_CU");
     t.spmm_cpl = num("SGX_SPMM_CPL");
     t.xw_sparse_lpr = num("SGX_XW_SPARSE_LPR");
     t.xw_sparse_streams = num("SGX_XW_SPARSE_STREAMS");

