@@ -37,7 +37,9 @@ downloaded by torch_geometric and are not available offline.
              the plain mini-batch mode hands batch.train_mask over as the mask (no boolean index, no read-back per step),
              and the final accuracies are counted on the device (NodeTrainer.evaluate)
 --replay     with --trainer on the full graph: the whole step captured once (torch.cuda.graph) and replayed every epoch;
-             mini-batches run eager only, their shapes vary
+             with --batch-size, --num-neighbors and --device-batches: the loader pads every full batch to one fixed
+             capacity (NeighborLoader(pad=True)) and ONE recorded step -- sample, preparation, layers, loss, backward,
+             Adam -- is replayed for each of them (NodeTrainer.capture_loader); the short last batch runs eager
 """
 import argparse
 import os
@@ -102,6 +104,8 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         train_mask[train] = True
         data = pyg_lite.NodeData(x, edge_index, y, train_mask=train_mask)
         ready = {"prepare": "sym_norm2", "transposed": bool(accb or attention), "quant": sgrace.quant_constants}
+        if replay:
+            ready["pad"] = True
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
                                          shuffle=True, seed=seed, **(ready if device_batches else {}))
     t0 = time.time()
@@ -114,6 +118,11 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
                 replay_step = node_trainer.capture(x, edge_index, y, full_mask)
             loss = replay_step() if replay else node_trainer.step(x, edge_index, y, full_mask)
             total, steps = loss[0], 1
+        elif node_trainer is not None and replay:
+            if replay_step is None:
+                replay_step = node_trainer.capture_loader(loader)
+            for loss in replay_step():
+                total, steps = total + loss[0], steps + 1
         elif node_trainer is not None:
             for batch in loader:
                 if device_batches:
@@ -146,6 +155,8 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         epoch_loss.append(total / max(steps, 1))
         if verbose and (epoch + 1) % 20 == 0:
             print(f"epoch {epoch + 1:3d}  loss {float(loss):.4f}", flush=True)
+    if loader is not None and replay:
+        loader.status()                                     # what a failed batch would have raised, read back once
     if device.type == "cuda":
         torch.cuda.synchronize()
     elapsed = time.time() - t0
@@ -191,8 +202,10 @@ if __name__ == "__main__":
         ap.error("--device-batches selects the loader of the mini-batch mode (--batch-size, --num-neighbors)")
     if a.trainer and a.acc != 1:
         ap.error("--trainer runs the tail on the kernels (--acc 1)")
-    if a.replay and (not a.trainer or a.batch_size is not None):
-        ap.error("--replay replays the full-graph step of --trainer; mini-batches run eager only")
+    if a.replay and (not a.trainer or (a.batch_size is not None and not a.device_batches)):
+        ap.error("--replay replays the step of --trainer: the full-graph one, or the padded mini-batch one of --device-batches")
+    if a.replay and a.batch_size is not None and (a.qbits != 32 or a.accb):
+        ap.error("--replay on mini-batches covers the unquantised layers with the staged backward (no --qbits, no --accb)")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
         num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches,
         accb=int(a.accb), trainer=a.trainer, replay=a.replay)

@@ -1619,6 +1619,85 @@ int sgx_head_eval(int n_graphs, int n_real, int P, int C, const float *pooled, c
                   const int64_t *target, int64_t *totals /* [2] */, double *loss_sum /* [1] */, float *logits /* or NULL */,
                   void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- padded node batches: every full batch of a loader in buffers of one fixed capacity -------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * A neighbour-sampled batch has its own node, edge and entry counts; sgx_node_batch_sample reads them back, and they are
+ * tensor sizes and launch arguments of everything behind it, so a recorded step fits one batch.  A PADDED node batch has
+ * the counts of a capacity the host computes once per (graph, batch, fanouts, feature CSR), the spare rows and entries
+ * held by well-defined filler rows; one recorded step then serves every batch of `batch` seeds.
+ *
+ * Capacity (sgx_node_batch_pad_capacity; host arithmetic only).  mn, me = the bounds max_nodes, max_edges of
+ * sgx_node_batch_workspace_bytes:
+ *   C_f   the feature entries: the sum of the mn largest per-row entry counts of the whole graph's feature CSR
+ *         (fea_row_counts, HOST [n_nodes]; NULL: no features, C_f = 0);
+ *   F     max(ceil(me / 63), ceil(C_f / 64)) guaranteed filler rows;
+ *   N     mn + F rows of every padded array;       E = me entries of a row of the edge lists;
+ *   C_a   me + mn + F = me + N entries of the normalised adjacency.
+ * Every batch fits.  A batch with n live rows, `edges` sampled edges, a adjacency and f feature entries has n <= mn and
+ * edges <= me (the sampler's bounds), n <= a <= edges + n (a row gets one loop unless it stores one) and f <= C_f (its n
+ * distinct nodes hold no more than the mn fullest rows).  It leaves P = N - n >= F filler rows, which take one diagonal
+ * entry each; the spare adjacency entries are C_a - a - P = me + n - a, within 0 .. me <= 63 F <= 63 P, and the spare
+ * feature entries C_f - f are within 0 .. C_f <= 64 F <= 64 P: dealt 63 / 64 to a row they end inside the filler rows.
+ *
+ * A padded batch holds, in the live prefix of every array, exactly what sgx_node_batch_sample writes for the same (graph,
+ * seeds, fanouts, seed, step), bit for bit -- n_id, out_rowPtr / out_col / edge_pos, rowPtr_norm / columnIndex_norm /
+ * values_norm, dead_row, rowPtr_fea / columnIndex_fea / values_fea, y_out, mask_out, and the two edge lists as int64
+ * [2][E]: row 1 begins at entry E, not at `edges` -- and behind the prefix:
+ *   filler row n+j  n_id = -1, y_out = 0, every mask byte 0, dead_row = 0; whoever gathers dense x rows by n_id gives it a
+ *                   row of zeros (sgx_pack_rows: a negative index is a zero row);
+ *     adjacency     one diagonal entry (n + j, 1), then zero-valued diagonal entries (n + j, 0): the S_a = C_a - a - P
+ *                   spare entries dealt 63 to a row from filler row 0 on, so the row holds 1 + clamp(S_a - 63 j, 0, 63)
+ *                   entries: rowPtr_norm[n + j] = a + j + min(S_a, 63 j), rowPtr_norm[N] = C_a;
+ *     features      zero-valued entries (0, 0): the S_f = C_f - f spare entries dealt 64 to a row from filler row 0 on:
+ *                   rowPtr_fea[n + j] = f + min(S_f, 64 j), rowPtr_fea[N] = C_f;
+ *     sampled CSR   empty: out_rowPtr[n .. N] = edges;
+ *   tails           out_col, edge_pos [edges, E) = -1; edge_index[:, edges:E] = -1 and edge_index_agg likewise (past the
+ *                   live edges a padded edge list is a key, not an edge list).
+ * Every stored entry of the normalised adjacency and of the feature CSR belongs to a row -- rowPtr[N] is the array's
+ * length in every batch -- so code that takes a CSR's entry count from its column array runs on them unchanged.
+ * Consequences: the longest row of the normalised adjacency is at most max(max(fanouts) + 1, 64) and of the feature CSR
+ * max(its longest row, 64); no filler row is dead under the GAT mask `adj > 0` (its first entry is 1); a filler row's D
+ * is 0 in every layer (X.W of a zero row is 0, and the row aggregates itself alone); no live row stores a filler
+ * column, so a filler row passes nothing on, and a loss over live rows hands it no gradient.  One exception is inherited
+ * from the layers: a DEAD live row of the GAT aggregate takes the uniform softmax over all N columns, fillers included
+ * (they add 0 to the sum; the mean divides by N, not n).
+ *
+ * sgx_node_batch_sample_padded(b, pad, stream): the launches of sgx_node_batch_sample on b's arguments with
+ *   pad->step    (device, uint64) in place of b->step: the sampling key is formed in the kernels from this word -- the
+ *                same key as the host forms for the same value -- so a replay draws a new sample once the word changes;
+ *   pad->status  (device, int32) |= the sampler's status word (1: bad or repeated seeds, 2: a capacity); never read back
+ *                by the call;
+ *   pad->counts  (device, int32 [4 + 2 (n_hops + 1)]) = n, edges, a, f, then the node count and the edge count after
+ *                every hop (hop_nodes, hop_edges), for tests and reports;
+ * and one more launch whose workgroups write the filler rows, the dealt spare entries and the tails: plain stores,
+ * 16 bytes a lane over the constant ranges, no atomics beyond the sampler's.  Array sizes: n_id, dead_row, y_out,
+ * mask_out [N]; the three row pointers [N + 1]; out_col, edge_pos [E]; columnIndex_norm, values_norm [C_a];
+ * columnIndex_fea, values_fea [C_f] (b->fea_capacity is ignored); the edge lists [2 E]; b->max_nodes / max_edges and the
+ * workspace as for sgx_node_batch_sample.  Nothing in *b is written: hop_nodes, hop_edges (may be NULL), nnz_norm,
+ * nnz_fea, has_dead_rows and max_row stay as they are.  No allocation, no synchronisation; capturable; the same bits on
+ * every run.  With a non-zero status the arrays hold a batch without a live row (n = edges = a = f = 0 in counts:
+ * filler rows only), so whatever runs behind the call reads a well-formed batch; nothing is written outside
+ * [0, capacity) of any array.  The quantised variant is not built.
+ * Argument errors, before anything is launched: those of sgx_node_batch_sample (without its host outputs); b, pad or a
+ * pointer of pad NULL: SGX_ERR_NULL; batch == 0, capacities below the rule's (N < mn, E < me, C_a < me + N, C_a - N >
+ * 63 (N - mn), C_f > 64 (N - mn)) or over INT32_MAX: SGX_ERR_SHAPE; a fan-out of -1 (an unbounded row):
+ * SGX_ERR_UNSUPPORTED.  sgx_node_batch_pad_capacity: pad or fanouts NULL: SGX_ERR_NULL; arguments the bounds refuse,
+ * batch == 0, a negative row count or a capacity over INT32_MAX: SGX_ERR_SHAPE; a fan-out of -1: SGX_ERR_UNSUPPORTED. */
+typedef struct sgx_node_batch_pad {
+    int32_t n_rows;                            /* N */
+    int32_t reserved;
+    int64_t nnz_norm, nnz_fea, n_edges;        /* C_a, C_f, E */
+    const uint64_t *step;                      /* device */
+    int32_t *status;                           /* device, OR-ed into */
+    int32_t *counts;                           /* device out [4 + 2 (n_hops + 1)] */
+} sgx_node_batch_pad;
+
+/* fills n_rows, nnz_norm, nnz_fea and n_edges of *pad by the rule; the pointers are left alone */
+int sgx_node_batch_pad_capacity(int n_nodes, int64_t nnz, int batch, int n_hops, const int *fanouts,
+                                const int32_t *fea_row_counts, sgx_node_batch_pad *pad);
+int sgx_node_batch_sample_padded(sgx_node_batch *b, const sgx_node_batch_pad *pad, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

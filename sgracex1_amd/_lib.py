@@ -46,6 +46,7 @@ SYMBOLS = [
     "sgx_collate_graphs", "sgx_collate_graphs_extras", "sgx_batch_plan_group_count", "sgx_batch_plan_create_known", "sgx_batch_plan_export_groups",
     "sgx_gat_aggregate_stats", "sgx_layer_forward_stats", "sgx_gat_edge_outputs", "sgx_gat_backward_edges_stats",
     "sgx_node_batch_workspace_bytes", "sgx_node_batch_sample", "sgx_node_batch_sample_quant",
+    "sgx_node_batch_pad_capacity", "sgx_node_batch_sample_padded",
     "sgx_layer_backward_workspace_bytes", "sgx_layer_backward", "sgx_gat_attention_grad_workspace_bytes",
     "sgx_gat_attention_grad",
     "sgx_csr_transpose_workspace_bytes", "sgx_csr_transpose",
@@ -285,6 +286,15 @@ class NodeBatchQuant(ctypes.Structure):
     ]
 
 
+class NodeBatchPad(ctypes.Structure):
+    """struct sgx_node_batch_pad -- field order and types must match include/sgx.h."""
+    _fields_ = [
+        ("n_rows", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("nnz_norm", ctypes.c_int64), ("nnz_fea", ctypes.c_int64), ("n_edges", ctypes.c_int64),
+        ("step", ctypes.c_void_p), ("status", ctypes.c_void_p), ("counts", ctypes.c_void_p),
+    ]
+
+
 class LayerGradDesc(ctypes.Structure):
     """struct sgx_layer_grad_desc -- field order and types must match include/sgx.h."""
     _fields_ = [
@@ -505,6 +515,10 @@ def _load():
     lib.sgx_node_batch_sample.restype = c_int
     lib.sgx_node_batch_sample_quant.argtypes = [ctypes.POINTER(NodeBatch), ctypes.POINTER(NodeBatchQuant), vp]
     lib.sgx_node_batch_sample_quant.restype = c_int
+    lib.sgx_node_batch_pad_capacity.argtypes = [c_int, c_i64, c_int, c_int, i32p, i32p, ctypes.POINTER(NodeBatchPad)]
+    lib.sgx_node_batch_pad_capacity.restype = c_int
+    lib.sgx_node_batch_sample_padded.argtypes = [ctypes.POINTER(NodeBatch), ctypes.POINTER(NodeBatchPad), vp]
+    lib.sgx_node_batch_sample_padded.restype = c_int
     lib.sgx_layer_backward_workspace_bytes.argtypes = [ctypes.POINTER(LayerGradDesc)]
     lib.sgx_layer_backward_workspace_bytes.restype = sz
     lib.sgx_layer_backward.argtypes = [ctypes.POINTER(LayerGradDesc), vp]

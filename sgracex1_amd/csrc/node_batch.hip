@@ -11,7 +11,14 @@
 //         constant sets, their dead-row masks and flags, and the lean form's mask values
 //   7-9   exclusive scan of the lengths of the feature rows n_id -> rowPtr                   (scan_*<FeatureRows>)
 //   10    those rows' columns and values copied; y and the masks gathered                    (gather_kernel)
+//   11    sgx_node_batch_sample_padded only: the filler rows, the dealt spare entries and the -1 tails behind the
+//         live prefix of every array, up to a fixed capacity (pad_kernel); the counts go to a device array instead
+//         of the read-back, so that call is capturable
 // Kernel boundaries are the only ordering between workgroups.
+#include <algorithm>
+#include <functional>
+#include <vector>
+
 #include "sample_device.h"
 #include "quant_device.h"
 
@@ -28,6 +35,7 @@ struct Args {
     sgx_node_batch b;
     int32_t *miss;                            // [max_nodes] 1 = the row holds no self loop
     float *dis, *w;                           // [max_nodes] 1 / sqrt(deg); [max_edges + max_nodes] weights in stored order
+    int64_t ei_stride;                        // entries of one row of the edge lists; 0: the live edge count (unpadded)
     __device__ int N() const { return ctr.nodes(ctr.H); }
     __device__ int E() const { return ctr.edges(ctr.H); }
 };
@@ -36,7 +44,7 @@ __global__ __launch_bounds__(kBlock) void loops_kernel(Args a)
 {
     if (a.ctr.status()) return;
     const int N = a.N(), lane = threadIdx.x & 63;
-    const int64_t E = a.E();
+    const int64_t E = a.ei_stride ? a.ei_stride : a.E();
     for (int r = blockIdx.x * kWaves + (threadIdx.x >> 6); r < N; r += gridDim.x * kWaves) {
         const int p0 = a.b.out_rowPtr[r], p1 = a.b.out_rowPtr[r + 1];
         bool found = false;
@@ -281,6 +289,93 @@ __global__ __launch_bounds__(kBlock) void gather_kernel(Args a)
     }
 }
 
+// ---- padded node batches (sgx.h): what stands behind the live prefix of every array ----
+struct PadArgs {
+    int32_t N;                                // rows of every padded array
+    int64_t Ca, Cf, E;                        // entries of the normalised adjacency, of the features, of the edge lists
+    int32_t *status, *counts;
+};
+
+typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+
+// bytes [lo, hi) set to the byte `pat` (0x00: zeros; 0xff: -1 in every integer type): single bytes up to the first
+// and behind the last 16-byte boundary, 16 bytes a lane between them
+__device__ inline void fill_bytes(void *base, int64_t lo_bytes, int64_t hi_bytes, unsigned pat, int64_t tid, int64_t nth)
+{
+    if (!base || hi_bytes <= lo_bytes) return;
+    char *lo = (char *)base + lo_bytes, *hi = (char *)base + hi_bytes;
+    char *al = (char *)(((uintptr_t)lo + 15) & ~(uintptr_t)15);
+    if (al > hi) al = hi;
+    char *ah = al + ((hi - al) & ~(int64_t)15);
+    const unsigned w = pat * 0x01010101u;
+    const u32x4 v = {w, w, w, w};
+    for (int64_t i = tid; i < al - lo; i += nth) lo[i] = (char)pat;
+    for (int64_t i = tid; i < (ah - al) / 16; i += nth) reinterpret_cast<u32x4 *>(al)[i] = v;
+    for (int64_t i = tid; i < hi - ah; i += nth) ah[i] = (char)pat;
+}
+
+// Behind the batch's last preparation kernel.  With a set status the batch is written as one without a live row (n =
+// edges = a = f = 0: filler rows only), so that whatever reads the buffers next finds a well-formed batch; every range
+// below lies inside its array's capacity whatever the counters hold (the capacities are checked on the host against the
+// bounds the counters cannot pass with a clear status).
+template <class T>
+__global__ __launch_bounds__(kBlock) void pad_kernel(Args a, PadArgs p)
+{
+    const sgx_node_batch &b = a.b;
+    const int st = a.ctr.status(), H = a.ctr.H;
+    const int n = st ? 0 : a.N(), e = st ? 0 : a.E();
+    const int na = st ? 0 : a.ctr.extra(kNormNnz), nf = (st || !b.rowPtr_x) ? 0 : a.ctr.extra(kFeaNnz);
+    const int64_t tid = (int64_t)blockIdx.x * kBlock + threadIdx.x, nth = (int64_t)gridDim.x * kBlock;
+    if (tid == 0) {
+        if (st) *p.status |= st;                           // (one thread, in stream order: no other writer)
+        p.counts[0] = n, p.counts[1] = e, p.counts[2] = na, p.counts[3] = nf;
+        for (int h = 0; h <= H; ++h) {
+            p.counts[4 + h] = st ? 0 : a.ctr.nodes(h);
+            p.counts[5 + H + h] = st ? 0 : a.ctr.edges(h);
+        }
+    }
+    const int P = p.N - n;                                 // filler rows; >= the rule's F
+    const int64_t Sa = p.Ca - na - P, Sf = p.Cf - nf;      // spare entries, dealt 63 / 64 to a filler row from row 0 on
+    // row pointers n .. N (entry n as the preparation left it, written again where the status skipped it)
+    for (int64_t j = tid; j <= P; j += nth) {
+        const int64_t da = 63 * j < Sa ? 63 * j : Sa, df = 64 * j < Sf ? 64 * j : Sf;
+        b.out_rowPtr[n + j] = e;
+        b.rowPtr_norm[n + j] = (int32_t)(na + j + da);
+        if (b.rowPtr_x) b.rowPtr_fea[n + j] = (int32_t)(nf + df);
+    }
+    // the filler rows' adjacency entries: rows 0 .. full-1 hold 64, row `full` 1 + Sa % 63, the rest their diagonal 1
+    T *val = (T *)b.values_norm;
+    const int64_t full = Sa / 63, part = 1 + Sa % 63;
+    for (int64_t t = tid; t < p.Ca - na; t += nth) {
+        int64_t j, k;
+        if (t < 64 * full) {
+            j = t >> 6, k = t & 63;
+        } else {
+            const int64_t u = t - 64 * full;
+            j = u < part ? full : full + 1 + (u - part);
+            k = u < part ? u : 0;
+        }
+        b.columnIndex_norm[na + t] = (int32_t)(n + j);
+        val[na + t] = k == 0 ? (T)1.0f : (T)0.0f;
+    }
+    // constant ranges
+    fill_bytes(b.n_id, 4ll * n, 4ll * p.N, 0xff, tid, nth);
+    fill_bytes(b.dead_row, n, p.N, 0, tid, nth);
+    fill_bytes(b.y_out, 8ll * n, 8ll * p.N, 0, tid, nth);
+#pragma unroll
+    for (int m = 0; m < 3; ++m) fill_bytes(b.mask_out[m], n, p.N, 0, tid, nth);
+    if (b.rowPtr_x) {
+        fill_bytes(b.columnIndex_fea, 4ll * nf, 4ll * p.Cf, 0, tid, nth);
+        fill_bytes(b.values_fea, (int64_t)sizeof(T) * nf, (int64_t)sizeof(T) * p.Cf, 0, tid, nth);
+    }
+    fill_bytes(b.out_col, 4ll * e, 4ll * p.E, 0xff, tid, nth);
+    fill_bytes(b.edge_pos, 4ll * e, 4ll * p.E, 0xff, tid, nth);
+    for (int row = 0; row < 2; ++row) {
+        fill_bytes(b.edge_index, 8ll * (row * p.E + e), 8ll * (row + 1) * p.E, 0xff, tid, nth);
+        fill_bytes(b.edge_index_agg, 8ll * (row * p.E + e), 8ll * (row + 1) * p.E, 0xff, tid, nth);
+    }
+}
+
 size_t region(size_t bytes) { return sgx_align_up(bytes, 256); }
 
 }  // namespace
@@ -316,11 +411,9 @@ QuantSets<NQ> quant_sets(const sgx_node_batch_quant *q)
     return qs;
 }
 
-// sgx_node_batch_sample (q == NULL) and sgx_node_batch_sample_quant on their checked quantiser arguments
-int node_batch_sample(sgx_node_batch *b, sgx_node_batch_quant *q, void *stream)
+// the argument checks every node-batch call shares, behind those of its host outputs
+int check_batch(const sgx_node_batch *b, Bounds &bd)
 {
-    if (!b->fanouts || !b->hop_nodes || !b->hop_edges) return SGX_ERR_NULL;
-    Bounds bd;
     if (!bounds(b->n_nodes, b->nnz, b->batch, b->n_hops, b->fanouts, &bd)) return SGX_ERR_SHAPE;
     if (b->max_nodes < bd.max_nodes || b->max_edges < bd.max_edges || b->fea_capacity < 0) return SGX_ERR_SHAPE;
     if (b->dtype != SGX_F16 && b->dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;
@@ -335,33 +428,30 @@ int node_batch_sample(sgx_node_batch *b, sgx_node_batch_quant *q, void *stream)
     if (!b->workspace || b->workspace_bytes < sgx_node_batch_workspace_bytes(b->n_nodes, b->nnz, b->batch, b->n_hops, b->fanouts,
                                                                              nullptr, nullptr))
         return SGX_ERR_WORKSPACE;
-    hipStream_t s = (hipStream_t)stream;
+    return SGX_OK;
+}
+
+// every launch of a node batch (batch >= 1) on checked arguments, nothing read back: the sampler and the preparation
+// kernels.  step_dev / ei_stride: the padded call's step word and edge-list row length (NULL / 0 otherwise).
+int enqueue_batch(const sgx_node_batch *b, const sgx_node_batch_quant *q, const Bounds &bd, const uint64_t *step_dev,
+                  int64_t ei_stride, Args &a, hipStream_t s)
+{
     const int H = b->n_hops;
-    for (int h = 0; h <= H; ++h) b->hop_nodes[h] = b->hop_edges[h] = 0;
-    b->nnz_norm = b->nnz_fea = 0;
-    b->has_dead_rows = b->max_row = 0;
-    if (q) q->has_dead_rows_q[0] = q->has_dead_rows_q[1] = 0;
-    if (b->batch == 0) {
-        SGX_HIP_CHECK(hipMemsetAsync(b->out_rowPtr, 0, sizeof(int32_t), s));
-        SGX_HIP_CHECK(hipMemsetAsync(b->rowPtr_norm, 0, sizeof(int32_t), s));
-        if (b->rowPtr_x) SGX_HIP_CHECK(hipMemsetAsync(b->rowPtr_fea, 0, sizeof(int32_t), s));
-        return SGX_OK;
-    }
     char *ws = (char *)b->workspace;
     int32_t *cbuf = (int32_t *)ws;
     ws += counters_bytes(H);
     int32_t *bsum = (int32_t *)ws;
     const int64_t tiles = bd.max_tiles > bd.max_nodes / kTile + 1 ? bd.max_tiles : bd.max_nodes / kTile + 1;
     ws += region(sizeof(int32_t) * tiles);
-    Args a{Counters{cbuf, H}, *b, nullptr, nullptr, nullptr};
+    a = Args{Counters{cbuf, H}, *b, nullptr, nullptr, nullptr, ei_stride};
     a.miss = (int32_t *)ws;
     ws += region(sizeof(int32_t) * (bd.max_nodes + 1));
     a.dis = (float *)ws;
     ws += region(sizeof(int32_t) * (bd.max_nodes + 1));
     a.w = (float *)ws;
     const int st = sample_enqueue(b->rowPtr, b->columnIndex, b->n_nodes, b->seeds, b->batch, H, b->fanouts, b->seed, b->step,
-                                  b->node_map, b->n_id, b->out_rowPtr, b->out_col, b->edge_pos, b->max_nodes, b->max_edges, bd,
-                                  cbuf, bsum, s);
+                                  step_dev, b->node_map, b->n_id, b->out_rowPtr, b->out_col, b->edge_pos, b->max_nodes,
+                                  b->max_edges, bd, cbuf, bsum, s);
     if (st != SGX_OK) return st;
     const unsigned rows = grid_of(bd.max_nodes, kWaves, 65536);
     hipLaunchKernelGGL(loops_kernel, dim3(rows), dim3(kBlock), 0, s, a);
@@ -385,8 +475,33 @@ int node_batch_sample(sgx_node_batch *b, sgx_node_batch_quant *q, void *stream)
             hipLaunchKernelGGL(gather_kernel<float>, dim3(rows), dim3(kBlock), 0, s, a);
     }
     SGX_LAUNCH_CHECK();
+    return SGX_OK;
+}
+
+// sgx_node_batch_sample (q == NULL) and sgx_node_batch_sample_quant on their checked quantiser arguments
+int node_batch_sample(sgx_node_batch *b, sgx_node_batch_quant *q, void *stream)
+{
+    if (!b->fanouts || !b->hop_nodes || !b->hop_edges) return SGX_ERR_NULL;
+    Bounds bd;
+    const int ok = check_batch(b, bd);
+    if (ok != SGX_OK) return ok;
+    hipStream_t s = (hipStream_t)stream;
+    const int H = b->n_hops;
+    for (int h = 0; h <= H; ++h) b->hop_nodes[h] = b->hop_edges[h] = 0;
+    b->nnz_norm = b->nnz_fea = 0;
+    b->has_dead_rows = b->max_row = 0;
+    if (q) q->has_dead_rows_q[0] = q->has_dead_rows_q[1] = 0;
+    if (b->batch == 0) {
+        SGX_HIP_CHECK(hipMemsetAsync(b->out_rowPtr, 0, sizeof(int32_t), s));
+        SGX_HIP_CHECK(hipMemsetAsync(b->rowPtr_norm, 0, sizeof(int32_t), s));
+        if (b->rowPtr_x) SGX_HIP_CHECK(hipMemsetAsync(b->rowPtr_fea, 0, sizeof(int32_t), s));
+        return SGX_OK;
+    }
+    Args a;
+    const int st = enqueue_batch(b, q, bd, nullptr, 0, a, s);
+    if (st != SGX_OK) return st;
     int32_t extras[kExtras];
-    const int done = sample_finish(cbuf, H, b->hop_nodes, b->hop_edges, extras, s);
+    const int done = sample_finish(a.ctr.c, H, b->hop_nodes, b->hop_edges, extras, s);
     if (done != SGX_OK) return done;
     b->nnz_norm = extras[kNormNnz];
     b->nnz_fea = extras[kFeaNnz];
@@ -414,4 +529,78 @@ extern "C" int sgx_node_batch_sample_quant(sgx_node_batch *b, sgx_node_batch_qua
     for (int k = 0; k < q->n_sets; ++k)
         if (!q->values_q[k] || !q->dead_row_q[k]) return SGX_ERR_NULL;
     return node_batch_sample(b, q, stream);
+}
+
+// ---- padded node batches: the capacity rule and the capturable call (sgx.h) ----
+namespace {
+
+int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
+
+// the rule's conditions on capacities that need not be the rule's own: every batch within the bounds fits
+bool pad_fits(const sgx_node_batch_pad *p, const Bounds &bd, bool features)
+{
+    const int64_t N = p->n_rows, spare = N - bd.max_nodes;
+    if (N < bd.max_nodes || p->n_edges < bd.max_edges || p->nnz_norm < bd.max_edges + N || p->nnz_fea < 0) return false;
+    if (p->nnz_norm > 0x7ffffffe || p->nnz_fea > 0x7ffffffe || p->n_edges > 0x3ffffffe) return false;
+    if (p->nnz_norm - N > 63 * spare) return false;        // the spare adjacency entries, 63 to a filler row
+    if (features && p->nnz_fea > 64 * spare) return false; // the spare feature entries, 64 to a filler row
+    return true;
+}
+
+}  // namespace
+
+extern "C" int sgx_node_batch_pad_capacity(int n_nodes, int64_t nnz, int batch, int n_hops, const int *fanouts,
+                                           const int32_t *fea_row_counts, sgx_node_batch_pad *pad)
+{
+    if (!pad || !fanouts) return SGX_ERR_NULL;
+    Bounds bd;
+    if (!bounds(n_nodes, nnz, batch, n_hops, fanouts, &bd) || batch < 1) return SGX_ERR_SHAPE;
+    for (int h = 0; h < n_hops; ++h)
+        if (fanouts[h] < 0) return SGX_ERR_UNSUPPORTED;    // an unbounded row
+    int64_t Cf = 0;
+    if (fea_row_counts) {
+        std::vector<int32_t> c(fea_row_counts, fea_row_counts + n_nodes);
+        for (int32_t v : c)
+            if (v < 0) return SGX_ERR_SHAPE;
+        std::nth_element(c.begin(), c.begin() + (bd.max_nodes < n_nodes ? bd.max_nodes : n_nodes), c.end(), std::greater<int32_t>());
+        for (int64_t i = 0; i < bd.max_nodes; ++i) Cf += c[i];
+    }
+    const int64_t F = std::max(ceil_div(bd.max_edges, 63), ceil_div(Cf, 64));
+    const int64_t N = bd.max_nodes + F, Ca = bd.max_edges + N;
+    if (N > 0x7ffffffe || Ca > 0x7ffffffe || Cf > 0x7ffffffe) return SGX_ERR_SHAPE;
+    pad->n_rows = (int32_t)N;
+    pad->nnz_norm = Ca;
+    pad->nnz_fea = Cf;
+    pad->n_edges = bd.max_edges;
+    return SGX_OK;
+}
+
+extern "C" int sgx_node_batch_sample_padded(sgx_node_batch *b, const sgx_node_batch_pad *pad, void *stream)
+{
+    if (!b || !pad) return SGX_ERR_NULL;
+    if (!b->fanouts) return SGX_ERR_NULL;
+    sgx_node_batch c = *b;                                 // the arguments as the kernels take them; b itself is not written
+    Bounds bd;
+    if (!bounds(c.n_nodes, c.nnz, c.batch, c.n_hops, c.fanouts, &bd) || c.batch < 1) return SGX_ERR_SHAPE;
+    for (int h = 0; h < c.n_hops; ++h)
+        if (c.fanouts[h] < 0) return SGX_ERR_UNSUPPORTED;  // an unbounded row
+    c.fea_capacity = pad->nnz_fea;
+    const int ok = check_batch(&c, bd);
+    if (ok != SGX_OK) return ok;
+    if (!pad->step || !pad->status || !pad->counts) return SGX_ERR_NULL;
+    if (!pad_fits(pad, bd, c.rowPtr_x != nullptr)) return SGX_ERR_SHAPE;
+    c.max_nodes = bd.max_nodes;                            // the arrays hold more; the sampler is held to its bounds
+    c.max_edges = bd.max_edges;
+    hipStream_t s = (hipStream_t)stream;
+    Args a;
+    const int st = enqueue_batch(&c, nullptr, bd, pad->step, pad->n_edges, a, s);
+    if (st != SGX_OK) return st;
+    const PadArgs pa{pad->n_rows, pad->nnz_norm, c.rowPtr_x ? pad->nnz_fea : 0, pad->n_edges, pad->status, pad->counts};
+    const unsigned grid = grid_of(pa.N + pa.Ca + pa.Cf + 2 * pa.E, kBlock * 4, 1024);
+    if (c.dtype == SGX_F16)
+        hipLaunchKernelGGL(pad_kernel<f16>, dim3(grid), dim3(kBlock), 0, s, a, pa);
+    else
+        hipLaunchKernelGGL(pad_kernel<float>, dim3(grid), dim3(kBlock), 0, s, a, pa);
+    SGX_LAUNCH_CHECK();
+    return SGX_OK;
 }

@@ -80,6 +80,11 @@ struct FirstSeen {
     __device__ void total(int t) const { ctr.nodes(h + 1) = ctr.nodes(h) + t; }
 };
 
+__global__ __launch_bounds__(kBlock) void clear_kernel(int32_t *__restrict__ c, int n)
+{
+    for (int i = threadIdx.x; i < n; i += kBlock) c[i] = 0;
+}
+
 __global__ __launch_bounds__(kBlock) void seed_kernel(const int32_t *__restrict__ seeds, int B, int n_nodes,
                                                       int32_t *__restrict__ map, int32_t *__restrict__ n_id, Counters ctr)
 {
@@ -96,8 +101,11 @@ struct SampleArgs {
     const int32_t *rowPtr, *colIdx, *n_id, *out_rowPtr;
     int32_t *out_col, *edge_pos, *map;
     int64_t max_edges;
-    uint64_t key;
+    uint64_t key;                             // of (seed, step, h), formed on the host; or, with step_dev:
+    const uint64_t *step_dev;                 // the step word on the device, and seed_mix = mix64(seed)
+    uint64_t seed_mix;
     int h, k;
+    __device__ uint64_t hop_key() const { return step_dev ? mix64(mix64(seed_mix ^ *step_dev) ^ (uint64_t)h) : key; }
 };
 
 __device__ inline void put(const SampleArgs &a, int slot, int pos)
@@ -120,6 +128,7 @@ __global__ __launch_bounds__(kBlock) void sample_kernel(SampleArgs a, Counters c
     const int p0 = a.rowPtr[v], deg = a.rowPtr[v + 1] - p0;
     const int off = a.out_rowPtr[f0 + r];
     const int k = a.k;
+    const uint64_t key = a.hop_key();                      // uniform over the grid
     const bool all = k < 0 || deg <= k;
     if ((int64_t)off + (all ? deg : k) > a.max_edges) {
         if (lane == 0) atomicOr(&ctr.status(), kStatusCapacity);
@@ -130,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void sample_kernel(SampleArgs a, Counters c
     } else if (k <= kFast) {
         // Floyd: lane i draws for j = deg - k + i; the insertions run in order, membership by ballot
         const int j = deg - k + lane;
-        const int t = lane < k ? draw(a.key, v, j) : -1;
+        const int t = lane < k ? draw(key, v, j) : -1;
         int elem = -1;
         for (int i = 0; i < k; ++i) {
             const int ti = __shfl(t, i, 64);
@@ -144,7 +153,7 @@ __global__ __launch_bounds__(kBlock) void sample_kernel(SampleArgs a, Counters c
         // fan-outs over 64: the same rule on one lane, the subset kept in the row's own edge_pos slots (O(k^2))
         int32_t *set = a.edge_pos + off;
         for (int i = 0; i < k; ++i) {
-            const int j = deg - k + i, t = draw(a.key, v, j);
+            const int j = deg - k + i, t = draw(key, v, j);
             bool hit = false;
             for (int l = 0; l < i; ++l) hit |= set[l] == t;
             set[i] = hit ? j : t;
@@ -192,19 +201,27 @@ __global__ __launch_bounds__(kBlock) void reset_kernel(const int32_t *__restrict
 }  // namespace
 
 int sgx_sample::sample_enqueue(const int32_t *rowPtr, const int32_t *columnIndex, int n_nodes, const int32_t *seeds, int batch,
-                               int n_hops, const int *fanouts, uint64_t seed, uint64_t step, int32_t *node_map, int32_t *n_id,
-                               int32_t *out_rowPtr, int32_t *out_col, int32_t *edge_pos, int64_t max_nodes, int64_t max_edges,
-                               const Bounds &b, int32_t *cbuf, int32_t *bsum, hipStream_t s)
+                               int n_hops, const int *fanouts, uint64_t seed, uint64_t step, const uint64_t *step_dev,
+                               int32_t *node_map, int32_t *n_id, int32_t *out_rowPtr, int32_t *out_col, int32_t *edge_pos,
+                               int64_t max_nodes, int64_t max_edges, const Bounds &b, int32_t *cbuf, int32_t *bsum, hipStream_t s)
 {
     const Counters ctr{cbuf, n_hops};
-    SGX_HIP_CHECK(hipMemsetAsync(cbuf, 0, sizeof(int32_t) * counter_count(n_hops), s));
+    if (step_dev) {
+        // the recorded call clears the counters with a kernel node, not a memset node: replayed after a plan build between
+        // two replays (its stream-ordered allocations and frees), the memset node of the instantiated graph was seen to leave
+        // the block as the previous replay had left it, and every kernel behind it then read a set status
+        hipLaunchKernelGGL(clear_kernel, dim3(1), dim3(kBlock), 0, s, cbuf, counter_count(n_hops));
+    } else {
+        SGX_HIP_CHECK(hipMemsetAsync(cbuf, 0, sizeof(int32_t) * counter_count(n_hops), s));
+    }
     hipLaunchKernelGGL(seed_kernel, dim3(grid_of(batch, kBlock, 0)), dim3(kBlock), 0, s, seeds, batch, n_nodes, node_map,
                        n_id, ctr);
     SGX_LAUNCH_CHECK();
     for (int h = 0; h < n_hops; ++h) {
         const uint64_t key = mix64(mix64(mix64(seed) ^ step) ^ (uint64_t)h);
         scan_launch(RowCounts{ctr, rowPtr, n_id, out_rowPtr, h, fanouts[h]}, b.front[h], bsum, s);
-        const SampleArgs sa{rowPtr, columnIndex, n_id, out_rowPtr, out_col, edge_pos, node_map, max_edges, key, h, fanouts[h]};
+        const SampleArgs sa{rowPtr, columnIndex, n_id, out_rowPtr, out_col, edge_pos, node_map, max_edges, key, step_dev, mix64(seed),
+                            h, fanouts[h]};
         hipLaunchKernelGGL(sample_kernel, dim3(grid_of(b.front[h], kBlock / 64, 0)), dim3(kBlock), 0, s, sa, ctr);
         scan_launch(FirstSeen{ctr, out_col, node_map, n_id, max_nodes, h}, b.edges[h], bsum, s);
         hipLaunchKernelGGL(relabel_kernel, dim3(grid_of(b.edges[h], kBlock, 2048)), dim3(kBlock), 0, s, out_col, node_map,
@@ -270,7 +287,7 @@ extern "C" int sgx_sample_neighbors(const int32_t *rowPtr, const int32_t *column
     }
     int32_t *cbuf = (int32_t *)workspace;
     int32_t *bsum = (int32_t *)((char *)workspace + counters_bytes(n_hops));
-    const int st = sample_enqueue(rowPtr, columnIndex, n_nodes, seeds, batch, n_hops, fanouts, seed, step, node_map, n_id,
+    const int st = sample_enqueue(rowPtr, columnIndex, n_nodes, seeds, batch, n_hops, fanouts, seed, step, nullptr, node_map, n_id,
                                   out_rowPtr, out_col, edge_pos, max_nodes, max_edges, b, cbuf, bsum, s);
     if (st != SGX_OK) return st;
     return sample_finish(cbuf, n_hops, hop_nodes, hop_edges, nullptr, s);

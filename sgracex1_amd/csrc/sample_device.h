@@ -163,12 +163,14 @@ static inline unsigned grid_of(int64_t items, int per, int64_t cap)
 }
 
 // sample.hip.  sample_enqueue: every launch of sgx_sample_neighbors on its checked arguments (batch >= 1), the counter
-// block `cbuf` cleared first, nothing read back.  sample_finish: the one read-back of counter_count(n_hops) int32 and
-// the stream synchronisation; status and hop counts decoded, the extras copied to `extras` (may be NULL).
+// block `cbuf` cleared first, nothing read back.  step_dev != NULL: the sampling key is formed in the kernel from that
+// device word in place of `step` (the same key for the same value), so a recorded call draws anew once the word changes.
+// sample_finish: the one read-back of counter_count(n_hops) int32 and the stream synchronisation; status and hop
+// counts decoded, the extras copied to `extras` (may be NULL).
 int sample_enqueue(const int32_t *rowPtr, const int32_t *columnIndex, int n_nodes, const int32_t *seeds, int batch, int n_hops,
-                   const int *fanouts, uint64_t seed, uint64_t step, int32_t *node_map, int32_t *n_id, int32_t *out_rowPtr,
-                   int32_t *out_col, int32_t *edge_pos, int64_t max_nodes, int64_t max_edges, const Bounds &b, int32_t *cbuf,
-                   int32_t *bsum, hipStream_t s);
+                   const int *fanouts, uint64_t seed, uint64_t step, const uint64_t *step_dev, int32_t *node_map, int32_t *n_id,
+                   int32_t *out_rowPtr, int32_t *out_col, int32_t *edge_pos, int64_t max_nodes, int64_t max_edges, const Bounds &b,
+                   int32_t *cbuf, int32_t *bsum, hipStream_t s);
 int sample_finish(const int32_t *cbuf, int n_hops, int64_t *hop_nodes, int64_t *hop_edges, int32_t *extras, hipStream_t s);
 
 }  // namespace sgx_sample

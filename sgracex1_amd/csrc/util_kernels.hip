@@ -126,9 +126,16 @@ __global__ __launch_bounds__(kBlock) void pack_rows_kernel(const char *__restric
     for (int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x; i < total; i += (int64_t)gridDim.x * kBlock) {
         const int64_t r = i / chunks;
         const int k = (int)(i - r * chunks);
-        const char *from = src + (int64_t)row_index[r] * src_pitch + 16 * k;
+        const int32_t s = row_index[r];
+        const char *from = src + (int64_t)s * src_pitch + 16 * k;
         char *to = dst + r * dst_pitch + 16 * k;
-        if (16 * k + 16 <= row_bytes) {
+        if (s < 0) {                                       // a filler row of a padded node batch (n_id = -1): zeros
+            if (16 * k + 16 <= row_bytes) {
+                *reinterpret_cast<u32x4_u *>(to) = u32x4{0, 0, 0, 0};
+            } else {
+                for (int b = 0; 16 * k + 2 * b < row_bytes; ++b) *reinterpret_cast<unsigned short *>(to + 2 * b) = 0;
+            }
+        } else if (16 * k + 16 <= row_bytes) {
             *reinterpret_cast<u32x4_u *>(to) = *reinterpret_cast<const u32x4_u *>(from);
         } else {
             for (int b = 0; 16 * k + 2 * b < row_bytes; ++b)

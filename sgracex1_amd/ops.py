@@ -1158,8 +1158,140 @@ def _adj_quant_key(qc):
     return (qc.w_qbits, qc.a_s, qc.a_z)
 
 
+class PaddedNodeSample(NodeSample):
+    """A NodeSample at a fixed capacity (sample_node_batch(pad=); include/sgx.h, "padded node batches"): every tensor has
+    its capacity size in every batch, the live rows and entries first and filler rows behind (n_id = -1).  The live
+    counts stay on the device -- `counts`, int32: n, edges, adjacency entries, feature entries, then the node and the edge
+    count after every hop -- so hop_nodes / hop_edges are empty and num_sampled_nodes / num_sampled_edges None.  adj is
+    None: the sampled CSR has spare entries behind its last row (its raw arrays are out_rowptr, out_col and edge_pos,
+    -1 past the live edges); adj_norm and fea are exact CSRs.  The tensors are views of the NodePadBuffers the call wrote:
+    valid until the next batch is drawn into them."""
+
+    num_sampled_nodes = num_sampled_edges = None
+
+
+class NodePadCapacity:
+    """The fixed sizes of a padded node batch (node_pad_capacity): n_rows (N), nnz_norm (C_a), nnz_fea (C_f), n_edges (E),
+    the sampler's bounds max_nodes / max_edges they come from, batch_size, fanouts, whether a feature CSR was counted, and
+    max_row = max(max(fanouts) + 1, 64), the bound on the longest row of the normalised adjacency."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+
+def node_pad_capacity(csr, batch_size, fanouts, features=None):
+    """The capacity every batch of `batch_size` seeds sampled from `csr` with `fanouts` fits (sgx_node_batch_pad_capacity;
+    rule and proof in include/sgx.h): host arithmetic, computed once per (graph, batch, fanouts, feature CSR).  features:
+    the feature_csr of the graph's x, or None; its per-row entry counts are read back once here."""
+    fan = [int(k) for k in fanouts]
+    H = len(fan)
+    if any(k < 0 for k in fan):
+        raise ValueError("node_pad_capacity: a fan-out of -1 leaves a row unbounded; padded batches need fan-outs >= 0")
+    fan_c = (ctypes.c_int32 * max(H, 1))(*fan)
+    rows = None
+    if features is not None:
+        rows = (features.rowptr[1:] - features.rowptr[:-1]).to(torch.int32).cpu().contiguous()
+    p = _lib.NodeBatchPad()
+    check(lib.sgx_node_batch_pad_capacity(csr.n_rows, csr.nnz, int(batch_size), H, fan_c,
+                                          None if rows is None else ctypes.cast(rows.data_ptr(), ctypes.POINTER(ctypes.c_int32)),
+                                          ctypes.byref(p)), "sgx_node_batch_pad_capacity")
+    mn, me = ctypes.c_int64(0), ctypes.c_int64(0)
+    lib.sgx_node_batch_workspace_bytes(csr.n_rows, csr.nnz, int(batch_size), H, fan_c, ctypes.byref(mn), ctypes.byref(me))
+    return NodePadCapacity(n_rows=p.n_rows, nnz_norm=p.nnz_norm, nnz_fea=p.nnz_fea, n_edges=p.n_edges, max_nodes=mn.value,
+                           max_edges=me.value, batch_size=int(batch_size), fanouts=tuple(fan), features=features is not None,
+                           max_row=max(max(fan) + 1, 64))
+
+
+class NodePadBuffers:
+    """The output buffers of padded node batches of one capacity, written again by every sample_node_batch(pad=, out=):
+    what a recorded step reads at fixed addresses.  Also the sampler's node map (kept at the sentinel between calls), the
+    OR-ed status word and the live counts.  n_id starts at -1, so no gather by it ever leaves its source."""
+
+    def __init__(self, cap, n_nodes, dtype, device, n_feat=None, y=False, n_masks=0):
+        N, Ca, Cf, E = cap.n_rows, cap.nnz_norm, cap.nnz_fea, cap.n_edges
+        new = lambda k, dt, v=0: torch.full((max(int(k), 1),), v, dtype=dt, device=device)
+        self.capacity, self.dtype = cap, dtype
+        self.n_id, self.rowptr, self.col, self.pos = new(N, torch.int32, -1), new(N + 1, torch.int32), new(E, torch.int32, -1), new(E, torch.int32, -1)
+        self.n_rowptr, self.n_col, self.n_val = new(N + 1, torch.int32), new(Ca, torch.int32), new(Ca, dtype)
+        self.dead = new(N, torch.bool, False)
+        self.ei, self.ei_agg = new(2 * E, torch.int64, -1), new(2 * E, torch.int64, -1)
+        self.f_rowptr = self.f_col = self.f_val = None
+        if cap.features:
+            self.n_feat = int(n_feat)
+            self.f_rowptr, self.f_col, self.f_val = new(N + 1, torch.int32), new(Cf, torch.int32), new(Cf, dtype)
+        self.y = new(N, torch.int64) if y else None
+        self.masks = [new(N, torch.bool, False) for _ in range(n_masks)]
+        self.node_map = new(n_nodes, torch.int32, SAMPLE_SENTINEL)
+        self.status = new(1, torch.int32)
+        self.counts = new(4 + 2 * (len(cap.fanouts) + 1), torch.int32)
+
+
+def _sample_node_batch_padded(csr, seeds, seed, step, fill, dtype, edge_weight, features, y, masks, cap, out):
+    """sample_node_batch(pad=cap): sgx_node_batch_sample_padded into `out` (a NodePadBuffers; None: a fresh one)."""
+    dev, n, B, H = csr.rowptr.device, csr.n_rows, seeds.numel(), len(cap.fanouts)
+    if B != cap.batch_size or cap.features != (features is not None):
+        raise ValueError("sample_node_batch: pad= is the node_pad_capacity of this batch size, these fan-outs and these features")
+    _dev(step, "step")
+    if step.dtype != torch.int64 or step.numel() != 1:
+        raise ValueError("sample_node_batch(pad=): step is a device int64 [1] tensor (the word a replay reads)")
+    if features is not None and (features.val.dtype != torch.float32 or features.n_rows != n or features._max_row is None):
+        raise ValueError("features must be the feature_csr of the graph's x (fp32 values, one row per node)")
+    if out is None:
+        out = NodePadBuffers(cap, n, dtype, dev, None if features is None else features.n_cols, y is not None, len(masks))
+    if out.capacity is not cap or out.dtype != dtype or (out.y is None) != (y is None) or len(out.masks) != len(masks):
+        raise ValueError("sample_node_batch: out= was built for another capacity, dtype, label or mask set")
+    N, Ca, Cf, E = cap.n_rows, cap.nnz_norm, cap.nnz_fea, cap.n_edges
+    fan_c = (ctypes.c_int32 * max(H, 1))(*cap.fanouts)
+    ws = _workspace(dev, lib.sgx_node_batch_workspace_bytes(n, csr.nnz, B, H, fan_c, None, None))
+    b = _lib.NodeBatch()
+    b.rowPtr, b.columnIndex, b.n_nodes, b.nnz = csr.rowptr.data_ptr(), csr.col.data_ptr(), n, csr.nnz
+    b.seeds, b.batch, b.n_hops, b.fanouts, b.dtype = seeds.data_ptr(), B, H, fan_c, dtype_code(dtype)
+    b.seed = int(seed) & (2**64 - 1)
+    b.node_map, b.n_id, b.out_rowPtr, b.out_col, b.edge_pos = (out.node_map.data_ptr(), out.n_id.data_ptr(), out.rowptr.data_ptr(),
+                                                               out.col.data_ptr(), out.pos.data_ptr())
+    b.max_nodes, b.max_edges = cap.max_nodes, cap.max_edges
+    if edge_weight is not None:
+        _dev(edge_weight, "edge_weight")
+        if edge_weight.dtype != torch.float32 or edge_weight.numel() != csr.nnz:
+            raise ValueError("edge_weight must be float32 [csr.nnz]")
+        b.edge_weight = edge_weight.data_ptr()
+    b.fill = float(fill)
+    b.rowPtr_norm, b.columnIndex_norm, b.values_norm = out.n_rowptr.data_ptr(), out.n_col.data_ptr(), out.n_val.data_ptr()
+    b.dead_row, b.edge_index, b.edge_index_agg = out.dead.data_ptr(), out.ei.data_ptr(), out.ei_agg.data_ptr()
+    if features is not None:
+        b.rowPtr_x, b.columnIndex_x, b.values_x = features.rowptr.data_ptr(), features.col.data_ptr(), features.val.data_ptr()
+        b.rowPtr_fea, b.columnIndex_fea, b.values_fea = out.f_rowptr.data_ptr(), out.f_col.data_ptr(), out.f_val.data_ptr()
+    if y is not None:
+        _dev(y, "y")
+        if y.dtype != torch.int64 or y.numel() != n:
+            raise ValueError("y must be int64 [n_nodes]")
+        b.y, b.y_out = y.data_ptr(), out.y.data_ptr()
+    for k, m in enumerate(masks):
+        _dev(m, "mask")
+        if m.dtype != torch.bool or m.numel() != n:
+            raise ValueError("masks must be bool [n_nodes]")
+        b.mask[k], b.mask_out[k] = m.data_ptr(), out.masks[k].data_ptr()
+    b.workspace, b.workspace_bytes = ws.data_ptr(), ws.numel()
+    p = _lib.NodeBatchPad()
+    p.n_rows, p.nnz_norm, p.nnz_fea, p.n_edges = N, Ca, Cf, E
+    p.step, p.status, p.counts = step.data_ptr(), out.status.data_ptr(), out.counts.data_ptr()
+    check(lib.sgx_node_batch_sample_padded(ctypes.byref(b), ctypes.byref(p), _stream()), "sgx_node_batch_sample_padded")
+    s = PaddedNodeSample(out.n_id[:N], None, out.pos[:E], B, [], [])
+    s.buffers, s.counts, s.status = out, out.counts, out.status
+    s.out_rowptr, s.out_col = out.rowptr[:N + 1], out.col[:E]
+    s.adj_norm = Csr(out.n_rowptr[:N + 1], out.n_col[:Ca], out.n_val[:Ca], N).with_facts(out.dead[:N], True, cap.max_row)
+    s.edge_index, s.edge_index_agg = out.ei[:2 * E].view(2, E), out.ei_agg[:2 * E].view(2, E)
+    s.fea = None
+    if features is not None:
+        s.fea = Csr(out.f_rowptr[:N + 1], out.f_col[:Cf], out.f_val[:Cf], features.n_cols).with_facts(
+            max_row=max(features._max_row, 64))
+    s.y = None if y is None else out.y[:N]
+    s.masks = [m[:N] for m in out.masks]
+    return s
+
+
 def sample_node_batch(csr, seeds, fanouts, seed=0, step=0, fill=0, dtype=torch.float32, edge_weight=None, features=None,
-                      y=None, masks=(), quant=None):
+                      y=None, masks=(), quant=None, pad=None, out=None):
     """sample_neighbors plus, on the device right behind it and inside the same single synchronisation
     (sgx_node_batch_sample, rule in include/sgx.h): the normalised adjacency sym_norm2 gives for the sampled rows,
     the rows n_id of `features` (a feature_csr) as the batch's feature Csr, y[n_id] (int64) and each of up to three
@@ -1168,10 +1300,28 @@ def sample_node_batch(csr, seeds, fanouts, seed=0, step=0, fill=0, dtype=torch.f
     (sgx_node_batch_sample_quant, same single synchronisation): adj_norm.quantized(qc) for quant and for
     quant.second_layer() is delivered -- the values on the unsigned w_qbits grid with their dead-row mask, flag and
     longest row recorded, and the mask values of the lean GAT backward (sgrace._lean_mask) -- so that the layers launch no
-    quantiser for the adjacency and read nothing back."""
+    quantiser for the adjacency and read nothing back.
+    pad (a node_pad_capacity of this batch size, fan-outs and features) with step a device int64 [1] tensor: the same
+    batch at the capacity's fixed sizes (sgx_node_batch_sample_padded) -> PaddedNodeSample, written into `out` (the
+    NodePadBuffers of an earlier call, at `.buffers` of what it returned; None: fresh ones).  The live prefix of every
+    tensor holds the unpadded call's bits for the step the word holds; the facts are constants -- max_row =
+    max(max(fanouts) + 1, 64), has_dead_rows = True with the exact mask -- and nothing is read from the device: no
+    synchronisation, capturable.  Errors of the sample (repeated seeds) reach out.status, not an exception."""
     _dev(seeds, "seeds")
     fan = [int(k) for k in fanouts]
     dev = csr.rowptr.device
+    if pad is not None:
+        if quant is not None:
+            raise ValueError("sample_node_batch: pad= does not go with quant= (padded quantised node batches are not built)")
+        if tuple(fan) != pad.fanouts:
+            raise ValueError("sample_node_batch: pad= was computed for other fan-outs")
+        masks = list(masks)
+        if len(masks) > 3:
+            raise ValueError("sample_node_batch gathers up to three masks")
+        return _sample_node_batch_padded(csr, seeds.to(torch.int32).contiguous(), seed, step, fill, dtype, edge_weight,
+                                         features, y, masks, pad, out)
+    if out is not None:
+        raise ValueError("sample_node_batch: out= needs pad=")
     if quant is not None and dtype != torch.float32:
         raise ValueError("sample_node_batch: quant needs dtype=torch.float32 (the quantised layer works on float32 buffers)")
     seeds = seeds.to(torch.int32).contiguous()

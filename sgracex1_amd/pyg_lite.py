@@ -268,7 +268,12 @@ class NodeBatch:
     input_id (positions of the seeds in input_nodes), num_sampled_nodes / num_sampled_edges per hop; plus adj, the same
     edges as a Csr whose row i holds the neighbours sampled for local node i (aggregation at the seed rows).
     From a loader with prepare="sym_norm2" also edge_index_agg (edge_index with its rows swapped: row 0 the aggregating
-    node, what the SGRACE layers take) and adj_norm (the Csr of sym_norm2 over it)."""
+    node, what the SGRACE layers take) and adj_norm (the Csr of sym_norm2 over it).
+    num_real_nodes: the sampled nodes' count -- None for a padded batch (NeighborLoader(pad=True)), whose tensors have the
+    capacity's sizes (filler rows behind the live ones: n_id = -1, x = 0, y = 0, masks False) and whose live count stays on
+    the device, in loader.counts; adj, num_sampled_nodes and num_sampled_edges are None there as well."""
+
+    num_real_nodes = None
 
     def __init__(self, **fields):
         self.__dict__.update(fields)
@@ -308,11 +313,39 @@ class NeighborLoader:
     for the QUANTISED layers as well -- adj_norm.quantized(qc) and .quantized(qc.second_layer()), what the layers look up,
     are delivered with their dead-row facts and the lean GAT backward's mask values, from the sampler's own launches and
     single read-back (ops.sample_node_batch(quant=)).  A training step of the quantised model then synchronises nowhere
-    outside the sampler."""
+    outside the sampler.
+
+    pad=True (with prepare="sym_norm2"): the same batches, and every FULL batch (exactly batch_size seeds) arrives PADDED to
+    one fixed capacity (ops.node_pad_capacity; rule in include/sgx.h, "padded node batches"): every tensor has the same
+    size in every batch, the sampled nodes come first and filler rows behind them -- x 0, n_id -1, y 0, masks False, an
+    adjacency row of one diagonal 1 -- which yield 0 in every layer and receive no gradient from a loss over the seeds,
+    out[:batch.batch_size].  Nothing is read back: no synchronisation, batch.num_real_nodes is None and the live counts
+    stay on the device (loader.counts, int32: nodes, edges, adjacency entries, feature entries, then per hop); the facts
+    the layers ask for are constants (longest row max(max(fanouts) + 1, 64), has_dead_rows = True with the exact mask).  A
+    padded batch lives in ONE set of buffers that the next batch overwrites: it is valid until the next one is drawn.
+    One recorded training step then serves every full batch (train.NodeTrainer.capture_loader).  The short last batch
+    arrives unpadded, as before.  What the eager call raises for a batch (repeated seeds) is OR-ed into a device word
+    instead; loader.status() reads it back once -- at the end of an epoch, say -- and raises it then.  transposed=True
+    works as before for the adjacency; the feature transpose is delivered only where it wants no plan (fewer than 64
+    entries per feature column at capacity), since a plan costs a read-back -- config.accb = 1 is not a padded route.
+    With attention on, a live row without a positive entry (fill = 0 leaves the rows of the last hop so) takes its
+    uniform softmax over the N padded columns rather than the live ones: the layers' rule, on the padded width.
+    ValueError where a batch CSR would want a plan (ops.Csr.wants_plan), which costs a read-back: a fan-out of -1,
+    max(fanouts) + 1 > 64, a feature row of over 64 entries, 2^20 or more adjacency or feature entries; and for quant=
+    (padded quantised batches are not built)."""
 
     def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0, prepare=None, fill=0,
-                 dtype=torch.float32, transposed=False, quant=None):
+                 dtype=torch.float32, transposed=False, quant=None, pad=False):
         from . import ops
+        if pad and prepare != "sym_norm2":
+            raise ValueError("pad=True needs prepare='sym_norm2'")
+        if pad and quant is not None:
+            raise ValueError("pad=True does not go with quant=: padded quantised node batches are not built")
+        if pad and any(int(k) < 0 for k in num_neighbors):
+            raise ValueError("pad=True needs fan-outs >= 0: a fan-out of -1 leaves a row unbounded")
+        if pad and max(int(k) for k in num_neighbors) + 1 > 64:
+            raise ValueError("pad=True needs max(num_neighbors) + 1 <= 64: a longer adjacency row wants a plan, and a plan "
+                             "costs a read-back")
         if quant is not None and not prepare:
             raise ValueError("quant needs prepare='sym_norm2'")
         if quant is not None and dtype != torch.float32:
@@ -347,11 +380,30 @@ class NeighborLoader:
             self.y = None if getattr(data, "y", None) is None else data.y.to(dev, torch.int64).contiguous()
             self.masks = [(name, getattr(data, name).to(dev, torch.bool).contiguous()) for name in _MASKS
                           if getattr(data, name, None) is not None]
+        self.pad = bool(pad)
+        if self.pad:
+            m = self.input_nodes
+            if m.numel() and (int(m.min()) < 0 or int(m.max()) >= n):      # (once per loader; a batch's status is not read)
+                raise ValueError("input_nodes must be node ids of the graph")
+            if self.fea._max_row > 64:
+                raise ValueError("pad=True needs feature rows of at most 64 entries: a longer one wants a plan, and a plan "
+                                 "costs a read-back")
+            B = min(self.batch_size, n)
+            self.capacity = cap = ops.node_pad_capacity(self.csr, B, self.num_neighbors, self.fea)
+            if cap.nnz_norm >= 1 << 20 or cap.nnz_fea >= 1 << 20:
+                raise ValueError(f"pad=True: the capacity ({cap.nnz_norm} adjacency, {cap.nnz_fea} feature entries) reaches 2^20 "
+                                 "entries: such a batch wants a plan, and a plan costs a read-back")
+            self.buffers = ops.NodePadBuffers(cap, n, dtype, dev, x.shape[1], self.y is not None, len(self.masks))
+            self.counts = self.buffers.counts
+            self.seeds_buf = torch.zeros(B, dtype=torch.int32, device=dev)      # what a recorded sample reads: load()
+            self.step_buf = torch.zeros(1, dtype=torch.int64, device=dev)
+            self.x_buf = torch.zeros((cap.n_rows, x.shape[1]), dtype=x.dtype, device=dev)
 
     def __len__(self):
         return (self.input_nodes.numel() + self.batch_size - 1) // self.batch_size
 
-    def __iter__(self):
+    def epoch_batches(self):
+        """(seeds, input_id, step) of the next epoch's batches, in order, as __iter__ samples them; takes one epoch number."""
         m = self.input_nodes.numel()
         if self.shuffle:
             g = torch.Generator().manual_seed(self.seed * 1000003 + self.epoch)
@@ -362,7 +414,60 @@ class NeighborLoader:
         first_step, self.epoch = self.epoch * len(self), self.epoch + 1
         for b, i in enumerate(range(0, m, self.batch_size)):
             input_id = perm[i:i + self.batch_size]
-            yield self._batch(self.input_nodes[input_id], input_id, first_step + b)
+            yield self.input_nodes[input_id], input_id, first_step + b
+
+    def __iter__(self):
+        for seeds, input_id, step in self.epoch_batches():
+            yield self._batch(seeds, input_id, step)
+
+    def padded(self, seeds):
+        """Whether the batch of `seeds` arrives padded: pad=True and a full batch.  Host only."""
+        return self.pad and seeds.numel() == self.capacity.batch_size
+
+    def load(self, seeds, step):
+        """The seeds and the step word of the next padded batch, copied into the fixed buffers padded_batch() reads (two
+        launches, no synchronisation): what changes between two replays of a recorded padded_batch()."""
+        self.seeds_buf.copy_(seeds)
+        self.step_buf.fill_(int(step))
+
+    def padded_batch(self, input_id=None):
+        """The padded NodeBatch of what load() put in place, drawn into the loader's one set of buffers: every launch of
+        it is capturable, and it reads nothing back."""
+        from . import ops
+        s = ops.sample_node_batch(self.csr, self.seeds_buf, self.num_neighbors, seed=self.seed, step=self.step_buf,
+                                  fill=self.fill, dtype=self.dtype, features=self.fea, y=self.y,
+                                  masks=[m for _, m in self.masks], pad=self.capacity, out=self.buffers)
+        x = ops.pack_rows(self.data.x, s.n_id, out=self.x_buf)
+        A, n, cap = s.adj_norm, self.capacity.n_rows, self.capacity
+        ops.attach(x, ("fea_csr", self.dtype), s.fea)
+        ops.attach(s.edge_index_agg, ("sym_norm2", n, 1, self.dtype), (s.edge_index_agg, A.val, A))
+        if self.transposed:
+            if cap.nnz_fea < 64 * s.fea.n_cols:          # (ops.csr_transpose builds a plan, with its read-back, from there on)
+                fea32 = s.fea
+                if self.dtype != torch.float32:
+                    fea32 = ops.attach(x, ("fea_csr", torch.float32),
+                                       ops.Csr(s.fea.rowptr, s.fea.col, s.fea.val.float(), s.fea.n_cols).with_facts(
+                                           max_row=s.fea._max_row))
+                ops.attach(x, ("fea_csr_t", torch.float32), ops.csr_transpose(fea32, method="device"))
+            A._transpose_pattern = ops.csr_transpose(A, return_order=True, method="device")
+        fields = dict(x=x, edge_index=s.edge_index, edge_index_agg=s.edge_index_agg, adj_norm=A, n_id=s.n_id.long(),
+                      adj=None, batch_size=s.batch_size, input_id=input_id, num_sampled_nodes=None,
+                      num_sampled_edges=None, num_real_nodes=None)
+        if s.y is not None:
+            fields["y"] = s.y
+        for (name, _), m in zip(self.masks, s.masks):
+            fields[name] = m
+        return NodeBatch(**fields)
+
+    def status(self):
+        """Reads the OR-ed status word of the padded batches drawn since the last call back (one synchronisation), clears
+        it, and raises what the eager call would have raised for such a batch (ops.SgxError)."""
+        from . import _lib
+        st = int(self.buffers.status.item())
+        self.buffers.status.zero_()
+        if st:
+            # (the sampler's status bits as sgx_node_batch_sample maps them: 1 = seeds, else a capacity = SGX_ERR_SHAPE, -2)
+            raise _lib.SgxError(_lib.SGX_ERR_SEEDS if st & 1 else -2, "sgx_node_batch_sample_padded")
 
     def _prepared(self, seeds, input_id, step):
         from . import ops
@@ -383,7 +488,7 @@ class NeighborLoader:
             A._transpose_pattern = ops.csr_transpose(A, return_order=True, method="device")
         fields = dict(x=x, edge_index=s.edge_index, edge_index_agg=s.edge_index_agg, adj_norm=A, n_id=s.n_id.long(),
                       adj=s.adj, batch_size=s.batch_size, input_id=input_id, num_sampled_nodes=s.num_sampled_nodes,
-                      num_sampled_edges=s.num_sampled_edges)
+                      num_sampled_edges=s.num_sampled_edges, num_real_nodes=n)
         if s.y is not None:
             fields["y"] = s.y
         for (name, _), m in zip(self.masks, s.masks):
@@ -393,6 +498,9 @@ class NeighborLoader:
     def _batch(self, seeds, input_id, step):
         from . import ops
         if self.prepare:
+            if self.padded(seeds):
+                self.load(seeds, step)
+                return self.padded_batch(input_id)
             return self._prepared(seeds, input_id, step)
         d = self.data
         s = ops.sample_neighbors(self.csr, seeds, self.num_neighbors, seed=self.seed, step=step)
@@ -402,7 +510,8 @@ class NeighborLoader:
                                          (A.rowptr[1:] - A.rowptr[:-1]).long(), output_size=A.nnz)
         fields = dict(x=ops.pack_rows(d.x, s.n_id), edge_index=torch.stack([A.col[:A.nnz].long(), target]),
                       n_id=n_idx, adj=A, batch_size=s.batch_size, input_id=input_id,
-                      num_sampled_nodes=s.num_sampled_nodes, num_sampled_edges=s.num_sampled_edges)
+                      num_sampled_nodes=s.num_sampled_nodes, num_sampled_edges=s.num_sampled_edges,
+                      num_real_nodes=n_idx.numel())
         if getattr(d, "y", None) is not None:
             fields["y"] = d.y[n_idx]
         for name in _MASKS:

@@ -281,7 +281,9 @@ class FPYNQ_GAT(torch.autograd.Function):
             else:
                 E, S = saved[3], saved[4]
                 sg, g1 = ops.gat_backward_edges(A, E, S, g.contiguous(), Wh, ctx.alpha, dead=ctx.dead)
-            P = ops.Csr(A.rowptr, A.col, S.contiguous(), A.n_cols, A.plan if A.wants_plan else None)   # attention matrix, fp32 values; A's schedule
+            # attention matrix, fp32 values; A's schedule -- and A's longest row where its builder knew it, so that P wants a
+            # plan exactly where A does (a loader's batch of short rows builds none: no read-back, capturable)
+            P = ops.Csr(A.rowptr, A.col, S.contiguous(), A.n_cols, A.plan if A.wants_plan else None).with_facts(max_row=A._max_row)
             # column sums of sg = row sums over A^T; the transposed pattern is built once per graph
             if getattr(A, "_transpose_pattern", None) is None:
                 A._transpose_pattern = ops.csr_transpose(A, return_order=True)

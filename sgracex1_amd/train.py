@@ -418,20 +418,74 @@ class NodeTrainer(_Trainer):
         last warm-up step runs under torch.cuda.set_sync_debug_mode("error"): a layer path that synchronises cannot be
         captured, and capture() raises a RuntimeError that names the configuration instead of recording it."""
         batch = (x, edge_index, y, mask, n_prefix)
+        return self._capture(batch, warmup, self._sync_probe("capture", lambda: self.step(*batch)))
 
+    def _sync_probe(self, name, run):
+        """The probe of capture() and capture_loader(): run() once more under torch.cuda.set_sync_debug_mode("error") ->
+        None, or the RuntimeError to raise in place of recording a step that synchronises."""
         def probe():
             mode = torch.cuda.get_sync_debug_mode()
             torch.cuda.set_sync_debug_mode("error")
             try:
-                self.step(*batch)
+                run()
             except RuntimeError as e:
                 if "synchroniz" not in str(e):        # torch's sync-debug message; any other error is the caller's to see
                     raise
-                failure = RuntimeError(f"NodeTrainer.capture: the layer path synchronises with {self._configuration()}; "
+                failure = RuntimeError(f"NodeTrainer.{name}: the layer path synchronises with {self._configuration()}; "
                                        f"the step is not captured ({e})")
                 failure.__cause__ = e
                 return failure
             finally:
                 torch.cuda.set_sync_debug_mode(mode)
 
-        return self._capture(batch, warmup, probe)
+        return probe
+
+    def capture_loader(self, loader, warmup=2):
+        """ONE recorded step for every full batch of `loader` (a pyg_lite.NeighborLoader(pad=True); anything else:
+        ValueError) -> a callable that runs one epoch and returns its losses, one device tensor [1] per batch, in the
+        loader's order.
+
+        The recorded step is the padded sample and its preparation (loader.padded_batch(): sgx_node_batch_sample_padded
+        into the loader's one set of buffers, the gather of x and, with transposed=True, the transposes), model.features,
+        ops.NodeLoss with n_prefix = batch_size, the layers' backward and ops.adam_step -- one stream, no parallel
+        branches, as capture().  An epoch draws its batches as iterating the loader would; per full batch the seeds and the
+        step word are copied into the loader's fixed buffers (loader.load: device to device, no synchronisation) and the
+        recording is replayed; the short last batch runs through step() unpadded in its place.  An epoch thus takes
+        exactly the steps of `for b in loader: step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size)`, bit for bit.
+        Covers GAT_PYNQ with config.compute_attention 0 and 1 (attention needs a transposed=True loader: the backward's
+        transposed pattern is then built on the device), fp32 and fp16, config.accb = 0.  The warm-up steps run on the
+        loader's first batch_size input nodes on a copy of the state; the last of them runs under
+        torch.cuda.set_sync_debug_mode("error"), and a configuration whose layer path synchronises raises capture()'s
+        RuntimeError instead of being recorded.  loader.status() tells, once per epoch or run, whether a batch failed."""
+        from . import config
+        if not getattr(loader, "pad", False) or not hasattr(loader, "padded_batch"):
+            raise ValueError("capture_loader takes a NeighborLoader(pad=True)")
+        if int(config.compute_attention) and not loader.transposed:
+            raise ValueError("capture_loader: with config.compute_attention the loader needs transposed=True (the backward "
+                             "would otherwise build the transposed pattern with a sort, per batch)")
+        if loader.y is None:
+            raise ValueError("capture_loader: the loader's data carries no labels")
+        B = loader.capacity.batch_size
+        if loader.input_nodes.numel() < B:
+            raise RuntimeError("capture_loader: the loader has no full batch to record a step on")
+        loader.load(loader.input_nodes[:B], 0)
+
+        def run():
+            b = loader.padded_batch()
+            return self.step(b.x, b.edge_index_agg, b.y, n_prefix=B)
+
+        replay = self._capture((), warmup, self._sync_probe("capture_loader", run), run=run)
+
+        def epoch():
+            losses = []
+            for seeds, input_id, step in loader.epoch_batches():
+                if loader.padded(seeds):
+                    loader.load(seeds, step)
+                    losses.append(replay().clone())
+                else:
+                    b = loader._batch(seeds, input_id, step)
+                    losses.append(self.step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size))
+            return losses
+
+        epoch.graph, epoch.replay = replay.graph, replay
+        return epoch

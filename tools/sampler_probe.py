@@ -8,6 +8,7 @@ of examples/sgrace_node_classification.py (GCN and GAT).  One JSON line per meas
     python tools/sampler_probe.py > sampler.jsonl
     python tools/sampler_probe.py --quick          # only the kernels, for a rocprofv3 --kernel-trace --stats run
     python tools/sampler_probe.py --node-batch [--arms default] [--trace]
+    python tools/sampler_probe.py --node-batch --replay replay|eager [--label L]    # profiles/r22_node_replay.jsonl
                                                    # the training step through the default and the prepared NeighborLoader
                                                    # (GCN and GAT, the example's shape and the ogbn-products shape), the arms
                                                    # interleaved, median of repeated windows and their spread; and the batch
@@ -275,6 +276,74 @@ def node_batch(arms, trace, accbs=(0,), qbits=None):
         torch.cuda.empty_cache()
 
 
+def node_replay(leg):
+    """--node-batch --replay: the NodeTrainer mini-batch step on the example's graph at batch 128 and [10, 10], GCN and
+    attention, as ONE leg per process so that two checkouts can take turns in one visit: leg "replay" -- the padded loader
+    and NodeTrainer.capture_loader's recorded step; leg "eager" -- NodeTrainer.step on the prepared loader's batches (runs
+    on a checkout without padded batches too).  640 training nodes: five full batches an epoch, no short one."""
+    import importlib.util
+    import statistics
+    from sgracex1_amd import config, pyg_lite, sgrace
+    from sgracex1_amd.train import NodeTrainer
+    dev = torch.device("cuda")
+    spec = importlib.util.spec_from_file_location("nc", os.path.join(ROOT, "examples", "sgrace_node_classification.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    x, ei, y = mod.planted_partition(3000, 5, 200, 0.02, 0.002, 1, dev)
+    train = torch.zeros(3000, dtype=torch.bool, device=dev)
+    train[:640] = True
+    data = pyg_lite.NodeData(x, ei, y, train_mask=train)
+    bs, fan, windows, epochs = 128, [10, 10], 7, 6
+    for attention in (0, 1):
+        config.acc, config.accb, config.device, config.compute_attention, config.gat_edge_outputs = 1, 0, "cuda", attention, 1
+        sgrace.init_SGRACE()
+        torch.manual_seed(0)
+        model = sgrace.GAT_PYNQ(x.shape[1], 16, 1, 5).to(dev).train()
+        trainer = NodeTrainer(model, lr=0.01)
+        kw = dict(batch_size=bs, input_nodes=train, shuffle=True, seed=1, prepare="sym_norm2", transposed=bool(attention))
+        extra = {}
+        if leg == "replay":
+            loader = pyg_lite.NeighborLoader(data, fan, pad=True, **kw)
+            epoch = trainer.capture_loader(loader)
+            live = torch.zeros(4, dtype=torch.int64, device=dev)
+
+            def one_epoch():
+                return epoch()
+        else:
+            loader = pyg_lite.NeighborLoader(data, fan, **kw)
+
+            def one_epoch():
+                return [trainer.step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size) for b in loader]
+        for _ in range(3):
+            one_epoch()
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(windows):
+            t0 = time.perf_counter()
+            for _ in range(epochs):
+                n_steps = len(one_epoch())
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) / (epochs * n_steps) * 1e3)
+        if leg == "replay":
+            loader.status()
+            seen = 0
+            for seeds, _, step in loader.epoch_batches():          # the live counts of one more epoch, summed on the device
+                loader.load(seeds, step)
+                epoch.replay()
+                live += loader.counts[:4]
+                seen += 1
+            cap = loader.capacity
+            mean = [round(v / seen, 1) for v in live.tolist()]
+            extra = {"padded_rows": cap.n_rows, "padded_adj_entries": cap.nnz_norm, "padded_fea_entries": cap.nnz_fea,
+                     "padded_edges": cap.n_edges, "live_rows_mean": mean[0], "live_edges_mean": mean[1],
+                     "live_adj_entries_mean": mean[2], "live_fea_entries_mean": mean[3]}
+        print(json.dumps({"end_to_end": "NodeTrainer mini-batch step (sample + preparation + layers + loss + backward + Adam)",
+                          "leg": leg, "model": "GAT" if attention else "GCN", "graph": "example (3 000 nodes)", "batch": bs,
+                          "fanouts": fan, "steps_per_epoch": n_steps, "step_ms_median": round(statistics.median(times), 4),
+                          "step_ms_min": round(min(times), 4), "step_ms_max": round(max(times), 4), "windows": windows,
+                          "steps_per_window": epochs * n_steps, **extra}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -289,10 +358,16 @@ def main():
                          "or is left at its default")
     ap.add_argument("--transposed", action="store_true", help="--node-batch: add the arm prepared_t (the prepared loader with "
                                                               "transposed=True) to the same windows")
+    ap.add_argument("--replay", default=None, choices=["replay", "eager"],
+                    help="--node-batch: one leg of the replayed-step measurement (profiles/r22_node_replay.jsonl): 'replay' = "
+                         "the padded loader through NodeTrainer.capture_loader, 'eager' = NodeTrainer.step on the prepared "
+                         "loader (also on a checkout without padded batches); run the two alternately, a process each")
     a = ap.parse_args()
     if a.node_batch:
         if a.label:
             print(json.dumps({"label": a.label}), flush=True)
+        if a.replay:
+            return node_replay(a.replay)
         arms = a.arms.split(",") + (["prepared_t"] if a.transposed else [])
         if a.quant and a.arms == "default,prepared":
             arms = ["prepared", "prepared_q"] + arms[2:]
