@@ -1193,8 +1193,7 @@ def node_pad_capacity(csr, batch_size, fanouts, features=None):
         rows = (features.rowptr[1:] - features.rowptr[:-1]).to(torch.int32).cpu().contiguous()
     p = _lib.NodeBatchPad()
     check(lib.sgx_node_batch_pad_capacity(csr.n_rows, csr.nnz, int(batch_size), H, fan_c,
-                                          None if rows is None else ctypes.cast(rows.data_ptr(), ctypes.POINTER(ctypes.c_int32)),
-                                          ctypes.byref(p)), "sgx_node_batch_pad_capacity")
+                                          _ptr(rows), ctypes.byref(p)), "sgx_node_batch_pad_capacity")
     mn, me = ctypes.c_int64(0), ctypes.c_int64(0)
     lib.sgx_node_batch_workspace_bytes(csr.n_rows, csr.nnz, int(batch_size), H, fan_c, ctypes.byref(mn), ctypes.byref(me))
     return NodePadCapacity(n_rows=p.n_rows, nnz_norm=p.nnz_norm, nnz_fea=p.nnz_fea, n_edges=p.n_edges, max_nodes=mn.value,

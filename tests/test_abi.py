@@ -1,6 +1,7 @@
 """CPU-side checks of the drop-in boundary: the C-ABI library loads and exports exactly what
-include/sgx.h declares, the ctypes struct mirrors the header, and argument validation answers
-with the documented status codes without touching a GPU."""
+include/sgx.h declares, the binding _lib derives from the header agrees with the C compiler on every struct,
+field and constant and refuses C it does not know, and argument validation answers with the documented
+status codes without touching a GPU."""
 import ctypes
 import os
 import re
@@ -20,15 +21,17 @@ def L():
     return _lib
 
 
+def _header_text():
+    return re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+
+
 def _header_functions():
-    text = open(HEADER).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(sgx_[a-z0-9_]+)\s*\(", text)))
+    return sorted(set(re.findall(r"\b(sgx_[a-z0-9_]+)\s*\(", _header_text())))
 
 
 def test_every_declared_symbol_is_exported(L):
     declared = _header_functions()
-    assert declared == sorted(L.SYMBOLS)
+    assert declared == sorted(L.SYMBOLS) and len(L.SYMBOLS) == len(set(L.SYMBOLS))
     for name in declared:
         assert hasattr(L.lib, name), name
     out = subprocess.check_output(["nm", "-D", "--defined-only", L.LIB_PATH], text=True)
@@ -36,30 +39,117 @@ def test_every_declared_symbol_is_exported(L):
     assert exported == set(declared)
 
 
-def test_header_compiles_as_c_and_struct_layout_matches(L, tmp_path):
-    src = tmp_path / "layout.c"
-    src.write_text(
-        '#include <stdio.h>\n#include <stddef.h>\n#include "sgx.h"\n'
-        "int main(void){\n"
-        ' printf("%zu\\n", sizeof(sgx_layer_desc));\n'
-        + "".join(f' printf("{name} %zu\\n", offsetof(sgx_layer_desc, {name}));\n' for name, _ in L.LayerDesc._fields_)
-        + ' printf("quant_struct %zu\\n", sizeof(sgx_quant));\n'
-        + "".join(f' printf("q.{name} %zu\\n", offsetof(sgx_quant, {name}));\n' for name, _ in L.Quant._fields_)
-        + " return 0;}\n")
-    exe = tmp_path / "layout"
+@pytest.fixture(scope="module")
+def compiler_says(L, tmp_path_factory):
+    """What the C compiler makes of everything the reader took from the header: {"sizeof T": n, "offsetof T.f": n,
+    "fieldsize T.f": n, "const NAME": v}, from one C99 program compiled with -Wall -Werror."""
+    body = []
+    for c_name, cls in L.ABI.structs.items():
+        body.append(f' printf("sizeof {c_name} %zu\\n", sizeof({c_name}));\n')
+        for f, _ in cls._fields_:
+            body.append(f' printf("offsetof {c_name}.{f} %zu\\n", offsetof({c_name}, {f}));\n')
+            body.append(f' printf("fieldsize {c_name}.{f} %zu\\n", sizeof((({c_name} *)0)->{f}));\n')
+    for name in L.ABI.constants:
+        body.append(f' printf("const {name} %lld\\n", (long long)({name}));\n')
+    tmp = tmp_path_factory.mktemp("layout")
+    src, exe = tmp / "layout.c", tmp / "layout"
+    src.write_text('#include <stdio.h>\n#include <stddef.h>\n#include "sgx.h"\nint main(void){\n' + "".join(body)
+                   + " return 0;}\n")
     subprocess.check_call(["gcc", "-std=c99", "-Wall", "-Werror", "-I", os.path.join(ROOT, "include"), str(src),
                            "-o", str(exe)])
-    lines = subprocess.check_output([str(exe)], text=True).split("\n")
-    assert int(lines[0]) == ctypes.sizeof(L.LayerDesc)
-    for ln in lines[1:]:
-        if ln:
-            name, off = ln.split()
-            if name == "quant_struct":
-                assert ctypes.sizeof(L.Quant) == int(off)
-            elif name.startswith("q."):
-                assert getattr(L.Quant, name[2:]).offset == int(off), name
-            else:
-                assert getattr(L.LayerDesc, name).offset == int(off), name
+    said = {}
+    for ln in subprocess.check_output([str(exe)], text=True).splitlines():
+        kind, what, value = ln.split()
+        said[f"{kind} {what}"] = int(value)
+    assert len(said) == len(body)
+    return said
+
+
+def test_header_compiles_as_c_and_struct_layout_matches(L, compiler_says):
+    """Every struct of the header, not a chosen few: size, the offset of every field, and the size of every field -- a
+    4-byte type bound where the header has 8 shows there even when padding hides it from the offsets."""
+    declared = re.findall(r"typedef\s+struct\s+(\w+)\s*\{", _header_text())
+    assert list(L.ABI.structs) == declared and len(declared) >= 25
+    assert {"sgx_layer_desc", "sgx_quant"} <= set(declared)
+    for c_name, cls in L.ABI.structs.items():
+        assert getattr(L, cls.__name__) is cls and "sgx_" + re.sub(r"(?<!^)([A-Z])", r"_\1", cls.__name__).lower() == c_name
+        assert ctypes.sizeof(cls) == compiler_says[f"sizeof {c_name}"], c_name
+        for f, ctype in cls._fields_:
+            assert getattr(cls, f).offset == compiler_says[f"offsetof {c_name}.{f}"], (c_name, f)
+            assert ctypes.sizeof(ctype) == getattr(cls, f).size == compiler_says[f"fieldsize {c_name}.{f}"], (c_name, f)
+
+
+def test_every_constant_matches_the_compiler(L, compiler_says):
+    text = _header_text()
+    declared = set(re.findall(r"#define[ \t]+(SGX_\w+)[ \t]+\S", text))
+    for body in re.findall(r"typedef\s+enum\s+\w+\s*\{(.*?)\}", text, flags=re.S):
+        declared |= set(re.findall(r"(\w+)\s*=", body))
+    assert set(L.ABI.constants) == declared and len(declared) >= 27          # 9 #defines, 18 enumerators
+    for name, value in L.ABI.constants.items():
+        assert compiler_says[f"const {name}"] == value == getattr(L, name), name
+    assert (L.SGX_OK, L.SGX_ERR_NULL, L.SGX_ERR_BLOCKS, L.SGX_VERSION, L.SGX_F32, L.SGX_BATCH_BACKWARD) == (0, -1, -9, 110, 1, 1)
+
+
+def test_representative_signatures(L):
+    """One function per kind of type in the header, written out by hand: what the reader must give for them."""
+    from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p as vp
+
+    def sig(name):
+        fn = getattr(L.lib, name)
+        return fn.restype, list(fn.argtypes)
+
+    assert sig("sgx_spmm_csr") == (c_int, [c_int] * 7 + [vp] * 4 + [c_int64, vp, c_int64, vp, vp, c_size_t, vp])
+    assert sig("sgx_head_loss") == (c_int, [c_int] * 3 + [vp] * 4 + [c_float, c_uint64, c_uint64, vp, c_float] + [vp] * 6
+                                    + [c_size_t, vp])
+    assert sig("sgx_plan_create_ex") == (c_int, [POINTER(vp), vp, c_int, c_int, c_int, vp])
+    assert sig("sgx_layer_forward_stats") == (c_int, [POINTER(L.LayerDesc), POINTER(L.GatStats), vp])
+    assert sig("sgx_plan_natural_utilization") == (c_float, [vp])
+    assert sig("sgx_plan_export") == (c_int64, [vp, c_int, vp, c_int64, vp])
+    assert sig("sgx_status_string") == (c_char_p, [c_int])
+    assert sig("sgx_reload_env") == (None, [])
+    assert sig("sgx_adam_step") == (c_int, [POINTER(L.AdamDesc), vp])
+    assert L.AdamTensor._fields_ == [("param", vp), ("m", vp), ("v", vp), ("grad", vp), ("n", c_int64), ("param_t_out", vp),
+                                     ("dtype_t", c_int32), ("rows", c_int32), ("cols", c_int32)]
+    assert L.AdamDesc._fields_ == [("n_tensors", c_int32), ("lr", c_double), ("beta1", c_double), ("beta2", c_double),
+                                   ("eps", c_double), ("weight_decay", c_double), ("step", vp),
+                                   ("tensor", L.AdamTensor * 16)]
+    # the two kinds of pointer field that are not c_void_p: to a complete struct, and the host arrays of sgx_node_batch
+    assert dict(L.LayerDesc._fields_)["quant"] is POINTER(L.Quant)
+    assert dict(L.LayerGradDesc._fields_)["stats"] is POINTER(L.GatStats)
+    node = dict(L.NodeBatch._fields_)
+    assert (node["fanouts"], node["hop_nodes"], node["hop_edges"]) == (POINTER(c_int32), POINTER(c_int64), POINTER(c_int64))
+    assert node["seeds"] is vp and node["mask"] is vp * 3 and node["seed"] is c_uint64
+    assert dict(L.LayerDesc._fields_)["plan_adj"] is vp and dict(L.NodeBatchQuant._fields_)["values_q"] is vp * 2
+
+
+_PROLOGUE = "#include <stdint.h>\n#define SGX_N 3\ntypedef struct sgx_ok { int32_t a[SGX_N]; float *p, *q[2]; } sgx_ok;\n"
+
+
+@pytest.mark.parametrize("bad, line", [
+    ("int sgx_f(const sgx_ok *d,\n          int64x_t n);", 5),                          # an unknown type name
+    ("typedef struct sgx_s {\n  unsigned flags;\n} sgx_s;", 5),                         # another: no `unsigned` in the ABI
+    ("int sgx_f(int n,\n          void (*done)(int), void *stream);", 5),               # a function-pointer parameter
+    ("typedef struct sgx_s {\n  int32_t a;\n  int32_t flag : 1;\n} sgx_s;", 6),         # a bit-field
+    ("typedef struct sgx_s {\n  float x[SGX_N + 1];\n} sgx_s;", 5),                     # an extent that is an expression
+    ("typedef struct sgx_s {\n  float x[SGX_M];\n} sgx_s;", 5),                         # ... or a name never defined
+    ("typedef struct sgx_s {\n  float x[2][2];\n} sgx_s;", 5),
+    ("typedef struct sgx_s {\n  float **x;\n} sgx_s;", 5),
+    ("#define SGX_M (1 << 4)", 4),
+    ("typedef enum sgx_e { SGX_A = 0,\n SGX_B } sgx_e;", 5),                             # an enumerator without a value
+    ("sgx_ok sgx_f(void);", 4),                                                         # a struct by value
+    ("int sgx_f(sgx_ok d);", 4),
+    ("int sgx_f(int n, ...);", 4),
+])
+def test_the_reader_refuses_what_it_does_not_know(bad, line):
+    """Strictness: each text is one declaration shape the header does not use.  The reader raises naming the line."""
+    from sgracex1_amd import _abi
+    good = _abi.read_header(_PROLOGUE)
+    assert good.constants == {"SGX_N": 3} and [n for n, _ in good.structs["sgx_ok"]._fields_] == ["a", "p", "q"]
+    text = _PROLOGUE + bad + "\n"
+    with pytest.raises(_abi.HeaderError) as err:
+        _abi.read_header(text, "bad.h")
+    assert str(err.value).startswith(f"bad.h:{line}: "), str(err.value)
+    assert str(err.value).endswith(text.split("\n")[line - 1].strip()), str(err.value)
 
 
 def test_version_and_status_strings(L):
