@@ -311,6 +311,52 @@ int sgx_xw_dense_act(int dtype, int relu, int n_rows, int M_fea, int P,
                      const void *X, int64_t ldx, const void *Wt, int64_t ldw,
                      void *H, int64_t ldh, void *stream);
 
+/* Which kernel arm sgx_xw_dense / sgx_xw_dense_act take for these operands, for reports and tests (added without a version
+ * bump, SGX_VERSION stays 110: a new declaration, nothing else changes): a host query without a launch and without a
+ * device (where the launch would fall back to 256 CUs the query does too), answered by the functions the launch itself
+ * uses.  X, Wt, H: the pointers the call would get (only their alignment is read; non-NULL when n_rows > 0); pitches in
+ * elements.  Returns the negative sgx error the call would return before a launch, or
+ *   kind | a << 4 | b << 10 | vec << 16 | wgs_per_cu << 17 | blocks << 21 | waves << 32
+ * in fields of 4 (kind), 6 (a), 6 (b), 1 (vec), 4 (wgs_per_cu), 11 (blocks) and 31 (waves) bits: the SGX_XW_FORM_*_SHIFT and
+ * _MASK constants below, field = word >> SHIFT & MASK.
+ * kind    a, b      blocks                                waves
+ * TILE       NT, MT    column blocks of 256 (a, b: the LAST  wavefronts of one block's launch: one tile of 16 MT rows
+ *                      block's; whole ones before it are      each, never more
+ *                      <16, 1>, or <16, 2> from 32768 rows)
+ * STATIONARY KS, NTW   column groups of 16 NTW columns        wavefronts the persistent grid holds (whole workgroups of
+ *            (fp32:                                           four): the kernel makes waves / blocks (rounded down)
+ *            KB, NTW)                                         streams of them, stream s walks row tiles s, s + streams,
+ *                                                             ... of 32 rows (fp32: 16); waves % blocks wavefronts idle
+ * TILE_LDS   8, 8      column blocks of 128                  wavefronts of the grid (four per 128 x 128 tile)
+ * WLDS       fp16: NT, n_cb; fp32: KB and the LAST block's NT (whole blocks before it: 16)
+ *                      fp16: column blocks of 16 NT          fp16: per column block, wavefront w walks row tiles
+ *                      columns (one grid); fp32: blocks      w, w + waves, ... of 32 rows; fp32: of one block's launch,
+ *                      of 256 (one launch each)              tiles of 16 rows
+ * REF_HALF   0, 0      0                                     0   (SGX_ACC_REF_HALF: its arms are refhalf.hip's own)
+ * NONE       n_rows == 0: nothing is launched
+ * vec = 1: H is stored by vectors (16 bytes: fp32, fp16 STATIONARY with NTW even, fp16 WLDS; 8 bytes otherwise), 0: element
+ * by element (H or its pitch under-aligned).  wgs_per_cu: workgroups a CU is given by the persistent grids (STATIONARY,
+ * WLDS), 0 otherwise.  blocks saturates at 2047. */
+#define SGX_XW_FORM_NONE 0
+#define SGX_XW_FORM_TILE 1
+#define SGX_XW_FORM_STATIONARY 2
+#define SGX_XW_FORM_TILE_LDS 3
+#define SGX_XW_FORM_WLDS 4
+#define SGX_XW_FORM_REF_HALF 5
+#define SGX_XW_FORM_KIND_MASK 15
+#define SGX_XW_FORM_A_SHIFT 4
+#define SGX_XW_FORM_A_MASK 63
+#define SGX_XW_FORM_B_SHIFT 10
+#define SGX_XW_FORM_B_MASK 63
+#define SGX_XW_FORM_VEC_SHIFT 16
+#define SGX_XW_FORM_WGS_SHIFT 17
+#define SGX_XW_FORM_WGS_MASK 15
+#define SGX_XW_FORM_BLOCKS_SHIFT 21
+#define SGX_XW_FORM_BLOCKS_MASK 2047
+#define SGX_XW_FORM_WAVES_SHIFT 32
+int64_t sgx_xw_dense_form(int dtype, int acc_mode, int n_rows, int M_fea, int P, const void *X, int64_t ldx,
+                          const void *Wt, int64_t ldw, const void *H, int64_t ldh);
+
 /* X.W with CSR X = loop_fea / compute1 in gemm_mode 0 (K.cpp:1960-2078).
  * W_rowmajor is [M_fea][ldw] (use sgx_transpose to get it from B). */
 int sgx_xw_sparse(int dtype, int acc_mode, int spmm_block, int n_rows, int M_fea, int P,

@@ -159,6 +159,18 @@ int sgx_xw_sparse_lds(int dtype, int n_rows, int m_fea, int n_feat, const int32_
 // rows copied from one pitch to another (util_kernels.hip); dst 16-byte aligned with a pitch that is a multiple of 16
 int sgx_repitch_rows(const void *src, int64_t src_pitch, void *dst, int64_t dst_pitch, int row_bytes, int64_t n_rows,
                      hipStream_t stream);
+// The arm a dense X.W call takes (what sgx_xw_dense_form packs, include/sgx.h): filled by the function of each file that
+// its launch reads too.  kind: SGX_XW_FORM_*; a, b: the template arguments; blocks: column blocks or groups; waves: the
+// wavefronts one launch's grid holds (weights-in-LDS: per column block); vec: H stored by vectors.
+struct sgx_xw_form {
+    int kind, a, b, blocks, vec, wgs_per_cu;
+    int64_t waves;
+};
+// the arm of sgx_xw_dense_wlds / _wlds_f32 for these operands; false = not that kernel's shape
+bool sgx_xw_dense_wlds_form(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, const void *H,
+                            int64_t ldh, sgx_xw_form *form);
+bool sgx_xw_dense_wlds_f32_form(int n_rows, int M, int P, const void *Wt, int64_t ldw, const void *H, int64_t ldh, int h_aligned,
+                                sgx_xw_form *form);
 // X.W, fp16, long K, the weight tile resident in LDS (xw_dense_wlds.hip); SGX_ERR_UNSUPPORTED = not its shape
 int sgx_xw_dense_wlds(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H, int64_t ldh,
                       int relu, hipStream_t stream);

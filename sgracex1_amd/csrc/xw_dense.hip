@@ -562,73 +562,97 @@ __global__ __launch_bounds__(kBlock) void xw_dense_lds_f16_kernel(
     }
 }
 
-template <int KS, int NTW>
-int launch_stationary(int n_rows, int M, int P, int nt_total, const void *X, int64_t ldx, const void *Wt, int64_t ldw,
-                      void *H, int64_t ldh, int ha, hipStream_t s, int relu)
+// The grid of the persistent stationary kernels: wgs_per_cu workgroups on each of 256 CUs, trimmed to the work there is,
+// whole column-group sets only, then whole workgroups: the wavefronts the grid HOLDS, of which the kernel makes
+// waves / groups streams (the wavefronts left over return at once).  One function for the plain, the fp32 and the SC
+// launches and for sgx_xw_dense_form.
+int64_t stationary_waves(int64_t n_tiles, int groups, int wgs_per_cu)
 {
-    constexpr int MT = 2;
-    const int groups = (nt_total + NTW - 1) / NTW;
-    const int64_t n_tiles = ((int64_t)n_rows + MT * 16 - 1) / (MT * 16);
-    // persistent grid: 8 workgroups per CU, trimmed to the work there is, whole column-group sets only
-    int64_t waves = (int64_t)256 * 8 * (kBlock / 64);
+    int64_t waves = (int64_t)256 * wgs_per_cu * (kBlock / 64);
     if (waves > n_tiles * groups) waves = n_tiles * groups;
     waves = (waves + groups - 1) / groups * groups;
-    const unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
-    hipLaunchKernelGGL((xw_dense_stationary_f16_kernel<KS, NTW, MT>), dim3(grid), dim3(kBlock), 0, s, n_rows, M, P, groups,
-                       (const f16 *)X, ldx, (const f16 *)Wt, ldw, (f16 *)H, ldh, ha, relu);
+    return (waves + kBlock / 64 - 1) / (kBlock / 64) * (kBlock / 64);
+}
+
+template <int KS, int NTW>
+int launch_stationary(const sgx_xw_form &f, int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw,
+                      void *H, int64_t ldh, hipStream_t s, int relu)
+{
+    constexpr int MT = 2;
+    const unsigned grid = (unsigned)(f.waves / (kBlock / 64));
+    hipLaunchKernelGGL((xw_dense_stationary_f16_kernel<KS, NTW, MT>), dim3(grid), dim3(kBlock), 0, s, n_rows, M, P, f.blocks,
+                       (const f16 *)X, ldx, (const f16 *)Wt, ldw, (f16 *)H, ldh, f.vec, relu);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }
 
-// picks (KS, NTW) for the stationary kernel; SGX_ERR_UNSUPPORTED = use the tiled kernel
-int try_stationary(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H,
-                   int64_t ldh, int ha, hipStream_t s, int relu)
+// picks (KS, NTW), the column groups and the grid of the stationary kernel; false = use the tiled kernel
+bool stationary_arm(int n_rows, int M, const void *H, int64_t ldh, int ha, sgx_xw_form *f)
 {
     // measured (tools/bench_configs.py): 100 -> 256 on 2.4 M rows 1.31 -> 0.66 ms; with K > 128 the W
     // fragments leave room for one column tile only and the re-reads of X cost more than they save
     // (602 -> 128: 0.23 -> 0.38 ms), so longer K stays on the tiled kernel
-    if (M > 128 || n_rows < 8192) return SGX_ERR_UNSUPPORTED;
+    if (M > 128 || n_rows < 8192) return false;
     const int nt_total = (int)((ldh + 15) / 16);               // pad columns P..ldh-1 are produced (as zeros) too
     const int ks = (M + 31) / 32;
-#define SGX_ST(KS_, NTW_) return launch_stationary<KS_, NTW_>(n_rows, M, P, nt_total, X, ldx, Wt, ldw, H, ldh, ha, s, relu)
-    if (ks <= 2) { if (nt_total >= 8) SGX_ST(2, 8); if (nt_total >= 4) SGX_ST(2, 4); if (nt_total >= 2) SGX_ST(2, 2); SGX_ST(2, 1); }
-    if (ks <= 4) { if (nt_total >= 4) SGX_ST(4, 4); if (nt_total >= 2) SGX_ST(4, 2); SGX_ST(4, 1); }
-    SGX_ST(4, 1);
+    int KS, NTW;
+    if (ks <= 2) { KS = 2; NTW = nt_total >= 8 ? 8 : nt_total >= 4 ? 4 : nt_total >= 2 ? 2 : 1; }
+    else { KS = 4; NTW = nt_total >= 4 ? 4 : nt_total >= 2 ? 2 : 1; }
+    const int groups = (nt_total + NTW - 1) / NTW;
+    const int64_t n_tiles = ((int64_t)n_rows + 2 * 16 - 1) / (2 * 16);         // MT = 2
+    // persistent grid: 8 workgroups per CU
+    // (paired tiles leave as 16-byte pieces, a single tile as 8-byte ones; the launch hands the kernel this flag)
+    const int vec = NTW % 2 == 0 ? (ha && ldh % 8 == 0 && (uintptr_t)H % 16 == 0) : ha;
+    *f = sgx_xw_form{SGX_XW_FORM_STATIONARY, KS, NTW, groups, vec, 8, stationary_waves(n_tiles, groups, 8)};
+    return true;
+}
+
+int run_stationary(const sgx_xw_form &f, int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H,
+                   int64_t ldh, hipStream_t s, int relu)
+{
+#define SGX_ST(KS_, NTW_) if (f.a == KS_ && f.b == NTW_) return launch_stationary<KS_, NTW_>(f, n_rows, M, P, X, ldx, Wt, ldw, H, ldh, s, relu)
+    SGX_ST(2, 8); SGX_ST(2, 4); SGX_ST(2, 2); SGX_ST(2, 1);
+    SGX_ST(4, 4); SGX_ST(4, 2); SGX_ST(4, 1);
 #undef SGX_ST
+    return SGX_ERR_UNSUPPORTED;
 }
 
 template <int KB, int NTW>
-int launch_stationary_f32(int n_rows, int M, int P, int nt_total, const void *X, int64_t ldx, const void *Wt, int64_t ldw,
-                          void *H, int64_t ldh, int xa, int wa, int ha, hipStream_t s, sgx_epilogue ep, int relu)
+int launch_stationary_f32(const sgx_xw_form &f, int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw,
+                          void *H, int64_t ldh, int xa, int wa, hipStream_t s, sgx_epilogue ep, int relu)
 {
-    const int groups = (nt_total + NTW - 1) / NTW;
-    const int64_t n_tiles = ((int64_t)n_rows + 15) / 16;
-    // persistent grid: 2 workgroups per CU (some 200 VGPRs per lane), trimmed to the work there is, whole column-group sets only
-    int64_t waves = (int64_t)256 * 2 * (kBlock / 64);
-    if (waves > n_tiles * groups) waves = n_tiles * groups;
-    waves = (waves + groups - 1) / groups * groups;
-    const unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
-    hipLaunchKernelGGL((xw_dense_stationary_f32_kernel<KB, NTW>), dim3(grid), dim3(kBlock), 0, s, n_rows, M, P, groups,
-                       (const float *)X, ldx, (const float *)Wt, ldw, (float *)H, ldh, xa, wa, ha, ep, relu);
+    const unsigned grid = (unsigned)(f.waves / (kBlock / 64));
+    hipLaunchKernelGGL((xw_dense_stationary_f32_kernel<KB, NTW>), dim3(grid), dim3(kBlock), 0, s, n_rows, M, P, f.blocks,
+                       (const float *)X, ldx, (const float *)Wt, ldw, (float *)H, ldh, xa, wa, f.vec, ep, relu);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }
 
-// picks (KB, NTW) for the fp32 stationary kernel; SGX_ERR_UNSUPPORTED = use the tile kernel
-int try_stationary_f32(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H, int64_t ldh,
-                       int xa, int wa, int ha, hipStream_t s, sgx_epilogue ep, int relu)
+// picks (KB, NTW), the column groups and the grid of the fp32 stationary kernel; false = use the tile kernel
+bool stationary_f32_arm(int n_rows, int M, int64_t ldh, int ha, sgx_xw_form *f)
 {
-    if (M > 128 || n_rows < 8192 || sgx_tune().xw_no_stationary_f32) return SGX_ERR_UNSUPPORTED;      // (tuning / test override)
+    if (M > 128 || n_rows < 8192 || sgx_tune().xw_no_stationary_f32) return false;      // (tuning / test override)
     // the workgroup's 4 wavefronts take the column groups of the same row tile when there are 4 of them (X from L1 then)
     const int nt_total = (int)((ldh + 15) / 16);               // pad columns P..ldh-1 are produced (as zeros) too
     const int kb = (M + 15) / 16;
-#define SGX_ST32(KB_, NTW_) return launch_stationary_f32<KB_, NTW_>(n_rows, M, P, nt_total, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu)
-    if (kb <= 2) { if (nt_total >= 4) SGX_ST32(2, 4); if (nt_total >= 2) SGX_ST32(2, 2); SGX_ST32(2, 1); }
-    if (kb <= 4) { if (nt_total >= 4) SGX_ST32(4, 4); if (nt_total >= 2) SGX_ST32(4, 2); SGX_ST32(4, 1); }
-    if (nt_total >= 4) SGX_ST32(8, 4);
-    if (nt_total >= 2) SGX_ST32(8, 2);
-    SGX_ST32(8, 1);
+    const int KB = kb <= 2 ? 2 : kb <= 4 ? 4 : 8;
+    const int NTW = nt_total >= 4 ? 4 : nt_total >= 2 ? 2 : 1;
+    const int groups = (nt_total + NTW - 1) / NTW;
+    const int64_t n_tiles = ((int64_t)n_rows + 15) / 16;
+    // persistent grid: 2 workgroups per CU (some 200 VGPRs per lane)
+    *f = sgx_xw_form{SGX_XW_FORM_STATIONARY, KB, NTW, groups, ha, 2, stationary_waves(n_tiles, groups, 2)};
+    return true;
+}
+
+int run_stationary_f32(const sgx_xw_form &f, int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw,
+                       void *H, int64_t ldh, int xa, int wa, hipStream_t s, sgx_epilogue ep, int relu)
+{
+#define SGX_ST32(KB_, NTW_) if (f.a == KB_ && f.b == NTW_) return launch_stationary_f32<KB_, NTW_>(f, n_rows, M, P, X, ldx, Wt, ldw, H, ldh, xa, wa, s, ep, relu)
+    SGX_ST32(2, 4); SGX_ST32(2, 2); SGX_ST32(2, 1);
+    SGX_ST32(4, 4); SGX_ST32(4, 2); SGX_ST32(4, 1);
+    SGX_ST32(8, 4); SGX_ST32(8, 2); SGX_ST32(8, 1);
 #undef SGX_ST32
+    return SGX_ERR_UNSUPPORTED;
 }
 
 template <int KS, int SC>
@@ -639,22 +663,29 @@ int launch_stationary_scores(int n_rows, int M, int P, const void *X, int64_t ld
     const int nt_total = (int)((ldh + 15) / 16);
     const int groups = (nt_total + NTW - 1) / NTW;
     const int64_t n_tiles = ((int64_t)n_rows + MT * 16 - 1) / (MT * 16);
-    int64_t waves = (int64_t)256 * 8 * (kBlock / 64);
-    if (waves > n_tiles * groups) waves = n_tiles * groups;
-    waves = (waves + groups - 1) / groups * groups;
-    const unsigned grid = (unsigned)((waves + kBlock / 64 - 1) / (kBlock / 64));
+    const int64_t waves = stationary_waves(n_tiles, groups, 8);         // (the grid of the plain (KS, 4) launch at this shape)
+    const unsigned grid = (unsigned)(waves / (kBlock / 64));
     hipLaunchKernelGGL((xw_dense_stationary_f16_kernel<KS, NTW, MT, SC>), dim3(grid), dim3(kBlock), 0, s, n_rows, M, P, groups,
                        (const f16 *)X, ldx, (const f16 *)Wt, ldw, (f16 *)H, ldh, ha, 0, (const f16 *)att, s1, s2, n_heads, P / n_heads);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }
 
+// the tile kernel's workgroups for tiles of MT x 16 rows, one tile per wavefront (launch_tile and sgx_xw_dense_form)
+int64_t tile_grid(int n_rows, int MT)
+{
+    const int64_t rows_per_block = (int64_t)MT * 16 * (kBlock / 64);
+    return (n_rows + rows_per_block - 1) / rows_per_block;
+}
+
+// with rows to spare the tile kernel and the long-K kernels take their tall forms (SGX_XW_SHORT_TILES: tuning override)
+bool dense_tall(int n_rows) { return n_rows >= 32768 && !sgx_tune().xw_short_tiles; }
+
 template <int NT, int MT>
 int launch_tile(int dtype, int n_rows, int M, int P, int p_base, const void *X, int64_t ldx, const void *Wt,
                 int64_t ldw, void *H, int64_t ldh, int xa, int wa, int ha, hipStream_t s, sgx_epilogue ep, int relu)
 {
-    const int64_t rows_per_block = (int64_t)MT * 16 * (kBlock / 64);
-    const unsigned grid = (unsigned)((n_rows + rows_per_block - 1) / rows_per_block);
+    const unsigned grid = (unsigned)tile_grid(n_rows, MT);
     if (dtype == SGX_F16)
         hipLaunchKernelGGL((xw_dense_f16_kernel<NT, MT>), dim3(grid), dim3(kBlock), 0, s, n_rows, M, P, p_base,
                            (const f16 *)X, ldx, (const f16 *)Wt, ldw, (f16 *)H, ldh, xa, wa, ha, relu);
@@ -681,66 +712,138 @@ extern "C" int sgx_xw_dense_act(int dtype, int relu, int n_rows, int M_fea, int 
                            sgx_no_epilogue(), relu ? 1 : 0);
 }
 
-int sgx_xw_dense_ep(int dtype, int acc_mode, int spmm_block, int n_rows, int M_fea, int P, const void *X, int64_t ldx,
-                    const void *Wt, int64_t ldw, void *H, int64_t ldh, hipStream_t stream, sgx_epilogue ep, int relu)
+namespace {
+
+// what the call is refused for before an arm is chosen (SGX_OK: go on; n_rows == 0 is SGX_OK without a launch)
+int dense_check(int dtype, int acc_mode, int n_rows, int M_fea, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw,
+                const void *H, int64_t ldh, int relu)
 {
-    if (ep.rq_ten_pow != 0.0f && dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;      // the quantised layer is fp32
     if (n_rows < 0 || M_fea < 1 || P < 1 || ldx < M_fea || ldw < M_fea || ldh < P) return SGX_ERR_SHAPE;
     if (n_rows == 0) return SGX_OK;
     if (!X || !Wt || !H) return SGX_ERR_NULL;
     if (dtype != SGX_F16 && dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;
-    hipStream_t s = stream;
     if (relu && acc_mode != SGX_ACC_F32) return SGX_ERR_UNSUPPORTED;                  // ReLU on the stores: fp32-accumulate kernels only
+    if (acc_mode == SGX_ACC_REF_HALF) return dtype == SGX_F16 ? SGX_OK : SGX_ERR_UNSUPPORTED;
+    return acc_mode == SGX_ACC_F32 ? SGX_OK : SGX_ERR_UNSUPPORTED;
+}
+
+struct DenseAlign {
+    int xa, wa, ha;
+};
+
+DenseAlign dense_align(int dtype, const void *X, int64_t ldx, const void *Wt, int64_t ldw, const void *H, int64_t ldh)
+{
+    const size_t es = sgx_elem_size(dtype);
+    DenseAlign al;
+    al.xa = ((uintptr_t)X % 16 == 0) && ((ldx * es) % 16 == 0);
+    al.wa = ((uintptr_t)Wt % 16 == 0) && ((ldw * es) % 16 == 0);
+    al.ha = ((uintptr_t)H % (4 * es) == 0) && ((ldh * es) % (4 * es) == 0);
+    return al;
+}
+
+// the tile kernel's instantiation <NT, MT> for a block of `cols` columns
+void tile_arm(int cols, bool tall, int *NT, int *MT)
+{
+    const int nt = (cols + 15) / 16;
+    // every wavefront re-reads its W fragments from L1/L2 each k-step, so with rows to spare a taller tile halves
+    // those reads per flop (602 -> 128 on 233 K rows: 0.234 -> 0.190 ms fp16, 0.62 -> 0.47 ms fp32)
+    if (nt <= 1)      { *NT = 1;  *MT = 4; }
+    else if (nt <= 2) { *NT = 2;  *MT = 4; }
+    else if (nt <= 4) { *NT = 4;  *MT = 4; }
+    else if (nt <= 8) { *NT = 8;  *MT = tall ? 4 : 2; }
+    else              { *NT = 16; *MT = tall ? 2 : 1; }
+}
+
+// The arm a call takes, decided in ONE place: sgx_xw_dense_ep and sgx_xw_dense_form both read it from here (for operands
+// dense_check lets through with rows to produce and fp32 accumulation).
+sgx_xw_form dense_form(int dtype, int n_rows, int M_fea, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, const void *H,
+                       int64_t ldh)
+{
+    const DenseAlign al = dense_align(dtype, X, ldx, Wt, ldw, H, ldh);
+    sgx_xw_form f{};
+    // (the LDS kernel below loses to the stationary one on short K: 100 -> 256 on 2.4 M rows 0.78 vs 0.52 ms, 64 -> 64 0.29 vs 0.22 ms)
+    if (dtype == SGX_F16) {
+        if (stationary_arm(n_rows, M_fea, H, ldh, al.ha, &f)) return f;
+    } else {
+        if (sgx_xw_dense_wlds_f32_form(n_rows, M_fea, P, Wt, ldw, H, ldh, al.ha, &f)) return f;
+        if (stationary_f32_arm(n_rows, M_fea, ldh, al.ha, &f)) return f;
+    }
+    const bool no_lds = sgx_tune().xw_no_lds;      // tuning override
+    const bool tall = dense_tall(n_rows);
+    if (dtype == SGX_F16 && tall && !no_lds && M_fea > 128) {
+        // all of W^T in LDS, X streamed through a register ring (xw_dense_wlds.hip): 602 -> 128 on 233 K rows
+        if (sgx_xw_dense_wlds_form(n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, &f)) return f;
+        const int64_t row_blocks = ((int64_t)n_rows + kLdsBM - 1) / kLdsBM;
+        const int col_blocks = (int)((ldh + kLdsBN - 1) / kLdsBN);
+        return sgx_xw_form{SGX_XW_FORM_TILE_LDS, kLdsBM / 16, kLdsBN / 16, col_blocks, al.ha, 0, row_blocks * col_blocks * (kBlock / 64)};
+    }
+    // columns are produced in blocks of up to 256 (16 tiles); the pad columns P..ldh-1 belong to the last block
+    const int blocks = (int)((ldh + 255) / 256);
+    int NT, MT;
+    tile_arm((int)(ldh - (int64_t)256 * (blocks - 1)), tall, &NT, &MT);
+    return sgx_xw_form{SGX_XW_FORM_TILE, NT, MT, blocks, al.ha, 0, tile_grid(n_rows, MT) * (kBlock / 64)};
+}
+
+}  // namespace
+
+int sgx_xw_dense_ep(int dtype, int acc_mode, int spmm_block, int n_rows, int M_fea, int P, const void *X, int64_t ldx,
+                    const void *Wt, int64_t ldw, void *H, int64_t ldh, hipStream_t stream, sgx_epilogue ep, int relu)
+{
+    if (ep.rq_ten_pow != 0.0f && dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;      // the quantised layer is fp32
+    const int ok = dense_check(dtype, acc_mode, n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, relu);
+    if (ok != SGX_OK || n_rows == 0) return ok;
+    hipStream_t s = stream;
     if (acc_mode == SGX_ACC_REF_HALF) {
         // the reference's sequential half arithmetic (refhalf.hip)
-        if (dtype != SGX_F16) return SGX_ERR_UNSUPPORTED;
         if (ldh > P) SGX_HIP_CHECK(hipMemsetAsync(H, 0, (size_t)n_rows * ldh * sizeof(f16), s));
         return sgx_refhalf_dense(spmm_block, 1, n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, s);
     }
-    if (acc_mode != SGX_ACC_F32) return SGX_ERR_UNSUPPORTED;
-    const size_t es = sgx_elem_size(dtype);
-    const int xa = ((uintptr_t)X % 16 == 0) && ((ldx * es) % 16 == 0);
-    const int wa = ((uintptr_t)Wt % 16 == 0) && ((ldw * es) % 16 == 0);
-    const int ha = ((uintptr_t)H % (4 * es) == 0) && ((ldh * es) % (4 * es) == 0);
-    // (the LDS kernel below loses to this one on short K: 100 -> 256 on 2.4 M rows 0.78 vs 0.52 ms, 64 -> 64 0.29 vs 0.22 ms)
-    if (dtype == SGX_F16) {
-        const int rc = try_stationary(n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, ha, s, relu);
-        if (rc != SGX_ERR_UNSUPPORTED) return rc;
-    } else {
-        int rc = sgx_xw_dense_wlds_f32(n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, ha, ep, relu, s);
-        if (rc != SGX_ERR_UNSUPPORTED) return rc;
-        rc = try_stationary_f32(n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu);
-        if (rc != SGX_ERR_UNSUPPORTED) return rc;
-    }
-    const bool short_tiles = sgx_tune().xw_short_tiles, no_lds = sgx_tune().xw_no_lds;      // tuning overrides
-    const bool tall = n_rows >= 32768 && !short_tiles;
-    if (dtype == SGX_F16 && tall && !no_lds && M_fea > 128) {
-        // all of W^T in LDS, X streamed through a register ring (xw_dense_wlds.hip): 602 -> 128 on 233 K rows
-        const int rc = sgx_xw_dense_wlds(n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, relu, s);
-        if (rc != SGX_ERR_UNSUPPORTED) return rc;
-        const dim3 grid((unsigned)((n_rows + kLdsBM - 1) / kLdsBM), (unsigned)((ldh + kLdsBN - 1) / kLdsBN));
+    const DenseAlign al = dense_align(dtype, X, ldx, Wt, ldw, H, ldh);
+    const sgx_xw_form f = dense_form(dtype, n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh);
+    const int xa = al.xa, wa = al.wa, ha = f.vec;              // how H is stored: the flag the form reports
+    switch (f.kind) {
+    case SGX_XW_FORM_STATIONARY:
+        return dtype == SGX_F16 ? run_stationary(f, n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, s, relu)
+                                : run_stationary_f32(f, n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, xa, wa, s, ep, relu);
+    case SGX_XW_FORM_WLDS:
+        return dtype == SGX_F16 ? sgx_xw_dense_wlds(n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, relu, s)
+                                : sgx_xw_dense_wlds_f32(n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, ha, ep, relu, s);
+    case SGX_XW_FORM_TILE_LDS: {
+        const dim3 grid((unsigned)(f.waves / (kBlock / 64) / f.blocks), (unsigned)f.blocks);      // row blocks x column blocks
         hipLaunchKernelGGL(xw_dense_lds_f16_kernel, grid, dim3(kBlock), 0, s, n_rows, M_fea, P, (const f16 *)X, ldx,
                            (const f16 *)Wt, ldw, (f16 *)H, ldh, ha, relu);
         SGX_LAUNCH_CHECK();
         return SGX_OK;
     }
-    // columns are produced in blocks of up to 256 (16 tiles); the pad columns P..ldh-1 belong to the last block
+    default: break;
+    }
+    const bool tall = dense_tall(n_rows);
     for (int p_base = 0; p_base < ldh; p_base += 256) {
         const int cols = (int)((ldh - p_base) < 256 ? (ldh - p_base) : 256);
-        const int nt = (cols + 15) / 16;
-        int rc;
-        if (nt <= 1)       rc = launch_tile<1, 4>(dtype, n_rows, M_fea, P, p_base, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu);
-        else if (nt <= 2)  rc = launch_tile<2, 4>(dtype, n_rows, M_fea, P, p_base, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu);
-        else if (nt <= 4)  rc = launch_tile<4, 4>(dtype, n_rows, M_fea, P, p_base, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu);
-        // every wavefront re-reads its W fragments from L1/L2 each k-step, so with rows to spare a taller tile halves
-        // those reads per flop (602 -> 128 on 233 K rows: 0.234 -> 0.190 ms fp16, 0.62 -> 0.47 ms fp32)
-        else if (nt <= 8)  rc = tall ? launch_tile<8, 4>(dtype, n_rows, M_fea, P, p_base, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu)
-                                     : launch_tile<8, 2>(dtype, n_rows, M_fea, P, p_base, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu);
-        else               rc = tall ? launch_tile<16, 2>(dtype, n_rows, M_fea, P, p_base, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu)
-                                     : launch_tile<16, 1>(dtype, n_rows, M_fea, P, p_base, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu);
+        int NT, MT, rc = SGX_ERR_UNSUPPORTED;
+        tile_arm(cols, tall, &NT, &MT);
+#define SGX_TILE(NT_, MT_) if (NT == NT_ && MT == MT_) rc = launch_tile<NT_, MT_>(dtype, n_rows, M_fea, P, p_base, X, ldx, Wt, ldw, H, ldh, xa, wa, ha, s, ep, relu)
+        SGX_TILE(1, 4); SGX_TILE(2, 4); SGX_TILE(4, 4); SGX_TILE(8, 4); SGX_TILE(8, 2); SGX_TILE(16, 2); SGX_TILE(16, 1);
+#undef SGX_TILE
         if (rc != SGX_OK) return rc;
     }
     return SGX_OK;
+}
+
+// Which arm sgx_xw_dense / sgx_xw_dense_act take for these operands (include/sgx.h), from the functions the launch uses.
+extern "C" int64_t sgx_xw_dense_form(int dtype, int acc_mode, int n_rows, int M_fea, int P, const void *X, int64_t ldx, const void *Wt,
+                                     int64_t ldw, const void *H, int64_t ldh)
+{
+    const int ok = dense_check(dtype, acc_mode, n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh, 0);
+    if (ok != SGX_OK) return ok;
+    sgx_xw_form f{};
+    if (n_rows == 0) f.kind = SGX_XW_FORM_NONE;
+    else if (acc_mode == SGX_ACC_REF_HALF) f.kind = SGX_XW_FORM_REF_HALF;
+    else f = dense_form(dtype, n_rows, M_fea, P, X, ldx, Wt, ldw, H, ldh);
+    const int64_t blocks = f.blocks > SGX_XW_FORM_BLOCKS_MASK ? SGX_XW_FORM_BLOCKS_MASK : f.blocks;
+    return (int64_t)f.kind | (int64_t)f.a << SGX_XW_FORM_A_SHIFT | (int64_t)f.b << SGX_XW_FORM_B_SHIFT |
+           (int64_t)(f.vec ? 1 : 0) << SGX_XW_FORM_VEC_SHIFT | (int64_t)f.wgs_per_cu << SGX_XW_FORM_WGS_SHIFT |
+           blocks << SGX_XW_FORM_BLOCKS_SHIFT | f.waves << SGX_XW_FORM_WAVES_SHIFT;
 }
 
 // X.W of a GAT layer with the attention scores formed beside H (see the SC form of the stationary kernel): fp16, K <= 128,

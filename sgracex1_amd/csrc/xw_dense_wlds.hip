@@ -240,12 +240,57 @@ __global__ __launch_bounds__(kWldsThreads) void xw_dense_wlds_f16_kernel(
     }
 }
 
+// The arm a launch takes, decided in ONE place: sgx_xw_dense_wlds below and sgx_xw_dense_wlds_form (what sgx_xw_dense_form
+// reports and the tests assert on) both read it from here.
+struct WldsArm {
+    int nt, n_cb, LP, KS, wgs_per_cu, grid;
+    size_t lds_bytes;
+    int n_streams() const { return grid / 8 / n_cb * 8; }      // as the kernel counts them
+};
+
+bool wlds_arm(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, const void *H, int64_t ldh, WldsArm *arm)
+{
+    if (sgx_tune().xw_no_wlds) return false;                            // tuning override (tools/xw_dense_long_k_probe.py)
+    if (M <= 128 || n_rows < 32768) return false;
+    // X through 32-bit buffer offsets, 4-byte aligned rows (a 16-byte buffer load wants dword alignment)
+    if ((uint64_t)n_rows * (uint64_t)ldx * 2ull >= 0xFFF00000ull || (ldx & 1) || ((uintptr_t)X & 3)) return false;
+    // H in 16-byte pieces through 32-bit buffer offsets
+    if ((uint64_t)n_rows * (uint64_t)ldh * 2ull >= 0xFFF00000ull || (ldh & 7) || ((uintptr_t)H & 15)) return false;
+    if ((uint64_t)P * (uint64_t)ldw * 2ull >= 0xFFF00000ull || (ldw & 1) || ((uintptr_t)Wt & 3)) return false;
+    const int KS = (M + 31) / 32, LP = 32 * KS + 8;
+    const int cols = (int)ldh;                                          // the pad columns P .. ldh - 1 are produced (as zeros) too
+    int nt = 0, n_cb = 0;
+    for (int cand = 2; cand <= 8; cand *= 2) {                          // the narrowest column block that covers all columns ...
+        if ((size_t)16 * cand * LP * 2 > kWldsLds) break;
+        nt = cand;
+        n_cb = (cols + 16 * cand - 1) / (16 * cand);
+        if (n_cb == 1) break;
+    }                                                                   // ... or the widest that fits, X then read once per block
+    if (nt == 0 || n_cb > 2) return false;
+    arm->nt = nt;
+    arm->n_cb = n_cb;
+    arm->LP = LP;
+    arm->KS = KS;
+    arm->lds_bytes = (size_t)16 * nt * LP * 2;
+    int cus = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
+        cus = 256;
+    arm->wgs_per_cu = arm->lds_bytes * 2 <= kWldsLds ? 2 : 1;
+    int grid = cus / 8 * 8 * arm->wgs_per_cu;
+    grid = grid / (8 * n_cb) * (8 * n_cb);
+    const int64_t tiles = ((int64_t)n_rows + 16 * kMT - 1) / (16 * kMT);
+    const int64_t want = ((tiles + kWldsWaves - 1) / kWldsWaves + 7) / 8 * 8 * n_cb;       // no more streams than sets of 8 tiles
+    if (want < grid) grid = (int)want;
+    if (grid < 8 * n_cb) grid = 8 * n_cb;
+    arm->grid = grid;
+    return true;
+}
+
 template <int NT>
-int launch_wlds(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H, int64_t ldh,
-                int relu, int n_cb, int LP, int KS, hipStream_t s)
+int launch_wlds(const WldsArm &arm, int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H,
+                int64_t ldh, int relu, hipStream_t s)
 {
     auto kernel = xw_dense_wlds_f16_kernel<NT>;
-    const size_t lds_bytes = (size_t)16 * NT * LP * 2;
     static bool attr_set = false;                     // per instantiation
     if (!attr_set) {
         if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWldsLds) !=
@@ -253,18 +298,8 @@ int launch_wlds(int n_rows, int M, int P, const void *X, int64_t ldx, const void
             return SGX_ERR_HIP;
         attr_set = true;
     }
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-        cus = 256;
-    const int wgs_per_cu = lds_bytes * 2 <= kWldsLds ? 2 : 1;
-    int grid = cus / 8 * 8 * wgs_per_cu;
-    grid = grid / (8 * n_cb) * (8 * n_cb);
-    const int64_t tiles = ((int64_t)n_rows + 16 * kMT - 1) / (16 * kMT);
-    const int64_t want = ((tiles + kWldsWaves - 1) / kWldsWaves + 7) / 8 * 8 * n_cb;       // no more streams than sets of 8 tiles
-    if (want < grid) grid = (int)want;
-    if (grid < 8 * n_cb) grid = 8 * n_cb;
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kWldsThreads), lds_bytes, s, n_rows, M, P, (const f16 *)X, ldx, (const f16 *)Wt, ldw,
-                       (f16 *)H, ldh, relu, n_cb, LP, KS);
+    hipLaunchKernelGGL(kernel, dim3(arm.grid), dim3(kWldsThreads), arm.lds_bytes, s, n_rows, M, P, (const f16 *)X, ldx, (const f16 *)Wt,
+                       ldw, (f16 *)H, ldh, relu, arm.n_cb, arm.LP, arm.KS);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }
@@ -275,28 +310,22 @@ int launch_wlds(int n_rows, int M, int P, const void *X, int64_t ldx, const void
 int sgx_xw_dense_wlds(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H, int64_t ldh,
                       int relu, hipStream_t stream)
 {
-    if (sgx_tune().xw_no_wlds) return SGX_ERR_UNSUPPORTED;             // tuning override (tools/xw_dense_long_k_probe.py)
-    if (M <= 128 || n_rows < 32768) return SGX_ERR_UNSUPPORTED;
-    // X through 32-bit buffer offsets, 4-byte aligned rows (a 16-byte buffer load wants dword alignment)
-    if ((uint64_t)n_rows * (uint64_t)ldx * 2ull >= 0xFFF00000ull || (ldx & 1) || ((uintptr_t)X & 3)) return SGX_ERR_UNSUPPORTED;
-    // H in 16-byte pieces through 32-bit buffer offsets
-    if ((uint64_t)n_rows * (uint64_t)ldh * 2ull >= 0xFFF00000ull || (ldh & 7) || ((uintptr_t)H & 15)) return SGX_ERR_UNSUPPORTED;
-    if ((uint64_t)P * (uint64_t)ldw * 2ull >= 0xFFF00000ull || (ldw & 1) || ((uintptr_t)Wt & 3)) return SGX_ERR_UNSUPPORTED;
-    const int KS = (M + 31) / 32, LP = 32 * KS + 8;
-    const int cols = (int)ldh;                                          // the pad columns P .. ldh - 1 are produced (as zeros) too
-    int nt = 0, n_cb = 0;
-    for (int cand = 2; cand <= 8; cand *= 2) {                          // the narrowest column block that covers all columns ...
-        if ((size_t)16 * cand * LP * 2 > kWldsLds) break;
-        nt = cand;
-        n_cb = (cols + 16 * cand - 1) / (16 * cand);
-        if (n_cb == 1) break;
-    }                                                                   // ... or the widest that fits, X then read once per block
-    if (nt == 0 || n_cb > 2) return SGX_ERR_UNSUPPORTED;
-    switch (nt) {
-    case 2: return launch_wlds<2>(n_rows, M, P, X, ldx, Wt, ldw, H, ldh, relu, n_cb, LP, KS, stream);
-    case 4: return launch_wlds<4>(n_rows, M, P, X, ldx, Wt, ldw, H, ldh, relu, n_cb, LP, KS, stream);
-    default: return launch_wlds<8>(n_rows, M, P, X, ldx, Wt, ldw, H, ldh, relu, n_cb, LP, KS, stream);
+    WldsArm arm;
+    if (!wlds_arm(n_rows, M, P, X, ldx, Wt, ldw, H, ldh, &arm)) return SGX_ERR_UNSUPPORTED;
+    switch (arm.nt) {
+    case 2: return launch_wlds<2>(arm, n_rows, M, P, X, ldx, Wt, ldw, H, ldh, relu, stream);
+    case 4: return launch_wlds<4>(arm, n_rows, M, P, X, ldx, Wt, ldw, H, ldh, relu, stream);
+    default: return launch_wlds<8>(arm, n_rows, M, P, X, ldx, Wt, ldw, H, ldh, relu, stream);
     }
+}
+
+bool sgx_xw_dense_wlds_form(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, const void *H,
+                            int64_t ldh, sgx_xw_form *form)
+{
+    WldsArm arm;
+    if (!wlds_arm(n_rows, M, P, X, ldx, Wt, ldw, H, ldh, &arm)) return false;
+    *form = sgx_xw_form{SGX_XW_FORM_WLDS, arm.nt, arm.n_cb, arm.n_cb, 1, arm.wgs_per_cu, (int64_t)arm.n_streams() * kWldsWaves};
+    return true;
 }
 
 // ---------------------------------------------------------------------------------------
@@ -425,9 +454,39 @@ __global__ __launch_bounds__(kW32Threads) void xw_dense_wlds_f32_kernel(
     }
 }
 
+// The arm of the fp32 launches, decided in ONE place (as WldsArm above): the blocks of 256 columns, the k blocks the
+// instantiation holds, and the grid every block's launch gets.
+struct Wlds32Arm {
+    int kb, blocks, grid;
+};
+
+inline int wlds_f32_nt(int n_out) { return n_out <= 128 ? 8 : 16; }       // column tiles of a block's instantiation
+
+bool wlds_f32_arm(int n_rows, int M, int P, const void *Wt, int64_t ldw, int64_t ldh, Wlds32Arm *arm)
+{
+    if (sgx_tune().xw_no_wlds) return false;                            // tuning / test override
+    const int cols = (int)ldh;                                          // pad columns are produced (as zeros) too
+    // wide outputs only: with few column tiles the register-stationary kernel reads X once as well; more than 256 columns
+    // go in blocks of 256 (X re-read per block: 602 columns of the backward's g . W^T = 3 passes instead of the 10 of the
+    // register-stationary kernel's column groups)
+    if (M > 128 || M <= 32 || cols <= 64 || cols > 1024 || n_rows < 32768) return false;
+    if ((uint64_t)P * (uint64_t)ldw * 4ull >= 0xFFF00000ull || (ldw & 3) || ((uintptr_t)Wt & 15)) return false;
+    arm->kb = (M + 15) / 16 <= 4 ? 4 : 8;
+    arm->blocks = (cols + 255) / 256;
+    int cus = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
+        cus = 256;
+    const int64_t tiles = ((int64_t)n_rows + 15) / 16;
+    int64_t grid = cus;                               // one workgroup per CU (the table takes most of its LDS)
+    const int64_t want = (tiles + kW32Threads / 64 - 1) / (kW32Threads / 64);
+    if (want < grid) grid = want;
+    arm->grid = (int)grid;
+    return true;
+}
+
 template <int KB, int NT>
-int launch_wlds_f32(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H, int64_t ldh, int n_out,
-                    int ha, sgx_epilogue ep, int relu, hipStream_t s)
+int launch_wlds_f32(const Wlds32Arm &arm, int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H,
+                    int64_t ldh, int n_out, int ha, sgx_epilogue ep, int relu, hipStream_t s)
 {
     auto kernel = xw_dense_wlds_f32_kernel<KB, NT>;
     const size_t lds_bytes = (size_t)16 * NT * (16 * KB + 4) * 4;
@@ -438,14 +497,7 @@ int launch_wlds_f32(int n_rows, int M, int P, const void *X, int64_t ldx, const 
             return SGX_ERR_HIP;
         attr_set = true;
     }
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    const int64_t tiles = ((int64_t)n_rows + 15) / 16;
-    int64_t grid = cus;                               // one workgroup per CU (the table takes most of its LDS)
-    const int64_t want = (tiles + kW32Threads / 64 - 1) / (kW32Threads / 64);
-    if (want < grid) grid = want;
-    hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(kW32Threads), lds_bytes, s, n_rows, M, P, (const float *)X, ldx,
+    hipLaunchKernelGGL(kernel, dim3((unsigned)arm.grid), dim3(kW32Threads), lds_bytes, s, n_rows, M, P, (const float *)X, ldx,
                        (const float *)Wt, ldw, (float *)H, ldh, n_out, ha, ep, relu);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
@@ -457,14 +509,9 @@ int launch_wlds_f32(int n_rows, int M, int P, const void *X, int64_t ldx, const 
 int sgx_xw_dense_wlds_f32(int n_rows, int M, int P, const void *X, int64_t ldx, const void *Wt, int64_t ldw, void *H, int64_t ldh,
                           int h_aligned, sgx_epilogue ep, int relu, hipStream_t stream)
 {
-    if (sgx_tune().xw_no_wlds) return SGX_ERR_UNSUPPORTED;             // tuning / test override
-    const int cols = (int)ldh;                                          // pad columns are produced (as zeros) too
-    // wide outputs only: with few column tiles the register-stationary kernel reads X once as well; more than 256 columns
-    // go in blocks of 256 (X re-read per block: 602 columns of the backward's g . W^T = 3 passes instead of the 10 of the
-    // register-stationary kernel's column groups)
-    if (M > 128 || M <= 32 || cols <= 64 || cols > 1024 || n_rows < 32768) return SGX_ERR_UNSUPPORTED;
-    if ((uint64_t)P * (uint64_t)ldw * 4ull >= 0xFFF00000ull || (ldw & 3) || ((uintptr_t)Wt & 15)) return SGX_ERR_UNSUPPORTED;
-    const int kb = (M + 15) / 16 <= 4 ? 4 : 8;
+    Wlds32Arm arm;
+    if (!wlds_f32_arm(n_rows, M, P, Wt, ldw, ldh, &arm)) return SGX_ERR_UNSUPPORTED;
+    const int cols = (int)ldh;
     for (int c0 = 0; c0 < cols; c0 += 256) {
         const int n_out = cols - c0 < 256 ? cols - c0 : 256;
         const int p_blk = P - c0 < 0 ? 0 : (P - c0 < 256 ? P - c0 : 256);
@@ -473,11 +520,24 @@ int sgx_xw_dense_wlds_f32(int n_rows, int M, int P, const void *X, int64_t ldx, 
         const int ha = h_aligned && ((uintptr_t)h_blk % 16 == 0);
         int rc;
         if (p_blk == 0) w_blk = (const float *)Wt;                      // (only pad columns left: every row of the block reads as zero)
-#define SGX_W32(KB_, NT_) rc = launch_wlds_f32<KB_, NT_>(n_rows, M, p_blk, X, ldx, w_blk, ldw, h_blk, ldh, n_out, ha, ep, relu, stream)
-        if (kb == 4) { if (n_out <= 128) SGX_W32(4, 8); else SGX_W32(4, 16); }
-        else { if (n_out <= 128) SGX_W32(8, 8); else SGX_W32(8, 16); }
+#define SGX_W32(KB_, NT_) rc = launch_wlds_f32<KB_, NT_>(arm, n_rows, M, p_blk, X, ldx, w_blk, ldw, h_blk, ldh, n_out, ha, ep, relu, stream)
+        if (arm.kb == 4) { if (wlds_f32_nt(n_out) == 8) SGX_W32(4, 8); else SGX_W32(4, 16); }
+        else { if (wlds_f32_nt(n_out) == 8) SGX_W32(8, 8); else SGX_W32(8, 16); }
 #undef SGX_W32
         if (rc != SGX_OK) return rc;
     }
     return SGX_OK;
+}
+
+// a = KB, b = NT of the LAST block of 256 columns (the blocks before it are whole: NT = 16)
+bool sgx_xw_dense_wlds_f32_form(int n_rows, int M, int P, const void *Wt, int64_t ldw, const void *H, int64_t ldh, int h_aligned,
+                                sgx_xw_form *form)
+{
+    Wlds32Arm arm;
+    if (!wlds_f32_arm(n_rows, M, P, Wt, ldw, ldh, &arm)) return false;
+    const int last = (int)ldh - 256 * (arm.blocks - 1);
+    // (a block starts 256 floats into a row: as aligned as H itself)
+    *form = sgx_xw_form{SGX_XW_FORM_WLDS, arm.kb, wlds_f32_nt(last), arm.blocks, h_aligned && ((uintptr_t)H % 16 == 0), 1,
+                        (int64_t)arm.grid * (kW32Threads / 64)};
+    return true;
 }

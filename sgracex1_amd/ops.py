@@ -469,18 +469,30 @@ def table_pitch(width, elem_size):
     return pitch // elem_size
 
 
-def xw_dense(X, Wt, ldh=None, acc_mode=SGX_ACC_F32, spmm_block=1, relu=False):
-    """H = X @ Wt.T on the matrix cores (sgx_xw_dense).  Wt = weights transposed, [P, M].
-    relu: the activation on the stores (sgx_xw_dense_act; the second stage of the aggregate-first order)."""
+def _xw_dense_operands(X, Wt, ldh, out):
     _dev2d(X, "X")
     _dev2d(Wt, "Wt")
-    code = dtype_code(X.dtype)
     if Wt.dtype != X.dtype or X.shape[1] != Wt.shape[1]:
         raise TypeError(f"X [n, M] and Wt [P, M] must share the element type and M (got {X.dtype} {tuple(X.shape)}, "
                         f"{Wt.dtype} {tuple(Wt.shape)})")
-    P, M = Wt.shape
-    ldh = table_pitch(P, X.element_size()) if ldh is None else ldh
-    H = torch.empty((X.shape[0], ldh), dtype=X.dtype, device=X.device)
+    P = Wt.shape[0]
+    if out is not None:
+        _out(out, X.shape[0], P, X.dtype, X.device)
+        if ldh is not None and ldh != out.stride(0):
+            raise ValueError(f"ldh = {ldh} but out has a row stride of {out.stride(0)}")
+        return P, out.stride(0)
+    return P, (table_pitch(P, X.element_size()) if ldh is None else ldh)
+
+
+def xw_dense(X, Wt, ldh=None, acc_mode=SGX_ACC_F32, spmm_block=1, relu=False, out=None):
+    """H = X @ Wt.T on the matrix cores (sgx_xw_dense).  Wt = weights transposed, [P, M].
+    relu: the activation on the stores (sgx_xw_dense_act; the second stage of the aggregate-first order).
+    out: a [n, P] view whose row stride is the pitch ldh of H -- ALL ldh elements of each of its rows are written (the
+    columns P..ldh-1 with zeros), so the view's rows must own them; the result is `out` itself."""
+    P, ldh = _xw_dense_operands(X, Wt, ldh, out)
+    M = Wt.shape[1]
+    code = dtype_code(X.dtype)
+    H = torch.empty((X.shape[0], ldh), dtype=X.dtype, device=X.device) if out is None else out
     if relu:
         if acc_mode != SGX_ACC_F32:
             raise ValueError("the activation rides on the fp32-accumulate kernels only")
@@ -490,6 +502,45 @@ def xw_dense(X, Wt, ldh=None, acc_mode=SGX_ACC_F32, spmm_block=1, relu=False):
     check(lib.sgx_xw_dense(code, acc_mode, spmm_block, X.shape[0], M, P, _ptr(X), X.stride(0), _ptr(Wt), Wt.stride(0),
                            _ptr(H), ldh, _stream()), "sgx_xw_dense")
     return H[:, :P]
+
+
+XW_DENSE_KINDS = ("none", "tile", "stationary", "tile_lds", "wlds", "ref_half")     # SGX_XW_FORM_*
+XwDenseForm = collections.namedtuple("XwDenseForm", "kind a b blocks waves vec wgs_per_cu max_trips")
+
+
+def unpack_xw_dense_form(word, dtype, n_rows):
+    """sgx_xw_dense_form's word (include/sgx.h) as an XwDenseForm.  max_trips: the most units of work -- row tiles of one
+    column group or block -- one wavefront walks: 1 for the tile kernels, the longest stream's row tiles for the persistent
+    grids (tiles of 32 rows in fp16, of 16 in fp32)."""
+    if word < 0:
+        raise _lib.SgxError(int(word), "sgx_xw_dense_form")
+    kind = XW_DENSE_KINDS[word & _lib.SGX_XW_FORM_KIND_MASK]
+    a = word >> _lib.SGX_XW_FORM_A_SHIFT & _lib.SGX_XW_FORM_A_MASK
+    b = word >> _lib.SGX_XW_FORM_B_SHIFT & _lib.SGX_XW_FORM_B_MASK
+    vec = bool(word >> _lib.SGX_XW_FORM_VEC_SHIFT & 1)
+    wgs = word >> _lib.SGX_XW_FORM_WGS_SHIFT & _lib.SGX_XW_FORM_WGS_MASK
+    blocks = word >> _lib.SGX_XW_FORM_BLOCKS_SHIFT & _lib.SGX_XW_FORM_BLOCKS_MASK
+    waves = word >> _lib.SGX_XW_FORM_WAVES_SHIFT
+    tiles = -(-n_rows // (32 if dtype == torch.float16 else 16))
+    if kind == "stationary":
+        trips = -(-tiles // (waves // blocks))
+    elif kind == "wlds":
+        trips = -(-tiles // waves)
+    else:
+        trips = 1 if kind in ("tile", "tile_lds") else 0
+    return XwDenseForm(kind, a, b, blocks, waves, vec, wgs, trips)
+
+
+def xw_dense_form(X, Wt, ldh=None, acc_mode=SGX_ACC_F32, out=None):
+    """Which kernel arm xw_dense(X, Wt, ldh, acc_mode, out=out) takes (sgx_xw_dense_form; no launch): the kind, its template
+    arguments a, b, the column blocks or groups, the wavefronts of the grid, whether H leaves in vector stores, the
+    workgroups per CU and max_trips.  Without `out` the result is a fresh allocation: aligned at any pitch."""
+    P, ldh = _xw_dense_operands(X, Wt, ldh, out)
+    h_ptr = ctypes.c_void_p(256) if out is None else _ptr(out)
+    n = X.shape[0]
+    word = lib.sgx_xw_dense_form(dtype_code(X.dtype), acc_mode, n, Wt.shape[1], P, _ptr(X) if n else None, X.stride(0), _ptr(Wt),
+                                 Wt.stride(0), h_ptr if n else None, ldh)
+    return unpack_xw_dense_form(word, X.dtype, n)
 
 
 def transpose(x, ldo=None):

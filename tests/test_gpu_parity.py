@@ -777,8 +777,14 @@ def test_xw_dense_fp32_weights_in_lds(M, P):
     assert not base[ok][:, P:].any()
 
 
+# the cases of the test below whose SC launch walks more than one row tile per wavefront, and their rows: the SC launches
+# take the grid of the plain stationary <4, 4> launch at the same shape (stationary_waves, csrc/xw_dense.hip), whose form
+# ops.xw_dense_form reports -- 2048 streams of 4 column groups walk 2049 row tiles, 1024 streams of 8 groups 1025
+_SCORES_PAST_ONE_TRIP = {(96, 256, 8): 65_536 + 7, (100, 512, 1): 32_768 + 7}
+
+
 @pytest.mark.parametrize("M,P,heads", [(128, 256, 8), (100, 256, 8), (64, 128, 4), (40, 64, 2), (128, 256, 1), (100, 256, 2),
-                                       (64, 128, 1), (33, 64, 1), (128, 512, 1)])
+                                       (64, 128, 1), (33, 64, 1), (128, 512, 1), *_SCORES_PAST_ONE_TRIP])
 @pytest.mark.parametrize("gen_name", ["uniform", "rmat"])
 def test_gat_layer_scores_from_the_product_epilogue(M, P, heads, gen_name):
     """A GAT layer whose heads are 32 columns or whole 64-column groups (one head of 256: the reference's semantics; 8 of
@@ -787,13 +793,16 @@ def test_gat_layer_scores_from_the_product_epilogue(M, P, heads, gen_name):
     pass over H of its own.  Same eight-term chains and the same tree, so the layer equals -- bit for bit -- the same layer
     with SGX_GAT_NO_FUSED_SCORES and the composition xw_dense + gat_aggregate; E and S too."""
     from sgracex1_amd import _lib, graphs, ops
-    n = 24_000 + 7
+    n = _SCORES_PAST_ONE_TRIP.get((M, P, heads), 24_000 + 7)
     A = (graphs.rmat_graph_n if gen_name == "rmat" else graphs.uniform_graph)(n, 400_000, seed=M + P)
     g = torch.Generator(device="cuda")
     g.manual_seed(M * 3 + P)
     X = (torch.rand((n, M), generator=g, device="cuda") - 0.4).half()
     Wt = ((torch.rand((P, M), generator=g, device="cuda") * 2 - 1) / M ** 0.5).half()
     att = ((torch.rand(2 * P, generator=g, device="cuda") * 2 - 1) * 0.3).half()
+    if (M, P, heads) in _SCORES_PAST_ONE_TRIP:
+        form = ops.xw_dense_form(X, Wt)
+        assert form[:3] == ("stationary", 4, 4) and form.blocks == P // 64 and form.max_trips >= 2 and n % 32 != 0, form
     fused, E, S = ops.layer_forward(A, X, Wt, relu=True, gat_attention=att, gat_heads=heads, want_edge_outputs=True)
     with _lib.tuning(SGX_GAT_NO_FUSED_SCORES="1"):
         plain, E0, S0 = ops.layer_forward(A, X, Wt, relu=True, gat_attention=att, gat_heads=heads, want_edge_outputs=True)
