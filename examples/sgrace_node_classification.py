@@ -35,11 +35,18 @@ downloaded by torch_geometric and are not available offline.
 --trainer    on the kernels: the tail of every step -- dropout, the Linear head, the cross entropy over the training rows,
              their gradients and Adam -- as train.NodeTrainer runs it (sgx_node_loss, sgx_adam_step) instead of torch's;
              the plain mini-batch mode hands batch.train_mask over as the mask (no boolean index, no read-back per step),
-             and the final accuracies are counted on the device (NodeTrainer.evaluate)
---replay     with --trainer on the full graph: the whole step captured once (torch.cuda.graph) and replayed every epoch;
+             and the final accuracies are counted on the device (NodeTrainer.evaluate); with --batch-size and
+             --device-batches (unquantised, no --accb) every epoch also ends as the demo's does, with test(loader, split):
+             the nodes outside the training set are split into a validation and a test set, each with a NeighborLoader of
+             its own, a pass over each sums hits and loss on the device (NodeTrainer.evaluate(into=), sgx_node_eval) and
+             both sets' sums are read back in one transfer; test_acc is then the sampled test accuracy -- hits over
+             selected rows -- of the epoch that validated best
+--replay    with --trainer on the full graph: the whole step captured once (torch.cuda.graph) and replayed every epoch;
              with --batch-size, --num-neighbors and --device-batches: the loader pads every full batch to one fixed
              capacity (NeighborLoader(pad=True)) and ONE recorded step -- sample, preparation, layers, loss, backward,
-             Adam -- is replayed for each of them (NodeTrainer.capture_loader); the short last batch runs eager
+             Adam -- is replayed for each of them (NodeTrainer.capture_loader); the short last batch runs eager; the
+             validation and test passes are replayed the same way, ONE recorded evaluation per padded loader
+             (NodeTrainer.capture_eval_loader)
 """
 import argparse
 import os
@@ -108,6 +115,28 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
             ready["pad"] = True
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
                                          shuffle=True, seed=seed, **(ready if device_batches else {}))
+    passes = None
+    if loader is not None and node_trainer is not None and device_batches and qbits == 32 and not accb:
+        # the demo's test(loader, split) every epoch (demo_sgrace.py:509-601), summed on the device: the nodes outside the
+        # training set are split into a validation and a test set with a loader each; an epoch ends with a pass over both
+        # (NodeTrainer.evaluate(into=); with --replay ONE recorded evaluation per loader, NodeTrainer.capture_eval_loader)
+        # and reads both sets' sums back in one transfer
+        from sgracex1_amd.train import EvalSums
+        val, test = test[: n // 5], test[n // 5:]
+        passes = []
+        for nodes in (val, test):
+            ev = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=nodes, shuffle=False,
+                                         seed=seed, prepare="sym_norm2", pad=bool(replay))
+            if replay and nodes.numel() >= batch_size:
+                passes.append((ev, node_trainer.capture_eval_loader(ev)))
+            else:
+                def eager(ev=ev, sums=EvalSums(device)):
+                    sums.zero_()
+                    for b in ev:
+                        node_trainer.evaluate(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size, into=sums)
+                    return sums
+                passes.append((ev, eager))
+    best_val, test_at_best = -1.0, 0.0
     t0 = time.time()
     epoch_loss = []                                         # mean training loss of every epoch, kept on the device
     for epoch in range(epochs):
@@ -153,10 +182,15 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
                 opt.step()
                 total, steps = total + loss.detach(), steps + 1
         epoch_loss.append(total / max(steps, 1))
+        if passes is not None:
+            (m_val, hit_val, _), (m_te, hit_te, _) = EvalSums.read(*[run_pass() for _, run_pass in passes])
+            if hit_val / m_val > best_val:                  # the test accuracy of the epoch that validates best
+                best_val, test_at_best = hit_val / m_val, hit_te / m_te
         if verbose and (epoch + 1) % 20 == 0:
             print(f"epoch {epoch + 1:3d}  loss {float(loss):.4f}", flush=True)
     if loader is not None and replay:
-        loader.status()                                     # what a failed batch would have raised, read back once
+        for ld in [loader] + [ev for ev, _ in passes or []]:
+            ld.status()                                     # what a failed batch would have raised, read back once
     if device.type == "cuda":
         torch.cuda.synchronize()
     elapsed = time.time() - t0
@@ -164,6 +198,8 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
     if node_trainer is not None:
         (m_tr, hit_tr), (m_te, hit_te) = (node_trainer.evaluate(x, edge_index, y, m)[0].tolist() for m in (full_mask, ~full_mask))
         train_acc, test_acc = hit_tr / m_tr, hit_te / m_te
+        if passes is not None:
+            test_acc = test_at_best
     else:
         with torch.no_grad():
             pred = model(x, edge_index).argmax(1)

@@ -1744,6 +1744,51 @@ int sgx_node_batch_pad_capacity(int n_nodes, int64_t nnz, int batch, int n_hops,
                                 const int32_t *fea_row_counts, sgx_node_batch_pad *pad);
 int sgx_node_batch_sample_padded(sgx_node_batch *b, const sgx_node_batch_pad *pad, void *stream);
 
+/* ---- the node evaluation head: hits and the summed loss of a pass over node batches, kept on the device ----------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_node_eval is the evaluation of GAT_PYNQ behind the last layer -- Linear [C][P], arg-max against the label,
+ * CrossEntropyLoss(reduction = sum) over out[mask] / out[:batch_size] -- for one batch of a pass over a loader
+ * (demo_sgrace.py's test(loader, split)).  It is sgx_head_eval for the rows sgx_node_loss selects: it ADDS to accumulators
+ * the caller zeroes once per pass, so batches of unequal size accumulate on the device and a pass is read back once.
+ * H [n_rows][P], W [C][P], bias [C] or NULL fp32, target int64 [n_rows], mask bytes [n_rows] or NULL, all on the device.
+ *   selection  sgx_node_loss's: row i is selected iff i < n_prefix && (mask == NULL || mask[i] != 0); M = their number,
+ *              counted on the device (integers); the host never learns it.  n_prefix > n_rows selects as n_rows does.
+ *   logits     z[i][c] of sgx_node_loss with p_drop = 0, bit for bit (x == H): one fmaf chain from 0 over j ascending from
+ *              0 of W[c][j] * H[i][j], then + bias[c] (0 without a bias).  Not sgx_head_eval's 64-lane form.
+ *   per selected row:  sgx_node_loss's per-row term, bit for bit: m = max_c z_c;  lse = m + logf(sum_c expf(z_c - m)),
+ *              c ascending from 0;  loss_i = lse - z[target_i]
+ *              hit_i: arg-max of z[i] == target_i, sgx_node_loss's arg-max: over c ascending with a strict > from z[0]
+ *              (a NaN z[0] counts as -inf): the lowest index wins a tie, a NaN never wins
+ *              a target outside [0, C): loss_i = 0, no hit, nothing is indexed; the row still counts in totals[0]
+ *   the call adds:  totals[0] += M;  totals[1] += sum_i hit_i   (integers);
+ *              loss_sum[0] += S, a double formed in two levels over blocks of SGX_NODE_LOSS_ROWS consecutive rows:
+ *              s_b = (double)loss_i added from 0.0 over the selected rows i of block b in ascending row order;
+ *              S = s_0 + s_1 + ... added from 0.0 over the blocks b = 0 .. ceil(min(n_prefix, n_rows) / SGX_NODE_LOSS_ROWS)
+ *              - 1 in ascending block order (a block without a selected row adds 0.0); S is added to loss_sum[0] once.
+ *              A full-graph call thus ends in n_rows / SGX_NODE_LOSS_ROWS sequential additions, not n_rows.
+ *   M == 0     nothing is added: the accumulators keep their bits; only `logits` is written.
+ *   unselected rows are never read for a sum (they may hold anything, NaN included); without `logits` a block of
+ *              SGX_NODE_LOSS_ROWS rows without a selected row is not read at all, and an unselected row of another block is
+ *              not read either.  logits, when given, receives z for every i < n_rows, selected or not.
+ * Two launches, as sgx_head_eval: sgx_node_loss's walk without its gradients (W in LDS, a thread per (row, class)), every
+ * block's record (s_b, its selected rows, its hits) to a slot of its own in the workspace, so nothing that is summed
+ * depends on the grid; then one workgroup adds the records in block order and adds to the accumulators.  No atomics: the
+ * same bits on every run, for any grid and on every device.  Capturable: no allocation, no synchronisation.  The
+ * accumulators are read and written by the second launch, on the stream.
+ *
+ * Limits: sgx_node_loss's, P <= 1024, C <= 64, C * P <= 16384; beyond: SGX_ERR_UNSUPPORTED and a workspace size of 0.
+ * Argument errors, returned before anything reaches the device, in this order: n_rows, P or C below 1, n_prefix < 0:
+ * SGX_ERR_SHAPE; H, W, target, totals or loss_sum NULL: SGX_ERR_NULL (bias NULL: no bias; mask NULL: the prefix alone;
+ * logits NULL: not written); over a limit: SGX_ERR_UNSUPPORTED; workspace missing or below
+ * sgx_node_eval_workspace_bytes: SGX_ERR_WORKSPACE; not 256-byte aligned: SGX_ERR_ALIGN. */
+/* 256 + 16 bytes per block of SGX_NODE_LOSS_ROWS rows among the first min(n_prefix, n_rows) (n_prefix < 0 as 0) rounded up
+ * to 256 bytes; 0 for a shape the call refuses */
+size_t sgx_node_eval_workspace_bytes(int64_t n_rows, int64_t n_prefix, int P, int C);
+int sgx_node_eval(int64_t n_rows, int64_t n_prefix, int P, int C, const float *H, const float *W, const float *bias,
+                  const int64_t *target, const uint8_t *mask, int64_t *totals /* [2] */, double *loss_sum /* [1] */,
+                  float *logits /* or NULL */, void *workspace, size_t workspace_bytes, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2583,3 +2583,34 @@ def head_eval(pooled, weight, bias, target, n_real=None, totals=None, loss_sum=N
           "sgx_head_eval")
     return (totals, loss_sum, logits) if want_logits else (totals, loss_sum)
 
+
+# ---- the tail of an evaluation pass over node batches: the same sums over selected rows (sgx_node_eval) ---------------------
+def node_eval(H, weight, bias, target, totals, loss_sum, mask=None, n_prefix=None, want_logits=False):
+    """The Linear head, the arg-max's hits and the summed cross entropy of the SELECTED rows of H, ADDED to accumulators
+    that stay on the device, in one call (sgx_node_eval; the rule is in include/sgx.h, "the node evaluation head").
+    H [n, P] fp32, weight [C, P] fp32, bias [C] fp32 or None, target [n] int64; row i is selected iff i < n_prefix (default
+    n) and mask[i] (a bool or uint8 tensor [n], passed as its bytes; None: every row), node_loss's selection; the logits
+    are node_loss's at p = 0 bit for bit.  totals: a device int64 [2] that receives += (selected rows, hits); loss_sum: a
+    device float64 [1] that receives += the rows' losses (train.EvalSums holds such a pair).  Returns (totals, loss_sum),
+    and the logits [n, C] of every row behind them with want_logits.  Never synchronises."""
+    H, w, b = _loss_operands("node_eval", "H", H, weight, bias, target, None)
+    (n, P), C = H.shape, w.shape[0]
+    if mask is not None:
+        _dev(mask, "mask")
+        if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != (n,):
+            raise TypeError("mask must be a bool or uint8 tensor [n]")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+    n_prefix = n if n_prefix is None else int(n_prefix)
+    if n_prefix < 0:
+        raise ValueError(f"node_eval: n_prefix = {n_prefix} is negative")
+    _dev(totals, "totals"), _dev(loss_sum, "loss_sum")
+    if totals.dtype != torch.int64 or totals.numel() != 2 or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise TypeError("node_eval accumulates into totals int64 [2] and loss_sum float64 [1]")
+    logits = torch.empty((n, C), dtype=torch.float32, device=H.device) if want_logits else None
+    nbytes = lib.sgx_node_eval_workspace_bytes(n, n_prefix, P, C)
+    ws = _workspace(H.device, nbytes) if nbytes else None
+    check(lib.sgx_node_eval(n, n_prefix, P, C, _ptr(H), _ptr(w), _ptr(b), _ptr(target), _ptr(mask), _ptr(totals), _ptr(loss_sum),
+                            _ptr(logits), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+          "sgx_node_eval")
+    return (totals, loss_sum, logits) if want_logits else (totals, loss_sum)

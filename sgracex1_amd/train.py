@@ -9,6 +9,8 @@ can be captured once (torch.cuda.graph) and replayed: the regime of the notebook
 NodeTrainer is the same for node classification (sgrace.GAT_PYNQ): the model's two layers through their own autograd,
 ops.NodeLoss (the tail over the selected rows, the count of which never leaves the device) and ops.adam_step.
 """
+import contextlib
+
 import numpy as np
 import torch
 import torch.nn.functional as F
@@ -82,6 +84,33 @@ class _Trainer:
 
         replay.graph = graph
         return replay
+
+    @contextlib.contextmanager
+    def _eval_mode(self):
+        """Around one batch of an evaluation: the model in eval mode with gradients off; its mode is put back."""
+        model = self.model
+        was_training = model.training
+        model.eval()
+        try:
+            with torch.no_grad():
+                yield model
+        finally:
+            model.train(was_training)
+
+    @staticmethod
+    def _eval_pass(sums, walk, one, result, **attrs):
+        """What the two capture_eval_loader return: the callable of a whole pass over the loader behind `walk` (the trainer's
+        _capture_padded made it) -- the EvalSums `sums` zeroed (one launch), every padded batch replayed, every batch that
+        arrives unpadded run through one(batch) into the same sums -> `result`.  It carries sums and attrs as attributes."""
+        def run_pass():
+            sums.zero_()
+            walk(lambda _: None, one)
+            return result
+
+        run_pass.sums = sums
+        for name, value in attrs.items():
+            setattr(run_pass, name, value)
+        return run_pass
 
 
 class StackTrainer(_Trainer):
@@ -283,29 +312,23 @@ class StackTrainer(_Trainer):
         (model.layers_pooled) with the same tail, as in step(); a padded batch is refused there with step()'s
         RuntimeError, and so is a batch whose `batch` vector is not sorted (its pooling exists only inside the model's
         forward)."""
-        model = self.model
-        was_training = model.training
-        model.eval()
-        try:
-            with torch.no_grad():
-                pooled = model.eval_pooled(x, edge_index, batch)
-                if pooled is None:
-                    if self._is_padded(batch):
-                        raise RuntimeError(f"StackTrainer.evaluate: the fused route declined a padded batch: "
-                                           f"{self._declined(batch, training=False)}")
-                    pooled = model.layers_pooled(x, edge_index, batch)
-                if pooled is None:
-                    raise RuntimeError("StackTrainer.evaluate: `batch` is not sorted (or the kernels are off): the model pools "
-                                       "inside its own forward")
-                if into is None:
-                    into = EvalSums(pooled.device)
-                pooled = pooled.float().contiguous()
-                if n_real is not None and y.shape[0] == n_real < pooled.shape[0]:
-                    pooled = pooled[:n_real]           # the labels of the real graphs only
-                ops.head_eval(pooled, model.lin.weight, model.lin.bias, y, n_real=n_real, totals=into.totals,
-                              loss_sum=into.loss_sum)
-        finally:
-            model.train(was_training)
+        with self._eval_mode() as model:
+            pooled = model.eval_pooled(x, edge_index, batch)
+            if pooled is None:
+                if self._is_padded(batch):
+                    raise RuntimeError(f"StackTrainer.evaluate: the fused route declined a padded batch: "
+                                       f"{self._declined(batch, training=False)}")
+                pooled = model.layers_pooled(x, edge_index, batch)
+            if pooled is None:
+                raise RuntimeError("StackTrainer.evaluate: `batch` is not sorted (or the kernels are off): the model pools "
+                                   "inside its own forward")
+            if into is None:
+                into = EvalSums(pooled.device)
+            pooled = pooled.float().contiguous()
+            if n_real is not None and y.shape[0] == n_real < pooled.shape[0]:
+                pooled = pooled[:n_real]               # the labels of the real graphs only
+            ops.head_eval(pooled, model.lin.weight, model.lin.bias, y, n_real=n_real, totals=into.totals,
+                          loss_sum=into.loss_sum)
         return into.totals, into.loss_sum
 
     def capture_eval_loader(self, loader, warmup=2):
@@ -331,14 +354,7 @@ class StackTrainer(_Trainer):
             return self.evaluate(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs, into=sums)
 
         replay, c, walk = self._capture_padded(loader, warmup, "capture_eval_loader", accepts, one)
-
-        def run_pass():
-            sums.zero_()
-            walk(lambda _: None, one)
-            return sums.totals, sums.loss_sum
-
-        run_pass.graph, run_pass.collated, run_pass.sums = replay.graph, c, sums
-        return run_pass
+        return self._eval_pass(sums, walk, one, (sums.totals, sums.loss_sum), graph=replay.graph, collated=c)
 
 
 class EvalSums:
@@ -368,6 +384,10 @@ class NodeTrainer(_Trainer):
         loss = trainer.step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size)      # a seeds-first mini-batch
         counts, loss = trainer.evaluate(x, edge_index, y, test_mask)      # device int64 [selected, hits], device loss [1]
         replay = trainer.capture(x, edge_index, y, train_mask)            # the full-graph step, recorded once
+        epoch = trainer.capture_loader(loader)                            # a NeighborLoader(pad=True): one recorded step for every full batch
+        sums = trainer.evaluate(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size, into=sums)      # ADDS the batch to an EvalSums
+        test = trainer.capture_eval_loader(test_loader)                   # a NeighborLoader(pad=True): one recorded evaluation
+        (rows, hits, loss_sum), = EvalSums.read(test())                   # one pass over the loader's nodes, one read-back
 
     A step is model.features -> ops.NodeLoss on the device counter `t` -> loss.backward() through the layers' own autograd
     -> one ops.adam_step over every parameter that received a gradient (the layers' never-used `bias` parameters receive
@@ -390,19 +410,20 @@ class NodeTrainer(_Trainer):
         self._adam([p.grad for p in self.params])
         return loss.detach().reshape(1)
 
-    def evaluate(self, x, edge_index, y, mask=None, n_prefix=None):
+    def evaluate(self, x, edge_index, y, mask=None, n_prefix=None, into=None):
         """(counts, loss) of the selected rows in eval mode without dropout: counts = device int64 [selected rows, rows
-        whose arg-max class is the target].  No logits leave the device; the model's mode is put back."""
-        model = self.model
-        was_training = model.training
-        model.eval()
-        try:
-            with torch.no_grad():
-                H = model.features(x, edge_index).contiguous()
-                loss, _, _, _, counts = ops.node_loss(H, model.lin.weight, model.lin.bias, y, mask=mask, n_prefix=n_prefix, p=0.0,
-                                                      want_counts=True, grads=False)
-        finally:
-            model.train(was_training)
+        whose arg-max class is the target], loss their mean.  No logits leave the device; the model's mode is put back.
+
+        into: an EvalSums to ADD this batch to, for a pass over a loader -- the same features, then ops.node_eval in place
+        of ops.node_loss: totals += (selected rows, hits), the hits that `counts` holds without it, and loss_sum += the
+        rows' summed loss in double.  Returns `into`.  Nothing synchronises, and no parameter, moment or `t` is touched."""
+        with self._eval_mode() as model:
+            H = model.features(x, edge_index).contiguous()
+            if into is not None:
+                ops.node_eval(H, model.lin.weight, model.lin.bias, y, into.totals, into.loss_sum, mask=mask, n_prefix=n_prefix)
+                return into
+            loss, _, _, _, counts = ops.node_loss(H, model.lin.weight, model.lin.bias, y, mask=mask, n_prefix=n_prefix, p=0.0,
+                                                  want_counts=True, grads=False)
         return counts, loss
 
     def _configuration(self):
@@ -457,35 +478,73 @@ class NodeTrainer(_Trainer):
         loader's first batch_size input nodes on a copy of the state; the last of them runs under
         torch.cuda.set_sync_debug_mode("error"), and a configuration whose layer path synchronises raises capture()'s
         RuntimeError instead of being recorded.  loader.status() tells, once per epoch or run, whether a batch failed."""
-        from . import config
-        if not getattr(loader, "pad", False) or not hasattr(loader, "padded_batch"):
-            raise ValueError("capture_loader takes a NeighborLoader(pad=True)")
-        if int(config.compute_attention) and not loader.transposed:
-            raise ValueError("capture_loader: with config.compute_attention the loader needs transposed=True (the backward "
-                             "would otherwise build the transposed pattern with a sort, per batch)")
-        if loader.y is None:
-            raise ValueError("capture_loader: the loader's data carries no labels")
-        B = loader.capacity.batch_size
-        if loader.input_nodes.numel() < B:
-            raise RuntimeError("capture_loader: the loader has no full batch to record a step on")
-        loader.load(loader.input_nodes[:B], 0)
-
-        def run():
-            b = loader.padded_batch()
-            return self.step(b.x, b.edge_index_agg, b.y, n_prefix=B)
-
-        replay = self._capture((), warmup, self._sync_probe("capture_loader", run), run=run)
+        one = lambda b: self.step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size)
+        replay, walk = self._capture_padded(loader, warmup, "capture_loader", "a step", one, backward=True)
 
         def epoch():
             losses = []
-            for seeds, input_id, step in loader.epoch_batches():
-                if loader.padded(seeds):
-                    loader.load(seeds, step)
-                    losses.append(replay().clone())
-                else:
-                    b = loader._batch(seeds, input_id, step)
-                    losses.append(self.step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size))
+            walk(lambda loss: losses.append(loss.clone()), lambda b: losses.append(one(b)))
             return losses
 
         epoch.graph, epoch.replay = replay.graph, replay
         return epoch
+
+    def _capture_padded(self, loader, warmup, name, what, run_batch, backward=False):
+        """What capture_loader and capture_eval_loader share: ONE recording of run_batch(b) on the padded batch b of
+        `loader` (a pyg_lite.NeighborLoader(pad=True) with labels; anything else: ValueError) behind its sample and
+        preparation (loader.padded_batch()) -> (replay, walk).  The warm-up runs on the loader's first batch_size input
+        nodes, the last of them through _sync_probe.  backward: what is recorded runs the layers' backward, which with
+        config.compute_attention needs a transposed=True loader.  walk(replayed, eager) takes one pass over the loader as
+        iterating it would (loader.epoch_batches()): per full batch the seeds and the step word are copied into the
+        loader's fixed buffers (loader.load), the recording is replayed and replayed(what run_batch returned) called; the
+        short last batch is drawn unpadded and handed to eager(batch) in its place."""
+        from . import config
+        if not getattr(loader, "pad", False) or not hasattr(loader, "padded_batch"):
+            raise ValueError(f"{name} takes a NeighborLoader(pad=True)")
+        if backward and int(config.compute_attention) and not loader.transposed:
+            raise ValueError(f"{name}: with config.compute_attention the loader needs transposed=True (the backward "
+                             "would otherwise build the transposed pattern with a sort, per batch)")
+        if loader.y is None:
+            raise ValueError(f"{name}: the loader's data carries no labels")
+        B = loader.capacity.batch_size
+        if loader.input_nodes.numel() < B:
+            raise RuntimeError(f"{name}: the loader has no full batch to record {what} on")
+        loader.load(loader.input_nodes[:B], 0)
+        run = lambda: run_batch(loader.padded_batch())
+        replay = self._capture((), warmup, self._sync_probe(name, run), run=run)
+
+        def walk(replayed, eager):
+            for seeds, input_id, step in loader.epoch_batches():
+                if loader.padded(seeds):
+                    loader.load(seeds, step)
+                    replayed(replay())
+                else:
+                    eager(loader._batch(seeds, input_id, step))
+
+        return replay, walk
+
+    def capture_eval_loader(self, loader, warmup=2):
+        """ONE recorded evaluation for every full batch of `loader` (a pyg_lite.NeighborLoader(pad=True), shuffled or not;
+        anything else, or a loader without labels: ValueError) -> a callable that runs a whole pass over the loader's input
+        nodes and returns its EvalSums (pass.sums: the selected rows, the hits and the summed loss, on the device).
+
+        The recording is the padded sample and its preparation (loader.padded_batch(), into the loader's one set of
+        buffers), model.features in eval mode and ops.node_eval with n_prefix = batch_size, adding into one EvalSums -- one
+        stream, no parallel branches: capture_loader's machinery (_capture_padded) around evaluate(into=) in place of
+        step().  A pass zeroes the sums (one launch), draws its batches as iterating the loader would, per full batch copies
+        the seeds and the step word into the loader's fixed buffers and replays, and runs the short last batch through
+        evaluate(into=) unpadded: every input node is counted exactly once, and the pass equals
+        `for b in loader: evaluate(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size, into=sums)` bit for bit.  Nothing
+        synchronises: EvalSums.read(pass(), ...) reads one or several passes back in one copy; the sums are the pass's
+        own, overwritten by the next pass.  Parameters, moments and `t` are untouched and the model's mode is put back.
+        The forward reads no transposed pattern, so transposed=True is not needed.  The last warm-up evaluation runs under
+        torch.cuda.set_sync_debug_mode("error"): a configuration whose layer path synchronises raises capture()'s
+        RuntimeError instead of being recorded.  A loader shared with capture_loader shares its buffers: a padded batch
+        is valid until the next one is drawn, so passes and training epochs run one after the other, never interleaved
+        batch by batch on one loader.  loader.status() tells, once per epoch or run, whether a batch failed."""
+        def one(b):
+            return self.evaluate(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size, into=sums)
+
+        sums = EvalSums(self.t.device)
+        replay, walk = self._capture_padded(loader, warmup, "capture_eval_loader", "an evaluation", one)
+        return self._eval_pass(sums, walk, one, sums, graph=replay.graph, replay=replay)
