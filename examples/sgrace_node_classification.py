@@ -36,7 +36,8 @@ downloaded by torch_geometric and are not available offline.
              their gradients and Adam -- as train.NodeTrainer runs it (sgx_node_loss, sgx_adam_step) instead of torch's;
              the plain mini-batch mode hands batch.train_mask over as the mask (no boolean index, no read-back per step),
              and the final accuracies are counted on the device (NodeTrainer.evaluate); with --batch-size and
-             --device-batches (unquantised, no --accb) every epoch also ends as the demo's does, with test(loader, split):
+             --device-batches (no --accb; with --qbits the loaders carry the quantised adjacency too) every epoch also
+             ends as the demo's does, with test(loader, split):
              the nodes outside the training set are split into a validation and a test set, each with a NeighborLoader of
              its own, a pass over each sums hits and loss on the device (NodeTrainer.evaluate(into=), sgx_node_eval) and
              both sets' sums are read back in one transfer; test_acc is then the sampled test accuracy -- hits over
@@ -46,7 +47,9 @@ downloaded by torch_geometric and are not available offline.
              capacity (NeighborLoader(pad=True)) and ONE recorded step -- sample, preparation, layers, loss, backward,
              Adam -- is replayed for each of them (NodeTrainer.capture_loader); the short last batch runs eager; the
              validation and test passes are replayed the same way, ONE recorded evaluation per padded loader
-             (NodeTrainer.capture_eval_loader)
+             (NodeTrainer.capture_eval_loader); with --qbits the padded batches carry the quantised adjacency of both
+             layers (NeighborLoader(pad=True, quant=sgrace.quant_constants)) and the recorded step and evaluations are the
+             quantised model's; --accb stays an eager route
 """
 import argparse
 import os
@@ -116,7 +119,7 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
                                          shuffle=True, seed=seed, **(ready if device_batches else {}))
     passes = None
-    if loader is not None and node_trainer is not None and device_batches and qbits == 32 and not accb:
+    if loader is not None and node_trainer is not None and device_batches and not accb:
         # the demo's test(loader, split) every epoch (demo_sgrace.py:509-601), summed on the device: the nodes outside the
         # training set are split into a validation and a test set with a loader each; an epoch ends with a pass over both
         # (NodeTrainer.evaluate(into=); with --replay ONE recorded evaluation per loader, NodeTrainer.capture_eval_loader)
@@ -126,7 +129,7 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         passes = []
         for nodes in (val, test):
             ev = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=nodes, shuffle=False,
-                                         seed=seed, prepare="sym_norm2", pad=bool(replay))
+                                         seed=seed, prepare="sym_norm2", quant=sgrace.quant_constants, pad=bool(replay))
             if replay and nodes.numel() >= batch_size:
                 passes.append((ev, node_trainer.capture_eval_loader(ev)))
             else:
@@ -240,8 +243,8 @@ if __name__ == "__main__":
         ap.error("--trainer runs the tail on the kernels (--acc 1)")
     if a.replay and (not a.trainer or (a.batch_size is not None and not a.device_batches)):
         ap.error("--replay replays the step of --trainer: the full-graph one, or the padded mini-batch one of --device-batches")
-    if a.replay and a.batch_size is not None and (a.qbits != 32 or a.accb):
-        ap.error("--replay on mini-batches covers the unquantised layers with the staged backward (no --qbits, no --accb)")
+    if a.replay and a.batch_size is not None and a.accb:
+        ap.error("--replay on mini-batches covers the layers with the staged backward, quantised or not (no --accb)")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
         num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches,
         accb=int(a.accb), trainer=a.trainer, replay=a.replay)

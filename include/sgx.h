@@ -1724,7 +1724,36 @@ int sgx_head_eval(int n_graphs, int n_real, int P, int C, const float *pooled, c
  * nnz_fea, has_dead_rows and max_row stay as they are.  No allocation, no synchronisation; capturable; the same bits on
  * every run.  With a non-zero status the arrays hold a batch without a live row (n = edges = a = f = 0 in counts:
  * filler rows only), so whatever runs behind the call reads a well-formed batch; nothing is written outside
- * [0, capacity) of any array.  The quantised variant is not built.
+ * [0, capacity) of any array.
+ *
+ * sgx_node_batch_sample_padded_quant(b, pad, q, stream): the padded batch ready for the QUANTISED layers.  It is
+ * sgx_node_batch_sample_padded(b, pad) -- the same launches, the same bits in every array that call writes, the same
+ * status, counts and step word -- and for each constant set k < q->n_sets (sgx_node_batch_quant above) it also writes, with
+ * fq_k the unsigned-grid device function sgx_fake_quantize(0, qbits, inv_scale_adj[k], zero_adj[k]) runs
+ * (csrc/quant_device.h, the one quantiser):
+ *   values_q[k][e]    = fq_k(values_norm[e]) for every e < C_a, the whole capacity: the live prefix holds the bits
+ *                       sgx_node_batch_sample_quant writes for the same draw; a filler row holds fq_k(1) on its first entry
+ *                       and fq_k(0) on its dealt spare entries, formed in the pad launch by the same device function;
+ *   dead_row_q[k][r]  = row r holds no values_q[k] > 0, for every r < N;
+ *   values_lean[k][e] (optional, NULL = not written) = values_norm[e] on the rows with dead_row_q[k], values_q[k][e]
+ *                       elsewhere, for every e < C_a.
+ * values_q / values_lean hold C_a floats, dead_row_q N bytes.  q is const: has_dead_rows_q is NOT written, the call reads
+ * nothing back (a caller takes "some row may be dead" as a constant fact with the exact mask, as for dead_row).
+ * Capturable, no allocation, no synchronisation, the same bits on every run.  With a set status every row is a filler
+ * row in these arrays too.
+ * The call requires, for every k, fq_k(1) > 0 and fq_k(0) == 0, evaluated on the host by the same rule.  Then no filler
+ * row is dead under the quantised mask `values_q > 0` (its first entry is fq_k(1) > 0; its values_lean are its values_q),
+ * and a filler row's spare entries carry no weight in the GCN aggregate (they are 0), so every consequence above holds for
+ * the quantised adjacency as well: a filler row's D is 0 in every layer and it passes nothing on.  Both conditions hold for
+ * the constants the reference publishes for w_qbits = 8, 4, 2, 1: zero_adj = 0 there, and round(inv_scale_adj) is 255, 15,
+ * 30, 10 before the clip to the grid.  A live row may still be dead under the quantised mask alone (an entry may round to
+ * 0); it then takes the inherited uniform softmax over all N columns.
+ * Argument errors of the quantised call, before anything is launched: b, pad or q NULL: SGX_ERR_NULL; then those of
+ * sgx_node_batch_sample_quant's quantiser arguments (b->dtype other than SGX_F32: SGX_ERR_UNSUPPORTED; n_sets outside
+ * {1, 2} or qbits outside {8, 4, 2, 1}: SGX_ERR_SHAPE; values_q[k] or dead_row_q[k] NULL for a k < n_sets: SGX_ERR_NULL);
+ * fq_k(1) <= 0 (or not a number) or fq_k(0) != 0 for some k -- the filler rows would be dead or would carry weight --:
+ * SGX_ERR_UNSUPPORTED; then those of sgx_node_batch_sample_padded.
+ *
  * Argument errors, before anything is launched: those of sgx_node_batch_sample (without its host outputs); b, pad or a
  * pointer of pad NULL: SGX_ERR_NULL; batch == 0, capacities below the rule's (N < mn, E < me, C_a < me + N, C_a - N >
  * 63 (N - mn), C_f > 64 (N - mn)) or over INT32_MAX: SGX_ERR_SHAPE; a fan-out of -1 (an unbounded row):
@@ -1743,6 +1772,8 @@ typedef struct sgx_node_batch_pad {
 int sgx_node_batch_pad_capacity(int n_nodes, int64_t nnz, int batch, int n_hops, const int *fanouts,
                                 const int32_t *fea_row_counts, sgx_node_batch_pad *pad);
 int sgx_node_batch_sample_padded(sgx_node_batch *b, const sgx_node_batch_pad *pad, void *stream);
+int sgx_node_batch_sample_padded_quant(sgx_node_batch *b, const sgx_node_batch_pad *pad, const sgx_node_batch_quant *q,
+                                       void *stream);
 
 /* ---- the node evaluation head: hits and the summed loss of a pass over node batches, kept on the device ----------
  * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.

@@ -14,6 +14,8 @@
 //   11    sgx_node_batch_sample_padded only: the filler rows, the dealt spare entries and the -1 tails behind the
 //         live prefix of every array, up to a fixed capacity (pad_kernel); the counts go to a device array instead
 //         of the read-back, so that call is capturable
+//         sgx_node_batch_sample_padded_quant: pass 6 as sgx_node_batch_sample_quant runs it, and in pass 11 the filler
+//         rows' entries of every constant set's values and lean values, on the grid, and its dead-row mask
 // Kernel boundaries are the only ordering between workgroups.
 #include <algorithm>
 #include <functional>
@@ -318,8 +320,11 @@ __device__ inline void fill_bytes(void *base, int64_t lo_bytes, int64_t hi_bytes
 // edges = a = f = 0: filler rows only), so that whatever reads the buffers next finds a well-formed batch; every range
 // below lies inside its array's capacity whatever the counters hold (the capacities are checked on the host against the
 // bounds the counters cannot pass with a clear status).
-template <class T>
-__global__ __launch_bounds__(kBlock) void pad_kernel(Args a, PadArgs p)
+// NQ > 0 (sgx_node_batch_sample_padded_quant): the same positions of every constant set's arrays as well.  The host has
+// checked that the filler's 1 stays positive and its 0 stays 0 on every set's grid, so no filler row is dead under a
+// quantised mask and its lean values are its quantised ones.
+template <class T, int NQ>
+__global__ __launch_bounds__(kBlock) void pad_kernel(Args a, PadArgs p, QuantSets<NQ> qs)
 {
     const sgx_node_batch &b = a.b;
     const int st = a.ctr.status(), H = a.ctr.H;
@@ -357,10 +362,22 @@ __global__ __launch_bounds__(kBlock) void pad_kernel(Args a, PadArgs p)
         }
         b.columnIndex_norm[na + t] = (int32_t)(n + j);
         val[na + t] = k == 0 ? (T)1.0f : (T)0.0f;
+        if constexpr (NQ > 0) {
+#pragma unroll
+            for (int s = 0; s < NQ; ++s) {
+                const float vq = sgx_quantizer::fake_quantize_value(0, qs.qbits, qs.inv_scale[s], qs.zero[s], k == 0 ? 1.0f : 0.0f);
+                qs.val[s][na + t] = vq;
+                if (qs.lean[s]) qs.lean[s][na + t] = vq;
+            }
+        }
     }
     // constant ranges
     fill_bytes(b.n_id, 4ll * n, 4ll * p.N, 0xff, tid, nth);
     fill_bytes(b.dead_row, n, p.N, 0, tid, nth);
+    if constexpr (NQ > 0) {
+#pragma unroll
+        for (int s = 0; s < NQ; ++s) fill_bytes(qs.dead[s], n, p.N, 0, tid, nth);
+    }
     fill_bytes(b.y_out, 8ll * n, 8ll * p.N, 0, tid, nth);
 #pragma unroll
     for (int m = 0; m < 3; ++m) fill_bytes(b.mask_out[m], n, p.N, 0, tid, nth);
@@ -428,6 +445,17 @@ int check_batch(const sgx_node_batch *b, Bounds &bd)
     if (!b->workspace || b->workspace_bytes < sgx_node_batch_workspace_bytes(b->n_nodes, b->nnz, b->batch, b->n_hops, b->fanouts,
                                                                              nullptr, nullptr))
         return SGX_ERR_WORKSPACE;
+    return SGX_OK;
+}
+
+// the quantiser arguments sgx_node_batch_sample_quant and the padded quantised call share
+int check_quant(const sgx_node_batch *b, const sgx_node_batch_quant *q)
+{
+    if (b->dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;   // the quantised layer works on fp32
+    if (q->n_sets != 1 && q->n_sets != 2) return SGX_ERR_SHAPE;
+    if (q->qbits != 8 && q->qbits != 4 && q->qbits != 2 && q->qbits != 1) return SGX_ERR_SHAPE;
+    for (int k = 0; k < q->n_sets; ++k)
+        if (!q->values_q[k] || !q->dead_row_q[k]) return SGX_ERR_NULL;
     return SGX_OK;
 }
 
@@ -523,11 +551,8 @@ extern "C" int sgx_node_batch_sample(sgx_node_batch *b, void *stream)
 extern "C" int sgx_node_batch_sample_quant(sgx_node_batch *b, sgx_node_batch_quant *q, void *stream)
 {
     if (!b || !q) return SGX_ERR_NULL;
-    if (b->dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;   // the quantised layer works on fp32
-    if (q->n_sets != 1 && q->n_sets != 2) return SGX_ERR_SHAPE;
-    if (q->qbits != 8 && q->qbits != 4 && q->qbits != 2 && q->qbits != 1) return SGX_ERR_SHAPE;
-    for (int k = 0; k < q->n_sets; ++k)
-        if (!q->values_q[k] || !q->dead_row_q[k]) return SGX_ERR_NULL;
+    const int ok = check_quant(b, q);
+    if (ok != SGX_OK) return ok;
     return node_batch_sample(b, q, stream);
 }
 
@@ -575,9 +600,11 @@ extern "C" int sgx_node_batch_pad_capacity(int n_nodes, int64_t nnz, int batch, 
     return SGX_OK;
 }
 
-extern "C" int sgx_node_batch_sample_padded(sgx_node_batch *b, const sgx_node_batch_pad *pad, void *stream)
+namespace {
+
+// sgx_node_batch_sample_padded (q == NULL) and sgx_node_batch_sample_padded_quant on their checked quantiser arguments
+int node_batch_sample_padded(const sgx_node_batch *b, const sgx_node_batch_pad *pad, const sgx_node_batch_quant *q, void *stream)
 {
-    if (!b || !pad) return SGX_ERR_NULL;
     if (!b->fanouts) return SGX_ERR_NULL;
     sgx_node_batch c = *b;                                 // the arguments as the kernels take them; b itself is not written
     Bounds bd;
@@ -593,14 +620,42 @@ extern "C" int sgx_node_batch_sample_padded(sgx_node_batch *b, const sgx_node_ba
     c.max_edges = bd.max_edges;
     hipStream_t s = (hipStream_t)stream;
     Args a;
-    const int st = enqueue_batch(&c, nullptr, bd, pad->step, pad->n_edges, a, s);
+    const int st = enqueue_batch(&c, q, bd, pad->step, pad->n_edges, a, s);
     if (st != SGX_OK) return st;
     const PadArgs pa{pad->n_rows, pad->nnz_norm, c.rowPtr_x ? pad->nnz_fea : 0, pad->n_edges, pad->status, pad->counts};
     const unsigned grid = grid_of(pa.N + pa.Ca + pa.Cf + 2 * pa.E, kBlock * 4, 1024);
-    if (c.dtype == SGX_F16)
-        hipLaunchKernelGGL(pad_kernel<f16>, dim3(grid), dim3(kBlock), 0, s, a, pa);
+    if (q && q->n_sets == 2)
+        hipLaunchKernelGGL((pad_kernel<float, 2>), dim3(grid), dim3(kBlock), 0, s, a, pa, quant_sets<2>(q));
+    else if (q)
+        hipLaunchKernelGGL((pad_kernel<float, 1>), dim3(grid), dim3(kBlock), 0, s, a, pa, quant_sets<1>(q));
+    else if (c.dtype == SGX_F16)
+        hipLaunchKernelGGL((pad_kernel<f16, 0>), dim3(grid), dim3(kBlock), 0, s, a, pa, QuantSets<0>{});
     else
-        hipLaunchKernelGGL(pad_kernel<float>, dim3(grid), dim3(kBlock), 0, s, a, pa);
+        hipLaunchKernelGGL((pad_kernel<float, 0>), dim3(grid), dim3(kBlock), 0, s, a, pa, QuantSets<0>{});
     SGX_LAUNCH_CHECK();
     return SGX_OK;
+}
+
+}  // namespace
+
+extern "C" int sgx_node_batch_sample_padded(sgx_node_batch *b, const sgx_node_batch_pad *pad, void *stream)
+{
+    if (!b || !pad) return SGX_ERR_NULL;
+    return node_batch_sample_padded(b, pad, nullptr, stream);
+}
+
+extern "C" int sgx_node_batch_sample_padded_quant(sgx_node_batch *b, const sgx_node_batch_pad *pad,
+                                                  const sgx_node_batch_quant *q, void *stream)
+{
+    if (!b || !pad || !q) return SGX_ERR_NULL;
+    const int ok = check_quant(b, q);
+    if (ok != SGX_OK) return ok;
+    // the filler rows' 1 and 0 on every set's grid, by the rule the kernels run: a 1 that rounds to 0 would leave the
+    // filler rows dead under the quantised mask, a 0 that does not stay 0 would give their spare entries weight
+    for (int k = 0; k < q->n_sets; ++k) {
+        const float one = sgx_quantizer::fake_quantize_value(0, q->qbits, q->inv_scale_adj[k], q->zero_adj[k], 1.0f);
+        const float zero = sgx_quantizer::fake_quantize_value(0, q->qbits, q->inv_scale_adj[k], q->zero_adj[k], 0.0f);
+        if (!(one > 0.0f) || zero != 0.0f) return SGX_ERR_UNSUPPORTED;
+    }
+    return node_batch_sample_padded(b, pad, q, stream);
 }

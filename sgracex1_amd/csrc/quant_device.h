@@ -1,12 +1,13 @@
 // The fake quantiser of one fp32 value (SG.py:177-265), shared by every kernel that puts values on the w_qbits grid:
 // quant.hip (sgx_fake_quantize) and node_batch.hip (the quantised adjacency of a prepared batch).  One statement of the
-// rounding points, so that every caller gives the same bits.
+// rounding points, so that every caller gives the same bits.  Host code may evaluate it too (node_batch.hip checks the
+// filler entries of a padded quantised batch with it): IEEE fp32, round to nearest even, as on the device.
 #pragma once
 #include <hip/hip_runtime.h>
 
 namespace sgx_quantizer {
 
-__device__ __forceinline__ float clipf(float v, float lo, float hi)
+__host__ __device__ __forceinline__ float clipf(float v, float lo, float hi)
 {
     // torch.clip: min(max(v, lo), hi); NaN propagates
     v = v < lo ? lo : v;
@@ -15,7 +16,7 @@ __device__ __forceinline__ float clipf(float v, float lo, float hi)
 
 // kind 0: quantization_ufbits (SG.py:253-265): unsigned grid 0 .. 2^q - 1
 // kind 1: quantization_fbits  (SG.py:238-251): signed grid -(2^(q-1) - 1) .. 2^(q-1) - 1
-__device__ __forceinline__ float fake_quantize_value(int kind, int qbits, float inv_scale, float zero, float x)
+__host__ __device__ __forceinline__ float fake_quantize_value(int kind, int qbits, float inv_scale, float zero, float x)
 {
 // `1 / s * x + z` is a rounded product followed by a rounded sum in the reference (two torch ops), not one fma -- in
 // whatever kernel this is inlined

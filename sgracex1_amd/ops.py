@@ -1255,9 +1255,11 @@ def node_pad_capacity(csr, batch_size, fanouts, features=None):
 class NodePadBuffers:
     """The output buffers of padded node batches of one capacity, written again by every sample_node_batch(pad=, out=):
     what a recorded step reads at fixed addresses.  Also the sampler's node map (kept at the sentinel between calls), the
-    OR-ed status word and the live counts.  n_id starts at -1, so no gather by it ever leaves its source."""
+    OR-ed status word and the live counts.  n_id starts at -1, so no gather by it ever leaves its source.  n_quant: the
+    number of constant sets of a quantised padded batch (sample_node_batch(pad=, quant=)); `quant` then holds (q_val [C_a]
+    fp32, q_dead [N] bool, q_lean [C_a] fp32) per set."""
 
-    def __init__(self, cap, n_nodes, dtype, device, n_feat=None, y=False, n_masks=0):
+    def __init__(self, cap, n_nodes, dtype, device, n_feat=None, y=False, n_masks=0, n_quant=0):
         N, Ca, Cf, E = cap.n_rows, cap.nnz_norm, cap.nnz_fea, cap.n_edges
         new = lambda k, dt, v=0: torch.full((max(int(k), 1),), v, dtype=dt, device=device)
         self.capacity, self.dtype = cap, dtype
@@ -1274,10 +1276,12 @@ class NodePadBuffers:
         self.node_map = new(n_nodes, torch.int32, SAMPLE_SENTINEL)
         self.status = new(1, torch.int32)
         self.counts = new(4 + 2 * (len(cap.fanouts) + 1), torch.int32)
+        self.quant = [(new(Ca, torch.float32), new(N, torch.bool, False), new(Ca, torch.float32)) for _ in range(int(n_quant))]
 
 
-def _sample_node_batch_padded(csr, seeds, seed, step, fill, dtype, edge_weight, features, y, masks, cap, out):
-    """sample_node_batch(pad=cap): sgx_node_batch_sample_padded into `out` (a NodePadBuffers; None: a fresh one)."""
+def _sample_node_batch_padded(csr, seeds, seed, step, fill, dtype, edge_weight, features, y, masks, cap, out, quant=None):
+    """sample_node_batch(pad=cap): sgx_node_batch_sample_padded -- with quant= sgx_node_batch_sample_padded_quant -- into
+    `out` (a NodePadBuffers; None: a fresh one)."""
     dev, n, B, H = csr.rowptr.device, csr.n_rows, seeds.numel(), len(cap.fanouts)
     if B != cap.batch_size or cap.features != (features is not None):
         raise ValueError("sample_node_batch: pad= is the node_pad_capacity of this batch size, these fan-outs and these features")
@@ -1286,10 +1290,15 @@ def _sample_node_batch_padded(csr, seeds, seed, step, fill, dtype, edge_weight, 
         raise ValueError("sample_node_batch(pad=): step is a device int64 [1] tensor (the word a replay reads)")
     if features is not None and (features.val.dtype != torch.float32 or features.n_rows != n or features._max_row is None):
         raise ValueError("features must be the feature_csr of the graph's x (fp32 values, one row per node)")
+    # one constant set per distinct key of the two layers' constants, as the unpadded call builds them
+    sets = {} if quant is None else {_adj_quant_key(qc): qc for qc in (quant, quant.second_layer())}
     if out is None:
-        out = NodePadBuffers(cap, n, dtype, dev, None if features is None else features.n_cols, y is not None, len(masks))
-    if out.capacity is not cap or out.dtype != dtype or (out.y is None) != (y is None) or len(out.masks) != len(masks):
-        raise ValueError("sample_node_batch: out= was built for another capacity, dtype, label or mask set")
+        out = NodePadBuffers(cap, n, dtype, dev, None if features is None else features.n_cols, y is not None, len(masks),
+                             len(sets))
+    if (out.capacity is not cap or out.dtype != dtype or (out.y is None) != (y is None) or len(out.masks) != len(masks)
+            or len(out.quant) != len(sets)):
+        raise ValueError("sample_node_batch: out= was built for another capacity, dtype, label, mask set or number of "
+                         "quantiser constant sets")
     N, Ca, Cf, E = cap.n_rows, cap.nnz_norm, cap.nnz_fea, cap.n_edges
     fan_c = (ctypes.c_int32 * max(H, 1))(*cap.fanouts)
     ws = _workspace(dev, lib.sgx_node_batch_workspace_bytes(n, csr.nnz, B, H, fan_c, None, None))
@@ -1325,11 +1334,25 @@ def _sample_node_batch_padded(csr, seeds, seed, step, fill, dtype, edge_weight, 
     p = _lib.NodeBatchPad()
     p.n_rows, p.nnz_norm, p.nnz_fea, p.n_edges = N, Ca, Cf, E
     p.step, p.status, p.counts = step.data_ptr(), out.status.data_ptr(), out.counts.data_ptr()
-    check(lib.sgx_node_batch_sample_padded(ctypes.byref(b), ctypes.byref(p), _stream()), "sgx_node_batch_sample_padded")
+    if quant is None:
+        check(lib.sgx_node_batch_sample_padded(ctypes.byref(b), ctypes.byref(p), _stream()), "sgx_node_batch_sample_padded")
+    else:
+        q = _lib.NodeBatchQuant()
+        q.n_sets, q.qbits = len(sets), int(quant.w_qbits)
+        for k, (qc, (q_val, q_dead, q_lean)) in enumerate(zip(sets.values(), out.quant)):
+            q.inv_scale_adj[k], q.zero_adj[k] = float(1 / qc.a_s), float(qc.a_z)
+            q.values_q[k], q.dead_row_q[k], q.values_lean[k] = q_val.data_ptr(), q_dead.data_ptr(), q_lean.data_ptr()
+        check(lib.sgx_node_batch_sample_padded_quant(ctypes.byref(b), ctypes.byref(p), ctypes.byref(q), _stream()),
+              "sgx_node_batch_sample_padded_quant")
     s = PaddedNodeSample(out.n_id[:N], None, out.pos[:E], B, [], [])
     s.buffers, s.counts, s.status = out, out.counts, out.status
     s.out_rowptr, s.out_col = out.rowptr[:N + 1], out.col[:E]
-    s.adj_norm = Csr(out.n_rowptr[:N + 1], out.n_col[:Ca], out.n_val[:Ca], N).with_facts(out.dead[:N], True, cap.max_row)
+    s.adj_norm = A = Csr(out.n_rowptr[:N + 1], out.n_col[:Ca], out.n_val[:Ca], N).with_facts(out.dead[:N], True, cap.max_row)
+    # the quantised adjacencies with the padded batch's constant facts: one kernel path for every batch, nothing read back
+    for key, (q_val, q_dead, q_lean) in zip(sets, out.quant):
+        Q = Csr(A.rowptr, A.col, q_val[:Ca], N).with_facts(q_dead[:N], True, cap.max_row)
+        Q._lean_values = Csr(A.rowptr, A.col, q_lean[:Ca], N)
+        A._quantized[key] = Q
     s.edge_index, s.edge_index_agg = out.ei[:2 * E].view(2, E), out.ei_agg[:2 * E].view(2, E)
     s.fea = None
     if features is not None:
@@ -1356,20 +1379,26 @@ def sample_node_batch(csr, seeds, fanouts, seed=0, step=0, fill=0, dtype=torch.f
     NodePadBuffers of an earlier call, at `.buffers` of what it returned; None: fresh ones).  The live prefix of every
     tensor holds the unpadded call's bits for the step the word holds; the facts are constants -- max_row =
     max(max(fanouts) + 1, 64), has_dead_rows = True with the exact mask -- and nothing is read from the device: no
-    synchronisation, capturable.  Errors of the sample (repeated seeds) reach out.status, not an exception."""
+    synchronisation, capturable.  Errors of the sample (repeated seeds) reach out.status, not an exception.
+    pad with quant (sgx_node_batch_sample_padded_quant, fp32 only): the padded batch also carries adj_norm.quantized(qc)
+    for quant and quant.second_layer() at capacity size -- the live prefix holds the unpadded quant= call's bits, a filler
+    row fq(1) on its diagonal entry and fq(0) on its spare ones -- with the same constant facts (has_dead_rows = True with
+    the exact quantised mask) and the lean mask values.  The constants must leave fq(1) > 0 and fq(0) == 0 (SgxError
+    otherwise): a filler row is then not dead and its spare entries carry no weight.  out= holds one (values, mask, lean
+    values) triple per distinct constant set; one built for another number of sets is refused."""
     _dev(seeds, "seeds")
     fan = [int(k) for k in fanouts]
     dev = csr.rowptr.device
     if pad is not None:
-        if quant is not None:
-            raise ValueError("sample_node_batch: pad= does not go with quant= (padded quantised node batches are not built)")
+        if quant is not None and dtype != torch.float32:
+            raise ValueError("sample_node_batch: quant needs dtype=torch.float32 (the quantised layer works on float32 buffers)")
         if tuple(fan) != pad.fanouts:
             raise ValueError("sample_node_batch: pad= was computed for other fan-outs")
         masks = list(masks)
         if len(masks) > 3:
             raise ValueError("sample_node_batch gathers up to three masks")
         return _sample_node_batch_padded(csr, seeds.to(torch.int32).contiguous(), seed, step, fill, dtype, edge_weight,
-                                         features, y, masks, pad, out)
+                                         features, y, masks, pad, out, quant)
     if out is not None:
         raise ValueError("sample_node_batch: out= needs pad=")
     if quant is not None and dtype != torch.float32:

@@ -286,6 +286,39 @@ class NodeBatch:
 _MASKS = ("train_mask", "val_mask", "test_mask")
 
 
+def _fq_unsigned_scalar(x, s, z, qbits):
+    """sgrace._fq_unsigned (quantization_ufbits, SG.py:253-265) of one number, on the host, as the library evaluates it:
+    1 / s rounded to fp32 (what ops hands the C ABI as inv_scale_adj), the product and the sum each rounded to fp32, round
+    half to even, the clip and the division."""
+    import numpy as np
+    f = np.float32
+    t = f(f(1.0 / s) * f(x)) + f(z)
+    q = min(max(float(np.rint(f(t))), 0.0), float(2 ** qbits - 1))
+    return q / 2 if qbits == 1 else q / 2 ** (qbits - 1)
+
+
+def check_pad_quant(quant):
+    """The conditions NeighborLoader(pad=True, quant=) puts on the adjacency's quantiser constants (include/sgx.h, "padded
+    node batches"), for `quant` and quant.second_layer(): ValueError naming `quant` where one fails.  Host arithmetic only."""
+    import math
+    try:
+        sets = [(int(qc.w_qbits), float(qc.a_s), float(qc.a_z)) for qc in (quant, quant.second_layer())]
+    except (AttributeError, TypeError, ValueError) as e:
+        raise ValueError(f"pad=True with quant=: quant carries no adjacency constants (w_qbits, a_s, a_z): {e}") from None
+    for bits, a_s, a_z in sets:
+        if bits not in (8, 4, 2, 1):
+            raise ValueError(f"pad=True with quant=: quant.w_qbits must be 8, 4, 2 or 1, not {bits}")
+        if not (math.isfinite(a_s) and a_s > 0 and math.isfinite(a_z)):
+            raise ValueError(f"pad=True with quant=: quant.a_s must be finite and positive (a_s {a_s}, a_z {a_z})")
+        one, zero = _fq_unsigned_scalar(1.0, a_s, a_z, bits), _fq_unsigned_scalar(0.0, a_s, a_z, bits)
+        if not one > 0:
+            raise ValueError(f"pad=True with quant=: with quant's a_s {a_s}, a_z {a_z} at {bits} bits a filler row's diagonal 1 "
+                             "rounds to 0: the filler rows would be dead under the quantised mask")
+        if zero != 0:
+            raise ValueError(f"pad=True with quant=: with quant's a_s {a_s}, a_z {a_z} at {bits} bits a filler row's spare 0 "
+                             f"becomes {zero}: the spare entries would carry weight")
+
+
 class NeighborLoader:
     """torch_geometric.loader.NeighborLoader(data, num_neighbors, batch_size, input_nodes, shuffle) on the HIP sampler
     (ops.sample_neighbors, rule in include/sgx.h).  The CSR on the targets of edge_index (row v = the edges j -> v,
@@ -331,16 +364,21 @@ class NeighborLoader:
     With attention on, a live row without a positive entry (fill = 0 leaves the rows of the last hop so) takes its
     uniform softmax over the N padded columns rather than the live ones: the layers' rule, on the padded width.
     ValueError where a batch CSR would want a plan (ops.Csr.wants_plan), which costs a read-back: a fan-out of -1,
-    max(fanouts) + 1 > 64, a feature row of over 64 entries, 2^20 or more adjacency or feature entries; and for quant=
-    (padded quantised batches are not built)."""
+    max(fanouts) + 1 > 64, a feature row of over 64 entries, 2^20 or more adjacency or feature entries.
+
+    pad=True with quant=qc: the padded batches carry the quantised adjacencies too, at capacity size and with the same
+    constant facts (ops.sample_node_batch(pad=, quant=), sgx_node_batch_sample_padded_quant): a filler row holds fq(1) on
+    its diagonal entry and fq(0) on its spare ones, fq the unsigned-grid quantiser of the adjacency.  The constants are
+    checked here, before any device work (check_pad_quant): w_qbits in {8, 4, 2, 1}, a finite positive a_s, fq(1) > 0 -- no
+    filler row is dead under the quantised mask -- and fq(0) == 0 -- its spare entries carry no weight; ValueError naming
+    `quant` otherwise.  quant.constants(w) passes at every width.  The recorded step then covers the quantised model as
+    well; the short last batch takes the unpadded quant= route."""
 
     def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0, prepare=None, fill=0,
                  dtype=torch.float32, transposed=False, quant=None, pad=False):
         from . import ops
         if pad and prepare != "sym_norm2":
             raise ValueError("pad=True needs prepare='sym_norm2'")
-        if pad and quant is not None:
-            raise ValueError("pad=True does not go with quant=: padded quantised node batches are not built")
         if pad and any(int(k) < 0 for k in num_neighbors):
             raise ValueError("pad=True needs fan-outs >= 0: a fan-out of -1 leaves a row unbounded")
         if pad and max(int(k) for k in num_neighbors) + 1 > 64:
@@ -350,6 +388,8 @@ class NeighborLoader:
             raise ValueError("quant needs prepare='sym_norm2'")
         if quant is not None and dtype != torch.float32:
             raise ValueError("quant needs dtype=torch.float32: the quantised layer works on float32 buffers")
+        if pad and quant is not None:
+            check_pad_quant(quant)
         self.quant = quant
         self.data, self.num_neighbors = data, [int(k) for k in num_neighbors]
         self.batch_size, self.shuffle, self.seed = int(batch_size), bool(shuffle), int(seed)
@@ -393,7 +433,8 @@ class NeighborLoader:
             if cap.nnz_norm >= 1 << 20 or cap.nnz_fea >= 1 << 20:
                 raise ValueError(f"pad=True: the capacity ({cap.nnz_norm} adjacency, {cap.nnz_fea} feature entries) reaches 2^20 "
                                  "entries: such a batch wants a plan, and a plan costs a read-back")
-            self.buffers = ops.NodePadBuffers(cap, n, dtype, dev, x.shape[1], self.y is not None, len(self.masks))
+            n_quant = 0 if quant is None else len({ops._adj_quant_key(qc) for qc in (quant, quant.second_layer())})
+            self.buffers = ops.NodePadBuffers(cap, n, dtype, dev, x.shape[1], self.y is not None, len(self.masks), n_quant)
             self.counts = self.buffers.counts
             self.seeds_buf = torch.zeros(B, dtype=torch.int32, device=dev)      # what a recorded sample reads: load()
             self.step_buf = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -436,7 +477,7 @@ class NeighborLoader:
         from . import ops
         s = ops.sample_node_batch(self.csr, self.seeds_buf, self.num_neighbors, seed=self.seed, step=self.step_buf,
                                   fill=self.fill, dtype=self.dtype, features=self.fea, y=self.y,
-                                  masks=[m for _, m in self.masks], pad=self.capacity, out=self.buffers)
+                                  masks=[m for _, m in self.masks], quant=self.quant, pad=self.capacity, out=self.buffers)
         x = ops.pack_rows(self.data.x, s.n_id, out=self.x_buf)
         A, n, cap = s.adj_norm, self.capacity.n_rows, self.capacity
         ops.attach(x, ("fea_csr", self.dtype), s.fea)

@@ -9,6 +9,7 @@ of examples/sgrace_node_classification.py (GCN and GAT).  One JSON line per meas
     python tools/sampler_probe.py --quick          # only the kernels, for a rocprofv3 --kernel-trace --stats run
     python tools/sampler_probe.py --node-batch [--arms default] [--trace]
     python tools/sampler_probe.py --node-batch --replay replay|eager [--label L]    # profiles/r22_node_replay.jsonl
+    python tools/sampler_probe.py --node-batch --replay replay|eager --quant 8      # profiles/r24_node_replay_quant.jsonl
                                                    # the training step through the default and the prepared NeighborLoader
                                                    # (GCN and GAT, the example's shape and the ogbn-products shape), the arms
                                                    # interleaved, median of repeated windows and their spread; and the batch
@@ -276,14 +277,18 @@ def node_batch(arms, trace, accbs=(0,), qbits=None):
         torch.cuda.empty_cache()
 
 
-def node_replay(leg):
+def node_replay(leg, qbits=None):
     """--node-batch --replay: the NodeTrainer mini-batch step on the example's graph at batch 128 and [10, 10], GCN and
     attention, as ONE leg per process so that two checkouts can take turns in one visit: leg "replay" -- the padded loader
     and NodeTrainer.capture_loader's recorded step; leg "eager" -- NodeTrainer.step on the prepared loader's batches (runs
-    on a checkout without padded batches too).  640 training nodes: five full batches an epoch, no short one."""
+    on a checkout without padded batches too).  640 training nodes: five full batches an epoch, no short one.
+    qbits (--quant): the QUANTISED model (config.fake_quantization and hardware_quantize) from loaders with quant= -- the
+    eager leg runs on a checkout without padded quantised batches too (profiles/r24_node_replay_quant.jsonl) -- and the
+    evaluation pass over the same loader: NodeTrainer.capture_eval_loader against evaluate(into=) per batch."""
     import importlib.util
     import statistics
-    from sgracex1_amd import config, pyg_lite, sgrace
+    from sgracex1_amd import config, pyg_lite, quant, sgrace
+    from sgracex1_amd.train import EvalSums
     from sgracex1_amd.train import NodeTrainer
     dev = torch.device("cuda")
     spec = importlib.util.spec_from_file_location("nc", os.path.join(ROOT, "examples", "sgrace_node_classification.py"))
@@ -296,11 +301,16 @@ def node_replay(leg):
     bs, fan, windows, epochs = 128, [10, 10], 7, 6
     for attention in (0, 1):
         config.acc, config.accb, config.device, config.compute_attention, config.gat_edge_outputs = 1, 0, "cuda", attention, 1
+        if qbits:
+            config.fake_quantization = config.hardware_quantize = 1
+            config.w_qbits = qbits
         sgrace.init_SGRACE()
         torch.manual_seed(0)
         model = sgrace.GAT_PYNQ(x.shape[1], 16, 1, 5).to(dev).train()
         trainer = NodeTrainer(model, lr=0.01)
         kw = dict(batch_size=bs, input_nodes=train, shuffle=True, seed=1, prepare="sym_norm2", transposed=bool(attention))
+        if qbits:
+            kw["quant"] = quant.constants(qbits)
         extra = {}
         if leg == "replay":
             loader = pyg_lite.NeighborLoader(data, fan, pad=True, **kw)
@@ -314,16 +324,39 @@ def node_replay(leg):
 
             def one_epoch():
                 return [trainer.step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size) for b in loader]
-        for _ in range(3):
-            one_epoch()
-        torch.cuda.synchronize()
-        times = []
-        for _ in range(windows):
-            t0 = time.perf_counter()
-            for _ in range(epochs):
-                n_steps = len(one_epoch())
+
+        def windows_of(run):
+            for _ in range(3):
+                run()
             torch.cuda.synchronize()
-            times.append((time.perf_counter() - t0) / (epochs * n_steps) * 1e3)
+            out = []
+            for _ in range(windows):
+                t0 = time.perf_counter()
+                for _ in range(epochs):
+                    k = run()
+                torch.cuda.synchronize()
+                out.append((time.perf_counter() - t0) / (epochs * k) * 1e3)
+            return out, k
+
+        times, n_steps = windows_of(lambda: len(one_epoch()))
+        if qbits:
+            # the evaluation pass over the same loader and model: one recorded evaluation per full batch against
+            # evaluate(into=) per batch; timed per batch of the pass
+            if leg == "replay":
+                run_pass = trainer.capture_eval_loader(loader)
+            else:
+                sums = EvalSums(dev)
+
+                def run_pass():
+                    sums.zero_()
+                    for b in loader:
+                        trainer.evaluate(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size, into=sums)
+                    return sums
+            ev, _ = windows_of(lambda: (run_pass(), len(loader))[1])
+            extra_eval = {"qbits": qbits, "eval_batch_ms_median": round(statistics.median(ev), 4), "eval_batch_ms_min": round(min(ev), 4),
+                          "eval_batch_ms_max": round(max(ev), 4)}
+        else:
+            extra_eval = {}
         if leg == "replay":
             loader.status()
             seen = 0
@@ -341,7 +374,7 @@ def node_replay(leg):
                           "leg": leg, "model": "GAT" if attention else "GCN", "graph": "example (3 000 nodes)", "batch": bs,
                           "fanouts": fan, "steps_per_epoch": n_steps, "step_ms_median": round(statistics.median(times), 4),
                           "step_ms_min": round(min(times), 4), "step_ms_max": round(max(times), 4), "windows": windows,
-                          "steps_per_window": epochs * n_steps, **extra}), flush=True)
+                          "steps_per_window": epochs * n_steps, **extra_eval, **extra}), flush=True)
 
 
 def main():
@@ -367,7 +400,7 @@ def main():
         if a.label:
             print(json.dumps({"label": a.label}), flush=True)
         if a.replay:
-            return node_replay(a.replay)
+            return node_replay(a.replay, a.quant)
         arms = a.arms.split(",") + (["prepared_t"] if a.transposed else [])
         if a.quant and a.arms == "default,prepared":
             arms = ["prepared", "prepared_q"] + arms[2:]
