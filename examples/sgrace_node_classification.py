@@ -6,7 +6,7 @@ downloaded by torch_geometric and are not available offline.
 
     python examples/sgrace_node_classification.py [--attention [--lean-gat]] [--qbits 8] [--epochs 60] [--acc 0]
                                                   [--batch-size 128 --num-neighbors 10,10 [--device-batches]] [--accb]
-                                                  [--trainer [--replay]]
+                                                  [--trainer [--replay] [--keep-best]]
 
 --attention  GAT edge softmax instead of the GCN aggregate (config.compute_attention)
 --lean-gat   with --attention on the kernels: the forward keeps the row softmax statistics instead of the per-edge outputs
@@ -50,6 +50,14 @@ downloaded by torch_geometric and are not available offline.
              (NodeTrainer.capture_eval_loader); with --qbits the padded batches carry the quantised adjacency of both
              layers (NeighborLoader(pad=True, quant=sgrace.quant_constants)) and the recorded step and evaluations are the
              quantised model's; --accb stays an eager route
+--keep-best  with --trainer, --batch-size and --device-batches (no --accb), where every epoch ends with the validation and
+             test passes: the demo's save-best / load-best step on the device (train.BestTracker, sgx_keep_best).  Every
+             epoch ends with one call that compares the validation counts with the best so far in integers, keeps a copy
+             of the weights where the epoch wins and logs both passes' sums; nothing is read back per epoch (with --replay
+             the loop runs under torch.cuda.set_sync_debug_mode("error")).  After the last epoch the run is read back in
+             ONE transfer, the best epoch's weights are put back and both passes run once more on the samples of that
+             epoch: restored_test_acc, which equals that epoch's logged test accuracy; the final train_acc is then the
+             restored model's
 """
 import argparse
 import os
@@ -80,7 +88,7 @@ def planted_partition(n, classes, f_in, p_in, p_out, seed, device):
 
 def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, verbose=True, emulate=False,
         batch_size=None, num_neighbors=None, lean_gat=False, device_batches=False, accb=0, trainer=False,
-        replay=False):
+        replay=False, keep_best=False):
     from sgracex1_amd import config, sgrace
     config.acc = acc
     config.accb = int(accb)
@@ -139,7 +147,18 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
                         node_trainer.evaluate(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size, into=sums)
                     return sums
                 passes.append((ev, eager))
+    tracker = None
+    if keep_best:
+        if passes is None:
+            raise ValueError("keep_best needs the per-epoch passes: trainer, batch_size, device_batches, no accb")
+        tracker = node_trainer.track_best(epochs)
+        first_pass = [ev.epoch for ev, _ in passes]         # the epoch number (it seeds the samples) of every loader's first pass
+        if replay:
+            replay_step = node_trainer.capture_loader(loader)
+            sync_mode = torch.cuda.get_sync_debug_mode()
+            torch.cuda.set_sync_debug_mode("error")         # from the first epoch to the last nothing may synchronise
     best_val, test_at_best = -1.0, 0.0
+    printed = []
     t0 = time.time()
     epoch_loss = []                                         # mean training loss of every epoch, kept on the device
     for epoch in range(epochs):
@@ -185,18 +204,37 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
                 opt.step()
                 total, steps = total + loss.detach(), steps + 1
         epoch_loss.append(total / max(steps, 1))
-        if passes is not None:
+        if tracker is not None:
+            tracker.update(*[run_pass() for _, run_pass in passes])      # validation decides; nothing is read back
+        elif passes is not None:
             (m_val, hit_val, _), (m_te, hit_te, _) = EvalSums.read(*[run_pass() for _, run_pass in passes])
             if hit_val / m_val > best_val:                  # the test accuracy of the epoch that validates best
                 best_val, test_at_best = hit_val / m_val, hit_te / m_te
         if verbose and (epoch + 1) % 20 == 0:
-            print(f"epoch {epoch + 1:3d}  loss {float(loss):.4f}", flush=True)
+            if tracker is not None:
+                printed.append((epoch, loss.detach().clone()))       # printed behind the loop
+            else:
+                print(f"epoch {epoch + 1:3d}  loss {float(loss):.4f}", flush=True)
+    if tracker is not None and replay:
+        torch.cuda.set_sync_debug_mode(sync_mode)
     if loader is not None and replay:
         for ld in [loader] + [ev for ev, _ in passes or []]:
             ld.status()                                     # what a failed batch would have raised, read back once
     if device.type == "cuda":
         torch.cuda.synchronize()
     elapsed = time.time() - t0
+    kept = {}
+    if tracker is not None:
+        best_epoch, _, _, _, log = tracker.read()           # the whole run in ONE device-to-host copy
+        for epoch, loss in printed:
+            print(f"epoch {epoch + 1:3d}  loss {float(loss):.4f}", flush=True)
+        epoch_acc = [[hits / n for n, hits, _ in row] for row in log]
+        test_at_best = epoch_acc[best_epoch][1] if best_epoch >= 0 else 0.0
+        tracker.restore()                                   # the demo's load_state_dict(best)
+        for (ev, _), first in zip(passes, first_pass):
+            ev.epoch = first + max(best_epoch, 0)           # the passes of the best epoch drew their samples from this number
+        _, (m_te, hit_te, _) = EvalSums.read(*[run_pass() for _, run_pass in passes])
+        kept = {"best_epoch": best_epoch, "restored_test_acc": hit_te / m_te, "epoch_acc": epoch_acc}
     model.eval()
     if node_trainer is not None:
         (m_tr, hit_tr), (m_te, hit_te) = (node_trainer.evaluate(x, edge_index, y, m)[0].tolist() for m in (full_mask, ~full_mask))
@@ -209,7 +247,7 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         train_acc, test_acc = float((pred[train] == y[train]).float().mean()), float((pred[test] == y[test]).float().mean())
     result = {"train_acc": train_acc, "test_acc": test_acc,
               "edges": int(edge_index.shape[1]), "ms_per_epoch": 1000 * elapsed / epochs,
-              "epoch_loss": [float(v) for v in epoch_loss]}
+              "epoch_loss": [float(v) for v in epoch_loss], **kept}
     if loader is not None:
         result["batches_per_epoch"] = len(loader)
     if verbose:
@@ -234,6 +272,7 @@ if __name__ == "__main__":
     ap.add_argument("--accb", action="store_true")
     ap.add_argument("--trainer", action="store_true")
     ap.add_argument("--replay", action="store_true")
+    ap.add_argument("--keep-best", action="store_true")
     a = ap.parse_args()
     if (a.batch_size is None) != (a.num_neighbors is None) or (a.batch_size is not None and a.acc != 1):
         ap.error("--batch-size and --num-neighbors go together, on the kernels (--acc 1)")
@@ -245,6 +284,8 @@ if __name__ == "__main__":
         ap.error("--replay replays the step of --trainer: the full-graph one, or the padded mini-batch one of --device-batches")
     if a.replay and a.batch_size is not None and a.accb:
         ap.error("--replay on mini-batches covers the layers with the staged backward, quantised or not (no --accb)")
+    if a.keep_best and not (a.trainer and a.batch_size is not None and a.device_batches and not a.accb):
+        ap.error("--keep-best needs --trainer with the per-epoch passes: --batch-size, --num-neighbors, --device-batches, no --accb")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
         num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches,
-        accb=int(a.accb), trainer=a.trainer, replay=a.replay)
+        accb=int(a.accb), trainer=a.trainer, replay=a.replay, keep_best=a.keep_best)

@@ -1820,6 +1820,58 @@ int sgx_node_eval(int64_t n_rows, int64_t n_prefix, int P, int C, const float *H
                   const int64_t *target, const uint8_t *mask, int64_t *totals /* [2] */, double *loss_sum /* [1] */,
                   float *logits /* or NULL */, void *workspace, size_t workspace_bytes, void *stream);
 
+/* ---- model selection: keep the best epoch's weights on the device --------------------------------------
+ * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.
+ *
+ * sgx_keep_best is the reference training loop's `if test_acc > best_acc: torch.save(model.state_dict())`
+ * (demo_sgrace.py:583-610) without the read-back: one call per epoch compares the counts an evaluation pass left in its
+ * accumulators (sgx_head_eval / sgx_node_eval: int64 [3] = rows, hits, the bits of the double loss sum) with the best so
+ * far, in integers, copies up to SGX_BEST_MAX_TENSORS fp32 tensors into a snapshot where the epoch wins, and appends the
+ * epoch's sums to a log on the device, so a whole run is read back once.  The tensor table travels in the kernel
+ * arguments, as sgx_adam_step's does.
+ *   state      device int64 [4] = (best_n, best_hits, best_epoch, epoch); a fresh one is (1, 0, -1, 0): the fraction 0 / 1
+ *              stands for the reference's best_acc = 0
+ *   operands   (n, hits) = sums[0][0], sums[0][1] -- sums[0] is the pass that decides -- and e = state[3]
+ *   better     exactly when  0 < n < 2^31  and  0 <= hits <= n  and  best_n < 2^31  and
+ *                  hits * best_n > best_hits * n       (64-bit integers: no division, no floating point)
+ *              the reference's strict >: an epoch that ties the best (1/3 after 2/6, the same counts again) does not
+ *              replace it, an epoch without a hit never becomes best, and a candidate outside the bounds is not better
+ *   where better:  dst[i] = src[i] bit for bit, i < n, for every tensor (n == 0: skipped); then
+ *              best_n, best_hits, best_epoch = n, hits, e
+ *   in every call, better or not:  with log != NULL and 0 <= e < log_rows, row e of the log [log_rows][3 * n_sums]
+ *              receives the three words of sums[0], sums[1], ... in order (the loss sum's double as its 64 bits); then
+ *              epoch = e + 1
+ * Two launches, as sgx_adam_step: one copies and logs and only READS state, so every workgroup forms the same decision
+ * from the same words; a trailing one-thread launch forms it once more and writes state.  No atomics.  The copy strides
+ * the grid over every tensor: 16-byte stores over the 16-byte-aligned body of dst and single elements at both ends; a src
+ * that is not aligned as its dst is read by dwords.  src and dst of one tensor must not overlap.
+ *
+ * Capturable: no allocation, no synchronisation, the same bits on every run.  Argument errors, returned before anything
+ * reaches the device: d, state or one of sums[0 .. n_sums) NULL, src or dst NULL with n > 0, log NULL with log_rows > 0:
+ * SGX_ERR_NULL; n_tensors outside 0 .. SGX_BEST_MAX_TENSORS, n_sums outside 1 .. SGX_BEST_MAX_SUMS, n < 0, log_rows < 0:
+ * SGX_ERR_SHAPE; src == dst on a tensor with n > 0: SGX_ERR_UNSUPPORTED; a src or dst of such a tensor off a 4-byte
+ * boundary: SGX_ERR_ALIGN. */
+#define SGX_BEST_MAX_TENSORS 16
+#define SGX_BEST_MAX_SUMS 4
+
+typedef struct sgx_best_tensor {
+    const float *src;            /* [n] fp32: the parameter */
+    float *dst;                  /* [n] fp32: its snapshot */
+    int64_t n;                   /* elements; 0 = skipped */
+} sgx_best_tensor;
+
+typedef struct sgx_best_desc {
+    int32_t n_tensors;           /* 0 .. SGX_BEST_MAX_TENSORS */
+    int32_t n_sums;              /* 1 .. SGX_BEST_MAX_SUMS; sums[0] is the one that decides */
+    const int64_t *sums[SGX_BEST_MAX_SUMS];  /* device, each int64 [3] = (n, hits, loss_sum bits) */
+    int64_t *state;              /* device int64 [4]: best_n, best_hits, best_epoch, epoch */
+    int64_t *log;                /* device int64 [log_rows][3 * n_sums], or NULL */
+    int64_t log_rows;
+    sgx_best_tensor tensor[SGX_BEST_MAX_TENSORS];
+} sgx_best_desc;
+
+int sgx_keep_best(const sgx_best_desc *d, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -2540,6 +2540,57 @@ def adam_step(params, grads, exp_avgs, exp_avg_sqs, step, lr=1e-3, betas=(0.9, 0
     check(lib.sgx_adam_step(ctypes.byref(d), _stream()), "sgx_adam_step")
 
 
+# ---- model selection: the best epoch's weights kept on the device (sgx_keep_best) --------------------------------------------
+def keep_best(params, snapshot, sums, state, log=None):
+    """One epoch of model selection in one call (sgx_keep_best; the rule is in include/sgx.h, "model selection"): where
+    the counts in sums[0] beat the best so far -- hits * best_n > best_hits * n, in integers -- every params[k] is copied
+    into snapshot[k] bit for bit and `state` takes the epoch; in every call the sums go to row `epoch` of `log` and the
+    epoch advances.  params, snapshot: up to 16 fp32 tensors of equal sizes, pair by pair distinct; sums: 1 to 4 device
+    int64 [3] buffers (train.EvalSums.buffer: rows, hits, the loss sum's bits), the first decides; state: a device int64
+    [4] = (best_n, best_hits, best_epoch, epoch), fresh as (1, 0, -1, 0); log: None or a device int64 [rows, 3 * len(sums)].
+    More than 16 tensors: ValueError.  Never synchronises."""
+    n = len(params)
+    if len(snapshot) != n:
+        raise ValueError("keep_best takes one snapshot tensor per parameter")
+    if n > _lib.SGX_BEST_MAX_TENSORS:
+        raise ValueError(f"keep_best takes at most {_lib.SGX_BEST_MAX_TENSORS} tensors in a call (got {n})")
+    if not 1 <= len(sums) <= _lib.SGX_BEST_MAX_SUMS:
+        raise ValueError(f"keep_best takes 1 to {_lib.SGX_BEST_MAX_SUMS} sums (got {len(sums)})")
+    _dev(state, "state")
+    if state.dtype != torch.int64 or state.numel() != 4:
+        raise TypeError("state must be a device int64 tensor of four elements")
+    for k, s in enumerate(sums):
+        _dev(s, f"sums[{k}]")
+        if s.dtype != torch.int64 or s.numel() != 3 or s.device != state.device:
+            raise TypeError(f"sums[{k}] must be an int64 tensor of three elements on the state's device")
+    if log is not None:
+        _dev(log, "log")
+        if log.dtype != torch.int64 or log.dim() != 2 or log.shape[1] != 3 * len(sums) or log.device != state.device:
+            raise TypeError(f"log must be an int64 tensor [rows, {3 * len(sums)}] on the state's device")
+    d = _lib.BestDesc()
+    d.n_tensors, d.n_sums = n, len(sums)
+    for k in range(n):
+        p, s = params[k].detach(), snapshot[k].detach()
+        for name, t in (("params", p), ("snapshot", s)):
+            _dev(t, f"{name}[{k}]")
+            if t.dtype != torch.float32 or t.device != state.device:
+                raise ValueError(f"{name}[{k}] must be a float32 tensor on the state's device")
+        if s.numel() != p.numel():
+            raise ValueError(f"snapshot[{k}] must have the size of params[{k}]")
+        T = d.tensor[k]
+        T.n = p.numel()
+        if T.n:
+            if p.data_ptr() == s.data_ptr():
+                raise ValueError(f"snapshot[{k}] is params[{k}] itself")
+            T.src, T.dst = p.data_ptr(), s.data_ptr()
+    for k, s in enumerate(sums):
+        d.sums[k] = s.data_ptr()
+    d.state = state.data_ptr()
+    if log is not None and log.shape[0] > 0:
+        d.log, d.log_rows = log.data_ptr(), log.shape[0]
+    check(lib.sgx_keep_best(ctypes.byref(d), _stream()), "sgx_keep_best")
+
+
 # ---- the tail of a node-classification step: the loss head over selected rows (sgx_node_loss) ----------------------------------
 def node_loss(H, weight, bias, target, mask=None, n_prefix=None, p=0.0, seed=0, step=0, step_dev=None, grad_scale=1.0,
               want_logits=False, want_counts=False, grads=True):

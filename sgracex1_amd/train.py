@@ -8,6 +8,9 @@ can be captured once (torch.cuda.graph) and replayed: the regime of the notebook
 
 NodeTrainer is the same for node classification (sgrace.GAT_PYNQ): the model's two layers through their own autograd,
 ops.NodeLoss (the tail over the selected rows, the count of which never leaves the device) and ops.adam_step.
+
+BestTracker (trainer.track_best()) is the loop's model selection on the device: one ops.keep_best per epoch keeps the
+weights of the epoch that evaluated best and logs every epoch's sums, so a run is read back once.
 """
 import contextlib
 
@@ -48,6 +51,11 @@ class _Trainer:
         with torch.no_grad():
             for dst, src in zip((*self.params, *self.exp_avg, *self.exp_avg_sq, self.t), state):
                 dst.copy_(src)
+
+    def track_best(self, epochs=None):
+        """A BestTracker over this trainer's parameters: the best epoch's weights kept on the device, a run read back once.
+        epochs: the rows of its log (None: no log)."""
+        return BestTracker(self, epochs)
 
     def _capture(self, batch, warmup, probe=None, counters=(), run=None):
         """Record self.step(*batch) (or run(), where a step has more in front of it) with torch.cuda.graph (one stream, no parallel branches) and return a callable that
@@ -374,6 +382,83 @@ class EvalSums:
         """[(graphs, hits, loss_sum)] of several EvalSums on the host, by ONE device-to-host copy (it synchronises)."""
         host = torch.stack([s.buffer for s in sums]).cpu()
         return [(int(row[0]), int(row[1]), float(row[2:].view(torch.float64)[0])) for row in host]
+
+
+class BestTracker:
+    """The reference loop's save-best / load-best step on the device (demo_sgrace.py:583-610: `if test_acc > best_acc:
+    torch.save(model.state_dict())`, and `load_state_dict(best)` after the last epoch), without a read-back per epoch.
+
+        tracker = trainer.track_best(epochs=E)
+        for epoch in range(E):
+            ...                                   # the epoch's steps, then the evaluation passes into their EvalSums
+            tracker.update(val_sums, test_sums)   # one ops.keep_best: val_sums decides; nothing synchronises
+        best_epoch, best_n, best_hits, done, log = tracker.read()      # ONE device-to-host copy for the whole run
+        tracker.restore()                         # the model is the best epoch's again
+
+    It holds one snapshot tensor per trainer.params (initialised to the parameters' current values, so restore() before
+    any winning epoch leaves the model as it is), the state int64 [4] = (best_n, best_hits, best_epoch, epoch), fresh as
+    (1, 0, -1, 0), and with `epochs` a log of that many rows for up to 4 EvalSums.  The comparison is exact and in
+    integers (include/sgx.h, "model selection"): strictly more hits per row wins, a tie keeps the earlier epoch.  The
+    optimiser's moments and `t` are neither kept nor restored."""
+
+    def __init__(self, trainer, epochs=None):
+        self.trainer = trainer
+        self.params = trainer.params
+        if len(self.params) > ops._lib.SGX_BEST_MAX_TENSORS:
+            raise ValueError(f"BestTracker keeps at most {ops._lib.SGX_BEST_MAX_TENSORS} tensors (the model has {len(self.params)})")
+        dev = self.params[0].device
+        self.snapshot = [p.detach().clone(memory_format=torch.contiguous_format) for p in self.params]
+        self.state = torch.tensor([1, 0, -1, 0], dtype=torch.int64).to(dev)
+        self.epochs = None if epochs is None else int(epochs)
+        if self.epochs is not None and self.epochs < 0:
+            raise ValueError("epochs must not be negative")
+        # the log's rows are 3 words per EvalSums; how many there are is known at the first update()
+        self._log_words = None if not self.epochs else torch.zeros(self.epochs * 3 * ops._lib.SGX_BEST_MAX_SUMS, dtype=torch.int64,
+                                                                   device=dev)
+        self.n_sums, self.log = None, None
+
+    def update(self, *sums):
+        """One epoch: ops.keep_best on the trainer's parameters with `sums` -- EvalSums (or their int64 [3] buffers), the
+        first decides.  Every call of one tracker takes the same number of them.  Does not synchronise and may be called
+        inside torch.cuda.graph."""
+        buffers = [getattr(s, "buffer", s) for s in sums]
+        if self.n_sums is None:
+            if not 1 <= len(buffers) <= ops._lib.SGX_BEST_MAX_SUMS:
+                raise ValueError(f"update takes 1 to {ops._lib.SGX_BEST_MAX_SUMS} EvalSums (got {len(buffers)})")
+            self.n_sums = len(buffers)
+            if self._log_words is not None:
+                self.log = self._log_words[: self.epochs * 3 * self.n_sums].view(self.epochs, 3 * self.n_sums)
+        elif len(buffers) != self.n_sums:
+            raise ValueError(f"this tracker's epochs carry {self.n_sums} EvalSums (got {len(buffers)})")
+        ops.keep_best(self.params, self.snapshot, buffers, self.state, self.log)
+
+    def restore(self):
+        """Copies the snapshot into the parameters, device to device, without a read-back.  The copies are torch's in-place
+        ones, so every parameter's version counter moves and whatever is cached by it is rebuilt; the models and trainers
+        themselves derive the transposed and quantised weights from the parameters in every forward.  The moments and `t`
+        are not touched."""
+        with torch.no_grad():
+            for p, s in zip(self.params, self.snapshot):
+                p.copy_(s)
+
+    def read(self):
+        """(best_epoch, best_n, best_hits, epochs_done, log) by ONE device-to-host copy (it synchronises): best_epoch is
+        -1 while no epoch has won; log holds, per logged epoch, [(n, hits, loss_sum), ...] in the order update() took the
+        sums -- the epochs done, as far as the log's rows go; empty without `epochs`."""
+        words = self.state if self.log is None else torch.cat([self.state, self.log.reshape(-1)])
+        host = words.cpu()
+        best_n, best_hits, best_epoch, done = (int(v) for v in host[:4])
+        rows = host[4:].view(-1, 3) if self.log is not None else host[4:]
+        log = []
+        for e in range(min(done, self.epochs or 0) if self.log is not None else 0):
+            row = rows[e * self.n_sums:(e + 1) * self.n_sums]
+            log.append([(int(r[0]), int(r[1]), float(r[2:].view(torch.float64)[0])) for r in row])
+        return best_epoch, best_n, best_hits, done, log
+
+    def state_dict(self):
+        """The snapshot under the model's parameter names (clones; parameters the trainer does not train are left out)."""
+        names = {id(p): name for name, p in self.trainer.model.named_parameters()}
+        return {names[id(p)]: s.clone() for p, s in zip(self.params, self.snapshot)}
 
 
 class NodeTrainer(_Trainer):
