@@ -4,22 +4,23 @@
 // What the notebook's accuracy() runs as self.lin, argmax, ==, sum and a read-back per set.
 //
 // Two launches, as sgx_head_loss.  The first, a wavefront per graph: wave w of workgroup b takes the graphs 4 b + w,
-// 4 b + w + 4 grid, ...; per graph the logits in sgx_head_loss's order (lane-strided fmaf, xor butterfly, bias), then
-// lane 0 forms lse, the loss and the arg-max exactly as sgx_head_loss / sgx_node_loss do, stores the graph's fp32 loss in
-// its own workspace slot and counts its hits.  Nothing that is summed depends on the grid: the loss slots are per graph,
-// the hit counts are integers.  The second, one workgroup: the slots added in graph order into a double, the counts,
-// and both added to the accumulators.  No atomics: the same bits on every run and for any grid.
+// 4 b + w + 4 grid, ...; per graph the logits (tail_device.h: wave_class_logit, on pooled itself: p_drop = 0), then
+// lane 0 forms lse, the loss and the arg-max (row_cross_entropy), stores the graph's fp32 loss in its own workspace slot
+// and counts its hits.  Nothing that is summed depends on the grid: the loss slots are per graph, the hit counts are
+// integers.  The second, one workgroup: the slots added in graph order into a double (ordered_sum), the counts, and both
+// added to the accumulators.  No atomics: the same bits on every run and for any grid.
 // (A one-launch form -- the last workgroup to draw a ticket, zeroed by a memset node, doing the second launch's work behind
 // an agent-scope release / acquire -- passed every test and then lost whole calls' sums after some tens of back-to-back
 // graph replays (tools/eval_probe.py: a pass counted 0 graphs); the cause was not established, and the launch boundary
 // it saved is about 2 us.)
-#include "sgx_internal.h"
+#include "tail_device.h"
+
+using namespace sgx_tail;
 
 namespace {
 
-constexpr int kBlock = 256, kWaves = kBlock / 64;
+constexpr int kWaves = kBlock / 64;
 constexpr int kEvalGrid = 256;        // workgroups at most
-constexpr int kMaxP = 1024, kMaxC = 64;               // sgx_head_loss's limits
 constexpr size_t kHeader = 256;       // the workspace's first 256 bytes are reserved
 
 struct EvalArgs {
@@ -46,30 +47,17 @@ __global__ __launch_bounds__(kBlock) void head_eval_kernel(EvalArgs a)
     for (int g = (int)blockIdx.x * kWaves + wave; g < rows; g += n_waves) {
         const float *xs = a.pooled + (int64_t)g * P;         // p_drop = 0: x == pooled bit for bit
         for (int c = 0; c < C; ++c) {
-            float s = 0.0f;
-            for (int j = lane; j < P; j += 64) s = __builtin_fmaf(a.W[(int64_t)c * P + j], xs[j], s);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            const float s = wave_class_logit(a.W + (int64_t)c * P, xs, P, lane, a.bias, c);
             if (lane == 0) {
-                s = s + (a.bias ? a.bias[c] : 0.0f);
                 z[c] = s;
                 if (a.logits) a.logits[(int64_t)g * C + c] = s;
             }
         }
         if (lane == 0 && g < a.n_real) {                     // z is lane 0's own: written and read by the one thread
             const int64_t t = a.target[g];
-            const bool live = t >= 0 && t < C;
-            float m = z[0];
-            for (int c = 1; c < C; ++c) m = z[c] > m ? z[c] : m;
-            float s = 0.0f;
-            for (int c = 0; c < C; ++c) s = s + expf(z[c] - m);
-            const float lse = m + logf(s);
-            int best = 0;
-            float bv = z[0] == z[0] ? z[0] : -INFINITY;
-            for (int c = 1; c < C; ++c)
-                if (z[c] > bv) bv = z[c], best = c;
-            a.row_loss[g] = live ? lse - z[t] : 0.0f;
-            hits += live && best == (int)t;
+            const RowCe ce = row_cross_entropy(z, C, t);
+            a.row_loss[g] = ce.live ? ce.lse - z[t] : 0.0f;
+            hits += ce.live && ce.best == (int)t;
         }
     }
     if (lane == 0) a.wave_hits[(int)blockIdx.x * kWaves + wave] = hits;
@@ -86,15 +74,7 @@ __global__ __launch_bounds__(kBlock) void head_eval_sum_kernel(EvalArgs a, int n
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) h += __shfl_xor(h, off);
     if (lane == 0) hits_s[wave] = h;
-    double sum = 0.0;                                        // thread 0's
-    for (int k0 = 0; k0 < a.n_real; k0 += kBlock) {
-        const int cnt = a.n_real - k0 < kBlock ? a.n_real - k0 : kBlock;
-        __syncthreads();
-        if (tid < cnt) chunk[tid] = a.row_loss[k0 + tid];
-        __syncthreads();
-        if (tid == 0)
-            for (int k = 0; k < cnt; ++k) sum += (double)chunk[k];
-    }
+    const double sum = ordered_sum(a.n_real, chunk, [&](int k) { return a.row_loss[k]; });      // thread 0's
     __syncthreads();
     if (tid == 0) {
         int64_t n = 0;
@@ -105,13 +85,11 @@ __global__ __launch_bounds__(kBlock) void head_eval_sum_kernel(EvalArgs a, int n
     }
 }
 
-bool eval_shape_ok(int G, int P, int C) { return G >= 1 && P >= 1 && C >= 1 && P <= kMaxP && C <= kMaxC; }
-
 }  // namespace
 
 extern "C" size_t sgx_head_eval_workspace_bytes(int n_graphs, int P, int C)
 {
-    if (!eval_shape_ok(n_graphs, P, C)) return 0;
+    if (!head_shape_ok(n_graphs, P, C)) return 0;
     return kHeader + sgx_align_up((size_t)n_graphs * sizeof(float), 256) + (size_t)kEvalGrid * kWaves * sizeof(int);
 }
 

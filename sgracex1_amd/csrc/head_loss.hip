@@ -4,31 +4,23 @@
 // F.dropout, self.lin, CrossEntropyLoss and their autograd nodes.
 //
 // One workgroup per graph slot: workgroup b takes the graphs b, b + grid, ... (grid = min(G, kHeadGrid) whatever the
-// device).  Per graph: x = dropout(pooled[g]) into LDS, the logits in readout_mean_linear_kernel's order (a wave per
-// class, lane-strided fmaf, xor butterfly, bias), lse and dz by one thread per class, grad_pooled a column per thread,
-// and the graph's share of grad_W / grad_bias / the loss sum added to the workgroup's own fp32 slice (plain loads and
-// stores).  A second launch adds the slices in slice order.  No atomics: the same bits on every run.
-#include "sgx_internal.h"
+// device).  Per graph: x = dropout(pooled[g]) into LDS, the logits a wave per class, lse by thread 0 and dz by one thread
+// per class, grad_pooled a column per thread, and the graph's share of grad_W / grad_bias / the loss sum added to the
+// workgroup's own fp32 slice (plain loads and stores).  A second launch adds the slices in slice order.  No atomics: the
+// same bits on every run.  The dropout rule, the logit and the row's cross entropy are tail_device.h's.
+#include "tail_device.h"
+
+using namespace sgx_tail;
 
 namespace {
 
-constexpr int kBlock = 256;
 constexpr int kHeadGrid = 256;        // slices: a fixed bound, so the summation order does not depend on the device
-constexpr int kMaxP = 1024, kMaxC = 64;
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z)       // the sampler's (sample.hip): the splitmix64 finaliser
-{
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
 
 struct HeadArgs {
     int G, P, C, grid;
     const float *pooled, *W, *bias;
     const int64_t *target;
-    uint32_t keep_from;               // floor(p * 2^24): an element is kept iff the top 24 bits of its hash reach it
-    float scale;                      // 1 / (1 - p), formed once in fp32
+    Dropout drop;
     uint64_t seed, step;
     const int64_t *step_dev;
     float gs;                         // grad_scale / G
@@ -44,26 +36,20 @@ __global__ __launch_bounds__(kBlock) void head_loss_kernel(HeadArgs a)
     __shared__ float lse_s;
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int P = a.P, C = a.C;
-    const uint64_t step_total = a.step + (a.step_dev ? (uint64_t)a.step_dev[0] : 0ull);
-    const uint64_t key = mix64(mix64(a.seed) ^ step_total);
+    const uint64_t key = dropout_key(a.seed, a.step, a.step_dev);
     const int64_t stride = (int64_t)C * P + C + 1;
     float *slice = a.slices + (int64_t)blockIdx.x * stride;
     float loss_sum = 0.0f;                                   // thread 0's
     bool first = true;
     for (int g = blockIdx.x; g < a.G; g += a.grid, first = false) {
         for (int j = tid; j < P; j += kBlock) {
-            const uint64_t k = mix64(key ^ (uint64_t)((int64_t)g * P + j));
-            const bool keep = (uint32_t)(k >> 40) >= a.keep_from;
-            xs[j] = keep ? a.pooled[(int64_t)g * P + j] * a.scale : 0.0f;
+            const bool keep = dropout_keep(key, (int64_t)g * P + j, a.drop.keep_from);
+            xs[j] = keep ? a.pooled[(int64_t)g * P + j] * a.drop.scale : 0.0f;
         }
         __syncthreads();
         for (int c = wave; c < C; c += kBlock / 64) {
-            float s = 0.0f;
-            for (int j = lane; j < P; j += 64) s = __builtin_fmaf(a.W[(int64_t)c * P + j], xs[j], s);
-#pragma unroll
-            for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
+            const float s = wave_class_logit(a.W + (int64_t)c * P, xs, P, lane, a.bias, c);
             if (lane == 0) {
-                s = s + (a.bias ? a.bias[c] : 0.0f);
                 z[c] = s;
                 if (a.logits) a.logits[(int64_t)g * C + c] = s;
             }
@@ -72,11 +58,7 @@ __global__ __launch_bounds__(kBlock) void head_loss_kernel(HeadArgs a)
         const int64_t t = a.target[g];
         const bool live = t >= 0 && t < C;
         if (tid == 0) {
-            float m = z[0];
-            for (int c = 1; c < C; ++c) m = z[c] > m ? z[c] : m;
-            float s = 0.0f;
-            for (int c = 0; c < C; ++c) s = s + expf(z[c] - m);
-            const float lse = m + logf(s);
+            const float lse = row_cross_entropy(z, C, t).lse;
             lse_s = lse;
             if (live) loss_sum = loss_sum + (lse - z[t]);
         }
@@ -88,11 +70,10 @@ __global__ __launch_bounds__(kBlock) void head_loss_kernel(HeadArgs a)
         }
         __syncthreads();
         for (int j = tid; j < P; j += kBlock) {
-            const uint64_t k = mix64(key ^ (uint64_t)((int64_t)g * P + j));
-            const bool keep = (uint32_t)(k >> 40) >= a.keep_from;
+            const bool keep = dropout_keep(key, (int64_t)g * P + j, a.drop.keep_from);
             float s = 0.0f;
             for (int c = 0; c < C; ++c) s = __builtin_fmaf(dz[c], a.W[(int64_t)c * P + j], s);
-            a.grad_pooled[(int64_t)g * P + j] = keep ? a.scale * s : 0.0f;
+            a.grad_pooled[(int64_t)g * P + j] = keep ? a.drop.scale * s : 0.0f;
         }
         for (int e = tid; e < C * P; e += kBlock) {
             const int c = e / P, j = e - c * P;
@@ -122,8 +103,6 @@ __global__ __launch_bounds__(kBlock) void head_loss_reduce_kernel(int G, int P, 
         loss[0] = s / (float)G;
 }
 
-bool head_shape_ok(int G, int P, int C) { return G >= 1 && P >= 1 && C >= 1 && P <= kMaxP && C <= kMaxC; }
-
 }  // namespace
 
 extern "C" size_t sgx_head_loss_workspace_bytes(int n_graphs, int P, int C)
@@ -147,8 +126,7 @@ extern "C" int sgx_head_loss(int n_graphs, int P, int C, const float *pooled, co
     HeadArgs a;
     a.G = n_graphs, a.P = P, a.C = C, a.grid = n_graphs < kHeadGrid ? n_graphs : kHeadGrid;
     a.pooled = pooled, a.W = W, a.bias = bias, a.target = target;
-    a.keep_from = (uint32_t)((double)p_drop * 16777216.0);
-    a.scale = 1.0f / (1.0f - p_drop);
+    a.drop = dropout_of(p_drop);
     a.seed = seed, a.step = step, a.step_dev = step_dev;
     a.gs = grad_scale / (float)n_graphs;
     a.logits = logits, a.grad_pooled = grad_pooled;

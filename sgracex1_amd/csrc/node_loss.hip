@@ -5,32 +5,22 @@
 // F.dropout, self.lin, out[mask], CrossEntropyLoss and their autograd nodes.
 //
 // Three launches: the count M of selected rows (integers: a partial count per workgroup, stored plainly, which the later
-// launches add up; gs = grad_scale / M needs it before any gradient); the main kernel; the reduction of its slices.  In the main kernel a workgroup owns the row blocks b = slice,
-// slice + S, ... of SGX_NODE_LOSS_ROWS rows (S = min(n_blocks, SGX_NODE_LOSS_GRID) whatever the device).  A block none of
-// whose rows is needed (selected, or wanted for the logits output) only zero-fills its grad_H rows: it loads neither H nor
-// W.  Otherwise W is staged in LDS (once per workgroup, at the first block that needs it), the block's x = dropout(H) and
-// dz tiles live in LDS, and every thread keeps its C * P / 256 grad_W accumulators in registers across all the blocks of
-// the slice; the slice's sums go to the workspace with plain stores and the last launch adds the slices in slice order.
+// launches add up; gs = grad_scale / M needs it before any gradient); the main kernel; the reduction of its slices.  In
+// the main kernel a workgroup owns the row blocks b = slice, slice + S, ... of SGX_NODE_LOSS_ROWS rows (S = min(n_blocks,
+// SGX_NODE_LOSS_GRID) whatever the device).  A block none of whose rows is needed only zero-fills its grad_H rows.
+// Otherwise the block's x = dropout(H), logits (tail_device.h: node_block_front, row_cross_entropy) and dz tiles live in
+// LDS, and every thread keeps its C * P / 256 grad_W accumulators in registers across all the blocks of the slice; the
+// slice's sums go to the workspace with plain stores and the last launch adds the slices in slice order.
 // No floating-point atomics: the same bits on every run.
-#include "sgx_internal.h"
+#include "tail_device.h"
+
+using namespace sgx_tail;
 
 namespace {
 
-constexpr int kBlock = 256;
-constexpr int kRows = SGX_NODE_LOSS_ROWS;
-constexpr int kGrid = SGX_NODE_LOSS_GRID;
-constexpr int kMaxP = 1024, kMaxC = 64, kMaxCP = 16384;
 constexpr int kAcc = kMaxCP / kBlock;                       // grad_W accumulators a thread holds at most
 constexpr int kCountPerThread = 16, kCountGrid = 256;
 constexpr size_t kHeader = kCountGrid * sizeof(int64_t);    // the workspace begins with the count's partials
-static_assert(kRows <= 32 && kRows <= kBlock / 4, "a block's selection is one 32-bit word formed by wave 0");
-
-__device__ __forceinline__ uint64_t mix64(uint64_t z)       // the sampler's (sample.hip): the splitmix64 finaliser
-{
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
 
 // parts[b] = the number of rows i < n_sel (= min(n_prefix, n_rows)) with mask[i] != 0 that workgroup b walks; M is their sum
 __global__ __launch_bounds__(kBlock) void node_count_kernel(int64_t n_sel, const uint8_t *__restrict__ mask, int64_t *__restrict__ parts)
@@ -62,17 +52,15 @@ __device__ __forceinline__ int64_t node_count_total(const int64_t *__restrict__ 
 }
 
 struct NodeArgs {
-    int64_t n_rows, n_prefix, n_blocks;
-    int P, C, S, pitch_w, n_parts;
-    const float *H, *W, *bias;
+    NodeRows r;
+    int64_t n_blocks;
+    int S, n_parts;
     const int64_t *target;
-    const uint8_t *mask;
-    uint32_t keep_from;               // floor(p * 2^24): an element is kept iff the top 24 bits of its hash reach it
-    float scale;                      // 1 / (1 - p), formed once in fp32
+    Dropout drop;
     uint64_t seed, step;
     const int64_t *step_dev;
     float grad_scale;
-    float *logits, *grad_H;           // grad_H NULL: evaluation mode, no gradient is formed
+    float *grad_H;                    // NULL: evaluation mode, no gradient is formed
     const int64_t *parts;             // the count kernel's partial counts [n_parts]
     float *slices;                    // [S][C * P + C + 2]: grad_W, grad_bias, the loss sum, the correct count (an int's bits)
 };
@@ -85,8 +73,8 @@ __global__ __launch_bounds__(kBlock) void node_loss_kernel(NodeArgs a)
 #pragma clang fp contract(off)
     extern __shared__ __attribute__((aligned(16))) unsigned char node_lds[];
     const int tid = threadIdx.x;
-    const int P = a.P, C = a.C, CP = C * P, pitch = a.pitch_w;
-    float *const Ws = reinterpret_cast<float *>(node_lds);  // [C][pitch]: an odd pitch, a class per lane reads conflict-free
+    const int P = a.r.P, C = a.r.C, CP = C * P, pitch = a.r.pitch_w;
+    float *const Ws = reinterpret_cast<float *>(node_lds);  // [C][pitch]; the layout is node_loss_lds_bytes's
     float *const xs = Ws + (size_t)C * pitch;               // [kRows][P]
     float *const zs = xs + (size_t)kRows * P;               // [kRows][C]
     float *const dzs = zs + (size_t)kRows * C;              // [kRows][C]
@@ -94,8 +82,7 @@ __global__ __launch_bounds__(kBlock) void node_loss_kernel(NodeArgs a)
     __shared__ int tgt_s[kRows], corr_s[kRows];
     __shared__ unsigned sel_s[2];                           // by the parity of the iteration: a wave may still read the last one
     const bool grads = a.grad_H != nullptr;
-    const uint64_t step_total = a.step + (a.step_dev ? (uint64_t)a.step_dev[0] : 0ull);
-    const uint64_t key = mix64(mix64(a.seed) ^ step_total);
+    const uint64_t key = dropout_key(a.seed, a.step, a.step_dev);
     const float gs = a.grad_scale / (float)node_count_total(a.parts, a.n_parts);    // M == 0: no row is selected, gs is never used
     float acc[NK];
 #pragma unroll
@@ -105,72 +92,26 @@ __global__ __launch_bounds__(kBlock) void node_loss_kernel(NodeArgs a)
     bool w_ready = false;
     int it = 0;
     for (int64_t b = blockIdx.x; b < a.n_blocks; b += a.S, it ^= 1) {
-        const int64_t base = b * kRows;
-        const int rows_here = (int)(a.n_rows - base < kRows ? a.n_rows - base : kRows);
-        if (tid < 64) {
-            const int64_t i = base + tid;
-            const bool sel = tid < rows_here && i < a.n_prefix && (!a.mask || a.mask[i] != 0);
-            const unsigned long long bal = __ballot(sel);
-            if (tid == 0) sel_s[it] = (unsigned)bal;
-        }
-        __syncthreads();
-        const unsigned selbits = sel_s[it];
-        const unsigned needbits = a.logits ? (rows_here >= 32 ? 0xffffffffu : (1u << rows_here) - 1u) : selbits;
-        if (needbits == 0) {                                // nothing to compute: H is not read
+        const NodeBlock blk = node_block_front<true>(a.r, b, it, w_ready, Ws, xs, zs, sel_s, key, a.drop);
+        const int64_t base = blk.base;
+        const int rows_here = blk.rows_here;
+        const unsigned selbits = blk.selbits;
+        if (blk.needbits == 0) {                             // nothing to compute: H is not read
             if (grads)
                 for (int e = tid; e < rows_here * P; e += kBlock) a.grad_H[base * P + e] = 0.0f;
             continue;
         }
-        if (!w_ready) {
-            for (int e = tid; e < CP; e += kBlock) {
-                const int c = e / P, j = e - c * P;
-                Ws[c * pitch + j] = a.W[e];
-            }
-            w_ready = true;
-        }
-        for (int e = tid; e < rows_here * P; e += kBlock) {
-            const int r = e / P;
-            float v = 0.0f;
-            if ((needbits >> r) & 1u) {
-                const int64_t idx = base * P + e;           // i * P + j
-                const uint64_t k = mix64(key ^ (uint64_t)idx);
-                const bool keep = (uint32_t)(k >> 40) >= a.keep_from;
-                v = keep ? a.H[idx] * a.scale : 0.0f;
-            }
-            xs[e] = v;
-        }
-        __syncthreads();
-        for (int e = tid; e < rows_here * C; e += kBlock) {
-            const int r = e / C, c = e - r * C;
-            if (!((needbits >> r) & 1u)) continue;
-            const float *w = Ws + c * pitch, *x = xs + r * P;
-            float s = 0.0f;
-            for (int j = 0; j < P; ++j) s = __builtin_fmaf(w[j], x[j], s);
-            s = s + (a.bias ? a.bias[c] : 0.0f);
-            zs[e] = s;
-            if (a.logits) a.logits[base * C + e] = s;
-        }
-        __syncthreads();
         if (tid < kRows) {
             int tgt = -1;
             if ((selbits >> tid) & 1u) {
                 const float *z = zs + tid * C;
                 const int64_t t = a.target[base + tid];
-                const bool live = t >= 0 && t < C;
-                float m = z[0];
-                for (int c = 1; c < C; ++c) m = z[c] > m ? z[c] : m;
-                float s = 0.0f;
-                for (int c = 0; c < C; ++c) s = s + expf(z[c] - m);
-                const float lse = m + logf(s);
-                lse_s[tid] = lse;
-                int best = 0;
-                float bv = z[0] == z[0] ? z[0] : -INFINITY;
-                for (int c = 1; c < C; ++c)
-                    if (z[c] > bv) bv = z[c], best = c;
-                if (live) {
+                const RowCe ce = row_cross_entropy(z, C, t);
+                lse_s[tid] = ce.lse;
+                if (ce.live) {
                     tgt = (int)t;
-                    loss_sum = loss_sum + (lse - z[t]);
-                    correct += best == tgt;
+                    loss_sum = loss_sum + (ce.lse - z[t]);
+                    correct += ce.best == tgt;
                 }
             }
             tgt_s[tid] = tgt;
@@ -188,12 +129,10 @@ __global__ __launch_bounds__(kBlock) void node_loss_kernel(NodeArgs a)
                 const int r = e / P, j = e - r * P;
                 float v = 0.0f;
                 if ((selbits >> r) & 1u) {
-                    const int64_t idx = base * P + e;
-                    const uint64_t k = mix64(key ^ (uint64_t)idx);
-                    if ((uint32_t)(k >> 40) >= a.keep_from) {
+                    if (dropout_keep(key, base * P + e, a.drop.keep_from)) {
                         float s = 0.0f;
                         for (int c = 0; c < C; ++c) s = __builtin_fmaf(dzs[r * C + c], Ws[c * pitch + j], s);
-                        v = a.scale * s;
+                        v = a.drop.scale * s;
                     }
                 }
                 a.grad_H[base * P + e] = v;
@@ -266,26 +205,13 @@ __global__ __launch_bounds__(kBlock) void node_loss_reduce_kernel(int P, int C, 
     }
 }
 
-bool node_shape_ok(int64_t n_rows, int P, int C)
-{
-    return n_rows >= 1 && P >= 1 && C >= 1 && P <= kMaxP && C <= kMaxC && C * P <= kMaxCP;
-}
-int64_t node_blocks(int64_t n_rows) { return (n_rows + kRows - 1) / kRows; }
-size_t node_lds_bytes(int P, int C) { return ((size_t)C * (P | 1) + (size_t)kRows * P + 2 * (size_t)kRows * C) * sizeof(float); }
-
 template <int NK>
 int node_loss_launch(const NodeArgs &a, hipStream_t s)
 {
-    static bool attr_set_on[64] = {};                 // per instantiation and device (a racing first call sets it twice)
-    int dev = 0;
-    SGX_HIP_CHECK(hipGetDevice(&dev));
-    bool unset = true, &attr_set = dev >= 0 && dev < 64 ? attr_set_on[dev] : unset;
-    if (!attr_set) {
-        SGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&node_loss_kernel<NK>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                          (int)(((size_t)kMaxCP + kMaxC + (size_t)kRows * kMaxP + 2 * (size_t)kRows * kMaxC) * sizeof(float))));
-        attr_set = true;
-    }
-    hipLaunchKernelGGL(node_loss_kernel<NK>, dim3(a.S), dim3(kBlock), node_lds_bytes(a.P, a.C), s, a);
+    static sgx_lds_optin optin;                       // this instantiation's
+    const int rc = sgx_raise_dynamic_lds(&node_loss_kernel<NK>, optin, kNodeLossLdsMax);
+    if (rc != SGX_OK) return rc;
+    hipLaunchKernelGGL(node_loss_kernel<NK>, dim3(a.S), dim3(kBlock), node_loss_lds_bytes(a.r.P, a.r.C), s, a);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }
@@ -295,7 +221,7 @@ int node_loss_launch(const NodeArgs &a, hipStream_t s)
 extern "C" size_t sgx_node_loss_workspace_bytes(int64_t n_rows, int P, int C)
 {
     if (!node_shape_ok(n_rows, P, C)) return 0;
-    const int64_t nb = node_blocks(n_rows);
+    const int64_t nb = row_blocks(n_rows);
     const size_t S = (size_t)(nb < kGrid ? nb : kGrid);
     return kHeader + sgx_align_up(S * ((size_t)C * P + C + 2) * sizeof(float), 256);
 }
@@ -315,13 +241,11 @@ extern "C" int sgx_node_loss(int64_t n_rows, int64_t n_prefix, int P, int C, con
     if ((uintptr_t)workspace % 256) return SGX_ERR_ALIGN;
     hipStream_t s = (hipStream_t)stream;
     NodeArgs a;
-    a.n_rows = n_rows, a.n_prefix = n_prefix, a.n_blocks = node_blocks(n_rows);
-    a.P = P, a.C = C, a.S = (int)(a.n_blocks < kGrid ? a.n_blocks : kGrid), a.pitch_w = P | 1;
-    a.H = H, a.W = W, a.bias = bias, a.target = target, a.mask = mask;
-    a.keep_from = (uint32_t)((double)p_drop * 16777216.0);
-    a.scale = 1.0f / (1.0f - p_drop);
+    a.r = NodeRows{n_rows, n_prefix, P, C, P | 1, H, W, bias, mask, logits};
+    a.n_blocks = row_blocks(n_rows), a.S = (int)(a.n_blocks < kGrid ? a.n_blocks : kGrid);
+    a.target = target, a.drop = dropout_of(p_drop);
     a.seed = seed, a.step = step, a.step_dev = step_dev, a.grad_scale = grad_scale;
-    a.logits = logits, a.grad_H = any ? grad_H : nullptr;
+    a.grad_H = any ? grad_H : nullptr;
     a.parts = (const int64_t *)workspace;
     a.slices = (float *)((char *)workspace + kHeader);
     const int64_t n_sel = n_prefix < n_rows ? n_prefix : n_rows;

@@ -6,9 +6,9 @@
 // Nodes of one graph are contiguous (PyG batching, `batch` sorted), so a graph is a row segment
 // [ptr[g], ptr[g+1]).  One workgroup per graph: the segment mean is accumulated in fp32 with one
 // column per lane (coalesced row reads), then the C output classes are C wave reductions.
-// The training tail behind the pooled means -- dropout, this head (in this kernel's summation order), the loss and
+// The training tail behind the pooled means -- dropout, this head (the one wave_class_logit of tail_device.h), the loss and
 // their gradients -- is head_loss.hip (sgx_head_loss).
-#include "sgx_internal.h"
+#include "tail_device.h"
 
 namespace {
 
@@ -35,11 +35,8 @@ __global__ __launch_bounds__(kBlock) void readout_mean_linear_kernel(
     if (!logits) return;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     for (int c = wave; c < C; c += kBlock / 64) {
-        float s = 0.0f;
-        for (int j = lane; j < F; j += 64) s = __builtin_fmaf(W[(int64_t)c * F + j], mean[j], s);
-#pragma unroll
-        for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) logits[(int64_t)g * C + c] = s + (bias ? bias[c] : 0.0f);
+        const float s = sgx_tail::wave_class_logit(W + (int64_t)c * F, mean, F, lane, bias, c);
+        if (lane == 0) logits[(int64_t)g * C + c] = s;
     }
 }
 

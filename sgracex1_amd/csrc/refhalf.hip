@@ -291,9 +291,11 @@ int launch_dense_rows(int spmm_block, int threads, int n_rows, int M, int n_feat
     kc_rows = kc_rows / 8 * 8;
     const size_t lds = (size_t)kc_rows * PL * sizeof(f16);
     const int rows_per_block = (64 / LPR) * (kBlock / 64);
-    if (lds > 48 * 1024)
-        SGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(&refhalf_dense_rows_kernel<LPR>),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 48 * 1024) {                                        // lds follows from LPR alone
+        static sgx_lds_optin optin;                               // per instantiation
+        const int rc = sgx_raise_dynamic_lds(&refhalf_dense_rows_kernel<LPR>, optin, lds);
+        if (rc != SGX_OK) return rc;
+    }
     int64_t blocks = ((int64_t)n_rows + rows_per_block - 1) / rows_per_block;
     if (M <= kc_rows && blocks > 256 * 8) blocks = 256 * 8;       // W staged once per workgroup, row groups walked in a stride
     hipLaunchKernelGGL((refhalf_dense_rows_kernel<LPR>), dim3((unsigned)blocks), dim3(kBlock), lds, s, n_rows, M, n_feat,

@@ -14,6 +14,7 @@
 // nodes, and the map entries of every node of n_id are put back to the sentinel.
 // The counter block, the scan and the capacity bounds are in sample_device.h, shared with node_batch.hip.
 #include "sample_device.h"
+#include "tail_device.h"
 
 using namespace sgx_sample;
 
@@ -22,12 +23,7 @@ namespace {
 constexpr int kFast = 64;                     // fan-outs up to this keep the subset in registers, one element per lane
 constexpr int32_t kSentinel = 0x7fffffff;
 
-__host__ __device__ inline uint64_t mix64(uint64_t z)
-{
-    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-    z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-    return z ^ (z >> 31);
-}
+using sgx_tail::mix64;                        // the splitmix64 finaliser, which the tail's dropout hashes with too
 
 __device__ inline int draw(uint64_t key, int v, int j)
 {

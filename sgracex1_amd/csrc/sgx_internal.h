@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stddef.h>
 
+#include <atomic>
 #include <type_traits>
 
 #include "sgx.h"
@@ -20,6 +21,27 @@
     } while (0)
 
 typedef _Float16 f16;
+
+// A kernel's opt-in to more dynamic LDS than the default (hipFuncAttributeMaxDynamicSharedMemorySize) belongs to that kernel
+// ON A DEVICE.  sgx_lds_optin remembers per device that it was made: one object per kernel instantiation, a function-local
+// static at the launch site.  sgx_raise_dynamic_lds makes it once per device, before the first launch that needs `bytes`
+// or fewer; a device outside the table is opted in on every call (two threads racing on a first call both set it: the
+// same value).  SGX_ERR_HIP when the runtime refuses.
+struct sgx_lds_optin {
+    static constexpr int kDevices = 64;
+    std::atomic<bool> done[kDevices];
+};
+template <typename Kernel>
+int sgx_raise_dynamic_lds(Kernel kernel, sgx_lds_optin &optin, size_t bytes)
+{
+    int dev = 0;
+    SGX_HIP_CHECK(hipGetDevice(&dev));
+    const bool known = dev >= 0 && dev < sgx_lds_optin::kDevices;
+    if (known && optin.done[dev].load(std::memory_order_acquire)) return SGX_OK;
+    SGX_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+    if (known) optin.done[dev].store(true, std::memory_order_release);
+    return SGX_OK;
+}
 
 // Tuning / test overrides: the SGX_* environment variables, read ONCE per process -- not per call: a getenv
 // walks the whole environment, and half a dozen of them per layer were a measurable share of a 20-microsecond layer

@@ -52,9 +52,9 @@ int run_gat_fused(const sgx_gat_stack_desc *d, hipStream_t s)
 {
     size_t lds;
     const GatStackArgs g = gat_stack_args(d, &lds);
-    static bool attr_f16 = false, attr_f32 = false;       // per kernel: its LDS limit is raised once
-    return d->dtype == SGX_F16 ? launch_stack_kernel(gat_stack_kernel<f16>, &attr_f16, g, d->plan->n_groups, lds, s)
-                               : launch_stack_kernel(gat_stack_kernel<float>, &attr_f32, g, d->plan->n_groups, lds, s);
+    static sgx_lds_optin optin_f16, optin_f32;            // per kernel
+    return d->dtype == SGX_F16 ? launch_stack_kernel(gat_stack_kernel<f16>, optin_f16, g, d->plan->n_groups, lds, s)
+                               : launch_stack_kernel(gat_stack_kernel<float>, optin_f32, g, d->plan->n_groups, lds, s);
 }
 
 }  // namespace

@@ -6,9 +6,9 @@ namespace {
 
 int launch_plain_backward(const sgx_gat_stack_grad_desc *d, const GatGradArgs &a, int grid, size_t lds, hipStream_t s)
 {
-    static std::atomic<bool> attr_f16[kGatMaxDevices], attr_f32[kGatMaxDevices];   // per instantiation and device
-    return d->dtype == SGX_F16 ? launch_gat_backward(gat_stack_backward_kernel<f16>, attr_f16, a, grid, lds, s)
-                               : launch_gat_backward(gat_stack_backward_kernel<float>, attr_f32, a, grid, lds, s);
+    static sgx_lds_optin optin_f16, optin_f32;            // per instantiation
+    return d->dtype == SGX_F16 ? launch_gat_backward(gat_stack_backward_kernel<f16>, optin_f16, a, grid, lds, s)
+                               : launch_gat_backward(gat_stack_backward_kernel<float>, optin_f32, a, grid, lds, s);
 }
 
 }  // namespace

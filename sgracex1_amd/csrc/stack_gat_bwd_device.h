@@ -13,7 +13,6 @@
 // from the unquantised operands over the same tile, so that everything a gradient multiplies with is unquantised
 // (FPYNQ_GAT.backward).  GCN layers never see the quantiser.
 #pragma once
-#include <atomic>
 #include "stack_device.h"
 #include "gat_device.h"
 
@@ -25,7 +24,6 @@ constexpr int kGatScoreLanes = 8;         // lanes per row of the score and stat
 constexpr float kGatLog2e = 1.44269504088896340736f;
 constexpr size_t kGatLdsLimit = 160 * 1024;   // what a workgroup on gfx950 may declare
 constexpr int kGatRowFloats = 6;          // s1, s2, m, 1 / l, rs, g1
-constexpr int kGatMaxDevices = 64;        // devices whose raised LDS limit is remembered
 
 struct GatGradArgs {
     int n_layers, gemm0, pitch_t, pitch_f, rows, n_groups, slice;
@@ -644,22 +642,15 @@ size_t gat_grad_workspace(const Desc *d)
     return sgx_align_up((size_t)gat_grad_grid(d->plan) * gat_grad_slice(d, nullptr, nullptr) * sizeof(float), 256);
 }
 
-// kernel: gat_stack_backward_kernel<T> or quant_stack_backward_kernel<float>; attr_set: that kernel's, [kGatMaxDevices];
-// extra: what follows GatGradArgs in its arguments
+// kernel: gat_stack_backward_kernel<T> or quant_stack_backward_kernel<float>; optin: that kernel's; extra: what follows
+// GatGradArgs in its arguments
 template <typename Kernel, typename... Extra>
-int launch_gat_backward(Kernel kernel, std::atomic<bool> *attr_set, const GatGradArgs &a, int grid, size_t lds, hipStream_t s,
+int launch_gat_backward(Kernel kernel, sgx_lds_optin &optin, const GatGradArgs &a, int grid, size_t lds, hipStream_t s,
                         const Extra &...extra)
 {
     if (lds > (size_t)kStackLds) {
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess) return SGX_ERR_HIP;
-        const bool known = dev >= 0 && dev < kGatMaxDevices;
-        if (!known || !attr_set[dev].load(std::memory_order_acquire)) {  // (setting it twice is harmless)
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)kGatLdsLimit) != hipSuccess)
-                return SGX_ERR_HIP;
-            if (known) attr_set[dev].store(true, std::memory_order_release);
-        }
+        const int rc = sgx_raise_dynamic_lds(kernel, optin, kGatLdsLimit);
+        if (rc != SGX_OK) return rc;
     }
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(kBlock), lds, s, a, extra...);
     SGX_LAUNCH_CHECK();

@@ -175,17 +175,16 @@ __global__ __launch_bounds__(kBlock, 2) void quant_stack_kernel(GatStackArgs g, 
     gat_stack_body<T>(g, q);
 }
 
-// the launch; kernel: gat_stack_kernel<T> or quant_stack_kernel, extra: what follows GatStackArgs in its arguments
+// the launch; kernel: gat_stack_kernel<T> or quant_stack_kernel, optin: that kernel's, extra: what follows GatStackArgs in
+// its arguments
 template <typename Kernel, typename... Extra>
-int launch_stack_kernel(Kernel kernel, bool *attr_set, const GatStackArgs &g, int n_groups, size_t lds, hipStream_t s,
+int launch_stack_kernel(Kernel kernel, sgx_lds_optin &optin, const GatStackArgs &g, int n_groups, size_t lds, hipStream_t s,
                         const Extra &...extra)
 {
-    if (lds > (size_t)kStackLds && !*attr_set) {
+    if (lds > (size_t)kStackLds) {
         // tiles that fill 64 KiB (fp32 at width 252: 32 rows of 2 KiB) plus the score arrays
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                kStackLds + (int)score_bytes(SGX_STACK_ROWS_CAP)) != hipSuccess)
-            return SGX_ERR_HIP;
-        *attr_set = true;
+        const int rc = sgx_raise_dynamic_lds(kernel, optin, kStackLds + score_bytes(SGX_STACK_ROWS_CAP));
+        if (rc != SGX_OK) return rc;
     }
     hipLaunchKernelGGL(kernel, dim3(n_groups), dim3(kBlock), lds, s, g, extra...);
     SGX_LAUNCH_CHECK();

@@ -164,8 +164,8 @@ int run_quant_fused(const sgx_quant_stack_desc *d, hipStream_t s)
         sq.ep_d[l] = sgx_no_epilogue();
         sq.ep_d[l].out_scale = q->deq_factor;
     }
-    static bool attr_set = false;
-    return launch_stack_kernel(quant_stack_kernel<float>, &attr_set, g, d->plan->n_groups, lds, s, sq);
+    static sgx_lds_optin optin;
+    return launch_stack_kernel(quant_stack_kernel<float>, optin, g, d->plan->n_groups, lds, s, sq);
 }
 
 }  // namespace

@@ -62,7 +62,7 @@ sgx_gat_stack_grad_desc plain_grad_desc(const sgx_quant_stack_grad_desc *d)
 
 int launch_quant_backward(const sgx_quant_stack_grad_desc *d, const GatGradArgs &a, int grid, size_t lds, hipStream_t s)
 {
-    static std::atomic<bool> attr_set[kGatMaxDevices];                   // per device
+    static sgx_lds_optin optin;
     StackQuantGrad sq = {};
     for (int l = 0; l < d->n_layers; ++l) {
         const sgx_quant *q = d->layer[l].quant;
@@ -77,7 +77,7 @@ int launch_quant_backward(const sgx_quant_stack_grad_desc *d, const GatGradArgs 
         sq.ep_d[l] = sgx_no_epilogue();                                   // (deq_factor reaches no gradient)
     }
     sq.val_q = static_cast<const float *>(d->values_adj_q);
-    return launch_gat_backward(quant_stack_backward_kernel<float>, attr_set, a, grid, lds, s, sq);
+    return launch_gat_backward(quant_stack_backward_kernel<float>, optin, a, grid, lds, s, sq);
 }
 
 }  // namespace

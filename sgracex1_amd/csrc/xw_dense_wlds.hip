@@ -291,13 +291,9 @@ int launch_wlds(const WldsArm &arm, int n_rows, int M, int P, const void *X, int
                 int64_t ldh, int relu, hipStream_t s)
 {
     auto kernel = xw_dense_wlds_f16_kernel<NT>;
-    static bool attr_set = false;                     // per instantiation
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWldsLds) !=
-            hipSuccess)
-            return SGX_ERR_HIP;
-        attr_set = true;
-    }
+    static sgx_lds_optin optin;                       // per instantiation
+    const int rc = sgx_raise_dynamic_lds(kernel, optin, kWldsLds);
+    if (rc != SGX_OK) return rc;
     hipLaunchKernelGGL(kernel, dim3(arm.grid), dim3(kWldsThreads), arm.lds_bytes, s, n_rows, M, P, (const f16 *)X, ldx, (const f16 *)Wt,
                        ldw, (f16 *)H, ldh, relu, arm.n_cb, arm.LP, arm.KS);
     SGX_LAUNCH_CHECK();
@@ -490,13 +486,9 @@ int launch_wlds_f32(const Wlds32Arm &arm, int n_rows, int M, int P, const void *
 {
     auto kernel = xw_dense_wlds_f32_kernel<KB, NT>;
     const size_t lds_bytes = (size_t)16 * NT * (16 * KB + 4) * 4;
-    static bool attr_set = false;                     // per instantiation
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)kWldsLds) !=
-            hipSuccess)
-            return SGX_ERR_HIP;
-        attr_set = true;
-    }
+    static sgx_lds_optin optin;                       // per instantiation
+    const int rc = sgx_raise_dynamic_lds(kernel, optin, kWldsLds);
+    if (rc != SGX_OK) return rc;
     hipLaunchKernelGGL(kernel, dim3((unsigned)arm.grid), dim3(kW32Threads), lds_bytes, s, n_rows, M, P, (const float *)X, ldx,
                        (const float *)Wt, ldw, (float *)H, ldh, n_out, ha, ep, relu);
     SGX_LAUNCH_CHECK();

@@ -521,13 +521,9 @@ int launch_lds_impl(const LdsForm &f, int n_work, int n_feat, int m_fea, const i
                     hipStream_t stream)
 {
     auto kernel = xw_sparse_lds_kernel<T, VEC, LPR, FULL>;
-    static bool attr_set = false;                     // per instantiation
-    if (!attr_set) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)kLdsBudget) != hipSuccess)
-            return SGX_ERR_HIP;
-        attr_set = true;
-    }
+    static sgx_lds_optin optin;                       // per instantiation
+    const int rc = sgx_raise_dynamic_lds(kernel, optin, kLdsBudget);
+    if (rc != SGX_OK) return rc;
     hipLaunchKernelGGL(kernel, dim3(f.grid), dim3(kThreads), f.lds_bytes, stream, n_work, n_feat, m_fea, rowptr, col,
                        (const T *)val, (const T *)W, ldw, f.w_vec, (T *)H, ldh, f.n_split, (unsigned)(nnz * 4), win_order, ep);
     SGX_LAUNCH_CHECK();

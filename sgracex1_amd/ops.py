@@ -2447,6 +2447,30 @@ def _u64(v):
     return int(v) & (2 ** 64 - 1)
 
 
+def _tail_workspace(device, nbytes):
+    """(pointer, bytes) of a tail entry's workspace of `nbytes`, (None, 0) where it asks for none."""
+    ws = _workspace(device, nbytes) if nbytes else None
+    return _ptr(ws), 0 if ws is None else ws.numel()
+
+
+def _row_selection(mask, n_prefix, n):
+    """node_loss's and node_eval's selection, normalised -> (mask as uint8 bytes or None, n_prefix as an int, default n)."""
+    if mask is not None:
+        _dev(mask, "mask")
+        if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != (n,):
+            raise TypeError("mask must be a bool or uint8 tensor [n]")
+        if mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)
+    return mask, n if n_prefix is None else int(n_prefix)
+
+
+def _eval_accumulators(fn, totals, loss_sum):
+    """The check of the device accumulators head_eval and node_eval add into."""
+    _dev(totals, "totals"), _dev(loss_sum, "loss_sum")
+    if totals.dtype != torch.int64 or totals.numel() != 2 or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
+        raise TypeError(f"{fn} accumulates into totals int64 [2] and loss_sum float64 [1]")
+
+
 def head_loss(pooled, weight, bias, target, p=0.0, seed=0, step=0, step_dev=None, grad_scale=1.0, want_logits=False):
     """Dropout(p), the Linear head and the mean cross entropy with every gradient, in one call (sgx_head_loss; the rule is
     in include/sgx.h, "the loss head").  pooled [G, P] fp32, weight [C, P] fp32, bias [C] fp32 or None, target [G] int64;
@@ -2456,11 +2480,10 @@ def head_loss(pooled, weight, bias, target, p=0.0, seed=0, step=0, step_dev=None
     pooled, w, b = _loss_operands("head_loss", "pooled", pooled, weight, bias, target, step_dev)
     (G, P), C = pooled.shape, w.shape[0]
     loss, grad_pooled, grad_W, grad_b, logits = _loss_outputs(pooled, w, b, True, want_logits)
-    nbytes = lib.sgx_head_loss_workspace_bytes(G, P, C)
-    ws = _workspace(pooled.device, nbytes) if nbytes else None
+    ws = _tail_workspace(pooled.device, lib.sgx_head_loss_workspace_bytes(G, P, C))
     check(lib.sgx_head_loss(G, P, C, _ptr(pooled), _ptr(w), _ptr(b), _ptr(target), float(p), _u64(seed), _u64(step),
                             _ptr(step_dev), float(grad_scale), _ptr(loss), _ptr(logits), _ptr(grad_pooled), _ptr(grad_W),
-                            _ptr(grad_b), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+                            _ptr(grad_b), *ws, _stream()),
           "sgx_head_loss")
     out = (loss, grad_pooled, grad_W, grad_b)
     return out + (logits,) if want_logits else out
@@ -2603,20 +2626,13 @@ def node_loss(H, weight, bias, target, mask=None, n_prefix=None, p=0.0, seed=0, 
     [n, C] of every row with want_logits.  Never synchronises."""
     H, w, b = _loss_operands("node_loss", "H", H, weight, bias, target, step_dev)
     (n, P), C = H.shape, w.shape[0]
-    if mask is not None:
-        _dev(mask, "mask")
-        if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != (n,):
-            raise TypeError("mask must be a bool or uint8 tensor [n]")
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-    n_prefix = n if n_prefix is None else int(n_prefix)
+    mask, n_prefix = _row_selection(mask, n_prefix, n)
     loss, grad_H, grad_W, grad_b, logits = _loss_outputs(H, w, b, grads, want_logits)
     counts = torch.empty(2, dtype=torch.int64, device=H.device) if want_counts else None
-    nbytes = lib.sgx_node_loss_workspace_bytes(n, P, C)
-    ws = _workspace(H.device, nbytes) if nbytes else None
+    ws = _tail_workspace(H.device, lib.sgx_node_loss_workspace_bytes(n, P, C))
     check(lib.sgx_node_loss(n, n_prefix, P, C, _ptr(H), _ptr(w), _ptr(b), _ptr(target), _ptr(mask), float(p), _u64(seed),
                             _u64(step), _ptr(step_dev), float(grad_scale), _ptr(loss), _ptr(counts), _ptr(logits), _ptr(grad_H),
-                            _ptr(grad_W), _ptr(grad_b), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+                            _ptr(grad_W), _ptr(grad_b), *ws, _stream()),
           "sgx_node_loss")
     out = (loss, grad_H, grad_W, grad_b)
     if want_counts:
@@ -2652,14 +2668,11 @@ def head_eval(pooled, weight, bias, target, n_real=None, totals=None, loss_sum=N
         totals = torch.zeros(2, dtype=torch.int64, device=pooled.device)
     if loss_sum is None:
         loss_sum = torch.zeros(1, dtype=torch.float64, device=pooled.device)
-    _dev(totals, "totals"), _dev(loss_sum, "loss_sum")
-    if totals.dtype != torch.int64 or totals.numel() != 2 or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
-        raise TypeError("head_eval accumulates into totals int64 [2] and loss_sum float64 [1]")
+    _eval_accumulators("head_eval", totals, loss_sum)
     logits = torch.empty((G, C), dtype=torch.float32, device=pooled.device) if want_logits else None
-    nbytes = lib.sgx_head_eval_workspace_bytes(G, P, C)
-    ws = _workspace(pooled.device, nbytes) if nbytes else None
+    ws = _tail_workspace(pooled.device, lib.sgx_head_eval_workspace_bytes(G, P, C))
     check(lib.sgx_head_eval(G, n_real, P, C, _ptr(pooled), _ptr(w), _ptr(b), _ptr(target), _ptr(totals), _ptr(loss_sum),
-                            _ptr(logits), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+                            _ptr(logits), *ws, _stream()),
           "sgx_head_eval")
     return (totals, loss_sum, logits) if want_logits else (totals, loss_sum)
 
@@ -2675,22 +2688,13 @@ def node_eval(H, weight, bias, target, totals, loss_sum, mask=None, n_prefix=Non
     and the logits [n, C] of every row behind them with want_logits.  Never synchronises."""
     H, w, b = _loss_operands("node_eval", "H", H, weight, bias, target, None)
     (n, P), C = H.shape, w.shape[0]
-    if mask is not None:
-        _dev(mask, "mask")
-        if mask.dtype not in (torch.bool, torch.uint8) or mask.shape != (n,):
-            raise TypeError("mask must be a bool or uint8 tensor [n]")
-        if mask.dtype == torch.bool:
-            mask = mask.view(torch.uint8)
-    n_prefix = n if n_prefix is None else int(n_prefix)
+    mask, n_prefix = _row_selection(mask, n_prefix, n)
     if n_prefix < 0:
         raise ValueError(f"node_eval: n_prefix = {n_prefix} is negative")
-    _dev(totals, "totals"), _dev(loss_sum, "loss_sum")
-    if totals.dtype != torch.int64 or totals.numel() != 2 or loss_sum.dtype != torch.float64 or loss_sum.numel() != 1:
-        raise TypeError("node_eval accumulates into totals int64 [2] and loss_sum float64 [1]")
+    _eval_accumulators("node_eval", totals, loss_sum)
     logits = torch.empty((n, C), dtype=torch.float32, device=H.device) if want_logits else None
-    nbytes = lib.sgx_node_eval_workspace_bytes(n, n_prefix, P, C)
-    ws = _workspace(H.device, nbytes) if nbytes else None
+    ws = _tail_workspace(H.device, lib.sgx_node_eval_workspace_bytes(n, n_prefix, P, C))
     check(lib.sgx_node_eval(n, n_prefix, P, C, _ptr(H), _ptr(w), _ptr(b), _ptr(target), _ptr(mask), _ptr(totals), _ptr(loss_sum),
-                            _ptr(logits), _ptr(ws), 0 if ws is None else ws.numel(), _stream()),
+                            _ptr(logits), *ws, _stream()),
           "sgx_node_eval")
     return (totals, loss_sum, logits) if want_logits else (totals, loss_sum)

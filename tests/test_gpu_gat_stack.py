@@ -258,6 +258,18 @@ def test_fp32_tiles_that_fill_64_kib(monkeypatch):
     check_case(c, "f32")
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
+def test_fp32_tiles_that_fill_64_kib_on_a_second_device_of_the_process(monkeypatch):
+    """The same launch on device 0 and then on device 1: the kernel's opt-in to more than 64 KiB of LDS is per device."""
+    for k in (0, 1):
+        with torch.cuda.device(k):
+            no_workspace(monkeypatch)
+            c = run_case("f32", 64, (252, 64), (1, 1), [True, False], False, seed=9)
+            assert c["plan"].fits and c["plan"].rows == 32 and c["outs"][0].device.index == k
+            monkeypatch.undo()
+            check_case(c, "f32")
+
+
 # ---- 6. model and capture --------------------------------------------------------------------------------------------------
 def _mutag_batch(n=48):
     from sgracex1_amd import pyg_lite as G

@@ -152,6 +152,28 @@ def test_node_loss_captured_once_and_replayed_equals_eager_calls():
     assert not same_bits(eager[0][1], eager[1][1])
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
+def test_more_than_64_kib_of_lds_on_a_second_device_of_the_process():
+    """The opt-in to more dynamic LDS belongs to a kernel on a device: at n = 17, P = 1024, C = 16 both node kernels ask
+    for more than 64 KiB, on device 0 and then on device 1 of the one process, each against its own device's reference."""
+    import _node_eval_ref as E
+    from sgracex1_amd import ops
+    n, P, C = R.ROWS + 1, 1024, 16
+    c, e = R.make_case(n, P, C, select="mask", seed=31), E.make_case(n, P, C, mask="sparse", seed=31)
+    (M, hits), loss, bound, z32, _ = E.eval_ref(e["H"], e["W"], e["bias"], e["target"], e["mask"], n)
+    for k in (0, 1):
+        with torch.cuda.device(k):
+            _check(c)
+            operands = [None if a is None else torch.from_numpy(a).to(f"cuda:{k}") for a in (e["H"], e["W"], e["bias"], e["target"], e["mask"])]
+            totals = torch.zeros(2, dtype=torch.int64, device=f"cuda:{k}")
+            loss_sum = torch.zeros(1, dtype=torch.float64, device=f"cuda:{k}")
+            _, _, logits = ops.node_eval(*operands[:4], totals, loss_sum, mask=operands[4], n_prefix=n, want_logits=True)
+            torch.cuda.synchronize()
+            assert logits.device.index == k and totals.tolist() == [M, hits]
+            assert abs(float(loss_sum.cpu()[0]) - loss) <= bound
+            assert np.array_equal(logits.cpu().numpy().view(np.int32), z32.view(np.int32))
+
+
 def test_node_loss_refuses_what_the_header_refuses():
     from sgracex1_amd import _lib, ops
     c = R.make_case(R.ROWS + 1, 257, 64, select="mask")

@@ -268,6 +268,22 @@ def test_gat_layers_inside_the_bound(case, path, monkeypatch):
     check_stages(c, RELUS[:n], got, gat)
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two devices")
+def test_tiles_that_fill_64_kib_on_a_second_device_of_the_process(monkeypatch):
+    """Width 252 (the last GAT case) on device 0 and then on device 1: the kernel's opt-in to more than 64 KiB of LDS is per
+    device."""
+    nbits, m_in, widths, gat, sparse = GAT[3]
+    assert max(widths) == 252
+    for k in (0, 1):
+        with torch.cuda.device(k):
+            c = build_case(nbits, m_in, widths, gat, sparse, seed=23)
+            no_workspace(monkeypatch)
+            got = run(c, RELUS[:2])
+            assert got["plan"].fits
+            monkeypatch.undo()
+            check_stages(c, RELUS[:2], got, gat)
+
+
 # ---- 3. adjacency quantised in flight against quantised beforehand ----------------------------------------------------
 @pytest.mark.parametrize("nbits,gat", [(8, (1, 0)), (4, (0, 1))])
 def test_adjacency_quantised_in_flight_and_beforehand(nbits, gat, monkeypatch):
