@@ -45,7 +45,9 @@ reaches test accuracy 0.76 at epoch 34 (README.md:126: "0.76 accuracy around epo
         Adam -- serves every batch of every epoch (StackTrainer.capture_loader); the short last batch runs eagerly.
         With --trainer the accuracies are counted on the device (StackTrainer.evaluate) and read back in one transfer per
         epoch; with --replay --batch-size N the evaluation replays as well (StackTrainer.capture_eval_loader over
-        unshuffled padded loaders of the train and test sets).  Without --trainer nothing changes
+        unshuffled padded loaders of the train and test sets).  With --model gat --qbits 8 the padded batches carry the
+        quantised adjacencies (GraphLoader(quant=, pad=True, pad_quant=True)) and the quantised step and passes replay.
+        Without --trainer nothing changes
 """
 import argparse
 import json
@@ -86,8 +88,8 @@ def main():
         ap.error("--trainer runs the fused training route: --acc 1 --layer-count 2 --train-stack")
     if args.replay and not args.trainer:
         ap.error("--replay replays the trainer's step: --trainer")
-    if args.replay and args.batch_size > 0 and (args.host_loader or args.plain_loader or args.qbits != 32):
-        ap.error("--replay with --batch-size > 0 takes the device loader's prepared, unquantised batches")
+    if args.replay and args.batch_size > 0 and (args.host_loader or args.plain_loader):
+        ap.error("--replay with --batch-size > 0 takes the device loader's prepared batches")
     if args.host_loader and args.batch_size <= 0:
         ap.error("--host-loader needs --batch-size > 0")
     dev = torch.device("cuda")
@@ -111,10 +113,11 @@ def main():
         torch.manual_seed(12345)
         gat = sgrace.GAT_POOL_PYNQ(7, 64, 2, train_stack=args.train_stack).to(dev)   # demo_sgrace.py:137-190
         if args.batch_size > 0 and not args.host_loader and not args.plain_loader:
-            # the batches layer-ready: normalised (and quantised) once per set, gathered per batch by the collation launch
+            # the batches layer-ready: normalised (and quantised) once per set, gathered per batch by the collation launch;
+            # with --replay padded, the quantised adjacencies with them (pad_quant)
+            quantised = dict(quant=sgrace.quant_constants, pad_quant=args.replay and sgrace.quant_constants is not None)
             loader = G.GraphLoader(loader.graphs, batch_size=args.batch_size, shuffle=True, generator=gen, device=dev,
-                                   dtypes=(sgrace._torch_dtype(),), prepare="sym_norm2", quant=sgrace.quant_constants,
-                                   pad=args.replay)
+                                   dtypes=(sgrace._torch_dtype(),), prepare="sym_norm2", pad=args.replay, **quantised)
         model = lambda _acc, x, edge_index, batch: gat(x, edge_index, batch)
         model.train, model.eval, model.parameters = gat.train, gat.eval, gat.parameters
     else:
@@ -137,7 +140,7 @@ def main():
     eval_passes = None
     if replay_epoch is not None:
         # the accuracy pass replayed too: one recorded evaluation per set over unshuffled padded loaders
-        prepared = dict(dtypes=loader.dtypes, prepare=loader.prepare) if args.model == "gat" else {}
+        prepared = dict(dtypes=loader.dtypes, prepare=loader.prepare, **quantised) if args.model == "gat" else {}
         eval_passes = [trainer.capture_eval_loader(G.GraphLoader(gs, batch_size=args.batch_size, shuffle=False, device=dev,
                                                                  pad=True, **prepared))
                        for gs in (loader.graphs, graphs[50:100])]

@@ -889,7 +889,8 @@ int64_t sgx_batch_plan_export_groups(const sgx_batch_plan *plan, int32_t *dst, i
  *                   0: a GAT row is never dead.  Every filler row's D is 0 in every layer and its gradient is 0;
  *   tails           the entries past the live count up to the capacity are 0, and edge_index[:, E:E_cap] = -1 (the
  *                   padded edge_index is a key, not an edge list, past E).
- * An extra without a pattern of its own (values only: the quantised adjacencies) is refused: SGX_ERR_UNSUPPORTED.
+ * An extra without a pattern of its own (values only: the quantised adjacencies) is refused: SGX_ERR_UNSUPPORTED
+ * (sgx_collate_graphs_padded_quant below takes them).
  *
  * sgx_collate_graphs_padded(set, b, extras, n_extras, pad, stream): b->n_graphs = B, and the totals of b and the nnz
  * of the extras are not read -- pad's capacities take their place, as the sizes of the output arrays (graph_ptr
@@ -914,6 +915,57 @@ typedef struct sgx_collate_pad {
 
 int sgx_collate_graphs_padded(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
                               int n_extras, const sgx_collate_pad *pad, void *stream);
+
+/* Padded batches ready for the QUANTISED layers.  Added without a version bump (SGX_VERSION stays 110): the two
+ * declarations below are new, sgx_collate_graphs_padded and everything above it are unchanged (it goes on refusing a
+ * values-only extra).
+ *
+ * sgx_collate_graphs_padded_quant(set, b, extras, n_extras, pad, q, stream) is sgx_collate_graphs_padded -- the same one
+ * launch, the same bits in every array that call writes -- with the values-only extras admitted.  An extra k without a
+ * pattern of its own (rowPtr_out == columnIndex_out == NULL: a quantised adjacency) shares the pattern of the first
+ * pattern-bearing extra met going back from it (the normalised adjacency) and must have that extra's capacity.  Its live entries and
+ * row bytes are gathered as sgx_collate_graphs_extras gathers them, so the live prefix holds that call's bits.  Behind
+ * them, with a the extra's live entry count, read on the device from its entry_off[B] and clamped to the capacity as
+ * every live total is, and fq_k the unsigned-grid device function sgx_fake_quantize(0, qbits[k], inv_scale_adj[k],
+ * zero_adj[k]) runs (csrc/quant_device.h, the one quantiser), evaluated in the fill workgroups:
+ *   values_out[SGX_F32][a + j] = fq_k(1) for the P = N - n diagonal entries of the filler rows (as far as the capacity
+ *                                goes), fq_k(0) from there up to the capacity (values_out[SGX_F16], where given, holds the
+ *                                same two numbers rounded to fp16);
+ *   dead_row_out[n .. N)       = 0.
+ * The call requires, for every values-only extra, fq_k(1) > 0 and fq_k(0) == 0, evaluated on the host by the same
+ * function before anything is launched (the check sgx_node_batch_sample_padded_quant makes).  Then a filler graph is as
+ * inert under the quantised layers (sgx_quant_stack_forward, sgx_quant_stack_backward) as under the plain ones:
+ *   - its feature rows are empty, so X_q . W_q has no term, and the re-quantisation of H (a shift, a clip, a decimal
+ *     rounding) leaves a zero row 0;
+ *   - its single diagonal entry is live under the mask values_q > 0 and takes softmax weight 1 on a zero H row -- in a GCN
+ *     layer the weight fq_k(1) on a zero H row -- so D = 0 after ReLU and deq_factor;
+ *   - the next layer reads that D row on its unsigned FEATURE grid (inv_scale_fea, zero_fea of the next layer's
+ *     sgx_quant): it stays 0 exactly when that grid maps 0 to 0.  This call does not see those constants; the caller
+ *     checks them (pyg_lite.GraphLoader(pad_quant=True) refuses a constant set whose feature grid moves 0) and does not
+ *     pad such a set;
+ *   - it pools to 0, the loss takes the first B rows of the pooled means, so its grad_pooled row is 0; the backward
+ *     forms the same S (weight 1 on the diagonal), every product with its zero rows of X_l, H and g is 0, and no entry
+ *     joins it to a live row: its aggregated gradients are 0 and it adds nothing to any weight or attention gradient.
+ * A live row may still be dead under the quantised mask alone (an entry may round to 0); the fused attention route
+ * declines such a batch, and the loaders do not pad it.
+ *
+ * The contracts of sgx_collate_graphs_padded stay: one launch of the same shape (a wavefront per graph, fill workgroups
+ * with 16-byte stores over the constant ranges), no allocation, no synchronisation, no atomics, plain vector stores,
+ * capturable, the same bits on every run, and whatever the offset arrays hold nothing is written outside [0, capacity)
+ * of any array.  q is read only for values-only extras (entry k belongs to extras[k]) and may be NULL without one.
+ *
+ * Argument errors, before anything is launched: n_extras outside 0 .. SGX_COLLATE_MAX_EXTRAS: SGX_ERR_SHAPE; b, pad, or
+ * extras with n_extras > 0, NULL: SGX_ERR_NULL; then per values-only extra, in order: q NULL: SGX_ERR_NULL; no
+ * pattern-bearing extra before it, or a capacity other than that extra's: SGX_ERR_SHAPE; qbits outside {8, 4, 2, 1}:
+ * SGX_ERR_UNSUPPORTED; fq_k(1) <= 0 (or not a number) or fq_k(0) != 0: SGX_ERR_UNSUPPORTED; then everything
+ * sgx_collate_graphs_padded returns. */
+typedef struct sgx_collate_pad_quant {
+    int32_t qbits[SGX_COLLATE_MAX_EXTRAS];         /* 8, 4, 2, 1 */
+    float   inv_scale_adj[SGX_COLLATE_MAX_EXTRAS], zero_adj[SGX_COLLATE_MAX_EXTRAS];
+} sgx_collate_pad_quant;
+
+int sgx_collate_graphs_padded_quant(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
+                                    int n_extras, const sgx_collate_pad *pad, const sgx_collate_pad_quant *q, void *stream);
 
 /* The group table of a plan from sgx_batch_plan_create_known written again from `graph_ptr` -- the same n_rows, n_graphs
  * and max_graph, other contents, as a padded batch's buffers hold after the next collation: one launch with the plan's own

@@ -1,5 +1,5 @@
 // Shuffled graph mini-batches collated on the device (sgx_collate_graphs, sgx_collate_graphs_extras,
-// sgx_collate_graphs_padded, include/sgx.h).
+// sgx_collate_graphs_padded, sgx_collate_graphs_padded_quant, include/sgx.h).
 //
 // The dataset lives on the device in dataset order (sgx_graph_set); a batch is a list of graph ids plus the exclusive
 // offsets of every graph's rows, stored edges, adjacency entries and feature entries inside the batch, which the host
@@ -14,6 +14,9 @@
 // the last graph; the others (fill blocks) read the live totals from the offset arrays' last entries and write what lies
 // behind them -- the filler rows in their trailing filler graphs, those end entries, and the tails up to every capacity --
 // striding over the ranges together, 16 bytes a lane where the value is constant.  The two kinds write disjoint ranges.
+// sgx_collate_graphs_padded_quant is that launch with the values-only extras (the quantised adjacencies) admitted: behind
+// their live entries the fill blocks write the filler rows' 1 and the spare 0 as the extra's grid holds them.
+#include "quant_device.h"
 #include "sgx_device.h"
 
 namespace {
@@ -184,6 +187,7 @@ struct CollatePadArgs {
     CollateExtraArgs c;
     int G, R_f;                  // graphs with the fillers, rows of a full filler graph
     unsigned graph_blocks;       // blocks [0, graph_blocks) gather the graphs, the others write the filler rows and the tails
+    sgx_collate_pad_quant q;     // the grid of every values-only extra (sgx_collate_graphs_padded_quant; unread otherwise)
 };
 
 constexpr int kFillThreads = kWave * kWavesPerBlock;
@@ -258,7 +262,18 @@ __device__ __forceinline__ void fill_padding(const CollatePadArgs &a, int64_t t,
     fill_range(static_cast<float *>(b.values_fea[SGX_F32]), nf, b.nnz_fea, 0.0f, t, nt);
     for (int k = 0; k < a.c.n_extras; ++k) {
         const sgx_collate_extra &x = a.c.x[k];
-        if (!x.rowPtr_out) continue;
+        if (!x.rowPtr_out) {
+            // values over the pattern of an extra before it: the filler rows' diagonal 1 and the spare 0 on this extra's grid
+            const float one = sgx_quantizer::fake_quantize_value(0, a.q.qbits[k], a.q.inv_scale_adj[k], a.q.zero_adj[k], 1.0f);
+            const float zero = sgx_quantizer::fake_quantize_value(0, a.q.qbits[k], a.q.inv_scale_adj[k], a.q.zero_adj[k], 0.0f);
+            const int64_t live = clamp_to(x.entry_off[B], x.nnz), diag = live + P < x.nnz ? live + P : x.nnz;
+            fill_range(static_cast<f16 *>(x.values_out[SGX_F16]), live, diag, (f16)one, t, nt);
+            fill_range(static_cast<f16 *>(x.values_out[SGX_F16]), diag, x.nnz, (f16)zero, t, nt);
+            fill_range(static_cast<float *>(x.values_out[SGX_F32]), live, diag, one, t, nt);
+            fill_range(static_cast<float *>(x.values_out[SGX_F32]), diag, x.nnz, zero, t, nt);
+            fill_range(x.dead_row_out, (int64_t)n, (int64_t)N, (uint8_t)0, t, nt);
+            continue;
+        }
         fill_pattern(x.rowPtr_out, x.columnIndex_out, static_cast<f16 *>(x.values_out[SGX_F16]), static_cast<float *>(x.values_out[SGX_F32]),
                      n, N, clamp_to(x.entry_off[B], x.nnz), x.nnz, t, nt);
         fill_range(x.dead_row_out, (int64_t)n, (int64_t)N, (uint8_t)0, t, nt);
@@ -340,8 +355,27 @@ extern "C" int sgx_collate_graphs_extras(const sgx_graph_set *set, const sgx_gra
     return SGX_OK;
 }
 
-extern "C" int sgx_collate_graphs_padded(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
-                                         int n_extras, const sgx_collate_pad *pad, void *stream)
+namespace {
+
+// the quantiser arguments of sgx_collate_graphs_padded_quant: every values-only extra k of x [n_extras] (capacities in place)
+// has a pattern-bearing extra of its capacity before it and a grid q that keeps the filler entries inert
+int check_pad_quant(const sgx_collate_extra *x, int n_extras, const sgx_collate_pad_quant *q)
+{
+    int pattern = -1;
+    for (int k = 0; k < n_extras; ++k) {
+        if (x[k].rowPtr_out) { pattern = k; continue; }
+        if (!q) return SGX_ERR_NULL;
+        if (pattern < 0 || x[k].nnz != x[pattern].nnz) return SGX_ERR_SHAPE;
+        const int bits = q->qbits[k];
+        if (bits != 8 && bits != 4 && bits != 2 && bits != 1) return SGX_ERR_UNSUPPORTED;
+        if (!sgx_quantizer::filler_entries_stay_inert(bits, q->inv_scale_adj[k], q->zero_adj[k])) return SGX_ERR_UNSUPPORTED;
+    }
+    return SGX_OK;
+}
+
+// both padded entry points; quant: values-only extras are admitted, on the grids of q
+int collate_padded(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras, int n_extras,
+                   const sgx_collate_pad *pad, bool quant, const sgx_collate_pad_quant *q, void *stream)
 {
     if (n_extras < 0 || n_extras > SGX_COLLATE_MAX_EXTRAS) return SGX_ERR_SHAPE;
     if (!b || !pad) return SGX_ERR_NULL;
@@ -356,7 +390,9 @@ extern "C" int sgx_collate_graphs_padded(const sgx_graph_set *set, const sgx_gra
         a.c.x[k] = extras[k];
         a.c.x[k].nnz = pad->nnz_extra[k];
     }
-    int rc = check_collate(set, &a.c.b);
+    int rc = quant ? check_pad_quant(a.c.x, n_extras, q) : SGX_OK;
+    if (rc != SGX_OK) return rc;
+    rc = check_collate(set, &a.c.b);
     if (rc != SGX_OK) return rc;
     rc = check_extras(&a.c.b, a.c.x, n_extras);
     if (rc != SGX_OK) return rc;
@@ -365,9 +401,10 @@ extern "C" int sgx_collate_graphs_padded(const sgx_graph_set *set, const sgx_gra
     const int64_t least = N > B * R ? N - B * R : 0;
     if (G < B || R < 0 || G * R < N || pad->nnz_adj < least || pad->nnz_adj > INT32_MAX || pad->nnz_fea > INT32_MAX) return SGX_ERR_SHAPE;
     for (int k = 0; k < n_extras; ++k) {
-        if (!a.c.x[k].rowPtr_out) return SGX_ERR_UNSUPPORTED;         // values only (the quantised adjacencies)
+        if (!a.c.x[k].rowPtr_out && !quant) return SGX_ERR_UNSUPPORTED;         // values only (the quantised adjacencies)
         if (a.c.x[k].nnz < least || a.c.x[k].nnz > INT32_MAX) return SGX_ERR_SHAPE;
     }
+    if (q) a.q = *q;
     a.c.s = *set;
     a.c.n_extras = n_extras;
     a.G = (int)G;
@@ -382,4 +419,18 @@ extern "C" int sgx_collate_graphs_padded(const sgx_graph_set *set, const sgx_gra
                        (hipStream_t)stream, a);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
+}
+
+}  // namespace
+
+extern "C" int sgx_collate_graphs_padded(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
+                                         int n_extras, const sgx_collate_pad *pad, void *stream)
+{
+    return collate_padded(set, b, extras, n_extras, pad, false, nullptr, stream);
+}
+
+extern "C" int sgx_collate_graphs_padded_quant(const sgx_graph_set *set, const sgx_graph_batch *b, const sgx_collate_extra *extras,
+                                               int n_extras, const sgx_collate_pad *pad, const sgx_collate_pad_quant *q, void *stream)
+{
+    return collate_padded(set, b, extras, n_extras, pad, true, q, stream);
 }

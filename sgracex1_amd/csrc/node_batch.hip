@@ -650,12 +650,8 @@ extern "C" int sgx_node_batch_sample_padded_quant(sgx_node_batch *b, const sgx_n
     if (!b || !pad || !q) return SGX_ERR_NULL;
     const int ok = check_quant(b, q);
     if (ok != SGX_OK) return ok;
-    // the filler rows' 1 and 0 on every set's grid, by the rule the kernels run: a 1 that rounds to 0 would leave the
-    // filler rows dead under the quantised mask, a 0 that does not stay 0 would give their spare entries weight
-    for (int k = 0; k < q->n_sets; ++k) {
-        const float one = sgx_quantizer::fake_quantize_value(0, q->qbits, q->inv_scale_adj[k], q->zero_adj[k], 1.0f);
-        const float zero = sgx_quantizer::fake_quantize_value(0, q->qbits, q->inv_scale_adj[k], q->zero_adj[k], 0.0f);
-        if (!(one > 0.0f) || zero != 0.0f) return SGX_ERR_UNSUPPORTED;
-    }
+    // the filler rows' 1 and 0 on every set's grid, by the rule the kernels run
+    for (int k = 0; k < q->n_sets; ++k)
+        if (!sgx_quantizer::filler_entries_stay_inert(q->qbits, q->inv_scale_adj[k], q->zero_adj[k])) return SGX_ERR_UNSUPPORTED;
     return node_batch_sample_padded(b, pad, q, stream);
 }

@@ -30,4 +30,12 @@ __host__ __device__ __forceinline__ float fake_quantize_value(int kind, int qbit
     return clipf(rintf(t), lo, hi) * back;                         // fake_quantization, SG.py:191-235
 }
 
+// Host: what every padded batch requires of an adjacency grid before it launches (include/sgx.h, "padded node batches" and
+// "padded batches"): the filler rows' diagonal 1 stays positive -- a 1 that rounds to 0 would leave them dead under the
+// quantised mask -- and their spare 0 stays 0 -- it would otherwise carry weight.  Not-a-number fails both.
+inline bool filler_entries_stay_inert(int qbits, float inv_scale, float zero)
+{
+    return fake_quantize_value(0, qbits, inv_scale, zero, 1.0f) > 0.0f && fake_quantize_value(0, qbits, inv_scale, zero, 0.0f) == 0.0f;
+}
+
 }  // namespace sgx_quantizer

@@ -1919,7 +1919,8 @@ class Collated:
             return False
         if pad is not None:
             if self.pad.key() != pad.key() or (extras is not None and (self.norm_rowptr is None or not
-                                                                       set(self.norm_val) >= set(extras.dtypes))):
+                                                                       set(self.norm_val) >= set(extras.dtypes) or not
+                                                                       set(self.q_val) >= set(extras.keys))):
                 return False
             return self.n_feat == n_feat and set(self.adj_val) >= set(dtypes) and set(self.fea_val) >= set(dtypes)
         i, j = self.index, index
@@ -1977,10 +1978,12 @@ def _regroup_cached_plans(out):
                 plan.regroup(out.graph_ptr)
 
 
-def _collate_padded(graphset, index, dtypes, out, extras, pad):
-    """collate_graphs(pad=): the checks, the capacity-sized Collated and the one launch of sgx_collate_graphs_padded."""
-    if extras is not None and extras.keys:
-        raise ValueError("collate_graphs: padded batches do not carry the quantised adjacencies (pad with quant=)")
+def _collate_padded(graphset, index, dtypes, out, extras, pad, pad_quant=False):
+    """collate_graphs(pad=): the checks, the capacity-sized Collated and the one launch of sgx_collate_graphs_padded -- with
+    pad_quant of sgx_collate_graphs_padded_quant, which also pads the quantised adjacencies of extras.keys."""
+    if extras is not None and extras.keys and not pad_quant:
+        raise ValueError("collate_graphs: padded batches carry the quantised adjacencies (pad with quant=) only with "
+                         "pad_quant=True")
     if extras is not None and pad.nnz_norm is None:
         raise ValueError("collate_graphs: `pad` was computed before graphset.prepare_sym_norm2; compute it after")
     if not pad.fits(index.n_graphs, index.n_rows):
@@ -1998,13 +2001,20 @@ def _collate_padded(graphset, index, dtypes, out, extras, pad):
     xs, n = (None, 0) if extras is None else _collate_extras(index, out, extras)
     for k in range(n):
         c.nnz_extra[k] = pad.nnz_norm
-    check(lib.sgx_collate_graphs_padded(ctypes.byref(graphset.desc), ctypes.byref(b), xs, n, ctypes.byref(c), _stream()),
-          "sgx_collate_graphs_padded")
+    if pad_quant:
+        q = _lib.CollatePadQuant()
+        for k, (bits, a_s, a_z) in enumerate(() if extras is None else extras.keys, 1):       # (extra 0: the normalised adjacency)
+            q.qbits[k], q.inv_scale_adj[k], q.zero_adj[k] = int(bits), float(1 / a_s), float(a_z)
+        check(lib.sgx_collate_graphs_padded_quant(ctypes.byref(graphset.desc), ctypes.byref(b), xs, n, ctypes.byref(c),
+                                                  ctypes.byref(q), _stream()), "sgx_collate_graphs_padded_quant")
+    else:
+        check(lib.sgx_collate_graphs_padded(ctypes.byref(graphset.desc), ctypes.byref(b), xs, n, ctypes.byref(c), _stream()),
+              "sgx_collate_graphs_padded")
     _regroup_cached_plans(out)
     return out
 
 
-def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None, extras=None, pad=None):
+def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None, extras=None, pad=None, pad_quant=False):
     """The batch of the graphs `idx` of `graphset` in that order, built on the device by one launch of
     sgx_collate_graphs: the same x / edge_index / batch / y as pyg_lite.collate, the same adjacency as
     csr_from_edge_index, the same feature CSR as Csr.from_dense, graph_ptr as graph_ptr_of -- with the CSR values in each
@@ -2016,15 +2026,19 @@ def collate_graphs(graphset, idx, dtypes=(torch.float16,), out=None, extras=None
     batches"; one launch of sgx_collate_graphs_padded) -- every tensor has the capacity's size whatever the batch, the
     batch's graphs in the live prefix and filler graphs behind (y, graph_ptr: pad.n_graphs entries) -- and the trusted
     batch plans cached for the buffers of `out` have their tables written again, so that a recorded step which collates
-    into `out` serves every batch that fits.  Extras with quantised values are refused."""
+    into `out` serves every batch that fits.  Extras with quantised values are refused unless pad_quant=True: the launch
+    is then sgx_collate_graphs_padded_quant, which pads out.q_val / out.q_dead as well -- a filler row's diagonal entry
+    holds the grid's image of 1, the spare entries its image of 0 (which must be positive and 0: SgxError otherwise)."""
     index = idx if isinstance(idx, BatchIndex) else graphset.prepare(idx)
     dtypes = tuple(dtypes)
     for dt in dtypes:
         dtype_code(dt)
     if extras is not None and (index.norm_off is None or extras.prepared is not graphset._sym_norm2):
         raise ValueError("collate_graphs: extras need a batch prepared after graphset.prepare_sym_norm2, and extras of this set")
+    if pad_quant and pad is None:
+        raise ValueError("collate_graphs: pad_quant goes with pad=")
     if pad is not None:
-        return _collate_padded(graphset, index, dtypes, out, extras, pad)
+        return _collate_padded(graphset, index, dtypes, out, extras, pad, pad_quant)
     if out is None:
         out = Collated(index, graphset.n_feat, dtypes, graphset.device, extras)
     elif not out.fits(index, graphset.n_feat, dtypes, extras):

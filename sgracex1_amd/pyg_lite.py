@@ -128,14 +128,30 @@ class GraphLoader:
     the layer-by-layer route it then takes was written for CSRs without spare capacity) arrive unpadded, as before.  A
     padded batch is made for the fused stack routes, which read the attached CSRs through their row pointers;
     train.StackTrainer.step refuses to run one layer by layer, and the attention model takes padded batches from a
-    prepare="sym_norm2" loader only (it would otherwise normalise the padded edge_index).  pad=True with quant= raises
-    ValueError: padding the quantised adjacencies is not built."""
+    prepare="sym_norm2" loader only (it would otherwise normalise the padded edge_index).
+
+    pad=True with quant= takes pad_quant=True as well (ValueError without it): the padded batches then carry the quantised
+    adjacencies of both layers at capacity size (ops.collate_graphs(pad_quant=True), sgx_collate_graphs_padded_quant) -- a
+    filler row's diagonal entry holds the grid's image of 1, the spare entries its image of 0, the Csrs' facts say "no
+    dead row" and carry the set's longest row, as an unpadded prepared batch's -- so the fused quantised stack
+    (ops.QuantStack) runs them and one recorded step serves every such batch.  The constants must keep a filler graph
+    inert, which is checked here on the host before any device work (ValueError naming quant): on the adjacency grid of
+    quant and quant.second_layer() 1 stays positive and 0 stays 0 (check_pad_quant), and on their feature grids 0 stays 0
+    (a filler row's zero output is the next layer's input).  A batch with a graph that has a dead row under the
+    quantised mask of either layer (a host fact of the prepared set; at 4 bits and below an entry may round to 0) arrives
+    unpadded, like a batch with a dead-row graph."""
 
     def __init__(self, dataset, batch_size=1, shuffle=False, generator=None, device=None, dtypes=(torch.float16,),
-                 prepare=None, quant=None, pad=False, pad_rows=None):
+                 prepare=None, quant=None, pad=False, pad_rows=None, pad_quant=False):
         from . import ops
-        if pad and quant is not None:
-            raise ValueError("pad=True does not go with quant=: padded batches do not carry the quantised adjacencies")
+        if pad_quant and not (pad and quant is not None):
+            raise ValueError("pad_quant=True needs pad=True and quant=: it pads the quantised adjacencies of a padding loader")
+        if pad and quant is not None and not pad_quant:
+            raise ValueError("pad=True with quant= needs pad_quant=True: without it padded batches do not carry the quantised "
+                             "adjacencies")
+        if pad_quant:
+            check_pad_quant(quant)
+            check_pad_quant_features(quant)
         if pad_rows is not None and not pad:
             raise ValueError("pad_rows needs pad=True")
         if quant is not None and not prepare:
@@ -151,7 +167,7 @@ class GraphLoader:
             raise ValueError("batch_size must be >= 1")
         self.prepare, self.quant = prepare, quant
         self.extras = self.graphs.prepare_sym_norm2(self.dtypes, quant) if prepare else None
-        self.pad = bool(pad)
+        self.pad, self.pad_quant = bool(pad), bool(pad_quant)
         # (after the set is prepared: the capacity counts the normalised adjacency's entries too)
         self.capacity = ops.pad_capacity(self.graphs, min(self.batch_size, len(self.graphs)), pad_rows) if self.pad else None
 
@@ -171,19 +187,30 @@ class GraphLoader:
 
     def padded(self, idx):
         """Whether the batch of graph ids `idx` arrives padded: pad=True, exactly batch_size graphs, rows within the
-        capacity and, with a prepared adjacency, no graph with a dead row.  Host only."""
+        capacity and, with a prepared adjacency, no graph with a dead row -- under the normalised values or, with
+        pad_quant, under the quantised values of either layer.  Host only."""
         idx = np.asarray(idx, dtype=np.int64).reshape(-1)
         if not self.pad or not self.capacity.fits(idx.size, int(self.graphs.counts[0][idx].sum())):
             return False
-        return self.extras is None or not bool(self.extras.prepared.has_dead[idx].any())
+        return self.extras is None or not bool(self.has_dead()[idx].any())
+
+    def has_dead(self):
+        """Per graph of a prepared set (host bool [graphs]): it has a dead row under the normalised adjacency or, from a
+        loader with pad_quant, under the quantised adjacency of either layer -- the graphs whose batches arrive unpadded."""
+        p = self.extras.prepared
+        dead = p.has_dead
+        for key in (self.extras.keys if getattr(self, "pad_quant", False) else ()):
+            dead = dead | p.quant[key][2]
+        return dead
 
     def collate(self, idx, out=None):
         """The Batch of graph ids `idx` (host, in batch order, or an ops.BatchIndex of them), caches attached; out: an
         ops.Collated to reuse."""
         from . import ops
         ids = idx.ids if isinstance(idx, ops.BatchIndex) else idx
+        padded = self.padded(ids)
         c = ops.collate_graphs(self.graphs, idx, self.dtypes, out=out, extras=self.extras,
-                               pad=self.capacity if self.padded(ids) else None)
+                               pad=self.capacity if padded else None, pad_quant=padded and self.pad_quant)
         return attach_batch(c)
 
 
@@ -317,6 +344,21 @@ def check_pad_quant(quant):
         if zero != 0:
             raise ValueError(f"pad=True with quant=: with quant's a_s {a_s}, a_z {a_z} at {bits} bits a filler row's spare 0 "
                              f"becomes {zero}: the spare entries would carry weight")
+
+
+def check_pad_quant_features(quant):
+    """What GraphLoader(pad_quant=True) asks of the FEATURE grids of `quant` and quant.second_layer() besides
+    check_pad_quant (include/sgx.h, "padded batches ready for the quantised layers"): 0 stays 0, so that a filler row's
+    zero output is a zero input of the next quantised layer.  ValueError naming `quant` otherwise.  Host arithmetic only."""
+    import math
+    for qc in (quant, quant.second_layer()):
+        bits, f_s, f_z = int(qc.w_qbits), float(qc.f_s), float(qc.f_z)
+        if not (math.isfinite(f_s) and f_s > 0 and math.isfinite(f_z)):
+            raise ValueError(f"pad_quant=True: quant.f_s must be finite and positive (f_s {f_s}, f_z {f_z})")
+        zero = _fq_unsigned_scalar(0.0, f_s, f_z, bits)
+        if zero != 0:
+            raise ValueError(f"pad_quant=True: with quant's f_s {f_s}, f_z {f_z} at {bits} bits a filler row's zero output "
+                             f"becomes {zero} as the next layer's input: the filler graphs would not stay inert")
 
 
 class NeighborLoader:

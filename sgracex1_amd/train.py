@@ -57,13 +57,20 @@ class _Trainer:
         epochs: the rows of its log (None: no log)."""
         return BestTracker(self, epochs)
 
-    def _capture(self, batch, warmup, probe=None, counters=(), run=None):
+    def _capture(self, batch, warmup, probe=None, counters=(), run=None, guard_workspace=False):
         """Record self.step(*batch) (or run(), where a step has more in front of it) with torch.cuda.graph (one stream, no parallel branches) and return a callable that
         replays it and returns the loss tensor the replay fills.  The warm-up steps it needs first (they build what a step
         caches: the CSRs, the plans, the workspaces) run on a side stream on a copy of the state, which is put back before
         the capture: the trainer is where it was, and n replays equal n eager steps.  probe: run on the side stream after
         the warm-up steps; what it returns is raised once the state is back.  counters: the names of host-side counts that
-        the recorded step (which computes nothing until it is replayed) must leave as the warm-up left them."""
+        the recorded step (which computes nothing until it is replayed) must leave as the warm-up left them.
+
+        guard_workspace: ops._workspace keeps one grow-only scratch tensor per stream, and a recording holds the address
+        it saw.  The recording is then made ON the warm-up's stream, so that every call it runs has already asked that
+        stream's workspace for its size; the tensor's address is compared before and after the capture, and RuntimeError
+        is raised -- no recording is returned -- if a call inside the recording replaced it (an earlier launch of the
+        same recording would hold the old address).  The recording keeps a reference to the tensor (replay.workspace), so
+        that its memory outlives a later growth of that stream's workspace.  A host-side check; nothing synchronises."""
         if run is None:
             run = lambda: self.step(*batch)
         saved = self.state()
@@ -81,16 +88,30 @@ class _Trainer:
             raise failure
         kept = [(name, getattr(self, name)) for name in counters]
         graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            loss = run()
+        workspace = moved = None
+        if guard_workspace:
+            key = (self.t.device.index, side.cuda_stream)
+            address = lambda: getattr(ops._workspaces.get(key), "data_ptr", lambda: None)()
+            workspace, before = ops._workspaces.get(key), address()
+            side.wait_stream(torch.cuda.current_stream())          # (the state was put back on the current stream)
+            with torch.cuda.graph(graph, stream=side):
+                loss = run()
+            moved = address() != before
+        else:
+            with torch.cuda.graph(graph):
+                loss = run()
         for name, value in kept:
             setattr(self, name, value)
+        if moved:
+            raise RuntimeError("the recorded step replaced its stream's workspace (ops._workspace) in the middle of the "
+                               "recording: a call in it asked for more scratch than the warm-up steps did, and an earlier "
+                               "launch of the recording holds the old address; nothing was recorded")
 
         def replay():
             graph.replay()
             return loss
 
-        replay.graph = graph
+        replay.graph, replay.workspace = graph, workspace
         return replay
 
     @contextlib.contextmanager
@@ -222,12 +243,15 @@ class StackTrainer(_Trainer):
         if training and not torch.is_grad_enabled():
             return "gradients are disabled"
         facts = self._block_facts(batch)
+        quantised = ("; with the quantiser on (config.fake_quantization / hardware_quantize) also: config.float_type is "
+                     "float32, the quantiser constants are set (sgrace.init_SGRACE after the config), no row is dead under "
+                     "the QUANTISED adjacency, and not both config.hardware_quantize and a hidden width over 128 (the int8 form)")
         if not training:
             return ("a condition of the model's fused eval route fails on the padded batch (its class docstring lists them): "
-                    "no row of the adjacency may be dead")
+                    "no row of the adjacency may be dead" + quantised)
         return (f"a condition of the model's fused training route fails on the padded batch (its class docstring lists "
                 f"them); the largest graph of the set has {facts['max_graph'] if facts else '?'} rows, which must be within "
-                f"the backward plan's row budget, and no row of the adjacency may be dead")
+                f"the backward plan's row budget, and no row of the adjacency may be dead" + quantised)
 
     def capture_loader(self, loader, warmup=2):
         """One recorded step for every padded batch of `loader` (a pyg_lite.GraphLoader(pad=True)) -> a callable that runs
@@ -242,7 +266,12 @@ class StackTrainer(_Trainer):
         the prepared set; the fused GAT route declines it) -- runs through step() unpadded in its place, so an epoch
         takes exactly the steps of `for b in loader: step(b.x, b.edge_index, b.batch, b.y, b.num_real_graphs)`.
         The warm-up steps run on a padded batch of the set's smallest graphs without a dead row, on a copy of the state.
-        If the model's fused route declines that batch, RuntimeError names the reason: a padded batch never falls back."""
+        If the model's fused route declines that batch, RuntimeError names the reason: a padded batch never falls back.
+        A loader with quant= and pad_quant=True serves GAT_POOL_PYNQ(train_stack=True) with the quantiser on (attention
+        and GCN layers, config.fake_quantization with and without config.hardware_quantize, hidden <= 128): the padded
+        batches carry the quantised adjacencies, a batch with a graph dead under the quantised mask arrives unpadded too,
+        and the recording is made on the warm-up's stream under _capture's workspace guard (RuntimeError, and no
+        recording, if a call in it replaced the stream's workspace)."""
         def accepts(b):
             with torch.enable_grad():                  # (before any state is touched: step() raises on a declined padded batch)
                 if self.model.train_pooled(b.x, b.edge_index, b.batch) is None:
@@ -274,21 +303,23 @@ class StackTrainer(_Trainer):
         if not getattr(loader, "pad", False):
             raise ValueError(f"{name} takes a GraphLoader(pad=True)")
         gs, cap, B = loader.graphs, loader.capacity, loader.capacity.batch_size
+        quant = bool(getattr(loader, "pad_quant", False))          # the loader's mode: its padded batches carry the quantised adjacencies
         rows = gs.counts[0]
-        dead = loader.extras.prepared.has_dead if loader.extras is not None else np.zeros(len(gs), dtype=bool)
+        dead = loader.has_dead() if loader.extras is not None else np.zeros(len(gs), dtype=bool)
         first = [int(g) for g in np.argsort(rows, kind="stable") if not dead[g]][:B]
         if len(first) < B or not loader.padded(first):
             raise RuntimeError(f"{name}: the set has no padded batch without a dead-row graph to record a step on")
         index = gs.prepare(first)                      # the static index buffer: every replay reads this address
-        c = ops.collate_graphs(gs, index, loader.dtypes, extras=loader.extras, pad=cap)
+        c = ops.collate_graphs(gs, index, loader.dtypes, extras=loader.extras, pad=cap, pad_quant=quant)
         b = pyg_lite.attach_batch(c)
 
         def run():
-            ops.collate_graphs(gs, index, loader.dtypes, out=c, extras=loader.extras, pad=cap)
+            ops.collate_graphs(gs, index, loader.dtypes, out=c, extras=loader.extras, pad=cap, pad_quant=quant)
             return run_batch(b)
 
         accepts(b)
-        replay = self._capture((), warmup, counters=counters, run=run)
+        # (the quantised routes ask ops._workspace for other sizes than the plain ones: their recording is guarded)
+        replay = self._capture((), warmup, counters=counters, run=run, guard_workspace=quant)
         counts = gs.counts if gs._sym_norm2 is None else gs.counts + (gs._sym_norm2.counts,)
 
         def walk(replayed, eager):

@@ -22,7 +22,10 @@ GCN_PYNQ(train_stack=True), layer_count 2, fp16 layers:
           tree without padded batches too; replay: StackTrainer.capture_loader over GraphLoader(pad=True), one recorded
           step for every full batch -- on MUTAG at batch 64, or with --big on the million-graph replica at batch 4096.
           step_ms = host wall clock of whole epochs over their steps, closed by a synchronisation, after one warm-up
-          epoch; the replay line also gives the padding overhead N over the mean n.
+          epoch; the replay line also gives the padding overhead N over the mean n.  --model gat --quant 8
+          [--attention 0]: the quantised step (GCN layers with --attention 0) -- eager over GraphLoader(prepare=
+          "sym_norm2", quant=), which a tree without padded quantised batches runs too; replay over the same loader with
+          pad=True, pad_quant=True.
 One JSON line each.  --stats CSV turns a `rocprofv3 --kernel-trace --stats` kernel_stats file of a `--only collate` run
 into one line for the collate kernel.
 
@@ -95,9 +98,9 @@ def step_times(graphs, batch_size, dev, max_steps, which):
     return out
 
 
-def gat_model(dev, qbits):
+def gat_model(dev, qbits, attention=1):
     from sgracex1_amd import config, sgrace
-    config.acc, config.compute_attention, config.float_type = 1, 1, np.float32
+    config.acc, config.compute_attention, config.float_type = 1, int(attention), np.float32
     config.fake_quantization, config.w_qbits = int(qbits is not None), qbits or 8
     sgrace.init_SGRACE().register_map.layer_count = 2
     return sgrace.GAT_POOL_PYNQ(7, 64, 2, train_stack=True).to(dev).train(), sgrace.quant_constants
@@ -167,20 +170,26 @@ def replay_line(graphs, name, batch_size, dev, args):
     from sgracex1_amd import train
     torch.manual_seed(5)
     gat = args.model == "gat"
-    m = gat_model(dev, None)[0] if gat else model(dev)
+    m, qc = gat_model(dev, args.quant, args.attention) if gat else (model(dev), None)
     kw = dict(dtypes=(torch.float32,), prepare="sym_norm2") if gat else {}
+    if qc is not None:
+        kw.update(quant=qc)                        # the quantised step: the prepared quantised loader in both legs
     gs = ops.GraphSet(graphs, dev)
     replay = args.replay_leg == "replay"
     if replay:
-        kw.update(pad=True, pad_rows=args.pad_rows)
+        kw.update(pad=True, pad_rows=args.pad_rows, **({} if qc is None else {"pad_quant": True}))
     loader = G.GraphLoader(gs, batch_size=batch_size, shuffle=True, generator=torch.Generator().manual_seed(12345), **kw)
     trainer = train.StackTrainer(m, lr=0.01)
     line = {"workload": f"{name}_{args.model}_trainer_epoch", "leg": args.replay_leg, "graphs": len(gs), "batch_size": batch_size}
+    if gat:
+        line.update(quant=args.quant, attention=args.attention)
     if replay:
         epoch = trainer.capture_loader(loader)
         cap = loader.capacity
+        padded = [loader.padded(ids) for ids in loader.batches()]
         line.update(pad_rows=cap.n_rows, pad_graphs=cap.n_graphs, filler_rows=cap.filler_rows,
-                    rows_over_mean_rows=cap.n_rows / (float(np.mean(gs.counts[0])) * batch_size))
+                    rows_over_mean_rows=cap.n_rows / (float(np.mean(gs.counts[0])) * batch_size),
+                    padded_batches_of_an_epoch=f"{sum(padded)} of {len(padded)}")
     else:
         def epoch():
             return [trainer.step(b.x, b.edge_index, b.batch, b.y) for b in loader]
@@ -258,6 +267,7 @@ def main():
     ap.add_argument("--stats", default=None)
     ap.add_argument("--model", choices=["gcn", "gat"], default="gcn")
     ap.add_argument("--quant", type=int, default=None, choices=[8, 4, 2, 1])
+    ap.add_argument("--attention", type=int, default=1, choices=[0, 1])      # --only replay --model gat: 0 = GCN layers
     ap.add_argument("--leg", choices=["both", "plain", "prepared"], default="both")
     args = ap.parse_args()
     if args.quant is not None and args.model != "gat":
