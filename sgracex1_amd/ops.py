@@ -1133,6 +1133,30 @@ def _node_map(device, n_nodes):
     return m
 
 
+def _fan_array(fanouts):
+    """-> (the fan-outs as a list of int, the same as the int32 array the C calls read)"""
+    fan = [int(k) for k in fanouts]
+    return fan, (ctypes.c_int32 * max(len(fan), 1))(*fan)
+
+
+def _sampler_workspace(call, query, csr, B, fan, fan_c):
+    """-> (workspace, max_nodes, max_edges): the scratch of one sampling call as `query` (an sgx_*_workspace_bytes) sizes
+    it, and the sampler's bounds on the batch's nodes and edges.  ValueError naming `call` where the query refuses."""
+    max_nodes, max_edges = ctypes.c_int64(0), ctypes.c_int64(0)
+    nbytes = query(csr.n_rows, csr.nnz, B, len(fan), fan_c, ctypes.byref(max_nodes), ctypes.byref(max_edges))
+    if nbytes == 0:
+        raise ValueError(f"{call}: bad arguments (n_nodes {csr.n_rows}, nnz {csr.nnz}, batch {B}, fanouts {fan}): "
+                         "fan-outs must be >= -1, 1 to 64 hops, batch <= n_nodes")
+    return _workspace(csr.rowptr.device, nbytes), max_nodes.value, max_edges.value
+
+
+def _check_sample(status, node_map, call):
+    """check() of an eager sampling call's status, with the map put back first where the library left it used."""
+    if status not in (0, _lib.SGX_ERR_SEEDS):
+        node_map.fill_(SAMPLE_SENTINEL)                 # (sgx.h: the map is restored on success and on SGX_ERR_SEEDS only)
+    check(status, call)
+
+
 class Sample:
     """One sampled mini-batch (include/sgx.h, "neighbour sampling"): n_id (global ids, seeds first), adj (Csr over the
     local nodes: row i = the sampled in-neighbours of local node i), edge_pos (position of every sampled edge in the
@@ -1159,30 +1183,21 @@ def sample_neighbors(csr, seeds, fanouts, seed=0, step=0, gather_values=False):
     (graph, seeds, fanouts, seed, step).  adj holds fp32 ones, or the sampled entries of csr.val with gather_values.
     One stream synchronisation per call."""
     _dev(seeds, "seeds")
-    fan = [int(k) for k in fanouts]
     dev = csr.rowptr.device
     seeds = seeds.to(torch.int32).contiguous()
-    B, H, n = seeds.numel(), len(fan), csr.n_rows
-    fan_c = (ctypes.c_int32 * max(H, 1))(*fan)
-    max_nodes, max_edges = ctypes.c_int64(0), ctypes.c_int64(0)
-    nbytes = lib.sgx_sample_workspace_bytes(n, csr.nnz, B, H, fan_c, ctypes.byref(max_nodes), ctypes.byref(max_edges))
-    if nbytes == 0:
-        raise ValueError(f"sample_neighbors: bad arguments (n_nodes {n}, nnz {csr.nnz}, batch {B}, fanouts {fan}): "
-                         "fan-outs must be >= -1, 1 to 64 hops, batch <= n_nodes")
-    n_id = torch.empty(max(max_nodes.value, 1), dtype=torch.int32, device=dev)
-    rowptr = torch.empty(max_nodes.value + 1, dtype=torch.int32, device=dev)
-    col = torch.empty(max(max_edges.value, 1), dtype=torch.int32, device=dev)
-    pos = torch.empty(max(max_edges.value, 1), dtype=torch.int32, device=dev)
+    B, n = seeds.numel(), csr.n_rows
+    fan, fan_c = _fan_array(fanouts)
+    H = len(fan)
+    ws, mn, me = _sampler_workspace("sample_neighbors", lib.sgx_sample_workspace_bytes, csr, B, fan, fan_c)
+    i32 = lambda k: torch.empty(max(int(k), 1), dtype=torch.int32, device=dev)
+    n_id, rowptr, col, pos = i32(mn), i32(mn + 1), i32(me), i32(me)
     hop_nodes, hop_edges = (ctypes.c_int64 * (H + 1))(), (ctypes.c_int64 * (H + 1))()
     node_map = _node_map(dev, n)
-    ws = _workspace(dev, nbytes)
     status = lib.sgx_sample_neighbors(_ptr(csr.rowptr), _ptr(csr.col), n, csr.nnz, _ptr(seeds) if B else None, B, H, fan_c,
                                       int(seed) & (2**64 - 1), int(step) & (2**64 - 1), _ptr(node_map), _ptr(n_id),
-                                      _ptr(rowptr), _ptr(col), _ptr(pos), max_nodes.value, max_edges.value, hop_nodes,
-                                      hop_edges, _ptr(ws), ws.numel(), _stream())
-    if status not in (0, _lib.SGX_ERR_SEEDS):
-        node_map.fill_(SAMPLE_SENTINEL)                 # (sgx.h: the map is restored on success and on SGX_ERR_SEEDS only)
-    check(status, "sgx_sample_neighbors")
+                                      _ptr(rowptr), _ptr(col), _ptr(pos), mn, me, hop_nodes, hop_edges, _ptr(ws), ws.numel(),
+                                      _stream())
+    _check_sample(status, node_map, "sgx_sample_neighbors")
     N, E = hop_nodes[H], hop_edges[H]
     val = csr.val[pos[:E].long()] if gather_values else torch.ones(E, dtype=torch.float32, device=dev)
     adj = Csr(rowptr[:N + 1], col[:E], val, N)
@@ -1207,6 +1222,12 @@ def feature_csr(x):
 def _adj_quant_key(qc):
     """The key Csr.quantized files a quantised adjacency under: the constants the adjacency's quantiser reads."""
     return (qc.w_qbits, qc.a_s, qc.a_z)
+
+
+def _adj_quant_sets(quant):
+    """{_adj_quant_key: constants} of the quantised adjacencies a batch for `quant` carries, in order: one set per distinct
+    key of quant and quant.second_layer() (the demo's two layers share the adjacency's constants); {} without quant."""
+    return {} if quant is None else {_adj_quant_key(qc): qc for qc in (quant, quant.second_layer())}
 
 
 class PaddedNodeSample(NodeSample):
@@ -1234,11 +1255,10 @@ def node_pad_capacity(csr, batch_size, fanouts, features=None):
     """The capacity every batch of `batch_size` seeds sampled from `csr` with `fanouts` fits (sgx_node_batch_pad_capacity;
     rule and proof in include/sgx.h): host arithmetic, computed once per (graph, batch, fanouts, feature CSR).  features:
     the feature_csr of the graph's x, or None; its per-row entry counts are read back once here."""
-    fan = [int(k) for k in fanouts]
+    fan, fan_c = _fan_array(fanouts)
     H = len(fan)
     if any(k < 0 for k in fan):
         raise ValueError("node_pad_capacity: a fan-out of -1 leaves a row unbounded; padded batches need fan-outs >= 0")
-    fan_c = (ctypes.c_int32 * max(H, 1))(*fan)
     rows = None
     if features is not None:
         rows = (features.rowptr[1:] - features.rowptr[:-1]).to(torch.int32).cpu().contiguous()
@@ -1257,41 +1277,141 @@ class NodePadBuffers:
     what a recorded step reads at fixed addresses.  Also the sampler's node map (kept at the sentinel between calls), the
     OR-ed status word and the live counts.  n_id starts at -1, so no gather by it ever leaves its source.  n_quant: the
     number of constant sets of a quantised padded batch (sample_node_batch(pad=, quant=)); `quant` then holds (q_val [C_a]
-    fp32, q_dead [N] bool, q_lean [C_a] fp32) per set."""
+    fp32, q_dead [N] bool, q_lean [C_a] fp32) per set.  worst_case: the same arrays for one unpadded batch."""
 
     def __init__(self, cap, n_nodes, dtype, device, n_feat=None, y=False, n_masks=0, n_quant=0):
-        N, Ca, Cf, E = cap.n_rows, cap.nnz_norm, cap.nnz_fea, cap.n_edges
         new = lambda k, dt, v=0: torch.full((max(int(k), 1),), v, dtype=dt, device=device)
         self.capacity, self.dtype = cap, dtype
+        self._outputs(new, cap.n_rows, cap.n_edges, cap.nnz_norm, cap.nnz_fea if cap.features else None, dtype, y, n_masks, n_quant)
+        if cap.features:
+            self.n_feat = int(n_feat)
+        self.max_nodes, self.max_edges = cap.max_nodes, cap.max_edges
+        self.node_map = new(n_nodes, torch.int32, SAMPLE_SENTINEL)
+        self.status = new(1, torch.int32)
+        self.counts = new(4 + 2 * (len(cap.fanouts) + 1), torch.int32)
+
+    def _outputs(self, new, N, E, Ca, Cf, dtype, y, n_masks, n_quant):
+        """Every output array of a batch of up to N nodes, E edges, Ca adjacency and Cf feature entries (None: no feature
+        CSR), each from new(size, dtype[, fill])."""
         self.n_id, self.rowptr, self.col, self.pos = new(N, torch.int32, -1), new(N + 1, torch.int32), new(E, torch.int32, -1), new(E, torch.int32, -1)
         self.n_rowptr, self.n_col, self.n_val = new(N + 1, torch.int32), new(Ca, torch.int32), new(Ca, dtype)
         self.dead = new(N, torch.bool, False)
         self.ei, self.ei_agg = new(2 * E, torch.int64, -1), new(2 * E, torch.int64, -1)
         self.f_rowptr = self.f_col = self.f_val = None
-        if cap.features:
-            self.n_feat = int(n_feat)
+        if Cf is not None:
             self.f_rowptr, self.f_col, self.f_val = new(N + 1, torch.int32), new(Cf, torch.int32), new(Cf, dtype)
         self.y = new(N, torch.int64) if y else None
         self.masks = [new(N, torch.bool, False) for _ in range(n_masks)]
-        self.node_map = new(n_nodes, torch.int32, SAMPLE_SENTINEL)
-        self.status = new(1, torch.int32)
-        self.counts = new(4 + 2 * (len(cap.fanouts) + 1), torch.int32)
         self.quant = [(new(Ca, torch.float32), new(N, torch.bool, False), new(Ca, torch.float32)) for _ in range(int(n_quant))]
 
+    @classmethod
+    def worst_case(cls, max_nodes, max_edges, dtype, device, fea_capacity, y, n_masks, n_quant, node_map):
+        """The buffers of ONE unpadded batch at the sampler's bounds, unfilled (the kernels write all that is read), over the
+        stream's shared node map: what sample_node_batch without pad= draws into and returns views of."""
+        self = object.__new__(cls)
+        empty = lambda k, dt, v=None: torch.empty(max(int(k), 1), dtype=dt, device=device)
+        self._outputs(empty, max_nodes, max_edges, max_edges + max_nodes, fea_capacity, dtype, y, n_masks, n_quant)
+        self.max_nodes, self.max_edges, self.node_map = max_nodes, max_edges, node_map
+        return self
 
-def _sample_node_batch_padded(csr, seeds, seed, step, fill, dtype, edge_weight, features, y, masks, cap, out, quant=None):
-    """sample_node_batch(pad=cap): sgx_node_batch_sample_padded -- with quant= sgx_node_batch_sample_padded_quant -- into
-    `out` (a NodePadBuffers; None: a fresh one)."""
-    dev, n, B, H = csr.rowptr.device, csr.n_rows, seeds.numel(), len(cap.fanouts)
+
+def _check_node_batch(csr, seeds, dtype, edge_weight, features, y, masks, quant):
+    """The argument checks of sample_node_batch, padded or not -> (seeds as int32, masks as a list)."""
+    _dev(seeds, "seeds")
+    n = csr.n_rows
+    if quant is not None and dtype != torch.float32:
+        raise ValueError("sample_node_batch: quant needs dtype=torch.float32 (the quantised layer works on float32 buffers)")
+    masks = list(masks)
+    if len(masks) > 3:
+        raise ValueError("sample_node_batch gathers up to three masks")
+    if features is not None and (features.val.dtype != torch.float32 or features.n_rows != n or features._max_row is None):
+        raise ValueError("features must be the feature_csr of the graph's x (fp32 values, one row per node)")
+    optional = [(edge_weight, "edge_weight", torch.float32, csr.nnz, "edge_weight must be float32 [csr.nnz]"),
+                (y, "y", torch.int64, n, "y must be int64 [n_nodes]")]
+    for t, name, dt, size, what in ([c for c in optional if c[0] is not None]
+                                    + [(m, "mask", torch.bool, n, "masks must be bool [n_nodes]") for m in masks]):
+        _dev(t, name)
+        if t.dtype != dt or t.numel() != size:
+            raise ValueError(what)
+    return seeds.to(torch.int32).contiguous(), masks
+
+
+def _node_batch_desc(csr, seeds, fan, fan_c, seed, dtype, edge_weight, fill, features, y, masks, out, ws):
+    """struct sgx_node_batch of checked arguments, writing into `out` (a NodePadBuffers of either kind).  The caller adds
+    what its mode alone has: the host step, hop_nodes / hop_edges and fea_capacity, or the NodeBatchPad."""
+    b = _lib.NodeBatch()
+    B = seeds.numel()
+    b.rowPtr, b.columnIndex, b.n_nodes, b.nnz = csr.rowptr.data_ptr(), csr.col.data_ptr(), csr.n_rows, csr.nnz
+    b.seeds, b.batch, b.n_hops, b.fanouts = (seeds.data_ptr() if B else None), B, len(fan), fan_c
+    b.dtype, b.seed, b.fill = dtype_code(dtype), int(seed) & (2**64 - 1), float(fill)
+    b.node_map, b.n_id, b.out_rowPtr, b.out_col, b.edge_pos = (out.node_map.data_ptr(), out.n_id.data_ptr(), out.rowptr.data_ptr(),
+                                                               out.col.data_ptr(), out.pos.data_ptr())
+    b.max_nodes, b.max_edges = out.max_nodes, out.max_edges
+    if edge_weight is not None:
+        b.edge_weight = edge_weight.data_ptr()
+    b.rowPtr_norm, b.columnIndex_norm, b.values_norm = out.n_rowptr.data_ptr(), out.n_col.data_ptr(), out.n_val.data_ptr()
+    b.dead_row, b.edge_index, b.edge_index_agg = out.dead.data_ptr(), out.ei.data_ptr(), out.ei_agg.data_ptr()
+    if features is not None:
+        b.rowPtr_x, b.columnIndex_x, b.values_x = features.rowptr.data_ptr(), features.col.data_ptr(), features.val.data_ptr()
+        b.rowPtr_fea, b.columnIndex_fea, b.values_fea = out.f_rowptr.data_ptr(), out.f_col.data_ptr(), out.f_val.data_ptr()
+    if y is not None:
+        b.y, b.y_out = y.data_ptr(), out.y.data_ptr()
+    for k, m in enumerate(masks):
+        b.mask[k], b.mask_out[k] = m.data_ptr(), out.masks[k].data_ptr()
+    b.workspace, b.workspace_bytes = ws.data_ptr(), ws.numel()
+    return b
+
+
+def _node_batch_quant_desc(sets, out):
+    """struct sgx_node_batch_quant of the constant sets `sets` (_adj_quant_sets), writing into out.quant; None without sets."""
+    if not sets:
+        return None
+    q = _lib.NodeBatchQuant()
+    q.n_sets, q.qbits = len(sets), int(next(iter(sets.values())).w_qbits)
+    for k, (qc, (q_val, q_dead, q_lean)) in enumerate(zip(sets.values(), out.quant)):
+        q.inv_scale_adj[k], q.zero_adj[k] = float(1 / qc.a_s), float(qc.a_z)
+        q.values_q[k], q.dead_row_q[k], q.values_lean[k] = q_val.data_ptr(), q_dead.data_ptr(), q_lean.data_ptr()
+    return q
+
+
+def _node_batch_call(b, p, q):
+    """The one of the four sgx_node_batch_sample* entries that takes these descriptors (p the NodeBatchPad, q the
+    NodeBatchQuant; None: the entry without) on the current stream -> (status, the entry's name)."""
+    name = "sgx_node_batch_sample" + ("_padded" if p is not None else "") + ("_quant" if q is not None else "")
+    return getattr(lib, name)(*[ctypes.byref(d) for d in (b, p, q) if d is not None], _stream()), name
+
+
+def _wrap_node_batch(s, out, sets, features, N, E, nnz_norm, nnz_fea, has_dead_rows, has_dead_rows_q, max_row, fea_max_row):
+    """Fills the NodeSample `s` with what a batch call wrote into `out`, as views of N nodes, E edges, nnz_norm adjacency and
+    nnz_fea feature entries with the given facts (has_dead_rows_q: one per set of `sets`).  Every array is cut to its
+    count: an empty Csr keeps one-element stand-ins for col and val, which must not pass for an entry."""
+    s.adj_norm = A = Csr(out.n_rowptr[:N + 1], out.n_col[:nnz_norm], out.n_val[:nnz_norm], N).with_facts(
+        out.dead[:N], has_dead_rows, max_row)
+    col = A.col if A.nnz else A.col[:0]                 # the quantised adjacencies share A's pattern, the tensors themselves
+    for key, (q_val, q_dead, q_lean), dead_q in zip(sets, out.quant, has_dead_rows_q):
+        Q = Csr(A.rowptr, col, q_val[:nnz_norm], N).with_facts(q_dead[:N], dead_q, max_row)
+        Q._lean_values = Csr(A.rowptr, col, q_lean[:nnz_norm], N)
+        A._quantized[key] = Q
+    s.edge_index, s.edge_index_agg = out.ei[:2 * E].view(2, E), out.ei_agg[:2 * E].view(2, E)
+    s.fea = None
+    if features is not None:
+        s.fea = Csr(out.f_rowptr[:N + 1], out.f_col[:nnz_fea], out.f_val[:nnz_fea], features.n_cols).with_facts(max_row=fea_max_row)
+    s.y = None if out.y is None else out.y[:N]
+    s.masks = [m[:N] for m in out.masks]
+    return s
+
+
+def _sample_node_batch_padded(csr, seeds, fan, fan_c, seed, step, fill, dtype, edge_weight, features, y, masks, sets, cap, out):
+    """sample_node_batch(pad=cap) of checked arguments: sgx_node_batch_sample_padded -- with constant sets
+    sgx_node_batch_sample_padded_quant -- into `out` (a NodePadBuffers; None: a fresh one).  Reads nothing back."""
+    dev, n, B = csr.rowptr.device, csr.n_rows, seeds.numel()
+    if tuple(fan) != cap.fanouts:
+        raise ValueError("sample_node_batch: pad= was computed for other fan-outs")
     if B != cap.batch_size or cap.features != (features is not None):
         raise ValueError("sample_node_batch: pad= is the node_pad_capacity of this batch size, these fan-outs and these features")
     _dev(step, "step")
     if step.dtype != torch.int64 or step.numel() != 1:
         raise ValueError("sample_node_batch(pad=): step is a device int64 [1] tensor (the word a replay reads)")
-    if features is not None and (features.val.dtype != torch.float32 or features.n_rows != n or features._max_row is None):
-        raise ValueError("features must be the feature_csr of the graph's x (fp32 values, one row per node)")
-    # one constant set per distinct key of the two layers' constants, as the unpadded call builds them
-    sets = {} if quant is None else {_adj_quant_key(qc): qc for qc in (quant, quant.second_layer())}
     if out is None:
         out = NodePadBuffers(cap, n, dtype, dev, None if features is None else features.n_cols, y is not None, len(masks),
                              len(sets))
@@ -1299,68 +1419,19 @@ def _sample_node_batch_padded(csr, seeds, seed, step, fill, dtype, edge_weight, 
             or len(out.quant) != len(sets)):
         raise ValueError("sample_node_batch: out= was built for another capacity, dtype, label, mask set or number of "
                          "quantiser constant sets")
+    ws = _workspace(dev, lib.sgx_node_batch_workspace_bytes(n, csr.nnz, B, len(fan), fan_c, None, None))
+    b = _node_batch_desc(csr, seeds, fan, fan_c, seed, dtype, edge_weight, fill, features, y, masks, out, ws)
     N, Ca, Cf, E = cap.n_rows, cap.nnz_norm, cap.nnz_fea, cap.n_edges
-    fan_c = (ctypes.c_int32 * max(H, 1))(*cap.fanouts)
-    ws = _workspace(dev, lib.sgx_node_batch_workspace_bytes(n, csr.nnz, B, H, fan_c, None, None))
-    b = _lib.NodeBatch()
-    b.rowPtr, b.columnIndex, b.n_nodes, b.nnz = csr.rowptr.data_ptr(), csr.col.data_ptr(), n, csr.nnz
-    b.seeds, b.batch, b.n_hops, b.fanouts, b.dtype = seeds.data_ptr(), B, H, fan_c, dtype_code(dtype)
-    b.seed = int(seed) & (2**64 - 1)
-    b.node_map, b.n_id, b.out_rowPtr, b.out_col, b.edge_pos = (out.node_map.data_ptr(), out.n_id.data_ptr(), out.rowptr.data_ptr(),
-                                                               out.col.data_ptr(), out.pos.data_ptr())
-    b.max_nodes, b.max_edges = cap.max_nodes, cap.max_edges
-    if edge_weight is not None:
-        _dev(edge_weight, "edge_weight")
-        if edge_weight.dtype != torch.float32 or edge_weight.numel() != csr.nnz:
-            raise ValueError("edge_weight must be float32 [csr.nnz]")
-        b.edge_weight = edge_weight.data_ptr()
-    b.fill = float(fill)
-    b.rowPtr_norm, b.columnIndex_norm, b.values_norm = out.n_rowptr.data_ptr(), out.n_col.data_ptr(), out.n_val.data_ptr()
-    b.dead_row, b.edge_index, b.edge_index_agg = out.dead.data_ptr(), out.ei.data_ptr(), out.ei_agg.data_ptr()
-    if features is not None:
-        b.rowPtr_x, b.columnIndex_x, b.values_x = features.rowptr.data_ptr(), features.col.data_ptr(), features.val.data_ptr()
-        b.rowPtr_fea, b.columnIndex_fea, b.values_fea = out.f_rowptr.data_ptr(), out.f_col.data_ptr(), out.f_val.data_ptr()
-    if y is not None:
-        _dev(y, "y")
-        if y.dtype != torch.int64 or y.numel() != n:
-            raise ValueError("y must be int64 [n_nodes]")
-        b.y, b.y_out = y.data_ptr(), out.y.data_ptr()
-    for k, m in enumerate(masks):
-        _dev(m, "mask")
-        if m.dtype != torch.bool or m.numel() != n:
-            raise ValueError("masks must be bool [n_nodes]")
-        b.mask[k], b.mask_out[k] = m.data_ptr(), out.masks[k].data_ptr()
-    b.workspace, b.workspace_bytes = ws.data_ptr(), ws.numel()
     p = _lib.NodeBatchPad()
     p.n_rows, p.nnz_norm, p.nnz_fea, p.n_edges = N, Ca, Cf, E
     p.step, p.status, p.counts = step.data_ptr(), out.status.data_ptr(), out.counts.data_ptr()
-    if quant is None:
-        check(lib.sgx_node_batch_sample_padded(ctypes.byref(b), ctypes.byref(p), _stream()), "sgx_node_batch_sample_padded")
-    else:
-        q = _lib.NodeBatchQuant()
-        q.n_sets, q.qbits = len(sets), int(quant.w_qbits)
-        for k, (qc, (q_val, q_dead, q_lean)) in enumerate(zip(sets.values(), out.quant)):
-            q.inv_scale_adj[k], q.zero_adj[k] = float(1 / qc.a_s), float(qc.a_z)
-            q.values_q[k], q.dead_row_q[k], q.values_lean[k] = q_val.data_ptr(), q_dead.data_ptr(), q_lean.data_ptr()
-        check(lib.sgx_node_batch_sample_padded_quant(ctypes.byref(b), ctypes.byref(p), ctypes.byref(q), _stream()),
-              "sgx_node_batch_sample_padded_quant")
+    check(*_node_batch_call(b, p, _node_batch_quant_desc(sets, out)))
     s = PaddedNodeSample(out.n_id[:N], None, out.pos[:E], B, [], [])
     s.buffers, s.counts, s.status = out, out.counts, out.status
     s.out_rowptr, s.out_col = out.rowptr[:N + 1], out.col[:E]
-    s.adj_norm = A = Csr(out.n_rowptr[:N + 1], out.n_col[:Ca], out.n_val[:Ca], N).with_facts(out.dead[:N], True, cap.max_row)
-    # the quantised adjacencies with the padded batch's constant facts: one kernel path for every batch, nothing read back
-    for key, (q_val, q_dead, q_lean) in zip(sets, out.quant):
-        Q = Csr(A.rowptr, A.col, q_val[:Ca], N).with_facts(q_dead[:N], True, cap.max_row)
-        Q._lean_values = Csr(A.rowptr, A.col, q_lean[:Ca], N)
-        A._quantized[key] = Q
-    s.edge_index, s.edge_index_agg = out.ei[:2 * E].view(2, E), out.ei_agg[:2 * E].view(2, E)
-    s.fea = None
-    if features is not None:
-        s.fea = Csr(out.f_rowptr[:N + 1], out.f_col[:Cf], out.f_val[:Cf], features.n_cols).with_facts(
-            max_row=max(features._max_row, 64))
-    s.y = None if y is None else out.y[:N]
-    s.masks = [m[:N] for m in out.masks]
-    return s
+    # the capacity's constant facts: one kernel path for every batch, nothing read back
+    return _wrap_node_batch(s, out, sets, features, N, E, Ca, Cf, True, [True] * len(sets), cap.max_row,
+                            None if features is None else max(features._max_row, 64))
 
 
 def sample_node_batch(csr, seeds, fanouts, seed=0, step=0, fill=0, dtype=torch.float32, edge_weight=None, features=None,
@@ -1386,120 +1457,33 @@ def sample_node_batch(csr, seeds, fanouts, seed=0, step=0, fill=0, dtype=torch.f
     the exact quantised mask) and the lean mask values.  The constants must leave fq(1) > 0 and fq(0) == 0 (SgxError
     otherwise): a filler row is then not dead and its spare entries carry no weight.  out= holds one (values, mask, lean
     values) triple per distinct constant set; one built for another number of sets is refused."""
-    _dev(seeds, "seeds")
-    fan = [int(k) for k in fanouts]
-    dev = csr.rowptr.device
+    fan, fan_c = _fan_array(fanouts)
+    seeds, masks = _check_node_batch(csr, seeds, dtype, edge_weight, features, y, masks, quant)
+    sets = _adj_quant_sets(quant)
     if pad is not None:
-        if quant is not None and dtype != torch.float32:
-            raise ValueError("sample_node_batch: quant needs dtype=torch.float32 (the quantised layer works on float32 buffers)")
-        if tuple(fan) != pad.fanouts:
-            raise ValueError("sample_node_batch: pad= was computed for other fan-outs")
-        masks = list(masks)
-        if len(masks) > 3:
-            raise ValueError("sample_node_batch gathers up to three masks")
-        return _sample_node_batch_padded(csr, seeds.to(torch.int32).contiguous(), seed, step, fill, dtype, edge_weight,
-                                         features, y, masks, pad, out, quant)
+        return _sample_node_batch_padded(csr, seeds, fan, fan_c, seed, step, fill, dtype, edge_weight, features, y, masks, sets,
+                                         pad, out)
     if out is not None:
         raise ValueError("sample_node_batch: out= needs pad=")
-    if quant is not None and dtype != torch.float32:
-        raise ValueError("sample_node_batch: quant needs dtype=torch.float32 (the quantised layer works on float32 buffers)")
-    seeds = seeds.to(torch.int32).contiguous()
-    B, H, n = seeds.numel(), len(fan), csr.n_rows
-    masks = list(masks)
-    if len(masks) > 3:
-        raise ValueError("sample_node_batch gathers up to three masks")
-    fan_c = (ctypes.c_int32 * max(H, 1))(*fan)
-    max_nodes, max_edges = ctypes.c_int64(0), ctypes.c_int64(0)
-    nbytes = lib.sgx_node_batch_workspace_bytes(n, csr.nnz, B, H, fan_c, ctypes.byref(max_nodes), ctypes.byref(max_edges))
-    if nbytes == 0:
-        raise ValueError(f"sample_node_batch: bad arguments (n_nodes {n}, nnz {csr.nnz}, batch {B}, fanouts {fan}): "
-                         "fan-outs must be >= -1, 1 to 64 hops, batch <= n_nodes")
-    mn, me = max_nodes.value, max_edges.value
-    i32 = lambda k: torch.empty(max(int(k), 1), dtype=torch.int32, device=dev)
-    n_id, rowptr, col, pos = i32(mn), i32(mn + 1), i32(me), i32(me)
-    n_rowptr, n_col = i32(mn + 1), i32(me + mn)
-    n_val = torch.empty(max(me + mn, 1), dtype=dtype, device=dev)
-    dead = torch.empty(max(mn, 1), dtype=torch.bool, device=dev)
-    ei = torch.empty(max(2 * me, 1), dtype=torch.int64, device=dev)
-    ei_agg = torch.empty(max(2 * me, 1), dtype=torch.int64, device=dev)
+    dev, B, H = csr.rowptr.device, seeds.numel(), len(fan)
+    ws, mn, me = _sampler_workspace("sample_node_batch", lib.sgx_node_batch_workspace_bytes, csr, B, fan, fan_c)
+    fea_capacity = None if features is None else min(features.nnz, mn * features._max_row)
+    out = NodePadBuffers.worst_case(mn, me, dtype, dev, fea_capacity, y is not None, len(masks), len(sets),
+                                    _node_map(dev, csr.n_rows))
+    b = _node_batch_desc(csr, seeds, fan, fan_c, seed, dtype, edge_weight, fill, features, y, masks, out, ws)
+    b.step = int(step) & (2**64 - 1)
     hop_nodes, hop_edges = (ctypes.c_int64 * (H + 1))(), (ctypes.c_int64 * (H + 1))()
-    node_map = _node_map(dev, n)
-    ws = _workspace(dev, nbytes)
-    b = _lib.NodeBatch()
-    b.rowPtr, b.columnIndex, b.n_nodes, b.nnz = csr.rowptr.data_ptr(), csr.col.data_ptr(), n, csr.nnz
-    b.seeds, b.batch, b.n_hops, b.fanouts = (seeds.data_ptr() if B else None), B, H, fan_c
-    b.dtype = dtype_code(dtype)
-    b.seed, b.step = int(seed) & (2**64 - 1), int(step) & (2**64 - 1)
-    b.node_map, b.n_id, b.out_rowPtr, b.out_col, b.edge_pos = (node_map.data_ptr(), n_id.data_ptr(), rowptr.data_ptr(),
-                                                               col.data_ptr(), pos.data_ptr())
-    b.max_nodes, b.max_edges, b.hop_nodes, b.hop_edges = mn, me, hop_nodes, hop_edges
-    if edge_weight is not None:
-        _dev(edge_weight, "edge_weight")
-        if edge_weight.dtype != torch.float32 or edge_weight.numel() != csr.nnz:
-            raise ValueError("edge_weight must be float32 [csr.nnz]")
-        b.edge_weight = edge_weight.data_ptr()
-    b.fill = float(fill)
-    b.rowPtr_norm, b.columnIndex_norm, b.values_norm = n_rowptr.data_ptr(), n_col.data_ptr(), n_val.data_ptr()
-    b.dead_row, b.edge_index, b.edge_index_agg = dead.data_ptr(), ei.data_ptr(), ei_agg.data_ptr()
-    f_rowptr = f_col = f_val = None
+    b.hop_nodes, b.hop_edges = hop_nodes, hop_edges
     if features is not None:
-        if features.val.dtype != torch.float32 or features.n_rows != n or features._max_row is None:
-            raise ValueError("features must be the feature_csr of the graph's x (fp32 values, one row per node)")
-        cap = min(features.nnz, mn * features._max_row)
-        f_rowptr, f_col = i32(mn + 1), i32(cap)
-        f_val = torch.empty(max(cap, 1), dtype=dtype, device=dev)
-        b.rowPtr_x, b.columnIndex_x, b.values_x = features.rowptr.data_ptr(), features.col.data_ptr(), features.val.data_ptr()
-        b.rowPtr_fea, b.columnIndex_fea, b.values_fea, b.fea_capacity = f_rowptr.data_ptr(), f_col.data_ptr(), f_val.data_ptr(), cap
-    y_out = None
-    if y is not None:
-        _dev(y, "y")
-        if y.dtype != torch.int64 or y.numel() != n:
-            raise ValueError("y must be int64 [n_nodes]")
-        y_out = torch.empty(max(mn, 1), dtype=torch.int64, device=dev)
-        b.y, b.y_out = y.data_ptr(), y_out.data_ptr()
-    m_out = []
-    for k, m in enumerate(masks):
-        _dev(m, "mask")
-        if m.dtype != torch.bool or m.numel() != n:
-            raise ValueError("masks must be bool [n_nodes]")
-        m_out.append(torch.empty(max(mn, 1), dtype=torch.bool, device=dev))
-        b.mask[k], b.mask_out[k] = m.data_ptr(), m_out[k].data_ptr()
-    b.workspace, b.workspace_bytes = ws.data_ptr(), ws.numel()
-    if quant is None:
-        status = lib.sgx_node_batch_sample(ctypes.byref(b), _stream())
-    else:
-        # one constant set per distinct key of the two layers' constants (the demo's layers share the adjacency's)
-        sets = {_adj_quant_key(qc): qc for qc in (quant, quant.second_layer())}
-        q = _lib.NodeBatchQuant()
-        q.n_sets, q.qbits = len(sets), int(quant.w_qbits)
-        q_out = []
-        for k, qc in enumerate(sets.values()):
-            q_val, q_lean = (torch.empty(max(me + mn, 1), dtype=torch.float32, device=dev) for _ in range(2))
-            q_dead = torch.empty(max(mn, 1), dtype=torch.bool, device=dev)
-            q.inv_scale_adj[k], q.zero_adj[k] = float(1 / qc.a_s), float(qc.a_z)
-            q.values_q[k], q.dead_row_q[k], q.values_lean[k] = q_val.data_ptr(), q_dead.data_ptr(), q_lean.data_ptr()
-            q_out.append((q_val, q_dead, q_lean))
-        status = lib.sgx_node_batch_sample_quant(ctypes.byref(b), ctypes.byref(q), _stream())
-    if status not in (0, _lib.SGX_ERR_SEEDS):
-        node_map.fill_(SAMPLE_SENTINEL)                 # (sgx.h: the map is restored on success and on SGX_ERR_SEEDS only)
-    check(status, "sgx_node_batch_sample" if quant is None else "sgx_node_batch_sample_quant")
-    N, E, nn, nf = hop_nodes[H], hop_edges[H], b.nnz_norm, b.nnz_fea
-    adj = Csr(rowptr[:N + 1], col[:E], torch.ones(E, dtype=torch.float32, device=dev), N)
-    s = NodeSample(n_id[:N], adj, pos[:E], B, hop_nodes[:], hop_edges[:])
-    s.adj_norm = Csr(n_rowptr[:N + 1], n_col[:nn], n_val[:nn], N).with_facts(dead[:N], b.has_dead_rows, b.max_row)
-    if quant is not None:
-        A = s.adj_norm
-        for k, (key, (q_val, q_dead, q_lean)) in enumerate(zip(sets, q_out)):
-            Q = Csr(A.rowptr, A.col[:nn], q_val[:nn], N).with_facts(q_dead[:N], q.has_dead_rows_q[k], b.max_row)
-            Q._lean_values = Csr(A.rowptr, A.col[:nn], q_lean[:nn], N)
-            A._quantized[key] = Q
-    s.edge_index, s.edge_index_agg = ei[:2 * E].view(2, E), ei_agg[:2 * E].view(2, E)
-    s.fea = None
-    if features is not None:
-        s.fea = Csr(f_rowptr[:N + 1], f_col[:nf], f_val[:nf], features.n_cols).with_facts(max_row=features._max_row)
-    s.y = None if y_out is None else y_out[:N]
-    s.masks = [m[:N] for m in m_out]
-    return s
+        b.fea_capacity = fea_capacity
+    q = _node_batch_quant_desc(sets, out)
+    status, call = _node_batch_call(b, None, q)
+    _check_sample(status, out.node_map, call)
+    N, E = hop_nodes[H], hop_edges[H]                   # what the call read back, inside its one synchronisation
+    adj = Csr(out.rowptr[:N + 1], out.col[:E], torch.ones(E, dtype=torch.float32, device=dev), N)
+    s = NodeSample(out.n_id[:N], adj, out.pos[:E], B, hop_nodes[:], hop_edges[:])
+    return _wrap_node_batch(s, out, sets, features, N, E, b.nnz_norm, b.nnz_fea, b.has_dead_rows, q.has_dead_rows_q if sets else (), b.max_row,
+                            None if features is None else features._max_row)
 
 
 # ---- a batch of small graphs through the whole GCN stack in one launch (sgx_stack_forward) ----------------------------
@@ -1739,15 +1723,12 @@ class GraphSet:
                 raise ValueError("GraphSet holds fewer than 2^31 normalised entries")
             p = self._sym_norm2 = _PreparedAdjacency(A, np.diff(rp[self._node_ptr_host]), int(np.diff(rp).max()))
             p.dead, p.has_dead = self._dead_facts(A)
-        keys = []
-        for qc in (() if quant is None else (quant, quant.second_layer())):
-            key = _adj_quant_key(qc)
+        sets = _adj_quant_sets(quant)
+        for key, qc in sets.items():
             if key not in p.quant:
                 Q = p.adj.quantized(qc)
                 p.quant[key] = (Q.val,) + self._dead_facts(Q)
-            if key not in keys:                  # (the demo's two layers share the adjacency's constants)
-                keys.append(key)
-        return GraphExtras(p, dtypes, tuple(keys))
+        return GraphExtras(p, dtypes, tuple(sets))
 
     def prepare(self, idx):
         """The batch of graph ids `idx` (a host sequence, in batch order) ready to collate: its exclusive offsets

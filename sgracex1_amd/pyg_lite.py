@@ -475,8 +475,8 @@ class NeighborLoader:
             if cap.nnz_norm >= 1 << 20 or cap.nnz_fea >= 1 << 20:
                 raise ValueError(f"pad=True: the capacity ({cap.nnz_norm} adjacency, {cap.nnz_fea} feature entries) reaches 2^20 "
                                  "entries: such a batch wants a plan, and a plan costs a read-back")
-            n_quant = 0 if quant is None else len({ops._adj_quant_key(qc) for qc in (quant, quant.second_layer())})
-            self.buffers = ops.NodePadBuffers(cap, n, dtype, dev, x.shape[1], self.y is not None, len(self.masks), n_quant)
+            self.buffers = ops.NodePadBuffers(cap, n, dtype, dev, x.shape[1], self.y is not None, len(self.masks),
+                                              len(ops._adj_quant_sets(quant)))
             self.counts = self.buffers.counts
             self.seeds_buf = torch.zeros(B, dtype=torch.int32, device=dev)      # what a recorded sample reads: load()
             self.step_buf = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -516,31 +516,9 @@ class NeighborLoader:
     def padded_batch(self, input_id=None):
         """The padded NodeBatch of what load() put in place, drawn into the loader's one set of buffers: every launch of
         it is capturable, and it reads nothing back."""
-        from . import ops
-        s = ops.sample_node_batch(self.csr, self.seeds_buf, self.num_neighbors, seed=self.seed, step=self.step_buf,
-                                  fill=self.fill, dtype=self.dtype, features=self.fea, y=self.y,
-                                  masks=[m for _, m in self.masks], quant=self.quant, pad=self.capacity, out=self.buffers)
-        x = ops.pack_rows(self.data.x, s.n_id, out=self.x_buf)
-        A, n, cap = s.adj_norm, self.capacity.n_rows, self.capacity
-        ops.attach(x, ("fea_csr", self.dtype), s.fea)
-        ops.attach(s.edge_index_agg, ("sym_norm2", n, 1, self.dtype), (s.edge_index_agg, A.val, A))
-        if self.transposed:
-            if cap.nnz_fea < 64 * s.fea.n_cols:          # (ops.csr_transpose builds a plan, with its read-back, from there on)
-                fea32 = s.fea
-                if self.dtype != torch.float32:
-                    fea32 = ops.attach(x, ("fea_csr", torch.float32),
-                                       ops.Csr(s.fea.rowptr, s.fea.col, s.fea.val.float(), s.fea.n_cols).with_facts(
-                                           max_row=s.fea._max_row))
-                ops.attach(x, ("fea_csr_t", torch.float32), ops.csr_transpose(fea32, method="device"))
-            A._transpose_pattern = ops.csr_transpose(A, return_order=True, method="device")
-        fields = dict(x=x, edge_index=s.edge_index, edge_index_agg=s.edge_index_agg, adj_norm=A, n_id=s.n_id.long(),
-                      adj=None, batch_size=s.batch_size, input_id=input_id, num_sampled_nodes=None,
-                      num_sampled_edges=None, num_real_nodes=None)
-        if s.y is not None:
-            fields["y"] = s.y
-        for (name, _), m in zip(self.masks, s.masks):
-            fields[name] = m
-        return NodeBatch(**fields)
+        s = self._sample(self.seeds_buf, self.step_buf, pad=self.capacity, out=self.buffers)
+        return self._hand_over(s, self.x_buf, input_id)
+
 
     def status(self):
         """Reads the OR-ed status word of the padded batches drawn since the last call back (one synchronisation), clears
@@ -552,26 +530,38 @@ class NeighborLoader:
             # (the sampler's status bits as sgx_node_batch_sample maps them: 1 = seeds, else a capacity = SGX_ERR_SHAPE, -2)
             raise _lib.SgxError(_lib.SGX_ERR_SEEDS if st & 1 else -2, "sgx_node_batch_sample_padded")
 
-    def _prepared(self, seeds, input_id, step):
+    def _sample(self, seeds, step, **pad):
         from . import ops
-        s = ops.sample_node_batch(self.csr, seeds, self.num_neighbors, seed=self.seed, step=step, fill=self.fill,
-                                  dtype=self.dtype, features=self.fea, y=self.y, masks=[m for _, m in self.masks],
-                                  quant=self.quant)
-        x = ops.pack_rows(self.data.x, s.n_id)
-        A, n = s.adj_norm, s.n_id.numel()
-        ops.attach(x, ("fea_csr", self.dtype), s.fea)
+        return ops.sample_node_batch(self.csr, seeds, self.num_neighbors, seed=self.seed, step=step, fill=self.fill,
+                                     dtype=self.dtype, features=self.fea, y=self.y, masks=[m for _, m in self.masks],
+                                     quant=self.quant, **pad)
+
+    def _prepared(self, seeds, input_id, step):
+        """The unpadded layer-ready NodeBatch of `seeds` at `step`: the sampler's one synchronisation."""
+        return self._hand_over(self._sample(seeds, step), None, input_id)
+
+    def _hand_over(self, s, x_buf, input_id):
+        """The NodeBatch of the NodeSample `s` with everything the layers look up attached: x gathered into x_buf (the
+        padded loader's buffer; None: a fresh tensor of an unpadded batch).  Launches only, no synchronisation of its own."""
+        from . import ops
+        padded = x_buf is not None
+        x = ops.pack_rows(self.data.x, s.n_id, out=x_buf)
+        A, fea, n = s.adj_norm, s.fea, s.n_id.numel()           # (n: the capacity's rows when padded)
+        ops.attach(x, ("fea_csr", self.dtype), fea)
         ops.attach(s.edge_index_agg, ("sym_norm2", n, 1, self.dtype), (s.edge_index_agg, A.val[:A.nnz], A))
         if self.transposed:
-            fea32 = s.fea
-            if self.dtype != torch.float32:              # (the values alone are cast: never through a dense tensor)
-                fea32 = ops.attach(x, ("fea_csr", torch.float32),
-                                   ops.Csr(s.fea.rowptr, s.fea.col[:s.fea.nnz], s.fea.val[:s.fea.nnz].float(),
-                                           s.fea.n_cols).with_facts(max_row=s.fea._max_row))
-            ops.attach(x, ("fea_csr_t", torch.float32), ops.csr_transpose(fea32, method="device"))
+            # (padded: ops.csr_transpose builds a plan, with its read-back, from 64 entries per feature column on)
+            if not padded or self.capacity.nnz_fea < 64 * fea.n_cols:
+                fea32 = fea
+                if self.dtype != torch.float32:          # (the values alone are cast: never through a dense tensor)
+                    fea32 = ops.attach(x, ("fea_csr", torch.float32),
+                                       ops.Csr(fea.rowptr, fea.col[:fea.nnz], fea.val[:fea.nnz].float(), fea.n_cols).with_facts(
+                                           max_row=fea._max_row))
+                ops.attach(x, ("fea_csr_t", torch.float32), ops.csr_transpose(fea32, method="device"))
             A._transpose_pattern = ops.csr_transpose(A, return_order=True, method="device")
         fields = dict(x=x, edge_index=s.edge_index, edge_index_agg=s.edge_index_agg, adj_norm=A, n_id=s.n_id.long(),
                       adj=s.adj, batch_size=s.batch_size, input_id=input_id, num_sampled_nodes=s.num_sampled_nodes,
-                      num_sampled_edges=s.num_sampled_edges, num_real_nodes=n)
+                      num_sampled_edges=s.num_sampled_edges, num_real_nodes=None if padded else n)
         if s.y is not None:
             fields["y"] = s.y
         for (name, _), m in zip(self.masks, s.masks):

@@ -300,3 +300,92 @@ def test_a_training_epoch_on_prepared_batches_does_not_synchronise(attention, le
         torch.cuda.set_sync_debug_mode(0)
         config.restore(old)
         sgrace.init_SGRACE()
+
+
+def _tiny_graph(n=40, seed=3):
+    """40 nodes, 150 edges i -> j, none into nodes 0..2 -> (n, edge_index [2, E] int64 on the host, the CSR on the targets
+    as NeighborLoader builds it: rowptr, col)."""
+    rng = np.random.default_rng(seed)
+    m = rng.random((n, n)) < 0.1
+    m[:, :3] = False
+    src, dst = np.nonzero(m)
+    rowptr = np.zeros(n + 1, np.int64)
+    np.cumsum(np.bincount(dst, minlength=n), out=rowptr[1:])
+    return n, torch.as_tensor(np.stack([src, dst])), rowptr, src[np.argsort(dst * n + src, kind="stable")].astype(np.int64)
+
+
+def _bits(t):
+    return _np(t.contiguous().view(torch.uint8)).tobytes()
+
+
+def _live_columns(T, n):
+    """The CSR `T` without the entries of columns >= n (what filler rows add to a transposed matrix) -> rowptr, col, val."""
+    rowptr, col, val = _np(T.rowptr).astype(np.int64), _np(T.col[:T.nnz]), T.val[:T.nnz]
+    keep = col < n
+    kept = np.concatenate([[0], np.cumsum(keep)])
+    return kept[rowptr], col[keep], _bits(val[torch.as_tensor(keep, device=val.device)])
+
+
+@pytest.mark.parametrize("fanouts", [[3, 2], [3, 0]])
+@pytest.mark.parametrize("dtype,bits", [(torch.float32, None), (torch.float16, None), (torch.float32, 8)], ids=["f32", "f16", "f32-q8"])
+def test_padded_loader_batch_carries_the_unpadded_batches_attachments(dtype, bits, fanouts):
+    """One hand-over for both kinds of batch: NeighborLoader(prepare="sym_norm2", transposed=True) with pad=True attaches,
+    for the same seeds and step, the same entries under the same keys as without -- ("fea_csr", dtype), ("fea_csr", float32),
+    ("fea_csr_t", float32), ("sym_norm2", n, 1, dtype) with n each batch's own size, adj_norm._transpose_pattern and the
+    keys of adj_norm._quantized -- and every one holds the unpadded batch's bits on its live part: the first rows and entries
+    by loader.counts of a matrix over the batch's rows, the entries of the live columns of a transposed one.  Seed 1 has no
+    in-edge (a row without a sampled neighbour); under [3, 0] the last hop samples no edge."""
+    from sgracex1_amd import ops, pyg_lite, quant
+    F32 = torch.float32
+    n_nodes, ei, rowptr, col = _tiny_graph()
+    seeds, step = [1, 17, 30, 8], 5
+    n_id, rp, _, _, hop_nodes, hop_edges = R.sample(rowptr, col, seeds, fanouts, seed=7, step=step)
+    assert np.diff(rp)[0] == 0 and (hop_edges[2] == hop_edges[1]) == (fanouts[1] == 0)      # the two cases, by the restatement
+    x = torch.as_tensor(_features(n_nodes, f=8, seed=2), device=DEV)       # (rows 0, 17 and 34 all zero; 17 is a seed)
+    data = pyg_lite.NodeData(x, ei.to(DEV), torch.arange(n_nodes, device=DEV) % 5, train_mask=torch.arange(n_nodes, device=DEV) % 2 == 0,
+                             val_mask=torch.arange(n_nodes, device=DEV) % 3 == 0)
+    kw = dict(batch_size=len(seeds), seed=7, prepare="sym_norm2", transposed=True, dtype=dtype, fill=1,
+              quant=None if bits is None else quant.constants(bits))
+    plain, padded = pyg_lite.NeighborLoader(data, fanouts, **kw), pyg_lite.NeighborLoader(data, fanouts, pad=True, **kw)
+    seeds_dev = torch.as_tensor(seeds, device=DEV)
+    u = plain._prepared(seeds_dev, None, step)
+    assert padded.padded(seeds_dev)
+    padded.load(seeds_dev, step)
+    p = padded.padded_batch(None)
+    padded.status()
+    n, e, a, f = padded.counts[:4].tolist()
+    N = padded.capacity.n_rows
+    assert (n, e, a, f) == (u.num_real_nodes, sum(u.num_sampled_edges), u.adj_norm.nnz, ops.recorded(u.x, ("fea_csr", dtype)).nnz)
+    assert np.array_equal(_np(u.n_id), n_id) and u.num_sampled_edges[-1] == hop_edges[2] - hop_edges[1] and p.num_nodes == N > n
+
+    def same_prefix(P, U, rows, entries):
+        assert U.n_rows == rows and U.nnz == entries
+        assert _bits(P.rowptr[:rows + 1]) == _bits(U.rowptr) and _bits(P.col[:entries]) == _bits(U.col[:entries])
+        assert P.val.dtype == U.val.dtype and _bits(P.val[:entries]) == _bits(U.val[:entries])
+
+    def same_live_columns(P, U):
+        assert P.n_rows == U.n_rows and P.val.dtype == U.val.dtype
+        (p_ptr, p_col, p_val), (u_ptr, u_col, u_val) = _live_columns(P, n), _live_columns(U, n)
+        assert np.array_equal(p_ptr, u_ptr) and u_ptr[-1] == U.nnz and np.array_equal(p_col, u_col) and p_val == u_val
+
+    for key in [("fea_csr", dtype), ("fea_csr", F32)]:
+        same_prefix(ops.recorded(p.x, key), ops.recorded(u.x, key), n, f)
+        assert ops.recorded(p.x, key).n_cols == ops.recorded(u.x, key).n_cols == 8
+    same_live_columns(ops.recorded(p.x, ("fea_csr_t", F32)), ops.recorded(u.x, ("fea_csr_t", F32)))
+    hit_p, hit_u = ops.recorded(p.edge_index_agg, ("sym_norm2", N, 1, dtype)), ops.recorded(u.edge_index_agg, ("sym_norm2", n, 1, dtype))
+    assert hit_p[0] is p.edge_index_agg and hit_u[0] is u.edge_index_agg and _bits(p.edge_index_agg[:, :e]) == _bits(u.edge_index_agg)
+    assert hit_p[2] is p.adj_norm and hit_u[2] is u.adj_norm
+    assert hit_p[1].dtype == hit_u[1].dtype == dtype and _bits(hit_p[1][:a]) == _bits(hit_u[1][:a])
+    same_prefix(p.adj_norm, u.adj_norm, n, a)
+    assert _bits(p.adj_norm.dead_rows[:n]) == _bits(u.adj_norm.dead_rows)
+    (Pt, p_order), (Ut, u_order) = p.adj_norm._transpose_pattern, u.adj_norm._transpose_pattern
+    same_prefix(Pt, Ut, n, a)                                       # (a filler row's entries all stand in its own column)
+    assert _bits(p_order[:a]) == _bits(u_order[:a])
+    assert list(p.adj_norm._quantized) == list(u.adj_norm._quantized) and bool(u.adj_norm._quantized) == (bits is not None)
+    for key, Q in u.adj_norm._quantized.items():
+        G = p.adj_norm._quantized[key]
+        same_prefix(G, Q, n, a)
+        same_prefix(G._lean_values, Q._lean_values, n, a)
+        assert _bits(G.dead_rows[:n]) == _bits(Q.dead_rows)
+    for name in ("x", "y", "train_mask", "val_mask", "n_id"):
+        assert _bits(getattr(p, name)[:n]) == _bits(getattr(u, name)), name
