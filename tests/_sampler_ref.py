@@ -79,3 +79,37 @@ def sample(rowptr, col, seeds, fanouts, seed=0, step=0):
     out_rowptr = [row_start.get(i, len(out_col)) for i in range(len(n_id))] + [len(out_col)]
     return (np.asarray(n_id, np.int64), np.asarray(out_rowptr, np.int64), np.asarray(out_col, np.int64),
             np.asarray(edge_pos, np.int64), hop_nodes, hop_edges)
+
+
+def sample_take_all(rowptr, col, seeds, n_hops):
+    """sample(rowptr, col, seeds, [-1] * n_hops) -- or any fan-outs no row's degree exceeds -- in closed form: every
+    frontier row keeps all its positions, so nothing is drawn and a hop is a handful of array operations.  For the
+    frontiers of millions of rows that sample()'s loop over rows cannot walk.  Same six values, same ValueError."""
+    rowptr, col = np.asarray(rowptr, np.int64), np.asarray(col, np.int64)
+    seeds = np.asarray(seeds, np.int64).reshape(-1)
+    local = np.full(len(rowptr) - 1, -1, np.int64)         # node -> local id, -1 = not in n_id yet
+    local[seeds] = np.arange(len(seeds))
+    if (local[seeds] != np.arange(len(seeds))).any():
+        raise ValueError("repeated seed")
+    n_id, row_ends, out_col, edge_pos = [seeds], [], [], []
+    hop_nodes, hop_edges = [len(seeds)], [0]
+    frontier = seeds
+    for _ in range(n_hops):
+        deg = rowptr[frontier + 1] - rowptr[frontier]
+        ends = np.cumsum(deg)
+        # the ranges [rowptr[v], rowptr[v + 1]) of the frontier rows, one behind the other
+        pos = np.repeat(rowptr[frontier] - (ends - deg), deg) + np.arange(int(deg.sum()))
+        c = col[pos]
+        fresh = c[local[c] < 0]
+        first = np.sort(np.unique(fresh, return_index=True)[1])          # first appearance of every new node in the hop
+        frontier = fresh[first]
+        local[frontier] = hop_nodes[-1] + np.arange(len(frontier))
+        n_id.append(frontier)
+        row_ends.append(hop_edges[-1] + ends)
+        out_col.append(local[c])
+        edge_pos.append(pos)
+        hop_nodes.append(hop_nodes[-1] + len(frontier))
+        hop_edges.append(hop_edges[-1] + len(pos))
+    # the rows of the nodes new at the last hop are empty
+    out_rowptr = np.concatenate([np.zeros(1, np.int64)] + row_ends + [np.full(len(frontier), hop_edges[-1], np.int64)])
+    return (np.concatenate(n_id), out_rowptr, np.concatenate(out_col), np.concatenate(edge_pos), hop_nodes, hop_edges)

@@ -132,3 +132,102 @@ def test_sampler_argument_checks_need_no_gpu(L):
     assert call(ws=None) == -4
     assert call(ws_bytes=16) == -4
     assert L.status_string(-8) != "unknown status"
+
+
+# ---- the closed form for "every row keeps all its edges", and the graphs of tests/test_gpu_sampler_scan.py ------------
+import _sampler_scan_graphs as G
+
+
+def _same_sample(a, b):
+    for x, y in zip(a[:4], b[:4]):
+        assert x.dtype == y.dtype == np.int64 and np.array_equal(x, y)
+    assert list(a[4]) == list(b[4]) and list(a[5]) == list(b[5])
+
+
+@pytest.mark.parametrize("n_hops", [1, 2, 3])
+def test_take_all_equals_the_row_loop(n_hops):
+    # row v = the sources of the edges into v: empty rows (2, 8, 9), repeated edges (into 0 and 5), self loops (0, 3, 6),
+    # seeds that neighbour each other (0, 1, 3), columns that point back at seeds from later hops (4 -> 0, 6 -> 1, 7 -> 3)
+    edges = [(0, 0), (1, 0), (1, 0), (4, 0), (0, 1), (3, 1), (5, 1), (3, 3), (1, 3), (6, 3), (6, 3), (0, 4), (7, 4),
+             (4, 5), (4, 5), (2, 5), (6, 6), (1, 6), (8, 6), (3, 7), (9, 7), (5, 7)]
+    rowptr, col = _csr(10, edges)
+    for seeds in ([0, 1, 3], [3, 0, 1], [2], [8, 2, 9], [5], [], list(range(9, -1, -1))):
+        _same_sample(R.sample_take_all(rowptr, col, seeds, n_hops), R.sample(rowptr, col, seeds, [-1] * n_hops))
+    # any fan-out no degree exceeds is the same sample (the largest degree here is 4)
+    _same_sample(R.sample_take_all(rowptr, col, [0, 1, 3], n_hops), R.sample(rowptr, col, [0, 1, 3], [4] * n_hops, seed=3, step=9))
+    with pytest.raises(ValueError):
+        R.sample_take_all(rowptr, col, [1, 4, 1], n_hops)
+    # random multigraphs, a third of the rows empty, and the scan graphs' builders at sizes the row loop can walk
+    rng = np.random.default_rng(n_hops)
+    for n in (1, 7, 60):
+        deg = rng.integers(0, 6, n) * (rng.random(n) < 0.67)
+        rp = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+        c = rng.integers(0, n, rp[-1])
+        seeds = rng.permutation(n)[:max(1, n // 4)]
+        _same_sample(R.sample_take_all(rp, c, seeds, n_hops), R.sample(rp, c, seeds, [-1] * n_hops))
+    for g in (G.frontier_graph(50), G.edge_graph(70), G.second_hop_graph(40), G.node_batch_graph(90, new=20)):
+        _same_sample(R.sample_take_all(g.rowptr, g.col, g.seeds, n_hops), R.sample(g.rowptr, g.col, g.seeds, [-1] * n_hops))
+
+
+def _hop0(g):
+    """(degrees of the seeds' rows, first-appearance flags of their slots) from the arrays alone."""
+    assert len(np.unique(g.seeds)) == len(g.seeds) and g.rowptr[0] == 0 and g.rowptr[-1] == len(g.col)
+    assert (np.diff(g.rowptr) >= 0).all() and np.diff(g.rowptr).max() <= 3
+    deg = g.rowptr[g.seeds + 1] - g.rowptr[g.seeds]
+    c = np.concatenate([g.col[g.rowptr[v]:g.rowptr[v + 1]] for v in g.seeds.tolist()]) if len(g.seeds) < 5000 else None
+    ends = np.cumsum(deg)
+    slots = g.col[np.repeat(g.rowptr[g.seeds] - (ends - deg), deg) + np.arange(int(deg.sum()))]
+    assert c is None or np.array_equal(c, slots)
+    is_seed = np.zeros(len(g.rowptr) - 1, bool)
+    is_seed[g.seeds] = True
+    first = np.zeros(len(slots), bool)
+    first[np.unique(slots, return_index=True)[1]] = True
+    return deg, first & ~is_seed[slots]
+
+
+@pytest.mark.parametrize("size", G.SIZES)
+def test_scan_graphs_hold_the_item_counts_they_claim(size):
+    """The cap on the degrees (3) and the exact item counts are what test_gpu_sampler_scan.py's sizes rest on."""
+    g = G.frontier_graph(size)
+    deg, flags = _hop0(g)
+    assert g.frontier == len(g.seeds) == size and g.edges == deg.sum() and g.new == flags.sum()
+    assert G.seams_hold(deg > 0) and G.seams_hold(flags)
+    assert not np.array_equal(g.seeds, np.sort(g.seeds)) or size == 1
+    g = G.edge_graph(size)
+    deg, flags = _hop0(g)
+    assert g.edges == deg.sum() == len(flags) == size and g.frontier == len(g.seeds) and g.new == flags.sum()
+    assert G.seams_hold(flags)
+    if size > 8:                                            # every kind of column that is not a first appearance
+        ends = np.cumsum(deg)
+        slots = g.col[np.repeat(g.rowptr[g.seeds] - (ends - deg), deg) + np.arange(size)]
+        named = np.isin(slots, g.seeds)
+        assert named.any() and (~named & ~flags).any() and (slots == np.repeat(g.seeds, deg)).any()
+
+
+def test_scan_graphs_of_the_other_tests_hold_their_counts():
+    top = G.TOP + 1
+    g = G.second_hop_graph(top)
+    deg, flags = _hop0(g)
+    assert g.new == flags.sum() == top and g.edges == deg.sum() > 0 and g.frontier == len(g.seeds) > 0
+    deg1 = np.diff(g.rowptr)[g.fresh_ids]                   # the rows of hop 1's frontier, in its order
+    assert len(deg1) == top and G.seams_hold(deg1 > 0)
+    g = G.frontier_graph(top, (0, 1, 3))
+    deg, flags = _hop0(g)
+    assert g.frontier == len(deg) == top and set(np.unique(deg)) == {0, 1, 3} and G.seams_hold(deg > 0)
+    for k in (1, 2):                                        # rows over the fan-out in every seam tile, rows within it beside them
+        assert G.seams_hold(deg > k)
+    for nodes in (G.TILE + 1, top):
+        g = G.node_batch_graph(nodes)
+        deg, flags = _hop0(g)
+        assert len(g.seeds) + flags.sum() == nodes == len(g.n_id) and np.array_equal(g.n_id[:len(g.seeds)], g.seeds)
+        assert len(np.unique(g.n_id)) == nodes
+        ends = np.cumsum(deg)
+        slots = g.col[np.repeat(g.rowptr[g.seeds] - (ends - deg), deg) + np.arange(int(deg.sum()))]
+        loop = np.zeros(nodes, bool)                        # sampled rows that hold a self loop (the found rows are empty)
+        loop[np.repeat(np.arange(len(deg)), deg)[slots == np.repeat(g.seeds, deg)]] = True
+        assert G.seams_hold(~loop) and loop.any()
+        stored = (g.x != 0).sum(1)
+        assert g.x.dtype == np.float32 and g.x.shape == (len(g.rowptr) - 1, 3) and set(np.unique(stored)) == {0, 1, 2, 3}
+        assert G.seams_hold(stored[g.n_id] > 0)
+        if nodes > G.TOP:                                   # empty feature rows on both sides of item TOP
+            assert (stored[g.n_id[G.TOP - G.TILE:G.TOP]] == 0).any() and (stored[g.n_id[:G.TOP - G.TILE]] == 0).any()
