@@ -279,7 +279,6 @@ int gat_two_stage(const sgx_gat_args &a)
 {
     const sgx_plan *p = a.plan_any;
     const sgx_gat_scratch &L = a.lay;
-    const int thr = p->n_long > 0 ? p->long_threshold : 0;
     // One walk pays while a head spans few lanes -- every lane of a head forms the piece's 8 scores and exponentials itself, and
     // a head wider than a DPP row half sums its dots through LDS permutes (measured, tools/gat_probe.py: 8 heads x 32 columns
     // 0.286 -> 0.234 ms on the arxiv shape, one head of 64 columns 0.80 -> 0.70 ms and 8 heads 1.94 -> 0.74 ms on a 29 M-entry
@@ -292,12 +291,9 @@ int gat_two_stage(const sgx_gat_args &a)
         // no side outputs wanted: one walk over the rows, the neighbours' scores formed from the rows it gathers (gat_fused.hip)
         sgx_gat_fused_args f{};
         f.dtype = a.dtype; f.lpr = a.lpr; f.relu = a.relu; f.n_feat = a.n_feat; f.n_heads = a.n_heads;
-        f.n_work = p->row_order ? p->n_ordered : a.n_rows;
-        f.long_threshold = thr; f.vec_store = a.vec_store; f.n_tasks = thr > 0 ? p->n_tasks : 0; f.ldp = L.ldp;
+        f.n_rows = a.n_rows; f.plan = p; f.vec_store = a.vec_store; f.ldp = L.ldp;
         f.alpha = a.alpha; f.out_scale = a.out_scale;
-        f.rowptr = a.rowptr; f.col = a.col; f.row_order = p->row_order;
-        f.task_row = p->task_row; f.task_e0 = p->task_e0; f.task_e1 = p->task_e1;
-        f.long_row = p->long_row; f.long_first = p->long_first; f.n_long = p->n_long; f.n_multi = p->n_multi;
+        f.rowptr = a.rowptr; f.col = a.col;
         f.val = a.val; f.Wh = a.Wh; f.att = a.att; f.h_bytes = a.h_bytes; f.ld_bytes = a.ld_bytes;
         f.s1 = a.scratch + L.s1; f.fill = a.fill; f.D = a.D; f.ldd = a.ldd;
         f.pacc = a.scratch + L.pacc; f.pm = a.scratch + L.pm; f.pl = a.scratch + L.pl; f.stream = a.stream;

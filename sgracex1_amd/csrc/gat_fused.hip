@@ -9,7 +9,7 @@
 // registers, and the softmax costs no memory traffic at all.  exp is the hardware's v_exp_f32 on (x - max) log2(e) --
 // relative error about (2 + |x|) 2^-24 on a weight that only ever reaches the caller inside the 16- or 32-bit sums of D.
 // Rows over the plan's cut: a wavefront per task with a state per lane group, merged over the groups, the tasks of a row
-// merged in task order by gat_fused_finalize_kernel.  Same schedule as gat_weighted_kernel otherwise: degree order where
+// merged in task order by gat_fused_finalize_kernel.  The plan's row schedule as row_schedule.h states it: degree order where
 // the plan has one (its one-piece tail 64 rows per wavefront), long rows through tasks.
 // Rows without a live entry give `fill` (the dense emulation's mean row, SG.py:638-641) or 0.
 #include "gat_device.h"
@@ -172,28 +172,18 @@ __global__ __launch_bounds__(kBlock, SGX_GAT_FUSED_WAVES) void gat_fused_kernel(
 
     auto finish_row = [&](const SoftState<VEC> &st, int64_t r) {
         if (!mine) return;
-        T out[VEC];
         const float inv = st.l > 0.0f ? 1.0f / st.l : 0.0f;
-#pragma unroll
-        for (int i = 0; i < VEC; ++i) {
+        store_lane_outputs<T, VEC, SGX_STORE_ALIGNED16>(D + r * ldd, col0, n_feat, vec_store != 0, [&](int i) SGX_LAMBDA_INLINE {
             const float o = st.l > 0.0f ? st.acc[i] * inv : ((fill && col0 + i < n_feat) ? fill[col0 + i] : 0.0f);
-            out[i] = gat_finish<T>(o, relu, out_scale);
-        }
-        T *drow = D + r * ldd;
-        if (VEC > 1 && vec_store && col0 + VEC <= n_feat) {
-            *reinterpret_cast<u32x4 *>(drow + col0) = *reinterpret_cast<const u32x4 *>(out);
-        } else {
-#pragma unroll
-            for (int i = 0; i < VEC; ++i)
-                if (col0 + i < n_feat) drow[col0 + i] = out[i];
-        }
+            return gat_finish<T>(o, relu, out_scale);
+        });
     };
 
     if ((int)blockIdx.x < split_blocks) {
         // a task of a long row: every lane group of the wavefront on its own pieces, then the groups merged
-        const int task = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-        if (task >= n_tasks) return;
-        const int e0 = task_e0[task], e1 = task_e1[task];
+        const sgx_task t = schedule_task(n_tasks, task_e0, task_e1);
+        if (t.index < 0) return;
+        const int task = t.index, e0 = t.e0, e1 = t.e1;
         const float si = s1[(int64_t)task_row[task] * n_heads + my_head];
         SoftState<VEC> st;
         st.clear();
@@ -219,16 +209,13 @@ __global__ __launch_bounds__(kBlock, SGX_GAT_FUSED_WAVES) void gat_fused_kernel(
     }
     if constexpr (SHORT && LPR >= 8) {
         // the degree order's tail of one-piece rows (at most 8 entries), 64 rows per wavefront: row ids, row pointers and the
-        // (column, value) pieces of 64 rows are one round trip each instead of one per 64 / LPR rows (spmm_csr.hip's
-        // spmm_short_rows, gat_weighted_kernel's SHORT); a row is one fold
+        // (column, value) pieces of 64 rows are one round trip each instead of one per 64 / LPR rows (row_schedule.h, part 3);
+        // a row is one fold
         if ((int)blockIdx.x >= short_first) {
-            const int64_t i0 = (int64_t)n_multi + ((int64_t)((int)blockIdx.x - short_first) * (kBlock / 64) + (threadIdx.x >> 6)) * 64;
-            if (i0 >= n_work) return;
-            const int64_t idx = i0 + lane;
-            const bool valid = idx < n_work;
-            const int rid = row_order[valid ? idx : (int64_t)n_work - 1];
-            const int re0 = rowptr[rid];
-            const int rdeg = valid ? rowptr[rid + 1] - re0 : 0;                      // at most 8 (the order's last buckets)
+            sgx_tail_tile tile;
+            if (!schedule_tail_tile(short_first, n_multi, n_work, row_order, rowptr, tile)) return;
+            const int rid = tile.r, re0 = tile.e0, rdeg = tile.deg;
+            const bool valid = tile.valid;
             constexpr int CH = 4;                        // rows per lane group and batch of requests
             for (int it0 = 0; it0 < LPR; it0 += CH) {
                 unsigned c[CH];
@@ -258,22 +245,13 @@ __global__ __launch_bounds__(kBlock, SGX_GAT_FUSED_WAVES) void gat_fused_kernel(
             }
             return;
         }
-        n_work = n_multi;                    // the walk below takes the rows of two pieces and more
     }
-    const int row_grid = (SHORT ? short_first : (int)gridDim.x) - split_blocks;
-    const int64_t wave = (int64_t)((int)blockIdx.x - split_blocks) * (kBlock / 64) + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)row_grid * (kBlock / 64);
-    for (int64_t r0 = wave * RPW; r0 < n_work; r0 += n_waves * RPW) {
-        int64_t r = r0 + grp;
-        int e0 = 0, e1 = 0;
-        bool live_row = r < n_work;
-        if (live_row) {
-            if (row_order) r = row_order[r];
-            e0 = rowptr[r];
-            e1 = rowptr[r + 1];
-            if (long_threshold > 0 && e1 - e0 > long_threshold) live_row = false;       // the tasks own it
-        }
-        if (!live_row) e1 = e0;
+    const int n_walk = (SHORT && LPR >= 8) ? n_multi : n_work;
+    int64_t r0, r_step;
+    schedule_row_range<LPR, SHORT>(split_blocks, short_first, r0, r_step);
+    for (; r0 < n_walk; r0 += r_step) {
+        int64_t r; int e0, e1;
+        const bool live_row = schedule_row<LPR>(r0, n_walk, long_threshold, row_order, rowptr, r, e0, e1);
         const float si = live_row ? s1[r * n_heads + my_head] : 0.0f;
         SoftState<VEC> st;
         st.clear();
@@ -335,31 +313,23 @@ __global__ __launch_bounds__(kBlock) void gat_fused_finalize_kernel(
 template <typename T, int VEC, int LPR, int HL>
 int launch_fused(const sgx_gat_fused_args &a)
 {
-    const int rows_per_block = (64 / LPR) * (kBlock / 64);
-    const int split_blocks = (a.n_tasks + kBlock / 64 - 1) / (kBlock / 64);
-    // the one-piece tail of a degree order 64 rows per wavefront (as the plain aggregation does, spmm_csr.hip)
-    const bool short_tail = LPR >= 8 && a.row_order && !sgx_tune().spmm_no_short_tail && a.n_multi >= 0 && a.n_multi < a.n_work &&
-                            a.n_work - a.n_multi >= 4096;
-    const int n_multi = short_tail ? a.n_multi : a.n_work;
-    const int64_t short_blocks = short_tail ? ((int64_t)(a.n_work - n_multi) + 64 * (kBlock / 64) - 1) / (64 * (kBlock / 64)) : 0;
-    int64_t row_blocks = ((int64_t)n_multi + rows_per_block - 1) / rows_per_block;
-    if (row_blocks > 256 * 512) row_blocks = 256 * 512;
-    const dim3 grid((unsigned)(split_blocks + row_blocks + short_blocks));
-    const int short_first = (int)(split_blocks + row_blocks);
+    const sgx_plan *p = a.plan;
+    // (n_feat <= LPR * VEC, the schedule's one-pass condition for the tail, always holds here: sgx_gat_fused_applicable asks it)
+    const sgx_row_schedule s = sgx_schedule_rows(p, a.n_rows, LPR, LPR * VEC, a.n_feat, true);
 #define SGX_GAT_FUSED_LAUNCH(SHORT_)                                                                                             \
-    hipLaunchKernelGGL((gat_fused_kernel<T, VEC, LPR, HL, SHORT_>), grid, dim3(kBlock), 0, a.stream, a.n_work, a.n_feat, a.n_heads,  \
+    hipLaunchKernelGGL((gat_fused_kernel<T, VEC, LPR, HL, SHORT_>), dim3(s.grid), dim3(kBlock), 0, a.stream, s.n_work, a.n_feat, a.n_heads, \
                        a.n_feat / a.n_heads, a.rowptr, a.col, (const T *)a.val, (const T *)a.Wh, a.h_bytes, a.ld_bytes,             \
-                       (const T *)a.att, a.s1, a.alpha, (T *)a.D, a.ldd, a.relu, a.out_scale, a.long_threshold, a.vec_store,        \
-                       a.row_order, split_blocks, a.n_tasks, a.task_row, a.task_e0, a.task_e1, a.pacc, a.ldp, a.pm, a.pl, a.fill,   \
-                       n_multi, short_first)
-    if (short_tail) SGX_GAT_FUSED_LAUNCH(true);
+                       (const T *)a.att, a.s1, a.alpha, (T *)a.D, a.ldd, a.relu, a.out_scale, s.long_threshold, a.vec_store,        \
+                       s.order, s.split_blocks, s.n_tasks, p->task_row, s.task_e0, s.task_e1, a.pacc, a.ldp, a.pm, a.pl, a.fill,    \
+                       s.n_multi, s.short_first)
+    if (s.short_tail) SGX_GAT_FUSED_LAUNCH(true);
     else SGX_GAT_FUSED_LAUNCH(false);
 #undef SGX_GAT_FUSED_LAUNCH
     SGX_LAUNCH_CHECK();
-    if (a.n_tasks > 0) {
-        const int64_t total = (int64_t)a.n_long * a.n_feat;
+    if (s.n_tasks > 0) {
+        const int64_t total = (int64_t)p->n_long * a.n_feat;
         hipLaunchKernelGGL((gat_fused_finalize_kernel<T>), dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, a.stream,
-                           a.n_long, a.n_feat, a.n_heads, a.n_feat / a.n_heads, a.long_row, a.long_first, a.pacc, a.ldp, a.pm, a.pl,
+                           p->n_long, a.n_feat, a.n_heads, a.n_feat / a.n_heads, p->long_row, p->long_first, a.pacc, a.ldp, a.pm, a.pl,
                            (T *)a.D, a.ldd, a.relu, a.fill, a.out_scale);
         SGX_LAUNCH_CHECK();
     }

@@ -1,5 +1,5 @@
 // Stage B of the two-stage GAT aggregate (gat.hip): D = act(sum_e alpha_e Wh[col_e]) -- the A.H aggregation with fp32 edge
-// weights: the same gather loop, long-row tasks and fixed-order finalize as spmm_csr.hip.  With several heads a lane reads
+// weights: the same gather loop as spmm_csr.hip, on the plan's row schedule (row_schedule.h: tasks, lane-group rows, tail).  With several heads a lane reads
 // the weight of ITS head for each edge (8 weights per edge lie in one 32-byte piece); each neighbour row is still gathered
 // once.  Then the rows stage A flagged as without a live edge receive the fill row.
 #include "gat_device.h"
@@ -12,9 +12,13 @@ namespace {
 // tasks (all lane groups of a wavefront on one task, fp32 partial rows), the others one row per lane group.  HEADS = 0:
 // one weight per edge, loaded with the column by the edge's lane and shuffled; HEADS = 1: every lane loads the weight
 // of its own head for each edge through a buffer resource (out of range past the row's end: 0, no access).
-// SHORT: the degree order's tail of one-step rows (at most 8 edges) 64 rows per wavefront, as spmm_short_rows does for the
-// plain aggregation (spmm_csr.hip: every link of row id -> row pointers -> (column, weight) -> gather is one round trip
-// for 64 rows; the same fma chain per output element, hence the same bits); workgroups from short_first on.
+// SHORT: the degree order's tail of one-step rows (at most 8 edges) 64 rows per wavefront (row_schedule.h, part 3: every
+// link of row id -> row pointers -> (column, weight) -> gather is one round trip for 64 rows; the same fma chain per
+// output element as the lane-group walk, hence the same bits); workgroups from short_first on.
+// The kernel keeps its own text of the schedule's device half (row_schedule.h states the same lines as functions): hipcc's
+// code for this kernel moves with any of them -- on a 2.3 M-entry R-MAT graph at 256 columns the aggregate takes 0.199 ms as
+// written here, 0.201 / 0.203 / 0.204 with the row walk / the tail tile / the row store through the header, 0.206 with all
+// (profiles/row_schedule_gat_weighted_variants.jsonl).  The grid it runs in and the finalize's sum are the header's.
 template <typename T, int VEC, int LPR, int HEADS, bool SHORT>
 __global__ __launch_bounds__(kBlock) void gat_weighted_kernel(
     int n_work, int n_feat, int n_heads, int f_head, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
@@ -217,19 +221,7 @@ __global__ __launch_bounds__(kBlock) void gat_weighted_finalize_kernel(
     const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (gid >= (int64_t)n_long * n_feat) return;
     const int l = (int)(gid / n_feat), j = (int)(gid % n_feat);
-    float s = 0.0f;
-    // task order, eight loads in flight at a time (the GAT plan cuts at 256 edges: a hub row of a power-law graph has
-    // hundreds of tasks, and one dependent load after the other made this kernel 89 us on a 29 M-edge graph)
-    const int t_end = long_first[l + 1];
-    int t = long_first[l];
-    for (; t + 8 <= t_end; t += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = partial[(int64_t)(t + u) * ldp + j];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; t < t_end; ++t) s += partial[(int64_t)t * ldp + j];
+    const float s = sum_task_partials(partial, ldp, j, long_first[l], long_first[l + 1], 0.0f);   // (the GAT plan cuts at 256 edges)
     D[(int64_t)long_row[l] * ldd + j] = gat_finish<T>(s, relu, out_scale);
 }
 
@@ -257,39 +249,25 @@ int weighted(const sgx_gat_args &a, const float *W)
     const float *pm = a.scratch + L.pm, *pl = a.scratch + L.pl;
     const unsigned char *dead = reinterpret_cast<const unsigned char *>(a.scratch + L.dead);
     const int ldp = L.ldp;
-    const int rows_per_block = (64 / LPR) * (kBlock / 64);
     const int f_head = a.n_feat / a.n_heads;
-    const int thr = p->n_long > 0 ? p->long_threshold : 0;
-    const int32_t *order = p->row_order;
-    const int n_work = order ? p->n_ordered : a.n_rows;
-    const int n_tasks = thr > 0 ? p->n_tasks : 0;
-    const int split_blocks = (n_tasks + kBlock / 64 - 1) / (kBlock / 64);
-    // the one-step tail of a degree order 64 rows per wavefront (as the plain aggregation does, spmm_csr.hip)
-    const bool short_tail = LPR >= 8 && order && !sgx_tune().spmm_no_short_tail && p->n_multi >= 0 && p->n_multi < n_work &&
-                            a.n_feat <= LPR * VEC && n_work - p->n_multi >= 4096;
-    const int n_multi = short_tail ? p->n_multi : n_work;
-    const int64_t short_blocks = short_tail ? ((int64_t)(n_work - n_multi) + 64 * (kBlock / 64) - 1) / (64 * (kBlock / 64)) : 0;
-    int64_t row_blocks = ((int64_t)n_multi + rows_per_block - 1) / rows_per_block;
-    if (row_blocks > 256 * 512) row_blocks = 256 * 512;
+    const sgx_row_schedule s = sgx_schedule_rows(p, a.n_rows, LPR, LPR * VEC, a.n_feat, true);
     const unsigned w_bytes = (unsigned)((size_t)p->nnz * a.n_heads * sizeof(float));
-    const dim3 grid_b((unsigned)(split_blocks + row_blocks + short_blocks));
-    const int short_first = (int)(split_blocks + row_blocks);
 #define SGX_GAT_WEIGHTED(HEADS_, SHORT_)                                                                                          \
-    hipLaunchKernelGGL((gat_weighted_kernel<T, VEC, LPR, HEADS_, SHORT_>), grid_b, dim3(kBlock), 0, a.stream, n_work, a.n_feat,     \
+    hipLaunchKernelGGL((gat_weighted_kernel<T, VEC, LPR, HEADS_, SHORT_>), dim3(s.grid), dim3(kBlock), 0, a.stream, s.n_work, a.n_feat, \
                        a.n_heads, f_head, a.rowptr, a.col, W, w_bytes, (const T *)a.Wh, a.h_bytes, a.ld_bytes, (T *)a.D, a.ldd,      \
-                       a.relu, a.out_scale, thr, a.vec_store, order, split_blocks, n_tasks, n_tasks ? p->task_e0 : nullptr,         \
-                       n_tasks ? p->task_e1 : nullptr, pacc, ldp, n_multi, short_first,                                            \
-                       (n_tasks && !a.S) ? pm : nullptr, (n_tasks && !a.S) ? pl : nullptr)
+                       a.relu, a.out_scale, s.long_threshold, a.vec_store, s.order, s.split_blocks, s.n_tasks, s.task_e0, s.task_e1,  \
+                       pacc, ldp, s.n_multi, s.short_first,                                                                       \
+                       (s.n_tasks && !a.S) ? pm : nullptr, (s.n_tasks && !a.S) ? pl : nullptr)
     if (a.n_heads > 1) {
-        if (short_tail) SGX_GAT_WEIGHTED(1, true);
+        if (s.short_tail) SGX_GAT_WEIGHTED(1, true);
         else SGX_GAT_WEIGHTED(1, false);
     } else {
-        if (short_tail) SGX_GAT_WEIGHTED(0, true);
+        if (s.short_tail) SGX_GAT_WEIGHTED(0, true);
         else SGX_GAT_WEIGHTED(0, false);
     }
 #undef SGX_GAT_WEIGHTED
     SGX_LAUNCH_CHECK();
-    if (n_tasks > 0) {
+    if (s.n_tasks > 0) {
         const int64_t total = (int64_t)p->n_long * a.n_feat;
         hipLaunchKernelGGL((gat_weighted_finalize_kernel<T>), dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0,
                            a.stream, p->n_long, a.n_feat, p->long_row, p->long_first, pacc, ldp, (T *)a.D, a.ldd, a.relu,

@@ -204,3 +204,5 @@ __device__ __forceinline__ T finish_value(float sum, int relu, const sgx_epilogu
     }
     return v;
 }
+
+#include "row_schedule.h"

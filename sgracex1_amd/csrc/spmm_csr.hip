@@ -35,9 +35,6 @@
 #ifndef SGX_SPMM_PIECES
 #define SGX_SPMM_PIECES 1            // pieces of LPR edges per loop iteration (gathers in flight x PIECES)
 #endif
-#ifndef SGX_SPMM_BLOCKS_PER_CU
-#define SGX_SPMM_BLOCKS_PER_CU 512   // grid cap (2.18 vs 2.21 ms at 64 on S-100M); rows beyond it are grid-strided
-#endif
 
 namespace {
 
@@ -168,27 +165,10 @@ __device__ __forceinline__ void accumulate_edges(float *acc, int e0, int e1, int
 }
 
 template <typename T, int VEC>
-__device__ __forceinline__ void store_row(T *__restrict__ drow, int col0, int n_feat, const float *acc, int relu,
-                                          bool vec_store, const sgx_epilogue &ep)
+__device__ __forceinline__ void store_row(T *__restrict__ drow, int col0, int n_feat, const float *acc, int relu, const sgx_epilogue &ep)
 {
-    T out[VEC];
-#pragma unroll
-    for (int i = 0; i < VEC; ++i) out[i] = finish_value<T>(acc[i], relu, ep);
-    (void)vec_store;
-    if (VEC > 1 && col0 + VEC <= n_feat) {
-        // one 16-byte store even when the row of D is only element-aligned (P_w = 41, 47 ...):
-        // gfx950 global stores need element alignment only
-#if SGX_SPMM_NT_STORE
-        __builtin_nontemporal_store(*reinterpret_cast<const u32x4 *>(out),
-                                    reinterpret_cast<typename Elem<T>::vec16_u *>(drow + col0));
-#else
-        *reinterpret_cast<typename Elem<T>::vec16_u *>(drow + col0) = *reinterpret_cast<const u32x4 *>(out);
-#endif
-    } else {
-#pragma unroll
-        for (int i = 0; i < VEC; ++i)
-            if (col0 + i < n_feat) drow[col0 + i] = out[i];
-    }
+    store_lane_outputs<T, VEC, SGX_SPMM_NT_STORE ? SGX_STORE_ELEM_ALIGNED_NT : SGX_STORE_ELEM_ALIGNED>(
+        drow, col0, n_feat, true, [&](int i) SGX_LAMBDA_INLINE { return finish_value<T>(acc[i], relu, ep); });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -202,20 +182,16 @@ __device__ __forceinline__ void store_row(T *__restrict__ drow, int col0, int n_
 // ---------------------------------------------------------------------------------------
 template <typename T, int VEC, int LPR>
 __device__ __forceinline__ void spmm_short_rows(
-    int64_t i0, int n_items, int n_feat, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
-    const T *__restrict__ val, __amdgpu_buffer_rsrc_t rsrc, unsigned ld_bytes, T *__restrict__ D, int64_t ldd, int relu,
-    int vec_store, const int32_t *__restrict__ row_order, const float *__restrict__ acc_in, float *__restrict__ acc_out,
+    const sgx_tail_tile &tile, int n_feat, const int32_t *__restrict__ col, const T *__restrict__ val, __amdgpu_buffer_rsrc_t rsrc,
+    unsigned ld_bytes, T *__restrict__ D, int64_t ldd, int relu, const float *__restrict__ acc_in, float *__restrict__ acc_out,
     int64_t ld_acc, const sgx_epilogue &ep)
 {
     static_assert(LPR >= 8, "a row's 8 edge slots are loaded by 8 lanes of its group");
     constexpr int RPW = 64 / LPR, ITER = LPR;
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPR, grp = lane / LPR;
-    const int64_t idx = i0 + lane;
-    const bool valid = idx < n_items;
-    const int r = row_order[valid ? idx : (int64_t)n_items - 1];
-    const int e0 = rowptr[r];
-    const int deg = valid ? rowptr[r + 1] - e0 : 0;               // at most 8 (the plan's last buckets)
+    const int r = tile.r, e0 = tile.e0, deg = tile.deg;
+    const bool valid = tile.valid;
     // the (column, value) pairs of all iterations; unconditional loads (a conditional load makes hipcc wait for it at
     // the join): slots past the end of a row read entry 0 and are masked when they are used
     // (the iterations are taken 8 at a time -- the pairs of one batch are 16 registers -- whatever the lane split)
@@ -259,7 +235,7 @@ __device__ __forceinline__ void spmm_short_rows(
             for (int i = 0; i < VEC; ++i)
                 if (col0 + i < n_feat) acc_out[rr * ld_acc + col0 + i] = acc[i];
         } else if (live && col0 < n_feat) {
-            store_row<T, VEC>(D + rr * ldd, col0, n_feat, acc, relu, vec_store != 0, ep);
+            store_row<T, VEC>(D + rr * ldd, col0, n_feat, acc, relu, ep);
         }
     }
     }
@@ -282,7 +258,6 @@ __device__ __forceinline__ void spmm_body(
     float *__restrict__ partial, int ldp,
     const float *__restrict__ acc_in, float *__restrict__ acc_out, int64_t ld_acc, sgx_epilogue ep, int n_multi, int short_first)
 {
-    constexpr int RPW = 64 / LPR;                 // rows per wavefront
     constexpr int LANE_COLS = CPL * VEC;          // columns per lane
     constexpr int TILE = LPR * LANE_COLS;         // columns covered per pass
     const int lane = threadIdx.x & 63;
@@ -293,9 +268,9 @@ __device__ __forceinline__ void spmm_body(
 
     if ((int)blockIdx.x < split_blocks) {
         // ---- split path ----
-        const int task = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
-        if (task >= n_tasks) return;
-        const int e0 = task_e0[task], e1 = task_e1[task];
+        const sgx_task t = schedule_task(n_tasks, task_e0, task_e1);
+        if (t.index < 0) return;
+        const int task = t.index, e0 = t.e0, e1 = t.e1;
         for (int c0 = 0; c0 < n_feat; c0 += TILE) {
             const int col0 = c0 + sub * LANE_COLS;
             unsigned chunk_off[CPL];
@@ -320,34 +295,23 @@ __device__ __forceinline__ void spmm_body(
         return;
     }
 
-    if constexpr (SHORT && LPR >= 8 && CPL == 1 && !BIG) {
-        // ---- one-step rows: the tail of the degree order, 64 rows per wavefront (workgroups from short_first on) ----
+    constexpr bool TAIL = SHORT && LPR >= 8 && CPL == 1 && !BIG;
+    if constexpr (TAIL) {
+        // ---- one-step rows: the tail of the degree order, 64 rows per wavefront ----
         if ((int)blockIdx.x >= short_first) {
-            const int64_t i0 = (int64_t)n_multi + ((int64_t)((int)blockIdx.x - short_first) * (kBlock / 64) + (threadIdx.x >> 6)) * 64;
-            if (i0 < n_rows)
-                spmm_short_rows<T, VEC, LPR>(i0, n_rows, n_feat, rowptr, col, val, rsrc, ld_bytes, D, ldd, relu, vec_store, row_order,
-                                             acc_in, acc_out, ld_acc, ep);
+            sgx_tail_tile tile;
+            if (schedule_tail_tile(short_first, n_multi, n_rows, row_order, rowptr, tile))
+                spmm_short_rows<T, VEC, LPR>(tile, n_feat, col, val, rsrc, ld_bytes, D, ldd, relu, acc_in, acc_out, ld_acc, ep);
             return;
         }
-        n_rows = n_multi;                    // the sblock path below walks the rows of two steps and more
     }
-    const int row_grid = (SHORT ? short_first : (int)gridDim.x) - split_blocks;
-    // ---- sblock path ----
-    const int64_t wave = (int64_t)(blockIdx.x - split_blocks) * (kBlock / 64) + (threadIdx.x >> 6);
-    const int64_t n_waves = (int64_t)row_grid * (kBlock / 64);
-    // n_rows = number of work items; row_order (from the plan) lists the rows in degree order so
-    // that the 64/LPR rows a wavefront owns need about the same number of steps
-    for (int64_t r0 = wave * RPW; r0 < n_rows; r0 += n_waves * RPW) {
-        int64_t r = r0 + grp;
-        int e0 = 0, e1 = 0;
-        bool live = r < n_rows;
-        if (live) {
-            if (row_order) r = row_order[r];
-            e0 = rowptr[r];
-            e1 = rowptr[r + 1];
-            if (long_threshold > 0 && e1 - e0 > long_threshold) live = false;   // split path owns it
-        }
-        if (!live) e1 = e0;
+    // ---- sblock path: n_rows = number of work items, n_multi of them ahead of a tail ----
+    const int n_walk = TAIL ? n_multi : n_rows;
+    int64_t r0, r_step;
+    schedule_row_range<LPR, SHORT>(split_blocks, short_first, r0, r_step);
+    for (; r0 < n_walk; r0 += r_step) {
+        int64_t r; int e0, e1;
+        const bool live = schedule_row<LPR>(r0, n_walk, long_threshold, row_order, rowptr, r, e0, e1);
         for (int c0 = 0; c0 < n_feat; c0 += TILE) {
             const int col0 = c0 + sub * LANE_COLS;
             unsigned chunk_off[CPL];
@@ -372,8 +336,7 @@ __device__ __forceinline__ void spmm_body(
             } else if (live) {
 #pragma unroll
                 for (int j = 0; j < CPL; ++j)
-                    if (col0 + j * VEC < n_feat)
-                        store_row<T, VEC>(D + r * ldd, col0 + j * VEC, n_feat, acc + j * VEC, relu, vec_store != 0, ep);
+                    if (col0 + j * VEC < n_feat) store_row<T, VEC>(D + r * ldd, col0 + j * VEC, n_feat, acc + j * VEC, relu, ep);
             }
         }
     }
@@ -537,19 +500,7 @@ __global__ __launch_bounds__(kBlock) void spmm_split_finalize_kernel(
     if (gid >= total) return;
     const int l = (int)(gid / n_feat), j = (int)(gid % n_feat);
     const int64_t row = long_row[l];
-    float s = acc_in ? acc_in[row * ld_acc + j] : 0.0f;
-    // the partial rows of a long row are added in task order; eight loads are in flight at a time (a hub row has tens to
-    // hundreds of tasks: one dependent load after the other was a round trip to memory each)
-    const int t_end = long_first[l + 1];
-    int t = long_first[l];
-    for (; t + 8 <= t_end; t += 8) {
-        float v[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) v[u] = partial[(int64_t)(t + u) * ldp + j];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) s += v[u];
-    }
-    for (; t < t_end; ++t) s += partial[(int64_t)t * ldp + j];
+    const float s = sum_task_partials(partial, ldp, j, long_first[l], long_first[l + 1], acc_in ? acc_in[row * ld_acc + j] : 0.0f);
     if (acc_out) { acc_out[row * ld_acc + j] = s; return; }
     D[row * ldd + j] = finish_value<T>(s, relu, ep);
 }
@@ -577,48 +528,21 @@ struct LaunchArgs {
     hipStream_t stream;
 };
 
-int grid_for_rows(int64_t n_rows, int rows_per_wave)
-{
-    const int64_t rows_per_block = (int64_t)rows_per_wave * (kBlock / 64);
-    int64_t blocks = (n_rows + rows_per_block - 1) / rows_per_block;
-    const int64_t cap = 256 * SGX_SPMM_BLOCKS_PER_CU;      // grid-stride beyond
-    if (blocks > cap) blocks = cap;
-    if (blocks < 1) blocks = 1;
-    return (int)blocks;
-}
-
 template <typename T, int VEC, int LPR, int CPL, bool BIG>
 int launch_one_impl(const LaunchArgs &a)
 {
     const sgx_plan *p = a.plan;
-    const int long_thr = (p && p->n_long > 0) ? p->long_threshold : 0;
-    const int32_t *order = p ? p->row_order : nullptr;
-    const int n_work = order ? p->n_ordered : a.n_rows;
-    const int n_tasks = long_thr > 0 ? p->n_tasks : 0;
-    const int split_blocks = (n_tasks + kBlock / 64 - 1) / (kBlock / 64);
-    // the one-step tail of a degree order: 64 rows per wavefront (spmm_short_rows); the rows ahead of it keep the sblock path
-    int n_multi = n_work, short_blocks = 0;
-    bool short_tail = false;
-    if constexpr (LPR >= 8 && CPL == 1 && !BIG) {
-        short_tail = order && !a.fea_stage && !sgx_tune().spmm_no_short_tail && p->n_multi >= 0 && p->n_multi < n_work &&
-                     a.n_feat <= LPR * VEC && n_work - p->n_multi >= 4096;
-        if (short_tail) {
-            n_multi = p->n_multi;
-            short_blocks = (int)(((int64_t)(n_work - n_multi) + 64 * (kBlock / 64) - 1) / (64 * (kBlock / 64)));
-        }
-    }
-    const int row_blocks = n_multi > 0 ? grid_for_rows(n_multi, 64 / LPR) : 0;
-    if (split_blocks + row_blocks + short_blocks > 0) {
+    const sgx_row_schedule s = sgx_schedule_rows(p, a.n_rows, LPR, LPR * VEC, a.n_feat, !a.fea_stage && CPL == 1 && !BIG);
+    if (s.grid > 0) {
         auto kernel = a.fea_stage ? xw_sparse_kernel<T, VEC, LPR, CPL, BIG>
-                                  : (short_tail ? spmm_short_tail_kernel<T, VEC, LPR, CPL, BIG> : spmm_kernel<T, VEC, LPR, CPL, BIG>);
-        hipLaunchKernelGGL(kernel, dim3(split_blocks + row_blocks + short_blocks), dim3(kBlock), 0,
-                           a.stream, n_work, a.n_feat, a.rowptr, a.col, (const T *)a.val, (const T *)a.H, a.h_bytes,
-                           a.ld_bytes, (T *)a.D, a.ldd, a.relu, long_thr, a.vec_store, order, split_blocks, n_tasks,
-                           n_tasks ? p->task_e0 : nullptr, n_tasks ? p->task_e1 : nullptr, a.partial, a.ldp, a.acc_in,
-                           a.acc_out, a.ld_acc, a.ep, n_multi, split_blocks + row_blocks);
+                                  : (s.short_tail ? spmm_short_tail_kernel<T, VEC, LPR, CPL, BIG> : spmm_kernel<T, VEC, LPR, CPL, BIG>);
+        hipLaunchKernelGGL(kernel, dim3(s.grid), dim3(kBlock), 0, a.stream, s.n_work, a.n_feat, a.rowptr, a.col, (const T *)a.val,
+                           (const T *)a.H, a.h_bytes, a.ld_bytes, (T *)a.D, a.ldd, a.relu, s.long_threshold, a.vec_store, s.order,
+                           s.split_blocks, s.n_tasks, s.task_e0, s.task_e1, a.partial, a.ldp, a.acc_in, a.acc_out, a.ld_acc, a.ep,
+                           s.n_multi, s.short_first);
         SGX_LAUNCH_CHECK();
     }
-    if (n_tasks > 0) {
+    if (s.n_tasks > 0) {
         const int64_t total = (int64_t)p->n_long * a.n_feat;
         hipLaunchKernelGGL((spmm_split_finalize_kernel<T>), dim3((unsigned)((total + kBlock - 1) / kBlock)),
                            dim3(kBlock), 0, a.stream, p->n_long, a.n_feat, p->long_row, p->long_first, a.partial,
