@@ -297,6 +297,43 @@ int sgx_spmm_csr_acc(int dtype, int relu, int n_rows, int n_cols, int n_feat,
                      const float *acc_in, float *acc_out, int64_t ld_acc,
                      const sgx_plan *plan, void *scratch, size_t scratch_bytes, void *stream);
 
+/* ---- entry-split aggregation ----------------------------------------------------------------------------
+ * sgx_spmm_csr's contract in SGX_ACC_F32 arithmetic (fp16 or fp32 storage, fp32 products and sums, one rounding on
+ * the store) on a schedule that depends on the stored-entry count alone: no plan, nothing read back, nothing allocated,
+ * no synchronisation, the grids a function of `nnz` -- so the call records into a graph and replays on other matrices
+ * of the same capacity -- and balanced on any degree distribution, because the work is cut by stored entries, not by rows.
+ *
+ * Ownership rule, with T = sgx_spmm_flat_chunk() and end = rowPtr[n_rows] as the device reads it:
+ *   - the stored entries are cut into chunks of T consecutive entries, chunk c = entries [cT, min((c+1)T, end)), one
+ *     wavefront per chunk; a chunk finds its first row by a search in rowPtr on the device;
+ *   - a row that lies wholly inside one chunk is summed and stored by that chunk;
+ *   - a row that crosses a chunk end leaves one fp32 partial row per chunk it touches in `scratch`;
+ *   - the chunk that holds a crossing row's first entry is its leader: in a second launch, whose grid is again a
+ *     function of the chunk count only, the leader adds the row's partials in chunk order and stores the row once;
+ *   - an empty row belongs to the chunk that holds entry index rowPtr[r]; if that index equals end, to the last chunk;
+ *     for end == 0 a single degenerate chunk owns all rows.  It is stored as act(0), which is +0.
+ * Every row of D is therefore written exactly once, by plain vector stores and without atomics, and the order in which
+ * a row is summed depends only on rowPtr and T (and the call's operand layout): two runs give the same bits.  A row
+ * of fewer than 64 entries inside one chunk gets the bits sgx_spmm_csr gives it without a plan.
+ *
+ * nnz is a host argument and may be a capacity: a bound on rowPtr[n_rows] (and no more than columnIndex / values
+ * hold).  Chunks that start at or past the real end do nothing; empty rows are assigned by the real end.
+ * H is gathered as by sgx_spmm_csr (16 bytes per lane where rows start on a dword, one element per lane on odd
+ * halves, range-checked buffer loads, any n_feat >= 1); tables of 4 GiB and more: SGX_ERR_UNSUPPORTED -- the form is
+ * for batch-sized matrices.  scratch: sgx_spmm_flat_scratch_bytes(nnz, n_feat) bytes (never 0 for valid arguments; 0
+ * for nnz < 0, nnz > INT32_MAX or n_feat < 1), 256-byte aligned, needed by every call.
+ * Argument errors, returned before anything is launched: a negative size, n_feat < 1, ldh or ldd below n_feat, nnz
+ * outside [0, INT32_MAX]: SGX_ERR_SHAPE; a dtype other than SGX_F16 / SGX_F32: SGX_ERR_UNSUPPORTED; (n_rows == 0:
+ * SGX_OK;) rowPtr or D NULL, columnIndex or values NULL with nnz > 0, H NULL with nnz > 0 and n_cols > 0:
+ * SGX_ERR_NULL; a table past 32-bit byte offsets: SGX_ERR_UNSUPPORTED; scratch NULL or too small: SGX_ERR_WORKSPACE;
+ * scratch off a 256-byte boundary, an index array off 4 bytes, values, H or D off an element: SGX_ERR_ALIGN. */
+int    sgx_spmm_flat_chunk(void);
+size_t sgx_spmm_flat_scratch_bytes(int64_t nnz, int n_feat);
+int    sgx_spmm_csr_flat(int dtype, int relu, int n_rows, int n_cols, int n_feat, int64_t nnz,
+                         const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                         const void *H, int64_t ldh, void *D, int64_t ldd,
+                         void *scratch, size_t scratch_bytes, void *stream);
+
 /* X.W with dense X = loop_fea / compute1 in gemm_mode 1 (K.cpp:2932, :2605, :847-865),
  * on the matrix cores:  H[r][0:P] = sum_k X[r][k] * Wt[p][k].
  * X [n_rows][ldx], Wt [P][ldw] (= B), H [n_rows][ldh]; columns P..ldh-1 of H are zeroed. */

@@ -211,6 +211,7 @@ class Csr:
         self._dead_row_mask = None
         self._dead_rows_version = self._dead_row_mask_version = None      # the values' version a computed answer holds for
         self._max_row = None                   # the longest row, or a bound on it, where the builder knows it
+        self._flat = False                     # aggregates by the entry-split form (with_facts(flat=True)): never wants a plan
         self._quantized = {}
 
     @property
@@ -272,15 +273,22 @@ class Csr:
         in microseconds on any schedule, so they run without one unless a plan already exists."""
         if self._plan is not None:
             return True
+        if self._flat:
+            # the entry-split aggregation (sgx_spmm_csr_flat) balances any degree distribution from the entry count alone
+            return False
         if self._max_row is not None and self._max_row <= 64 and self.nnz < (1 << 20):
             # known facts (a loader's batch): under 2^20 entries a plan cuts rows over 64 entries and there are none, so
             # it would only reorder short rows -- not worth its read-back, synchronisation and allocations per batch
             return False
         return self.nnz >= 8192
 
-    def with_facts(self, dead_row_mask=None, has_dead_rows=None, max_row=None):
+    def with_facts(self, dead_row_mask=None, has_dead_rows=None, max_row=None, flat=None):
         """Records what the builder of this matrix already knows, so that nothing is computed or read back for it:
-        dead_rows (bool [n_rows]), has_dead_rows, and the longest row (or a bound on it; see wants_plan)."""
+        dead_rows (bool [n_rows]), has_dead_rows, and the longest row (or a bound on it; see wants_plan).
+        flat=True: this matrix aggregates by the entry-split form -- ops.spmm takes sgx_spmm_csr_flat for it without
+        being asked, and it wants no plan (unless one exists already), whatever its rows are like."""
+        if flat is not None:
+            self._flat = bool(flat)
         if dead_row_mask is not None:
             self._dead_row_mask, self._dead_row_mask_version = dead_row_mask, None
         if has_dead_rows is not None:
@@ -295,7 +303,7 @@ class Csr:
         if self.val.dtype == dtype:
             return self
         return Csr(self.rowptr, self.col, self.val.to(dtype), self.n_cols,
-                   self.plan if self.wants_plan else None).with_facts(max_row=self._max_row)
+                   self.plan if self.wants_plan else None).with_facts(max_row=self._max_row, flat=self._flat)
 
     def validate(self):
         check(lib.sgx_csr_validate(_ptr(self.rowptr), _ptr(self.col), self.n_rows, self.n_cols, self.nnz, _stream()),
@@ -357,8 +365,16 @@ def _gatherable_copies(H, n_feat, nnz):
     return H.shape[0] * n_feat >= (1 << 16)
 
 
-def spmm(adj, H, relu=False, n_feat=None, out=None, use_plan=True, acc_mode=SGX_ACC_F32, spmm_block=1):
-    """D = act(A @ H[:, :n_feat]) -- the aggregation stage alone (sgx_spmm_csr)."""
+def spmm(adj, H, relu=False, n_feat=None, out=None, use_plan=True, acc_mode=SGX_ACC_F32, spmm_block=1, schedule=None):
+    """D = act(A @ H[:, :n_feat]) -- the aggregation stage alone (sgx_spmm_csr).
+    schedule="flat", or a matrix that carries the fact (Csr.with_facts(flat=True)): the entry-split form
+    (sgx_spmm_csr_flat) -- no plan, no read-back, the grid a function of the entries adj.col holds (a capacity: the
+    matrix's own end is read from rowptr on the device), so the call records into a graph and replays."""
+    if schedule not in (None, "flat"):
+        raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
+    flat = schedule == "flat" or adj._flat
+    if flat and acc_mode != SGX_ACC_F32:
+        raise ValueError("the entry-split aggregation is SGX_ACC_F32 arithmetic only")
     _dev2d(H, "H")
     n_feat = H.shape[1] if n_feat is None else n_feat
     if acc_mode == SGX_ACC_F32:
@@ -369,6 +385,13 @@ def spmm(adj, H, relu=False, n_feat=None, out=None, use_plan=True, acc_mode=SGX_
     if H.shape[0] < adj.n_cols:
         raise ValueError(f"H has {H.shape[0]} rows, the adjacency refers to {adj.n_cols} columns")
     out = _out(out, adj.n_rows, n_feat, H.dtype, H.device)
+    if flat:
+        sbytes = lib.sgx_spmm_flat_scratch_bytes(adj.nnz, n_feat)
+        scratch = _workspace(H.device, sbytes)
+        check(lib.sgx_spmm_csr_flat(code, int(bool(relu)), adj.n_rows, H.shape[0], n_feat, adj.nnz, _ptr(adj.rowptr), _ptr(adj.col),
+                                    _ptr(adj.val), _ptr(H), H.stride(0), _ptr(out), out.stride(0), _ptr(scratch), sbytes, _stream()),
+              "sgx_spmm_csr_flat")
+        return out
     plan = adj.plan if (use_plan and adj.wants_plan) else None
     sbytes = lib.sgx_spmm_scratch_bytes(plan.handle, n_feat) if plan is not None else 0
     scratch = _workspace(H.device, sbytes) if sbytes else None
