@@ -27,6 +27,7 @@
 // term, and write S_e out when the caller wants the attention matrix.  The STATS = false kernels do what they did before
 // (the added arguments are not read).
 #include "gat_device.h"
+#include "long_rows.h"
 
 #include <type_traits>
 
@@ -34,7 +35,6 @@ namespace {
 
 constexpr int kDotBlock = 256;           // stored entries per workgroup pass of the dots kernel
 constexpr int kRowLanes = 8;             // lanes per row in the rows kernel
-constexpr int kRowLong = 256;            // rows over this many entries: the whole wavefront
 
 // what the STATS kernels read in place of E and S (one head): the statistics, the mask's values and the dead rows' weight
 struct StatsIn {
@@ -126,6 +126,31 @@ __global__ __launch_bounds__(kDotBlock) void gat_bwd_dots_kernel(
     }
 }
 
+// One stored entry of row r on its parked dx: E_e and S_e from memory or formed again from the statistics (STATS, which
+// also writes S_e out where the caller wants it), the softmax backward with the row's sum rs, the mask, the LeakyReLU
+// slope.  Writes sg_e and returns it.
+template <typename TV, bool STATS>
+__device__ __forceinline__ float edge_step(int idx, int64_t r, float rs, const TV *__restrict__ val, const float *__restrict__ E,
+                                           const float *__restrict__ S, float alpha, float *__restrict__ sg,
+                                           const int32_t *__restrict__ col, const StatsIn &st)
+{
+    float e_x, s_w;
+    if constexpr (STATS) {
+        const __amdgpu_buffer_rsrc_t sc_rsrc =
+            __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(st.score_col), 0, st.sc_bytes, 0x00020000);
+        stats_entry<TV>(st, sc_rsrc, idx, r, col[idx], e_x, s_w);
+        if (st.S_out) st.S_out[idx] = s_w;
+    } else {
+        e_x = E[idx];
+        s_w = S[idx];
+    }
+    float v = sg[idx] - s_w * rs;
+    if (!(Elem<TV>::to_f32(val[idx]) > 0.0f)) v = 0.0f;
+    if (!(e_x > 0.0f)) v *= alpha;
+    sg[idx] = v;
+    return v;
+}
+
 // softmax backward, mask, LeakyReLU backward on the parked dx; g1 = row sums of the result
 template <typename TV, bool STATS = false>
 __global__ __launch_bounds__(kBlock) void gat_bwd_rows_kernel(
@@ -139,40 +164,21 @@ __global__ __launch_bounds__(kBlock) void gat_bwd_rows_kernel(
     const bool live = r < n_rows;
     int e0 = 0, e1 = 0;
     if (live) { e0 = rowptr[r]; e1 = rowptr[r + 1]; }
-    const bool is_long = e1 - e0 > kRowLong;
-    auto finish = [&](int idx, float rs) -> float {
-        float e_x, s_w;
-        if constexpr (STATS) {
-            const __amdgpu_buffer_rsrc_t sc_rsrc =
-                __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(st.score_col), 0, st.sc_bytes, 0x00020000);
-            stats_entry<TV>(st, sc_rsrc, idx, r, col[idx], e_x, s_w);
-            if (st.S_out) st.S_out[idx] = s_w;
-        } else {
-            e_x = E[idx];
-            s_w = S[idx];
-        }
-        float v = sg[idx] - s_w * rs;
-        if (!(Elem<TV>::to_f32(val[idx]) > 0.0f)) v = 0.0f;
-        if (!(e_x > 0.0f)) v *= alpha;
-        sg[idx] = v;
-        return v;
-    };
-    if (!is_long) {
-        float rs = 0.0f;
-        for (int idx = e0 + sub; idx < e1; idx += kRowLanes) rs += sg[idx];
+    if (e1 - e0 > kLongRowCut) return;                                      // the long-rows launch owns it
+    float rs = 0.0f;
+    for (int idx = e0 + sub; idx < e1; idx += kRowLanes) rs += sg[idx];
 #pragma unroll
-        for (int off = 1; off < kRowLanes; off <<= 1) rs += __shfl_xor(rs, off);
-        if (dead != nullptr && live && dead[r]) rs = dead_row_sum[r];       // softmax over all N columns, not the stored ones
-        float acc = 0.0f;
-        for (int idx = e0 + sub; idx < e1; idx += kRowLanes) acc += finish(idx, rs);
+    for (int off = 1; off < kRowLanes; off <<= 1) rs += __shfl_xor(rs, off);
+    if (dead != nullptr && live && dead[r]) rs = dead_row_sum[r];           // softmax over all N columns, not the stored ones
+    float acc = 0.0f;
+    for (int idx = e0 + sub; idx < e1; idx += kRowLanes) acc += edge_step<TV, STATS>(idx, r, rs, val, E, S, alpha, sg, col, st);
 #pragma unroll
-        for (int off = 1; off < kRowLanes; off <<= 1) acc += __shfl_xor(acc, off);
-        if (live && sub == 0) g1[r] = acc;
-    }
+    for (int off = 1; off < kRowLanes; off <<= 1) acc += __shfl_xor(acc, off);
+    if (live && sub == 0) g1[r] = acc;
 }
 
-// rows over kRowLong entries: a workgroup of 1024 looks at 64 consecutive rows and takes the long ones among them one
-// after the other with all its threads (most workgroups find none and leave after reading 65 row pointers)
+// rows over kLongRowCut entries: a workgroup of 1024 looks at 64 consecutive rows and takes the long ones among them one
+// after the other with all its threads (long_rows.h; most workgroups find none and leave after reading 65 row pointers)
 constexpr int kLongThreads = 1024;
 template <typename TV, bool STATS = false>
 __global__ __launch_bounds__(kLongThreads) void gat_bwd_long_rows_kernel(
@@ -182,9 +188,9 @@ __global__ __launch_bounds__(kLongThreads) void gat_bwd_long_rows_kernel(
 {
     __shared__ float part[kLongThreads / 64];
     __shared__ float total;
+    __shared__ unsigned long long long_mask;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const int64_t r_first = (int64_t)blockIdx.x * 64;
-    auto block_sum = [&](float v) -> float {
+    auto block_sum = [&](float v) SGX_LAMBDA_INLINE -> float {
 #pragma unroll
         for (int off = 1; off < 64; off <<= 1) v += __shfl_xor(v, off);
         __syncthreads();                              // `total` of the previous sum has been read by everyone
@@ -198,45 +204,17 @@ __global__ __launch_bounds__(kLongThreads) void gat_bwd_long_rows_kernel(
         __syncthreads();
         return total;
     };
-    // which of the 64 rows are long: one look by the first wavefront
-    __shared__ unsigned long long long_mask;
-    if (wave == 0) {
-        const int64_t r = r_first + lane;
-        const int deg = r < n_rows ? rowptr[r + 1] - rowptr[r] : 0;
-        const unsigned long long m = __ballot(deg > kRowLong);
-        if (lane == 0) long_mask = m;
-    }
-    __syncthreads();
-    unsigned long long todo = long_mask;
-    while (todo) {                                    // (uniform over the workgroup)
-        const int64_t r = r_first + (__ffsll((long long)todo) - 1);
-        todo &= todo - 1;
+    for_each_long_row<64, kLongRowCut>(rowptr, (int64_t)blockIdx.x * 64, n_rows, &long_mask, [&](int64_t r) SGX_LAMBDA_INLINE {
         const int e0 = rowptr[r], e1 = rowptr[r + 1];
         float rs = 0.0f;
         for (int idx = e0 + (int)threadIdx.x; idx < e1; idx += kLongThreads) rs += sg[idx];
         rs = block_sum(rs);
         if (dead != nullptr && dead[r]) rs = dead_row_sum[r];
         float acc = 0.0f;
-        for (int idx = e0 + (int)threadIdx.x; idx < e1; idx += kLongThreads) {
-            float e_x, s_w;
-            if constexpr (STATS) {
-                const __amdgpu_buffer_rsrc_t sc_rsrc =
-                    __builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(st.score_col), 0, st.sc_bytes, 0x00020000);
-                stats_entry<TV>(st, sc_rsrc, idx, r, col[idx], e_x, s_w);
-                if (st.S_out) st.S_out[idx] = s_w;
-            } else {
-                e_x = E[idx];
-                s_w = S[idx];
-            }
-            float v = sg[idx] - s_w * rs;
-            if (!(Elem<TV>::to_f32(val[idx]) > 0.0f)) v = 0.0f;
-            if (!(e_x > 0.0f)) v *= alpha;
-            sg[idx] = v;
-            acc += v;
-        }
+        for (int idx = e0 + (int)threadIdx.x; idx < e1; idx += kLongThreads) acc += edge_step<TV, STATS>(idx, r, rs, val, E, S, alpha, sg, col, st);
         acc = block_sum(acc);
         if (threadIdx.x == 0) g1[r] = acc;
-    }
+    });
 }
 
 struct BwdArgs {
@@ -312,11 +290,7 @@ int prepare(BwdArgs &a, int dtype_values, int n_rows, int n_cols, int n_feat, co
     a.sg = sg; a.stream = s;
     a.g_vec = ((uintptr_t)G % 16 == 0 && (ldg * 4) % 16 == 0) ? 1 : 0;     // 16-byte loads of G's rows too, where they are aligned
     a.st = StatsIn{};
-    // persistent over the stored entries (their count is read on the device): 8 workgroups per CU
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    a.grid = (unsigned)cus * 8u;
+    a.grid = (unsigned)sgx_cu_count(1) * 8u;     // persistent over the stored entries (their count is read on the device): 8 workgroups per CU
     return SGX_OK;
 }
 

@@ -7,17 +7,22 @@
 // walk where it is taken), and one pass here forms (m, l) from the scores -- edge work only, the first stage of the
 // two-stage form without its weights: per stored entry a column index, a value and a 4-byte score gather per head.
 //   rows   8 lanes per row, 8 heads at a time in registers, the lanes' states merged by an xor butterfly; rows over
-//          kStatLong entries are left to a second launch in which a workgroup looks at 8 consecutive rows and takes the
-//          long ones among them with all its threads.
+//          kLongRowCut entries are left to a second launch in which a workgroup looks at 8 consecutive rows and takes
+//          the long ones among them with all its threads .
 // Both orders are fixed, so the statistics are the same bits on every run.
 #include "gat_device.h"
+#include "long_rows.h"
 
 namespace {
 
 constexpr int kStatLanes = 8;            // lanes per row
-constexpr int kStatLong = 256;           // rows over this many entries: a whole workgroup
 constexpr int kStatHeads = 8;            // heads kept in registers at a time
 
+// Both kernels keep their own text of the head-block accumulation, and the long-rows kernel its own walk over the window
+// (the one long_rows.h states for gat_bwd.hip and layer_bwd.hip).  Through one accumulation function gat_row_stats_kernel
+// took 62 VGPRs for 59 and row_sum of the 8-head layouts moved in its last bits (tools/gat_train_digest.py); through
+// for_each_long_row the long-rows kernel took 78 VGPRs for 73 and the 8-head statistics call on the R-MAT arxiv shape went
+// from 0.952 to 0.958 ms (fp32) and 0.781 to 0.787 ms (fp16), outside the parent's spread of 0.004 (profiles/long_rows_*).
 template <typename T>
 __global__ __launch_bounds__(kBlock) void gat_row_stats_kernel(
     int n_rows, int n_heads, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col, const T *__restrict__ val,
@@ -31,7 +36,7 @@ __global__ __launch_bounds__(kBlock) void gat_row_stats_kernel(
     bool mine = r < n_rows;
     int e0 = 0, e1 = 0;
     if (mine) { e0 = rowptr[r]; e1 = rowptr[r + 1]; }
-    if (e1 - e0 > kStatLong) { mine = false; e1 = e0; }          // the long-rows launch owns it
+    if (e1 - e0 > kLongRowCut) { mine = false; e1 = e0; }          // the long-rows launch owns it
     for (int hb0 = 0; hb0 < n_heads; hb0 += kStatHeads) {
         float m[kStatHeads], l[kStatHeads], si[kStatHeads];
 #pragma unroll
@@ -60,7 +65,7 @@ __global__ __launch_bounds__(kBlock) void gat_row_stats_kernel(
     }
 }
 
-// rows over kStatLong entries: a workgroup looks at kLongSpan consecutive rows and takes the long ones among them one after
+// rows over kLongRowCut entries: a workgroup looks at kLongSpan consecutive rows and takes the long ones among them one after
 // the other with all its threads, 8 heads at a time in registers (hub rows of a power-law graph sit next to each other:
 // a span of 64 rows left one workgroup with 64 hubs in a row)
 constexpr int kLongSpan = 8;
@@ -78,7 +83,7 @@ __global__ __launch_bounds__(kBlock) void gat_row_stats_long_kernel(
     if (wave == 0) {                                  // which of the rows are long: one look by the first wavefront
         const int64_t r = r_first + lane;
         const int deg = (lane < kLongSpan && r < n_rows) ? rowptr[r + 1] - rowptr[r] : 0;
-        const unsigned long long mask = __ballot(deg > kStatLong);
+        const unsigned long long mask = __ballot(deg > kLongRowCut);
         if (lane == 0) long_mask = mask;
     }
     __syncthreads();
@@ -152,14 +157,6 @@ __global__ __launch_bounds__(kBlock) void gat_edge_outputs_kernel(
     }
 }
 
-unsigned persistent_grid()
-{
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
-    return (unsigned)cus * 8u;
-}
-
 }  // namespace
 
 int sgx_gat_stats_check(const sgx_gat_stats *st, int n_cols, int n_heads)
@@ -182,21 +179,16 @@ int sgx_gat_row_stats(int dtype, int n_rows, int n_cols, int n_heads, float alph
     const unsigned s2_bytes = (unsigned)((size_t)n_cols * n_heads * 4);
     const int rows_per_block = (64 / kStatLanes) * (kBlock / 64);
     const dim3 grid((unsigned)((n_rows + rows_per_block - 1) / rows_per_block)), grid_long((unsigned)((n_rows + kLongSpan - 1) / kLongSpan));
-    if (dtype == SGX_F16) {
-        hipLaunchKernelGGL(gat_row_stats_kernel<f16>, grid, dim3(kBlock), 0, stream, n_rows, n_heads, rowPtr, columnIndex,
-                           (const f16 *)values, s1, s2, s2_bytes, alpha, st->row_max, st->row_sum);
+    return sgx_dtype_dispatch(dtype, [&](auto t) -> int {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gat_row_stats_kernel<T>, grid, dim3(kBlock), 0, stream, n_rows, n_heads, rowPtr, columnIndex,
+                           (const T *)values, s1, s2, s2_bytes, alpha, st->row_max, st->row_sum);
         SGX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gat_row_stats_long_kernel<f16>, grid_long, dim3(kBlock), 0, stream, n_rows, n_heads, rowPtr, columnIndex,
-                           (const f16 *)values, s1, s2, s2_bytes, alpha, st->row_max, st->row_sum);
-    } else {
-        hipLaunchKernelGGL(gat_row_stats_kernel<float>, grid, dim3(kBlock), 0, stream, n_rows, n_heads, rowPtr, columnIndex,
-                           (const float *)values, s1, s2, s2_bytes, alpha, st->row_max, st->row_sum);
+        hipLaunchKernelGGL(gat_row_stats_long_kernel<T>, grid_long, dim3(kBlock), 0, stream, n_rows, n_heads, rowPtr, columnIndex,
+                           (const T *)values, s1, s2, s2_bytes, alpha, st->row_max, st->row_sum);
         SGX_LAUNCH_CHECK();
-        hipLaunchKernelGGL(gat_row_stats_long_kernel<float>, grid_long, dim3(kBlock), 0, stream, n_rows, n_heads, rowPtr,
-                           columnIndex, (const float *)values, s1, s2, s2_bytes, alpha, st->row_max, st->row_sum);
-    }
-    SGX_LAUNCH_CHECK();
-    return SGX_OK;
+        return SGX_OK;
+    });
 }
 
 extern "C" int sgx_gat_aggregate_stats(int dtype, int relu, int n_rows, int n_cols, int n_feat, int n_heads, float alpha,
@@ -237,15 +229,13 @@ extern "C" int sgx_gat_edge_outputs(int dtype_values, int n_rows, int n_cols, in
     if (rc != SGX_OK) return rc;
     if (dtype_values != SGX_F16 && dtype_values != SGX_F32) return SGX_ERR_UNSUPPORTED;
     const unsigned sc_bytes = (unsigned)((size_t)n_cols * n_heads * 4);
-    const dim3 grid(persistent_grid());
-    if (dtype_values == SGX_F16)
-        hipLaunchKernelGGL(gat_edge_outputs_kernel<f16>, grid, dim3(kBlock), 0, (hipStream_t)stream, n_rows, n_heads, rowPtr,
-                           columnIndex, (const f16 *)values, stats->score_row, stats->score_col, sc_bytes, stats->row_max,
+    const dim3 grid((unsigned)sgx_cu_count(1) * 8u);               // persistent: 8 workgroups per CU
+    return sgx_dtype_dispatch(dtype_values, [&](auto t) -> int {
+        using T = decltype(t);
+        hipLaunchKernelGGL(gat_edge_outputs_kernel<T>, grid, dim3(kBlock), 0, (hipStream_t)stream, n_rows, n_heads, rowPtr,
+                           columnIndex, (const T *)values, stats->score_row, stats->score_col, sc_bytes, stats->row_max,
                            stats->row_sum, alpha, dead_weight, E, S);
-    else
-        hipLaunchKernelGGL(gat_edge_outputs_kernel<float>, grid, dim3(kBlock), 0, (hipStream_t)stream, n_rows, n_heads, rowPtr,
-                           columnIndex, (const float *)values, stats->score_row, stats->score_col, sc_bytes, stats->row_max,
-                           stats->row_sum, alpha, dead_weight, E, S);
-    SGX_LAUNCH_CHECK();
-    return SGX_OK;
+        SGX_LAUNCH_CHECK();
+        return SGX_OK;
+    });
 }

@@ -9,16 +9,17 @@
 //                        order and adds t_r and g1[r] Wh[r] into registers; the lane groups' sums are added in a fixed
 //                        order through LDS into the workgroup's slice of the workspace (plain stores, no atomics) and a
 //                        second launch adds the slices in slice order.  A row over 256 entries is left out of that walk
-//                        and taken by the whole workgroup afterwards: chunks of 256 entries, one per lane group, their
-//                        partial sums added in chunk order.  The grid depends on the shapes only.
+//                        and taken by the whole workgroup afterwards (long_rows.h): chunks of 256 entries, one per lane
+//                        group, their partial sums added in chunk order.  The grid depends on the shapes only.
 //   dead-row select      pg[r][:] = colsum(G)[:] * (1 / N) where dead[r], in place (the torch.where of the Python path):
 //                        a wavefront per row, rows by grid stride.
 //   casts                fp16 -> fp32 of the GCN adjacency values (and of a dense fp16 X for Wh = X . W).
 #include "gat_device.h"
+#include "long_rows.h"
 
 namespace {
 
-constexpr int kAgChunk = 256;            // entries of a long row one lane group takes at a time (the edge pass's kRowLong)
+constexpr int kAgChunk = kLongRowCut;    // entries of a long row one lane group takes at a time: the cut is the chunk
 constexpr int kAgRowsPerSlice = 64;      // a slice per this many rows ...
 constexpr int kAgMaxSlices = 1024;       // ... up to this many slices
 
@@ -120,19 +121,8 @@ __global__ __launch_bounds__(kBlock) void attention_grad_slices_kernel(
         const float s1 = fold(a1);
         float s2 = fold(a2);
         // longer rows, in ascending order: the whole workgroup, a chunk per lane group, chunk sums added in chunk order
-        for (int64_t win = r0; win < r1; win += 64) {
-            __syncthreads();                               // long_mask of the window before has been read
-            if (wave == 0) {
-                const int64_t r = win + lane;
-                const int deg = r < r1 ? rowptr[r + 1] - rowptr[r] : 0;
-                const unsigned long long m = __ballot(deg > kAgChunk);
-                if (lane == 0) long_mask = m;
-            }
-            __syncthreads();
-            unsigned long long todo = long_mask;
-            while (todo) {                                 // (uniform over the workgroup)
-                const int64_t r = win + (__ffsll((long long)todo) - 1);
-                todo &= todo - 1;
+        for (int64_t win = r0; win < r1; win += 64)
+            for_each_long_row<64, kAgChunk>(rowptr, win, r1, &long_mask, [&](int64_t r) SGX_LAMBDA_INLINE {
                 const int e0 = rowptr[r], e1 = rowptr[r + 1];
                 const int n_chunks = (e1 - e0 + kAgChunk - 1) / kAgChunk;
                 float row_t = 0.0f;
@@ -153,8 +143,7 @@ __global__ __launch_bounds__(kBlock) void attention_grad_slices_kernel(
                         for (int j = 0; j < n_here; ++j) row_t += part[j * TILE + threadIdx.x];
                 }
                 s2 += row_t;
-            }
-        }
+            });
         if ((int)threadIdx.x < TILE && c0 + (int)threadIdx.x < n_feat) {
             slice[c0 + threadIdx.x] = s1;
             slice[n_feat + c0 + threadIdx.x] = s2;

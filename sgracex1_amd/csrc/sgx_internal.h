@@ -69,6 +69,17 @@ static inline size_t sgx_elem_size(int dtype) { return dtype == SGX_F16 ? 2 : 4;
 static inline size_t sgx_align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int sgx_next_pow2(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
+// The compute units of the current device, for grids sized by them; 256 when the runtime does not say or says fewer than
+// `at_least` (what the caller's arithmetic needs: 1, or the 8 of a grid in whole groups of 8).
+static inline int sgx_cu_count(int at_least)
+{
+    int cus = 0, dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+        cus < at_least)
+        cus = 256;
+    return cus;
+}
+
 // Row schedule (see sgx.h).  Rows with more than `long_threshold` edges are cut into tasks
 // of at most `chunk` edges; each task is summed by one wavefront into an fp32 partial row,
 // and the partial rows of one long row are added in task order (bitwise reproducible).
@@ -266,6 +277,12 @@ int sgx_gat_dispatch(const sgx_gat_args &a, F &&f)
 {
     if (a.dtype == SGX_F16) return a.vec_ok ? sgx_gat_dispatch_lpr<f16, 8>(a.lpr, f) : sgx_gat_dispatch_lpr<f16, 1>(a.lpr, f);
     return a.vec_ok ? sgx_gat_dispatch_lpr<float, 4>(a.lpr, f) : sgx_gat_dispatch_lpr<float, 1>(a.lpr, f);
+}
+// The element type alone: f(T()) with f16 for SGX_F16 and float otherwise, so that the launch of kernel<T> is written once.
+template <typename F>
+int sgx_dtype_dispatch(int dtype, F &&f)
+{
+    return dtype == SGX_F16 ? f(f16()) : f(float());
 }
 
 // The forms of the aggregate behind gat.hip's choice, each on scores already in the scratch:

@@ -272,9 +272,7 @@ bool wlds_arm(int n_rows, int M, int P, const void *X, int64_t ldx, const void *
     arm->LP = LP;
     arm->KS = KS;
     arm->lds_bytes = (size_t)16 * nt * LP * 2;
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 8)
-        cus = 256;
+    const int cus = sgx_cu_count(8);
     arm->wgs_per_cu = arm->lds_bytes * 2 <= kWldsLds ? 2 : 1;
     int grid = cus / 8 * 8 * arm->wgs_per_cu;
     grid = grid / (8 * n_cb) * (8 * n_cb);
@@ -469,9 +467,7 @@ bool wlds_f32_arm(int n_rows, int M, int P, const void *Wt, int64_t ldw, int64_t
     if ((uint64_t)P * (uint64_t)ldw * 4ull >= 0xFFF00000ull || (ldw & 3) || ((uintptr_t)Wt & 15)) return false;
     arm->kb = (M + 15) / 16 <= 4 ? 4 : 8;
     arm->blocks = (cols + 255) / 256;
-    int cus = 0, dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus < 1)
-        cus = 256;
+    const int cus = sgx_cu_count(1);
     const int64_t tiles = ((int64_t)n_rows + 15) / 16;
     int64_t grid = cus;                               // one workgroup per CU (the table takes most of its LDS)
     const int64_t want = (tiles + kW32Threads / 64 - 1) / (kW32Threads / 64);

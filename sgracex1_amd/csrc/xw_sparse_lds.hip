@@ -453,12 +453,7 @@ __global__ __launch_bounds__(kThreads) void xw_sparse_lds_kernel(
 int device_cus()
 {
     static int cus = 0;
-    if (cus == 0) {
-        int dev = 0, n = 0;
-        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 8)
-            n = 256;
-        cus = n;
-    }
+    if (cus == 0) cus = sgx_cu_count(8);
     return cus;
 }
 

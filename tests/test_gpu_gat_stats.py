@@ -133,15 +133,22 @@ def test_backward_edges_from_statistics(cases, kind, dt, f_head, rule):
     out together with their row's g1 -- at most 0.5 % of the live entries, asserted."""
     from sgracex1_amd import ops
     c = cases(kind, dt, 1, f_head)
-    g, A = c.g, c.csr()
-    ref = c.ref(rule)
+    A = c.csr()
     _, stats = ops.gat_aggregate(A, c.Wh, c.att, want_row_stats=True, **c.kwargs(rule, True))
+    check_backward_from_statistics(c.g, c.ref(rule), A, stats, c.Wh, f_head, rule == "mean", c.dead_weight(rule),
+                                   (kind, dt, f_head, rule))
+
+
+def check_backward_from_statistics(g, ref, A, stats, Wh, f_head, mean_rule, dead_weight, what):
+    """The comparison of test_backward_edges_from_statistics on graph g with its forward restatement ref, the adjacency
+    A on the device, its statistics and Wh [n_cols, f_head]; returns (G, sg, g1, S_out)."""
+    from sgracex1_amd import ops
     gen = torch.Generator(device="cuda")
     gen.manual_seed(f_head)
     G = torch.randn((g["n_rows"], f_head), generator=gen, device="cuda")
-    Whf = c.Wh.float()
-    dead = A.dead_rows if rule == "mean" else None
-    run = lambda: ops.gat_backward_edges_stats(A, stats, G, Whf, alpha=0.2, dead=dead, dead_weight=c.dead_weight(rule))
+    Whf = Wh.float()
+    dead = A.dead_rows if mean_rule else None
+    run = lambda: ops.gat_backward_edges_stats(A, stats, G, Whf, alpha=0.2, dead=dead, dead_weight=dead_weight)
     sg, g1, S_out = run()
     again = run()
     assert all(torch.equal(a, b) for a, b in zip((sg, g1, S_out), again)), "not the same bits on a second run"
@@ -159,7 +166,7 @@ def test_backward_edges_from_statistics(cases, kind, dt, f_head, rule):
     extra = np.where(ref["live"], extra, 0.0)
     unsure = ref["live"] & (np.abs(ref["E"]) <= ref["bE"])
     n_live = int(ref["live"].sum())
-    print("backward_stats", kind, dt, f_head, rule, "left out", int(unsure.sum()), "of", n_live, "live entries")
+    print("backward_stats", *what, "left out", int(unsure.sum()), "of", n_live, "live entries")
     assert unsure.sum() <= MAX_LEFT_OUT * n_live
     keep_e = ~unsure
     keep_r = R._seg(np.add, unsure.astype(np.int64), rowptr, 0) == 0
@@ -168,6 +175,7 @@ def test_backward_edges_from_statistics(cases, kind, dt, f_head, rule):
     R.check("sg", sg.double().cpu().numpy()[keep_e], want_sg[keep_e], (b_sg + extra)[keep_e], row[keep_e], names)
     b_g1x = b_g1 + R._seg(np.add, extra, rowptr, 0.0)
     R.check("g1", g1.double().cpu().numpy()[keep_r], want_g1[keep_r], b_g1x[keep_r], np.arange(g["n_rows"])[keep_r], names)
+    return G, sg, g1, S_out
 
 
 # ---- the SGRACE layer with config.gat_edge_outputs = 0 -------------------------------------------------------------------

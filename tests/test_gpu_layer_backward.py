@@ -211,6 +211,14 @@ def _attention_grad_case(n_rows, n_cols, P, degs, seed, padded):
         g1 = g1 + 0.25 * torch.randn(n_rows, generator=g, device=dev)              # any g1, not only the row sums
     pitch = ops.table_pitch(P, 4) if padded else P
     Wh = torch.randn((n_cols, pitch), generator=g, device=dev)[:, :P]
+    return attention_grad_check(A, sg, g1, Wh, (n_rows, n_cols, P, "nnz", nnz, "padded", padded))
+
+
+def attention_grad_check(A, sg, g1, Wh, what):
+    """ops.gat_attention_grad on these operands: the same bits twice, and within TOL of float64 Wh^T g1 and Wh^T colsum(sg)
+    by the bounds |Wh|^T |g1| and |Wh|^T colsum|sg|."""
+    from sgracex1_amd import ops
+    n_rows, n_cols, nnz = A.n_rows, A.n_cols, A.nnz
     out = ops.gat_attention_grad(A, sg, g1, Wh)
     again = ops.gat_attention_grad(A, sg, g1, Wh)
     assert torch.equal(out.view(torch.int32), again.view(torch.int32))              # the same bits on every run
@@ -221,7 +229,7 @@ def _attention_grad_case(n_rows, n_cols, P, degs, seed, padded):
     want = torch.cat([Wd[:n_rows].t() @ g1.double(), Wd.t() @ cs])
     bound = torch.cat([Wd[:n_rows].abs().t() @ g1.double().abs(), Wd.abs().t() @ cs_abs])
     ratio = R.worst(out, want, bound)
-    print("attention_grad", n_rows, n_cols, P, "nnz", nnz, "padded", padded, f"{ratio:.2e}")
+    print("attention_grad", *what, f"{ratio:.2e}")
     assert torch.isfinite(out).all() and ratio <= TOL["grad_attention"], ratio
     return out
 
