@@ -541,6 +541,48 @@ int sgx_gat_backward_edges_stats(int dtype_values, int n_rows, int n_cols, int n
                                  const float *Wh, int64_t ldw, const uint8_t *dead, const float *dead_row_sum,
                                  float *sg, float *g1, float *S_out, void *stream);
 
+/* ---- entry-split GAT aggregate ---------------------------------------------------------------------------
+ * Added without a version bump: both declarations are new.  The counterpart of "entry-split aggregation" above; it stands
+ * here because it takes the sgx_gat_stats declared in this section.
+ * sgx_gat_aggregate's arithmetic for ONE head on the schedule of sgx_spmm_csr_flat: D_i = act(sum over live e of S_e Wh_c), with the
+ * score formed as the statistics form it ("from row softmax statistics" above): E_e = LeakyReLU_alpha(fp32(score_row[i] +
+ * score_col[c])), an entry live iff values[e] > 0 as stored, S_e = exp(E_e - m_i) / l_i.  No plan, nothing read back,
+ * nothing allocated, no synchronisation, the grids a function of `nnz`: the call records into a graph and replays on other
+ * matrices of the same capacity.  n_heads != 1 (0 counts as 1): SGX_ERR_UNSUPPORTED.  There are no E / S outputs.
+ *
+ * The ownership rule is sgx_spmm_csr_flat's, unchanged (T = sgx_spmm_flat_chunk(), one wavefront per chunk, two searches
+ * in rowPtr, head slot 2k / tail slot 2c + 1, the empty rows, nnz as a capacity).  What a piece leaves is a running
+ * softmax state (m, l, acc[n_feat]) in fp32: m the maximum of the live scores seen, l the sum of exp(E_e - m) over them,
+ * acc the weighted row, rescaled when m moves; a piece without a live entry is (-inf, 0, 0).
+ *   - a row wholly inside one chunk is normalised (acc / l) and stored by that chunk;
+ *   - a crossing row's leader merges its states in chunk order in the second launch: M = max m_k, l = sum l_k exp(m_k - M),
+ *     acc = sum acc_k exp(m_k - M), and stores the row once; a state with m_k = -inf contributes nothing, also when
+ *     M = -inf -- that row is dead.
+ * Every row of D is written exactly once, by plain stores and without atomics; the order of every sum depends on rowPtr,
+ * T and the operand layout only: two runs give the same bits.
+ * Dead rows (no live entry, l = 0), by the rule of sgx_gat_aggregate_stats: fill != NULL -- the row `fill` [n_feat] fp32
+ * (n_nodes >= 1); fill == NULL and n_nodes == 0 -- 0; fill == NULL and n_nodes == n_cols -- the mean row of Wh, formed in
+ * the scratch by the column-sum pre-pass in a fixed order; fill == NULL with any other n_nodes: SGX_ERR_SHAPE.
+ * stats is optional: NULL -- nothing is written; otherwise all four members are required, score_row / score_col receive
+ * the pre-pass's scores (those of sgx_gat_aggregate without a plan, bit for bit), row_max / row_sum the merged m and l, or
+ * 0 and 0 on a dead row, written by whoever stores the row.  sgx_gat_edge_outputs and sgx_gat_backward_edges_stats work on
+ * them as they are.
+ * scratch: sgx_gat_flat_scratch_bytes(nnz, n_rows, n_cols, n_feat, mean_rule) bytes, mean_rule != 0 for the mean-row rule;
+ * monotone in nnz, never 0 for valid arguments (0 for nnz outside [0, INT32_MAX], n_rows < 0, n_cols < n_rows, n_feat < 1);
+ * 256-byte aligned, needed by every call.  Row r of the adjacency is node r of Wh (n_rows <= n_cols).
+ * Argument errors, all returned before anything is launched: the dead-row rule's; a negative size, n_cols < n_rows,
+ * n_feat < 1, ldh or ldd below n_feat, nnz outside [0, INT32_MAX]: SGX_ERR_SHAPE; n_heads != 1, a dtype other than SGX_F16 /
+ * SGX_F32: SGX_ERR_UNSUPPORTED; (n_rows == 0: SGX_OK;) rowPtr, D, Wh or attention NULL, columnIndex or values NULL with
+ * nnz > 0, a member of a given stats NULL: SGX_ERR_NULL; a table past 32-bit byte offsets: SGX_ERR_UNSUPPORTED; scratch
+ * NULL or too small: SGX_ERR_WORKSPACE; scratch off a 256-byte boundary, an index array or fill off 4 bytes, values, Wh,
+ * attention or D off an element: SGX_ERR_ALIGN. */
+size_t sgx_gat_flat_scratch_bytes(int64_t nnz, int n_rows, int n_cols, int n_feat, int mean_rule);
+int    sgx_gat_aggregate_flat(int dtype, int relu, int n_rows, int n_cols, int n_feat, int n_heads, float alpha, int64_t nnz,
+                              const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                              const void *Wh, int64_t ldh, const void *attention, void *D, int64_t ldd,
+                              const float *fill, int64_t n_nodes, void *scratch, size_t scratch_bytes,
+                              const sgx_gat_stats *stats, void *stream);
+
 /* Readout + classifier head of the graph-classification model (MOL cell 18 tail) in one launch:
  * pooled[g][:] = mean of X rows [graph_ptr[g], graph_ptr[g+1])  (global_mean_pool over a sorted
  * `batch` vector), logits[g][c] = bias[c] + W[c][:] . pooled[g][:]  (torch Linear, W [C][F] fp32).

@@ -452,15 +452,35 @@ int sgx_gat_aggregate_ep(int dtype, int relu, int fill_dead_rows, int n_rows, in
         if (rc != SGX_OK) return rc;
         a.fill = mean;
     }
-    a.vec_ok = ((uintptr_t)Wh % 16 == 0) && ((ldh * es) % 16 == 0);
-    a.vec_store = ((uintptr_t)D % 16 == 0) && ((ldd * es) % 16 == 0);
-    const int per16 = (int)(16 / es);
-    if (n_heads > 1 && (n_feat / n_heads) % per16 != 0) a.vec_ok = 0;      // a lane's 16 bytes must stay inside one head
-    a.lpr = sgx_next_pow2(a.vec_ok ? (n_feat + per16 - 1) / per16 : n_feat);
-    if (a.lpr > 64) a.lpr = 64;
-    const int rc = sgx_gat_dispatch(a, [&](auto t, auto vec, auto lpr) {
-        return gat_scores<decltype(t), decltype(vec)::value, decltype(lpr)::value>(a);
-    });
+    sgx_gat_lane_split(a);
+    const int rc = sgx_gat_scores_launch(a);
     if (rc != SGX_OK) return rc;
     return a.lay.has_two_stage ? gat_two_stage(a) : sgx_gat_one_pass(a);
+}
+
+// vec_ok, vec_store and lpr (the kernels' template arguments, sgx_gat_dispatch) from the call's pointers and pitches
+void sgx_gat_lane_split(sgx_gat_args &a)
+{
+    const size_t es = sgx_elem_size(a.dtype);
+    a.vec_ok = ((uintptr_t)a.Wh % 16 == 0) && ((a.ldh * es) % 16 == 0);
+    a.vec_store = ((uintptr_t)a.D % 16 == 0) && ((a.ldd * es) % 16 == 0);
+    const int per16 = (int)(16 / es);
+    if (a.n_heads > 1 && (a.n_feat / a.n_heads) % per16 != 0) a.vec_ok = 0;      // a lane's 16 bytes must stay inside one head
+    a.lpr = sgx_next_pow2(a.vec_ok ? (a.n_feat + per16 - 1) / per16 : a.n_feat);
+    if (a.lpr > 64) a.lpr = 64;
+}
+
+// the score pre-pass of the call: Wh.a1 / Wh.a2 of every row of the table into a.scratch at a.lay.s1 / s2
+int sgx_gat_scores_launch(const sgx_gat_args &a)
+{
+    return sgx_gat_dispatch(a, [&](auto t, auto vec, auto lpr) {
+        return gat_scores<decltype(t), decltype(vec)::value, decltype(lpr)::value>(a);
+    });
+}
+
+// the dead rows' mean row of Wh (fill_dead_rows) into `mean`: the column-sum pre-pass, slabs added in slab order
+size_t sgx_gat_mean_slab_floats(int n_feat) { return (size_t)kMeanSlabs * n_feat; }
+int sgx_gat_mean_row(int dtype, int n_cols, int n_feat, const void *Wh, int64_t ldh, float *slabs, float *mean, hipStream_t stream)
+{
+    return col_sums_launch(dtype, n_cols, n_feat, Wh, ldh, slabs, mean, n_cols, stream);
 }

@@ -285,6 +285,14 @@ int sgx_dtype_dispatch(int dtype, F &&f)
     return dtype == SGX_F16 ? f(f16()) : f(float());
 }
 
+// gat.hip, for the forms and for sgx_gat_aggregate_flat (gat_flat.hip), which lays out a scratch of its own: the lane split
+// of a call (vec_ok, vec_store, lpr), its score pre-pass into a.scratch at a.lay.s1 / s2, and the mean row of Wh that the
+// dead rows of fill_dead_rows receive (slabs: sgx_gat_mean_slab_floats(n_feat) floats)
+void sgx_gat_lane_split(sgx_gat_args &a);
+int sgx_gat_scores_launch(const sgx_gat_args &a);
+size_t sgx_gat_mean_slab_floats(int n_feat);
+int sgx_gat_mean_row(int dtype, int n_cols, int n_feat, const void *Wh, int64_t ldh, float *slabs, float *mean, hipStream_t stream);
+
 // The forms of the aggregate behind gat.hip's choice, each on scores already in the scratch:
 // gat_one_pass.hip: one walk per row with a running softmax state (any adjacency, no plan needed; E / S optional)
 int sgx_gat_one_pass(const sgx_gat_args &a);

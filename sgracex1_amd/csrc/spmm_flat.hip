@@ -18,41 +18,13 @@
 // leave the other groups idle for 8 steps and longer: those are taken afterwards by all groups together, 64 entries a
 // step, folded with lane shuffles -- the split path's walk.
 #include "spmm_device.h"
+#include "flat_device.h"          // T, the piece kinds, the chunk count and the search in rowPtr
 
 namespace {
 
-constexpr int kFlatChunk = 256;      // T: 32 steps of a lane group at F = 64 fp16, 4 steps of the wavefront on one long row
-constexpr int kFlatCoop = 64;        // a piece this long is summed by all lane groups together
-constexpr int64_t kFlatMaxNnz = 0x7FFFFFFF;
-
-enum { FLAT_NONE = 0, FLAT_ROW = 1, FLAT_HEAD = 2, FLAT_TAIL = 3 };
-
-static inline int64_t flat_chunks(int64_t nnz) { return nnz <= 0 ? 1 : (nnz + kFlatChunk - 1) / kFlatChunk; }
-static inline int flat_ldp(int n_feat) { return (int)sgx_align_up((size_t)n_feat, 4); }
 static inline size_t flat_partial_bytes(int64_t chunks, int n_feat)
 {
     return sgx_align_up((size_t)chunks * 2 * (size_t)flat_ldp(n_feat) * sizeof(float), 256);
-}
-
-// The first r in [0, n] with rowptr[r] >= x (n: none of rowptr[0, n) is), by the whole wavefront: lane l probes the last
-// element of the l-th of 64 equal blocks of the range, so a step narrows it 64-fold -- 3 dependent loads for 2^18 rows
-// where a bisection makes 18.  Reads rowptr[0, n) only, whatever the array holds.
-__device__ __forceinline__ int wave_lower_bound(const int32_t *__restrict__ rowptr, int n, int x)
-{
-    const int lane = threadIdx.x & 63;
-    int lo = 0, hi = n;                           // the answer lies in [lo, hi]
-    while (lo < hi) {
-        const int step = (hi - lo - 1) / 64 + 1;
-        const int64_t p = (int64_t)lo + (int64_t)(lane + 1) * step - 1;
-        const bool ge = p >= hi || rowptr[p] >= x;
-        const unsigned long long m = __ballot(ge);
-        if (m == 0) return hi;                    // lane 63 probed hi - 1 and it is below x
-        const int f = __ffsll(m) - 1;
-        const int64_t pf = (int64_t)lo + (int64_t)(f + 1) * step - 1;
-        lo += f * step;
-        hi = pf < hi ? (int)pf : hi;
-    }
-    return lo;
 }
 
 // scratch: [chunks][2][ldp] fp32 partial rows (head slot, tail slot), then meta [chunks][2] = (the row the chunk leads

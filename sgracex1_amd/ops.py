@@ -739,7 +739,7 @@ def _check_fill_row(fill_row, F, n_nodes):
 
 
 def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=False, fill_dead_rows=None, out=None,
-                  heads=1, use_plan=True, fill_row=None, n_nodes=None, want_row_stats=False):
+                  heads=1, use_plan=True, fill_row=None, n_nodes=None, want_row_stats=False, schedule=None):
     """Edge-softmax aggregate over an already computed Wh [adj.n_cols, F]; row r of adj is node r of Wh.
     heads > 1: F/heads columns per head, attention = heads vectors of 2*F/heads (E, S become [nnz, heads]).
     fill_dead_rows: None = decide from the adjacency (rows without a positive entry get the mean of
@@ -747,7 +747,17 @@ def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=F
     fill_row (fp32 [F]) with n_nodes: one rank of a partitioned graph -- dead rows receive this row (the mean over
     ALL nodes, reduced across ranks by the caller) and S = 1/n_nodes (sgx_gat_aggregate_fill).
     want_row_stats (instead of want_edge_outputs): returns (out, GatStats) through sgx_gat_aggregate_stats; `out` is what
-    the call without side outputs gives on the same arguments, bit for bit."""
+    the call without side outputs gives on the same arguments, bit for bit.
+    schedule="flat", or a matrix that carries the fact (Csr.with_facts(flat=True)): the entry-split form
+    (sgx_gat_aggregate_flat) -- one head, no edge outputs, no plan, no read-back, the grid a function of the entries
+    adj.col holds (a capacity), so the call records into a graph and replays; a caller that replays passes fill_dead_rows
+    itself.  The keyword with heads > 1 or want_edge_outputs raises; a flat-marked matrix with them runs as without the fact."""
+    if schedule not in (None, "flat"):
+        raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
+    heads = int(heads)
+    if schedule == "flat" and (heads != 1 or want_edge_outputs):
+        raise ValueError("the entry-split GAT aggregate has one head and no edge outputs (want_row_stats gives the statistics)")
+    flat = schedule == "flat" or (adj._flat and heads == 1 and not want_edge_outputs)
     _dev2d(Wh, "Wh")
     code = dtype_code(Wh.dtype)
     N, F = Wh.shape
@@ -758,13 +768,14 @@ def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=F
         raise TypeError("adjacency values, Wh and the attention vector must share one element type (MM.h:129-139)")
     out = _out(out, adj.n_rows, F, Wh.dtype, Wh.device)
     E = S = None
-    heads = int(heads)
     if F % heads or att.numel() != 2 * F:
         raise ValueError("F must be a multiple of heads and attention must hold 2*F elements")
     if want_edge_outputs:
         es_shape = (adj.nnz,) if heads == 1 else (adj.nnz, heads)
         E = torch.empty(es_shape, dtype=torch.float32, device=Wh.device)
         S = torch.empty(es_shape, dtype=torch.float32, device=Wh.device)
+    if flat:
+        return _gat_aggregate_flat(adj, Wh, att, alpha, relu, fill_dead_rows, out, fill_row, n_nodes, want_row_stats)
     plan = adj.gat_plan.handle if (use_plan and adj.wants_plan) else None
     if want_row_stats:
         return _gat_aggregate_stats(adj, Wh, att, alpha, relu, want_edge_outputs, fill_dead_rows, out, heads, plan, fill_row,
@@ -805,6 +816,28 @@ def _gat_aggregate_stats(adj, Wh, att, alpha, relu, want_edge_outputs, fill_dead
                                       _ptr(out), out.stride(0), _ptr(fill_row), nn, plan, _ptr(s), ctypes.byref(st), _stream()),
           "sgx_gat_aggregate_stats")
     return out, stats
+
+
+def _gat_aggregate_flat(adj, Wh, att, alpha, relu, fill_dead_rows, out, fill_row, n_nodes, want_row_stats):
+    """gat_aggregate on its checked arguments through sgx_gat_aggregate_flat: the dead-row rule as _gat_aggregate_stats maps
+    it, the scratch from the grow-only workspace, nnz = the entries adj.col holds."""
+    N, F = Wh.shape
+    if fill_row is not None:
+        _check_fill_row(fill_row, F, n_nodes)
+        fill_row = fill_row.contiguous()
+        mean_rule, nn = 0, int(n_nodes)
+    else:
+        mean_rule = int(adj.has_dead_rows if fill_dead_rows is None else bool(fill_dead_rows))
+        nn = N if mean_rule else 0
+    sbytes = lib.sgx_gat_flat_scratch_bytes(adj.nnz, adj.n_rows, N, F, mean_rule)
+    scratch = _workspace(Wh.device, sbytes)
+    stats = GatStats(adj.n_rows, N, 1, Wh.device) if want_row_stats else None
+    st = stats.struct() if stats is not None else None
+    check(lib.sgx_gat_aggregate_flat(dtype_code(Wh.dtype), int(bool(relu)), adj.n_rows, N, F, 1, float(alpha), adj.nnz,
+                                     _ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(Wh), Wh.stride(0), _ptr(att), _ptr(out),
+                                     out.stride(0), _ptr(fill_row), nn, _ptr(scratch), sbytes,
+                                     ctypes.byref(st) if st is not None else None, _stream()), "sgx_gat_aggregate_flat")
+    return (out, stats) if want_row_stats else out
 
 
 def col_sums(X, n_feat=None):
