@@ -58,6 +58,11 @@ downloaded by torch_geometric and are not available offline.
              ONE transfer, the best epoch's weights are put back and both passes run once more on the samples of that
              epoch: restored_test_acc, which equals that epoch's logged test accuracy; the final train_acc is then the
              restored model's
+--flat      with --trainer, --batch-size and --device-batches (unquantised, no --accb): the padded loaders deliver their
+             batches for the entry-split schedule (NeighborLoader(pad=True, schedule="flat")): every CSR of a batch is
+             marked with_facts(flat=True), the layers aggregate by stored entries (SGX_SCHEDULE_FLAT) and build no plan, so
+             fan-outs over 63 (--num-neighbors 100,10), feature rows over 64 entries and capacities past 2^20 entries
+             pad -- and, with --replay, record -- like any other
 """
 import argparse
 import os
@@ -88,7 +93,7 @@ def planted_partition(n, classes, f_in, p_in, p_out, seed, device):
 
 def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, verbose=True, emulate=False,
         batch_size=None, num_neighbors=None, lean_gat=False, device_batches=False, accb=0, trainer=False,
-        replay=False, keep_best=False):
+        replay=False, keep_best=False, flat=False):
     from sgracex1_amd import config, sgrace
     config.acc = acc
     config.accb = int(accb)
@@ -122,8 +127,10 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         train_mask[train] = True
         data = pyg_lite.NodeData(x, edge_index, y, train_mask=train_mask)
         ready = {"prepare": "sym_norm2", "transposed": bool(accb or attention), "quant": sgrace.quant_constants}
-        if replay:
+        if replay or flat:
             ready["pad"] = True
+        if flat:
+            ready["schedule"] = "flat"
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
                                          shuffle=True, seed=seed, **(ready if device_batches else {}))
     passes = None
@@ -137,7 +144,8 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         passes = []
         for nodes in (val, test):
             ev = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=nodes, shuffle=False,
-                                         seed=seed, prepare="sym_norm2", quant=sgrace.quant_constants, pad=bool(replay))
+                                         seed=seed, prepare="sym_norm2", quant=sgrace.quant_constants, pad=bool(replay or flat),
+                                         schedule="flat" if flat else None)
             if replay and nodes.numel() >= batch_size:
                 passes.append((ev, node_trainer.capture_eval_loader(ev)))
             else:
@@ -273,6 +281,7 @@ if __name__ == "__main__":
     ap.add_argument("--trainer", action="store_true")
     ap.add_argument("--replay", action="store_true")
     ap.add_argument("--keep-best", action="store_true")
+    ap.add_argument("--flat", action="store_true")
     a = ap.parse_args()
     if (a.batch_size is None) != (a.num_neighbors is None) or (a.batch_size is not None and a.acc != 1):
         ap.error("--batch-size and --num-neighbors go together, on the kernels (--acc 1)")
@@ -286,6 +295,8 @@ if __name__ == "__main__":
         ap.error("--replay on mini-batches covers the layers with the staged backward, quantised or not (no --accb)")
     if a.keep_best and not (a.trainer and a.batch_size is not None and a.device_batches and not a.accb):
         ap.error("--keep-best needs --trainer with the per-epoch passes: --batch-size, --num-neighbors, --device-batches, no --accb")
+    if a.flat and not (a.trainer and a.batch_size is not None and a.device_batches and not a.accb and a.qbits == 32):
+        ap.error("--flat needs --trainer with --batch-size, --num-neighbors and --device-batches, unquantised and without --accb")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
         num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches,
-        accb=int(a.accb), trainer=a.trainer, replay=a.replay, keep_best=a.keep_best)
+        accb=int(a.accb), trainer=a.trainer, replay=a.replay, keep_best=a.keep_best, flat=a.flat)

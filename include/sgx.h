@@ -183,6 +183,12 @@ typedef enum sgx_layer_order {
     SGX_ORDER_AGGREGATE_FIRST = 1   /* D = act((A.X).W)                                    */
 } sgx_layer_order;
 
+/* The schedule of the layer's aggregate stage (sgx_layer_desc.schedule_adj). */
+typedef enum sgx_layer_schedule_kind {
+    SGX_SCHEDULE_DEFAULT = 0,       /* by rows: with plan_adj when one is given, without otherwise */
+    SGX_SCHEDULE_FLAT = 1           /* by stored entries: "entry-split aggregation" below          */
+} sgx_layer_schedule_kind;
+
 typedef struct sgx_layer_desc {
     /* AXI-Lite scalars of the reference, same names (K.cpp:3777-3790, MMN cell 13) */
     int32_t gemm_mode;   /* 0: X is CSR (rowPtr_fea, columnIndex_fea, values_fea)
@@ -265,10 +271,36 @@ typedef struct sgx_layer_desc {
      * sgx_layer_workspace_bytes answers for the form the descriptor it is given will take: size the workspace with the
      * descriptor that runs, pointers and plans set. */
     int32_t order;
+
+    /* Appended without a version bump (SGX_VERSION stays 110): both are 0 in a descriptor that was zeroed, and 0 is the
+     * layer as it was.
+     * schedule_adj: sgx_layer_schedule_kind.  Under SGX_SCHEDULE_FLAT the aggregate stage runs on the entry-split schedule
+     * -- sgx_spmm_csr_flat (gat_mode 0) or sgx_gat_aggregate_flat (gat_mode 1, one head) -- with its scratch laid out
+     * inside `workspace` (sgx_layer_workspace_bytes accounts for it at nnz_adj): no plan, nothing read back, nothing
+     * allocated, every grid a function of the descriptor's host fields, so the whole layer records into a graph and replays
+     * on another adjacency of the same capacity, whatever its rows are like.  The X.W stage runs as under the default
+     * schedule (with plan_fea if one is given); the fused square dense fp16 form is not taken.
+     * THE RULE: D is bit-equal to the X.W stage call (sgx_xw_dense, or sgx_transpose + sgx_xw_sparse, into an H whose
+     * rows start on 16-byte boundaries, as the layer's own H does) followed by sgx_spmm_csr_flat / sgx_gat_aggregate_flat on the
+     * same operands and the capacity nnz_adj; the statistics of sgx_layer_forward_stats are those of
+     * sgx_gat_aggregate_flat(stats=).  Dead rows: gat_fill_dead_rows = 1 is that call's mean-row rule (fill NULL,
+     * n_nodes = M_adj), 0 its zero rule (fill NULL, n_nodes = 0).
+     * SGX_ERR_UNSUPPORTED, before any launch, for SGX_SCHEDULE_FLAT together with any of: plan_adj != NULL, quant != NULL,
+     * acc_mode != SGX_ACC_F32, gat_heads > 1, E or S outputs, SGX_ORDER_AGGREGATE_FIRST; and for a schedule_adj that is
+     * neither enumerator.  nnz_adj < 0 (or above INT32_MAX): SGX_ERR_SHAPE.
+     * nnz_adj: the entries columnIndex_adj / values_adj hold -- a capacity, a bound on rowPtr_adj[N_adj], as `nnz` in the
+     * entry-split calls.  Read only under SGX_SCHEDULE_FLAT. */
+    int32_t schedule_adj;
+    int64_t nnz_adj;
 } sgx_layer_desc;
 
 size_t sgx_layer_workspace_bytes(const sgx_layer_desc *desc);
 int    sgx_layer_forward(const sgx_layer_desc *desc, void *stream);
+/* Which schedule the aggregate stage of sgx_layer_forward / sgx_layer_forward_stats takes for this descriptor, for reports
+ * and tests (added without a version bump: a new declaration): a host query without a launch that reads no device
+ * memory, answered by the checks the call itself makes.  0 = by rows without a plan, 1 = by rows with plan_adj,
+ * 2 = entry-split; negative = the sgx_status the call would return for the descriptor's modes and shapes. */
+int    sgx_layer_schedule(const sgx_layer_desc *desc);
 
 /* ---- the stages, individually (the dataflow processes of K.cpp:3629-3752) ---------- */
 

@@ -17,6 +17,7 @@ struct Carve {
     size_t q_off, q_bytes;        // quantised layer: copies of B, X (values), A (values), attention
     size_t qb, qx, qa, qt;        //   their offsets inside the q block
     size_t qw;                    //   int8 form: column sums of the weight codes
+    size_t f_off, f_bytes;        // SGX_SCHEDULE_FLAT: the entry-split aggregate's scratch (spmm_flat.hip / gat_flat.hip lay it out)
     int64_t ldc;                  //   int8 form: row pitch of the code matrices (bytes, multiple of 16); 0 = fp32 form
     size_t total;
 };
@@ -45,8 +46,11 @@ bool int8_form(const sgx_layer_desc *d)
 // two launches; under SGX_ORDER_REFERENCE it is the association the layer takes for this shape -- both gather 64 columns per
 // edge, and the default arithmetic is bound to the reference by a tolerance, not bit for bit (SGX_ACC_REF_HALF is, and stays
 // on the reference's order).  X comes dense at pitch M_fea = 64.
+bool flat_schedule(const sgx_layer_desc *d) { return d->schedule_adj == SGX_SCHEDULE_FLAT; }
+
 bool fused_dense_form(const sgx_layer_desc *d)
 {
+    if (flat_schedule(d)) return false;          // the entry-split schedule is the staged launches' (sgx_layer_desc.schedule_adj)
     if (d->dtype != SGX_F16 || d->gemm_mode != 1 || d->gat_mode || d->quant || d->acc_mode != SGX_ACC_F32) return false;
     if (d->M_fea != 64 || d->P_w != 64 || sgx_tune().layer_no_fused_dense) return false;
     return sgx_spmm_dense_applicable(d->M_adj, d->values_fea, d->B, d->D, d->plan_adj);
@@ -57,6 +61,7 @@ Carve carve(const sgx_layer_desc *d)
     Carve c;
     c.qw = 0;
     c.ldc = 0;
+    c.f_off = c.f_bytes = 0;
     const size_t es = sgx_elem_size(d->dtype);
     const size_t ldh = (size_t)sgx_ldh(d->dtype, d->P_w);
     size_t off = 0;
@@ -102,6 +107,15 @@ Carve carve(const sgx_layer_desc *d)
         c.qt = o; o += d->gat_mode ? sgx_align_up((size_t)2 * d->P_w * 4, 256) : 0;
         c.q_bytes = o; off += o;
     }
+    if (flat_schedule(d)) {
+        // behind everything the default schedule lays out, on a 256-byte boundary: the launch code of the two entry-split
+        // calls takes it as their `scratch`
+        off = sgx_align_up(off, 256);
+        c.f_off = off;
+        c.f_bytes = d->gat_mode ? sgx_gat_flat_scratch_bytes(d->nnz_adj, d->N_adj, d->M_adj, d->P_w, d->gat_fill_dead_rows)
+                                : sgx_spmm_flat_scratch_bytes(d->nnz_adj, d->P_w);
+        off += c.f_bytes;
+    }
     c.total = off;
     return c;
 }
@@ -116,6 +130,15 @@ int check_desc(const sgx_layer_desc *d)
     if (d->order == SGX_ORDER_AGGREGATE_FIRST &&
         (d->gemm_mode != 1 || d->gat_mode || d->quant || d->acc_mode != SGX_ACC_F32))
         return SGX_ERR_UNSUPPORTED;
+    if (d->schedule_adj != SGX_SCHEDULE_DEFAULT && d->schedule_adj != SGX_SCHEDULE_FLAT) return SGX_ERR_UNSUPPORTED;
+    if (flat_schedule(d)) {
+        // what the entry-split calls do not have: a plan to follow, the quantised epilogue, the reference-half sums, heads,
+        // per-edge outputs; and the aggregate-first order gathers X, not H
+        if (d->plan_adj || d->quant || d->acc_mode != SGX_ACC_F32 || d->gat_heads > 1 || d->E || d->S ||
+            d->order == SGX_ORDER_AGGREGATE_FIRST)
+            return SGX_ERR_UNSUPPORTED;
+        if (d->nnz_adj < 0 || d->nnz_adj > 0x7FFFFFFF) return SGX_ERR_SHAPE;
+    }
     if (d->quant) {
         const sgx_quant *q = d->quant;
         if (d->dtype != SGX_F32 || d->acc_mode != SGX_ACC_F32) return SGX_ERR_UNSUPPORTED;   // SG.py:1545: float32 buffers
@@ -255,7 +278,7 @@ int layer_forward(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *str
 
     // stage 1: H = X . W          (loop_fea, K.cpp:2932)
     int scores_ready = 0;
-    if (d->gat_mode && !q && d->gemm_mode == 1 && d->acc_mode == SGX_ACC_F32 && attention &&
+    if (d->gat_mode && !q && d->gemm_mode == 1 && d->acc_mode == SGX_ACC_F32 && attention && !flat_schedule(d) &&
         sgx_gat_scores_fusable(d->dtype, d->P_w, d->gat_heads, d->plan_adj)) {
         // the product's epilogue forms the attention scores beside H (one pass over H less)
         // heads of 32 columns: the scores themselves; wider heads: a partial per 64-column group, added up by a small kernel
@@ -295,7 +318,17 @@ int layer_forward(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *str
 
     // stage 2: D = act(A . H)     (loop_adj, K.cpp:3339) or the edge-softmax aggregate (SG.py:634-661)
     if (d->ev_agg_begin) SGX_HIP_CHECK(hipEventRecord((hipEvent_t)d->ev_agg_begin, s));
-    if (d->gat_mode) {
+    if (flat_schedule(d)) {
+        // the public entry-split calls are the launch code (argument checks, scratch layout, dispatch): the layer hands them
+        // its H and its slice of the workspace, so D -- and the statistics -- are theirs bit for bit
+        if (d->gat_mode)
+            rc = sgx_gat_aggregate_flat(d->dtype, d->relu, d->N_adj, d->M_adj, d->P_w, 1, d->alpha, d->nnz_adj, d->rowPtr_adj,
+                                        d->columnIndex_adj, values_adj, H, ldh, attention, d->D, d->P_w, /*fill*/nullptr,
+                                        d->gat_fill_dead_rows ? (int64_t)d->M_adj : 0, ws + c.f_off, c.f_bytes, stats, s);
+        else
+            rc = sgx_spmm_csr_flat(d->dtype, d->relu, d->N_adj, d->M_adj, d->P_w, d->nnz_adj, d->rowPtr_adj, d->columnIndex_adj,
+                                   values_adj, H, ldh, d->D, d->P_w, ws + c.f_off, c.f_bytes, s);
+    } else if (d->gat_mode) {
         if (!attention) return SGX_ERR_NULL;
         rc = sgx_gat_aggregate_ep(d->dtype, d->relu, d->gat_fill_dead_rows, d->N_adj, d->M_adj, d->P_w, d->gat_heads, d->alpha,
                                   d->rowPtr_adj, d->columnIndex_adj,
@@ -316,6 +349,13 @@ int layer_forward(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *str
     return SGX_OK;
 }
 }  // namespace
+
+extern "C" int sgx_layer_schedule(const sgx_layer_desc *d)
+{
+    const int rc = check_desc(d);
+    if (rc != SGX_OK) return rc;
+    return flat_schedule(d) ? 2 : (d->plan_adj ? 1 : 0);
+}
 
 extern "C" int sgx_layer_forward(const sgx_layer_desc *d, void *stream) { return layer_forward(d, nullptr, stream); }
 

@@ -242,7 +242,7 @@ class Csr:
         key = _adj_quant_key(qc)
         if key not in self._quantized:
             self._quantized[key] = Csr(self.rowptr, self.col, fake_quantize(self.val, 0, qc.w_qbits, qc.a_s, qc.a_z),
-                                       self.n_cols, self._plan)
+                                       self.n_cols, self._plan).with_facts(flat=self._flat)
         return self._quantized[key]
 
     @property
@@ -579,7 +579,8 @@ def transpose(x, ldo=None):
 def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_edge_outputs=False, quant_int8=False,
                   acc_mode=SGX_ACC_F32, spmm_block=1, bias_count=0, out=None, use_plan=True, agg_events=None,
                   quant=None, adj_quantized=False, cache_quantized_adj=True, fea_threads=1, adj_threads=1,
-                  gat_heads=1, order="reference", want_row_stats=False):
+                  gat_heads=1, order="reference", want_row_stats=False, schedule=None, fill_dead_rows=None,
+                  _schedule_query=False):
     """One fused layer  D = act(A . (X . W))  through sgx_layer_forward.
 
     adj : Csr [N, M_adj];  fea : Csr [M_adj, M_fea] (gemm_mode 0) or dense tensor (gemm_mode 1);
@@ -602,7 +603,29 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
     edge and the default arithmetic follows the reference within a tolerance, not bit for bit (SGX_ACC_REF_HALF does and
     keeps X.W first).  Plans that cut rows or reorder them, tables of 4 GiB and more and SGX_LAYER_NO_FUSED_DENSE in the
     environment keep the staged launches (include/sgx.h, sgx_layer_desc.order).
+    schedule="flat", or an adjacency that carries the fact (Csr.with_facts(flat=True)): the aggregate stage on the
+    entry-split schedule (SGX_SCHEDULE_FLAT, nnz_adj = adj.nnz, the entries adj.col holds: a capacity) -- no plan is looked
+    up, nothing is read back, so the layer records into a graph and replays on another adjacency of the same capacity; D is
+    bit-equal to the X.W stage call followed by spmm / gat_aggregate(schedule="flat").  The keyword together with quant,
+    gat_heads > 1, SGX_ACC_REF_HALF, want_edge_outputs or order="aggregate_first" raises; a flat-marked adjacency with one of
+    them runs as without the fact.  A flat-marked feature CSR on that route has its X.W stage run as spmm(fea, W,
+    schedule="flat") -- a CSR X.W is an aggregation over W -- and the layer is then the two stage calls, composed here.
+    fill_dead_rows (GAT): None = decide from the adjacency (adj.has_dead_rows: a read-back unless the fact is known), or the
+    rule itself, as gat_aggregate takes it.
     """
+    if schedule not in (None, "flat"):
+        raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
+    refused = [name for name, hit in (("quant", quant is not None), ("gat_heads > 1", int(gat_heads) > 1),
+                                      ("SGX_ACC_REF_HALF", acc_mode != SGX_ACC_F32), ("want_edge_outputs", want_edge_outputs),
+                                      ("order='aggregate_first'", order == "aggregate_first")) if hit]
+    if schedule == "flat" and refused:
+        raise ValueError(f"the entry-split schedule does not go with {', '.join(refused)} (sgx_layer_desc.schedule_adj)")
+    flat = schedule == "flat" or (adj._flat and not refused)
+    if flat and isinstance(fea, Csr) and fea._flat:
+        if _schedule_query:
+            return 2
+        return _layer_forward_flat_stages(adj, fea, Wt, relu, gat_attention, alpha, bias_count, out, agg_events, want_row_stats,
+                                          fill_dead_rows)
     _dev(Wt, "Wt")
     code = dtype_code(Wt.dtype)
     P, M_fea = Wt.shape
@@ -614,7 +637,7 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
     if order == "aggregate_first" and not can_swap:
         raise ValueError("aggregate_first needs dense features, the GCN aggregate and the default arithmetic "
                          "(no GAT, no quantised layer, no SGX_ACC_REF_HALF)")
-    swap = order == "aggregate_first" or (order == "auto" and can_swap and M_fea < P)
+    swap = order == "aggregate_first" or (order == "auto" and can_swap and M_fea < P and not flat)
     d.order = SGX_ORDER_AGGREGATE_FIRST if swap else SGX_ORDER_REFERENCE
     d.gemm_mode, d.relu, d.gat_mode = gemm_mode, int(bool(relu)), int(gat_attention is not None)
     d.N_adj, d.M_adj, d.M_fea, d.P_w = adj.n_rows, adj.n_cols, M_fea, P
@@ -639,9 +662,11 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
     if quant is not None and not adj_quantized and (cache_quantized_adj or gat_attention is not None):
         adj, adj_quantized = adj.quantized(quant), True
     if gat_attention is not None:
-        d.gat_fill_dead_rows = int(adj.has_dead_rows)
+        d.gat_fill_dead_rows = int(adj.has_dead_rows if fill_dead_rows is None else bool(fill_dead_rows))
     d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), adj.val.data_ptr()
-    if use_plan and adj.wants_plan:
+    if flat:
+        d.schedule_adj, d.nnz_adj = _lib.SGX_SCHEDULE_FLAT, adj.nnz
+    elif use_plan and adj.wants_plan:
         d.plan_adj = (adj.gat_plan if gat_attention is not None else adj.plan).handle
     d.B = Wt.data_ptr()
     out = _out(out, adj.n_rows, P, Wt.dtype, Wt.device)
@@ -673,6 +698,11 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
         elif quant_int8:
             qs.flags |= _lib.SGX_QUANT_INT8
         d.quant = ctypes.pointer(qs)
+    if _schedule_query:
+        route = lib.sgx_layer_schedule(ctypes.byref(d))
+        if route < 0:
+            check(int(route), "sgx_layer_schedule")
+        return int(route)
     nbytes = lib.sgx_layer_workspace_bytes(ctypes.byref(d))
     ws = _workspace(Wt.device, nbytes)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
@@ -683,6 +713,48 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
         return out, stats
     check(lib.sgx_layer_forward(ctypes.byref(d), _stream()), "sgx_layer_forward")
     return (out, E, S) if want_edge_outputs else out
+
+
+def layer_schedule(adj, fea, Wt, **kwargs):
+    """Which schedule the aggregate stage of layer_forward(adj, fea, Wt, **kwargs) takes (sgx_layer_schedule; no launch):
+    0 = by rows without a plan, 1 = by rows with the adjacency's plan, 2 = entry-split.  The operands are prepared as
+    layer_forward prepares them (a plan the call would build is built)."""
+    return layer_forward(adj, fea, Wt, _schedule_query=True, **kwargs)
+
+
+def _layer_forward_flat_stages(adj, fea, Wt, relu, gat_attention, alpha, bias_count, out, agg_events, want_row_stats,
+                               fill_dead_rows):
+    """layer_forward on the entry-split schedule for a flat-marked feature CSR: sgx_layer_forward has one X.W stage for a
+    CSR X (sgx_xw_sparse) and no way to take an H formed elsewhere, so the layer is its two stage calls -- H = spmm(fea,
+    W, schedule="flat") into rows of table_pitch() elements, then the entry-split aggregate of H -- and D is theirs bit for
+    bit."""
+    _dev(Wt, "Wt")
+    P, M_fea = Wt.shape
+    if adj.val.dtype != Wt.dtype:
+        raise TypeError("adjacency, features and weights must share one element type (MM.h:129-139)")
+    if fea.val.dtype != Wt.dtype or fea.n_rows != adj.n_cols or fea.n_cols != M_fea:
+        raise ValueError("feature CSR does not match adjacency / weights")
+    if want_row_stats and gat_attention is None:
+        raise ValueError("want_row_stats needs the GAT aggregate and excludes want_edge_outputs")
+    out = _out(out, adj.n_rows, P, Wt.dtype, Wt.device)
+    if out.stride(0) != P:
+        raise ValueError("the layer writes D densely ([N_adj][P_w], K.cpp:802): `out` must not have padded rows")
+    if bias_count > 0:                      # K.cpp:3876-3889: the reference preloads and returns without computing
+        return (out, GatStats(adj.n_rows, adj.n_cols, 1, Wt.device)) if want_row_stats else out
+    ldh = table_pitch(P, Wt.element_size())
+    W = transpose(Wt, ldo=ldh)                                              # B [P][M] -> W [M][ldh]
+    H = torch.zeros((adj.n_cols, ldh), dtype=Wt.dtype, device=Wt.device)
+    spmm(fea, W, n_feat=P, out=H[:, :P], schedule="flat")
+    if agg_events is not None:
+        check(lib.sgx_event_record(agg_events[0], _stream()), "sgx_event_record")
+    if gat_attention is None:
+        res = spmm(adj, H, relu=relu, n_feat=P, out=out, schedule="flat")
+    else:
+        res = gat_aggregate(adj, H[:, :P], gat_attention, alpha=alpha, relu=relu, fill_dead_rows=fill_dead_rows, out=out,
+                            want_row_stats=want_row_stats, schedule="flat")
+    if agg_events is not None:
+        check(lib.sgx_event_record(agg_events[1], _stream()), "sgx_event_record")
+    return res
 
 
 def fake_quantize(x, signed, qbits, scale, zero, out=None):
@@ -888,8 +960,11 @@ def xt_g(X, G):
 CSR_TRANSPOSE_DEFAULT = "device"
 
 
-def _transposed(T, return_order, order):
-    if T.n_rows > 0 and T.nnz >= 64 * T.n_rows:
+def _transposed(T, return_order, order, flat=False):
+    if flat:
+        # the transpose of an entry-split matrix is one: no plan for it, whatever its rows (a hub column's) are like
+        T.with_facts(flat=True)
+    elif T.n_rows > 0 and T.nnz >= 64 * T.n_rows:
         # a feature matrix transposed: a handful of rows, each as long as the graph is wide (MUTAG: 7 rows of ~500 entries) --
         # below the size at which a plan is built by itself, and exactly the shape that needs one: without it 7 lane groups
         # walk 60 dependent steps each (58 us for a 3.4 K-entry matrix) where the plan's 64-edge tasks take a few
@@ -903,7 +978,8 @@ def csr_transpose(A, return_order=False, method=None):
     method: "device" -- sgx_csr_transpose, the stable transpose of include/sgx.h in four launches per sort pass and no
     synchronisation; "torch" -- the int64 key, argsort and gathers this function was before; None -- CSR_TRANSPOSE_DEFAULT.
     On a matrix that stores every (row, col) pair once both give the same arrays; copies of a pair keep their source order
-    on the device and stand in no defined order under "torch"."""
+    on the device and stand in no defined order under "torch".
+    The transpose of a flat-marked matrix (Csr.with_facts(flat=True)) is flat-marked and no plan is built for it."""
     method = CSR_TRANSPOSE_DEFAULT if method is None else method
     if method == "device":
         nnz, dev = A.nnz, A.rowptr.device
@@ -916,7 +992,7 @@ def csr_transpose(A, return_order=False, method=None):
                                     _ptr(rowptr_t), _ptr(col_t), _ptr(val_t), _ptr(order), _ptr(ws), ws.numel(), _stream()),
               "sgx_csr_transpose")
         T = Csr(rowptr_t, col_t[:nnz], val_t[:nnz], A.n_rows)
-        return _transposed(T, return_order, order[:nnz].long() if return_order else None)
+        return _transposed(T, return_order, order[:nnz].long() if return_order else None, A._flat)
     if method != "torch":
         raise ValueError(f"csr_transpose: method must be None, 'device' or 'torch', not {method!r}")
     row = torch.repeat_interleave(torch.arange(A.n_rows, device=A.col.device, dtype=torch.int64),
@@ -926,7 +1002,7 @@ def csr_transpose(A, return_order=False, method=None):
     order = torch.argsort(key)
     T = Csr.from_coo(col[order].contiguous(), row[order].to(torch.int32).contiguous(), val[order].contiguous(),
                      A.n_cols, A.n_rows)
-    return _transposed(T, return_order, order)
+    return _transposed(T, return_order, order, A._flat)
 
 
 def _backward_edge_operands(adj, G, Wh, dead):

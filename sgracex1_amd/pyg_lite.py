@@ -414,16 +414,32 @@ class NeighborLoader:
     checked here, before any device work (check_pad_quant): w_qbits in {8, 4, 2, 1}, a finite positive a_s, fq(1) > 0 -- no
     filler row is dead under the quantised mask -- and fq(0) == 0 -- its spare entries carry no weight; ValueError naming
     `quant` otherwise.  quant.constants(w) passes at every width.  The recorded step then covers the quantised model as
-    well; the short last batch takes the unpadded quant= route."""
+    well; the short last batch takes the unpadded quant= route.
+
+    schedule="flat" (with pad=True; None by default): the batches are for the entry-split schedule -- adj_norm, the feature
+    CSR and, with transposed=True, the transposed pattern and X^T (always delivered) arrive with_facts(flat=True) at their
+    honest longest row, so none of them wants a plan (ops.Csr.wants_plan), at capacity and for the short last batch alike,
+    and the layers take sgx_layer_forward's SGX_SCHEDULE_FLAT, ops.spmm / ops.gat_aggregate(schedule="flat") for them.
+    The three refusals that exist because a plan costs a read-back then do not apply: max(fanouts) + 1 > 64, feature
+    rows of over 64 entries, capacities from 2^20 entries.  Still refused: a fan-out of -1 (an unbounded row has no
+    capacity) and quant= (the quantised layer has no entry-split epilogue yet)."""
 
     def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0, prepare=None, fill=0,
-                 dtype=torch.float32, transposed=False, quant=None, pad=False):
+                 dtype=torch.float32, transposed=False, quant=None, pad=False, schedule=None):
         from . import ops
+        if schedule not in (None, "flat"):
+            raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
+        if schedule == "flat" and not pad:
+            raise ValueError("schedule='flat' needs pad=True: it is the padded batches' route past the plan refusals")
+        if schedule == "flat" and quant is not None:
+            raise ValueError("quant= does not go with schedule='flat': the quantised layer has no entry-split epilogue yet")
+        self.schedule = schedule
+        flat = schedule == "flat"
         if pad and prepare != "sym_norm2":
             raise ValueError("pad=True needs prepare='sym_norm2'")
         if pad and any(int(k) < 0 for k in num_neighbors):
             raise ValueError("pad=True needs fan-outs >= 0: a fan-out of -1 leaves a row unbounded")
-        if pad and max(int(k) for k in num_neighbors) + 1 > 64:
+        if pad and not flat and max(int(k) for k in num_neighbors) + 1 > 64:
             raise ValueError("pad=True needs max(num_neighbors) + 1 <= 64: a longer adjacency row wants a plan, and a plan "
                              "costs a read-back")
         if quant is not None and not prepare:
@@ -467,12 +483,12 @@ class NeighborLoader:
             m = self.input_nodes
             if m.numel() and (int(m.min()) < 0 or int(m.max()) >= n):      # (once per loader; a batch's status is not read)
                 raise ValueError("input_nodes must be node ids of the graph")
-            if self.fea._max_row > 64:
+            if not flat and self.fea._max_row > 64:
                 raise ValueError("pad=True needs feature rows of at most 64 entries: a longer one wants a plan, and a plan "
                                  "costs a read-back")
             B = min(self.batch_size, n)
             self.capacity = cap = ops.node_pad_capacity(self.csr, B, self.num_neighbors, self.fea)
-            if cap.nnz_norm >= 1 << 20 or cap.nnz_fea >= 1 << 20:
+            if not flat and (cap.nnz_norm >= 1 << 20 or cap.nnz_fea >= 1 << 20):
                 raise ValueError(f"pad=True: the capacity ({cap.nnz_norm} adjacency, {cap.nnz_fea} feature entries) reaches 2^20 "
                                  "entries: such a batch wants a plan, and a plan costs a read-back")
             self.buffers = ops.NodePadBuffers(cap, n, dtype, dev, x.shape[1], self.y is not None, len(self.masks),
@@ -547,16 +563,21 @@ class NeighborLoader:
         padded = x_buf is not None
         x = ops.pack_rows(self.data.x, s.n_id, out=x_buf)
         A, fea, n = s.adj_norm, s.fea, s.n_id.numel()           # (n: the capacity's rows when padded)
+        flat = self.schedule == "flat"
+        if flat:                                                # the entry-split schedule: no plan for either, whatever their rows
+            A.with_facts(flat=True)
+            fea.with_facts(flat=True)
         ops.attach(x, ("fea_csr", self.dtype), fea)
         ops.attach(s.edge_index_agg, ("sym_norm2", n, 1, self.dtype), (s.edge_index_agg, A.val[:A.nnz], A))
         if self.transposed:
             # (padded: ops.csr_transpose builds a plan, with its read-back, from 64 entries per feature column on)
-            if not padded or self.capacity.nnz_fea < 64 * fea.n_cols:
+            # (the transpose of a flat-marked matrix is flat-marked and builds none)
+            if not padded or flat or self.capacity.nnz_fea < 64 * fea.n_cols:
                 fea32 = fea
                 if self.dtype != torch.float32:          # (the values alone are cast: never through a dense tensor)
                     fea32 = ops.attach(x, ("fea_csr", torch.float32),
                                        ops.Csr(fea.rowptr, fea.col[:fea.nnz], fea.val[:fea.nnz].float(), fea.n_cols).with_facts(
-                                           max_row=fea._max_row))
+                                           max_row=fea._max_row, flat=fea._flat))
                 ops.attach(x, ("fea_csr_t", torch.float32), ops.csr_transpose(fea32, method="device"))
             A._transpose_pattern = ops.csr_transpose(A, return_order=True, method="device")
         fields = dict(x=x, edge_index=s.edge_index, edge_index_agg=s.edge_index_agg, adj_norm=A, n_id=s.n_id.long(),

@@ -158,6 +158,9 @@ class FPYNQ_GAT(torch.autograd.Function):
             # config.accb = 1: the backward as one call (sgx_layer_backward); its fp32 CSRs of X and X^T are built here,
             # once per feature tensor, so that the backward itself builds nothing
             ctx.accb, ctx.gemm_mode = int(config.accb), int(rm.gemm_mode)
+            if ctx.accb == 1 and A._flat:
+                raise ValueError("config.accb = 1 does not take a flat-marked adjacency (Csr.with_facts(flat=True)): "
+                                 "sgx_layer_backward has no entry-split schedule yet; use config.accb = 0")
             if ctx.accb == 1 and ctx.gemm_mode == 0:
                 ctx.fea32 = ops.feature_csr32(input)
             my_ip.alpha = self.alpha
@@ -165,7 +168,9 @@ class FPYNQ_GAT(torch.autograd.Function):
             # they are the faster form (dense features wider than 128 columns; sgx.h SGX_QUANT_INT8_AUTO);
             # config.fake_quantization alone: the fp32 emulation of the grid, as the reference states it
             int8 = "auto" if (qc is not None and config.hardware_quantize) else False
-            ctx.lean = bool(ctx.gat) and not int(config.gat_edge_outputs)
+            # a flat-marked adjacency runs the entry-split aggregate, which writes no E / S: the statistics route whatever
+            # config.gat_edge_outputs says (the quantised layer has no entry-split form and runs as without the fact)
+            ctx.lean = bool(ctx.gat) and (not int(config.gat_edge_outputs) or (A._flat and qc is None))
             if ctx.lean:
                 # the row softmax statistics instead of E and S (3 n + n_cols floats in place of 2 nnz); the forward is
                 # the one without side outputs
@@ -283,13 +288,18 @@ class FPYNQ_GAT(torch.autograd.Function):
                 sg, g1 = ops.gat_backward_edges(A, E, S, g.contiguous(), Wh, ctx.alpha, dead=ctx.dead)
             # attention matrix, fp32 values; A's schedule -- and A's longest row where its builder knew it, so that P wants a
             # plan exactly where A does (a loader's batch of short rows builds none: no read-back, capturable)
-            P = ops.Csr(A.rowptr, A.col, S.contiguous(), A.n_cols, A.plan if A.wants_plan else None).with_facts(max_row=A._max_row)
+            # -- and A's entry-split fact, so that P @ g takes the schedule A's own aggregate took
+            P = ops.Csr(A.rowptr, A.col, S.contiguous(), A.n_cols, A.plan if A.wants_plan else None).with_facts(
+                max_row=A._max_row, flat=A._flat)
             # column sums of sg = row sums over A^T; the transposed pattern is built once per graph
             if getattr(A, "_transpose_pattern", None) is None:
                 A._transpose_pattern = ops.csr_transpose(A, return_order=True)
             AT, order = A._transpose_pattern
             ones = torch.ones((A.n_rows, 1), dtype=torch.float32, device=g.device)
-            g2 = ops.spmm(ops.Csr(AT.rowptr, AT.col, sg[order].contiguous(), AT.n_cols), ones, use_plan=False)
+            sgT = ops.Csr(AT.rowptr, AT.col, sg[order].contiguous(), AT.n_cols)
+            # a hub column of A is a long row here: by stored entries for a flat-marked A (its transpose carries the fact),
+            # one lane group per row otherwise
+            g2 = ops.spmm(sgT.with_facts(flat=True), ones) if AT._flat else ops.spmm(sgT, ones, use_plan=False)
             ga = ops.xt_g(Wh, torch.cat([g1.unsqueeze(1), g2], dim=1).contiguous())   # [F, 2] = Wh^T [g1 g2]
             grad_attention = torch.cat([ga[:, 0], ga[:, 1]]).unsqueeze(1)
         else:
