@@ -49,7 +49,8 @@ downloaded by torch_geometric and are not available offline.
              validation and test passes are replayed the same way, ONE recorded evaluation per padded loader
              (NodeTrainer.capture_eval_loader); with --qbits the padded batches carry the quantised adjacency of both
              layers (NeighborLoader(pad=True, quant=sgrace.quant_constants)) and the recorded step and evaluations are the
-             quantised model's; --accb stays an eager route
+             quantised model's; --accb is an eager route except with --flat, whose batches sgx_layer_backward takes
+             entry-split
 --keep-best  with --trainer, --batch-size and --device-batches (no --accb), where every epoch ends with the validation and
              test passes: the demo's save-best / load-best step on the device (train.BestTracker, sgx_keep_best).  Every
              epoch ends with one call that compares the validation counts with the best so far in integers, keeps a copy
@@ -58,11 +59,13 @@ downloaded by torch_geometric and are not available offline.
              ONE transfer, the best epoch's weights are put back and both passes run once more on the samples of that
              epoch: restored_test_acc, which equals that epoch's logged test accuracy; the final train_acc is then the
              restored model's
---flat      with --trainer, --batch-size and --device-batches (unquantised, no --accb): the padded loaders deliver their
+--flat      with --trainer, --batch-size and --device-batches (unquantised): the padded loaders deliver their
              batches for the entry-split schedule (NeighborLoader(pad=True, schedule="flat")): every CSR of a batch is
              marked with_facts(flat=True), the layers aggregate by stored entries (SGX_SCHEDULE_FLAT) and build no plan, so
              fan-outs over 63 (--num-neighbors 100,10), feature rows over 64 entries and capacities past 2^20 entries
-             pad -- and, with --replay, record -- like any other
+             pad -- and, with --replay, record -- like any other; with --accb every layer's backward is the one call on
+             the same schedule (sgx_layer_grad_desc.schedule_adj / _fea / _xt), X and X^T delivered flat-marked by the
+             loader (transposed=True), and records and replays as well
 """
 import argparse
 import os
@@ -134,7 +137,7 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
                                          shuffle=True, seed=seed, **(ready if device_batches else {}))
     passes = None
-    if loader is not None and node_trainer is not None and device_batches and not accb:
+    if loader is not None and node_trainer is not None and device_batches and (not accb or flat):
         # the demo's test(loader, split) every epoch (demo_sgrace.py:509-601), summed on the device: the nodes outside the
         # training set are split into a validation and a test set with a loader each; an epoch ends with a pass over both
         # (NodeTrainer.evaluate(into=); with --replay ONE recorded evaluation per loader, NodeTrainer.capture_eval_loader)
@@ -291,12 +294,12 @@ if __name__ == "__main__":
         ap.error("--trainer runs the tail on the kernels (--acc 1)")
     if a.replay and (not a.trainer or (a.batch_size is not None and not a.device_batches)):
         ap.error("--replay replays the step of --trainer: the full-graph one, or the padded mini-batch one of --device-batches")
-    if a.replay and a.batch_size is not None and a.accb:
-        ap.error("--replay on mini-batches covers the layers with the staged backward, quantised or not (no --accb)")
+    if a.replay and a.batch_size is not None and a.accb and not a.flat:
+        ap.error("--replay on mini-batches covers the layers with the staged backward, quantised or not (--accb only with --flat)")
     if a.keep_best and not (a.trainer and a.batch_size is not None and a.device_batches and not a.accb):
         ap.error("--keep-best needs --trainer with the per-epoch passes: --batch-size, --num-neighbors, --device-batches, no --accb")
-    if a.flat and not (a.trainer and a.batch_size is not None and a.device_batches and not a.accb and a.qbits == 32):
-        ap.error("--flat needs --trainer with --batch-size, --num-neighbors and --device-batches, unquantised and without --accb")
+    if a.flat and not (a.trainer and a.batch_size is not None and a.device_batches and a.qbits == 32):
+        ap.error("--flat needs --trainer with --batch-size, --num-neighbors and --device-batches, unquantised")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
         num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches,
         accb=int(a.accb), trainer=a.trainer, replay=a.replay, keep_best=a.keep_best, flat=a.flat)

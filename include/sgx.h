@@ -1270,11 +1270,42 @@ typedef struct sgx_layer_grad_desc {
 
     void          *workspace;         /* sgx_layer_backward_workspace_bytes(d), 256-byte aligned   */
     size_t         workspace_bytes;
+
+    /* Appended without a version bump (SGX_VERSION stays 110): all five are 0 in a descriptor that was zeroed, and 0 is
+     * the call as it was -- the same workspace size, status and bits.
+     * schedule_adj / schedule_fea / schedule_xt: sgx_layer_schedule_kind, per matrix.  Under SGX_SCHEDULE_FLAT the
+     * products over that matrix run on the entry-split schedule ("entry-split aggregation" above): no plan, nothing read
+     * back, every grid a function of the descriptor's host fields, so the call records into a graph and replays on other
+     * matrices inside the same capacities, whatever their rows are like.
+     *   schedule_adj   pg = P . G runs as sgx_spmm_csr_flat at nnz_adj and (GAT) the attention gradient as
+     *                  sgx_gat_attention_grad_flat at nnz_adj.  The edge pass and the dead-row select stay as they are:
+     *                  the edge pass reads its entry count from rowPtr_adj[N_adj] on the device, touches nothing at or
+     *                  behind it and sizes its launches by N_adj and the device alone.  nnz_adj is then a capacity: the
+     *                  entries columnIndex_adj / values_adj (and E, S) hold, a bound on rowPtr_adj[N_adj].
+     *   schedule_fea   GAT, gemm_mode 0: Wh = X . W runs as sgx_spmm_csr_flat(fea, W) at nnz_fea.  Not read otherwise.
+     *   schedule_xt    gemm_mode 0: grad_weights runs as sgx_spmm_csr_flat(X^T, pg) at nnz_xt.  Not read in gemm_mode 1.
+     * nnz_fea / nnz_xt: the entries columnIndex_fea / _xt and values_fea / _xt hold; read only under their flat schedule.
+     * THE RULE is the one above: every output equals the named stage calls composed on the same operands and capacities,
+     * bit for bit -- the edge pass, then the flat calls, then sgx_xw_dense / sgx_xt_g.
+     * The scratch of the flat calls lies behind the default layout inside `workspace`, each on a 256-byte boundary
+     * (sgx_layer_backward_workspace_bytes accounts for it at the capacities).
+     * Refused before any launch: a schedule that is read and is neither enumerator, or SGX_SCHEDULE_FLAT together with the
+     * plan of the same matrix (plan_adj / plan_fea / plan_xt): SGX_ERR_UNSUPPORTED; a capacity that is read and lies outside
+     * [0, INT32_MAX]: SGX_ERR_SHAPE (INT32_MAX itself is a capacity like any other, as in the entry-split calls; under the
+     * default schedule nnz_adj = INT32_MAX stays SGX_ERR_UNSUPPORTED);
+     * a table a flat product gathers (G, W, pg) past 32-bit byte offsets: SGX_ERR_UNSUPPORTED. */
+    int32_t        schedule_adj, schedule_fea, schedule_xt;
+    int64_t        nnz_fea, nnz_xt;
 } sgx_layer_grad_desc;
 
 /* 0 for a descriptor the call refuses (workspace and workspace_bytes are not looked at) */
 size_t sgx_layer_backward_workspace_bytes(const sgx_layer_grad_desc *d);
 int    sgx_layer_backward(const sgx_layer_grad_desc *d, void *stream);
+/* Which schedules sgx_layer_backward takes for this descriptor, for reports and tests (a new declaration, no version
+ * bump): a host query without a launch that reads no device memory and neither workspace field, answered by the checks
+ * the call itself makes.  Bit 0: the adjacency's products, bit 1: Wh = X . W, bit 2: grad_weights = X^T . pg run
+ * entry-split (a schedule field that is not read leaves its bit 0); negative: the sgx_status the call would return. */
+int    sgx_layer_backward_schedule(const sgx_layer_grad_desc *d);
 
 /* The attention gradient of the GAT backward from the edge pass's outputs, without a transposed pattern:
  *     grad_attention[0:F]  = Wh^T g1            = sum_r g1[r] Wh[r]
@@ -1294,6 +1325,37 @@ size_t sgx_gat_attention_grad_workspace_bytes(int n_rows, int n_feat);
 int sgx_gat_attention_grad(int n_rows, int n_cols, int n_feat, const int32_t *rowPtr, const int32_t *columnIndex,
                            const float *sg, const float *g1, const float *Wh, int64_t ldw, float *grad_attention,
                            void *workspace, size_t workspace_bytes, void *stream);
+
+/* The same two outputs by stored entries (added without a version bump: new declarations).  Neither half has rows --
+ * grad_attention[F:2F] = sum_{e < end} sg_e Wh[col_e] is one reduction over all stored entries -- so the schedule is a
+ * function of nnz, n_rows, F and Wh's alignment alone, balanced on any degree distribution: a hub row is spread over the
+ * chunks its entries fall in instead of being walked by one workgroup.  The rule, with T = sgx_spmm_flat_chunk():
+ *   - end = min(rowPtr[n_rows], nnz), read on the device.  nnz is a host argument and may be a capacity: a bound on
+ *     rowPtr[n_rows], and no more than columnIndex / sg hold.  Nothing at or behind end, and nothing behind the capacity,
+ *     is read, whatever rowPtr holds.
+ *   - the entries are cut into chunks of T consecutive entries, chunk c = [cT, min((c+1)T, end)), and the rows into
+ *     chunks of T consecutive rows for the first half; one wavefront per chunk.  No search in rowPtr is made.
+ *   - inside a chunk, L lanes (L = the power of two >= ceil(F / 4), at most 64; 16 bytes of a Wh row each) form a lane
+ *     group, 64 / L groups; group g takes items g, g + 64 / L, ... of the chunk in ascending order: one fp32 fma per item
+ *     and column, sg_e Wh[col_e][f] (g1[r] Wh[r][f] for a row chunk) onto a register that starts at +0.  The groups' sums
+ *     are added in group order, group 0 first, and the chunk's partial row [F] is stored to the workspace.
+ *   - a second launch adds the partials of a half by chunk index in a fixed two-level order: chain q = 0 .. 15 adds the
+ *     chunks q, q + 16, q + 32, ... below ceil(end / T) (ceil(n_rows / T) for the first half) in ascending order from +0;
+ *     the 16 chains are added in order q from +0 and the element is stored once.
+ * Rows of Wh are gathered through a range-checked buffer, 16 bytes per lane when Wh is 16-byte aligned and ldw a multiple
+ * of 4, one element at a time otherwise (the same sums).  Plain loads and stores, no atomics, every output element written
+ * once; chunks at or past end write nothing and the second launch does not read them: the result has the same bits on
+ * every run and for every capacity nnz >= rowPtr[n_rows].  n_rows == 0, or end == 0 with g1 = 0: both halves exactly +0.
+ * The longest addition chain of an element: T L / 64 + 64 / L + ceil(chunks / 16) + 16.
+ * workspace: sgx_gat_attention_grad_flat_workspace_bytes(nnz, n_rows, F) bytes (0 for nnz outside [0, INT32_MAX],
+ * n_rows < 0 or F < 1), 256-byte aligned.  Argument errors are those of sgx_gat_attention_grad, and nnz outside
+ * [0, INT32_MAX]: SGX_ERR_SHAPE; all are returned before anything reaches the device.  Asynchronous on `stream`, no
+ * allocation, no synchronisation: capturable, and a recorded call replays on any matrix inside the capacity. */
+size_t sgx_gat_attention_grad_flat_workspace_bytes(int64_t nnz, int n_rows, int n_feat);
+int    sgx_gat_attention_grad_flat(int n_rows, int n_cols, int n_feat, int64_t nnz,
+                                   const int32_t *rowPtr, const int32_t *columnIndex,
+                                   const float *sg, const float *g1, const float *Wh, int64_t ldw,
+                                   float *grad_attention, void *workspace, size_t workspace_bytes, void *stream);
 
 /* ---- the transpose of a CSR matrix -------------------------------------------------------------
  * Added without a version bump (SGX_VERSION stays 110): every declaration below is new, and nothing above changes.

@@ -233,7 +233,17 @@ int ag_launch(bool vec, unsigned grid, hipStream_t s, int n_rows, int n_feat, in
 struct Carve {
     size_t adj32, x32, wt, wh, sg, g1, s_out, cs, cs_scratch, mean, drs_tmp, drs, pg, ag, spmm, xtg, total;
     int64_t ldwh;
+    // behind the layout above: the scratch of the entry-split calls, with its size
+    size_t flat_adj, flat_adj_bytes, flat_ag, flat_ag_bytes, flat_fea, flat_fea_bytes, flat_xt, flat_xt_bytes;
 };
+
+// which of the three schedule fields the call reads, and takes as SGX_SCHEDULE_FLAT
+static inline bool reads_fea(const sgx_layer_grad_desc *d) { return d->gat_mode == 1 && d->gemm_mode == 0; }
+static inline bool reads_xt(const sgx_layer_grad_desc *d) { return d->gemm_mode == 0; }
+static inline bool flat_adj(const sgx_layer_grad_desc *d) { return d->schedule_adj == SGX_SCHEDULE_FLAT; }
+static inline bool flat_fea(const sgx_layer_grad_desc *d) { return reads_fea(d) && d->schedule_fea == SGX_SCHEDULE_FLAT; }
+static inline bool flat_xt(const sgx_layer_grad_desc *d) { return reads_xt(d) && d->schedule_xt == SGX_SCHEDULE_FLAT; }
+static inline bool schedule_known(int s) { return s == SGX_SCHEDULE_DEFAULT || s == SGX_SCHEDULE_FLAT; }
 
 int check_desc(const sgx_layer_grad_desc *d)
 {
@@ -241,9 +251,16 @@ int check_desc(const sgx_layer_grad_desc *d)
     if (d->gat_heads > 1) return SGX_ERR_UNSUPPORTED;
     if (d->gat_mode != 0 && d->gat_mode != 1) return SGX_ERR_UNSUPPORTED;
     if (d->gemm_mode != 0 && d->gemm_mode != 1) return SGX_ERR_UNSUPPORTED;
+    if (!schedule_known(d->schedule_adj) || (reads_fea(d) && !schedule_known(d->schedule_fea)) ||
+        (reads_xt(d) && !schedule_known(d->schedule_xt)))
+        return SGX_ERR_UNSUPPORTED;
+    if ((flat_adj(d) && d->plan_adj) || (flat_fea(d) && d->plan_fea) || (flat_xt(d) && d->plan_xt)) return SGX_ERR_UNSUPPORTED;
+    if (flat_adj(d) && d->nnz_adj > 0x7fffffffll) return SGX_ERR_SHAPE;
+    if ((flat_fea(d) && (d->nnz_fea < 0 || d->nnz_fea > 0x7fffffffll)) || (flat_xt(d) && (d->nnz_xt < 0 || d->nnz_xt > 0x7fffffffll)))
+        return SGX_ERR_SHAPE;
     if (d->N_adj < 1 || d->M_adj < 1 || d->M_fea < 1 || d->P_w < 1 || d->nnz_adj < 0) return SGX_ERR_SHAPE;
     if (d->N_adj != d->M_adj) return SGX_ERR_SHAPE;                            // P . G needs a square P
-    if (d->nnz_adj >= 0x7fffffffll) return SGX_ERR_UNSUPPORTED;
+    if (!flat_adj(d) && d->nnz_adj >= 0x7fffffffll) return SGX_ERR_UNSUPPORTED;          // (a flat capacity reaches INT32_MAX, as the entry-split calls do)
     if (d->dtype_adj != SGX_F16 && d->dtype_adj != SGX_F32) return SGX_ERR_UNSUPPORTED;
     if (!d->rowPtr_adj || !d->columnIndex_adj || !d->values_adj || !d->W || !d->G || !d->grad_weights) return SGX_ERR_NULL;
     if (d->ldg < d->P_w) return SGX_ERR_SHAPE;
@@ -270,6 +287,12 @@ int check_desc(const sgx_layer_grad_desc *d)
         const unsigned long long g_bytes = (unsigned long long)d->N_adj * (unsigned long long)d->ldg * 4ull;
         if (w_bytes >= 0xFFFFFFF0ull || g_bytes >= 0xFFFFFFF0ull) return SGX_ERR_UNSUPPORTED;   // the edge pass's 32-bit offsets
     }
+    // the entry-split calls take tables inside 32-bit byte offsets only: G (P . G), W (X . W), pg (X^T . pg)
+    if ((flat_adj(d) && sgx_spmm_table_big(SGX_F32, d->M_adj, d->ldg, d->P_w)) ||
+        (flat_fea(d) && sgx_spmm_table_big(SGX_F32, d->M_fea, d->P_w, d->P_w)) ||
+        (flat_xt(d) && sgx_spmm_table_big(SGX_F32, d->N_adj, d->P_w, d->P_w)))
+        return SGX_ERR_UNSUPPORTED;
+    if (flat_adj(d) && (unsigned long long)d->ldg * 4ull >= 0xFFFFFFF0ull) return SGX_ERR_UNSUPPORTED;
     return SGX_OK;
 }
 
@@ -305,6 +328,12 @@ Carve carve(const sgx_layer_grad_desc *d)
     }
     c.spmm = take(spmm);
     c.xtg = d->gemm_mode == 1 ? take(sgx_xt_g_workspace_bytes(d->N_adj, d->M_fea, d->P_w)) : 0;
+    auto take_sized = [&](bool wanted, size_t bytes, size_t &size) { size = wanted ? bytes : 0; return wanted ? take(bytes) : (size_t)0; };
+    c.flat_adj = take_sized(flat_adj(d), sgx_spmm_flat_scratch_bytes(d->nnz_adj, d->P_w), c.flat_adj_bytes);
+    c.flat_ag = take_sized(flat_adj(d) && d->gat_mode, sgx_gat_attention_grad_flat_workspace_bytes(d->nnz_adj, d->N_adj, d->P_w),
+                           c.flat_ag_bytes);
+    c.flat_fea = take_sized(flat_fea(d), sgx_spmm_flat_scratch_bytes(d->nnz_fea, d->P_w), c.flat_fea_bytes);
+    c.flat_xt = take_sized(flat_xt(d), sgx_spmm_flat_scratch_bytes(d->nnz_xt, d->P_w), c.flat_xt_bytes);
     c.total = at;
     return c;
 }
@@ -361,6 +390,13 @@ extern "C" size_t sgx_layer_backward_workspace_bytes(const sgx_layer_grad_desc *
     return carve(d).total;
 }
 
+extern "C" int sgx_layer_backward_schedule(const sgx_layer_grad_desc *d)
+{
+    const int rc = check_desc(d);
+    if (rc != SGX_OK) return rc;
+    return (flat_adj(d) ? 1 : 0) | (flat_fea(d) ? 2 : 0) | (flat_xt(d) ? 4 : 0);
+}
+
 extern "C" int sgx_layer_backward(const sgx_layer_grad_desc *d, void *stream)
 {
     int rc = check_desc(d);
@@ -392,6 +428,9 @@ extern "C" int sgx_layer_backward(const sgx_layer_grad_desc *d, void *stream)
             rc = sgx_transpose(SGX_F32, M, P, d->W, P, Wt, M, stream);
             if (rc != SGX_OK) return rc;
             rc = sgx_xw_dense(SGX_F32, SGX_ACC_F32, 1, n, M, P, X, ldx, Wt, M, Wh, c.ldwh, stream);
+        } else if (flat_fea(d)) {                            // a CSR X . W is an aggregation over the rows of W
+            rc = sgx_spmm_csr_flat(SGX_F32, 0, n, M, P, d->nnz_fea, d->rowPtr_fea, d->columnIndex_fea, d->values_fea, d->W, P, Wh, c.ldwh,
+                                   ws + c.flat_fea, c.flat_fea_bytes, stream);
         } else {
             rc = sgx_xw_sparse(SGX_F32, SGX_ACC_F32, 1, n, M, P, d->rowPtr_fea, d->columnIndex_fea, d->values_fea, d->W, P, Wh, c.ldwh,
                                d->plan_fea, spmm_scratch, sgx_spmm_scratch_bytes(d->plan_fea, P), stream);
@@ -422,8 +461,12 @@ extern "C" int sgx_layer_backward(const sgx_layer_grad_desc *d, void *stream)
             p_values = d->S;
         }
         if (rc != SGX_OK) return rc;
-        rc = sgx_gat_attention_grad(n, d->M_adj, P, d->rowPtr_adj, d->columnIndex_adj, sg, g1, Wh, c.ldwh, d->grad_attention, ws + c.ag,
-                                    (size_t)ag_slices(n) * 2 * (size_t)P * 4, stream);
+        if (flat_adj(d))
+            rc = sgx_gat_attention_grad_flat(n, d->M_adj, P, d->nnz_adj, d->rowPtr_adj, d->columnIndex_adj, sg, g1, Wh, c.ldwh,
+                                             d->grad_attention, ws + c.flat_ag, c.flat_ag_bytes, stream);
+        else
+            rc = sgx_gat_attention_grad(n, d->M_adj, P, d->rowPtr_adj, d->columnIndex_adj, sg, g1, Wh, c.ldwh, d->grad_attention, ws + c.ag,
+                                        (size_t)ag_slices(n) * 2 * (size_t)P * 4, stream);
         if (rc != SGX_OK) return rc;
     } else if (d->dtype_adj == SGX_F16) {
         rc = cast_f16_f32(1, (int)d->nnz_adj, d->values_adj, d->nnz_adj, (float *)(ws + c.adj32), d->nnz_adj, s);
@@ -434,8 +477,12 @@ extern "C" int sgx_layer_backward(const sgx_layer_grad_desc *d, void *stream)
     }
 
     // pg = P . G
-    rc = sgx_spmm_csr(SGX_F32, SGX_ACC_F32, 1, 0, n, d->M_adj, P, d->rowPtr_adj, d->columnIndex_adj, p_values, d->G, d->ldg, pg, P,
-                      d->plan_adj, spmm_scratch, sgx_spmm_scratch_bytes(d->plan_adj, P), stream);
+    if (flat_adj(d))
+        rc = sgx_spmm_csr_flat(SGX_F32, 0, n, d->M_adj, P, d->nnz_adj, d->rowPtr_adj, d->columnIndex_adj, p_values, d->G, d->ldg, pg, P,
+                               ws + c.flat_adj, c.flat_adj_bytes, stream);
+    else
+        rc = sgx_spmm_csr(SGX_F32, SGX_ACC_F32, 1, 0, n, d->M_adj, P, d->rowPtr_adj, d->columnIndex_adj, p_values, d->G, d->ldg, pg, P,
+                          d->plan_adj, spmm_scratch, sgx_spmm_scratch_bytes(d->plan_adj, P), stream);
     if (rc != SGX_OK) return rc;
     if (d->gat_mode && d->dead) {                                               // a dead row of P is 1/N on every column
         rc = sgx_col_sums(SGX_F32, n, P, d->G, d->ldg, cs, cs_scratch, stream);
@@ -451,6 +498,9 @@ extern "C" int sgx_layer_backward(const sgx_layer_grad_desc *d, void *stream)
     if (d->gemm_mode == 1)                                                       // X^T . pg
         return sgx_xt_g(d->dtype_x, n, M, P, d->X, d->ldx, pg, P, d->grad_weights, P, ws + c.xtg,
                         sgx_xt_g_workspace_bytes(n, M, P), stream);
+    if (flat_xt(d))
+        return sgx_spmm_csr_flat(SGX_F32, 0, M, n, P, d->nnz_xt, d->rowPtr_xt, d->columnIndex_xt, d->values_xt, pg, P, d->grad_weights, P,
+                                 ws + c.flat_xt, c.flat_xt_bytes, stream);
     return sgx_spmm_csr(SGX_F32, SGX_ACC_F32, 1, 0, M, n, P, d->rowPtr_xt, d->columnIndex_xt, d->values_xt, pg, P, d->grad_weights, P,
                         d->plan_xt, spmm_scratch, sgx_spmm_scratch_bytes(d->plan_xt, P), stream);
 }

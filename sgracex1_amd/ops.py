@@ -1081,9 +1081,15 @@ def gat_backward_edges_stats(adj, stats, G, Wh, alpha=0.2, dead=None, dead_weigh
     return sg, g1, S
 
 
-def gat_attention_grad(adj, sg, g1, Wh):
+def gat_attention_grad(adj, sg, g1, Wh, schedule=None):
     """[Wh^T g1 ; Wh^T colsum(sg)] fp32 [2 F] from the edge pass's outputs, gathered over the stored entries in row order
-    (sgx_gat_attention_grad): no transposed pattern; the same bits on every run."""
+    (sgx_gat_attention_grad): no transposed pattern; the same bits on every run.
+    schedule="flat", or a matrix that carries the fact (Csr.with_facts(flat=True)): by stored entries
+    (sgx_gat_attention_grad_flat) -- a hub row is spread over the chunks its entries fall in, the grid is a function of the
+    entries adj.col holds (a capacity: the matrix's own end is read from rowptr on the device), and the result has the same
+    bits at every capacity."""
+    if schedule not in (None, "flat"):
+        raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
     _dev2d(Wh, "Wh")
     if sg.dtype != torch.float32 or g1.dtype != torch.float32 or Wh.dtype != torch.float32:
         raise TypeError("gat_attention_grad works on float32 sg, g1, Wh")
@@ -1091,6 +1097,13 @@ def gat_attention_grad(adj, sg, g1, Wh):
         raise ValueError("Wh must be [adj.n_cols, F], g1 [adj.n_rows], sg [nnz], n_rows <= n_cols")
     F = Wh.shape[1]
     out = torch.empty(2 * F, dtype=torch.float32, device=Wh.device)
+    if schedule == "flat" or adj._flat:
+        nbytes = lib.sgx_gat_attention_grad_flat_workspace_bytes(adj.nnz, adj.n_rows, F)
+        ws = _workspace(Wh.device, nbytes)
+        check(lib.sgx_gat_attention_grad_flat(adj.n_rows, adj.n_cols, F, adj.nnz, _ptr(adj.rowptr), _ptr(adj.col), _ptr(sg), _ptr(g1),
+                                              _ptr(Wh), Wh.stride(0), _ptr(out), _ptr(ws), ws.numel(), _stream()),
+              "sgx_gat_attention_grad_flat")
+        return out
     nbytes = lib.sgx_gat_attention_grad_workspace_bytes(adj.n_rows, F)
     ws = _workspace(Wh.device, nbytes)
     check(lib.sgx_gat_attention_grad(adj.n_rows, adj.n_cols, F, _ptr(adj.rowptr), _ptr(adj.col), _ptr(sg), _ptr(g1), _ptr(Wh),
@@ -1100,23 +1113,38 @@ def gat_attention_grad(adj, sg, g1, Wh):
 
 def feature_csr32(x):
     """The fp32 CSR of a feature tensor and of its transpose, each built once per tensor (cached on it, as the forward's
-    fea_csr is): what the one-call backward reads in gemm_mode 0 instead of a dense X."""
+    fea_csr is): what the one-call backward reads in gemm_mode 0 instead of a dense X.  Where the tensor already carries
+    a flat-marked feature CSR of another element type (the forward's), the fact goes along: the pair built here is
+    flat-marked too and wants no plan (the transpose of a flat-marked matrix is flat-marked).  That build is reached only off
+    the loader path -- a caller who marked the forward's feature CSR by hand: it goes through a dense tensor and
+    synchronises, and the pair carries no longest-row fact.  NeighborLoader(schedule="flat", transposed=True) delivers both
+    entries itself, and nothing is built here."""
     def build():
         d = x.detach()
-        return Csr.from_dense(d if d.layout == torch.strided else d.to_dense(), torch.float32)     # (as the forward builds it)
+        Xc = Csr.from_dense(d if d.layout == torch.strided else d.to_dense(), torch.float32)       # (as the forward builds it)
+        seen = [recorded(x, ("fea_csr", dt)) for dt in (torch.float16, torch.float32)]
+        return Xc.with_facts(flat=True) if any(c is not None and c._flat for c in seen) else Xc
 
     Xc = cached_on(x, ("fea_csr", torch.float32), build)
     return Xc, cached_on(x, ("fea_csr_t", torch.float32), lambda: csr_transpose(Xc))
 
 
 def layer_backward(adj, X, W, G, gat=False, gemm_mode=1, alpha=0.2, E=None, S=None, stats=None, dead_weight=0.0, dead=None,
-                   mask=None, want_grad_input=True):
+                   mask=None, want_grad_input=True, schedule=None, _schedule_query=False):
     """The SGRACE layer's backward in one call (sgx_layer_backward): -> (grad_input [n, M] or None, grad_weights [M, P],
     grad_attention [2 P] or None), fp32.  adj: the forward's adjacency (GCN: its values are P); X: the layer's input -- a
     dense fp16|fp32 tensor (gemm_mode 1) or, gemm_mode 0, the feature tensor whose CSRs feature_csr32 caches (or that pair
     itself): never made dense; W [M, P] fp32; G = grad_output [n, P] fp32.  GAT: E and S, or stats with dead_weight; dead (bool [n]) the
     forward's dead rows; mask: the Csr whose values the edge pass masks with (default adj).  want_grad_input False: that
-    product is not launched."""
+    product is not launched.
+    schedule=None: each of the adjacency, the feature CSR and X^T that carries the entry-split fact (Csr.with_facts(flat=
+    True)) has its products run on that schedule (sgx_layer_grad_desc.schedule_adj / _fea / _xt = SGX_SCHEDULE_FLAT at the
+    entries its col holds, a capacity): no plan is built for it and nothing is read back, so the call records and replays
+    at any fan-out.  "flat": all three, marked or not; "rows": none of them -- a flat-marked matrix runs by rows without a
+    plan, as the layer does where its forward did not take the entry-split route."""
+    if schedule not in (None, "flat", "rows"):
+        raise ValueError(f"schedule must be None, 'flat' or 'rows', not {schedule!r}")
+    is_flat = lambda m: schedule == "flat" or (schedule is None and m._flat)
     _dev2d(G, "G")
     _dev(W, "W")
     if G.dtype != torch.float32 or W.dtype != torch.float32:
@@ -1131,8 +1159,11 @@ def layer_backward(adj, X, W, G, gat=False, gemm_mode=1, alpha=0.2, E=None, S=No
     d.dtype_adj = dtype_code(vals.dtype)
     d.rowPtr_adj, d.columnIndex_adj, d.values_adj = adj.rowptr.data_ptr(), adj.col.data_ptr(), vals.data_ptr()
     keep = [vals]
-    plan = adj.plan if adj.wants_plan else None
-    d.plan_adj = plan.handle if plan is not None else None
+    if is_flat(adj):
+        d.schedule_adj = _lib.SGX_SCHEDULE_FLAT                # (nnz_adj above: what adj.col holds)
+    else:
+        plan = adj.plan if adj.wants_plan else None
+        d.plan_adj = plan.handle if plan is not None else None
     if gemm_mode == 1:
         _dev2d(X, "X")
         if X.shape != (n, M):
@@ -1145,8 +1176,14 @@ def layer_backward(adj, X, W, G, gat=False, gemm_mode=1, alpha=0.2, E=None, S=No
         d.dtype_x = SGX_F32
         d.rowPtr_fea, d.columnIndex_fea, d.values_fea = Xc.rowptr.data_ptr(), Xc.col.data_ptr(), Xc.val.data_ptr()
         d.rowPtr_xt, d.columnIndex_xt, d.values_xt = Xt.rowptr.data_ptr(), Xt.col.data_ptr(), Xt.val.data_ptr()
-        d.plan_fea = Xc.plan.handle if Xc.wants_plan else None
-        d.plan_xt = Xt.plan.handle if Xt.wants_plan else None
+        if is_flat(Xc):
+            d.schedule_fea, d.nnz_fea = _lib.SGX_SCHEDULE_FLAT, Xc.nnz
+        else:
+            d.plan_fea = Xc.plan.handle if Xc.wants_plan else None
+        if is_flat(Xt):
+            d.schedule_xt, d.nnz_xt = _lib.SGX_SCHEDULE_FLAT, Xt.nnz
+        else:
+            d.plan_xt = Xt.plan.handle if Xt.wants_plan else None
         keep += [Xc, Xt]
     d.W, d.G, d.ldg = W.data_ptr(), G.data_ptr(), G.stride(0)
     grad_attention = None
@@ -1172,11 +1209,22 @@ def layer_backward(adj, X, W, G, gat=False, gemm_mode=1, alpha=0.2, E=None, S=No
     if want_grad_input:
         grad_input = torch.empty((n, table_pitch(M, 4)), dtype=torch.float32, device=G.device)
         d.grad_input, d.ld_gi = grad_input.data_ptr(), grad_input.stride(0)
+    if _schedule_query:
+        route = lib.sgx_layer_backward_schedule(ctypes.byref(d))
+        if route < 0:
+            check(int(route), "sgx_layer_backward_schedule")
+        return route
     nbytes = lib.sgx_layer_backward_workspace_bytes(ctypes.byref(d))
     ws = _workspace(G.device, nbytes)
     d.workspace, d.workspace_bytes = ws.data_ptr(), ws.numel()
     check(lib.sgx_layer_backward(ctypes.byref(d), _stream()), "sgx_layer_backward")
     return (None if grad_input is None else grad_input[:, :M]), grad_weights, grad_attention
+
+
+def layer_backward_schedule(adj, X, W, G, **kwargs):
+    """Which schedules layer_backward(adj, X, W, G, **kwargs) takes, from the very descriptor it builds
+    (sgx_layer_backward_schedule; no launch): bit 0 the adjacency's products, bit 1 Wh = X . W, bit 2 X^T . pg entry-split."""
+    return layer_backward(adj, X, W, G, _schedule_query=True, **kwargs)
 
 
 def readout_mean_linear(x, graph_ptr, weight=None, bias=None, want_pooled=False):

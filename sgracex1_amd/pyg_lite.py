@@ -402,7 +402,8 @@ class NeighborLoader:
     arrives unpadded, as before.  What the eager call raises for a batch (repeated seeds) is OR-ed into a device word
     instead; loader.status() reads it back once -- at the end of an epoch, say -- and raises it then.  transposed=True
     works as before for the adjacency; the feature transpose is delivered only where it wants no plan (fewer than 64
-    entries per feature column at capacity), since a plan costs a read-back -- config.accb = 1 is not a padded route.
+    entries per feature column at capacity), since a plan costs a read-back -- config.accb = 1 is a padded route only
+    with schedule="flat" (below).
     With attention on, a live row without a positive entry (fill = 0 leaves the rows of the last hop so) takes its
     uniform softmax over the N padded columns rather than the live ones: the layers' rule, on the padded width.
     ValueError where a batch CSR would want a plan (ops.Csr.wants_plan), which costs a read-back: a fan-out of -1,
@@ -420,6 +421,8 @@ class NeighborLoader:
     CSR and, with transposed=True, the transposed pattern and X^T (always delivered) arrive with_facts(flat=True) at their
     honest longest row, so none of them wants a plan (ops.Csr.wants_plan), at capacity and for the short last batch alike,
     and the layers take sgx_layer_forward's SGX_SCHEDULE_FLAT, ops.spmm / ops.gat_aggregate(schedule="flat") for them.
+    config.accb = 1 takes them too (with transposed=True): sgx_layer_backward runs the adjacency's products, Wh = X . W and
+    X^T . pg on its entry-split schedules at the capacities, so the one-call backward records and replays as well.
     The three refusals that exist because a plan costs a read-back then do not apply: max(fanouts) + 1 > 64, feature
     rows of over 64 entries, capacities from 2^20 entries.  Still refused: a fan-out of -1 (an unbounded row has no
     capacity) and quant= (the quantised layer has no entry-split epilogue yet)."""

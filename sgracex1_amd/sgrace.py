@@ -31,7 +31,10 @@ with (the quantised one in quantised mode) has P = 1/N on all N columns, not onl
 
 `config.accb == 1` (with `config.acc == 1`) runs that backward as ONE call of the C ABI, sgx_layer_backward: the same
 arithmetic on the same kernels, the attention gradient gathered in row order instead of through a transposed pattern, a
-CSR feature matrix never made dense, and grad_input left out when the input needs no gradient.
+CSR feature matrix never made dense, and grad_input left out when the input needs no gradient.  A flat-marked adjacency
+(Csr.with_facts(flat=True)) of an unquantised layer takes that call's entry-split schedules (SGX_SCHEDULE_FLAT per matrix,
+the attention gradient by stored entries): no plan, no read-back, so the step records and replays on padded batches of
+any fan-out; with a quantiser the forward runs as without the fact, and so does the backward.
 """
 import torch
 import torch.nn.functional as F
@@ -158,9 +161,8 @@ class FPYNQ_GAT(torch.autograd.Function):
             # config.accb = 1: the backward as one call (sgx_layer_backward); its fp32 CSRs of X and X^T are built here,
             # once per feature tensor, so that the backward itself builds nothing
             ctx.accb, ctx.gemm_mode = int(config.accb), int(rm.gemm_mode)
-            if ctx.accb == 1 and A._flat:
-                raise ValueError("config.accb = 1 does not take a flat-marked adjacency (Csr.with_facts(flat=True)): "
-                                 "sgx_layer_backward has no entry-split schedule yet; use config.accb = 0")
+            # a flat-marked adjacency: the one-call backward runs entry-split exactly where this forward does (unquantised)
+            ctx.bwd_schedule = None if qc is None else "rows"
             if ctx.accb == 1 and ctx.gemm_mode == 0:
                 ctx.fea32 = ops.feature_csr32(input)
             my_ip.alpha = self.alpha
@@ -264,7 +266,8 @@ class FPYNQ_GAT(torch.autograd.Function):
                 kw.update(dead=ctx.dead, alpha=ctx.alpha)
             X = ctx.fea32 if ctx.gemm_mode == 0 else saved[0].float().contiguous()
             grad_input, grad_weights, ga = ops.layer_backward(A, X, saved[1].float().contiguous(), g.contiguous(), gat=bool(ctx.gat),
-                                                              gemm_mode=ctx.gemm_mode, want_grad_input=ctx.needs_input_grad[4], **kw)
+                                                              gemm_mode=ctx.gemm_mode, want_grad_input=ctx.needs_input_grad[4],
+                                                              schedule=ctx.bwd_schedule, **kw)
             if grad_input is not None and grad_input.stride(0) != grad_input.shape[1]:
                 grad_input = grad_input.contiguous()
             grad_attention = ga.unsqueeze(1) if ctx.gat else torch.zeros((2 * saved[1].shape[1], 1), device=g.device)

@@ -590,7 +590,9 @@ class NodeTrainer(_Trainer):
         recording is replayed; the short last batch runs through step() unpadded in its place.  An epoch thus takes
         exactly the steps of `for b in loader: step(b.x, b.edge_index_agg, b.y, n_prefix=b.batch_size)`, bit for bit.
         Covers GAT_PYNQ with config.compute_attention 0 and 1 (attention needs a transposed=True loader: the backward's
-        transposed pattern is then built on the device), config.gat_edge_outputs 1 and 0, fp32 and fp16, config.accb = 0;
+        transposed pattern is then built on the device), config.gat_edge_outputs 1 and 0, fp32 and fp16, config.accb = 0
+        -- and config.accb = 1 from a loader with schedule="flat" and transposed=True, whose adjacency, X and X^T the one-call
+        backward takes on its entry-split schedules (no plan, no read-back);
         and the quantised model -- config.fake_quantization with and without config.hardware_quantize, fp32 -- from a
         loader with quant= (NeighborLoader(pad=True, quant=qc): the padded batch carries the quantised adjacencies of both
         layers with their constant facts and lean mask values, sgx_node_batch_sample_padded_quant, so the quantised layers
@@ -658,7 +660,8 @@ class NodeTrainer(_Trainer):
         synchronises: EvalSums.read(pass(), ...) reads one or several passes back in one copy; the sums are the pass's
         own, overwritten by the next pass.  Parameters, moments and `t` are untouched and the model's mode is put back.
         The forward reads no transposed pattern, so transposed=True is not needed.  Covers what capture_loader covers: GCN
-        and attention, config.gat_edge_outputs 1 and 0, config.accb = 0, and the quantised model (config.fake_quantization
+        and attention, config.gat_edge_outputs 1 and 0, config.accb = 0 (and 1 from a schedule="flat" loader: the forward
+        does not read the flag), and the quantised model (config.fake_quantization
         with and without config.hardware_quantize) from a loader with quant=.  The last warm-up evaluation runs under
         torch.cuda.set_sync_debug_mode("error"): a configuration whose layer path synchronises raises capture()'s
         RuntimeError instead of being recorded.  A loader shared with capture_loader shares its buffers: a padded batch
