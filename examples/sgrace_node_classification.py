@@ -59,13 +59,16 @@ downloaded by torch_geometric and are not available offline.
              ONE transfer, the best epoch's weights are put back and both passes run once more on the samples of that
              epoch: restored_test_acc, which equals that epoch's logged test accuracy; the final train_acc is then the
              restored model's
---flat      with --trainer, --batch-size and --device-batches (unquantised): the padded loaders deliver their
+--flat      with --trainer, --batch-size and --device-batches: the padded loaders deliver their
              batches for the entry-split schedule (NeighborLoader(pad=True, schedule="flat")): every CSR of a batch is
              marked with_facts(flat=True), the layers aggregate by stored entries (SGX_SCHEDULE_FLAT) and build no plan, so
              fan-outs over 63 (--num-neighbors 100,10), feature rows over 64 entries and capacities past 2^20 entries
              pad -- and, with --replay, record -- like any other; with --accb every layer's backward is the one call on
              the same schedule (sgx_layer_grad_desc.schedule_adj / _fea / _xt), X and X^T delivered flat-marked by the
-             loader (transposed=True), and records and replays as well
+             loader (transposed=True), and records and replays as well; with --qbits (no --accb) the loaders take the
+             quantised layers' opt-in as well (NeighborLoader(..., quant=qc, flat_quant=True)): the quantised adjacencies
+             arrive at capacity, marked with_facts(flat=True, flat_quant=True), and the quantised model -- the demo's
+             default arithmetic -- pads and records at those fan-outs too
 """
 import argparse
 import os
@@ -134,6 +137,7 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
             ready["pad"] = True
         if flat:
             ready["schedule"] = "flat"
+            ready["flat_quant"] = sgrace.quant_constants is not None
         loader = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=train_mask,
                                          shuffle=True, seed=seed, **(ready if device_batches else {}))
     passes = None
@@ -148,7 +152,8 @@ def run(attention=False, qbits=32, epochs=60, acc=1, n=3000, hidden=16, seed=1, 
         for nodes in (val, test):
             ev = pyg_lite.NeighborLoader(data, num_neighbors or [10], batch_size=batch_size, input_nodes=nodes, shuffle=False,
                                          seed=seed, prepare="sym_norm2", quant=sgrace.quant_constants, pad=bool(replay or flat),
-                                         schedule="flat" if flat else None)
+                                         schedule="flat" if flat else None,
+                                         flat_quant=bool(flat and sgrace.quant_constants is not None))
             if replay and nodes.numel() >= batch_size:
                 passes.append((ev, node_trainer.capture_eval_loader(ev)))
             else:
@@ -298,8 +303,10 @@ if __name__ == "__main__":
         ap.error("--replay on mini-batches covers the layers with the staged backward, quantised or not (--accb only with --flat)")
     if a.keep_best and not (a.trainer and a.batch_size is not None and a.device_batches and not a.accb):
         ap.error("--keep-best needs --trainer with the per-epoch passes: --batch-size, --num-neighbors, --device-batches, no --accb")
-    if a.flat and not (a.trainer and a.batch_size is not None and a.device_batches and a.qbits == 32):
-        ap.error("--flat needs --trainer with --batch-size, --num-neighbors and --device-batches, unquantised")
+    if a.flat and not (a.trainer and a.batch_size is not None and a.device_batches):
+        ap.error("--flat needs --trainer with --batch-size, --num-neighbors and --device-batches")
+    if a.flat and a.qbits != 32 and a.accb:
+        ap.error("--flat with --qbits runs the staged backward: the one-call backward of a quantised layer keeps the row schedule")
     run(a.attention, a.qbits, a.epochs, a.acc, n=a.nodes, hidden=a.hidden, emulate=a.emulate, batch_size=a.batch_size,
         num_neighbors=a.num_neighbors, lean_gat=a.lean_gat, seed=a.seed, device_batches=a.device_batches,
         accb=int(a.accb), trainer=a.trainer, replay=a.replay, keep_best=a.keep_best, flat=a.flat)

@@ -136,6 +136,9 @@ int sgx_xw_sparse_form(int dtype, int n_rows, int M_fea, int P, const void *W, i
                                   K <= 128: at K = 128 the two forms tie, at Reddit's 602 the integer form takes half
                                   the time, X being read as bytes).  What `config.hardware_quantize = 1` selects in
                                   the SGRACE library's layers (SG.py:570-616: the bitstream's own quantiser).       */
+#define SGX_QUANT_FLAT 8       /* flags: the opt-in of the quantised layer to SGX_SCHEDULE_FLAT ("quantised layer on the
+                                  entry-split schedule" under sgx_layer_desc.schedule_adj).  Without it a descriptor
+                                  with `quant` and SGX_SCHEDULE_FLAT is refused as before; read nowhere else.        */
 typedef struct sgx_quant {
     int32_t qbits;              /* config.w_qbits: 8, 4, 2 or 1                                       */
     int32_t scale_fea;          /* register scale_fea                                                 */
@@ -289,7 +292,19 @@ typedef struct sgx_layer_desc {
      * acc_mode != SGX_ACC_F32, gat_heads > 1, E or S outputs, SGX_ORDER_AGGREGATE_FIRST; and for a schedule_adj that is
      * neither enumerator.  nnz_adj < 0 (or above INT32_MAX): SGX_ERR_SHAPE.
      * nnz_adj: the entries columnIndex_adj / values_adj hold -- a capacity, a bound on rowPtr_adj[N_adj], as `nnz` in the
-     * entry-split calls.  Read only under SGX_SCHEDULE_FLAT. */
+     * entry-split calls.  Read only under SGX_SCHEDULE_FLAT.
+     * Quantised layer on the entry-split schedule (added without a version bump: one new flag, two new declarations):
+     * `quant != NULL` is accepted under SGX_SCHEDULE_FLAT when, and only when, quant->flags carries SGX_QUANT_FLAT; without
+     * the bit the answer stays SGX_ERR_UNSUPPORTED.  The other refusals above hold with the bit set (plan_adj, gat_heads > 1,
+     * E / S, SGX_ORDER_AGGREGATE_FIRST; dtype and acc_mode as for every quantised layer).  The quantised copies of B, X, A
+     * (skipped under SGX_QUANT_ADJ_DONE; quant->nnz_adj entries, which may be the capacity) and the attention vector are
+     * made as under the default schedule, and stage 1 runs as there with its requantising epilogue (the dense fp32 form,
+     * the int8 form under SGX_QUANT_INT8[_AUTO], a CSR X by rows with plan_fea).  Stage 2 is sgx_spmm_csr_flat_ep /
+     * sgx_gat_aggregate_flat_ep with out_scale = quant->deq_factor on the quantised operands.  The workspace is the default
+     * schedule's quantised layout followed, on a 256-byte boundary, by the entry-split scratch at nnz_adj.
+     * THE RULE: D, and the statistics of sgx_layer_forward_stats, are bit-equal to those named stage calls composed on the
+     * same operands and capacity (sgx_fake_quantize / sgx_quantize_codes_i8, the X.W stage + sgx_requantize or
+     * sgx_xw_dense_i8, then the _ep call).  sgx_layer_schedule answers 2. */
     int32_t schedule_adj;
     int64_t nnz_adj;
 } sgx_layer_desc;
@@ -365,6 +380,25 @@ int    sgx_spmm_csr_flat(int dtype, int relu, int n_rows, int n_cols, int n_feat
                          const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
                          const void *H, int64_t ldh, void *D, int64_t ldd,
                          void *scratch, size_t scratch_bytes, void *stream);
+/* The same call with the quantised layer's store epilogue (added without a version bump: a new declaration;
+ * sgx_spmm_csr_flat is this call with the epilogue off, and the scratch is the same size).
+ *   out_scale         0 = off; otherwise every element of D is multiplied by it after the activation (deq_o, SG.py:666-667)
+ *   rq_internal_bits  0 = no requantisation (rq_scale_fea is then not read); otherwise the H-stage rule of the quantised
+ *                     layer, round_decimals(clip(x / 2^rq_scale_fea, +-(2^ib - 1) / 2^ib), ib - 1), before the activation.
+ *                     rq_scale_fea outside [0, 30], rq_internal_bits outside [1, 30], or a dtype other than SGX_F32 when
+ *                     requantising: SGX_ERR_UNSUPPORTED, before anything is launched.
+ * The partial rows of a crossing row stay raw fp32 sums; the epilogue acts exactly once per element of D, on the store of
+ * a finished row -- inside a chunk, after the cooperative walk, or in the second launch.
+ * THE RULE (dtype SGX_F32: every step is one IEEE operation, so it holds bit for bit): with out_scale = s, D equals
+ * sgx_spmm_csr_flat's D times s in fp32; with requantisation, D equals sgx_requantize applied to sgx_spmm_csr_flat's D
+ * (the rule is odd and maps 0 to 0, so it commutes with the ReLU); with both, the requantised D times s.
+ * dtype SGX_F16: the rule of the row kernels (sgx_epilogue in the library: "fp16 instantiations ignore it") -- out_scale
+ * is NOT applied, D equals sgx_spmm_csr_flat's bit for bit.  The quantised layer is fp32-only. */
+int    sgx_spmm_csr_flat_ep(int dtype, int relu, int n_rows, int n_cols, int n_feat, int64_t nnz,
+                            const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                            const void *H, int64_t ldh, void *D, int64_t ldd,
+                            void *scratch, size_t scratch_bytes, float out_scale, int rq_scale_fea, int rq_internal_bits,
+                            void *stream);
 
 /* X.W with dense X = loop_fea / compute1 in gemm_mode 1 (K.cpp:2932, :2605, :847-865),
  * on the matrix cores:  H[r][0:P] = sum_k X[r][k] * Wt[p][k].
@@ -614,6 +648,17 @@ int    sgx_gat_aggregate_flat(int dtype, int relu, int n_rows, int n_cols, int n
                               const void *Wh, int64_t ldh, const void *attention, void *D, int64_t ldd,
                               const float *fill, int64_t n_nodes, void *scratch, size_t scratch_bytes,
                               const sgx_gat_stats *stats, void *stream);
+/* The same call with the quantised layer's deq_o on its stores (added without a version bump: a new declaration;
+ * sgx_gat_aggregate_flat is this call with out_scale = 0, which means off, and the scratch is the same size).  The running
+ * softmax states in the slots stay raw fp32; out_scale multiplies every element of a finished row exactly once, after the
+ * normalisation -- or the dead row's value under each of the three dead-row rules -- and after the activation, as the row
+ * kernels of sgx_layer_forward apply it.  THE RULE (SGX_F32): D equals sgx_gat_aggregate_flat's D times out_scale in fp32,
+ * bit for bit, and the statistics are unchanged.  SGX_F16: out_scale is not applied (the row kernels' rule). */
+int    sgx_gat_aggregate_flat_ep(int dtype, int relu, int n_rows, int n_cols, int n_feat, int n_heads, float alpha, int64_t nnz,
+                                 const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                                 const void *Wh, int64_t ldh, const void *attention, void *D, int64_t ldd,
+                                 const float *fill, int64_t n_nodes, void *scratch, size_t scratch_bytes,
+                                 const sgx_gat_stats *stats, float out_scale, void *stream);
 
 /* Readout + classifier head of the graph-classification model (MOL cell 18 tail) in one launch:
  * pooled[g][:] = mean of X rows [graph_ptr[g], graph_ptr[g+1])  (global_mean_pool over a sorted

@@ -46,6 +46,18 @@ gat_flat_layout flat_layout(int64_t nnz, int n_cols, int n_feat, int mean_rule)
     return L;
 }
 
+// What a finished element of D becomes: gat_finish (ReLU) and then the quantised layer's deq_o on fp32 outputs, as the row
+// kernels' gat_finish applies it.  The kernels take the factor as `scale`, with 1 for "off" (the host maps out_scale = 0 to
+// it): x * 1 is x bit for bit, and the unconditional multiply keeps the test of the factor -- a uniform branch and the
+// scalar registers it pins -- out of the store path (with it the two widest fp32 instantiations spilled two SGPRs).
+template <typename T>
+__device__ __forceinline__ T flat_finish(float sum, int relu, float scale)
+{
+    T v = gat_finish<T>(sum, relu, 0.0f);
+    if constexpr (sizeof(T) == 4) v = v * scale;
+    return v;
+}
+
 struct gat_flat_ptrs {
     const int32_t *rowptr, *col;
     const float *s1, *s2, *fill;
@@ -100,7 +112,7 @@ __device__ __forceinline__ void flat_walk(float &m, float &l, float *acc, int e0
 template <typename T, int VEC, int LPR>
 __global__ __launch_bounds__(kBlock) void gat_flat_kernel(
     int n_rows, int n_feat, int nnz_cap, int n_chunks, gat_flat_ptrs q, const T *__restrict__ val, const T *__restrict__ Wh,
-    unsigned h_bytes, unsigned ld_bytes, unsigned s2_bytes, float alpha, T *__restrict__ D, int64_t ldd, int relu, int vec_store, int ldp)
+    unsigned h_bytes, unsigned ld_bytes, unsigned s2_bytes, float alpha, T *__restrict__ D, int64_t ldd, int relu, float scale, int vec_store, int ldp)
 {
     constexpr int RPW = 64 / LPR, TILE = LPR * VEC;
     const int c = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -123,7 +135,7 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(
 #pragma unroll
             for (int i = 0; i < VEC; ++i) {
                 const float v = dead ? ((q.fill && col0 + i < n_feat) ? q.fill[col0 + i] : 0.0f) : acc[i] * inv_l;
-                out[i] = gat_finish<T>(v, relu, 0.0f);
+                out[i] = flat_finish<T>(v, relu, scale);
             }
             T *drow = D + (int64_t)r * ldd;
             if (VEC > 1 && vec_store && col0 + VEC <= n_feat) {
@@ -194,7 +206,7 @@ __global__ __launch_bounds__(kBlock) void gat_flat_kernel(
 // then the head slots of the chunks behind it up to the last one the row reaches -- and stores it.
 template <typename T>
 __global__ __launch_bounds__(kBlock) void gat_flat_finish_kernel(
-    int n_rows, int n_feat, int nnz_cap, int n_chunks, gat_flat_ptrs q, int ldp, T *__restrict__ D, int64_t ldd, int relu)
+    int n_rows, int n_feat, int nnz_cap, int n_chunks, gat_flat_ptrs q, int ldp, T *__restrict__ D, int64_t ldd, int relu, float scale)
 {
     const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (gid >= (int64_t)n_chunks * n_feat) return;
@@ -218,13 +230,13 @@ __global__ __launch_bounds__(kBlock) void gat_flat_finish_kernel(
     }
     const bool dead = !(l > 0.0f);
     const float out = dead ? (q.fill ? q.fill[j] : 0.0f) : a / l;
-    D[(int64_t)r * ldd + j] = gat_finish<T>(out, relu, 0.0f);
+    D[(int64_t)r * ldd + j] = flat_finish<T>(out, relu, scale);
     if (j == 0 && q.row_max) { q.row_max[r] = dead ? 0.0f : M; q.row_sum[r] = dead ? 0.0f : l; }
 }
 
 struct GatFlatArgs {
     int relu, n_rows, n_cols, n_feat, nnz, n_chunks, vec_store, ldp;
-    float alpha;
+    float alpha, scale;           // scale: deq_o of the quantised layer on the store of a finished row (fp32; 1 = off, see flat_finish)
     gat_flat_ptrs q;
     const void *val, *Wh;
     unsigned h_bytes, ld_bytes;
@@ -239,11 +251,11 @@ int gat_flat_launch(const GatFlatArgs &a)
     constexpr int kWaves = kBlock / 64;
     hipLaunchKernelGGL((gat_flat_kernel<T, VEC, LPR>), dim3((unsigned)((a.n_chunks + kWaves - 1) / kWaves)), dim3(kBlock), 0, a.stream,
                        a.n_rows, a.n_feat, a.nnz, a.n_chunks, a.q, (const T *)a.val, (const T *)a.Wh, a.h_bytes, a.ld_bytes,
-                       (unsigned)((size_t)a.n_cols * 4), a.alpha, (T *)a.D, a.ldd, a.relu, a.vec_store, a.ldp);
+                       (unsigned)((size_t)a.n_cols * 4), a.alpha, (T *)a.D, a.ldd, a.relu, a.scale, a.vec_store, a.ldp);
     SGX_LAUNCH_CHECK();
     const int64_t total = (int64_t)a.n_chunks * a.n_feat;
     hipLaunchKernelGGL((gat_flat_finish_kernel<T>), dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, a.stream,
-                       a.n_rows, a.n_feat, a.nnz, a.n_chunks, a.q, a.ldp, (T *)a.D, a.ldd, a.relu);
+                       a.n_rows, a.n_feat, a.nnz, a.n_chunks, a.q, a.ldp, (T *)a.D, a.ldd, a.relu, a.scale);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }
@@ -261,6 +273,18 @@ extern "C" int sgx_gat_aggregate_flat(int dtype, int relu, int n_rows, int n_col
                                       const void *Wh, int64_t ldh, const void *attention, void *D, int64_t ldd,
                                       const float *fill, int64_t n_nodes, void *scratch, size_t scratch_bytes,
                                       const sgx_gat_stats *stats, void *stream)
+{
+    return sgx_gat_aggregate_flat_ep(dtype, relu, n_rows, n_cols, n_feat, n_heads, alpha, nnz, rowPtr, columnIndex, values, Wh, ldh,
+                                     attention, D, ldd, fill, n_nodes, scratch, scratch_bytes, stats, /*out_scale*/0.0f, stream);
+}
+
+// With the quantised layer's deq_o on the store of a finished row (flat_finish: where the row kernels' gat_finish applies
+// it, after the normalisation or the dead row's fill, after ReLU); the states in the slots and the statistics never see it.
+extern "C" int sgx_gat_aggregate_flat_ep(int dtype, int relu, int n_rows, int n_cols, int n_feat, int n_heads, float alpha, int64_t nnz,
+                                         const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                                         const void *Wh, int64_t ldh, const void *attention, void *D, int64_t ldd,
+                                         const float *fill, int64_t n_nodes, void *scratch, size_t scratch_bytes,
+                                         const sgx_gat_stats *stats, float out_scale, void *stream)
 {
     if (n_heads < 1) n_heads = 1;
     int mean_rule = 0;
@@ -317,7 +341,7 @@ extern "C" int sgx_gat_aggregate_flat(int dtype, int relu, int n_rows, int n_col
 
     GatFlatArgs a;
     a.relu = relu; a.n_rows = n_rows; a.n_cols = n_cols; a.n_feat = n_feat; a.nnz = (int)nnz; a.n_chunks = (int)flat_chunks(nnz);
-    a.vec_store = g.vec_store; a.ldp = L.ldp; a.alpha = alpha;
+    a.vec_store = g.vec_store; a.ldp = L.ldp; a.alpha = alpha; a.scale = out_scale != 0.0f ? out_scale : 1.0f;
     a.q.rowptr = rowPtr; a.q.col = columnIndex; a.q.s1 = (const float *)(base + L.s1); a.q.s2 = (const float *)(base + L.s2);
     a.q.fill = fill_row; a.q.pacc = (float *)(base + L.acc); a.q.pml = (float *)(base + L.ml); a.q.meta = (int32_t *)(base + L.meta);
     a.q.row_max = stats ? stats->row_max : nullptr; a.q.row_sum = stats ? stats->row_sum : nullptr;

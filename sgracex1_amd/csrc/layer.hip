@@ -134,8 +134,9 @@ int check_desc(const sgx_layer_desc *d)
     if (flat_schedule(d)) {
         // what the entry-split calls do not have: a plan to follow, the quantised epilogue, the reference-half sums, heads,
         // per-edge outputs; and the aggregate-first order gathers X, not H
-        if (d->plan_adj || d->quant || d->acc_mode != SGX_ACC_F32 || d->gat_heads > 1 || d->E || d->S ||
-            d->order == SGX_ORDER_AGGREGATE_FIRST)
+        // (the quantised epilogue only by its own opt-in, SGX_QUANT_FLAT: the refusal without it is pinned by callers)
+        if (d->plan_adj || (d->quant && !(d->quant->flags & SGX_QUANT_FLAT)) || d->acc_mode != SGX_ACC_F32 || d->gat_heads > 1 ||
+            d->E || d->S || d->order == SGX_ORDER_AGGREGATE_FIRST)
             return SGX_ERR_UNSUPPORTED;
         if (d->nnz_adj < 0 || d->nnz_adj > 0x7FFFFFFF) return SGX_ERR_SHAPE;
     }
@@ -321,13 +322,15 @@ int layer_forward(const sgx_layer_desc *d, const sgx_gat_stats *stats, void *str
     if (flat_schedule(d)) {
         // the public entry-split calls are the launch code (argument checks, scratch layout, dispatch): the layer hands them
         // its H and its slice of the workspace, so D -- and the statistics -- are theirs bit for bit
+        // (quantised, under SGX_QUANT_FLAT: on the quantised copies, deq_o on the stores of the finished rows)
         if (d->gat_mode)
-            rc = sgx_gat_aggregate_flat(d->dtype, d->relu, d->N_adj, d->M_adj, d->P_w, 1, d->alpha, d->nnz_adj, d->rowPtr_adj,
-                                        d->columnIndex_adj, values_adj, H, ldh, attention, d->D, d->P_w, /*fill*/nullptr,
-                                        d->gat_fill_dead_rows ? (int64_t)d->M_adj : 0, ws + c.f_off, c.f_bytes, stats, s);
+            rc = sgx_gat_aggregate_flat_ep(d->dtype, d->relu, d->N_adj, d->M_adj, d->P_w, 1, d->alpha, d->nnz_adj, d->rowPtr_adj,
+                                           d->columnIndex_adj, values_adj, H, ldh, attention, d->D, d->P_w, /*fill*/nullptr,
+                                           d->gat_fill_dead_rows ? (int64_t)d->M_adj : 0, ws + c.f_off, c.f_bytes, stats,
+                                           ep_d.out_scale, s);
         else
-            rc = sgx_spmm_csr_flat(d->dtype, d->relu, d->N_adj, d->M_adj, d->P_w, d->nnz_adj, d->rowPtr_adj, d->columnIndex_adj,
-                                   values_adj, H, ldh, d->D, d->P_w, ws + c.f_off, c.f_bytes, s);
+            rc = sgx_spmm_csr_flat_ep(d->dtype, d->relu, d->N_adj, d->M_adj, d->P_w, d->nnz_adj, d->rowPtr_adj, d->columnIndex_adj,
+                                      values_adj, H, ldh, d->D, d->P_w, ws + c.f_off, c.f_bytes, ep_d.out_scale, 0, 0, s);
     } else if (d->gat_mode) {
         if (!attention) return SGX_ERR_NULL;
         rc = sgx_gat_aggregate_ep(d->dtype, d->relu, d->gat_fill_dead_rows, d->N_adj, d->M_adj, d->P_w, d->gat_heads, d->alpha,

@@ -33,7 +33,7 @@ template <typename T, int VEC, int LPR>
 __global__ __launch_bounds__(kBlock) void spmm_flat_kernel(
     int n_rows, int n_feat, int nnz_cap, int n_chunks, const int32_t *__restrict__ rowptr, const int32_t *__restrict__ col,
     const T *__restrict__ val, const T *__restrict__ H, unsigned h_bytes, unsigned ld_bytes, T *__restrict__ D, int64_t ldd,
-    int relu, float *__restrict__ partial, int ldp, int32_t *__restrict__ meta)
+    int relu, sgx_epilogue ep, float *__restrict__ partial, int ldp, int32_t *__restrict__ meta)
 {
     constexpr int RPW = 64 / LPR, TILE = LPR * VEC;
     const int c = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
@@ -65,9 +65,9 @@ __global__ __launch_bounds__(kBlock) void spmm_flat_kernel(
     }
 
     const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<T *>(H), 0, h_bytes, 0x00020000);
-    const sgx_epilogue ep = sgx_epilogue{0.0f, 0.0f, 0.0f, 0.0f};
     float *head_slot = partial + 2 * (int64_t)c * ldp;
-    // a lane's VEC sums of one piece go to the row of D, or to the chunk's head / tail partial row
+    // a lane's VEC sums of one piece go to the row of D -- through the epilogue, the one place this launch applies it -- or,
+    // raw, to the chunk's head / tail partial row
     auto emit = [&](int kind, int r, int col0, const float *acc) SGX_LAMBDA_INLINE {
         if (kind == FLAT_ROW) {
             if (col0 < n_feat) store_row<T, VEC>(D + (int64_t)r * ldd, col0, n_feat, acc, relu, ep);
@@ -139,7 +139,7 @@ __global__ __launch_bounds__(kBlock) void spmm_flat_kernel(
 template <typename T>
 __global__ __launch_bounds__(kBlock) void spmm_flat_finish_kernel(
     int n_rows, int n_feat, int nnz_cap, int n_chunks, const int32_t *__restrict__ rowptr, const float *__restrict__ partial, int ldp,
-    const int32_t *__restrict__ meta, T *__restrict__ D, int64_t ldd, int relu)
+    const int32_t *__restrict__ meta, T *__restrict__ D, int64_t ldd, int relu, sgx_epilogue ep)
 {
     const int64_t gid = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (gid >= (int64_t)n_chunks * n_feat) return;
@@ -151,7 +151,7 @@ __global__ __launch_bounds__(kBlock) void spmm_flat_finish_kernel(
     if (r < 0 || r >= n_rows) return;
     const int c_last = meta[2 * (int64_t)c + 1];
     const float s = sum_task_partials(partial, 2 * ldp, j, c + 1, c_last + 1, partial[(2 * (int64_t)c + 1) * ldp + j]);
-    D[(int64_t)r * ldd + j] = finish_value<T>(s, relu, sgx_epilogue{0.0f, 0.0f, 0.0f, 0.0f});
+    D[(int64_t)r * ldd + j] = finish_value<T>(s, relu, ep);       // the merged row's one pass through the epilogue
 }
 
 struct FlatArgs {
@@ -164,6 +164,7 @@ struct FlatArgs {
     float *partial;
     int ldp;
     int32_t *meta;
+    sgx_epilogue ep;              // on the store of a finished row (fp32 outputs; all zero = off)
     hipStream_t stream;
 };
 
@@ -173,11 +174,11 @@ int flat_launch(const FlatArgs &a)
     constexpr int kWaves = kBlock / 64;
     hipLaunchKernelGGL((spmm_flat_kernel<T, VEC, LPR>), dim3((unsigned)((a.n_chunks + kWaves - 1) / kWaves)), dim3(kBlock), 0, a.stream,
                        a.n_rows, a.n_feat, a.nnz, a.n_chunks, a.rowptr, a.col, (const T *)a.val, (const T *)a.H, a.h_bytes, a.ld_bytes,
-                       (T *)a.D, a.ldd, a.relu, a.partial, a.ldp, a.meta);
+                       (T *)a.D, a.ldd, a.relu, a.ep, a.partial, a.ldp, a.meta);
     SGX_LAUNCH_CHECK();
     const int64_t total = (int64_t)a.n_chunks * a.n_feat;
     hipLaunchKernelGGL((spmm_flat_finish_kernel<T>), dim3((unsigned)((total + kBlock - 1) / kBlock)), dim3(kBlock), 0, a.stream,
-                       a.n_rows, a.n_feat, a.nnz, a.n_chunks, a.rowptr, a.partial, a.ldp, a.meta, (T *)a.D, a.ldd, a.relu);
+                       a.n_rows, a.n_feat, a.nnz, a.n_chunks, a.rowptr, a.partial, a.ldp, a.meta, (T *)a.D, a.ldd, a.relu, a.ep);
     SGX_LAUNCH_CHECK();
     return SGX_OK;
 }
@@ -198,8 +199,28 @@ extern "C" int sgx_spmm_csr_flat(int dtype, int relu, int n_rows, int n_cols, in
                                  const void *H, int64_t ldh, void *D, int64_t ldd,
                                  void *scratch, size_t scratch_bytes, void *stream)
 {
+    return sgx_spmm_csr_flat_ep(dtype, relu, n_rows, n_cols, n_feat, nnz, rowPtr, columnIndex, values, H, ldh, D, ldd, scratch,
+                                scratch_bytes, /*out_scale*/0.0f, /*rq_scale_fea*/0, /*rq_internal_bits*/0, stream);
+}
+
+// The quantised layer's store epilogue on the entry-split schedule: the partial rows stay raw fp32 sums, and a finished row
+// passes finish_value once -- in the chunk that holds it whole, in the cooperative walk, or in the second launch.
+extern "C" int sgx_spmm_csr_flat_ep(int dtype, int relu, int n_rows, int n_cols, int n_feat, int64_t nnz,
+                                    const int32_t *rowPtr, const int32_t *columnIndex, const void *values,
+                                    const void *H, int64_t ldh, void *D, int64_t ldd,
+                                    void *scratch, size_t scratch_bytes, float out_scale, int rq_scale_fea, int rq_internal_bits,
+                                    void *stream)
+{
     if (n_rows < 0 || n_cols < 0 || n_feat < 1 || ldh < n_feat || ldd < n_feat || nnz < 0 || nnz > kFlatMaxNnz) return SGX_ERR_SHAPE;
     if (dtype != SGX_F16 && dtype != SGX_F32) return SGX_ERR_UNSUPPORTED;
+    sgx_epilogue ep = sgx_no_epilogue();
+    if (rq_internal_bits != 0) {
+        // the H-stage rule, with the layer's ranges (check_desc); fp32 only, as every requantising stage
+        if (rq_scale_fea < 0 || rq_scale_fea > 30 || rq_internal_bits < 1 || rq_internal_bits > 30 || dtype != SGX_F32)
+            return SGX_ERR_UNSUPPORTED;
+        ep = sgx_requant_epilogue(rq_scale_fea, rq_internal_bits);
+    }
+    ep.out_scale = out_scale;
     if (n_rows == 0) return SGX_OK;
     if (!rowPtr || !D) return SGX_ERR_NULL;
     if (nnz > 0 && (!columnIndex || !values)) return SGX_ERR_NULL;
@@ -216,7 +237,7 @@ extern "C" int sgx_spmm_csr_flat(int dtype, int relu, int n_rows, int n_cols, in
     a.relu = relu; a.n_rows = n_rows; a.n_feat = n_feat; a.nnz = (int)nnz; a.n_chunks = (int)flat_chunks(nnz);
     a.rowptr = rowPtr; a.col = columnIndex; a.val = values; a.H = H;
     a.h_bytes = (unsigned)((unsigned long long)n_cols * (unsigned long long)ldh * es); a.ld_bytes = (unsigned)(ldh * es);
-    a.D = D; a.ldd = ldd; a.stream = (hipStream_t)stream;
+    a.D = D; a.ldd = ldd; a.ep = ep; a.stream = (hipStream_t)stream;
     a.partial = (float *)scratch;
     a.ldp = flat_ldp(n_feat);
     a.meta = (int32_t *)((char *)scratch + flat_partial_bytes(a.n_chunks, n_feat));

@@ -212,6 +212,7 @@ class Csr:
         self._dead_rows_version = self._dead_row_mask_version = None      # the values' version a computed answer holds for
         self._max_row = None                   # the longest row, or a bound on it, where the builder knows it
         self._flat = False                     # aggregates by the entry-split form (with_facts(flat=True)): never wants a plan
+        self._flat_quant = False               # ... under a quantiser too (with_facts(flat_quant=True)); read only with _flat
         self._quantized = {}
 
     @property
@@ -242,7 +243,7 @@ class Csr:
         key = _adj_quant_key(qc)
         if key not in self._quantized:
             self._quantized[key] = Csr(self.rowptr, self.col, fake_quantize(self.val, 0, qc.w_qbits, qc.a_s, qc.a_z),
-                                       self.n_cols, self._plan).with_facts(flat=self._flat)
+                                       self.n_cols, self._plan).with_facts(flat=self._flat, flat_quant=self._flat_quant)
         return self._quantized[key]
 
     @property
@@ -282,13 +283,17 @@ class Csr:
             return False
         return self.nnz >= 8192
 
-    def with_facts(self, dead_row_mask=None, has_dead_rows=None, max_row=None, flat=None):
+    def with_facts(self, dead_row_mask=None, has_dead_rows=None, max_row=None, flat=None, flat_quant=None):
         """Records what the builder of this matrix already knows, so that nothing is computed or read back for it:
         dead_rows (bool [n_rows]), has_dead_rows, and the longest row (or a bound on it; see wants_plan).
         flat=True: this matrix aggregates by the entry-split form -- ops.spmm takes sgx_spmm_csr_flat for it without
-        being asked, and it wants no plan (unless one exists already), whatever its rows are like."""
+        being asked, and it wants no plan (unless one exists already), whatever its rows are like.
+        flat_quant=True: a flat-marked matrix keeps the entry-split route under a quantiser (layer_forward(quant=),
+        FPYNQ_GAT with quantisation on); without this fact a flat-marked matrix runs by rows there, as it always did."""
         if flat is not None:
             self._flat = bool(flat)
+        if flat_quant is not None:
+            self._flat_quant = bool(flat_quant)
         if dead_row_mask is not None:
             self._dead_row_mask, self._dead_row_mask_version = dead_row_mask, None
         if has_dead_rows is not None:
@@ -303,7 +308,8 @@ class Csr:
         if self.val.dtype == dtype:
             return self
         return Csr(self.rowptr, self.col, self.val.to(dtype), self.n_cols,
-                   self.plan if self.wants_plan else None).with_facts(max_row=self._max_row, flat=self._flat)
+                   self.plan if self.wants_plan else None).with_facts(max_row=self._max_row, flat=self._flat,
+                                                                     flat_quant=self._flat_quant)
 
     def validate(self):
         check(lib.sgx_csr_validate(_ptr(self.rowptr), _ptr(self.col), self.n_rows, self.n_cols, self.nnz, _stream()),
@@ -365,14 +371,22 @@ def _gatherable_copies(H, n_feat, nnz):
     return H.shape[0] * n_feat >= (1 << 16)
 
 
-def spmm(adj, H, relu=False, n_feat=None, out=None, use_plan=True, acc_mode=SGX_ACC_F32, spmm_block=1, schedule=None):
+def spmm(adj, H, relu=False, n_feat=None, out=None, use_plan=True, acc_mode=SGX_ACC_F32, spmm_block=1, schedule=None,
+         out_scale=None, requant=None):
     """D = act(A @ H[:, :n_feat]) -- the aggregation stage alone (sgx_spmm_csr).
     schedule="flat", or a matrix that carries the fact (Csr.with_facts(flat=True)): the entry-split form
     (sgx_spmm_csr_flat) -- no plan, no read-back, the grid a function of the entries adj.col holds (a capacity: the
-    matrix's own end is read from rowptr on the device), so the call records into a graph and replays."""
+    matrix's own end is read from rowptr on the device), so the call records into a graph and replays.
+    out_scale, requant=(scale_fea, internal_bits) (entry-split form only): the quantised layer's store epilogue
+    (sgx_spmm_csr_flat_ep) -- float32: D times out_scale, and requantize_ of D, bit for bit; float16 ignores out_scale as
+    the row kernels do, and requant raises."""
     if schedule not in (None, "flat"):
         raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
     flat = schedule == "flat" or adj._flat
+    if (out_scale is not None or requant is not None) and not flat:
+        raise ValueError("out_scale / requant are the entry-split form's epilogue: pass schedule='flat'")
+    if requant is not None and H.dtype != torch.float32:
+        raise TypeError("requant works on float32 (SG.py:1545)")
     if flat and acc_mode != SGX_ACC_F32:
         raise ValueError("the entry-split aggregation is SGX_ACC_F32 arithmetic only")
     _dev2d(H, "H")
@@ -388,9 +402,18 @@ def spmm(adj, H, relu=False, n_feat=None, out=None, use_plan=True, acc_mode=SGX_
     if flat:
         sbytes = lib.sgx_spmm_flat_scratch_bytes(adj.nnz, n_feat)
         scratch = _workspace(H.device, sbytes)
-        check(lib.sgx_spmm_csr_flat(code, int(bool(relu)), adj.n_rows, H.shape[0], n_feat, adj.nnz, _ptr(adj.rowptr), _ptr(adj.col),
-                                    _ptr(adj.val), _ptr(H), H.stride(0), _ptr(out), out.stride(0), _ptr(scratch), sbytes, _stream()),
-              "sgx_spmm_csr_flat")
+        if out_scale is None and requant is None:
+            check(lib.sgx_spmm_csr_flat(code, int(bool(relu)), adj.n_rows, H.shape[0], n_feat, adj.nnz, _ptr(adj.rowptr),
+                                        _ptr(adj.col), _ptr(adj.val), _ptr(H), H.stride(0), _ptr(out), out.stride(0), _ptr(scratch),
+                                        sbytes, _stream()), "sgx_spmm_csr_flat")
+            return out
+        scale_fea, internal_bits = (0, 0) if requant is None else (int(requant[0]), int(requant[1]))
+        if requant is not None and internal_bits < 1:
+            raise ValueError("requant=(scale_fea, internal_bits) needs internal_bits >= 1")
+        check(lib.sgx_spmm_csr_flat_ep(code, int(bool(relu)), adj.n_rows, H.shape[0], n_feat, adj.nnz, _ptr(adj.rowptr),
+                                       _ptr(adj.col), _ptr(adj.val), _ptr(H), H.stride(0), _ptr(out), out.stride(0), _ptr(scratch),
+                                       sbytes, float(out_scale or 0.0), scale_fea, internal_bits, _stream()),
+              "sgx_spmm_csr_flat_ep")
         return out
     plan = adj.plan if (use_plan and adj.wants_plan) else None
     sbytes = lib.sgx_spmm_scratch_bytes(plan.handle, n_feat) if plan is not None else 0
@@ -580,7 +603,7 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
                   acc_mode=SGX_ACC_F32, spmm_block=1, bias_count=0, out=None, use_plan=True, agg_events=None,
                   quant=None, adj_quantized=False, cache_quantized_adj=True, fea_threads=1, adj_threads=1,
                   gat_heads=1, order="reference", want_row_stats=False, schedule=None, fill_dead_rows=None,
-                  _schedule_query=False):
+                  quant_flat=False, _schedule_query=False):
     """One fused layer  D = act(A . (X . W))  through sgx_layer_forward.
 
     adj : Csr [N, M_adj];  fea : Csr [M_adj, M_fea] (gemm_mode 0) or dense tensor (gemm_mode 1);
@@ -610,12 +633,17 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
     gat_heads > 1, SGX_ACC_REF_HALF, want_edge_outputs or order="aggregate_first" raises; a flat-marked adjacency with one of
     them runs as without the fact.  A flat-marked feature CSR on that route has its X.W stage run as spmm(fea, W,
     schedule="flat") -- a CSR X.W is an aggregation over W -- and the layer is then the two stage calls, composed here.
+    quant_flat=True: the quantised layer's own opt-in to that schedule (SGX_QUANT_FLAT): schedule="flat" with quant= is then
+    taken instead of refused -- stage 1 as under the default schedule, stage 2 the entry-split aggregate with deq_o on its
+    stores; D equals the stage calls composed (include/sgx.h).  An adjacency marked with_facts(flat=True, flat_quant=True)
+    opts in by itself; one marked flat alone still runs a quantised layer by rows.  The other refusals stay.
     fill_dead_rows (GAT): None = decide from the adjacency (adj.has_dead_rows: a read-back unless the fact is known), or the
     rule itself, as gat_aggregate takes it.
     """
     if schedule not in (None, "flat"):
         raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
-    refused = [name for name, hit in (("quant", quant is not None), ("gat_heads > 1", int(gat_heads) > 1),
+    quant_ok = bool(quant_flat) or (schedule is None and adj._flat and adj._flat_quant)
+    refused = [name for name, hit in (("quant", quant is not None and not quant_ok), ("gat_heads > 1", int(gat_heads) > 1),
                                       ("SGX_ACC_REF_HALF", acc_mode != SGX_ACC_F32), ("want_edge_outputs", want_edge_outputs),
                                       ("order='aggregate_first'", order == "aggregate_first")) if hit]
     if schedule == "flat" and refused:
@@ -625,7 +653,7 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
         if _schedule_query:
             return 2
         return _layer_forward_flat_stages(adj, fea, Wt, relu, gat_attention, alpha, bias_count, out, agg_events, want_row_stats,
-                                          fill_dead_rows)
+                                          fill_dead_rows, quant, adj_quantized)
     _dev(Wt, "Wt")
     code = dtype_code(Wt.dtype)
     P, M_fea = Wt.shape
@@ -697,6 +725,8 @@ def layer_forward(adj, fea, Wt, relu=False, gat_attention=None, alpha=0.2, want_
             qs.flags |= _lib.SGX_QUANT_INT8_AUTO
         elif quant_int8:
             qs.flags |= _lib.SGX_QUANT_INT8
+        if flat:
+            qs.flags |= _lib.SGX_QUANT_FLAT
         d.quant = ctypes.pointer(qs)
     if _schedule_query:
         route = lib.sgx_layer_schedule(ctypes.byref(d))
@@ -723,13 +753,17 @@ def layer_schedule(adj, fea, Wt, **kwargs):
 
 
 def _layer_forward_flat_stages(adj, fea, Wt, relu, gat_attention, alpha, bias_count, out, agg_events, want_row_stats,
-                               fill_dead_rows):
+                               fill_dead_rows, quant=None, adj_quantized=False):
     """layer_forward on the entry-split schedule for a flat-marked feature CSR: sgx_layer_forward has one X.W stage for a
     CSR X (sgx_xw_sparse) and no way to take an H formed elsewhere, so the layer is its two stage calls -- H = spmm(fea,
     W, schedule="flat") into rows of table_pitch() elements, then the entry-split aggregate of H -- and D is theirs bit for
-    bit."""
+    bit.  quant: the same composition on the quantised operands -- W and the attention vector on the
+    signed grid, the stored values of X and A on the unsigned one (A once per matrix, Csr.quantized), the requantisation on
+    the stores of the X.W stage and deq_o on the aggregate's."""
     _dev(Wt, "Wt")
     P, M_fea = Wt.shape
+    if quant is not None and Wt.dtype != torch.float32:
+        raise TypeError("the quantised layer works on float32 buffers (SG.py:1545)")
     if adj.val.dtype != Wt.dtype:
         raise TypeError("adjacency, features and weights must share one element type (MM.h:129-139)")
     if fea.val.dtype != Wt.dtype or fea.n_rows != adj.n_cols or fea.n_cols != M_fea:
@@ -742,16 +776,28 @@ def _layer_forward_flat_stages(adj, fea, Wt, relu, gat_attention, alpha, bias_co
     if bias_count > 0:                      # K.cpp:3876-3889: the reference preloads and returns without computing
         return (out, GatStats(adj.n_rows, adj.n_cols, 1, Wt.device)) if want_row_stats else out
     ldh = table_pitch(P, Wt.element_size())
+    requant = deq_o = None
+    if quant is not None:
+        if quant.a_z != 0 or quant.f_z != 0:       # (sgx_layer_forward's rule: entries that are not stored must stay zero)
+            raise ValueError("the quantised layer needs zero points a_z = f_z = 0 for its CSR operands")
+        Wt = fake_quantize(Wt.contiguous(), 1, quant.w_qbits, quant.w_s, quant.w_z)
+        fea = Csr(fea.rowptr, fea.col, fake_quantize(fea.val, 0, quant.w_qbits, quant.f_s, quant.f_z), fea.n_cols)
+        if not adj_quantized:
+            adj = adj.quantized(quant)
+        if gat_attention is not None:
+            gat_attention = fake_quantize(_dev(gat_attention, "attention").reshape(-1).contiguous(), 1, quant.w_qbits, quant.w_s,
+                                          quant.w_z)
+        requant, deq_o = (quant.scale_fea, quant.internal_quantization), quant.deq_o
     W = transpose(Wt, ldo=ldh)                                              # B [P][M] -> W [M][ldh]
     H = torch.zeros((adj.n_cols, ldh), dtype=Wt.dtype, device=Wt.device)
-    spmm(fea, W, n_feat=P, out=H[:, :P], schedule="flat")
+    spmm(fea, W, n_feat=P, out=H[:, :P], schedule="flat", requant=requant)
     if agg_events is not None:
         check(lib.sgx_event_record(agg_events[0], _stream()), "sgx_event_record")
     if gat_attention is None:
-        res = spmm(adj, H, relu=relu, n_feat=P, out=out, schedule="flat")
+        res = spmm(adj, H, relu=relu, n_feat=P, out=out, schedule="flat", out_scale=deq_o)
     else:
         res = gat_aggregate(adj, H[:, :P], gat_attention, alpha=alpha, relu=relu, fill_dead_rows=fill_dead_rows, out=out,
-                            want_row_stats=want_row_stats, schedule="flat")
+                            want_row_stats=want_row_stats, schedule="flat", out_scale=deq_o)
     if agg_events is not None:
         check(lib.sgx_event_record(agg_events[1], _stream()), "sgx_event_record")
     return res
@@ -811,7 +857,7 @@ def _check_fill_row(fill_row, F, n_nodes):
 
 
 def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=False, fill_dead_rows=None, out=None,
-                  heads=1, use_plan=True, fill_row=None, n_nodes=None, want_row_stats=False, schedule=None):
+                  heads=1, use_plan=True, fill_row=None, n_nodes=None, want_row_stats=False, schedule=None, out_scale=None):
     """Edge-softmax aggregate over an already computed Wh [adj.n_cols, F]; row r of adj is node r of Wh.
     heads > 1: F/heads columns per head, attention = heads vectors of 2*F/heads (E, S become [nnz, heads]).
     fill_dead_rows: None = decide from the adjacency (rows without a positive entry get the mean of
@@ -823,13 +869,17 @@ def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=F
     schedule="flat", or a matrix that carries the fact (Csr.with_facts(flat=True)): the entry-split form
     (sgx_gat_aggregate_flat) -- one head, no edge outputs, no plan, no read-back, the grid a function of the entries
     adj.col holds (a capacity), so the call records into a graph and replays; a caller that replays passes fill_dead_rows
-    itself.  The keyword with heads > 1 or want_edge_outputs raises; a flat-marked matrix with them runs as without the fact."""
+    itself.  The keyword with heads > 1 or want_edge_outputs raises; a flat-marked matrix with them runs as without the fact.
+    out_scale (entry-split form only): the quantised layer's deq_o on the stores (sgx_gat_aggregate_flat_ep) -- float32: D
+    times out_scale bit for bit, the statistics unchanged; float16 ignores it as the row kernels do."""
     if schedule not in (None, "flat"):
         raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
     heads = int(heads)
     if schedule == "flat" and (heads != 1 or want_edge_outputs):
         raise ValueError("the entry-split GAT aggregate has one head and no edge outputs (want_row_stats gives the statistics)")
     flat = schedule == "flat" or (adj._flat and heads == 1 and not want_edge_outputs)
+    if out_scale is not None and not flat:
+        raise ValueError("out_scale is the entry-split form's epilogue: pass schedule='flat'")
     _dev2d(Wh, "Wh")
     code = dtype_code(Wh.dtype)
     N, F = Wh.shape
@@ -847,7 +897,7 @@ def gat_aggregate(adj, Wh, attention, alpha=0.2, relu=False, want_edge_outputs=F
         E = torch.empty(es_shape, dtype=torch.float32, device=Wh.device)
         S = torch.empty(es_shape, dtype=torch.float32, device=Wh.device)
     if flat:
-        return _gat_aggregate_flat(adj, Wh, att, alpha, relu, fill_dead_rows, out, fill_row, n_nodes, want_row_stats)
+        return _gat_aggregate_flat(adj, Wh, att, alpha, relu, fill_dead_rows, out, fill_row, n_nodes, want_row_stats, out_scale)
     plan = adj.gat_plan.handle if (use_plan and adj.wants_plan) else None
     if want_row_stats:
         return _gat_aggregate_stats(adj, Wh, att, alpha, relu, want_edge_outputs, fill_dead_rows, out, heads, plan, fill_row,
@@ -890,7 +940,7 @@ def _gat_aggregate_stats(adj, Wh, att, alpha, relu, want_edge_outputs, fill_dead
     return out, stats
 
 
-def _gat_aggregate_flat(adj, Wh, att, alpha, relu, fill_dead_rows, out, fill_row, n_nodes, want_row_stats):
+def _gat_aggregate_flat(adj, Wh, att, alpha, relu, fill_dead_rows, out, fill_row, n_nodes, want_row_stats, out_scale=None):
     """gat_aggregate on its checked arguments through sgx_gat_aggregate_flat: the dead-row rule as _gat_aggregate_stats maps
     it, the scratch from the grow-only workspace, nnz = the entries adj.col holds."""
     N, F = Wh.shape
@@ -905,10 +955,13 @@ def _gat_aggregate_flat(adj, Wh, att, alpha, relu, fill_dead_rows, out, fill_row
     scratch = _workspace(Wh.device, sbytes)
     stats = GatStats(adj.n_rows, N, 1, Wh.device) if want_row_stats else None
     st = stats.struct() if stats is not None else None
-    check(lib.sgx_gat_aggregate_flat(dtype_code(Wh.dtype), int(bool(relu)), adj.n_rows, N, F, 1, float(alpha), adj.nnz,
-                                     _ptr(adj.rowptr), _ptr(adj.col), _ptr(adj.val), _ptr(Wh), Wh.stride(0), _ptr(att), _ptr(out),
-                                     out.stride(0), _ptr(fill_row), nn, _ptr(scratch), sbytes,
-                                     ctypes.byref(st) if st is not None else None, _stream()), "sgx_gat_aggregate_flat")
+    args = (dtype_code(Wh.dtype), int(bool(relu)), adj.n_rows, N, F, 1, float(alpha), adj.nnz, _ptr(adj.rowptr), _ptr(adj.col),
+            _ptr(adj.val), _ptr(Wh), Wh.stride(0), _ptr(att), _ptr(out), out.stride(0), _ptr(fill_row), nn, _ptr(scratch), sbytes,
+            ctypes.byref(st) if st is not None else None)
+    if out_scale is None:
+        check(lib.sgx_gat_aggregate_flat(*args, _stream()), "sgx_gat_aggregate_flat")
+    else:
+        check(lib.sgx_gat_aggregate_flat_ep(*args, float(out_scale), _stream()), "sgx_gat_aggregate_flat_ep")
     return (out, stats) if want_row_stats else out
 
 
@@ -960,7 +1013,9 @@ def xt_g(X, G):
 CSR_TRANSPOSE_DEFAULT = "device"
 
 
-def _transposed(T, return_order, order, flat=False):
+def _transposed(T, return_order, order, flat=False, flat_quant=False):
+    if flat_quant:
+        T.with_facts(flat_quant=True)
     if flat:
         # the transpose of an entry-split matrix is one: no plan for it, whatever its rows (a hub column's) are like
         T.with_facts(flat=True)
@@ -992,7 +1047,7 @@ def csr_transpose(A, return_order=False, method=None):
                                     _ptr(rowptr_t), _ptr(col_t), _ptr(val_t), _ptr(order), _ptr(ws), ws.numel(), _stream()),
               "sgx_csr_transpose")
         T = Csr(rowptr_t, col_t[:nnz], val_t[:nnz], A.n_rows)
-        return _transposed(T, return_order, order[:nnz].long() if return_order else None, A._flat)
+        return _transposed(T, return_order, order[:nnz].long() if return_order else None, A._flat, A._flat_quant)
     if method != "torch":
         raise ValueError(f"csr_transpose: method must be None, 'device' or 'torch', not {method!r}")
     row = torch.repeat_interleave(torch.arange(A.n_rows, device=A.col.device, dtype=torch.int64),
@@ -1002,7 +1057,7 @@ def csr_transpose(A, return_order=False, method=None):
     order = torch.argsort(key)
     T = Csr.from_coo(col[order].contiguous(), row[order].to(torch.int32).contiguous(), val[order].contiguous(),
                      A.n_cols, A.n_rows)
-    return _transposed(T, return_order, order, A._flat)
+    return _transposed(T, return_order, order, A._flat, A._flat_quant)
 
 
 def _backward_edge_operands(adj, G, Wh, dead):

@@ -425,18 +425,28 @@ class NeighborLoader:
     X^T . pg on its entry-split schedules at the capacities, so the one-call backward records and replays as well.
     The three refusals that exist because a plan costs a read-back then do not apply: max(fanouts) + 1 > 64, feature
     rows of over 64 entries, capacities from 2^20 entries.  Still refused: a fan-out of -1 (an unbounded row has no
-    capacity) and quant= (the quantised layer has no entry-split epilogue yet)."""
+    capacity) and quant= (the quantised layer has no entry-split epilogue yet) -- unless flat_quant=True is passed as well.
+
+    flat_quant=True (with pad=True, schedule="flat" and quant=qc; ValueError without them): the quantised layers' opt-in to
+    the entry-split schedule.  The batches come from the padded quantised sampler as under pad=True with quant= (the same
+    host checks on qc: fq(1) > 0, fq(0) == 0), and every CSR -- adj_norm, both layers' quantised adjacencies with the lean
+    backward's mask values, the feature CSR, the transposes -- arrives with_facts(flat=True, flat_quant=True), the pair of
+    facts on which ops.layer_forward(quant=) and sgrace.FPYNQ_GAT (config.accb = 0) take SGX_SCHEDULE_FLAT with
+    SGX_QUANT_FLAT.  So the default quantised model records a step at any fan-out.  config.accb = 1 with a quantiser
+    keeps the row schedule in its backward and is not a padded route here."""
 
     def __init__(self, data, num_neighbors, batch_size=1, input_nodes=None, shuffle=False, seed=0, prepare=None, fill=0,
-                 dtype=torch.float32, transposed=False, quant=None, pad=False, schedule=None):
+                 dtype=torch.float32, transposed=False, quant=None, pad=False, schedule=None, flat_quant=False):
         from . import ops
         if schedule not in (None, "flat"):
             raise ValueError(f"schedule must be None or 'flat', not {schedule!r}")
         if schedule == "flat" and not pad:
             raise ValueError("schedule='flat' needs pad=True: it is the padded batches' route past the plan refusals")
-        if schedule == "flat" and quant is not None:
+        if flat_quant and not (schedule == "flat" and quant is not None):
+            raise ValueError("flat_quant=True needs schedule='flat' and quant=: it is the quantised layers' opt-in to that schedule")
+        if schedule == "flat" and quant is not None and not flat_quant:
             raise ValueError("quant= does not go with schedule='flat': the quantised layer has no entry-split epilogue yet")
-        self.schedule = schedule
+        self.schedule, self.flat_quant = schedule, bool(flat_quant)
         flat = schedule == "flat"
         if pad and prepare != "sym_norm2":
             raise ValueError("pad=True needs prepare='sym_norm2'")
@@ -568,8 +578,14 @@ class NeighborLoader:
         A, fea, n = s.adj_norm, s.fea, s.n_id.numel()           # (n: the capacity's rows when padded)
         flat = self.schedule == "flat"
         if flat:                                                # the entry-split schedule: no plan for either, whatever their rows
-            A.with_facts(flat=True)
-            fea.with_facts(flat=True)
+            fq = self.flat_quant or None                        # ... under the quantiser too, where the loader was asked
+            A.with_facts(flat=True, flat_quant=fq)
+            fea.with_facts(flat=True, flat_quant=fq)
+            if fq:                                              # the layers look these up (Csr.quantized, sgrace._lean_mask)
+                for Q in A._quantized.values():
+                    Q.with_facts(flat=True, flat_quant=True)
+                    if getattr(Q, "_lean_values", None) is not None:
+                        Q._lean_values.with_facts(flat=True, flat_quant=True)
         ops.attach(x, ("fea_csr", self.dtype), fea)
         ops.attach(s.edge_index_agg, ("sym_norm2", n, 1, self.dtype), (s.edge_index_agg, A.val[:A.nnz], A))
         if self.transposed:
@@ -580,7 +596,7 @@ class NeighborLoader:
                 if self.dtype != torch.float32:          # (the values alone are cast: never through a dense tensor)
                     fea32 = ops.attach(x, ("fea_csr", torch.float32),
                                        ops.Csr(fea.rowptr, fea.col[:fea.nnz], fea.val[:fea.nnz].float(), fea.n_cols).with_facts(
-                                           max_row=fea._max_row, flat=fea._flat))
+                                           max_row=fea._max_row, flat=fea._flat, flat_quant=fea._flat_quant))
                 ops.attach(x, ("fea_csr_t", torch.float32), ops.csr_transpose(fea32, method="device"))
             A._transpose_pattern = ops.csr_transpose(A, return_order=True, method="device")
         fields = dict(x=x, edge_index=s.edge_index, edge_index_agg=s.edge_index_agg, adj_norm=A, n_id=s.n_id.long(),

@@ -34,7 +34,10 @@ arithmetic on the same kernels, the attention gradient gathered in row order ins
 CSR feature matrix never made dense, and grad_input left out when the input needs no gradient.  A flat-marked adjacency
 (Csr.with_facts(flat=True)) of an unquantised layer takes that call's entry-split schedules (SGX_SCHEDULE_FLAT per matrix,
 the attention gradient by stored entries): no plan, no read-back, so the step records and replays on padded batches of
-any fan-out; with a quantiser the forward runs as without the fact, and so does the backward.
+any fan-out; with a quantiser the forward runs as without the fact, and so does the backward -- unless the adjacency also
+carries flat_quant (Csr.with_facts(flat=True, flat_quant=True), as NeighborLoader(flat_quant=True) delivers it): the quantised
+forward then takes the entry-split schedule (SGX_QUANT_FLAT) under config.accb = 0, whose staged backward already follows the
+flat fact; the one-call backward of a quantised layer keeps the row schedule.
 """
 import torch
 import torch.nn.functional as F
@@ -171,8 +174,9 @@ class FPYNQ_GAT(torch.autograd.Function):
             # config.fake_quantization alone: the fp32 emulation of the grid, as the reference states it
             int8 = "auto" if (qc is not None and config.hardware_quantize) else False
             # a flat-marked adjacency runs the entry-split aggregate, which writes no E / S: the statistics route whatever
-            # config.gat_edge_outputs says (the quantised layer has no entry-split form and runs as without the fact)
-            ctx.lean = bool(ctx.gat) and (not int(config.gat_edge_outputs) or (A._flat and qc is None))
+            # config.gat_edge_outputs says.  The quantised layer takes that aggregate only for an adjacency that also carries
+            # flat_quant (Csr.with_facts; ops.layer_forward reads the same two facts) and runs as without the fact otherwise
+            ctx.lean = bool(ctx.gat) and (not int(config.gat_edge_outputs) or (A._flat and (qc is None or A._flat_quant)))
             if ctx.lean:
                 # the row softmax statistics instead of E and S (3 n + n_cols floats in place of 2 nnz); the forward is
                 # the one without side outputs
