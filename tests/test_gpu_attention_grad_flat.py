@@ -20,7 +20,7 @@ import torch
 import _attention_grad_flat_ref as R
 
 pytestmark = pytest.mark.gpu
-WIDTHS = [3, 8, 64, 100, 256]
+WIDTHS = [3, 8, 12, 20, 64, 100, 256]
 SENTINEL = -77.0
 GUARD = 64                    # sentinel floats on either side of an output and of the workspace
 
