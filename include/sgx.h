@@ -727,10 +727,19 @@ int sgx_pack_rows(int dtype, int64_t n_rows, int n_feat, const void *src, int64_
  * Capacity: sgx_sample_workspace_bytes returns the workspace size (0 for bad arguments) and the bounds the outputs are
  * sized from: per hop, edges <= frontier * k (nnz for k == -1), new nodes (the next frontier) <= those edges and <=
  * n_nodes - B; max_edges <= nnz, max_nodes <= n_nodes.  Arguments: n_nodes >= 0, 0 <= nnz < 2^31 - 1, 0 <= batch <= n_nodes, 1 <= n_hops <= 64, fanouts[h] >= -1
- * (fan-outs up to 64 keep the subset in registers; larger ones are correct and slow).  max_nodes / max_edges below the
- * bounds: SGX_ERR_SHAPE. */
+ * (fan-outs up to 64 keep the subset in registers, one element per lane; fan-outs of 65 to sgx_sample_wide_max() = 1024
+ * keep it in the wavefront's LDS, the whole wavefront at work on the row; only fan-outs over 1024 run a row on one lane
+ * in O(k^2) global loads, correct and slow: sgx_sample_form).  max_nodes / max_edges below the bounds: SGX_ERR_SHAPE. */
 size_t sgx_sample_workspace_bytes(int n_nodes, int64_t nnz, int batch, int n_hops, const int *fanouts,
                                   int64_t *max_nodes, int64_t *max_edges);
+/* Which form of the subset step a hop with this fan-out runs on the rows whose degree exceeds it (rows up to the fan-out
+ * are copied whole in every form); the sampler chooses its kernel through this function.  Added without a version bump
+ * (SGX_VERSION stays 110): two new declarations, nothing else changes; the same bits come out of every form.
+ *   0  fanout == -1: every position, nothing drawn          1  0 .. 64: the subset in registers
+ *   2  65 .. sgx_sample_wide_max(): the subset in LDS        3  above: one lane, the subset in the row's output slots
+ * fanout < -1: SGX_ERR_SHAPE.  Host queries without a launch and without a device. */
+int sgx_sample_wide_max(void);
+int sgx_sample_form(int fanout);
 int sgx_sample_neighbors(const int32_t *rowPtr, const int32_t *columnIndex, int n_nodes, int64_t nnz,
                          const int32_t *seeds, int batch, int n_hops, const int *fanouts, uint64_t seed, uint64_t step,
                          int32_t *node_map, int32_t *n_id, int32_t *out_rowPtr, int32_t *out_col, int32_t *edge_pos,

@@ -6,7 +6,8 @@
 // read back between hops; every grid is sized on the host from the bound):
 //   1-3  row counts of the frontier -> exclusive scan -> out_rowPtr of the frontier rows     (scan_*<RowCounts>)
 //   4    one wavefront per frontier row: Floyd's subset, positions in ascending order, global column ids,
-//        atomicMin of each slot's ordinal into node_map[column]                              (sample_kernel)
+//        atomicMin of each slot's ordinal into node_map[column]                              (sample_kernel; for a
+//        fan-out of 65 .. kWideMax sample_wide_kernel, the same rule with the subset in LDS: sgx_sample_form)
 //   5-7  first-appearance flags (node_map[column] == own slot) -> exclusive scan -> new local ids; the first slot of a
 //        node writes n_id and stores -(id + 1) in node_map                                   (scan_*<FirstSeen>)
 //   8    columns relabelled through node_map                                                 (relabel_kernel)
@@ -164,6 +165,119 @@ __global__ __launch_bounds__(kBlock) void sample_kernel(SampleArgs a, Counters c
     }
 }
 
+// the lanes of a wavefront hand values to one another through its own LDS slice: LDS operations of one wavefront
+// complete in order, the fences keep the compiler from moving them across
+__device__ __forceinline__ void wave_lds_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+constexpr int32_t kHitBit = (int32_t)0x80000000;
+
+// The wide form: fan-outs kFast < k <= kWideMax (sgx_sample_form 2), one wavefront per frontier row as sample_kernel,
+// element i = 64 c + lane of chunk c < C = ceil(k / 64).  Floyd's loop restated so that no element waits for the one
+// before it (tests/_sampler_wide_ref.py is the same in numpy), with base = deg - k, j_i = base + i, t_i = draw(j_i):
+//   dup_i  = t_i is among t_0 .. t_{i-1}
+//   par_i  = t_i - base where 0 <= t_i - base < i, else none   (j_par is the only j that t_i can equal)
+//   hit_i  = dup_i or hit[par_i]                               = Floyd's "t_i is in S": an earlier element is t_i either
+//                                                                as its own draw (dup) or as its j, which it took on a hit
+//   elem_i = hit_i ? j_i : t_i
+// par_i < i, so hit is the OR of dup along a chain of falling indices: ceil(log2 k) rounds of pointer jumping over the
+// word (hit << 31 | par + 1), updated in place chunk by chunk -- a word read is whole, either version of it covers
+// its chain up to the parent it names, and the covered length at least doubles per round.  Then the rank of every
+// element among all of them gives its slot.
+// LDS: two int32 [kWideMax] arrays per wavefront (the draws, later the elements; the chain words) = 8 KiB, 32 KiB static
+// per workgroup of four rows: five workgroups = 20 wavefronts per CU, 5 per SIMD.  The slices are wavefront-private and
+// ordered by wave_lds_sync alone: the kernel has no workgroup barrier, so the early returns are free.  Every trip
+// count is a function of k (and the chunk index) alone; nothing of the subset touches global memory.
+__global__ __launch_bounds__(kBlock) void sample_wide_kernel(SampleArgs a, Counters ctr)
+{
+    __shared__ __attribute__((aligned(16))) int32_t s_val[kBlock / 64][kWideMax];
+    __shared__ __attribute__((aligned(16))) int32_t s_link[kBlock / 64][kWideMax];
+    if (ctr.status()) return;
+    const int f0 = ctr.frontier_begin(a.h);
+    const int r = blockIdx.x * (kBlock / 64) + (threadIdx.x >> 6);
+    if (r >= ctr.nodes(a.h) - f0) return;                  // uniform over the wavefront
+    const int lane = threadIdx.x & 63;
+    const int v = a.n_id[f0 + r];
+    const int p0 = a.rowPtr[v], deg = a.rowPtr[v + 1] - p0;
+    const int off = a.out_rowPtr[f0 + r];
+    const int k = a.k;                                     // kFast < k <= kWideMax: sample_enqueue launches nothing else here
+    const uint64_t key = a.hop_key();
+    const bool all = deg <= k;
+    if ((int64_t)off + (all ? deg : k) > a.max_edges) {
+        if (lane == 0) atomicOr(&ctr.status(), kStatusCapacity);
+        return;
+    }
+    if (all) {
+        for (int p = lane; p < deg; p += 64) put(a, off + p, p0 + p);
+        return;
+    }
+    int32_t *val = s_val[threadIdx.x >> 6], *link = s_link[threadIdx.x >> 6];
+    const int4 *val4 = (const int4 *)val;
+    const int C = (k + 63) >> 6, base = deg - k;
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {                          // slots k .. 64 C - 1 hold -1, which no draw equals
+        const int i = c * 64 + lane;
+        val[i] = i < k ? draw(key, v, base + i) : -1;
+    }
+    wave_lds_sync();
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+        const int i = c * 64 + lane, t = val[i];
+        unsigned diff = 1;                                 // the chunks before this one, every index below i: 0 once a draw equals t
+#pragma unroll 2
+        for (int g = 0; g < c * 16; ++g) {
+            const int4 x = val4[g];
+            diff = min(min(diff, (unsigned)(x.x ^ t)), min((unsigned)(x.y ^ t), min((unsigned)(x.z ^ t), (unsigned)(x.w ^ t))));
+        }
+        int first = i;                                     // this chunk: the first index that holds t, i itself at the latest
+#pragma unroll 2
+        for (int g = c * 16; g < c * 16 + 16; ++g) {
+            const int4 x = val4[g];
+            const int l = 4 * g;
+            first = min(min(first, x.x == t ? l : i), min(x.y == t ? l + 1 : i, min(x.z == t ? l + 2 : i, x.w == t ? l + 3 : i)));
+        }
+        const bool dup = diff == 0 || first < i;
+        const int par = t - base;
+        link[i] = (dup ? kHitBit : 0) | (par >= 0 && par < i ? par + 1 : 0);
+    }
+    wave_lds_sync();
+    const int rounds = 32 - __clz(k - 1);                  // ceil(log2 k)
+#pragma unroll 1
+    for (int round = 0; round < rounds; ++round) {
+#pragma unroll 1
+        for (int c = 0; c < C; ++c) {
+            const int i = c * 64 + lane;
+            const int32_t w = link[i];
+            const int par = (w & ~kHitBit) - 1;
+            const int32_t u = par >= 0 ? link[par] : 0;    // the parent's word: its hit so far and where its chain goes on
+            link[i] = (w & kHitBit) | u;
+            wave_lds_sync();
+        }
+    }
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {                          // slots k .. 64 C - 1 hold INT_MAX, which is below no element
+        const int i = c * 64 + lane;
+        const int t = val[i];
+        val[i] = i < k ? (link[i] < 0 ? base + i : t) : 0x7fffffff;
+    }
+    wave_lds_sync();
+#pragma unroll 1
+    for (int c = 0; c < C; ++c) {
+        const int i = c * 64 + lane, e = val[i];
+        int rank = 0;                                      // ascending order: rank among the k distinct positions
+#pragma unroll 2
+        for (int g = 0; g < C * 16; ++g) {
+            const int4 x = val4[g];
+            rank += (x.x < e) + (x.y < e) + (x.z < e) + (x.w < e);
+        }
+        if (i < k) put(a, off + rank, p0 + e);
+    }
+}
+
 __global__ __launch_bounds__(kBlock) void relabel_kernel(int32_t *__restrict__ col, const int32_t *__restrict__ map,
                                                          Counters ctr, int h)
 {
@@ -218,7 +332,9 @@ int sgx_sample::sample_enqueue(const int32_t *rowPtr, const int32_t *columnIndex
         scan_launch(RowCounts{ctr, rowPtr, n_id, out_rowPtr, h, fanouts[h]}, b.front[h], bsum, s);
         const SampleArgs sa{rowPtr, columnIndex, n_id, out_rowPtr, out_col, edge_pos, node_map, max_edges, key, step_dev, mix64(seed),
                             h, fanouts[h]};
-        hipLaunchKernelGGL(sample_kernel, dim3(grid_of(b.front[h], kBlock / 64, 0)), dim3(kBlock), 0, s, sa, ctr);
+        // the fan-out is uniform over the hop: its form is chosen here, through the function that reports it
+        hipLaunchKernelGGL(sgx_sample_form(fanouts[h]) == 2 ? sample_wide_kernel : sample_kernel,
+                           dim3(grid_of(b.front[h], kBlock / 64, 0)), dim3(kBlock), 0, s, sa, ctr);
         scan_launch(FirstSeen{ctr, out_col, node_map, n_id, max_nodes, h}, b.edges[h], bsum, s);
         hipLaunchKernelGGL(relabel_kernel, dim3(grid_of(b.edges[h], kBlock, 2048)), dim3(kBlock), 0, s, out_col, node_map,
                            ctr, h);
@@ -248,6 +364,14 @@ int sgx_sample::sample_finish(const int32_t *cbuf, int n_hops, int64_t *hop_node
     if (extras)
         for (int k = 0; k < kExtras; ++k) extras[k] = host[3 + 2 * n_hops + k];
     return SGX_OK;
+}
+
+extern "C" int sgx_sample_wide_max(void) { return kWideMax; }
+
+extern "C" int sgx_sample_form(int fanout)
+{
+    if (fanout < -1) return SGX_ERR_SHAPE;
+    return fanout < 0 ? 0 : fanout <= kFast ? 1 : fanout <= kWideMax ? 2 : 3;
 }
 
 extern "C" size_t sgx_sample_workspace_bytes(int n_nodes, int64_t nnz, int batch, int n_hops, const int *fanouts,

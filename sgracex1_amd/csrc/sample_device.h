@@ -10,6 +10,9 @@ constexpr int kPer = 8;                       // items per thread of a scan work
 constexpr int kTile = kBlock * kPer;          // items per scan workgroup
 constexpr int kScanTop = 1024;                // threads of the one workgroup that scans the workgroup sums
 constexpr int kStatusSeeds = 1, kStatusCapacity = 2;
+// the largest fan-out whose subset the sampler keeps in the wavefront's LDS slice (sample_wide_kernel, sgx_sample_form
+// 2); larger ones run on one lane
+constexpr int kWideMax = 1024;
 // behind the sampler's counters: what the batch preparation reports through the same read-back
 constexpr int kExtras = 4, kNormNnz = 0, kFeaNnz = 1, kDeadRows = 2, kMaxRow = 3;
 

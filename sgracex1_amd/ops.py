@@ -1355,7 +1355,18 @@ def relu_mask_backward_(out, grad):
 
 # ---- neighbour sampling (sgx_sample_neighbors): the NeighborLoader batches of demo_sgrace.py:112-125 ----------------
 SAMPLE_SENTINEL = 0x7FFFFFFF
+SAMPLE_WIDE_MAX = lib.sgx_sample_wide_max()     # the largest fan-out whose subset a whole wavefront builds in LDS
 _node_maps = {}
+
+
+def sample_form(fanout):
+    """Which form of the subset step a hop with this fan-out runs on rows over the fan-out (sgx_sample_form): 0 = -1,
+    every position; 1 = up to 64, in registers; 2 = 65 .. SAMPLE_WIDE_MAX, in LDS; 3 = above, one lane.  The same bits
+    come out of every form.  ValueError below -1.  No device needed."""
+    form = lib.sgx_sample_form(int(fanout))
+    if form < 0:
+        raise ValueError(f"sample_form: fan-out {fanout} is below -1")
+    return form
 
 
 def _node_map(device, n_nodes):

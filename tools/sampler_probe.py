@@ -29,6 +29,14 @@ of examples/sgrace_node_classification.py (GCN and GAT).  One JSON line per meas
                                                    # "prepared_q", beside --arms), and the preparation alone of both
                                                    # (profiles/r12_node_batch_quant.jsonl; --arms prepared runs on a tree
                                                    # without quant=)
+    python tools/sampler_probe.py --wide [--label L]    # profiles/sampler_wide.jsonl: ops.sample_neighbors alone at fan-outs
+                                                   # over 64 -- [100], [256], [1024], [100, 10] -- beside the controls [10]
+                                                   # and [15, 10, 5] and the one-lane path at [1025] (batch 16), both
+                                                   # products shapes, batch 1024; then the node example's replayed step at
+                                                   # [100, 10], unquantised.  One process = one run of every leg; run two
+                                                   # checkouts alternately, three processes each, and hold a leg against
+                                                   # the other checkout's run-to-run spread
+    python tools/sampler_probe.py --wide-summary FILE   # those run lines and a summary line per leg
 """
 import argparse
 import json
@@ -377,6 +385,122 @@ def node_replay(leg, qbits=None):
                           "steps_per_window": epochs * n_steps, **extra_eval, **extra}), flush=True)
 
 
+WIDE_LEGS = (([100], 1024), ([256], 1024), ([1024], 1024), ([100, 10], 1024), ([10], 1024), ([15, 10, 5], 1024), ([1025], 16))
+
+
+def wide(label):
+    """--wide: ops.sample_neighbors alone, stream synchronised, per leg three warm-up calls and five windows (every call a
+    new step, so a new draw); the sampled edges of the last call and the share of its frontier rows whose degree exceeds
+    their hop's fan-out (the rows that run the subset step).  ops.sample_form, where the checkout has it, names the form."""
+    import statistics
+    dev = torch.device("cuda")
+    form = getattr(ops, "sample_form", None)
+    shapes = [("products shape uniform", lambda: graphs.uniform_graph(2_450_000, 122_000_000, dtype=torch.float32,
+                                                                      normalize=False)),
+              ("products shape rmat", lambda: graphs.rmat_graph_n(2_450_000, 122_000_000, dtype=torch.float32,
+                                                                  normalize=False))]
+    for name, make in shapes:
+        A = make()
+        deg = (A.rowptr[1:] - A.rowptr[:-1]).long()
+        for fanouts, batch in WIDE_LEGS:
+            seeds = torch.randperm(A.n_rows, generator=torch.Generator().manual_seed(1))[:batch].to(dev)
+            steps = iter(range(10 ** 9))
+            call = lambda: ops.sample_neighbors(A, seeds, fanouts, seed=1, step=next(steps))
+            call()                                                   # warm-up: code objects, the workspace, the map
+            torch.cuda.synchronize()
+
+            def window(reps):
+                t0 = time.perf_counter()
+                for _ in range(reps):
+                    out = call()
+                torch.cuda.synchronize()
+                return (time.perf_counter() - t0) / reps * 1e3, out
+            ms1, _ = window(1)
+            reps = max(1, min(50, int(200 / max(ms1, 1e-3))))        # windows of about 0.2 s, 50 calls at the most
+            runs = [window(reps) for _ in range(5)]
+            windows, s = sorted(r[0] for r in runs), runs[-1][1]
+            rows = over = 0
+            for h, k in enumerate(fanouts):
+                d = deg[s.n_id[(s.hop_nodes[h - 1] if h else 0):s.hop_nodes[h]].long()]
+                rows, over = rows + d.numel(), over + int((d > k).sum())
+            print(json.dumps({"label": label, "leg": "sample_neighbors", "graph": name, "batch": batch, "fanouts": fanouts,
+                              "forms": [form(k) for k in fanouts] if form else None,
+                              "ms_per_call": [round(v, 4) for v in windows], "ms_median": round(statistics.median(windows), 4),
+                              "calls_per_window": reps, "sampled_edges": s.adj.nnz, "sampled_nodes": s.n_id.numel(),
+                              "frontier_rows": rows, "share_of_rows_over_fanout": round(over / max(rows, 1), 4)}), flush=True)
+        del A, deg
+        torch.cuda.empty_cache()
+    wide_step(label)
+
+
+def wide_step(label):
+    """The node example's replayed training step at batch 128 and fan-outs [100, 10] in the configuration of
+    tools/quant_flat_probe.py's leg a, unquantised: NeighborLoader(pad=True, schedule="flat") through
+    NodeTrainer.capture_loader, ms per step of a replayed epoch of ten steps, five epochs."""
+    import numpy as np
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    from sgrace_node_classification import planted_partition
+    from sgracex1_amd import config, pyg_lite, sgrace
+    from sgracex1_amd.train import NodeTrainer
+    for attention in (0, 1):
+        config.acc, config.accb, config.float_type, config.compute_attention = 1, 0, np.float32, attention
+        config.fake_quantization = config.hardware_quantize = 0
+        config.w_qbits, config.gat_edge_outputs, config.device = 32, 0, "cuda"
+        sgrace.init_SGRACE()
+        torch.manual_seed(1)
+        n = 3000
+        x, edge_index, y = planted_partition(n, 5, 200, 0.2, 0.02, 1, torch.device("cuda"))
+        train = torch.zeros(n, dtype=torch.bool, device="cuda")
+        train[torch.randperm(n, generator=torch.Generator().manual_seed(1))[:1280].cuda()] = True      # ten full batches
+        data = pyg_lite.NodeData(x, edge_index, y, train_mask=train)
+        model = sgrace.GAT_PYNQ(x.shape[1], 16, 1, 5).cuda().train()
+        trainer = NodeTrainer(model, lr=0.01, weight_decay=5e-4, seed=1)
+        loader = pyg_lite.NeighborLoader(data, [100, 10], pad=True, schedule="flat", batch_size=128, input_nodes=train,
+                                         shuffle=True, seed=1, prepare="sym_norm2", fill=1, transposed=True)
+        epoch = trainer.capture_loader(loader)
+        epoch()
+        ms = sorted(timed(epoch, 1)[0] / len(loader) for _ in range(5))
+        loader.status()
+        print(json.dumps({"label": label, "leg": "replayed step", "route": "flat-replayed", "attention": bool(attention),
+                          "graph": "example (3 000 nodes)", "batch": 128, "fanouts": [100, 10],
+                          "ms_per_step": [round(v, 4) for v in ms], "steps_per_epoch": len(loader)}), flush=True)
+
+
+def wide_summary(path):
+    """--wide-summary FILE: the run lines of FILE (labels "parent" and "this", --wide's output of several processes) and,
+    per leg, a summary line: the run medians of both, the parent's run-to-run spread of medians, the gap from this
+    commit's worst median to the parent's best, and the verdict -- a win only where the gap exceeds that spread and every
+    window of this commit lies below every window of the parent; "inside the spread" where the medians of this commit lie
+    within the parent's range widened by its spread; "not measured" where a label has fewer than two runs."""
+    import statistics
+    runs, order = {}, []
+    for line in open(path):
+        rec = json.loads(line)
+        print(json.dumps(rec))
+        if "leg" not in rec or rec.get("label") not in ("parent", "this"):
+            continue
+        key = (rec["leg"], rec["graph"], rec.get("attention"), tuple(rec["fanouts"]), rec["batch"])
+        if key not in runs:
+            order.append(key)
+        runs.setdefault(key, {"parent": [], "this": []})[rec["label"]].append(rec.get("ms_per_call") or rec["ms_per_step"])
+    for key in order:
+        what = {"summary_of": key[0], "graph": key[1], "fanouts": list(key[3]), "batch": key[4],
+                **({} if key[2] is None else {"attention": key[2]})}
+        r = runs[key]
+        if min(len(r["parent"]), len(r["this"])) < 2:
+            print(json.dumps(dict(what, status="not measured", runs={k: len(v) for k, v in r.items()})))
+            continue
+        med = {k: [statistics.median(v) for v in r[k]] for k in r}
+        spread = max(med["parent"]) - min(med["parent"])
+        gap = min(med["parent"]) - max(med["this"])
+        below = max(max(v) for v in r["this"]) < min(min(v) for v in r["parent"])
+        inside = min(med["parent"]) - spread <= min(med["this"]) and max(med["this"]) <= max(med["parent"]) + spread
+        print(json.dumps(dict(what, unit="ms", parent_run_medians=med["parent"], this_run_medians=med["this"],
+                              parent_run_to_run_spread_of_medians=round(spread, 4),
+                              gap_parent_best_median_minus_this_worst_median=round(gap, 4),
+                              verdict="win" if gap > spread and below else "inside the spread" if inside else "no claim")))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--quick", action="store_true")
@@ -395,7 +519,15 @@ def main():
                     help="--node-batch: one leg of the replayed-step measurement (profiles/r22_node_replay.jsonl): 'replay' = "
                          "the padded loader through NodeTrainer.capture_loader, 'eager' = NodeTrainer.step on the prepared "
                          "loader (also on a checkout without padded batches); run the two alternately, a process each")
+    ap.add_argument("--wide", action="store_true", help="fan-outs over 64: one run of every leg of profiles/sampler_wide.jsonl "
+                                                        "(--label names the checkout)")
+    ap.add_argument("--wide-summary", default=None, metavar="FILE", help="the run lines of FILE followed by one summary line "
+                                                                         "per leg (needs no device)")
     a = ap.parse_args()
+    if a.wide_summary:
+        return wide_summary(a.wide_summary)
+    if a.wide:
+        return wide(a.label)
     if a.node_batch:
         if a.label:
             print(json.dumps({"label": a.label}), flush=True)
